@@ -13,7 +13,11 @@ iteration.
 One "step" = one device-resident NPG.train_from_paths (mjrl/algos/npg_cg.py:108-142) with the
 whitened batch already in HBM:  K1 surrogate+VPG -> CG(10 x [K2 FVP + vector update]) ->
 alpha from g.x (host scalar) -> theta += alpha x -> K3 surrogate+KL (host scalars) -> old := new.
-Prints ONE JSON line (rank 0) with the `roofline` and `cpu_baseline` objects.
+
+A plain run sets up, warms up, times exactly K steps once and prints ONE JSON line (rank 0): the headline figure and the
+last step's scalars.  --full adds everything else, as before: the `roofline` (HIP events inside the timed region), three
+repeats of the timed region (median), the checks against the fp64 oracle and the reference, the `secondary` measurements
+and the `cpu_baseline`.  --dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy.
 """
 import argparse
 import ctypes
@@ -762,8 +766,8 @@ def rehearsal_world8(one_rank_updates_per_s):
     import subprocess
     out = {}
     for transport in ("peer", "rccl"):
-        cmd = [sys.executable, os.path.abspath(__file__), "--rehearse-world", "8", "--rehearse-transport", transport, "--no-cpu-baseline",
-               "--no-secondary", "--steps", "40", "--warmup", "5", "--repeats", "3"]
+        cmd = [sys.executable, os.path.abspath(__file__), "--rehearse-world", "8", "--rehearse-transport", transport, "--full",
+               "--no-cpu-baseline", "--no-secondary", "--steps", "40", "--warmup", "5", "--repeats", "3"]
         env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(29533 + (os.getpid() % 400) + (1 if transport == "rccl" else 0)))
         env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
         try:
@@ -788,6 +792,18 @@ def rehearsal_world8(one_rank_updates_per_s):
     return out
 
 
+def dump_outputs(out_dir, outputs):
+    """--dump-outputs: what the last timed step computed, as a caller of NPG.train_from_paths receives it -- the new flat
+    parameter vector (float32, d entries) and the update's scalars (float64, one entry each) -- as <out_dir>/<name>.npy"""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, val in outputs.items():
+        if hasattr(val, "cpu"):
+            arr = val.cpu().numpy().astype(np.float32)
+        else:
+            arr = np.array([val], dtype=np.float64)
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+
+
 def self_launch(n):
     import socket
     import subprocess
@@ -810,15 +826,20 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline figure: the roofline, repeats of the timed region, the checks against the fp64 oracle and "
+                         "the reference, the secondary measurements and the CPU baseline (the --no-* options below trim this)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (new parameters, alpha, KL, surrogates) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--fvp-event-stride", type=int, default=11,
                     help="bracket every k-th Fisher-vector-product launch with HIP events (k coprime to the CG iteration count: every CG position is sampled equally); 0: none")
     ap.add_argument("--cpu-sample-traj", type=int, default=0,
                     help="cpu_baseline: 0 (default) = the whole 1M-timestep batch through the staged reference (oracle/_ref, ~20 s) -- "
                          "or, without it, a 200-trajectory slice through the torch port; k > 0: exactly k trajectories, scaled linearly")
-    ap.add_argument("--repeats", type=int, default=3,
+    ap.add_argument("--repeats", type=int, default=None,
                     help="the timed region (barrier + synchronize, EXACTLY --steps updates, barrier + synchronize) is run this many "
-                         "times; `value` is the median repeat, all repeats are reported")
+                         "times; `value` is the median repeat, all repeats are reported (default: 1, with --full 3)")
     ap.add_argument("--no-secondary", action="store_true",
                     help="skip the secondary measurements (TRPO line-search update = BASELINE configs[2]; layer-wise FVP at the "
                          "per-GPU shard sizes of configs[3] / [4]); they run after the primary timed region, N = 1 only")
@@ -831,6 +852,10 @@ def main():
                     help="--rehearse-world: the rank sums on a 1-rank RCCL group, or on libmjx's peer exchange in loop-back (the stores "
                          "to R buffers, counter updates, stream wait and R-slot sums of an R-rank exchange, all onto this rank's buffer)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.repeats is None:
+        args.repeats = 3 if args.full else 1
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` on its own: become the launcher -- one rank per GPU under torch.distributed.run (what the
@@ -894,15 +919,18 @@ def main():
     theta0_dev = torch.from_numpy(theta0).to(eng.device)
     last, last_vec = {}, {}
 
-    def one_update():
+    def one_update(keep=False):
         # the call sequence of NPG.train_from_paths (mjrl_amd/algos/npg_cg.py): everything is enqueued, one read-back
         # ONE call into libmjx (mjx_npg_update): K1, rank sum, CG (10 x [K2, rank sum, vector update]), step length on the
         # device, step, K3, rank sum -- then one read-back
         surr_after, kl = eng.npg_update(CG_ITERS, DAMPING, STEP, -3.0)
         late = eng.deferred()
         last.update(alpha=late["alpha"], kl=kl, surr_improvement=surr_after - late["surr_before"])
-        if "step" not in last_vec:                   # (first warm-up update only: the step every later update repeats)
+        if args.full and "step" not in last_vec:     # (first warm-up update only: the step every later update repeats)
             last_vec["step"] = eng.theta_new.cpu().numpy().astype(np.float64) - theta0
+        if keep:                                     # (--dump-outputs, last timed step: what the caller receives, before the reset)
+            last_vec["outputs"] = dict(new_params=eng.theta_new.clone(), alpha=late["alpha"], kl=kl,
+                                       surr_before=late["surr_before"], surr_after=surr_after)
         # old := new happens here in training; the bench restores theta0 so every step does identical work
         eng.theta_new.copy_(theta0_dev)
         eng.old_is_new = True
@@ -916,21 +944,24 @@ def main():
     for _ in range(args.warmup):
         one_update()
     fence()
-    check(eng.lib.mjx_profile_enable(eng.ctx, args.fvp_event_stride))
+    if args.full:
+        check(eng.lib.mjx_profile_enable(eng.ctx, args.fvp_event_stride))
     dts = []
-    for _ in range(max(1, args.repeats)):
+    repeats = max(1, args.repeats)
+    for r in range(repeats):
         fence()
         t0 = time.perf_counter()
-        for _ in range(args.steps):
-            one_update()
+        for i in range(args.steps):
+            one_update(keep=args.dump_outputs is not None and r == repeats - 1 and i == args.steps - 1)
         fence()
         dts.append(time.perf_counter() - t0)
-    prof = (ctypes.c_double * 2)()
-    check(eng.lib.mjx_profile_read(eng.ctx, prof))
-    samples_buf, samples_n = (ctypes.c_double * 4096)(), ctypes.c_int(0)
-    check(eng.lib.mjx_profile_samples(eng.ctx, samples_buf, 4096, ctypes.byref(samples_n)))
-    fvp_samples = [float(samples_buf[i]) for i in range(min(samples_n.value, 4096))]
-    check(eng.lib.mjx_profile_enable(eng.ctx, 0))
+    if args.full:
+        prof = (ctypes.c_double * 2)()
+        check(eng.lib.mjx_profile_read(eng.ctx, prof))
+        samples_buf, samples_n = (ctypes.c_double * 4096)(), ctypes.c_int(0)
+        check(eng.lib.mjx_profile_samples(eng.ctx, samples_buf, 4096, ctypes.byref(samples_n)))
+        fvp_samples = [float(samples_buf[i]) for i in range(min(samples_n.value, 4096))]
+        check(eng.lib.mjx_profile_enable(eng.ctx, 0))
     tmax = torch.tensor(dts, dtype=torch.float64, device="cuda")
     if world > 1:
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)          # per repeat: the slowest rank
@@ -938,30 +969,48 @@ def main():
     dt = dts[len(dts) // 2] if len(dts) % 2 else 0.5 * (dts[len(dts) // 2 - 1] + dts[len(dts) // 2])     # the median repeat
 
     failed = False
+    if rank == 0 and args.dump_outputs is not None:
+        dump_outputs(args.dump_outputs, last_vec["outputs"])
     if rank == 0:
-        fvp_ms = prof[0] / prof[1] if prof[1] > 0 else float("nan")      # (--fvp-event-stride 0: no roofline figures)
-        P = N_OBS * 64 + 64 * 64 + 64 * N_ACT
-        # The CG loop runs the cached-forward FVP instance: K1 stores h1 / h2 and the normalised observation image once
-        # per update (theta is fixed during CG), each product then costs the tangent + backward passes:
-        # 2(4P - 2 n h1) FLOP and 4(h1 + h2 + NP) B per sample, NP = n + 1 padded to 4 (SURVEY 8d "cached-activation
-        # variant").  The recompute instance (2(5P - 2 n h1) = 51 328 FLOP, 68 B per sample) is what mjx_fvp runs
-        # without a preceding K1.
-        flop_per_sample = 2 * (4 * P - 2 * N_OBS * 64)               # 40 192 @cfg2
-        bytes_per_sample = 4 * (64 + 64 + ((N_OBS + 1 + 3) & ~3))    # 592 @cfg2
-        flop_recompute = 2 * (5 * P - 2 * N_OBS * 64)                # 51 328 @cfg2
-        n_loc = eng.N_local
-        achieved_tf = flop_per_sample * n_loc / (fvp_ms * 1e-3) / 1e12
-        traffic, traffic_source = None, None
-        import glob
-        pmcs = sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_fvp_pmc.json")))
-        if pmcs and world == 1:
-            try:
-                traffic = json.load(open(pmcs[-1])).get("hbm_bytes_per_launch")
-                traffic_source = ("%s: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes over an EARLIER run of this command "
-                                  "(tools/profile_bench.sh); a constant read from the file, not measured by this run"
-                                  % os.path.relpath(pmcs[-1], ROOT))
-            except Exception:
-                traffic = None
+        if args.full:
+            fvp_ms = prof[0] / prof[1] if prof[1] > 0 else float("nan")      # (--fvp-event-stride 0: no roofline figures)
+            P = N_OBS * 64 + 64 * 64 + 64 * N_ACT
+            # The CG loop runs the cached-forward FVP instance: K1 stores h1 / h2 and the normalised observation image once
+            # per update (theta is fixed during CG), each product then costs the tangent + backward passes:
+            # 2(4P - 2 n h1) FLOP and 4(h1 + h2 + NP) B per sample, NP = n + 1 padded to 4 (SURVEY 8d "cached-activation
+            # variant").  The recompute instance (2(5P - 2 n h1) = 51 328 FLOP, 68 B per sample) is what mjx_fvp runs
+            # without a preceding K1.
+            flop_per_sample = 2 * (4 * P - 2 * N_OBS * 64)               # 40 192 @cfg2
+            bytes_per_sample = 4 * (64 + 64 + ((N_OBS + 1 + 3) & ~3))    # 592 @cfg2
+            flop_recompute = 2 * (5 * P - 2 * N_OBS * 64)                # 51 328 @cfg2
+            n_loc = eng.N_local
+            achieved_tf = flop_per_sample * n_loc / (fvp_ms * 1e-3) / 1e12
+            traffic, traffic_source = None, None
+            import glob
+            pmcs = sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_fvp_pmc.json")))
+            if pmcs and world == 1:
+                try:
+                    traffic = json.load(open(pmcs[-1])).get("hbm_bytes_per_launch")
+                    traffic_source = ("%s: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes over an EARLIER run of this command "
+                                      "(tools/profile_bench.sh); a constant read from the file, not measured by this run"
+                                      % os.path.relpath(pmcs[-1], ROOT))
+                except Exception:
+                    traffic = None
+            roofline = {"bound": "mfma", "kernel": "k_fused<64,64,1,8,MODE_FVP,NP=20,CACHED>",
+                        "achieved": achieved_tf, "peak": FP32_MFMA_PEAK_TF, "unit": "TFLOP/s",
+                        "frac": achieved_tf / FP32_MFMA_PEAK_TF, "traffic": traffic, "traffic_source": traffic_source,
+                        "avg_launch_ms": fvp_ms, "launches": int(prof[1]),
+                        "launch_ms_samples": {"sorted": sorted(round(x, 5) for x in fvp_samples),
+                                              "min": min(fvp_samples) if fvp_samples else None,
+                                              "median": sorted(fvp_samples)[len(fvp_samples) // 2] if fvp_samples else None,
+                                              "max": max(fvp_samples) if fvp_samples else None,
+                                              "what": "every bracketed launch's HIP-event time (mjx_profile_samples); avg_launch_ms is their mean"},
+                        "launches_timed": "every %d-th of %d (HIP events on the launch stream, inside the timed regions)" % (max(args.fvp_event_stride, 1), args.steps * CG_ITERS * len(dts)),
+                        "flop_per_launch": flop_per_sample * n_loc,
+                        "algorithmic_bytes_per_launch": bytes_per_sample * n_loc,
+                        "hbm_GBps_algorithmic": bytes_per_sample * n_loc / (fvp_ms * 1e-3) / 1e9,
+                        "hbm_frac_algorithmic": bytes_per_sample * n_loc / (fvp_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                        "fvp_equivalent_TFLOPs_if_recomputed": flop_recompute * n_loc / (fvp_ms * 1e-3) / 1e12}
         out = {
             "metric": "NPG updates/sec (1M-timestep batch, 64x64 MLP)",
             "value": args.steps / dt,
@@ -979,30 +1028,17 @@ def main():
                                       % (world, {"rccl": "RCCL all-reduce inside libmjx", "peer": "libmjx peer exchange over HIP IPC",
                                                  "hook": "transport hook", None: "none at one rank"}.get(eng.comm_kind, str(eng.comm_kind))),
                        "cg_iters": CG_ITERS, "damping": DAMPING},
-            "roofline": {"bound": "mfma", "kernel": "k_fused<64,64,1,8,MODE_FVP,NP=20,CACHED>",
-                         "achieved": achieved_tf, "peak": FP32_MFMA_PEAK_TF, "unit": "TFLOP/s",
-                         "frac": achieved_tf / FP32_MFMA_PEAK_TF, "traffic": traffic, "traffic_source": traffic_source,
-                         "avg_launch_ms": fvp_ms, "launches": int(prof[1]),
-                         "launch_ms_samples": {"sorted": sorted(round(x, 5) for x in fvp_samples),
-                                               "min": min(fvp_samples) if fvp_samples else None,
-                                               "median": sorted(fvp_samples)[len(fvp_samples) // 2] if fvp_samples else None,
-                                               "max": max(fvp_samples) if fvp_samples else None,
-                                               "what": "every bracketed launch's HIP-event time (mjx_profile_samples); avg_launch_ms is their mean"},
-                         "launches_timed": "every %d-th of %d (HIP events on the launch stream, inside the timed regions)" % (max(args.fvp_event_stride, 1), args.steps * CG_ITERS * len(dts)),
-                         "flop_per_launch": flop_per_sample * n_loc,
-                         "algorithmic_bytes_per_launch": bytes_per_sample * n_loc,
-                         "hbm_GBps_algorithmic": bytes_per_sample * n_loc / (fvp_ms * 1e-3) / 1e9,
-                         "hbm_frac_algorithmic": bytes_per_sample * n_loc / (fvp_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                         "fvp_equivalent_TFLOPs_if_recomputed": flop_recompute * n_loc / (fvp_ms * 1e-3) / 1e12},
             "timing": {"repeats": len(dts), "ms_per_step_each_repeat_sorted": [1e3 * x / args.steps for x in dts],
                        "ms_per_step_min": 1e3 * dts[0] / args.steps, "ms_per_step_median": 1e3 * dt / args.steps,
                        "value_is": "steps / median repeat (each repeat: barrier + synchronize, exactly `steps` updates, barrier + synchronize; max over ranks)"},
             "check": last,
         }
+        if args.full:
+            out["roofline"] = roofline
         # the update's scalars against the fp64 oracle on this very batch (tests/golden/bench_cfg2_1m.npz, 125 s of CPU to
         # regenerate: tests/golden/make_golden_big.py): a drift beyond the 1e-5 parity bar fails the run loudly
         fx = os.path.join(ROOT, "tests", "golden", "bench_cfg2_1m.npz")
-        if os.path.exists(fx) and args.rehearse_world <= 1:
+        if args.full and os.path.exists(fx) and args.rehearse_world <= 1:
             g = np.load(fx)
             drift = {k: abs(last[k] - float(g[k])) / abs(float(g[k])) for k in ("alpha", "kl", "surr_improvement")}
             out["check_vs_fp64_oracle"] = {"rel_error": drift, "bars": {k: 1e-5 for k in drift}, "fixture": "tests/golden/bench_cfg2_1m.npz"}
@@ -1013,7 +1049,7 @@ def main():
         # tests/golden/make_golden_big.py bench_ref_1m: 25 s + 45 s of CPU for configs[1] / configs[2]): scalars and the step
         # direction at the north-star's 1e-5
         fr = os.path.join(ROOT, "tests", "golden", "bench_ref_1m.npz")
-        ref = np.load(fr) if os.path.exists(fr) else None
+        ref = np.load(fr) if args.full and os.path.exists(fr) else None
         if ref is not None and args.rehearse_world <= 1 and "step" in last_vec:
             rs = ref["npg_new_params"].astype(np.float64) - theta0
             drift = {"alpha": abs(last["alpha"] - float(ref["npg_alpha"])) / float(ref["npg_alpha"]),
@@ -1028,6 +1064,7 @@ def main():
         if args.rehearse_world > 1:
             out["rehearsal"] = "rank 0 of %d on one GPU, %s: NOT the metric" % (
                 args.rehearse_world, "1-rank RCCL group" if eng.comm_kind == "rccl" else "peer exchange in loop-back" if eng.comm_kind == "peer" else eng.comm_kind)
+        if args.rehearse_world > 1 and args.full:
             out["roofline"]["traffic"] = None
             # one more short pass with whole CG ITERATIONS between the events (mjx_profile_enable(ctx, -k)): product + reduction /
             # exchange + vector update; what is left of an update after 10 of those is K1, K3, their sums and the read-back
@@ -1047,7 +1084,7 @@ def main():
                 "what": "HIP events on the launch stream: fvp_us around the product kernel alone (every %d-th launch, in the timed region), "
                         "cg_iteration_us around a whole iteration (every 7-th, in 8 extra updates); outside = ms_per_update - %d x iteration "
                         "(K1, K3, their reductions and rank sums, the read-back, the host's turn-around)" % (max(args.fvp_event_stride, 1), CG_ITERS)}
-        if world == 1 and not args.no_secondary and args.rehearse_world <= 1:
+        if args.full and world == 1 and not args.no_secondary and args.rehearse_world <= 1:
             out["secondary"] = secondary_measurements(eng, theta0, theta0_dev, ref, full_size=not args.no_full_size)
             if not args.no_rehearsal:
                 eng.close()                                       # (the rehearsals run in processes of their own, on the same GPU)
@@ -1066,7 +1103,7 @@ def main():
                     print(json.dumps({"error": "%s: the shard's update differs from the reference beyond its bars" % lw_name,
                                       "check": lw_res["check_vs_reference"]}), file=sys.stderr, flush=True)
                     failed = True
-        if world == 1 and not args.no_cpu_baseline and args.rehearse_world <= 1:
+        if args.full and world == 1 and not args.no_cpu_baseline and args.rehearse_world <= 1:
             out["cpu_baseline"] = cpu_baseline(theta0, args.cpu_sample_traj)
             out["speedup_vs_cpu_baseline"] = out["value"] / out["cpu_baseline"]["value"]
         if not failed:
