@@ -1,0 +1,326 @@
+"""Every instantiation the layer-wise output-layer dispatcher and the CG vector-update dispatcher can pick, against the fp64
+oracle (oracle/npg_oracle.py, pinned to the reference by tests/test_oracle_golden.py).
+
+The device runs go through tests/_dispatch_matrix_worker.py in child processes, one per arm, with MJX_FORCE_LAYERWISE=1 and
+the arm's switches set in the child's environment (MJX_CG_MULTI is read once per process; the others per call, but no
+setenv races the library's threads this way).  Each worker asserts that the layer-wise path ran.
+
+Output-layer pass, LayerwiseWS::fvp_head (csrc/layerwise.h; kernels in csrc/lw_head.h).  KS = k-steps of two actions each
+in the delta product: 9 for m <= 18, 12 for m <= 24, 16 otherwise; MJX_LW_HEAD_KTRIM=0 forces 16.
+
+    last hidden layer, switches        kernel               cases (test_head_vs_oracle unless noted)
+    256, default, m <= 18              k_lw_head8<1, 9>     ant_256 (8 actions), m1_256, m2_256, m18_256 (step 8 exactly full)
+    256, default, 19 <= m <= 24        k_lw_head8<1, 12>    pen_256 (24), m19_256, m24_256; row edges m19_256_N*
+    256, default, m >= 25              k_lw_head8<1, 16>    hammer_256 (26), relocate_256 (30), door_256 (28), m25_256, m32_256
+    512, default, m <= 18              k_lw_head8<2, 9>     ant_512, humanoid_512 (376 obs, 17), m1_512, m2_512, m18_512
+    512, default, 19 <= m <= 24        k_lw_head8<2, 12>    pen_512, m19_512, m24_512
+    512, default, m >= 25              k_lw_head8<2, 16>    hammer_512, relocate_512, m25_512, m32_512; row edges m32_512_N*
+    256 / 512, MJX_LW_HEAD_KTRIM=0     k_lw_head8<CH, 16>   test_head_trim_is_bit_identical: every case above, row edges included
+    256, MJX_LW_HEAD8=0                k_lw_head<2>         test_head_four_wave_vs_oracle: every 256 case
+    512, MJX_LW_HEAD8=0                k_lw_head<4>         test_head_four_wave_vs_oracle: every 512 case
+
+Row edges (test_head_row_edges_vs_oracle): N in {1, 63, 64, 65, 256 x 64 + 65, 3 x 256 x 64 + 65}.  The grid is
+min(64-row tiles, CUs): on the MI355X's 256 CUs, 256 x 64 + 65 rows make 257 tiles (one workgroup walks a second tile) and
+3 x 256 x 64 + 65 make 769 (every workgroup walks three, one walks four).
+
+CG vector update, mjx_cg_step / cg_solve_impl (csrc/mjx.hip; kernels in csrc/vecops.h).  Hidden (64, 64): d = 64 n + 66 m + 4224.
+
+    d, switches                        update               finish                                  cases (test_cg_vs_oracle)
+    <= 8192, iters >= 1                k_cg_step_reg<8>     folded into the last update (CgFin)     d8192 (29, 32), d8190 (30, 31)
+    <= 8192, iters = 0                 --                   k_cg_finish, k_apply_npg_step           d8192, d8190 (iters = 0)
+    > 8192, default                    k_cgm_pz / xr / p    k_cg_finish, k_apply_npg_step           d8194 (28, 33: d % 4 = 2), large
+                                                                                                    (23, 5, (128, 128)): d = 20234
+    > 8192, MJX_CG_MULTI=0             k_cg_step            k_cg_finish, k_apply_npg_step           d8194-multi0, large-multi0
+
+Each CG case runs the standalone solve at iters 0, 1, 10, an early break decided on the device at a tolerance the k-th
+iteration is the first to reach, and the one-call NPG update at iters 10 (the oracle's step clamps the first and the last
+log_std entry) and 0.
+"""
+import functools
+import json
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+from oracle import npg_oracle as O
+from tests._dispatch_matrix_worker import cg_inputs, head_inputs, out_layer_offsets, probe_actions, probe_direction
+
+pytestmark = pytest.mark.gpu
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+
+TOL_VPG = 3e-6
+TOL_FVP = 3e-6
+TOL_STEP = 1e-5          # the north-star bar
+
+# Per-block bars (relative L2 of one block).  A whole-vector norm can absorb one wrong action row at m = 32, so every output
+# row W3[a, :] with its bias b3[a] is compared on its own, and so are each hidden layer's W and b and log_std.  Set at 3x the
+# largest error the two instantiations the suite tested before (k_lw_head8<1, 9>, k_lw_head8<2, 16>) show on these inputs,
+# measured on MI355X over the cases above (the other four instantiations and the four-wave kernels in brackets):
+#   K1 gradient, output rows:   1.20e-6 / 2.29e-6   (<= 3.46e-6)          other blocks: 4.12e-6 / 2.29e-6   (<= 6.39e-6)
+#   Fisher-vector product, rows: 1.82e-7 / 1.84e-7  (<= 2.98e-7)          other blocks: 3.18e-7 / 3.03e-7   (<= 5.12e-7)
+BAR_ROW_VPG, BAR_BLOCK_VPG = 6.9e-6, 1.24e-5
+BAR_ROW_FVP, BAR_BLOCK_FVP = 5.5e-7, 9.5e-7
+# A product over ONE row sums no rounding errors away.  Measured on MI355X at N = 1, on the three probe directions (0, m - 2,
+# m - 1), relative to fp64:
+#   k_lw_head8 (the kernels this bar gates):   m19_256 1.0e-6 / 3.0e-6 / 8.3e-7     m32_512 3.4e-7 / 4.6e-6 / 3.2e-7
+#   generic output-layer chain (MJX_LW_HEAD=0): m19_256 1.0e-6 / 3.5e-6 / 7.3e-7     m32_512 4.9e-6 / 5.3e-6 / 6.1e-7
+# -- fp32 rounding of one row, not the one-pass kernel (at N >= 63 every probe is <= 4.5e-7).  The N = 1 probes get 3x the
+# largest k_lw_head8 value.
+BAR_PROBE_N1 = 1.37e-5
+
+HEAD_SHAPES = [
+    # mjrl's own shapes
+    ("ant_256", 111, 8, 256), ("ant_512", 111, 8, 512),
+    ("pen_256", 45, 24, 256), ("pen_512", 45, 24, 512),
+    ("hammer_256", 46, 26, 256), ("hammer_512", 46, 26, 512),
+    ("relocate_256", 39, 30, 256), ("relocate_512", 39, 30, 512),
+    ("humanoid_512", 376, 17, 512), ("door_256", 39, 28, 256),
+] + [("m%d_%d" % (m, h), 13, m, h) for h in (256, 512) for m in (1, 2, 18, 19, 24, 25, 32)]
+ROW_EDGE_SHAPES = [("m%d_%d_N%d" % (m, h, N), 13, m, h, N) for (m, h) in ((19, 256), (32, 512))
+                   for N in (1, 63, 64, 65, 256 * 64 + 65, 3 * 256 * 64 + 65)]
+
+
+def _head_spec(name):
+    for nm, n, m, h in HEAD_SHAPES:
+        if nm == name:
+            return dict(name=nm, n=n, m=m, hid=[h, h], N=3000 + n, seed=n * 100 + m)
+    for nm, n, m, h, N in ROW_EDGE_SHAPES:
+        if nm == name:
+            return dict(name=nm, n=n, m=m, hid=[h, h], N=N, seed=n * 100 + m + N)
+    raise KeyError(name)
+
+
+HEAD_NAMES = [s[0] for s in HEAD_SHAPES]
+EDGE_NAMES = [s[0] for s in ROW_EDGE_SHAPES]
+
+# CG shapes.  Seeds picked so that the oracle's NPG step clamps the first and the last log_std entry (asserted below).
+CG_SHAPES = {"d8192": (29, 32, (64, 64), 12), "d8190": (30, 31, (64, 64), 1), "d8194": (28, 33, (64, 64), 4),
+             "large": (23, 5, (128, 128), 8)}
+# (the early-break solves run at damping 30, where the residual falls fast enough in 12 iterations for the pick in cg_break)
+CG_DAMPING, BRK_DAMPING, STEP_SIZE, MIN_LOG_STD = 1e-4, 30.0, 0.05, -0.5
+CG_CASES = [("d8192", "default"), ("d8190", "default"), ("d8194", "default"), ("large", "default"),
+            ("d8194", "multi0"), ("large", "multi0")]
+
+ARM_ENV = {"head": {}, "head_ktrim0": {"MJX_LW_HEAD_KTRIM": "0"}, "head_four": {"MJX_LW_HEAD8": "0"},
+           "cg_default": {}, "cg_multi0": {"MJX_CG_MULTI": "0"}}
+
+
+def rel(a, b):
+    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
+    return float(np.linalg.norm(a - b) / np.linalg.norm(b))
+
+
+def blocks(n, m, hid):
+    """(label, index) of every block of the flat vector: W / b of each hidden layer, each output row with its bias, log_std"""
+    ls = O.layer_sizes(n, m, hid)
+    out, k = [], 0
+    for i in range(len(ls) - 2):
+        out.append(("W%d" % (i + 1), np.arange(k, k + ls[i] * ls[i + 1]))); k += ls[i] * ls[i + 1]
+        out.append(("b%d" % (i + 1), np.arange(k, k + ls[i + 1]))); k += ls[i + 1]
+    oW, ob = out_layer_offsets(n, m, hid)
+    h = ls[-2]
+    for a in range(m):
+        out.append(("row%d" % a, np.r_[oW + a * h:oW + (a + 1) * h, ob + a]))
+    out.append(("log_std", np.arange(ob + m, ob + 2 * m)))
+    return out
+
+
+def block_errors(dev, ref, n, m, hid):
+    return {lab: rel(dev[ix], ref[ix]) for lab, ix in blocks(n, m, hid)}
+
+
+# ---------------------------------------------------------------------------------------------------------------- runs
+@functools.lru_cache(maxsize=None)
+def head_oracle(name):
+    c = _head_spec(name)
+    n, m, hid = c["n"], c["m"], tuple(c["hid"])
+    inp = head_inputs(n, m, hid, c["N"], c["seed"])
+    th, t2, tr = inp["th"].astype(np.float64), inp["th2"].astype(np.float64), inp["tr"]
+    obs, act, adv, v = (inp[k].astype(np.float64) for k in ("obs", "act", "adv", "v"))
+    r = dict(g=O.vpg(th, th, obs, act, adv, n, m, hid, tr, tr), hv=O.fvp(th, obs, v, n, m, hid, tr),
+             s=O.surrogate(t2, th, obs, act, adv, n, m, hid, tr, tr), kl=O.mean_kl(t2, th, obs, n, m, hid, tr, tr),
+             g2=O.vpg(t2, th, obs, act, adv, n, m, hid, tr, tr))
+    for a in probe_actions(m):
+        r["hv_a%d" % a] = O.fvp(th, obs, probe_direction(v, n, m, hid, a).astype(np.float64), n, m, hid, tr)
+    return r
+
+
+def _run_worker(kind, arm, names, spec_of, out_dir):
+    os.makedirs(out_dir, exist_ok=True)
+    spec = os.path.join(out_dir, "spec.json")
+    with open(spec, "w") as f:
+        json.dump({"kind": kind, "cases": [spec_of(nm) for nm in names]}, f)
+    env = dict(os.environ, MJX_FORCE_LAYERWISE="1", **ARM_ENV[arm])
+    subprocess.run([sys.executable, os.path.join(HERE, "_dispatch_matrix_worker.py"), spec, out_dir], check=True, env=env,
+                   timeout=900)
+    return {nm: dict(np.load(os.path.join(out_dir, nm + ".npz"))) for nm in names}
+
+
+@pytest.fixture(scope="module")
+def runs(tmp_path_factory):
+    """arm -> {case name: device results}; each arm's worker runs once, on first use.  A worker that fails (an error, a fault,
+    a timeout) is never started again: the failure is kept, and every later request -- for that arm or any other, since the
+    GPU may be left in a bad state -- fails at once without starting a process."""
+    cache, failed = {}, []
+
+    def get(arm):
+        if failed:
+            pytest.fail("not started: the %s worker failed earlier in this module (%s)" % failed[0])
+        if arm not in cache:
+            d = str(tmp_path_factory.mktemp(arm))
+            try:
+                if arm.startswith("head"):
+                    names = HEAD_NAMES if arm == "head_four" else HEAD_NAMES + EDGE_NAMES
+                    cache[arm] = _run_worker("head", arm, names, _head_spec, d)
+                else:
+                    names = [nm for nm, a in CG_CASES if "cg_" + a == arm]
+                    cache[arm] = _run_worker("cg", arm, names, cg_spec, d)
+            except (subprocess.SubprocessError, OSError) as e:
+                failed.append((arm, e))
+                raise
+        return cache[arm]
+    return get
+
+
+# ---------------------------------------------------------------------------------------------------------------- head
+def check_head(name, r, per_block=True, k3=True):
+    c = _head_spec(name)
+    n, m, hid = c["n"], c["m"], tuple(c["hid"])
+    ref = head_oracle(name)
+    assert rel(r["g"], ref["g"]) < TOL_VPG, "K1"
+    assert rel(r["hv"], ref["hv"]) < TOL_FVP, "FVP"
+    if per_block:
+        for key, row_bar, block_bar in (("g", BAR_ROW_VPG, BAR_BLOCK_VPG), ("hv", BAR_ROW_FVP, BAR_BLOCK_FVP)):
+            for lab, e in block_errors(r[key], ref[key], n, m, hid).items():
+                assert e < (row_bar if lab.startswith("row") else block_bar), (key, lab, e)
+    for a in probe_actions(m):                 # only output row a of the direction is non-zero: a dropped or misplaced action is O(1)
+        assert rel(r["hv_a%d" % a], ref["hv_a%d" % a]) < (BAR_PROBE_N1 if c["N"] == 1 else TOL_FVP), ("probe", a)
+    if k3:
+        assert abs(float(r["s"]) - ref["s"]) < 5e-6
+        assert abs(float(r["kl"]) - ref["kl"]) < 2e-5 * ref["kl"] + 1e-7
+        # (old != new: the m- and width-dependent bars of test_other_shapes_vs_oracle)
+        assert rel(r["g2"], ref["g2"]) < (5e-6 if m <= 16 else TOL_STEP if max(hid) <= 256 else 2e-5), "K1 old != new"
+
+
+@pytest.mark.parametrize("name", HEAD_NAMES)
+def test_head_vs_oracle(runs, name):
+    check_head(name, runs("head")[name])
+
+
+@pytest.mark.parametrize("name", EDGE_NAMES)
+def test_head_row_edges_vs_oracle(runs, name):
+    check_head(name, runs("head")[name], per_block=False)
+
+
+@pytest.mark.parametrize("name", HEAD_NAMES + EDGE_NAMES)
+def test_head_trim_is_bit_identical(runs, name):
+    """KS = 16 against the trimmed KS: the extra k-steps multiply exact zeros (the fragments of actions >= m)"""
+    a, b = runs("head")[name], runs("head_ktrim0")[name]
+    for k in ["g", "hv"] + ["hv_a%d" % x for x in probe_actions(_head_spec(name)["m"])]:
+        assert np.array_equal(a[k], b[k]), k
+
+
+@pytest.mark.parametrize("name", HEAD_NAMES)
+def test_head_four_wave_vs_oracle(runs, name):
+    check_head(name, runs("head_four")[name])
+
+
+# ---------------------------------------------------------------------------------------------------------------- CG
+def cg_spec(name):
+    n, m, hid, seed = CG_SHAPES[name]
+    return dict(name=name, n=n, m=m, hid=list(hid), N=4000 + 7, seed=seed, damping=CG_DAMPING, brk_damping=BRK_DAMPING,
+                brk_tol=cg_break(name)[0], step_size=STEP_SIZE, min_log_std=MIN_LOG_STD)
+
+
+def _residuals(hv, b, iters):
+    res, x, r = [], np.zeros_like(b), b.copy()
+    p_, rr = r.copy(), r.dot(r)
+    for _ in range(iters):
+        z = hv(p_); a = rr / p_.dot(z); x += a * p_; r -= a * z
+        new = r.dot(r); p_ = r + (new / rr) * p_; rr = new; res.append(rr)
+    return res
+
+
+@functools.lru_cache(maxsize=None)
+def cg_inputs64(name):
+    n, m, hid, seed = CG_SHAPES[name]
+    inp = cg_inputs(n, m, hid, 4000 + 7, seed)
+    return inp, {k: inp[k].astype(np.float64) for k in ("th", "th0", "obs", "act", "adv")}
+
+
+@functools.lru_cache(maxsize=None)
+def cg_break(name):
+    """-> (tol, k): a residual tolerance the k-th iteration (0-based) is the first to reach, with a factor >= 1.29 on both
+    sides (the logic of test_large_d_cg_update_on_many_workgroups_breaks_like_the_reference), on the oracle's gradient"""
+    n, m, hid, _ = CG_SHAPES[name]
+    inp, f = cg_inputs64(name)
+    g = O.vpg(f["th"], f["th"], f["obs"], f["act"], f["adv"], n, m, hid, inp["tr"], inp["tr"])
+    res = _residuals(lambda p: O.fvp(f["th"], f["obs"], p, n, m, hid, inp["tr"], damping=BRK_DAMPING), g, 12)
+    k = next(i for i in range(2, 10) if res[i] < 0.6 * min(res[:i]))    # (the residual is not monotone)
+    return float(np.sqrt(res[k] * min(res[:k]))), k
+
+
+@pytest.mark.parametrize("name,arm", CG_CASES)
+def test_cg_vs_oracle(runs, name, arm):
+    n, m, hid, _ = CG_SHAPES[name]
+    inp, f = cg_inputs64(name)
+    tr = inp["tr"]
+    r = runs("cg_" + arm)[name]
+    d = int(r["d"])
+    assert d == f["th"].size and (hid != (64, 64) or d == 64 * n + 66 * m + 4224)
+    if arm == "multi0":
+        assert d > 8192
+    oS = d - m
+    g = r["g"].astype(np.float64)
+    hv = lambda damping: (lambda p: O.fvp(f["th"], f["obs"], p, n, m, hid, tr, damping=damping))
+
+    # standalone solve on the device's gradient
+    assert not r["x0"].any() and float(r["bx0"]) == 0.0
+    for it in (1, 10):
+        x, xr = r["x%d" % it], O.cg_solve(hv(CG_DAMPING), g, it)
+        assert rel(x, xr) < TOL_STEP, it
+        assert rel(x[oS:], xr[oS:]) < TOL_STEP, ("log_std", it)      # (a lost tail element: below 1e-5 of the whole norm)
+        assert rel(x[-64:], xr[-64:]) < TOL_STEP, ("tail", it)
+        bxr = float(g.dot(xr))
+        assert abs(float(r["bx%d" % it]) - bxr) < TOL_STEP * abs(bxr), it
+
+    # early break at the residual tolerance, decided on the device
+    tol, k = cg_break(name)
+    res = _residuals(hv(BRK_DAMPING), g, 12)                             # (the same first iteration on the device's gradient)
+    assert res[k] < tol < min(res[:k])
+    xb = O.cg_solve(hv(BRK_DAMPING), g, 12, residual_tol=tol)
+    assert rel(r["xbrk"], xb) < TOL_STEP
+    assert rel(r["xbrk"][oS:], xb[oS:]) < TOL_STEP and rel(r["xbrk"][-64:], xb[-64:]) < TOL_STEP
+    assert rel(O.cg_solve(hv(BRK_DAMPING), g, 12), xb) > 10 * TOL_STEP   # (the unbroken solve really differs)
+
+    # one-call NPG update: x, alpha, theta_out, log_std clamp
+    ref = O.npg_update(f["th"], f["obs"], f["act"], f["adv"], n, m, hid, tr, cg_iters=10, damping=CG_DAMPING, delta=STEP_SIZE,
+                       min_log_std=MIN_LOG_STD)
+    unclamped = f["th"] + ref["alpha"] * ref["npg"]
+    assert unclamped[oS] < MIN_LOG_STD and unclamped[-1] < MIN_LOG_STD      # the case checks the clamp of both end entries
+    assert rel(r["upd_x"], ref["npg"]) < TOL_STEP
+    assert rel(r["upd_x"][oS:], ref["npg"][oS:]) < TOL_STEP
+    alpha = float(r["upd_alpha"])
+    assert abs(alpha - ref["alpha"]) < 1e-4 * ref["alpha"]
+    assert abs(float(r["upd_kl"]) - ref["kl"]) < 1e-4 * ref["kl"] + 1e-7
+    assert abs(float(r["upd_surr_after"]) - ref["surr_after"]) < 2e-5 and abs(float(r["upd_surr_before"]) - ref["surr_before"]) < 2e-5
+    # theta_out is fl(theta + fl(alpha x)) of the device's own x and alpha, clamped from oS on: bit for bit
+    want = inp["th"] + np.float32(alpha) * r["upd_x"]
+    want[oS:] = np.maximum(want[oS:], np.float32(MIN_LOG_STD))
+    assert np.array_equal(r["upd_theta"], want)
+    assert r["upd_theta"][oS] == np.float32(MIN_LOG_STD) and r["upd_theta"][-1] == np.float32(MIN_LOG_STD)
+    assert np.array_equal(r["upd_theta"][oS:] == np.float32(MIN_LOG_STD), ref["new_params"][oS:] == MIN_LOG_STD)
+
+    # iters = 0 (cg_solve.py: no iteration): x = 0, b.x = 0, alpha = sqrt(|step_size / 1e-20|), theta_out = theta but the clamp
+    assert not r["upd0_x"].any() and float(r["upd0_gdotx"]) == 0.0
+    assert float(r["upd0_alpha"]) == float(np.sqrt(np.abs(STEP_SIZE / (0.0 + 1e-20))))
+    want0 = inp["th0"].copy()
+    want0[oS] = np.float32(MIN_LOG_STD)                                  # (th0[oS] = -0.75: the one entry the clamp moves)
+    assert np.array_equal(r["upd0_theta"], want0)
+    ref0 = O.npg_update(f["th0"], f["obs"], f["act"], f["adv"], n, m, hid, tr, cg_iters=0, damping=CG_DAMPING, delta=STEP_SIZE,
+                        min_log_std=MIN_LOG_STD)
+    assert ref0["alpha"] == float(r["upd0_alpha"]) and np.array_equal(ref0["new_params"].astype(np.float32), want0)
