@@ -17,13 +17,7 @@ if ROOT not in sys.path:
 
 from oracle import npg_oracle as O  # noqa: E402
 from oracle import synth  # noqa: E402
-
-
-def out_layer_offsets(n, m, hid):
-    """-> (offset of the output layer's weights, offset of its bias) in the flat parameter vector"""
-    ls = O.layer_sizes(n, m, hid)
-    k = sum(ls[i] * ls[i + 1] + ls[i + 1] for i in range(len(ls) - 2))
-    return k, k + ls[-2] * m
+from tests._lw_check import out_layer_offsets  # noqa: E402
 
 
 def probe_actions(m):

@@ -18,8 +18,13 @@ in the delta product: 9 for m <= 18, 12 for m <= 24, 16 otherwise; MJX_LW_HEAD_K
     256 / 512, MJX_LW_HEAD_KTRIM=0     k_lw_head8<CH, 16>   test_head_trim_is_bit_identical: every case above, row edges included
     256, MJX_LW_HEAD8=0                k_lw_head<2>         test_head_four_wave_vs_oracle: every 256 case
     512, MJX_LW_HEAD8=0                k_lw_head<4>         test_head_four_wave_vs_oracle: every 512 case
+    128, any                           k_lw_head<1>         ant_128, m1_128, m2_128, m19_128, m32_128; row edges m32_128_N*
+    384, any                           k_lw_head<3>         humanoid_384, pen_384, m1_384, m2_384, m19_384, m32_384; row edges
+                                                            m19_384_N*
 
-Row edges (test_head_row_edges_vs_oracle): N in {1, 63, 64, 65, 256 x 64 + 65, 3 x 256 x 64 + 65}.  The grid is
+(The 128 / 384 cases run the same kernel in every arm: the bit-identity test and the four-wave arm repeat them unchanged.)
+
+Row edges (test_head_row_edges_vs_oracle): N in {1, 63, 64, 65, 256 x 64 + 65, 3 x 256 x 64 + 65}, 64-row tiles in both kernels.  The grid is
 min(64-row tiles, CUs): on the MI355X's 256 CUs, 256 x 64 + 65 rows make 257 tiles (one workgroup walks a second tile) and
 3 x 256 x 64 + 65 make 769 (every workgroup walks three, one walks four).
 
@@ -46,7 +51,8 @@ import numpy as np
 import pytest
 
 from oracle import npg_oracle as O
-from tests._dispatch_matrix_worker import cg_inputs, head_inputs, out_layer_offsets, probe_actions, probe_direction
+from tests._dispatch_matrix_worker import cg_inputs, head_inputs, probe_actions, probe_direction
+from tests._lw_check import block_errors, rel
 
 pytestmark = pytest.mark.gpu
 
@@ -71,6 +77,11 @@ BAR_ROW_FVP, BAR_BLOCK_FVP = 5.5e-7, 9.5e-7
 # -- fp32 rounding of one row, not the one-pass kernel (at N >= 63 every probe is <= 4.5e-7).  The N = 1 probes get 3x the
 # largest k_lw_head8 value.
 BAR_PROBE_N1 = 1.37e-5
+# At N = 1 every block of a probe's product scales with the one tangent mudot[a] = H . V3[a, :] + c3[a], so its rounding is that
+# sum's, which grows with the sum's condition number sum |terms| / |sum|.  That is <= 133 for the probes above (m32_512 action
+# 30); m19_384_N1 action 17 sums to 1 / 1713 of its terms (3.6e-5 measured on MI355X, where a plain fp32 loop over the same
+# terms is 3.1e-5 off).  A probe conditioned worse than 133 gets the bar scaled by the ratio.
+PROBE_COND_N1 = 133.0
 
 HEAD_SHAPES = [
     # mjrl's own shapes
@@ -79,8 +90,11 @@ HEAD_SHAPES = [
     ("hammer_256", 46, 26, 256), ("hammer_512", 46, 26, 512),
     ("relocate_256", 39, 30, 256), ("relocate_512", 39, 30, 512),
     ("humanoid_512", 376, 17, 512), ("door_256", 39, 28, 256),
-] + [("m%d_%d" % (m, h), 13, m, h) for h in (256, 512) for m in (1, 2, 18, 19, 24, 25, 32)]
-ROW_EDGE_SHAPES = [("m%d_%d_N%d" % (m, h, N), 13, m, h, N) for (m, h) in ((19, 256), (32, 512))
+] + [("m%d_%d" % (m, h), 13, m, h) for h in (256, 512) for m in (1, 2, 18, 19, 24, 25, 32)] + [
+    # the four-wave kernel, the default for a last hidden layer of 128 / 384 units
+    ("ant_128", 111, 8, 128), ("humanoid_384", 376, 17, 384), ("pen_384", 45, 24, 384),
+] + [("m%d_%d" % (m, h), 13, m, h) for h in (128, 384) for m in (1, 2, 19, 32)]
+ROW_EDGE_SHAPES = [("m%d_%d_N%d" % (m, h, N), 13, m, h, N) for (m, h) in ((19, 256), (32, 512), (32, 128), (19, 384))
                    for N in (1, 63, 64, 65, 256 * 64 + 65, 3 * 256 * 64 + 65)]
 
 
@@ -109,30 +123,6 @@ ARM_ENV = {"head": {}, "head_ktrim0": {"MJX_LW_HEAD_KTRIM": "0"}, "head_four": {
            "cg_default": {}, "cg_multi0": {"MJX_CG_MULTI": "0"}}
 
 
-def rel(a, b):
-    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
-    return float(np.linalg.norm(a - b) / np.linalg.norm(b))
-
-
-def blocks(n, m, hid):
-    """(label, index) of every block of the flat vector: W / b of each hidden layer, each output row with its bias, log_std"""
-    ls = O.layer_sizes(n, m, hid)
-    out, k = [], 0
-    for i in range(len(ls) - 2):
-        out.append(("W%d" % (i + 1), np.arange(k, k + ls[i] * ls[i + 1]))); k += ls[i] * ls[i + 1]
-        out.append(("b%d" % (i + 1), np.arange(k, k + ls[i + 1]))); k += ls[i + 1]
-    oW, ob = out_layer_offsets(n, m, hid)
-    h = ls[-2]
-    for a in range(m):
-        out.append(("row%d" % a, np.r_[oW + a * h:oW + (a + 1) * h, ob + a]))
-    out.append(("log_std", np.arange(ob + m, ob + 2 * m)))
-    return out
-
-
-def block_errors(dev, ref, n, m, hid):
-    return {lab: rel(dev[ix], ref[ix]) for lab, ix in blocks(n, m, hid)}
-
-
 # ---------------------------------------------------------------------------------------------------------------- runs
 @functools.lru_cache(maxsize=None)
 def head_oracle(name):
@@ -144,8 +134,12 @@ def head_oracle(name):
     r = dict(g=O.vpg(th, th, obs, act, adv, n, m, hid, tr, tr), hv=O.fvp(th, obs, v, n, m, hid, tr),
              s=O.surrogate(t2, th, obs, act, adv, n, m, hid, tr, tr), kl=O.mean_kl(t2, th, obs, n, m, hid, tr, tr),
              g2=O.vpg(t2, th, obs, act, adv, n, m, hid, tr, tr))
+    H = O.forward(th, obs, n, m, hid, tr, keep=True)[1][-1]
+    Vs, cs, _ = O.unflatten(v.astype(np.float64), n, m, hid)
     for a in probe_actions(m):
         r["hv_a%d" % a] = O.fvp(th, obs, probe_direction(v, n, m, hid, a).astype(np.float64), n, m, hid, tr)
+        t = np.append(H[0] * Vs[-1][a], cs[-1][a])                # (row 0's output-layer tangent of action a)
+        r["cond_a%d" % a] = float(np.abs(t).sum() / abs(t.sum()))
     return r
 
 
@@ -198,7 +192,8 @@ def check_head(name, r, per_block=True, k3=True):
             for lab, e in block_errors(r[key], ref[key], n, m, hid).items():
                 assert e < (row_bar if lab.startswith("row") else block_bar), (key, lab, e)
     for a in probe_actions(m):                 # only output row a of the direction is non-zero: a dropped or misplaced action is O(1)
-        assert rel(r["hv_a%d" % a], ref["hv_a%d" % a]) < (BAR_PROBE_N1 if c["N"] == 1 else TOL_FVP), ("probe", a)
+        bar = BAR_PROBE_N1 * max(1.0, ref["cond_a%d" % a] / PROBE_COND_N1) if c["N"] == 1 else TOL_FVP
+        assert rel(r["hv_a%d" % a], ref["hv_a%d" % a]) < bar, ("probe", a)
     if k3:
         assert abs(float(r["s"]) - ref["s"]) < 5e-6
         assert abs(float(r["kl"]) - ref["kl"]) < 2e-5 * ref["kl"] + 1e-7

@@ -994,7 +994,7 @@ def test_hvp_sample_frac_rng_parity():
     (10, 4, (256, 192), False),    # last hidden layer not a multiple of 128: the generic chain
     (40, 5, (256, 512, 256), False),   # three hidden layers through every r02 path: padded observation rows (40 -> 64), persistent
                                        # forward / tangent / delta products with one and two 256-column blocks, the eight-wave output pass
-    (33, 2, (128,), False),        # one hidden layer of 128 units, 33 observations (-> 64): no fused output pass (needs two layers)
+    (33, 2, (128,), False),        # one hidden layer of 128 units, 33 observations (-> 64): nL() = 2, so the one-pass output layer k_lw_head<1> runs
 ])
 def test_other_shapes_vs_oracle(n, m, hid, expect_fused):
     """every kernel variant / dispatch branch: K1, K2, K3 against the fp64 oracle (with transforms, old != new in K3)"""
