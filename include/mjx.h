@@ -388,6 +388,48 @@ int mjx_mlp_fit_adam(const float* feat, const float* y, int64_t N, int d_in, con
                      float* params, float* m, float* v, int64_t step0, const int32_t* perm, int epochs, int batch,
                      float lr, float wd, double* epoch_loss_out, void* stream);
 
+/* ---- model-based NPG (mjrl/algos/model_accel/) ----------------------------- */
+/* Nets: sizes = [d_in, h..., d_out] (n_sizes entries, at most 9); per member a flat parameter vector in
+ * DynamicsNet.parameters() order [W1 (h1 x d_in), b1, ..., W_out, b_out] (nn_dynamics.py:184-187) and transforms
+ * [in_shift (d_in), in_scale (d_in), out_shift (d_out), out_scale (d_out)] over the concatenated input ([s, a], or
+ * [s, a, s'] for RewardNet with the s transforms repeated for s', nn_dynamics.py:319-321).  act: 0 = ReLU, 1 = tanh
+ * (WorldModel(activation=), nn_dynamics.py:26).  flags: 1 = output affine out * (out_scale + 1e-8) + out_shift,
+ * 2 = mask (out_scale >= 1e-8), 4 = residual + s (= x[:, :d_out]) (nn_dynamics.py:241-244). */
+/* K members x rows of forward (DynamicsNet.forward nn_dynamics.py:230-245, RewardNet.forward :313-328): member k reads
+ * x + k * x_stride (x_stride 0: the same rows for all), params + k * P, tr + k * (2 d_in + 2 d_out) and writes
+ * out[k] (rows x d_out). */
+int mjx_dyn_forward(const float* x, int64_t x_stride, int64_t rows, int K, const int* sizes, int n_sizes,
+                    const float* params, const float* tr, int act, int flags, float* out, void* stream);
+/* policy_rollout (model_accel/sampling.py:16-89) for K members at once, in one persistent launch: per step the tanh
+ * policy mean (pol_sizes = [n, h..., m], pol_params = the policy's flat vector WITH log_std, pol_tr = its packed
+ * transforms), + noise[k][t] * exp(log_std) (noise: K x H x N x m normals drawn by the caller, torch.randn((N, m))
+ * per step; NULL = eval_mode), clamp to [a_min, a_max] (m each; NULL = no clamp), the dynamics forward of member k
+ * (dyn_sizes = [n + m, h..., n]), clamp to [s_min, s_max] (enforce_tensor_bounds, sampling.py:286-315).
+ * obs_out[k] (N x H x n) holds the state BEFORE step t, act_out[k] (N x H x m) the action.
+ * With actions != NULL (N x H x m; pol_sizes and noise NULL) it is trajectory_rollout (sampling.py:96-123). */
+int mjx_model_rollout(const float* s0, int64_t N, int H, int K, const int* pol_sizes, int pol_n_sizes,
+                      const float* pol_params, const float* pol_tr, const float* noise, const float* actions,
+                      const int* dyn_sizes, int dyn_n_sizes, const float* dyn_params, const float* dyn_tr, int act,
+                      int flags, const float* a_min, const float* a_max, const float* s_min, const float* s_max,
+                      float* obs_out, float* act_out, void* stream);
+/* fit_model (nn_dynamics.py:344-385) behind fit_dynamics (:87-116) / fit_reward (:118-147): `steps` minibatch steps of
+ * torch.optim.Adam(lr, weight_decay=wd) on the MSE over batch x d_out.  x: N x d_in raw inputs, normalised once with
+ * in_tr ([shift, scale]); y: N x d_out raw targets; out_tr = [out_shift, out_scale].  target_mode 0: the loss runs
+ * through the output affine (RewardNet), 1: targets (y - out_shift) / (out_scale + 1e-8), 2: residual targets
+ * (y - x[:, :d_out] - out_shift) / (out_scale + 1e-8).  idx: steps x batch row indices (per epoch the first
+ * (N // batch) x batch entries of np.random.permutation(N), drawn by the caller).  params / m / v updated in place,
+ * step0 = Adam steps already taken; loss_out[s] = the minibatch loss of step s (device fp32).  Hidden widths <= 128
+ * and batch <= 64 run as ONE persistent launch while the minibatch fits in LDS (csrc/dynamics.h), the rest one launch
+ * per layer and phase; MJX_DYN_FIT_LAUNCHES=1 forces the latter.  Uses per-host-thread scratch. */
+int mjx_dyn_fit_adam(const float* x, const float* y, int64_t N, const int* sizes, int n_sizes, const float* in_tr,
+                     const float* out_tr, int target_mode, int act, float* params, float* m, float* v, int64_t step0,
+                     const int32_t* idx, int64_t steps, int batch, float lr, float wd, float* loss_out, void* stream);
+/* ensemble-disagreement truncation (model_accel_npg.py:137-155): pred = K x rows x n model predictions, s_next the
+ * rows' next states; err_out[r] = max_k mean_j (s_next - pred)^2; segment g = rows [seg_off[g], seg_off[g+1]) (one
+ * path); first_out[g] = the first row of the segment whose error exceeds lim, -1 if none. */
+int mjx_dyn_pred_error(const float* pred, int K, int64_t rows, int n, const float* s_next, const int64_t* seg_off,
+                       int nseg, double lim, float* err_out, int32_t* first_out, void* stream);
+
 /* ---- in-library kernel timing (bench.py roofline) ------------------------- */
 /* While enabled (on = k >= 1), every k-th launch of the dominant Fisher-vector-product kernel
  * (fused k_fused MODE_FVP, or the whole layer-wise FVP chain) is bracketed by hipEvents recorded

@@ -83,6 +83,14 @@ PROTOTYPES = {
     "mjx_mlp_predict": (c_int, [c_void_p, c_int64, c_int, ctypes.POINTER(c_int), c_int, c_void_p, c_void_p, c_void_p]),
     "mjx_mlp_fit_adam": (c_int, [c_void_p, c_void_p, c_int64, c_int, ctypes.POINTER(c_int), c_int, c_void_p, c_void_p, c_void_p,
                                  c_int64, c_void_p, c_int, c_int, c_float, c_float, c_void_p, c_void_p]),
+    "mjx_dyn_forward": (c_int, [c_void_p, c_int64, c_int64, c_int, ctypes.POINTER(c_int), c_int, c_void_p, c_void_p, c_int, c_int, c_void_p,
+                                c_void_p]),
+    "mjx_model_rollout": (c_int, [c_void_p, c_int64, c_int, c_int, ctypes.POINTER(c_int), c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                  ctypes.POINTER(c_int), c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                  c_void_p, c_void_p, c_void_p]),
+    "mjx_dyn_fit_adam": (c_int, [c_void_p, c_void_p, c_int64, ctypes.POINTER(c_int), c_int, c_void_p, c_void_p, c_int, c_int, c_void_p,
+                                 c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_float, c_float, c_void_p, c_void_p]),
+    "mjx_dyn_pred_error": (c_int, [c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p, c_int, c_double, c_void_p, c_void_p, c_void_p]),
     "mjx_profile_enable": (c_int, [c_void_p, c_int]),
     "mjx_profile_read": (c_int, [c_void_p, ctypes.POINTER(c_double)]),
     "mjx_profile_samples": (c_int, [c_void_p, ctypes.POINTER(c_double), c_int, ctypes.POINTER(c_int)]),

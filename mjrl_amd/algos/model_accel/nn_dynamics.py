@@ -1,0 +1,475 @@
+"""Learned dynamics / reward models on the GPU.
+
+Mirrors ``mjrl.algos.model_accel.nn_dynamics`` (reference nn_dynamics.py:7-385): the same classes, constructor
+arguments, parameters (torch ``nn.Linear`` layers built after ``torch.manual_seed(seed)``, so the initial weights and the
+global torch stream are the reference's) and transforms.  What runs where:
+
+* ``forward`` / ``predict`` / ``reward`` / ``compute_loss``: the batched forward kernel (``mjx_dyn_forward``), K ensemble
+  members per launch through :func:`ensemble_forward`;
+* ``fit_dynamics`` / ``fit_reward``: the transforms are formed with the reference's torch expressions, the epoch
+  permutations are drawn from NumPy's global stream exactly where ``fit_model`` draws them, and every Adam step runs in
+  libmjx (``mjx_dyn_fit_adam``: one persistent launch for nets up to 128 wide at minibatch <= 64, a launch per layer and
+  phase otherwise).  The optimiser state (``dynamics_opt`` / ``reward_opt``) is torch.optim.Adam's -- step count and
+  both moments -- kept as flat fp32 vectors.
+
+The module parameters stay ordinary torch tensors (CPU by default, as in the reference): ``get_params`` /
+``set_params`` / ``to`` / ``is_cuda`` / pickling behave as the reference's.  There is no CPU path: without a GPU the
+operations raise.
+"""
+import ctypes
+
+import numpy as np
+import torch
+import torch.nn as nn
+
+from ..._lib import MjxError, check, load, ptr
+
+ACT_RELU, ACT_TANH = 0, 1
+OUT_AFFINE, MASK, RESIDUAL = 1, 2, 4
+TGT_AFFINE, TGT_PLAIN, TGT_RESIDUAL = 0, 1, 2
+
+
+def _device():
+    if not torch.cuda.is_available():
+        raise MjxError("model_accel: no GPU visible -- the learned-model operations run in libmjx only")
+    return torch.device("cuda", torch.cuda.current_device())
+
+
+def _stream(dev):
+    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+
+def _ints(v):
+    return (ctypes.c_int * len(v))(*[int(x) for x in v])
+
+
+def _f32(x, dev):
+    if isinstance(x, np.ndarray):
+        x = torch.from_numpy(x)
+    return x.to(device=dev, dtype=torch.float32).contiguous()
+
+
+def _act_code(net):
+    return ACT_TANH if net.nonlinearity is torch.tanh else ACT_RELU
+
+
+def _flat_params(net, dev):
+    return torch.cat([p.detach().reshape(-1).to(dev, torch.float32) for p in net.parameters()])
+
+
+def _vec(v, k):
+    if isinstance(v, torch.Tensor):
+        v = v.detach().to("cpu", torch.float32).reshape(-1)
+        return v.expand(k) if v.numel() == 1 else v
+    return torch.full((k,), float(v), dtype=torch.float32)
+
+
+def _packed_transforms(net, dev):
+    """[in_shift, in_scale, out_shift, out_scale] over the concatenated input (csrc/dynamics.h)"""
+    if isinstance(net, RewardNet):
+        sh = [net.s_shift, net.a_shift, net.sp_shift]
+        sc = [net.s_scale, net.a_scale, net.sp_scale]
+        k = 1
+    else:
+        sh, sc, k = [net.s_shift, net.a_shift], [net.s_scale, net.a_scale], net.out_dim
+    ins = [_vec(v, v.numel()) for v in sh] + [_vec(v, v.numel()) for v in sc]
+    return torch.cat(ins + [_vec(net.out_shift, k), _vec(net.out_scale, k)]).to(dev)
+
+
+def _flags(net):
+    if isinstance(net, RewardNet):
+        return OUT_AFFINE
+    if not net._apply_out_transforms:
+        return 0
+    return OUT_AFFINE | (MASK if net.use_mask else 0) | (RESIDUAL if net.residual else 0)
+
+
+def ensemble_forward(nets, x, dev=None):
+    """K nets of one shape over the same rows x (rows x d_in, the concatenated raw input) in one launch -> K x rows x d_out
+    (device tensor).  Each net's own activation, transforms and flags apply (one launch per distinct (activation, flags))."""
+    dev = dev or _device()
+    x = _f32(x, dev)
+    rows = x.shape[0]
+    sizes = nets[0].layer_sizes
+    out = torch.empty((len(nets), rows, sizes[-1]), dtype=torch.float32, device=dev)
+    groups = {}
+    for i, net in enumerate(nets):
+        assert tuple(net.layer_sizes) == tuple(sizes), "ensemble members must share one shape"
+        groups.setdefault((_act_code(net), _flags(net)), []).append(i)
+    lib = load()
+    for (act, flags), ids in groups.items():
+        P = torch.stack([_flat_params(nets[i], dev) for i in ids])
+        tr = torch.stack([_packed_transforms(nets[i], dev) for i in ids])
+        o = out if len(ids) == len(nets) else torch.empty((len(ids), rows, sizes[-1]), dtype=torch.float32, device=dev)
+        check(lib.mjx_dyn_forward(ptr(x), 0, rows, len(ids), _ints(sizes), len(sizes), ptr(P), ptr(tr), act, flags, ptr(o),
+                                  _stream(dev)))
+        if o is not out:
+            out[ids] = o
+    return out
+
+
+class _DeviceAdam:
+    """torch.optim.Adam(net.parameters(), lr, weight_decay) for one net: step count and flat fp32 moments (on the GPU
+    while fitting; ``to`` moves them)."""
+
+    def __init__(self, net, lr=1e-3, weight_decay=0.0):
+        self.param_groups = [dict(lr=lr, weight_decay=weight_decay, betas=(0.9, 0.999), eps=1e-8, amsgrad=False)]
+        self.num_params = int(sum(p.numel() for p in net.parameters()))
+        self.step_count = 0
+        self.exp_avg = self.exp_avg_sq = None
+
+    def to(self, device):
+        if self.exp_avg is not None:
+            self.exp_avg, self.exp_avg_sq = self.exp_avg.to(device), self.exp_avg_sq.to(device)
+        return self
+
+    def _state(self, dev):
+        if self.exp_avg is None:
+            self.exp_avg = torch.zeros(self.num_params, dtype=torch.float32, device=dev)
+            self.exp_avg_sq = torch.zeros(self.num_params, dtype=torch.float32, device=dev)
+        self.to(dev)
+        return self.exp_avg, self.exp_avg_sq
+
+
+class WorldModel:
+    def __init__(self, state_dim, act_dim,
+                 learn_reward=False,
+                 hidden_size=(64, 64),
+                 seed=123,
+                 fit_lr=1e-3,
+                 fit_wd=0.0,
+                 device='cpu',
+                 activation='relu',
+                 residual=True,
+                 *args,
+                 **kwargs,):
+        """Arguments as in the reference (nn_dynamics.py:8-38)."""
+        self.state_dim, self.act_dim = state_dim, act_dim
+        self.device, self.learn_reward = device, learn_reward
+        if self.device == 'gpu':
+            self.device = 'cuda'
+        self.dynamics_net = DynamicsNet(state_dim, act_dim, hidden_size, residual=residual, seed=seed).to(self.device)
+        self.dynamics_net.set_transformations()
+        if activation == 'tanh':
+            self.dynamics_net.nonlinearity = torch.tanh
+        self.dynamics_opt = _DeviceAdam(self.dynamics_net, lr=fit_lr, weight_decay=fit_wd)
+        self.dynamics_loss = torch.nn.MSELoss()
+        if self.learn_reward:
+            self.reward_net = RewardNet(state_dim, act_dim, hidden_size=(100, 100), seed=seed).to(self.device)
+            self.reward_net.set_transformations()
+            if activation == 'tanh':
+                self.reward_net.nonlinearity = torch.tanh
+            self.reward_opt = _DeviceAdam(self.reward_net, lr=fit_lr, weight_decay=fit_wd)
+            self.reward_loss = torch.nn.MSELoss()
+        else:
+            self.reward_net, self.reward_opt, self.reward_loss = None, None, None
+
+    def to(self, device):
+        self.dynamics_net.to(device)
+        self.dynamics_opt.to(device)
+        if self.learn_reward:
+            self.reward_net.to(device)
+            self.reward_opt.to(device)
+
+    def is_cuda(self):
+        return next(self.dynamics_net.parameters()).is_cuda
+
+    def forward(self, s, a):
+        if type(s) == np.ndarray:
+            s = torch.from_numpy(s).float()
+        if type(a) == np.ndarray:
+            a = torch.from_numpy(a).float()
+        return self.dynamics_net.forward(s.to(self.device), a.to(self.device))
+
+    def predict(self, s, a):
+        s = torch.from_numpy(s).float()
+        a = torch.from_numpy(a).float()
+        return self.dynamics_net.forward(s, a).to('cpu').data.numpy()
+
+    def reward(self, s, a):
+        if not self.learn_reward:
+            print("Reward model is not learned. Use the reward function from env.")
+            return None
+        if type(s) == np.ndarray:
+            s = torch.from_numpy(s).float()
+        if type(a) == np.ndarray:
+            a = torch.from_numpy(a).float()
+        s, a = s.to(self.device), a.to(self.device)
+        sp = self.dynamics_net.forward(s, a).detach().clone()
+        return self.reward_net.forward(s, a, sp)
+
+    def compute_loss(self, s, a, s_next):
+        # (logging only, as in the reference)
+        sp = self.forward(s, a)
+        s_next = torch.from_numpy(s_next).float() if type(s_next) == np.ndarray else s_next
+        loss = self.dynamics_loss(sp, s_next.to(sp.device))
+        return loss.to('cpu').data.numpy()
+
+    def fit_dynamics(self, s, a, sp, fit_mb_size, fit_epochs, max_steps=1e4,
+                     set_transformations=True, *args, **kwargs):
+        assert type(s) == type(a) == type(sp)
+        assert s.shape[0] == a.shape[0] == sp.shape[0]
+        if type(s) == np.ndarray:
+            s = torch.from_numpy(s).float()
+            a = torch.from_numpy(a).float()
+            sp = torch.from_numpy(sp).float()
+        s = s.to(self.device); a = a.to(self.device); sp = sp.to(self.device)
+        net = self.dynamics_net
+        # the reference's transform expressions, on the reference's device (nn_dynamics.py:99-104)
+        if set_transformations:
+            s_shift, a_shift = torch.mean(s, dim=0), torch.mean(a, dim=0)
+            s_scale, a_scale = torch.mean(torch.abs(s - s_shift), dim=0), torch.mean(torch.abs(a - a_shift), dim=0)
+            out_shift = torch.mean(sp - s, dim=0) if net.residual else torch.mean(sp, dim=0)
+            out_scale = torch.mean(torch.abs(sp - s - out_shift), dim=0) if net.residual else torch.mean(torch.abs(sp - out_shift), dim=0)
+            net.set_transformations(s_shift, s_scale, a_shift, a_scale, out_shift, out_scale)
+        # targets (sp [- s] - out_shift) / (out_scale + 1e-8) are formed on the GPU (k_dyn_prep); the fit runs in the
+        # transformed space (the reference's _apply_out_transforms = False, nn_dynamics.py:107-115)
+        return _fit(net, self.dynamics_opt, torch.cat([s, a], -1), sp, TGT_RESIDUAL if net.residual else TGT_PLAIN,
+                    fit_mb_size, fit_epochs, max_steps)
+
+    def fit_reward(self, s, a, r, fit_mb_size, fit_epochs, max_steps=1e4,
+                   set_transformations=True, *args, **kwargs):
+        if not self.learn_reward:
+            print("Reward model was not initialized to be learnable. Use the reward function from env.")
+            return None
+        assert type(s) == type(a) == type(r)
+        assert len(r.shape) == 2 and r.shape[1] == 1
+        assert s.shape[0] == a.shape[0] == r.shape[0]
+        if type(s) == np.ndarray:
+            s = torch.from_numpy(s).float()
+            a = torch.from_numpy(a).float()
+            r = torch.from_numpy(r).float()
+        s = s.to(self.device); a = a.to(self.device); r = r.to(self.device)
+        if set_transformations:
+            s_shift, a_shift = torch.mean(s, dim=0), torch.mean(a, dim=0)
+            s_scale, a_scale = torch.mean(torch.abs(s - s_shift), dim=0), torch.mean(torch.abs(a - a_shift), dim=0)
+            r_shift, r_scale = torch.mean(r, dim=0), torch.mean(torch.abs(r - r_shift), dim=0)
+            self.reward_net.set_transformations(s_shift, s_scale, a_shift, a_scale, r_shift, r_scale)
+        sp = self.dynamics_net.forward(s, a).detach().clone()
+        sp = sp.to(s.device)
+        return _fit(self.reward_net, self.reward_opt, torch.cat([s, a, sp], -1), r, TGT_AFFINE, fit_mb_size, fit_epochs,
+                    max_steps)
+
+    def compute_path_rewards(self, paths):
+        if not self.learn_reward:
+            print("Reward model is not learned. Use the reward function from env.")
+            return None
+        s, a = paths['observations'], paths['actions']
+        num_traj, horizon, s_dim = s.shape
+        a_dim = a.shape[-1]
+        r = self.reward(s.reshape(-1, s_dim), a.reshape(-1, a_dim))
+        paths['rewards'] = r.to('cpu').data.numpy().reshape(num_traj, horizon)
+
+
+def fit_permutations(num_samples, batch_size, epochs, max_steps=1e10):
+    """fit_model's host side (nn_dynamics.py:363-384): one np.random.permutation(num_samples) per epoch, (N // batch) steps
+    per epoch, stop after the epoch whose steps reach max_steps -> (row indices of every step, steps per epoch, epochs run)"""
+    num_steps = int(num_samples // batch_size)
+    idx, steps_so_far, ran = [], 0, 0
+    for ep in range(epochs):
+        perm = np.random.permutation(num_samples)
+        idx.append(perm[:num_steps * batch_size])
+        ran += 1
+        steps_so_far += num_steps
+        if steps_so_far >= max_steps:
+            print("Number of grad steps exceeded threshold. Terminating early..")
+            break
+    flat = np.concatenate(idx).astype(np.int32) if idx else np.zeros(0, np.int32)
+    return flat, num_steps, ran
+
+
+def epoch_means(step_losses, num_steps, epochs):
+    """the reference's per-epoch bookkeeping on fp32 losses (`ep_loss += loss.numpy()`, then `ep_loss * 1.0 / num_steps`)"""
+    out = []
+    for ep in range(epochs):
+        ep_loss = 0.0
+        for mb in range(num_steps):
+            ep_loss += np.array(step_losses[ep * num_steps + mb], dtype=np.float32)
+        out.append(ep_loss * 1.0 / num_steps)
+    return out
+
+
+def _fit(net, opt, X, Y, target_mode, batch_size, epochs, max_steps):
+    dev = _device()
+    N = int(Y.shape[0])
+    idx, num_steps, ran = fit_permutations(N, batch_size, epochs, max_steps)
+    steps = ran * num_steps
+    if steps == 0:
+        return epoch_means([], num_steps, ran)
+    X, Y = _f32(X, dev), _f32(Y.reshape(N, -1), dev)
+    P = _flat_params(net, dev)
+    tr = _packed_transforms(net, dev)
+    din, dout = net.layer_sizes[0], net.layer_sizes[-1]
+    in_tr = torch.cat([tr[:din], tr[din:2 * din]])
+    out_tr = tr[2 * din:]
+    m, v = opt._state(dev)
+    g = opt.param_groups[0]
+    idx_d = torch.from_numpy(idx).to(dev)
+    loss = torch.empty(steps, dtype=torch.float32, device=dev)
+    check(load().mjx_dyn_fit_adam(ptr(X), ptr(Y), N, _ints(net.layer_sizes), len(net.layer_sizes), ptr(in_tr), ptr(out_tr),
+                                  target_mode, _act_code(net), ptr(P), ptr(m), ptr(v), opt.step_count, ptr(idx_d), steps,
+                                  int(batch_size), float(g['lr']), float(g['weight_decay']), ptr(loss), _stream(dev)))
+    opt.step_count += steps
+    k = 0
+    with torch.no_grad():
+        for p in net.parameters():
+            p.data.copy_(P[k:k + p.numel()].view_as(p))
+            k += p.numel()
+    return epoch_means(loss.cpu().numpy(), num_steps, ran)
+
+
+class DynamicsNet(nn.Module):
+    def __init__(self, state_dim, act_dim, hidden_size=(64, 64),
+                 s_shift=None,
+                 s_scale=None,
+                 a_shift=None,
+                 a_scale=None,
+                 out_shift=None,
+                 out_scale=None,
+                 out_dim=None,
+                 residual=True,
+                 seed=123,
+                 use_mask=True,
+                 ):
+        """nn_dynamics.py:167-191: the same layers drawn from torch's stream after torch.manual_seed(seed)."""
+        super(DynamicsNet, self).__init__()
+        torch.manual_seed(seed)
+        self.state_dim, self.act_dim, self.hidden_size = state_dim, act_dim, hidden_size
+        self.out_dim = state_dim if out_dim is None else out_dim
+        self.layer_sizes = (state_dim + act_dim, ) + tuple(hidden_size) + (self.out_dim, )
+        self.fc_layers = nn.ModuleList([nn.Linear(self.layer_sizes[i], self.layer_sizes[i + 1])
+                                        for i in range(len(self.layer_sizes) - 1)])
+        self.nonlinearity = torch.relu
+        self.residual, self.use_mask = residual, use_mask
+        self._apply_out_transforms = True
+        self.set_transformations(s_shift, s_scale, a_shift, a_scale, out_shift, out_scale)
+
+    def set_transformations(self, s_shift=None, s_scale=None,
+                            a_shift=None, a_scale=None,
+                            out_shift=None, out_scale=None):
+        """nn_dynamics.py:193-228: tensors are kept as given, arrays become fp32 tensors, None = identity transforms"""
+        given = (s_shift, s_scale, a_shift, a_scale, out_shift, out_scale)
+        dims = (self.state_dim, self.state_dim, self.act_dim, self.act_dim, self.out_dim, self.out_dim)
+        if s_shift is None:
+            vals = [torch.full((k,), float(i % 2)) for i, k in enumerate(dims)]
+        elif type(s_shift) in (torch.Tensor, np.ndarray):
+            vals = [v if type(s_shift) == torch.Tensor else torch.from_numpy(np.float32(v)) for v in given]
+        else:
+            raise TypeError("Unknown type for transformations")
+        device = next(self.parameters()).data.device
+        (self.s_shift, self.s_scale, self.a_shift, self.a_scale, self.out_shift, self.out_scale) = [v.to(device) for v in vals]
+        self.mask = self.out_scale >= 1e-8          # output columns without variation are forced to zero
+        self.transformations = dict(s_shift=self.s_shift, s_scale=self.s_scale, a_shift=self.a_shift, a_scale=self.a_scale,
+                                    out_shift=self.out_shift, out_scale=self.out_scale)
+
+    def forward(self, s, a):
+        """nn_dynamics.py:230-245 on the GPU (mjx_dyn_forward); returns a tensor on s's device (no autograd)"""
+        if s.dim() != a.dim():
+            print("State and action inputs should be of the same size")
+        lead = s.shape[:-1]
+        dev = _device()
+        x = torch.cat([_f32(s, dev).reshape(-1, self.state_dim), _f32(a, dev).reshape(-1, self.act_dim)], -1)
+        out = ensemble_forward([self], x, dev)[0]
+        return out.reshape(*lead, self.out_dim).to(s.device)
+
+    def get_params(self):
+        network_weights = [p.data for p in self.parameters()]
+        transforms = (self.s_shift, self.s_scale,
+                      self.a_shift, self.a_scale,
+                      self.out_shift, self.out_scale)
+        return dict(weights=network_weights, transforms=transforms)
+
+    def set_params(self, new_params):
+        new_weights = new_params['weights']
+        s_shift, s_scale, a_shift, a_scale, out_shift, out_scale = new_params['transforms']
+        for idx, p in enumerate(self.parameters()):
+            p.data = new_weights[idx]
+        self.set_transformations(s_shift, s_scale, a_shift, a_scale, out_shift, out_scale)
+
+
+class RewardNet(nn.Module):
+    def __init__(self, state_dim, act_dim,
+                 hidden_size=(64, 64),
+                 s_shift=None,
+                 s_scale=None,
+                 a_shift=None,
+                 a_scale=None,
+                 seed=123,
+                 ):
+        """nn_dynamics.py:263-279: r = f(s, a, s')"""
+        super(RewardNet, self).__init__()
+        torch.manual_seed(seed)
+        self.state_dim, self.act_dim, self.hidden_size = state_dim, act_dim, hidden_size
+        self.layer_sizes = (state_dim + act_dim + state_dim, ) + tuple(hidden_size) + (1, )
+        self.fc_layers = nn.ModuleList([nn.Linear(self.layer_sizes[i], self.layer_sizes[i + 1])
+                                        for i in range(len(self.layer_sizes) - 1)])
+        self.nonlinearity = torch.relu
+        self.set_transformations(s_shift, s_scale, a_shift, a_scale)
+
+    def set_transformations(self, s_shift=None, s_scale=None,
+                            a_shift=None, a_scale=None,
+                            out_shift=None, out_scale=None):
+        """nn_dynamics.py:281-311: s' shares the s transforms; out_shift / out_scale are kept as given (0.0 / 1.0 if None)"""
+        n, m = self.state_dim, self.act_dim
+        if s_shift is None:
+            vals = [torch.zeros(n), torch.ones(n), torch.zeros(m), torch.ones(m)]
+            out_shift, out_scale = 0.0, 1.0
+        elif type(s_shift) == torch.Tensor:
+            vals = [s_shift, s_scale, a_shift, a_scale]
+        elif type(s_shift) == np.ndarray:
+            vals = [torch.from_numpy(v).float() for v in (s_shift, s_scale, a_shift, a_scale)]
+        else:
+            raise TypeError("Unknown type for transformations")
+        device = next(self.parameters()).data.device
+        self.s_shift, self.s_scale, self.a_shift, self.a_scale = [v.to(device) for v in vals]
+        self.sp_shift, self.sp_scale = self.s_shift, self.s_scale
+        self.out_shift, self.out_scale = out_shift, out_scale
+        self.transformations = dict(s_shift=self.s_shift, s_scale=self.s_scale, a_shift=self.a_shift, a_scale=self.a_scale,
+                                    out_shift=self.out_shift, out_scale=self.out_scale)
+
+    def forward(self, s, a, sp):
+        """nn_dynamics.py:313-328 on the GPU (mjx_dyn_forward)"""
+        if s.dim() != a.dim():
+            print("State and action inputs should be of the same size")
+        lead = s.shape[:-1]
+        dev = _device()
+        n, m = self.state_dim, self.act_dim
+        x = torch.cat([_f32(s, dev).reshape(-1, n), _f32(a, dev).reshape(-1, m), _f32(sp, dev).reshape(-1, n)], -1)
+        return ensemble_forward([self], x, dev)[0].reshape(*lead, 1).to(s.device)
+
+    def get_params(self):
+        network_weights = [p.data for p in self.parameters()]
+        transforms = (self.s_shift, self.s_scale,
+                      self.a_shift, self.a_scale)
+        return dict(weights=network_weights, transforms=transforms)
+
+    def set_params(self, new_params):
+        new_weights = new_params['weights']
+        s_shift, s_scale, a_shift, a_scale = new_params['transforms']
+        for idx, p in enumerate(self.parameters()):
+            p.data = new_weights[idx]
+        self.set_transformations(s_shift, s_scale, a_shift, a_scale)
+
+
+def fit_model(nn_model, X, Y, optimizer, loss_func, batch_size, epochs, max_steps=1e10):
+    """nn_dynamics.py:344-385 for this module's nets: X = (s, a) or (s, a, s'), Y the regression targets, optimizer a
+    ``_DeviceAdam`` (a net's ``dynamics_opt`` / ``reward_opt``).  The loss is the MSE (loss_func is not called).  A
+    DynamicsNet is fitted in the space it is in: with _apply_out_transforms False the targets are taken as given."""
+    assert type(X) == tuple
+    for d in X:
+        assert type(d) == torch.Tensor
+    assert type(Y) == torch.Tensor
+    if isinstance(nn_model, RewardNet):
+        mode = TGT_AFFINE
+    elif nn_model._apply_out_transforms:
+        raise MjxError("fit_model: a DynamicsNet is fitted with _apply_out_transforms = False (nn_dynamics.py:112)")
+    else:
+        mode = TGT_PLAIN
+    if mode == TGT_PLAIN:          # Y is already the target: fit against identity output transforms
+        saved = (nn_model.out_shift, nn_model.out_scale)
+        nn_model.out_shift, nn_model.out_scale = torch.zeros(nn_model.out_dim), torch.full((nn_model.out_dim,), 1.0 - 1e-8)
+        try:
+            return _fit(nn_model, optimizer, torch.cat(X, -1), Y, mode, batch_size, epochs, max_steps)
+        finally:
+            nn_model.out_shift, nn_model.out_scale = saved
+    return _fit(nn_model, optimizer, torch.cat(X, -1), Y, mode, batch_size, epochs, max_steps)

@@ -1,0 +1,186 @@
+"""Rollouts on learned models, on the GPU.
+
+Mirrors ``mjrl.algos.model_accel.sampling`` (reference sampling.py): ``policy_rollout`` and ``trajectory_rollout`` run as
+ONE persistent launch (``mjx_model_rollout``, csrc/dynamics.h) in which each workgroup walks a tile of trajectories of one
+ensemble member through all H steps: policy mean, + noise * exp(log_std), action clamp, dynamics, state clamp.  The noise
+is the reference's: ``torch.randn((N, m))`` once per step, drawn on the host from torch's global stream in the same order
+(:func:`draw_rollout_noise`) and uploaded once, so the noisy rollouts see the same numbers.  Real-environment sampling
+(``sample_paths``, ``evaluate_policy``) is out of scope here.
+"""
+import numpy as np
+import torch
+
+from ..._lib import check, load, ptr
+from .nn_dynamics import _act_code, _device, _f32, _flags, _flat_params, _ints, _packed_transforms, _stream
+
+
+def _as_env(env, env_kwargs=None):
+    if type(env) == str:
+        from mjrl.utils.gym_env import GymEnv
+        return GymEnv(env)
+    if hasattr(env, 'reset') and hasattr(env, 'horizon'):
+        return env
+    if callable(env):
+        return env(**(env_kwargs or {}))
+    print("Unsupported environment format")
+    raise AttributeError
+
+
+def draw_rollout_noise(num_models, horizon, num_traj, act_dim):
+    """the reference's draws for `num_models` consecutive noisy policy_rollout calls: torch.randn((N, m)) per step
+    (sampling.py:73) -> (K, H, N, m) fp32 CPU tensor"""
+    return torch.stack([torch.stack([torch.randn((num_traj, act_dim)) for _ in range(horizon)]) if horizon > 0
+                        else torch.zeros((0, num_traj, act_dim)) for _ in range(num_models)])
+
+
+def _bound(v, dim, default):
+    if v is None:
+        v = default
+    if isinstance(v, torch.Tensor):
+        v = v.detach().to('cpu', torch.float32).reshape(-1)
+        return v.expand(dim).contiguous() if v.numel() == 1 else v
+    return torch.full((dim,), float(v), dtype=torch.float32)
+
+
+def rollout_models(models, policy, init_states, horizon, noise=None, s_min=None, s_max=None, a_min=None, a_max=None,
+                   large_value=float(1e2), actions=None):
+    """K learned models (WorldModel) from the same N initial states in one launch -> (obs (K, N, H, n), act (K, N, H, m))
+    as NumPy fp32.  noise: (K, H, N, m) or None (eval_mode); actions (N, H, m): trajectory_rollout (no policy, no clamp)."""
+    dev = _device()
+    nets = [mdl.dynamics_net for mdl in models]
+    sizes = nets[0].layer_sizes
+    for net in nets:
+        assert tuple(net.layer_sizes) == tuple(sizes), "ensemble members must share one shape"
+    n, m = nets[0].state_dim, nets[0].act_dim
+    K = len(nets)
+    s0 = _f32(init_states, dev).reshape(-1, n)
+    N = s0.shape[0]
+    H = int(horizon)
+    acts = set((_act_code(net), _flags(net)) for net in nets)
+    assert len(acts) == 1, "ensemble members must share activation and output transforms"
+    act, flags = acts.pop()
+    P = torch.stack([_flat_params(net, dev) for net in nets])
+    tr = torch.stack([_packed_transforms(net, dev) for net in nets])
+    obs = torch.empty((K, N, H, n), dtype=torch.float32, device=dev)
+    act_out = torch.empty((K, N, H, m), dtype=torch.float32, device=dev)
+    lib = load()
+    if actions is None:
+        pol_sizes = (n,) + tuple(policy.hidden_sizes) + (m,)
+        pol_P = _f32(policy.get_param_values(), dev)
+        pol_tr = _f32(policy.model.packed_transforms(), dev)
+        nz = None if noise is None else _f32(noise, dev)
+        bnd = [_bound(a_min, m, -large_value), _bound(a_max, m, large_value),
+               _bound(s_min, n, -large_value), _bound(s_max, n, large_value)]
+        bnd = [b.to(dev) for b in bnd]
+        check(lib.mjx_model_rollout(ptr(s0), N, H, K, _ints(pol_sizes), len(pol_sizes), ptr(pol_P), ptr(pol_tr), ptr(nz), None,
+                                    _ints(sizes), len(sizes), ptr(P), ptr(tr), act, flags, ptr(bnd[0]), ptr(bnd[1]),
+                                    ptr(bnd[2]), ptr(bnd[3]), ptr(obs), ptr(act_out), _stream(dev)))
+    else:
+        ad = _f32(actions, dev).reshape(N, H, m)
+        check(lib.mjx_model_rollout(ptr(s0), N, H, K, None, 0, None, None, None, ptr(ad), _ints(sizes), len(sizes), ptr(P),
+                                    ptr(tr), act, flags, None, None, None, None, ptr(obs), ptr(act_out), _stream(dev)))
+    return obs.cpu().numpy(), act_out.cpu().numpy()
+
+
+# ===========================================================
+# Rollout parameteric policy on learned env to collect data
+# ===========================================================
+
+def policy_rollout(
+        num_traj,
+        env,
+        policy,
+        learned_model,
+        init_state=None,
+        eval_mode=False,
+        horizon=1e6,
+        env_kwargs=None,
+        seed=None,
+        s_min=None,
+        s_max=None,
+        a_min=None,
+        a_max=None,
+        large_value=float(1e2),
+        ):
+    """sampling.py:16-89: same arguments, same draws, same (num_traj, horizon, dim) outputs"""
+    env = _as_env(env, env_kwargs)
+    if seed is not None:
+        env.set_seed(seed)
+        torch.manual_seed(seed)
+    if init_state is None:
+        st = np.array([env.reset() for _ in range(num_traj)])
+    elif type(init_state) == np.ndarray:
+        st = init_state
+    elif type(init_state) == list:
+        st = np.array(init_state)
+    elif type(init_state) == torch.Tensor:
+        assert init_state.device == 'cpu'
+        st = init_state
+    else:
+        raise TypeError("Unsupported format for init state")
+    horizon = min(horizon, env.horizon)
+    m = learned_model.dynamics_net.act_dim
+    noise = None if eval_mode is True else draw_rollout_noise(1, int(horizon), int(np.shape(st)[0]), m)
+    obs, act = rollout_models([learned_model], policy, st, horizon, noise, s_min, s_max, a_min, a_max, large_value)
+    return dict(observations=obs[0], actions=act[0])
+
+
+# ===========================================================
+# Rollout action sequences on the learned model
+# ===========================================================
+
+def trajectory_rollout(actions, learned_model, init_states):
+    """sampling.py:96-123"""
+    actions = np.array(actions) if type(actions) == list else actions
+    num_traj, horizon = actions.shape[0], actions.shape[1]
+    if len(init_states.shape) == 1:
+        init_states = np.tile(init_states, (num_traj, 1))
+    obs, _ = rollout_models([learned_model], None, init_states, horizon, actions=actions)
+    return dict(observations=obs[0], actions=actions)
+
+
+# ===========================================================
+# Utility functions
+# ===========================================================
+
+def discount_sum(x, gamma, discounted_terminal=0.0):
+    """sampling.py:191-201: y[t] = x[t] + gamma * y[t + 1], y[T] = discounted_terminal"""
+    out, acc = [0.0] * len(x), discounted_terminal
+    for t in reversed(range(len(x))):
+        acc = x[t] + gamma * acc
+        out[t] = acc
+    return np.array(out)
+
+
+def generate_perturbed_actions(base_act, filter_coefs):
+    """sampling.py:204-215: base + sigma * N(0, 1) noise (NumPy's global stream), smoothed by a 3-tap recursive filter"""
+    sigma, b0, b1, b2 = filter_coefs
+    u = base_act + np.random.normal(loc=0, scale=1.0, size=base_act.shape) * sigma
+    u[0] = u[0] * (b0 + b1 + b2)
+    u[1] = b0 * u[1] + (b1 + b2) * u[0]
+    for t in range(2, u.shape[0]):
+        u[t] = b0 * u[t] + b1 * u[t - 1] + b2 * u[t - 2]
+    return u
+
+
+def generate_paths(num_traj, learned_model, start_state, base_act, filter_coefs, base_seed=None):
+    """sampling.py:218-232"""
+    if base_seed is not None:
+        np.random.seed(base_seed)
+    act = np.array([generate_perturbed_actions(base_act, filter_coefs) for _ in range(num_traj)])
+    return trajectory_rollout(act, learned_model, start_state)
+
+
+def enforce_tensor_bounds(torch_tensor, min_val=None, max_val=None, large_value=float(1e4), device=None):
+    """sampling.py:286-315: clamp to Box[min_val, max_val] (scalars or (B,) tensors; None = -/+ large_value)"""
+    min_val = -large_value if min_val is None else min_val
+    max_val = large_value if max_val is None else max_val
+    device = torch_tensor.data.device if device is None else device
+    assert type(min_val) == float or type(min_val) == torch.Tensor
+    assert type(max_val) == float or type(max_val) == torch.Tensor
+    lo = min_val if type(min_val) == torch.Tensor else torch.tensor(min_val)
+    hi = max_val if type(max_val) == torch.Tensor else torch.tensor(max_val)
+    for b in (lo, hi):
+        if len(b.shape) > 0:
+            assert b.shape[-1] == torch_tensor.shape[-1]
+    return torch.max(torch.min(torch_tensor, hi.to(device)), lo.to(device))

@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "baseline.h"
+#include "dynamics.h"
 #include "fused_policy.h"
 #include "policy_fit.h"
 #include "rccl_dyn.h"
@@ -735,6 +736,141 @@ int mjx_mlp_fit_adam(const float* feat, const float* y, int64_t N, int d_in, con
       hipLaunchKernelGGL(k_adam, dim3((unsigned)((net.P + 255) / 256)), dim3(256), 0, st, params, grads, m, v, net.P, lr, wd, b1, b2, eps, bc1, bc2s);
     }
   }
+  HIPCHK(hipGetLastError());
+  return MJX_OK;
+}
+
+// ---------------------------------------------------------------------------- model-based NPG (csrc/dynamics.h)
+namespace {
+int dyn_net(const int* sizes, int n_sizes, DynNet& net) {
+  if (!sizes || !net.init(sizes, n_sizes)) return fail(MJX_ERR_ARG, "bad layer sizes (2 .. %d entries, all > 0)", DYN_MAXL + 1);
+  return MJX_OK;
+}
+int dyn_lds_limit(const void* kern, size_t bytes) {
+  if (bytes > (size_t)160 * 1024) return fail(MJX_ERR_UNSUPPORTED, "needs %zu bytes of LDS (> 160 KiB)", bytes);
+  if (bytes > 64 * 1024) HIPCHK(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+  return MJX_OK;
+}
+}  // namespace
+
+int mjx_dyn_forward(const float* x, int64_t x_stride, int64_t rows, int K, const int* sizes, int n_sizes, const float* params,
+                    const float* tr, int act, int flags, float* out, void* stream) {
+  DynNet net;
+  if (int rc = dyn_net(sizes, n_sizes, net)) return rc;
+  if (!x || !params || !tr || !out || rows < 0 || K <= 0 || K > 65535 || (act != DYN_ACT_RELU && act != DYN_ACT_TANH) ||
+      ((flags & DYN_RESIDUAL) && net.dout() > net.din()))
+    return fail(MJX_ERR_ARG, "bad arguments");
+  if (rows == 0) return MJX_OK;
+  MJX_DEVICE_ENTRY();
+  const size_t bytes = sizeof(float) * 3 * DYN_FT * (size_t)net.maxw;
+  if (int rc = dyn_lds_limit((const void*)k_dyn_forward, bytes)) return rc;
+  DynFwdArgs a{net, x, x_stride, rows, params, tr, act, flags, out};
+  hipLaunchKernelGGL(k_dyn_forward, dim3((unsigned)((rows + DYN_FT - 1) / DYN_FT), (unsigned)K), dim3(256), bytes, (hipStream_t)stream, a);
+  HIPCHK(hipGetLastError());
+  return MJX_OK;
+}
+
+int mjx_model_rollout(const float* s0, int64_t N, int H, int K, const int* pol_sizes, int pol_n_sizes, const float* pol_params,
+                      const float* pol_tr, const float* noise, const float* actions, const int* dyn_sizes, int dyn_n_sizes,
+                      const float* dyn_params, const float* dyn_tr, int act, int flags, const float* a_min, const float* a_max,
+                      const float* s_min, const float* s_max, float* obs_out, float* act_out, void* stream) {
+  RolloutArgs a{};
+  if (int rc = dyn_net(dyn_sizes, dyn_n_sizes, a.dyn)) return rc;
+  const int n = a.dyn.dout(), m = a.dyn.din() - n;
+  if (!s0 || !dyn_params || !dyn_tr || !obs_out || !act_out || N < 0 || H < 0 || K <= 0 || K > 65535 || m <= 0 ||
+      (act != DYN_ACT_RELU && act != DYN_ACT_TANH) || (!a_min) != (!a_max) || (!s_min) != (!s_max))
+    return fail(MJX_ERR_ARG, "bad arguments");
+  if (actions) {
+    if (pol_sizes || noise) return fail(MJX_ERR_ARG, "given actions: no policy, no noise");
+  } else {
+    if (int rc = dyn_net(pol_sizes, pol_n_sizes, a.pol)) return rc;
+    if (!pol_params || !pol_tr || a.pol.din() != n || a.pol.dout() != m) return fail(MJX_ERR_ARG, "policy does not match the state / action dims");
+  }
+  if (N == 0 || H == 0) return MJX_OK;
+  MJX_DEVICE_ENTRY();
+  a.N = N; a.H = H; a.s0 = s0; a.actions = actions; a.pol_P = pol_params; a.pol_tr = pol_tr; a.noise = noise;
+  a.dyn_P = dyn_params; a.dyn_tr = dyn_tr; a.act = act; a.flags = flags;
+  a.a_lo = a_min; a.a_hi = a_max; a.s_lo = s_min; a.s_hi = s_max; a.obs = obs_out; a.act_out = act_out;
+  a.W = a.dyn.maxw > a.pol.maxw ? a.dyn.maxw : a.pol.maxw;
+  const int64_t Ppol = actions ? 0 : a.pol.P + m;
+  const size_t bytes = sizeof(float) * (size_t)(((Ppol + 3) & ~3) + DYN_RT * (n + m) + 4 * DYN_RT * (int64_t)a.W);
+  if (int rc = dyn_lds_limit((const void*)k_model_rollout, bytes)) return rc;
+  hipLaunchKernelGGL(k_model_rollout, dim3((unsigned)((N + DYN_RT - 1) / DYN_RT), (unsigned)K), dim3(256), bytes, (hipStream_t)stream, a);
+  HIPCHK(hipGetLastError());
+  return MJX_OK;
+}
+
+int mjx_dyn_fit_adam(const float* x, const float* y, int64_t N, const int* sizes, int n_sizes, const float* in_tr, const float* out_tr,
+                     int target_mode, int act, float* params, float* m, float* v, int64_t step0, const int32_t* idx, int64_t steps,
+                     int batch, float lr, float wd, float* loss_out, void* stream) {
+  DynNet net;
+  if (int rc = dyn_net(sizes, n_sizes, net)) return rc;
+  const int din = net.din(), dout = net.dout();
+  if (!x || !y || !in_tr || !out_tr || !params || !m || !v || (steps > 0 && (!idx || !loss_out)) || N <= 0 || batch <= 0 || batch > N ||
+      steps < 0 || step0 < 0 || target_mode < DYN_TGT_AFFINE || target_mode > DYN_TGT_RESIDUAL || (act != DYN_ACT_RELU && act != DYN_ACT_TANH) ||
+      (target_mode == DYN_TGT_RESIDUAL && dout > din))
+    return fail(MJX_ERR_ARG, "bad arguments");
+  if (steps == 0) return MJX_OK;
+  MJX_DEVICE_ENTRY();
+  hipStream_t st = (hipStream_t)stream;
+  // scratch: normalised inputs + targets (prep), then the launch route's minibatch activations and deltas
+  int wmax = 0; size_t hsum = 0;
+  for (int l = 1; l <= net.nl; ++l) { wmax = net.sz[l] > wmax ? net.sz[l] : wmax; hsum += net.sz[l]; }
+  const size_t prep = (size_t)N * (din + dout), mb = (size_t)batch * (din + dout + hsum + 2 * (size_t)wmax);
+  static thread_local Scratch sc;
+  if (int rc = get_scratch(sc, (prep + mb) * sizeof(float))) return rc;
+  float* xn = (float*)sc.p; float* tg = xn + (size_t)N * din;
+  {
+    const int64_t tot = N * (din > dout ? din : dout);
+    const unsigned grid = (unsigned)((tot + 255) / 256 < 4096 ? (tot + 255) / 256 : 4096);
+    hipLaunchKernelGGL(k_dyn_prep, dim3(grid), dim3(256), 0, st, x, y, N, din, dout, in_tr, out_tr, target_mode, xn, tg);
+  }
+  const float* oaff = target_mode == DYN_TGT_AFFINE ? out_tr : nullptr;
+  // persistent single-launch trainer for hidden widths <= 128 and minibatch <= 64 whose activations fit in LDS;
+  // MJX_DYN_FIT_LAUNCHES=1 forces the launch route (read per call: the tests compare the two routes in one process)
+  const char* force = getenv("MJX_DYN_FIT_LAUNCHES");
+  bool narrow = true;
+  for (int l = 1; l < net.nl; ++l) narrow = narrow && net.sz[l] <= 128;
+  const size_t fbytes = dyn_fit_lds_bytes(net, batch);
+  if (!(force && force[0] == '1') && narrow && batch <= 64 && fbytes <= (size_t)160 * 1024) {
+    if (int rc = dyn_lds_limit((const void*)k_dyn_fit, fbytes)) return rc;
+    DynFitArgs a{net, xn, tg, idx, steps, batch, params, m, v, step0, lr, wd, act, oaff, loss_out};
+    hipLaunchKernelGGL(k_dyn_fit, dim3(1), dim3(1024), fbytes, st, a);
+    HIPCHK(hipGetLastError());
+    return MJX_OK;
+  }
+  float* q = tg + (size_t)N * dout;
+  std::vector<float*> A(net.nl + 1);
+  for (int l = 0; l <= net.nl; ++l) { A[l] = q; q += (size_t)batch * net.sz[l]; }
+  float* T = q; q += (size_t)batch * dout;
+  float* D[2] = {q, q + (size_t)batch * wmax};
+  auto blocks = [](int64_t e) { return dim3((unsigned)((e + 255) / 256 < 2048 ? (e + 255) / 256 : 2048)); };
+  for (int64_t s = 0; s < steps; ++s) {
+    hipLaunchKernelGGL(k_dl_gather, blocks((int64_t)batch * (din + dout)), dim3(256), 0, st, xn, tg, idx + s * batch, batch, din, dout, A[0], T);
+    for (int l = 0; l < net.nl; ++l)
+      hipLaunchKernelGGL(k_dl_fwd, blocks((int64_t)batch * net.sz[l + 1]), dim3(256), 0, st, A[l], batch, net.sz[l], params + net.oW[l],
+                         params + net.ob[l], net.sz[l + 1], A[l + 1], l + 1 < net.nl ? act : -1);
+    hipLaunchKernelGGL(k_dl_loss, dim3(1), dim3(1024), 0, st, A[net.nl], T, batch, dout, oaff, D[0], loss_out + s);
+    int cur = 0;
+    for (int l = net.nl - 1; l >= 0; --l) {
+      const int di = net.sz[l], dj = net.sz[l + 1];
+      if (l > 0)
+        hipLaunchKernelGGL(k_dl_bwd, blocks((int64_t)batch * di), dim3(256), 0, st, D[cur], batch, di, params + net.oW[l], dj, A[l], act, D[cur ^ 1]);
+      hipLaunchKernelGGL(k_dl_adam, blocks((int64_t)di * dj + dj), dim3(256), 0, st, D[cur], A[l], batch, di, dj, params, m, v, net.oW[l],
+                         step0 + s + 1, lr, wd);
+      cur ^= 1;
+    }
+  }
+  HIPCHK(hipGetLastError());
+  return MJX_OK;
+}
+
+int mjx_dyn_pred_error(const float* pred, int K, int64_t rows, int n, const float* s_next, const int64_t* seg_off, int nseg, double lim,
+                       float* err_out, int32_t* first_out, void* stream) {
+  if (!pred || !s_next || !seg_off || !err_out || !first_out || K <= 0 || rows < 0 || n <= 0 || nseg < 0) return fail(MJX_ERR_ARG, "bad arguments");
+  if (nseg == 0) return MJX_OK;
+  MJX_DEVICE_ENTRY();
+  hipLaunchKernelGGL(k_dyn_pred_err, dim3((unsigned)nseg), dim3(256), 0, (hipStream_t)stream, pred, K, rows, n, s_next, seg_off, lim, err_out, first_out);
   HIPCHK(hipGetLastError());
   return MJX_OK;
 }

@@ -33,6 +33,27 @@ def _aliases():
     }
 
 
+def _model_accel_aliases():
+    """model-based NPG (reference mjrl/algos/model_accel/): bound by install() next to _aliases(), kept apart from its returned
+    list, which names the core bindings"""
+    from .algos.model_accel import model_accel_npg, nn_dynamics, sampling
+    return {
+        "mjrl.algos.model_accel.nn_dynamics": nn_dynamics,          # WorldModel / DynamicsNet / RewardNet
+        "mjrl.algos.model_accel.sampling": sampling,                # policy_rollout / trajectory_rollout
+        "mjrl.algos.model_accel.model_accel_npg": model_accel_npg,  # ModelAccelNPG
+    }
+
+
+def _bind(ref_name, mod):
+    sys.modules[ref_name] = mod
+    parent, _, leaf = ref_name.rpartition(".")
+    if parent in sys.modules:                       # `import mjrl.algos.npg_cg as x` resolves through the parent's attribute
+        try:
+            setattr(sys.modules[parent], leaf, mod)
+        except Exception:                           # pragma: no cover
+            pass
+
+
 def install(verbose=False):
     """bind the reference's class-bearing module names to this package's modules -> the list of names bound.  mjrl itself
     must be importable (its utils / samplers / envs are used as they are)."""
@@ -43,14 +64,14 @@ def install(verbose=False):
     import mjrl.utils  # noqa: F401
     bound = []
     for ref_name, mod in _aliases().items():
-        sys.modules[ref_name] = mod
-        parent, _, leaf = ref_name.rpartition(".")
-        if parent in sys.modules:                       # `import mjrl.algos.npg_cg as x` resolves through the parent's attribute
-            try:
-                setattr(sys.modules[parent], leaf, mod)
-            except Exception:                           # pragma: no cover
-                pass
+        _bind(ref_name, mod)
         bound.append(ref_name)
+    try:
+        import mjrl.algos.model_accel  # noqa: F401  (the parent package, as above)
+    except ImportError:                                 # (a reference without model_accel: only the names themselves)
+        pass
+    for ref_name, mod in _model_accel_aliases().items():
+        _bind(ref_name, mod)
     from .utils import ingest
     ingest.tune_malloc()                                # a training process from here on (utils/ingest.py; MJX_MALLOC_TUNE=0 opts out)
     if verbose:

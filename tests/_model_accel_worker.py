@@ -1,0 +1,304 @@
+"""GPU worker for tests/test_gpu_model_accel.py: every model-based NPG check in ONE fresh process; prints one JSON line of
+measured errors (the test module compares them with its bars).  python tests/_model_accel_worker.py"""
+import ctypes
+import json
+import os
+import sys
+import types
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+import _dyn_oracle as O  # noqa: E402
+from mjrl_amd._lib import check, load, ptr  # noqa: E402
+from mjrl_amd.algos.model_accel import nn_dynamics as D  # noqa: E402
+
+R = {}
+dev = torch.device("cuda", 0)
+lib = load()
+G = np.load(os.path.join(ROOT, "tests", "golden", "model_accel.npz"))
+
+
+def ints(v):
+    return (ctypes.c_int * len(v))(*v)
+
+
+KEEP = []          # every uploaded block stays alive until the process ends: no temporary is freed before its kernel ran
+
+
+def t32(x):
+    t = torch.as_tensor(np.ascontiguousarray(x, np.float32)).to(dev)
+    KEEP.append(t)
+    return t
+
+
+def rel(a, b):
+    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
+    return float(np.max(np.abs(a - b)) / max(1.0, float(np.max(np.abs(b)))))
+
+
+def nparams(sizes):
+    return sum(sizes[i] * sizes[i + 1] + sizes[i + 1] for i in range(len(sizes) - 1))
+
+
+def rand_tr(rng, din, dout, zero_col=None):
+    tr = np.concatenate([rng.randn(din) * 0.3, rng.rand(din) + 0.5, rng.randn(dout) * 0.2, rng.rand(dout) + 0.3])
+    if zero_col is not None:
+        tr[2 * din + dout + zero_col] = 0.0
+    return tr.astype(np.float32)
+
+
+def stream():
+    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+# ---- forward: K = 3 members, every flag combination, ReLU / tanh, a masked column
+rng = np.random.RandomState(0)
+sizes, K, rows = [9, 32, 48, 7], 3, 77
+th = (rng.randn(K, nparams(sizes)) * 0.3).astype(np.float32)
+trs = np.stack([rand_tr(rng, 9, 7, zero_col=2) for _ in range(K)])
+x = (rng.randn(rows, 9) * 1.5).astype(np.float32)
+err = 0.0
+for act in (0, 1):
+    for flags in (0, 1, 3, 7, 5):
+        out = torch.empty((K, rows, 7), device=dev)
+        check(lib.mjx_dyn_forward(ptr(t32(x)), 0, rows, K, ints(sizes), 4, ptr(t32(th)), ptr(t32(trs)), act, flags, ptr(out), stream()))
+        o = out.cpu().numpy()
+        for k in range(K):
+            ref = O.forward(th[k], sizes, trs[k], x, act, flags)
+            for j in range(7):
+                err = max(err, rel(o[k][:, j], ref[:, j]))
+            if flags & 2:
+                assert np.all(o[k][:, 2] == (x[:, 2] if flags & 4 else 0.0))
+R["forward"] = err
+
+# ---- rollout: step by step against fp64 given the same noise
+n, m = 5, 2
+dsz, psz = [7, 24, 5], [5, 16, 16, 2]
+err = 0.0
+for H in (1, 6):
+    for N in (13, 8):
+        for mode in ("eval", "noisy_scalar", "noisy_vec", "actions"):
+            rng = np.random.RandomState(H * 100 + N)
+            Kr = 2
+            dth = (rng.randn(Kr, nparams(dsz)) * 0.3).astype(np.float32)
+            dtr = np.stack([rand_tr(rng, 7, 5, zero_col=1) for _ in range(Kr)])
+            pth = (rng.randn(nparams(psz) + m) * 0.4).astype(np.float32)
+            ptr_ = np.concatenate([rng.randn(n) * 0.2, rng.rand(n) + 0.5, rng.randn(m) * 0.1, rng.rand(m) + 0.5]).astype(np.float32)
+            s0 = rng.randn(N, n).astype(np.float32)
+            noise = None if mode in ("eval", "actions") else rng.randn(Kr, H, N, m).astype(np.float32)
+            acts = rng.randn(N, H, m).astype(np.float32) if mode == "actions" else None
+            if mode == "noisy_scalar":
+                bnd = [np.full(m, -0.5), np.full(m, 0.5), np.full(n, -1.5), np.full(n, 1.5)]
+            elif mode == "noisy_vec":
+                bnd = [-0.3 - rng.rand(m), 0.3 + rng.rand(m), -1.0 - rng.rand(n), 1.0 + rng.rand(n)]
+            elif mode == "eval":
+                bnd = [np.full(m, -100.0), np.full(m, 100.0), np.full(n, -100.0), np.full(n, 100.0)]
+            else:
+                bnd = None
+            bd = [t32(b) for b in bnd] if bnd is not None else [None] * 4
+            obs = torch.empty((Kr, N, H, n), device=dev); ao = torch.empty((Kr, N, H, m), device=dev)
+            if acts is None:
+                check(lib.mjx_model_rollout(ptr(t32(s0)), N, H, Kr, ints(psz), 4, ptr(t32(pth)), ptr(t32(ptr_)),
+                                            ptr(t32(noise)) if noise is not None else None, None, ints(dsz), 3, ptr(t32(dth)),
+                                            ptr(t32(dtr)), 0, 7, ptr(bd[0]), ptr(bd[1]), ptr(bd[2]), ptr(bd[3]), ptr(obs), ptr(ao), stream()))
+                ro, ra = O.rollout(s0, H, pth, psz, ptr_, noise, dth, dsz, dtr, 0, 7, [np.float32(b) for b in bnd])
+            else:
+                check(lib.mjx_model_rollout(ptr(t32(s0)), N, H, Kr, None, 0, None, None, None, ptr(t32(acts)), ints(dsz), 3,
+                                            ptr(t32(dth)), ptr(t32(dtr)), 0, 7, None, None, None, None, ptr(obs), ptr(ao), stream()))
+                ro, ra = O.rollout(s0, H, None, psz, None, None, dth, dsz, dtr, 0, 7, None, actions=acts)
+            err = max(err, rel(obs.cpu().numpy(), ro), rel(ao.cpu().numpy(), ra))
+R["rollout"] = err
+
+
+# ---- truncation reduction against NumPy (model_accel_npg.py:139-147)
+rng = np.random.RandomState(3)
+Kp, rows, n_ = 3, 300, 5
+pred = (rng.randn(Kp, rows, n_) * 0.1).astype(np.float32)
+sn = (rng.randn(rows, n_) * 0.1).astype(np.float32)
+off = np.array([0, 40, 40, 117, 190, 300], np.int64)
+lim = 0.02
+ev = torch.empty(rows, device=dev); fv = torch.empty(len(off) - 1, dtype=torch.int32, device=dev)
+offd = torch.as_tensor(off).to(dev)
+check(lib.mjx_dyn_pred_error(ptr(t32(pred)), Kp, rows, n_, ptr(t32(sn)), ptr(offd), len(off) - 1, lim, ptr(ev), ptr(fv), stream()))
+eref = np.max(np.mean((sn[None] - pred) ** 2, -1), 0)
+fref = []
+for g in range(len(off) - 1):
+    v = np.where(eref[off[g]:off[g + 1]] > lim)[0]
+    fref.append(int(v[0]) if len(v) else -1)
+R["pred_error"] = rel(ev.cpu().numpy(), eref)
+R["pred_error_first"] = [fv.cpu().numpy().tolist(), fref]
+
+# ---- fit: 1 and 10 Adam steps against fp64, both routes; the routes against each other
+def gpu_fit(theta, sizes, tr, x, y, idx, steps, batch, act, tmode, lr, wd, launches):
+    os.environ["MJX_DYN_FIT_LAUNCHES"] = "1" if launches else "0"
+    din, dout = sizes[0], sizes[-1]
+    P = t32(theta); mm = torch.zeros_like(P); vv = torch.zeros_like(P)
+    loss = torch.empty(steps, device=dev)
+    ix = torch.as_tensor(idx[:steps * batch].astype(np.int32)).to(dev)
+    check(lib.mjx_dyn_fit_adam(ptr(t32(x)), ptr(t32(y)), x.shape[0], ints(sizes), len(sizes), ptr(t32(np.concatenate([tr[:2 * din]]))),
+                               ptr(t32(tr[2 * din:])), tmode, act, ptr(P), ptr(mm), ptr(vv), 0,
+                               ptr(ix), steps, batch, lr, wd, ptr(loss), stream()))
+    os.environ.pop("MJX_DYN_FIT_LAUNCHES")
+    return P.cpu().numpy(), loss.cpu().numpy()
+
+
+err_p, err_l, err_routes = 0.0, 0.0, 0.0
+for sizes_, tmode, act, wd, batch in [([8, 32, 32, 6], 2, 0, 0.0, 16), ([8, 32, 32, 6], 1, 1, 1e-5, 64), ([14, 20, 1], 0, 0, 0.0, 32),
+                                      ([8, 96, 6], 2, 0, 1e-5, 64)]:
+    rng = np.random.RandomState(len(sizes_) + batch)
+    Nf, din, dout = 200, sizes_[0], sizes_[-1]
+    th = (rng.randn(nparams(sizes_)) * 0.3).astype(np.float32)
+    tr = rand_tr(rng, din, dout)
+    xf = rng.randn(Nf, din).astype(np.float32)
+    yf = rng.randn(Nf, dout).astype(np.float32)
+    idx = np.concatenate([rng.permutation(Nf)[:(Nf // batch) * batch] for _ in range(10)])
+    lr = 1e-3
+    for steps in (1, 10):
+        ref, _, _, rl = O.adam_steps(th, sizes_, tr, xf, yf, idx[:steps * batch], batch, act, tmode, lr, wd)
+        outs = []
+        for launches in (False, True):
+            p, l = gpu_fit(th, sizes_, tr, xf, yf, idx, steps, batch, act, tmode, lr, wd, launches)
+            err_p = max(err_p, float(np.max(np.abs(p - ref))) / lr)
+            err_l = max(err_l, rel(l, rl))
+            outs.append(p)
+        err_routes = max(err_routes, float(np.max(np.abs(outs[0] - outs[1]))) / lr)
+R["fit_params_over_lr"] = err_p
+R["fit_loss"] = err_l
+R["fit_routes_over_lr"] = err_routes
+
+
+# ---- WorldModel fits against the reference fixtures
+def data(N, n, m, seed, zero_col=True):
+    rng = np.random.RandomState(seed)
+    s = rng.randn(N, n).astype(np.float32)
+    a = rng.randn(N, m).astype(np.float32)
+    W = rng.randn(n + m, n).astype(np.float32) * 0.3
+    sp = (s + np.tanh(np.concatenate([s, a], 1) @ W) * 0.5).astype(np.float32)
+    if zero_col:
+        sp[:, 1] = s[:, 1]
+    return s, a, sp
+
+
+def params(net):
+    return np.concatenate([p.detach().cpu().numpy().ravel() for p in net.parameters()])
+
+
+n, m = 6, 2
+fit_err, fit_loss_err, ep_counts = 0.0, 0.0, []
+for i in range(5):
+    hid0, hid1, bs, wd, res, ep, N, ms = G["fit%d_cfg" % i]
+    s, a, sp = data(int(N), n, m, 10 + i)
+    np.random.seed(100 + i)
+    wm = D.WorldModel(n, m, hidden_size=(int(hid0), int(hid1)), seed=3 + i, fit_wd=float(wd), residual=bool(res))
+    p0 = params(wm.dynamics_net)
+    losses = wm.fit_dynamics(s, a, sp, int(bs), int(ep), max_steps=float(ms))
+    ref = G["fit%d_params" % i]
+    fit_err = max(fit_err, float(np.linalg.norm(params(wm.dynamics_net) - ref) / np.linalg.norm(ref - p0)))
+    fit_loss_err = max(fit_loss_err, rel(np.array(losses, np.float64), G["fit%d_losses" % i]),
+                       abs(float(wm.compute_loss(s, a, sp)) - float(G["fit%d_loss" % i])) / float(G["fit%d_loss" % i]),
+                       rel(wm.predict(s[:50], a[:50]), G["fit%d_pred" % i]))
+    ep_counts.append([len(losses), len(G["fit%d_losses" % i])])
+R["fixture_fit_params_rel_step"] = fit_err
+R["fixture_fit_losses"] = fit_loss_err
+R["fixture_fit_epoch_counts"] = ep_counts
+
+s, a, sp = data(300, n, m, 40, zero_col=False)
+r = (-np.sum(s ** 2, 1, keepdims=True) + 0.1 * a[:, :1]).astype(np.float32)
+np.random.seed(41)
+wm = D.WorldModel(n, m, learn_reward=True, hidden_size=(32, 32), seed=5)
+p0 = params(wm.reward_net)
+wm.fit_dynamics(s, a, sp, 32, 1)
+rl = wm.fit_reward(s, a, r, 32, 2, set_transformations=False)
+R["fixture_reward"] = max(rel(np.array(rl), G["rew_losses"]), rel(wm.reward(s[:40], a[:40]).detach().cpu().numpy(), G["rew_pred"]),
+                          float(np.linalg.norm(params(wm.reward_net) - G["rew_params"]) / np.linalg.norm(G["rew_params"] - p0)))
+
+# ---- policy_rollout against the reference fixtures (eval; noisy with bounds) and the streams after it
+from mjrl_amd.algos.model_accel import sampling as S  # noqa: E402
+from mjrl_amd.policies.gaussian_mlp import MLP  # noqa: E402
+
+
+class Env:
+    def __init__(self, n, m, horizon):
+        self.horizon = horizon
+        self.spec = types.SimpleNamespace(observation_dim=n, action_dim=m, horizon=horizon)
+        self.observation_dim, self.action_dim = n, m
+
+    def reset(self):
+        return np.zeros(self.spec.observation_dim)
+
+    def set_seed(self, seed=None):
+        pass
+
+
+env = Env(n, m, 9)
+pol = MLP(env.spec, hidden_sizes=(16, 16), seed=2, init_log_std=-0.5)
+s, a, sp = data(400, n, m, 50)
+wm = D.WorldModel(n, m, hidden_size=(32, 32), seed=6)
+np.random.seed(51)
+wm.fit_dynamics(s, a, sp, 32, 1)
+# the rollouts start from the REFERENCE's fitted model, so that they test the rollout alone
+k = 0
+for p in wm.dynamics_net.parameters():
+    p.data.copy_(torch.from_numpy(G["roll_dyn_params"][k:k + p.numel()].reshape(p.shape))); k += p.numel()
+tr = G["roll_dyn_tr"]
+wm.dynamics_net.set_transformations(*[torch.from_numpy(tr[o:o + l].copy()) for o, l in zip(np.cumsum([0, n, n, m, m, n]), [n, n, m, m, n, n])])
+init = G["roll_init"]
+r1 = S.policy_rollout(21, env, pol, wm, init_state=init, eval_mode=True, horizon=30)
+torch.manual_seed(53)
+r2 = S.policy_rollout(21, env, pol, wm, init_state=list(init), eval_mode=False, horizon=30, a_min=-0.4, a_max=0.4,
+                      s_min=torch.full((n,), -2.0), s_max=torch.full((n,), 2.5))
+R["fixture_rollout_eval"] = max(rel(r1["observations"], G["roll_eval_obs"]), rel(r1["actions"], G["roll_eval_act"]))
+R["fixture_rollout_noisy"] = max(rel(r2["observations"], G["roll_noisy_obs"]), rel(r2["actions"], G["roll_noisy_act"]))
+R["fixture_rollout_shapes"] = [list(r2["observations"].shape), list(G["roll_noisy_obs"].shape)]
+R["streams_after_rollout"] = [np.random.rand(), torch.rand(1).item(), *G["rng_after_rollout"].tolist()]
+
+# ---- one ModelAccelNPG.train_step against its fixture
+from mjrl_amd.algos.model_accel.model_accel_npg import ModelAccelNPG  # noqa: E402
+from mjrl_amd.baselines.linear_baseline import LinearBaseline  # noqa: E402
+
+models = []
+for k in range(3):
+    wm = D.WorldModel(n, m, hidden_size=(32, 32), seed=70 + k)
+    th, tr = G["ts_model%d" % k], G["ts_model%d_tr" % k]
+    ws, o = [], 0
+    for p in wm.dynamics_net.parameters():
+        ws.append(torch.from_numpy(th[o:o + p.numel()].reshape(p.shape).copy())); o += p.numel()
+    trs = [torch.from_numpy(tr[o:o + l].copy()) for o, l in zip(np.cumsum([0, n, n, m, m, n]), [n, n, m, m, n, n])]
+    wm.dynamics_net.set_params(dict(weights=ws, transforms=trs))
+    models.append(wm)
+env = Env(n, m, 12)
+pol = MLP(env.spec, hidden_sizes=(8, 8), seed=4, init_log_std=-0.5)
+pol0 = pol.get_param_values()
+
+
+def reward_function(paths):
+    paths["rewards"] = -np.sum(paths["observations"] ** 2, -1) - 0.1 * np.sum(paths["actions"] ** 2, -1)
+    return paths
+
+
+agent = ModelAccelNPG(learned_model=models, env=env, policy=pol, baseline=LinearBaseline(env.spec), normalized_step_size=0.05,
+                      seed=9, save_logs=True, reward_function=reward_function)
+lens = []
+fit0 = agent.baseline.fit
+
+
+def fit(paths, return_errors=False):
+    lens.extend(len(p["rewards"]) for p in paths)
+    return fit0(paths, return_errors=return_errors)
+
+
+agent.baseline.fit = fit
+torch.manual_seed(81)
+stats = agent.train_step(40, env=env, init_states=[x for x in G["ts_init"]], truncate_lim=float(G["ts_trunc"]), truncate_reward=-1.0)
+R["train_step_pol0"] = rel(pol0, G["ts_pol0"])
+R["train_step_stats"] = rel(np.array(stats, np.float64), G["ts_stats"])
+step, rstep = pol.get_param_values().astype(np.float64) - pol0, G["ts_pol1"].astype(np.float64) - G["ts_pol0"]
+R["train_step_policy_rel_l2"] = float(np.linalg.norm(step - rstep) / np.linalg.norm(rstep))
+R["train_step_lens_equal"] = bool(np.array_equal(np.array(lens), G["ts_lens"]))
+R["train_step_keys"] = [sorted(agent.logger.log.keys()), sorted(G["ts_keys"].tolist())]
+R["train_step_seed"] = [int(agent.seed), int(G["ts_seed"])]
+print("RESULT " + json.dumps(R))

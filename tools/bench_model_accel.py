@@ -1,0 +1,125 @@
+#!/usr/bin/env python
+"""Model-based NPG timings: fit time per Adam step at (64, 64) and (256, 256), minibatch 16 and 64 (persistent route and the
+launch route), one policy_rollout over K = 4 models, N = 250, H = 50, and one ModelAccelNPG.train_step (3 models, 250 paths,
+horizon 25) -- on the MI355X (default) or, with --reference, the unmodified reference on the CPU for the same seeded inputs
+(build box only: it imports the reference through tests/golden/_ref_import.py).  Prints one JSON line.
+    python tools/bench_model_accel.py [--reference]"""
+import json
+import os
+import sys
+import time
+import types
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+REF = "--reference" in sys.argv
+if REF:
+    sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
+    import _ref_import
+    _ref_import.install()
+    sys.modules.setdefault("mjrl.envs", types.ModuleType("mjrl.envs"))
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+if REF:
+    from mjrl.algos.model_accel import nn_dynamics as D, sampling as S
+    from mjrl.algos.model_accel.model_accel_npg import ModelAccelNPG
+    from mjrl.baselines.linear_baseline import LinearBaseline
+    from mjrl.policies.gaussian_mlp import MLP
+else:
+    from mjrl_amd.algos.model_accel import nn_dynamics as D, sampling as S
+    from mjrl_amd.algos.model_accel.model_accel_npg import ModelAccelNPG
+    from mjrl_amd.baselines.linear_baseline import LinearBaseline
+    from mjrl_amd.policies.gaussian_mlp import MLP
+
+n, m = 11, 2                         # the reference's reacher config shapes (run_experiments/configs/reacher.txt)
+
+
+def sync():
+    if not REF:
+        torch.cuda.synchronize()
+
+
+def data(N, seed):
+    rng = np.random.RandomState(seed)
+    s = rng.randn(N, n).astype(np.float32)
+    a = rng.randn(N, m).astype(np.float32)
+    W = rng.randn(n + m, n).astype(np.float32) * 0.3
+    return s, a, (s + np.tanh(np.concatenate([s, a], 1) @ W) * 0.5).astype(np.float32)
+
+
+class Env:
+    def __init__(self, horizon):
+        self.horizon = horizon
+        self.spec = types.SimpleNamespace(observation_dim=n, action_dim=m, horizon=horizon)
+
+    def reset(self):
+        return np.zeros(n)
+
+    def set_seed(self, seed=None):
+        pass
+
+
+if REF:
+    from mjrl.utils.gym_env import GymEnv
+    Env = type("Env", (GymEnv,), {"__init__": Env.__init__, "horizon": None, "spec": None, "reset": Env.reset, "set_seed": Env.set_seed})
+
+out = {"side": "reference_cpu" if REF else "mi355x"}
+routes = [None] if REF else ["0", "1"]
+for hid in [(64, 64), (256, 256)]:
+    for bs in (16, 64):
+        for route in routes:
+            if route is not None:
+                os.environ["MJX_DYN_FIT_LAUNCHES"] = route
+            N = bs * (100 if REF else 400)
+            s, a, sp = data(N, 1)
+            np.random.seed(0)
+            wm = D.WorldModel(n, m, hidden_size=hid, seed=1)
+            wm.fit_dynamics(s[:bs * 4], a[:bs * 4], sp[:bs * 4], bs, 1)          # warm-up
+            sync()
+            t0 = time.perf_counter()
+            wm.fit_dynamics(s, a, sp, bs, 1)
+            sync()
+            key = "fit_us_per_step_%dx%d_mb%d%s" % (hid[0], hid[1], bs, "" if route is None else ("_launch" if route == "1" else ""))
+            out[key] = round((time.perf_counter() - t0) / (N // bs) * 1e6, 2)
+os.environ.pop("MJX_DYN_FIT_LAUNCHES", None)
+
+env = Env(50)
+pol = MLP(env.spec, hidden_sizes=(64, 64), seed=2)
+models = [D.WorldModel(n, m, hidden_size=(256, 256), seed=10 + k) for k in range(4)]
+init = np.random.RandomState(3).randn(250, n).astype(np.float32)
+S.policy_rollout(250, env, pol, models[0], init_state=init, eval_mode=False, horizon=2)
+sync()
+t0 = time.perf_counter()
+for mdl in models:
+    S.policy_rollout(250, env, pol, mdl, init_state=init, eval_mode=False, horizon=50)
+sync()
+out["rollout_ms_K4_N250_H50_per_model_calls"] = round((time.perf_counter() - t0) * 1e3, 2)
+if not REF:
+    noise = S.draw_rollout_noise(4, 50, 250, m)
+    sync()
+    t0 = time.perf_counter()
+    S.rollout_models(models, pol, init, 50, noise)
+    sync()
+    out["rollout_ms_K4_N250_H50_one_launch"] = round((time.perf_counter() - t0) * 1e3, 2)
+
+env = Env(25)
+pol = MLP(env.spec, hidden_sizes=(64, 64), seed=4)
+models = [D.WorldModel(n, m, hidden_size=(64, 64), seed=20 + k) for k in range(3)]
+
+
+def reward_function(paths):
+    paths["rewards"] = -np.sum(paths["observations"] ** 2, -1)
+    return paths
+
+
+agent = ModelAccelNPG(learned_model=models, env=env, policy=pol, baseline=LinearBaseline(env.spec), normalized_step_size=0.05,
+                      seed=0, save_logs=True, reward_function=reward_function)
+init = [x for x in np.random.RandomState(5).randn(250, n)]
+agent.train_step(250, env=env, init_states=init, truncate_lim=1.0)     # warm-up
+sync()
+t0 = time.perf_counter()
+agent.train_step(250, env=env, init_states=init, truncate_lim=1.0)
+sync()
+out["train_step_ms_3models_250paths_H25"] = round((time.perf_counter() - t0) * 1e3, 2)
+print(json.dumps(out))
