@@ -419,14 +419,16 @@ int mjx_model_rollout(const float* s0, int64_t N, int H, int K, const int* pol_s
  * (y - x[:, :d_out] - out_shift) / (out_scale + 1e-8).  idx: steps x batch row indices (per epoch the first
  * (N // batch) x batch entries of np.random.permutation(N), drawn by the caller).  params / m / v updated in place,
  * step0 = Adam steps already taken; loss_out[s] = the minibatch loss of step s (device fp32).  Hidden widths <= 128
- * and batch <= 64 run as ONE persistent launch while the minibatch fits in LDS (csrc/dynamics.h), the rest one launch
- * per layer and phase; MJX_DYN_FIT_LAUNCHES=1 forces the latter.  Uses per-host-thread scratch. */
+ * and batch <= 64 run as ONE persistent launch while the minibatch and the kernel's static LDS fit in 160 KiB
+ * (csrc/dynamics.h), the rest one launch per layer and phase; MJX_DYN_FIT_LAUNCHES=1 forces the latter.  Uses
+ * per-host-thread scratch. */
 int mjx_dyn_fit_adam(const float* x, const float* y, int64_t N, const int* sizes, int n_sizes, const float* in_tr,
                      const float* out_tr, int target_mode, int act, float* params, float* m, float* v, int64_t step0,
                      const int32_t* idx, int64_t steps, int batch, float lr, float wd, float* loss_out, void* stream);
 /* ensemble-disagreement truncation (model_accel_npg.py:137-155): pred = K x rows x n model predictions, s_next the
- * rows' next states; err_out[r] = max_k mean_j (s_next - pred)^2; segment g = rows [seg_off[g], seg_off[g+1]) (one
- * path); first_out[g] = the first row of the segment whose error exceeds lim, -1 if none. */
+ * rows' next states; err_out[r] = max_k mean_j (s_next - pred)^2, NaN if any member's is NaN (np.maximum);
+ * segment g = rows [seg_off[g], seg_off[g+1]) (one path); first_out[g] = the first row of the segment whose error
+ * exceeds lim (a NaN error does not), -1 if none. */
 int mjx_dyn_pred_error(const float* pred, int K, int64_t rows, int n, const float* s_next, const int64_t* seg_off,
                        int nseg, double lim, float* err_out, int32_t* first_out, void* stream);
 

@@ -25,9 +25,9 @@
 // Fit LDS budget (k_dyn_fit, 1024 threads, weights and Adam moments in global memory / L2, every one owned by one thread for
 // the update): the minibatch's activations of every layer, its targets and two delta blocks, B x (d_in + sum(h) + 2 d_out +
 // 2 max(h, d_out)) floats -- (64, 64) at d_in 30, d_out 20, B 64: 64 KiB.  Shapes up to hidden 128 and batch 64 take this route
-// while that budget fits in 160 KiB; the rest (256 x 256, RewardNet's 100 x 100 at large inputs) run k_dl_*: per Adam step one
-// gather, one launch per layer forward, a loss head, one backward launch per hidden layer and one gradient + Adam launch per
-// layer, activations in a global scratch block.
+// while that budget plus the kernel's 128 B of static LDS fits in 160 KiB; the rest (256 x 256, RewardNet's 100 x 100 at large
+// inputs) run k_dl_*: per Adam step one gather, one launch per layer forward, a loss head, one backward launch per hidden layer
+// and one gradient + Adam launch per layer, activations in a global scratch block.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -414,7 +414,8 @@ __global__ void k_dl_adam(const float* __restrict__ dz, const float* __restrict_
 }
 
 // ---- (d) truncation: err[r] = max_k mean_j (s_next[r][j] - pred[k][r][j])^2 over the rows of segment g = [off[g], off[g+1]);
-// first[g] = index (within the segment) of the first row with err > lim, -1 if none.  One workgroup per segment.
+// first[g] = index (within the segment) of the first row with err > lim, -1 if none.  One workgroup per segment.  As the
+// reference's np.maximum, a row where any member's error is NaN has a NaN error, and NaN > lim is false.
 __global__ __launch_bounds__(256) void k_dyn_pred_err(const float* __restrict__ pred, int K, int64_t rows, int n,
                                                       const float* __restrict__ s_next, const int64_t* __restrict__ off, double lim,
                                                       float* __restrict__ err, int32_t* __restrict__ first) {
@@ -429,7 +430,7 @@ __global__ __launch_bounds__(256) void k_dyn_pred_err(const float* __restrict__ 
       double s = 0.0;
       for (int j = 0; j < n; ++j) { const float d = s_next[r * n + j] - pred[((int64_t)k * rows + r) * n + j]; s += (double)(d * d); }
       const float mk = (float)(s / n);
-      e = k == 0 ? mk : fmaxf(e, mk);
+      if (k == 0 || mk > e || mk != mk) e = mk;       // np.maximum: a NaN member makes the row NaN (fmaxf would drop it)
     }
     err[r] = e;
     if ((double)e > lim) atomicMin((unsigned long long*)&hit, (unsigned long long)r);

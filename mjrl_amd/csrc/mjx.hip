@@ -746,9 +746,24 @@ int dyn_net(const int* sizes, int n_sizes, DynNet& net) {
   if (!sizes || !net.init(sizes, n_sizes)) return fail(MJX_ERR_ARG, "bad layer sizes (2 .. %d entries, all > 0)", DYN_MAXL + 1);
   return MJX_OK;
 }
+// a kernel's static LDS (its __shared__ arrays: k_dyn_fit's reduction block is 128 B); a workgroup gets static + dynamic bytes
+// out of the 160 KiB, so both count against the limit
+int dyn_static_lds(const void* kern, size_t& bytes) {
+  static thread_local std::vector<std::pair<const void*, size_t>> known;
+  for (const auto& e : known)
+    if (e.first == kern) { bytes = e.second; return MJX_OK; }
+  hipFuncAttributes fa{};
+  HIPCHK(hipFuncGetAttributes(&fa, kern));
+  known.emplace_back(kern, fa.sharedSizeBytes);
+  bytes = fa.sharedSizeBytes;
+  return MJX_OK;
+}
+bool dyn_lds_fits(size_t static_bytes, size_t bytes) { return static_bytes + bytes <= (size_t)160 * 1024; }
 int dyn_lds_limit(const void* kern, size_t bytes) {
-  if (bytes > (size_t)160 * 1024) return fail(MJX_ERR_UNSUPPORTED, "needs %zu bytes of LDS (> 160 KiB)", bytes);
-  if (bytes > 64 * 1024) HIPCHK(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+  size_t st = 0;
+  if (int rc = dyn_static_lds(kern, st)) return rc;
+  if (!dyn_lds_fits(st, bytes)) return fail(MJX_ERR_UNSUPPORTED, "needs %zu + %zu static bytes of LDS (> 160 KiB)", bytes, st);
+  if (st + bytes > 64 * 1024) HIPCHK(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
   return MJX_OK;
 }
 }  // namespace
@@ -832,7 +847,9 @@ int mjx_dyn_fit_adam(const float* x, const float* y, int64_t N, const int* sizes
   bool narrow = true;
   for (int l = 1; l < net.nl; ++l) narrow = narrow && net.sz[l] <= 128;
   const size_t fbytes = dyn_fit_lds_bytes(net, batch);
-  if (!(force && force[0] == '1') && narrow && batch <= 64 && fbytes <= (size_t)160 * 1024) {
+  size_t fstatic = 0;
+  if (int rc = dyn_static_lds((const void*)k_dyn_fit, fstatic)) return rc;
+  if (!(force && force[0] == '1') && narrow && batch <= 64 && dyn_lds_fits(fstatic, fbytes)) {
     if (int rc = dyn_lds_limit((const void*)k_dyn_fit, fbytes)) return rc;
     DynFitArgs a{net, xn, tg, idx, steps, batch, params, m, v, step0, lr, wd, act, oaff, loss_out};
     hipLaunchKernelGGL(k_dyn_fit, dim3(1), dim3(1024), fbytes, st, a);

@@ -1,6 +1,7 @@
 """fp64 NumPy oracle for the model-based NPG operations (csrc/dynamics.h): DynamicsNet / RewardNet forward
-(reference nn_dynamics.py:230-245, 313-328), torch.optim.Adam steps of fit_model (:344-385) and a learned-model rollout given
-its noise (sampling.py:16-89, enforce_tensor_bounds :286-315)."""
+(reference nn_dynamics.py:230-245, 313-328), torch.optim.Adam steps of fit_model (:344-385), a learned-model rollout given
+its noise (sampling.py:16-89, enforce_tensor_bounds :286-315), its single steps for a teacher-forced check, and the
+ensemble-disagreement truncation (model_accel_npg.py:139-150)."""
 import numpy as np
 
 AFF, MASK, RES = 1, 2, 4
@@ -40,9 +41,10 @@ def forward(theta, sizes, tr, x, act, flags, keep=False):
     return (h, hs) if keep else h
 
 
-def adam_steps(theta, sizes, tr, x, y, idx, batch, act, tmode, lr, wd, m=None, v=None, t0=0):
+def adam_steps(theta, sizes, tr, x, y, idx, batch, act, tmode, lr, wd, m=None, v=None, t0=0, g_first=None):
     """fit_model's Adam steps in fp64: tmode 0 = loss through the output affine on raw y, 1 = (y - out_shift) /
-    (out_scale + 1e-8), 2 = residual targets.  -> (theta, m, v, per-step losses)"""
+    (out_scale + 1e-8), 2 = residual targets.  -> (theta, m, v, per-step losses).  g_first: an array that takes |gradient|
+    (weight decay included) of the first step"""
     theta = np.array(theta, np.float64)
     x, y, tr = np.asarray(x, np.float64), np.asarray(y, np.float64).reshape(len(x), -1), np.asarray(tr, np.float64)
     din, dout = sizes[0], sizes[-1]
@@ -77,10 +79,66 @@ def adam_steps(theta, sizes, tr, x, y, idx, batch, act, tmode, lr, wd, m=None, v
                 dz = da * ((1.0 - hs[l] ** 2) if act == 1 else (hs[l] > 0))
         t = t0 + s + 1
         g = g + wd * theta
+        if g_first is not None and s == 0:
+            g_first[...] = np.abs(g)
         m = 0.9 * m + 0.1 * g
         v = 0.999 * v + 0.001 * g * g
         theta = theta - lr / (1 - 0.9 ** t) * m / (np.sqrt(v) / np.sqrt(1 - 0.999 ** t) + 1e-8)
     return theta, m, v, np.array(losses)
+
+
+def policy_mean(pol_theta, pol_sizes, pol_tr, s):
+    """the tanh FCNetwork's mean (fc_network.py:39-52) of states s (rows x n) -> (mean (rows x m), log_std (m));
+    pol_theta = [W1, b1, ..., W_out, b_out, log_std], pol_tr = [in_shift n, in_scale n, out_shift m, out_scale m]"""
+    n, m = pol_sizes[0], pol_sizes[-1]
+    pt, ptr = np.asarray(pol_theta, np.float64), np.asarray(pol_tr, np.float64)
+    P = pt.size - m
+    Ws, bs = unflatten(pt[:P], pol_sizes)
+    h = (np.asarray(s, np.float64) - ptr[:n]) / (ptr[n:2 * n] + 1e-8)
+    for i, (W, b) in enumerate(zip(Ws, bs)):
+        h = h @ W.T + b
+        if i < len(Ws) - 1:
+            h = np.tanh(h)
+    return h * ptr[2 * n + m:] + ptr[2 * n:2 * n + m], pt[P:]
+
+
+def clamp(x, lo, hi):
+    """torch.max(torch.min(x, hi), lo) (sampling.py:315)"""
+    return np.maximum(np.minimum(x, hi), lo)
+
+
+def rollout_action(s, pol_theta, pol_sizes, pol_tr, noise=None, bounds=None):
+    """one step's action from the states s: clamp(policy_mean(s) + noise * exp(log_std))"""
+    a, ls = policy_mean(pol_theta, pol_sizes, pol_tr, s)
+    if noise is not None:
+        a = a + np.asarray(noise, np.float64) * np.exp(ls)
+    return clamp(a, bounds[0], bounds[1]) if bounds is not None else a
+
+
+def rollout_next(s, a, dyn_theta, dyn_sizes, dyn_tr, act, flags, bounds=None):
+    """one step's next states: clamp(f([s, a]))"""
+    x = np.concatenate([np.asarray(s, np.float64), np.asarray(a, np.float64)], -1)
+    s = forward(dyn_theta, dyn_sizes, dyn_tr, x, act, flags)
+    return clamp(s, bounds[2], bounds[3]) if bounds is not None else s
+
+
+def pred_error(pred, s_next, off, lim):
+    """model_accel_npg.py:139-150 as written, per segment [off[g], off[g+1]) of rows: pred_err starts from zeros and takes
+    np.maximum with each model's mean squared error in model order; -> (pred_err per row, first violating row per segment or
+    -1).  pred: K x rows x n, s_next: rows x n, both taken as they are (fp32 values in fp64)."""
+    pred, s_next = np.asarray(pred, np.float64), np.asarray(s_next, np.float64)
+    errs, first = np.zeros(s_next.shape[0]), []
+    with np.errstate(invalid="ignore", over="ignore"):
+        for g in range(len(off) - 1):
+            a0, a1 = int(off[g]), int(off[g + 1])
+            pred_err = np.zeros(a1 - a0)
+            for k in range(pred.shape[0]):
+                model_err = np.mean((s_next[a0:a1] - pred[k, a0:a1]) ** 2, axis=-1)
+                pred_err = np.maximum(pred_err, model_err)
+            violations = np.where(pred_err > lim)[0]
+            errs[a0:a1] = pred_err
+            first.append(int(violations[0]) if len(violations) else -1)
+    return errs, np.array(first, np.int64)
 
 
 def rollout(s0, H, pol_theta, pol_sizes, pol_tr, noise, dyn_thetas, dyn_sizes, dyn_trs, act, flags, bounds=None, actions=None):
