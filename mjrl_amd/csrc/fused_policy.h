@@ -234,6 +234,47 @@ __device__ __forceinline__ void pk_mul_1mh2_far(f32x16& t, const f32x16& h) {
   }
 }
 
+// bf16x3 (the cached Fisher-vector product's 64x64 products on v_mfma_f32_32x32x16_bf16): x = hi + mid + lo EXACTLY, each piece a
+// bf16 -- hi = x with the low 16 bits cleared, r = x - hi (exact), mid = r truncated the same way, lo = r - mid (exact; at most 8
+// significant bits, so a bf16 as it stands).  The upper halves of x, r, lo ARE the three bf16 pieces: two values per register by
+// one v_perm_b32.  Only single-issue 4-cycle instructions (no packed fp32: beside MFMAs each costs +22-26 cycles).  Of the 9 piece
+// products the 6 with i + j <= 2 are formed (tools/probe_split_error.py: FVP / CG-10 at native-fp32 distance from fp64).
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+#define MJX_MFMA_BF16(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, (a)), __builtin_bit_cast(bf16x8, (b)), (c), 0, 0, 0)
+struct Pc3 { u32x4 p[3]; };                      // hi, mid, lo: 8 bf16 each (one operand of v_mfma_f32_32x32x16_bf16)
+__device__ __forceinline__ Pc3 split3(const float (&x)[8]) {
+  Pc3 o;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const uint32_t ua = __float_as_uint(x[2 * k]), ub = __float_as_uint(x[2 * k + 1]);
+    const float ra = x[2 * k] - __uint_as_float(ua & 0xffff0000u), rb = x[2 * k + 1] - __uint_as_float(ub & 0xffff0000u);
+    const uint32_t va = __float_as_uint(ra), vb = __float_as_uint(rb);
+    const float la = ra - __uint_as_float(va & 0xffff0000u), lb = rb - __uint_as_float(vb & 0xffff0000u);
+    o.p[0][k] = __builtin_amdgcn_perm(ub, ua, 0x07060302u);
+    o.p[1][k] = __builtin_amdgcn_perm(vb, va, 0x07060302u);
+    o.p[2][k] = __builtin_amdgcn_perm(__float_as_uint(lb), __float_as_uint(la), 0x07060302u);
+  }
+  return o;
+}
+// the pieces of registers 8 s .. 8 s + 7 of a 32x32 accumulator (K-step s of the next layer's operand)
+__device__ __forceinline__ Pc3 split3_of(const f32x16& v, int s) {
+  float x[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) x[i] = v[8 * s + i];
+  return split3(x);
+}
+// acc += a * b over the six piece products, the small ones first
+__device__ __forceinline__ f32x16 mfma_bf3(const Pc3& a, const Pc3& b, f32x16 c) {
+  c = MJX_MFMA_BF16(a.p[2], b.p[0], c);
+  c = MJX_MFMA_BF16(a.p[0], b.p[2], c);
+  c = MJX_MFMA_BF16(a.p[1], b.p[1], c);
+  c = MJX_MFMA_BF16(a.p[1], b.p[0], c);
+  c = MJX_MFMA_BF16(a.p[0], b.p[1], c);
+  c = MJX_MFMA_BF16(a.p[0], b.p[0], c);
+  return c;
+}
+
 // compile-time loop: f(std::integral_constant<int, 0>{}), ..., f(std::integral_constant<int, N - 1>{})
 template <int N, int I = 0, class F>
 __device__ __forceinline__ void static_for(F&& f) {
@@ -261,17 +302,22 @@ struct FusedLayout {
   // eval_only: the layout of MODE_EVAL launches -- no backward pass, so a wave's scratch is just the raw image of its
   // observation tile (3.2 KB instead of 25 KB at HalfCheetah shapes); the workgroup then needs ~64 KB and TWO of them
   // share a CU, i.e. two waves per SIMD: one wave's tanh / likelihood VALU work runs under the other's MFMAs
-  __host__ __device__ explicit FusedLayout(int n, bool eval_only = false) {
+  // bf3: the cached Fisher-vector product on bf16x3 MFMAs (k_fused<..., BF3 = true>).  After its prologue it reads no fp32 W2 of
+  // either slot: the prologue overwrites each slot's W2 region with that matrix's bf16 pieces (F2_IMG floats: V2 in R2's operand
+  // order in slot B, W2^T in R8's in slot A), so the region is padded to hold them.  The raw observation image xs is never read
+  // by the cached schedule (x~ comes from the cache) and has no room in it.
+  static constexpr int F2_IMG = 3 * H1 * H2 / 2;
+  __host__ __device__ explicit FusedLayout(int n, bool eval_only = false, bool bf3 = false) {
     NP = (n + 1 + 3) & ~3;
     S1 = NP + 2;
     oW1 = 0;
     oW2 = oW1 + H1 * S1;
-    oW3 = oW2 + H2 * S2;                        // [MP][S3]
+    oW3 = oW2 + ((bf3 && H2 * S2 < F2_IMG) ? F2_IMG : H2 * S2);   // [MP][S3]
     oB2 = oW3 + MP * S3;
     oB3 = oB2 + H2;
     SLOT = ((oB3 + MP + 3) / 4) * 4;
     oXS = 0;                                    // raw image of the tile: 32*n floats (+ float4 slack)
-    oXT = ((oXS + 32 * n + 4 * 64 + 3) / 4) * 4; // [NP][ST]
+    oXT = bf3 ? 0 : ((oXS + 32 * n + 4 * 64 + 3) / 4) * 4; // [NP][ST]
     oD3 = oXT + NP * ST;                        // [MP][ST]
     oBA = oD3 + MP * ST;                        // [HM][ST]
     oBB = oBA + HM * ST;                        // [HM][ST]
@@ -344,7 +390,7 @@ struct RawSlab {
   }
 };
 
-template <int H1, int H2, int NT1, int MP, int MODE, bool DBG = false, int NPC = 0, bool CACHED = false>
+template <int H1, int H2, int NT1, int MP, int MODE, bool DBG = false, int NPC = 0, bool CACHED = false, bool BF3 = false>
 __global__ __launch_bounds__(256, (MODE == MODE_EVAL && !DBG && MP <= 8) ? 2 : 1) void k_fused(FusedArgs A) {
   using LT = FusedLayout<H1, H2, NT1, MP>;
   constexpr int MT1 = LT::MT1, MT2 = LT::MT2, S2 = LT::S2, S3 = LT::S3, ST = LT::ST;
@@ -361,7 +407,10 @@ __global__ __launch_bounds__(256, (MODE == MODE_EVAL && !DBG && MP <= 8) ? 2 : 1
   // (instances with a compile-time feature count lay their LDS out for the widest observation they serve, NPC - 1 features:
   //  every offset is then a compile-time constant and folds into the DS instructions' immediate fields instead of costing a
   //  vector add per access -- vector-ALU instructions are not hidden by fp32 MFMAs, see the cached Fisher-vector product)
-  const LT L(NPC ? NPC - 1 : n, EV2);
+  // bf16x3 cached Fisher-vector product (64 x 64): R3 (t2 += W2 t1) and R8 (delta1 = W2^T delta2) on v_mfma_f32_32x32x16_bf16
+  constexpr bool XBF3 = (MODE == MODE_FVP) && CACHED && BF3;
+  static_assert(!BF3 || (CACHED && MODE == MODE_FVP && H1 == 64 && H2 == 64), "bf16x3: the cached 64 x 64 Fisher-vector product only");
+  const LT L(NPC ? NPC - 1 : n, EV2, XBF3);
   const int NP = NPC ? NPC : L.NP;                // compile-time when the variant is specialised for the obs dim
   const int S1 = NP + 2;
   const FlatOff fo(n, m, H1, H2);
@@ -523,6 +572,48 @@ __global__ __launch_bounds__(256, (MODE == MODE_EVAL && !DBG && MP <= 8) ? 2 : 1
   if (MODE == MODE_EVAL && A.ocache) {
     use_oc = (lds[L.oWAVES] == 0.0f);
     use_xi = use_oc && NPC != 0 && A.hcache != nullptr && (lds[L.oWAVES + 1] == 0.0f);
+    __syncthreads();
+  }
+  // bf16x3: the weight pieces are built once per launch.  R3's A operands (W2's pieces in the k-permuted order of the fp32
+  // fragments: lane (j, hi), element i of K-step s holds W2[32 mt + j][32 kb + unit_of(8 s + i, hi)]) go to registers; R2's A
+  // operands (V2's pieces, the same order) and R8's B operands (W2^T's pieces: W2[32 kb + unit_of(8 s + i, hi)][32 nt + j]) to
+  // images [piece][block][lane][8 bf16] over slot B's / slot A's W2 region, which the bf16x3 schedule no longer reads (block =
+  // (mt 2 + kb) 2 + s, resp. (nt 2 + kb) 2 + s): one conflict-free ds_read_b128 per operand
+  Pc3 w3p[XBF3 ? MT2 : 1][XBF3 ? MT1 : 1][2];
+  if constexpr (XBF3) {
+#pragma unroll
+    for (int mt = 0; mt < MT2; ++mt)
+#pragma unroll
+      for (int kb = 0; kb < MT1; ++kb)
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+          const float* row = &slotA[L.oW2 + (32 * mt + j) * S2 + 32 * kb + 16 * s + 4 * hi];
+          const f32x4 a = *(const f32x4*)row, b = *(const f32x4*)(row + 8);
+          const float x[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+          w3p[mt][kb][s] = split3(x);
+        }
+    Pc3 ip[2], vp[2];                           // this thread's operand blocks: blk = 4 e + wave, lane `lane`
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+      const int blk = 4 * e + wave, b2 = blk >> 2, kb = (blk >> 1) & 1, s = blk & 1;
+      float x[8];
+#pragma unroll
+      for (int i = 0; i < 8; ++i) x[i] = slotA[L.oW2 + (32 * kb + 16 * s + 8 * (i >> 2) + 4 * hi + (i & 3)) * S2 + 32 * b2 + j];
+      ip[e] = split3(x);
+      const float* row = &slotB[L.oW2 + (32 * b2 + j) * S2 + 32 * kb + 16 * s + 4 * hi];
+      const f32x4 a = *(const f32x4*)row, b = *(const f32x4*)(row + 8);
+      const float y[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+      vp[e] = split3(y);
+    }
+    __syncthreads();                            // every fp32 W2 / V2 value has been read
+    static_assert(LT::F2_IMG == 3 * 8 * 64 * 4, "image: 3 pieces x 8 operand blocks x 64 lanes x 4 dwords");
+#pragma unroll
+    for (int e = 0; e < 2; ++e)
+#pragma unroll
+      for (int p = 0; p < 3; ++p) {
+        *(u32x4*)&slotA[L.oW2 + ((p * 8 + 4 * e + wave) * 64 + lane) * 4] = ip[e].p[p];
+        *(u32x4*)&slotB[L.oW2 + ((p * 8 + 4 * e + wave) * 64 + lane) * 4] = vp[e].p[p];
+      }
     __syncthreads();
   }
   // FVP epilogue constants as wave-uniform scalars (no LDS round trip on the d3 critical path)
@@ -723,8 +814,8 @@ __global__ __launch_bounds__(256, (MODE == MODE_EVAL && !DBG && MP <= 8) ? 2 : 1
     for (int g = 0; g < (NPC / 4 + 1) / 2; ++g) pinX[g] = lds_pin(&xT[(8 * g + 2 * hi) * ST + j]);
   }
   // ... and in the k-groups of W2's rows the delta1 phase reads (rows 8 g + 4 hi .. + 3 of the NEW parameters' slot, columns j, 32 + j)
-  uint32_t pinW[PINNED ? 4 * MT2 : 1];
-  if constexpr (PINNED) {
+  uint32_t pinW[PINNED && !XBF3 ? 4 * MT2 : 1];
+  if constexpr (PINNED && !XBF3) {
 #pragma unroll
     for (int g = 0; g < 4 * MT2; ++g) pinW[g] = lds_pin(&slotA[L.oW2 + (8 * g + 4 * hi) * S2 + j]);
   }
@@ -828,7 +919,55 @@ __global__ __launch_bounds__(256, (MODE == MODE_EVAL && !DBG && MP <= 8) ? 2 : 1
           f32x4 c = *(const f32x4*)&slotB[L.oB2 + 32 * mt + 8 * q + 4 * hi];
           t2[mt][4 * q + 0] = c.x; t2[mt][4 * q + 1] = c.y; t2[mt][4 * q + 2] = c.z; t2[mt][4 * q + 3] = c.w;
         }
-      {
+      if constexpr (XBF3) {
+        // bf16x3: A = V2's pieces from slot B's image, B = h1's registers 8 s .. 8 s + 7 of block kb (K-step s) as they lie.  Both
+        // are prepared one K-step group ahead: the next group's split (44 single-issue VALU) and its 6 fragment reads go between
+        // this group's 12 MFMAs (<= 4 VALU per gap), with this group's 16 [unit][sample] stores of h1 / h2
+        __builtin_amdgcn_sched_barrier(0);
+        const u32x4* vimg = (const u32x4*)(slotB + L.oW2) + lane;
+        Pc3 ac[MT2], an[MT2], bc = split3_of(h1[0], 0), bn = bc;
+#pragma unroll
+        for (int mt = 0; mt < MT2; ++mt)
+#pragma unroll
+          for (int p = 0; p < 3; ++p) ac[mt].p[p] = vimg[(p * 8 + mt * 4) * 64];
+        __builtin_amdgcn_sched_barrier(0);
+        constexpr int NG2 = 2 * MT1;
+#pragma unroll
+        for (int g = 0; g < NG2; ++g) {
+          if (g + 1 < NG2) {
+            const int kb1 = (g + 1) >> 1, s1 = (g + 1) & 1;
+#pragma unroll
+            for (int mt = 0; mt < MT2; ++mt)
+#pragma unroll
+              for (int p = 0; p < 3; ++p) an[mt].p[p] = vimg[(p * 8 + (mt * 2 + kb1) * 2 + s1) * 64];
+            bn = split3_of(h1[kb1], s1);
+          }
+#pragma unroll
+          for (int mt = 0; mt < MT2; ++mt) t2[mt] = mfma_bf3(ac[mt], bc, t2[mt]);
+#pragma unroll
+          for (int e = 0; e < 8; ++e) {
+            const int idx = g * 8 + e, mt = idx >> 4, r = idx & 15;
+            LDS_AT(pinB[4 * mt + (r >> 2)])[(r & 3) * ST] = h1[mt][r];
+            LDS_AT(pinA[4 * mt + (r >> 2)])[(r & 3) * ST] = h2[mt][r];
+          }
+#pragma unroll
+          for (int mt = 0; mt < MT2; ++mt) ac[mt] = an[mt];
+          bc = bn;
+        }
+#pragma unroll
+        for (int g = 0; g < NG2; ++g)
+#pragma unroll
+          for (int i = 0; i < 6 * MT2; ++i) {
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+            if (g + 1 < NG2) {
+              __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);
+              if (i < 3 * MT2) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+            }
+            if (i < 4) __builtin_amdgcn_sched_group_barrier(0x200, 2, 0);
+            else __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);
+          }
+        __builtin_amdgcn_sched_barrier(0);
+      } else {
         __builtin_amdgcn_sched_barrier(0);
         f32x4 vc[MT2], vn[MT2];
 #pragma unroll
@@ -875,8 +1014,10 @@ __global__ __launch_bounds__(256, (MODE == MODE_EVAL && !DBG && MP <= 8) ? 2 : 1
       MJX_STAMP(2);
       // (the first operands of the next MFMA phases are requested before each burst, so that they land during it)
       f32x4 wc3[MT2];
+      if constexpr (!XBF3) {
 #pragma unroll
-      for (int mt = 0; mt < MT2; ++mt) wc3[mt] = *(const f32x4*)&slotA[L.oW2 + (32 * mt + j) * S2 + 4 * hi];
+        for (int mt = 0; mt < MT2; ++mt) wc3[mt] = *(const f32x4*)&slotA[L.oW2 + (32 * mt + j) * S2 + 4 * hi];
+      }
       __builtin_amdgcn_sched_barrier(0);
       // ---------------- VA: t1 *= 1 - h1^2 ; f2 = 1 - h2^2   (one burst; R1 retired long ago, R2 does not touch t1)
       // (packed: v_pk_fma_f32 / v_pk_mul_f32 handle two registers per instruction at the price of one in a burst -- probe_fill.hip)
@@ -884,10 +1025,34 @@ __global__ __launch_bounds__(256, (MODE == MODE_EVAL && !DBG && MP <= 8) ? 2 : 1
       for (int mt = 0; mt < MT1; ++mt) pk_mul_1mh2_far(t1[mt], h1[mt]);     // (t1: R1's result, the 64 MFMAs of R2 ago; h1 / h2: loaded)
 #pragma unroll
       for (int mt = 0; mt < MT2; ++mt) f2s[mt] = pk_1mh2_far(h2[mt]);
+      Pc3 b3first;                                // bf16x3: R3's first B operand, split in this burst
+      if constexpr (XBF3) b3first = split3_of(t1[0], 0);
       __builtin_amdgcn_sched_barrier(0);
       MJX_STAMP(3);
       // ---------------- R3: t2 += W2 t1
-      {
+      if constexpr (XBF3) {
+        // bf16x3: t1's registers 8 s .. 8 s + 7 of block kb are K-step s's B operand as they lie (the k-permuted order the weight
+        // pieces were built in); the first group is split in the VA burst above, each further one under the previous group's
+        // 12 MFMAs (<= 4 VALU per gap)
+        constexpr int NG3 = 2 * MT1;
+        Pc3 bc = b3first, bn = b3first;
+#pragma unroll
+        for (int g = 0; g < NG3; ++g) {
+          const int kb = g >> 1, s = g & 1;
+          if (g + 1 < NG3) bn = split3_of(t1[(g + 1) >> 1], (g + 1) & 1);
+#pragma unroll
+          for (int mt = 0; mt < MT2; ++mt) t2[mt] = mfma_bf3(w3p[mt][kb][s], bc, t2[mt]);
+          bc = bn;
+        }
+#pragma unroll
+        for (int g = 0; g < NG3; ++g)
+#pragma unroll
+          for (int i = 0; i < 6 * MT2; ++i) {
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+            if (g + 1 < NG3) __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);
+          }
+        __builtin_amdgcn_sched_barrier(0);
+      } else {
         f32x4 wc[MT2], wn[MT2];
 #pragma unroll
         for (int mt = 0; mt < MT2; ++mt) wc[mt] = wc3[mt];
@@ -1012,10 +1177,12 @@ __global__ __launch_bounds__(256, (MODE == MODE_EVAL && !DBG && MP <= 8) ? 2 : 1
               gW3b[nt] = __builtin_amdgcn_mfma_f32_4x4x1f32(avo[t], bvo[nt][t], gW3b[nt], 0, 0, 0);
             }
         }
+        if constexpr (!XBF3) {
 #pragma unroll
-        for (int t = 0; t < 4; ++t)
+          for (int t = 0; t < 4; ++t)
 #pragma unroll
-          for (int nt = 0; nt < MT1; ++nt) wc8[t][nt] = LDS_AT(pinW[0])[t * S2 + 32 * nt];
+            for (int nt = 0; nt < MT1; ++nt) wc8[t][nt] = LDS_AT(pinW[0])[t * S2 + 32 * nt];
+        }
       }
       __builtin_amdgcn_sched_barrier(0);
       MJX_STAMP(7);
@@ -1028,7 +1195,61 @@ __global__ __launch_bounds__(256, (MODE == MODE_EVAL && !DBG && MP <= 8) ? 2 : 1
       float dl2u[MT2][16];
 #pragma unroll
       for (int nt = 0; nt < MT1; ++nt) dl1u[nt] = (f32x16)(0.f);
-      {
+      if constexpr (XBF3) {
+        // bf16x3: delta2's registers 8 s .. 8 s + 7 of block kb are K-step s's A operand as they lie; B = W2^T's pieces from slot
+        // A's image.  As in R2, the next K-step group's split and fragment reads go between this group's 12 MFMAs; the transposed
+        // copy of delta2 (first two groups) and its read-back (last two) ride along as before.
+        __builtin_amdgcn_sched_barrier(0);
+        load_h(ptile((tile + tstride < ntiles) ? tile + tstride : tile));
+        const u32x4* img = (const u32x4*)(slotA + L.oW2) + lane;
+        constexpr int NG8 = 2 * MT2;
+        Pc3 ac = split3_of(dl2s[0], 0), an = ac, bc[MT1], bn[MT1];
+#pragma unroll
+        for (int nt = 0; nt < MT1; ++nt)
+#pragma unroll
+          for (int p = 0; p < 3; ++p) bc[nt].p[p] = img[(p * 8 + nt * 4) * 64];
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int g = 0; g < NG8; ++g) {
+          if (g + 1 < NG8) {
+            const int kb1 = (g + 1) >> 1, s1 = (g + 1) & 1;
+#pragma unroll
+            for (int nt = 0; nt < MT1; ++nt)
+#pragma unroll
+              for (int p = 0; p < 3; ++p) bn[nt].p[p] = img[(p * 8 + (nt * 2 + kb1) * 2 + s1) * 64];
+            an = split3_of(dl2s[kb1], s1);
+          }
+#pragma unroll
+          for (int nt = 0; nt < MT1; ++nt) dl1u[nt] = mfma_bf3(ac, bc[nt], dl1u[nt]);
+          if (g < MT2) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) LDS_AT(pinA[4 * g + (r >> 2)])[(r & 3) * ST] = dl2s[g][r];
+          } else {
+            const int nt = g - MT2;
+#pragma unroll
+            for (int qq = 0; qq < 4; ++qq) {
+              const f32x4 v = *(const f32x4*)&bufA[(32 * nt + j) * ST + 8 * qq + 4 * hi];
+              dl2u[nt][4 * qq] = v.x; dl2u[nt][4 * qq + 1] = v.y; dl2u[nt][4 * qq + 2] = v.z; dl2u[nt][4 * qq + 3] = v.w;
+            }
+          }
+          ac = an;
+#pragma unroll
+          for (int nt = 0; nt < MT1; ++nt) bc[nt] = bn[nt];
+        }
+#pragma unroll
+        for (int g = 0; g < NG8; ++g)
+#pragma unroll
+          for (int i = 0; i < 6 * MT1; ++i) {
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+            if (g + 1 < NG8) {
+              __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);
+              if (i < 3 * MT1) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+            }
+            if (g < MT2) { if (i < 4) __builtin_amdgcn_sched_group_barrier(0x200, 2, 0); else __builtin_amdgcn_sched_group_barrier(0x200, 1, 0); }
+            else if (i < 4) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+          }
+        __builtin_amdgcn_sched_barrier(0);
+      } else {
         constexpr int NG = MT2 * 4;                 // groups of 4 k-steps over the h2 units
         constexpr int NGH = NG / 2;
         float wc[4][MT1], wn[4][MT1];

@@ -140,13 +140,20 @@ using namespace mjx;
 template <int H1, int H2, int NT1, int MP, bool DBG = false, int NPC = 0>
 int launch_fused(mjx_ctx* c, int mode, const FusedArgs& a, hipStream_t st) {
   const bool ev2 = (mode == MODE_EVAL) && MP <= 8;   // MODE_EVAL (always the non-debug instance): small layout, two workgroups per CU (fused_policy.h)
-  FusedLayout<H1, H2, NT1, MP> L(NPC ? NPC - 1 : c->n, ev2);       // (the kernel's rule: fused_policy.h)
+  const bool cached = (mode == MODE_FVP) && a.hcache != nullptr && !DBG;
+  // the cached 64 x 64 product with up to 8 actions runs its 64x64 products on bf16x3 MFMAs (k_fused<..., BF3 = true>);
+  // MJX_FVP_BF16X3=0 selects the fp32 kernel (read once per process)
+  static const bool bf3_on = [] { const char* e = getenv("MJX_FVP_BF16X3"); return !(e && e[0] == '0'); }();
+  // (64 x 64 with up to 8 actions only, and only while its layout -- two 24 KB piece images -- fits 160 KB: up to 23 observations)
+  constexpr bool BF3_OK = H1 == 64 && H2 == 64 && MP == 8;
+  const bool bf3 = BF3_OK && cached && bf3_on && FusedLayout<H1, H2, NT1, MP>(NPC ? NPC - 1 : c->n, false, true).bytes() <= 160 * 1024;
+  FusedLayout<H1, H2, NT1, MP> L(NPC ? NPC - 1 : c->n, ev2, bf3);  // (the kernel's rule: fused_policy.h)
   size_t bytes = L.bytes();
   void (*k)(FusedArgs) = nullptr;
-  const bool cached = (mode == MODE_FVP) && a.hcache != nullptr && !DBG;
   if (mode == MODE_VPG) k = k_fused<H1, H2, NT1, MP, MODE_VPG, DBG, NPC>;
   else if (mode == MODE_FVP) k = cached ? k_fused<H1, H2, NT1, MP, MODE_FVP, false, NPC, true> : k_fused<H1, H2, NT1, MP, MODE_FVP, DBG, NPC>;
   else k = k_fused<H1, H2, NT1, MP, MODE_EVAL, false, NPC>;
+  if constexpr (BF3_OK) { if (bf3) k = k_fused<H1, H2, NT1, MP, MODE_FVP, false, NPC, true, true>; }
   if (cached) mode = 3;
   // the dynamic-LDS limit is a per-kernel, per-device attribute and FusedLayout::bytes() depends on the runtime observation
   // count (the generic NPC = 0 instances serve many): remember the largest size configured per (device, kernel) and raise it

@@ -6,10 +6,12 @@ formed from the piece products that matter, accumulated in fp32.  Before any ker
 emulated exactly on the CPU (bf16 x bf16 is exact in fp32, the accumulation is fp32 like the MFMA's), for one Fisher-vector
 product and one 10-iteration CG solve at the BASELINE configs[1] shapes, against fp64 truth, next to native fp32's.
 
-    python tools/probe_split_error.py [N=100000]
+    python tools/probe_split_error.py [N=100000] [mode,mode,...]
 
 modes: f32 (native), bf16x3 (3 pieces, the 6 products with i + j <= 2), bf16x3_all9, bf16x2 (2 pieces, 3 products -- what a
-"cheaper" split would give: lower precision than the reference, listed for contrast only).
+"cheaper" split would give: lower precision than the reference, listed for contrast only), bf16x3_kernel (what the bf16x3 cached
+kernel does: R3 / R8 alone on the exact truncation split, per 16-deep K-step, small piece products first onto the fp32
+accumulator; every other product fp32).
 (Nothing here imports oracle/: tools are measurement infrastructure, the FVP is restated inline.)
 """
 import json
@@ -56,6 +58,32 @@ def mm(a, b, mode):
     return acc
 
 
+def trunc16(x):
+    """fp32 with the low 16 bits cleared: a bf16 by truncation"""
+    return (x.astype(np.float32).view(np.uint32) & np.uint32(0xFFFF0000)).view(np.float32)
+
+
+def split_trunc(x):
+    """the kernel's exact split (fused_policy.h split3): hi = trunc(x), r = x - hi, mid = trunc(r), lo = r - mid; hi + mid + lo == x"""
+    x = x.astype(np.float32)
+    hi = trunc16(x)
+    r = x - hi
+    mid = trunc16(r)
+    return [hi, mid, r - mid]
+
+
+def mm_kernel(a, b, acc):
+    """acc + a @ b the way the bf16x3 kernel forms R3 / R8: per K-step of 16 (one v_mfma_f32_32x32x16_bf16 each) the six piece
+    products lo.hi, hi.lo, mid.mid, mid.hi, hi.mid, hi.hi onto ONE fp32 accumulator"""
+    A, B = split_trunc(a), split_trunc(b)
+    acc = acc.astype(np.float32)
+    for k0 in range(0, a.shape[1], 16):
+        ks = slice(k0, k0 + 16)
+        for i, j in ((2, 0), (0, 2), (1, 1), (1, 0), (0, 1), (0, 0)):
+            acc = acc + A[i][:, ks] @ B[j][ks, :]
+    return acc
+
+
 def unflatten(th):
     sizes = (n,) + H + (m,)
     Ws, bs, o = [], [], 0
@@ -70,6 +98,9 @@ def fvp(th, obs, v, mode, chunk=4096):
     """Gauss-Newton Fisher-vector product of mean_kl at theta_new == theta_old (mjrl/algos/npg_cg.py:62-81 restated: SURVEY 8a-a9);
     weight gradients accumulate per `chunk` samples in the mode's arithmetic and across chunks in fp64 (the kernel: per wave in MFMA
     accumulators, then fp64)"""
+    kern = mode == "bf16x3_kernel"               # the kernel: R3 / R8 on bf16x3 (truncation split), every other product fp32
+    if kern:
+        mode = "f32"
     dt = np.float64 if mode == "f64" else np.float32
     th, v, obs = th.astype(dt), v.astype(dt), obs.astype(dt)
     Ws, bs, s = unflatten(th)
@@ -85,11 +116,14 @@ def fvp(th, obs, v, mode, chunk=4096):
         h1 = np.tanh(mm(x, Ws[0].T, mode) + bs[0]).astype(dt)
         h2 = np.tanh(mm(h1, Ws[1].T, mode) + bs[1]).astype(dt)
         t1 = ((mm(x, Vs[0].T, mode) + cs[0]) * (1 - h1 * h1)).astype(dt)
-        t2 = ((mm(h1, Vs[1].T, mode) + mm(t1, Ws[1].T, mode) + cs[1]) * (1 - h2 * h2)).astype(dt)
+        if kern:                                 # t2 = c2 + V2 h1 (fp32), then R3's piece products onto it
+            t2 = (mm_kernel(t1, Ws[1].T, mm(h1, Vs[1].T, mode) + cs[1]) * (1 - h2 * h2)).astype(dt)
+        else:
+            t2 = ((mm(h1, Vs[1].T, mode) + mm(t1, Ws[1].T, mode) + cs[1]) * (1 - h2 * h2)).astype(dt)
         mud = (mm(h2, Vs[2].T, mode) + mm(t2, Ws[2].T, mode) + cs[2]).astype(dt)
         d3 = (D * mud / dt(N)).astype(dt)
         d2 = (mm(d3, Ws[2], mode) * (1 - h2 * h2)).astype(dt)
-        d1 = (mm(d2, Ws[1], mode) * (1 - h1 * h1)).astype(dt)
+        d1 = ((mm_kernel(d2, Ws[1], np.zeros((d2.shape[0], Ws[1].shape[1]), dt)) if kern else mm(d2, Ws[1], mode)) * (1 - h1 * h1)).astype(dt)
         for l, (d_, a_) in enumerate(((d1, x), (d2, h1), (d3, h2))):
             gW[l] += mm(d_.T, a_, mode).astype(np.float64)
             gb[l] += d_.sum(axis=0, dtype=np.float64)
@@ -128,7 +162,8 @@ def main():
     out = {"N": N, "shapes": "obs 17, act 6, 64x64 (BASELINE configs[1])", "cg_iters": 10, "damping": damping}
     h64 = fvp(th, obs, g, "f64")
     x64 = cg(lambda p: fvp(th, obs, p, "f64") + damping * p, g.astype(np.float64))
-    for mode in ("f32", "bf16x3", "bf16x3_all9", "bf16x2"):
+    modes = sys.argv[2].split(",") if len(sys.argv) > 2 else ("f32", "bf16x3", "bf16x3_all9", "bf16x2", "bf16x3_kernel")
+    for mode in modes:
         h = fvp(th, obs, g, mode)
         x = cg(lambda p: fvp(th, obs, p, mode) + np.float32(damping) * p, g.astype(np.float32))
         out[mode] = {"fvp_rel_l2_vs_f64": rel(h, h64), "cg10_rel_l2_vs_f64": rel(x, x64)}
