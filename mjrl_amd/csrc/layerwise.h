@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "fused_policy.h"
+#include "launch_state.h"
 #include "lw_head.h"
 #include "vecops.h"
 
@@ -51,41 +52,33 @@ struct GemmArgs {
 #endif
 };
 
-// Per-DEVICE one-time state of the layer-wise launchers (function-static flags configured only the device that
-// happened to be current at first use -- a second context on another GPU of the same process launched > 64 KB-LDS kernels
-// without the attribute and read a foreign device's ticket counter).
-inline int lw_cur_device() { int dev = 0; (void)hipGetDevice(&dev); return dev; }
-inline void lw_set_dyn_lds(const void* kern, int bytes) {                   // hipFuncAttributeMaxDynamicSharedMemorySize, once per (device, kernel)
-  static std::mutex mu;
-  static std::vector<std::pair<int, const void*>> done;
-  const int dev = lw_cur_device();
-  std::lock_guard<std::mutex> lk(mu);
-  for (auto& e : done) if (e.first == dev && e.second == kern) return;
-  (void)hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-  done.push_back({dev, kern});
-}
-inline int lw_ncu() {                                                        // compute units of the current device
-  static std::mutex mu;
-  static std::vector<std::pair<int, int>> cache;
-  const int dev = lw_cur_device();
-  std::lock_guard<std::mutex> lk(mu);
-  for (auto& e : cache) if (e.first == dev) return e.second;
-  int c = 256;
-  (void)hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev);
-  cache.push_back({dev, c});
-  return c;
-}
+// Per-DEVICE state of the layer-wise launchers lives in launch_state.h (function-static flags configured only the
+// device that happened to be current at first use -- a second context on another GPU of the same process launched > 64 KB-LDS
+// kernels without the attribute and read a foreign device's ticket counter).
 inline int* lw_ticket_ring() {                                               // 256 ticket counters (+ leaver counts) on the current device; nullptr if the allocation fails
   static std::mutex mu;
-  static std::vector<std::pair<int, int*>> rings;
-  const int dev = lw_cur_device();
+  static PerDevice<std::pair<bool, int*>> rings;                             // (tried, [256 tickets][256 leaver counts], zero between launches)
   std::lock_guard<std::mutex> lk(mu);
-  for (auto& e : rings) if (e.first == dev) return e.second;
-  int* p = nullptr;                                                          // [256 tickets][256 leaver counts], zero between launches
-  if (hipMalloc(&p, 512 * sizeof(int)) != hipSuccess) { (void)hipGetLastError(); p = nullptr; }
-  else if (hipMemset(p, 0, 512 * sizeof(int)) != hipSuccess) { (void)hipGetLastError(); (void)hipFree(p); p = nullptr; }
-  rings.push_back({dev, p});
-  return p;
+  auto& r = rings.here();
+  if (!r.first) {
+    r.first = true;
+    if (hipMalloc(&r.second, 512 * sizeof(int)) != hipSuccess) { (void)hipGetLastError(); r.second = nullptr; }
+    else if (hipMemset(r.second, 0, 512 * sizeof(int)) != hipSuccess) { (void)hipGetLastError(); (void)hipFree(r.second); r.second = nullptr; }
+  }
+  return r.second;
+}
+// The GEMM launchers below return nothing; every operation built from them ends with ONE status check, lw_status().  A
+// dynamic-LDS limit that could not be set keeps its kernel from being launched and is kept for that check.
+inline hipError_t& lw_refused() { static thread_local hipError_t e = hipSuccess; return e; }
+inline bool lw_dyn_lds(const void* kern, size_t bytes) {
+  const int e = dyn_lds(kern, bytes);
+  if (e != 0 && lw_refused() == hipSuccess) lw_refused() = e == LDS_OVER ? hipErrorInvalidValue : (hipError_t)e;
+  return e == 0;
+}
+inline hipError_t lw_status() {                                              // the first refusal since the last check, else the runtime's last error
+  const hipError_t refused = lw_refused(), last = hipGetLastError();
+  lw_refused() = hipSuccess;
+  return refused != hipSuccess ? refused : last;
 }
 
 #ifdef MJX_PHASE_CLOCK
@@ -940,7 +933,7 @@ struct LayerwiseWS {
   // ds_read_b128 per four).  MJX_LW_WT=0: the weights as they lie.
   std::vector<float*> Wt;
   const float* wt_theta = nullptr;
-  static bool wt_on() { static const bool on = [] { const char* e = getenv("MJX_LW_WT"); return !(e && e[0] == '0'); }(); return on; }
+  static bool wt_on() { static const bool on = env_flag("MJX_LW_WT", true); return on; }
   bool wt_eligible(int l) const { return l >= 1 && l < nL() && sizes[l + 1] >= 64 && (sizes[l + 1] % 32) == 0 && (sizes[l] % 4) == 0 && sizes[l] > 32; }
   // (up to 32 features: whole 16-byte granules; beyond: whole 128-byte k-tiles, so that every k-tile segment of a row is one
   //  cache line and the first layer needs no K tail -- 376 -> 384, 39 -> 64)
@@ -1047,10 +1040,10 @@ struct LayerwiseWS {
   template <int BM, int BN, int NTH = gemm_threads<BN>()>
   static void launch_tile(const GemmArgs& g, int splits, hipStream_t st) {
     void (*const kern)(GemmArgs) = k_gemm<BM, BN, NTH>;
-    lw_set_dyn_lds((const void*)kern, (int)gemm_lds_bytes<BM, BN>());      // double-buffered operand tiles: dynamic LDS beyond the 64 KB default
+    if (!lw_dyn_lds((const void*)kern, gemm_lds_bytes<BM, BN>())) return;   // double-buffered operand tiles: dynamic LDS beyond the 64 KB default
     dim3 grid((g.N + BN - 1) / BN, (g.M + BM - 1) / BM, splits);
     constexpr size_t lds = gemm_lds_bytes<BM, BN>();
-    const bool fast_on = [] { const char* e = getenv("MJX_LW_FAST"); return !(e && e[0] == '0'); }();   // MJX_LW_FAST=0: A/B
+    const bool fast_on = env_flag("MJX_LW_FAST", true);   // MJX_LW_FAST=0: A/B
     if (g.fast != (fast_on ? 1 : 0)) { GemmArgs h = g; h.fast = fast_on ? 1 : 0; launch_tile<BM, BN, NTH>(h, splits, st); return; }
 #ifdef MJX_PHASE_CLOCK
     if (lw_clk_buf() && !g.clk && lw_clk_slot() < LW_CLK_SLOTS && (int64_t)grid.x * grid.y <= 16384) {
@@ -1062,7 +1055,7 @@ struct LayerwiseWS {
 #ifdef MJX_GEMM_EXPERIMENTS
     // timing experiment (results are WRONG): every row of a K-contiguous A operand reads the same 128-byte line, so the
     // k-loop's activation stream comes from cache -- separates memory stalls from issue / LDS limits
-    const bool alias_a = [] { const char* e = getenv("MJX_LW_DEBUG_ALIAS_A"); return e && e[0] == '1'; }();
+    const bool alias_a = env_flag("MJX_LW_DEBUG_ALIAS_A", false);
     if (alias_a) {
       GemmArgs h = g;
       for (int p = 0; p < h.npairs; ++p) if (h.a_ks[p] == 1) h.a_rs[p] = 0;
@@ -1111,12 +1104,12 @@ struct LayerwiseWS {
     return v;
   }
   static bool thin_wgrad(int ncols) {
-    const bool on = [] { const char* e = getenv("MJX_LW_THIN"); return !(e && e[0] == '0'); }();
+    const bool on = env_flag("MJX_LW_THIN", true);
     return on && ncols > 32 && ncols <= 128 && tile_mode() == 1;
   }
   static int pick_splits(int64_t N, int row_tiles, int ncols, int cap) {
-    const int ncu = lw_ncu();
-    const bool on = [] { const char* e = getenv("MJX_LW_SPLITS"); return !(e && e[0] == '0'); }();
+    const int ncu = cu_count();
+    const bool on = env_flag("MJX_LW_SPLITS", true);
     if (cap < 4 || !on) return cap;
     int cb = 1;                                        // column blocks of the main launch (launch_gemm)
     if (ncols > 32) {
@@ -1137,7 +1130,7 @@ struct LayerwiseWS {
   // Sample-major products in their steady-state shape go to the persistent kernel (lw_gemm_p.h).
   // MJX_LW_PERSIST=0 keeps everything on the general kernel.
   static int persistent_lb(const GemmArgs& g, int splits) {        // -> 0 / 1: the B layout it can run with, -1: not eligible
-    const bool on = [] { const char* e = getenv("MJX_LW_PERSIST"); return !(e && e[0] == '0'); }();
+    const bool on = env_flag("MJX_LW_PERSIST", true);
     if (on && lw_ticket_ring() == nullptr) return -1;               // no ticket counters on this device: the general kernel serves the product
     if (!on || splits != 1 || tile_mode() != 1 || g.M < 2 * GP_BM || g.N < GP_BN || (g.N % GP_BN) != 0) return -1;
     if ((g.M % GP_BM) != 0 && !g.rows_padded) return -1;
@@ -1161,8 +1154,8 @@ struct LayerwiseWS {
   template <int LB, int EPI>
   static void launch_p(const GemmArgs& g, int row_tiles, hipStream_t st) {
     void (*const kern)(GemmArgs, int, int, int*) = k_gemm_p<LB, EPI, GemmArgs>;
-    lw_set_dyn_lds((const void*)kern, (int)gp_lds_bytes<LB>());
-    const int ncu = lw_ncu();
+    if (!lw_dyn_lds((const void*)kern, gp_lds_bytes<LB>())) return;
+    const int ncu = cu_count();
     const int cbs = g.N / GP_BN, ntiles = row_tiles * cbs;
     // (a ring of counters per device, one per launch in turn: launches on different streams do not share one;
     //  persistent_lb() has checked that the ring exists)
@@ -1201,7 +1194,7 @@ struct LayerwiseWS {
     if (splits > 1 && thin_wgrad(g.N)) {
       // (r04) up to 64 columns -- the 512 x 39 first-layer gradient of configs[4], stored 64 wide -- a 128 x 64 tile: the 128-column
       // tile spent half its matrix work and half its B-operand LDS traffic on padding (MJX_LW_THIN64=0: the r03 shape)
-      const bool t64 = [] { const char* e = getenv("MJX_LW_THIN64"); return !(e && e[0] == '0'); }();
+      const bool t64 = env_flag("MJX_LW_THIN64", true);
       if (t64 && g.N <= 64) { launch_tile<128, 64, 256>(g, splits, st); return; }
       launch_tile<128, 128, 256>(g, splits, st);
       return;
@@ -1270,7 +1263,7 @@ struct LayerwiseWS {
   int backward(const float* theta, int64_t N, float* grad, hipStream_t st, int l_start = -1, const float* delta0 = nullptr) {
     const float* delta = delta0 ? delta0 : d3;
     bool bias_done = delta0 != nullptr;
-    const bool overlap_on = [] { const char* e = getenv("MJX_LW_OVERLAP"); return e && e[0] == '1'; }();
+    const bool overlap_on = env_flag("MJX_LW_OVERLAP", false);
     const bool overlap = overlap_on && N >= 65536;
     if (overlap && !side) {
       if (hipStreamCreateWithFlags(&side, hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&ev_a, hipEventDisableTiming) != hipSuccess ||
@@ -1368,7 +1361,7 @@ struct LayerwiseWS {
       }
     }
     if (overlap) { (void)hipEventRecord(ev_b, side); (void)hipStreamWaitEvent(main_st, ev_b, 0); }      // join: the gradients are complete on the caller's stream
-    return hipGetLastError() == hipSuccess ? 0 : 1;
+    return lw_status() == hipSuccess ? 0 : 1;
   }
 
   int surr_vpg(const float* obs, const float* act, const float* adv, int64_t N, int64_t Ng, const float* th_new,
@@ -1431,7 +1424,7 @@ struct LayerwiseWS {
   // (the pass reads theta / v with 16-byte loads: a direction that is a view at an odd offset of a larger tensor takes the
   //  generic chain instead of failing -- the fast path is an optimisation, not a precondition)
   bool head_fused(const float* theta, const float* v) const {
-    const bool on = [] { const char* e = getenv("MJX_LW_HEAD"); return !(e && e[0] == '0'); }();
+    const bool on = env_flag("MJX_LW_HEAD", true);
     if (!on || nL() < 2 || m > 32) return false;
     if ((((uintptr_t)theta | (uintptr_t)v) & 15) != 0) return false;
     const int hl = sizes[nL() - 1];
@@ -1439,7 +1432,7 @@ struct LayerwiseWS {
   }
   int fvp_head(const float* theta, const float* tr, const float* v, int64_t N, int64_t Ng, float* out, hipStream_t st) {
     const int L = nL() - 1, hl = sizes[L];
-    const int ncu = lw_ncu();
+    const int ncu = cu_count();
     const int64_t ntile = (N + LH_R - 1) / LH_R;
     const int grid = (int)(ntile < ncu ? ntile : ncu);             // one workgroup per CU (the kernel takes the whole register file: lw_head.h)
     if (ensure_part((int64_t)grid * ((int64_t)m * hl + 32 + hl))) return 2;
@@ -1451,18 +1444,16 @@ struct LayerwiseWS {
     auto launch = [&](auto ch) {
       constexpr int CH = decltype(ch)::value;
       void (*const kern)(HeadArgs) = k_lw_head<CH>;
-      lw_set_dyn_lds((const void*)kern, (int)lw_head_lds_bytes());
-      hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lw_head_lds_bytes(), st, a);
+      if (lw_dyn_lds((const void*)kern, lw_head_lds_bytes())) hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lw_head_lds_bytes(), st, a);
     };
     auto launch8 = [&](auto ch) {             // 256 / 512 units: the eight-wave build (two waves per SIMD)
       constexpr int CH = decltype(ch)::value;
       // the delta product's contraction over the actions in ceil(m / 2) steps: 9 (m <= 18: Humanoid's 17), 12 (<= 24), else all 16
-      const bool trim = [] { const char* e = getenv("MJX_LW_HEAD_KTRIM"); return !(e && e[0] == '0'); }();
+      const bool trim = env_flag("MJX_LW_HEAD_KTRIM", true);
       void (*const kern)(HeadArgs) = !trim ? k_lw_head8<CH, 16> : m <= 18 ? k_lw_head8<CH, 9> : m <= 24 ? k_lw_head8<CH, 12> : k_lw_head8<CH, 16>;
-      lw_set_dyn_lds((const void*)kern, (int)lw_head8_lds_bytes());
-      hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lw_head8_lds_bytes(), st, a);
+      if (lw_dyn_lds((const void*)kern, lw_head8_lds_bytes())) hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lw_head8_lds_bytes(), st, a);
     };
-    const bool eight = [] { const char* e = getenv("MJX_LW_HEAD8"); return !(e && e[0] == '0'); }();
+    const bool eight = env_flag("MJX_LW_HEAD8", true);
     // (r06: k_lw_head8 re-bases its buffer resources per row tile -- no 4 GB limit on the blocks any more)
     if (eight && hl == 256) launch8(std::integral_constant<int, 1>{});
     else if (eight && hl == 512) launch8(std::integral_constant<int, 2>{});
@@ -1564,7 +1555,7 @@ struct LayerwiseWS {
         dl = P[l - 1]; rdl = RD[l - 1];
       }
     }
-    return hipGetLastError() == hipSuccess ? 0 : 1;
+    return lw_status() == hipSuccess ? 0 : 1;
   }
 
   // old_cached: the caller vouches that theta_old / tr_old / obs are what surr_vpg saw (the one-call updates: nothing outside the
@@ -1572,7 +1563,7 @@ struct LayerwiseWS {
   int eval(const float* obs, const float* act, const float* adv, int64_t N, const float* th_new, const float* th_old,
            const float* tr_new, const float* tr_old, double* scal, hipStream_t st, bool old_cached = false, bool old_is_new = false) {
     if (N > cap) return 1;
-    static const bool reuse_on = [] { const char* e = getenv("MJX_LW_OLD_OUTPUTS"); return !(e && e[0] == '0'); }();
+    static const bool reuse_on = env_flag("MJX_LW_OLD_OUTPUTS", true);
     const float *mnew = mu, *mold = mu2;
     if (reuse_on && old_cached && mu_valid && obs == mu_obs && N <= mu_rows) {
       if (old_is_new) { mnew = mu; mold = nullptr; }                    // LR = 1, KL = 0: no network runs at all; the caches stay
@@ -1589,7 +1580,7 @@ struct LayerwiseWS {
     hipLaunchKernelGGL(k_head, dim3(HEAD_G), dim3(HEAD_NT), 0, st, 2, mnew, mold, act, adv, N, m, th_new + oS, th_old + oS,
                        tr_new + 2 * n + m, 0.f, (float*)nullptr, hpart);
     hipLaunchKernelGGL(k_reduce_head, dim3(1), dim3(256), 0, st, hpart, HEAD_G, m, 2, scal, (float*)nullptr);
-    return hipGetLastError() == hipSuccess ? 0 : 1;
+    return lw_status() == hipSuccess ? 0 : 1;
   }
 };
 

@@ -24,6 +24,7 @@
 #include "fused_policy.h"
 #include "policy_fit.h"
 #include "rccl_dyn.h"
+#include "launch_state.h"
 #include "layerwise.h"
 #include "mlp_fit.h"
 #include "vecops.h"
@@ -47,6 +48,21 @@ int fail(int code, const char* fmt, ...) {
     hipError_t e_ = (expr);                                                              \
     if (e_ != hipSuccess) return fail((int)e_, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
   } while (0)
+
+// launch_state.h's answers as entry results: the dynamic-LDS limit of `kern` on the current device before a launch with `bytes`,
+// and a scratch block of the calling thread on (site, current device, stream)
+int lds_limit(const void* kern, size_t bytes) {
+  const int e = mjx::dyn_lds(kern, bytes);
+  if (e == mjx::LDS_OVER) return fail(MJX_ERR_UNSUPPORTED, "needs %zu + %zu static bytes of LDS (> 160 KiB)", bytes, mjx::static_lds(kern));
+  if (e) return fail(e, "dynamic LDS limit of %zu bytes: %s", bytes, hipGetErrorString((hipError_t)e));
+  return MJX_OK;
+}
+enum ScratchSite { SITE_GRAM, SITE_MLP_PREDICT, SITE_MLP_FIT, SITE_MLP_FIT_WIDE, SITE_MLP_FIT_LAUNCHES, SITE_DYN_FIT, SITE_SUM_STATS };
+template <class T>
+int dev_scratch(ScratchSite site, void* stream, size_t bytes, T** out) {
+  HIPCHK(mjx::scratch(site, (hipStream_t)stream, bytes, (void**)out));
+  return MJX_OK;
+}
 
 // ---- fork guard.  Sampler workers are FORKED from the training process (mjrl/samplers/core.py:189-210: mp.Pool under a parent
 // that holds an mjx_ctx, page-locked staging blocks and libmjx's gather threads).  None of that survives a fork in a usable
@@ -143,10 +159,10 @@ int launch_fused(mjx_ctx* c, int mode, const FusedArgs& a, hipStream_t st) {
   const bool cached = (mode == MODE_FVP) && a.hcache != nullptr && !DBG;
   // the cached 64 x 64 product with up to 8 actions runs its 64x64 products on bf16x3 MFMAs (k_fused<..., BF3 = true>);
   // MJX_FVP_BF16X3=0 selects the fp32 kernel (read once per process)
-  static const bool bf3_on = [] { const char* e = getenv("MJX_FVP_BF16X3"); return !(e && e[0] == '0'); }();
+  static const bool bf3_on = env_flag("MJX_FVP_BF16X3", true);
   // (64 x 64 with up to 8 actions only, and only while its layout -- two 24 KB piece images -- fits 160 KB: up to 23 observations)
   constexpr bool BF3_OK = H1 == 64 && H2 == 64 && MP == 8;
-  const bool bf3 = BF3_OK && cached && bf3_on && FusedLayout<H1, H2, NT1, MP>(NPC ? NPC - 1 : c->n, false, true).bytes() <= 160 * 1024;
+  const bool bf3 = BF3_OK && cached && bf3_on && FusedLayout<H1, H2, NT1, MP>(NPC ? NPC - 1 : c->n, false, true).bytes() <= LDS_MAX;
   FusedLayout<H1, H2, NT1, MP> L(NPC ? NPC - 1 : c->n, ev2, bf3);  // (the kernel's rule: fused_policy.h)
   size_t bytes = L.bytes();
   void (*k)(FusedArgs) = nullptr;
@@ -155,19 +171,8 @@ int launch_fused(mjx_ctx* c, int mode, const FusedArgs& a, hipStream_t st) {
   else k = k_fused<H1, H2, NT1, MP, MODE_EVAL, false, NPC>;
   if constexpr (BF3_OK) { if (bf3) k = k_fused<H1, H2, NT1, MP, MODE_FVP, false, NPC, true, true>; }
   if (cached) mode = 3;
-  // the dynamic-LDS limit is a per-kernel, per-device attribute and FusedLayout::bytes() depends on the runtime observation
-  // count (the generic NPC = 0 instances serve many): remember the largest size configured per (device, kernel) and raise it
-  // whenever a context needs more
-  static thread_local std::vector<std::pair<std::pair<int, const void*>, size_t>> configured;
-  {
-    size_t* have = nullptr;
-    for (auto& e : configured) if (e.first.first == c->device && e.first.second == (const void*)k) have = &e.second;
-    if (!have) { configured.push_back({{c->device, (const void*)k}, 0}); have = &configured.back().second; }
-    if (*have < bytes) {
-      HIPCHK(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-      *have = bytes;
-    }
-  }
+  // (FusedLayout::bytes() depends on the runtime observation count: the generic NPC = 0 instances serve many sizes)
+  if (int rc = lds_limit((const void*)k, bytes)) return rc;
   hipLaunchKernelGGL(k, dim3(ev2 ? 2 * c->grid : c->grid), dim3(256), bytes, st, a);
   HIPCHK(hipGetLastError());
   return MJX_OK;
@@ -206,7 +211,7 @@ template <int H1, int H2, int NT1, int MP>
 bool variant_fits(int n, int m, int h1, int h2, int64_t d, size_t* bytes) {
   if (h1 != H1 || h2 != H2 || m > MP || n + 1 > 32 * NT1) return false;
   FusedLayout<H1, H2, NT1, MP> L(n);
-  if (L.bytes() > 160 * 1024) return false;
+  if (L.bytes() > LDS_MAX) return false;
   if ((size_t)(4 * d + 64) * 4 > L.bytes()) return false;   // end-of-kernel reduction region
   *bytes = L.bytes();
   return true;
@@ -315,20 +320,17 @@ int mjx_create(mjx_ctx** out, int device, int n, int m, const int* hidden, int n
   c->oS = (int)d;
   d += m;
   c->d = d;
-  hipDeviceProp_t prop;
-  HIPCHK(hipGetDeviceProperties(&prop, device));
-  c->n_cu = prop.multiProcessorCount;
+  c->n_cu = cu_count();
   c->grid = c->n_cu;
   c->fused = pick_variant(n, m, c->hidden, d, &c->lds_bytes);
-  if (const char* e = getenv("MJX_FORCE_LAYERWISE")) if (e[0] == '1') c->fused = 0;
-  if (const char* e = getenv("MJX_NO_HCACHE")) if (e[0] == '1') c->use_hcache = 0;
+  if (env_flag("MJX_FORCE_LAYERWISE", false)) c->fused = 0;
+  if (env_flag("MJX_NO_HCACHE", false)) c->use_hcache = 0;
   if (c->fused) {
     // workgroup partials in accumulator order (RawSlab): the table is made here, once; any doubt about it (an instance this
     // switch does not know, a table that does not hit every flat index exactly once, no room for the four copies in LDS) keeps
     // the flat-order epilogue.  MJX_RAW_SLAB=0: A/B.
-    const char* e = getenv("MJX_RAW_SLAB");
     std::vector<int> perm;
-    const int dr = (e && e[0] == '0') ? 0 : raw_slab(c->fused, npc_of(c->fused, n), n, m, &perm);
+    const int dr = !env_flag("MJX_RAW_SLAB", true) ? 0 : raw_slab(c->fused, npc_of(c->fused, n), n, m, &perm);
     if (dr > 0 && (size_t)(4 * dr + 64) * 4 <= c->lds_bytes) {
       HIPCHK(hipMalloc((void**)&c->raw_perm, (size_t)dr * sizeof(int)));
       HIPCHK(hipMemcpy(c->raw_perm, perm.data(), (size_t)dr * sizeof(int), hipMemcpyHostToDevice));
@@ -437,10 +439,11 @@ static int bind_policy_impl(mjx_ctx* c, const float* theta_new, const float* the
 // ---------------------------------------------------------------------------- K6 baselines
 namespace {
 struct FeatTableCache { int kind = -1, n = -1, F = 0; FeatDesc* dev = nullptr; };
+struct FeatTables { FeatTableCache kind[3]; };
 int get_feat_table(int kind, int n, FeatTableCache** out) {
-  static thread_local FeatTableCache cache[3];
+  static thread_local PerDevice<FeatTables> cache;         // the last table of each kind, per device
   if (kind < 0 || kind > 2 || n <= 0 || n > 4096) return fail(MJX_ERR_ARG, "bad feature kind / obs dim");
-  FeatTableCache& c = cache[kind];
+  FeatTableCache& c = cache.here().kind[kind];
   if (c.n != n) {
     std::vector<FeatDesc> t = build_feat_table(kind, n);
     if (c.dev) hipFree(c.dev);
@@ -449,15 +452,6 @@ int get_feat_table(int kind, int n, FeatTableCache** out) {
     c.kind = kind; c.n = n; c.F = (int)t.size();
   }
   *out = &c;
-  return MJX_OK;
-}
-struct Scratch { void* p = nullptr; size_t cap = 0; };
-int get_scratch(Scratch& s, size_t bytes) {
-  if (bytes <= s.cap) return MJX_OK;
-  if (s.p) hipFree(s.p);
-  s.p = nullptr; s.cap = 0;
-  HIPCHK(hipMalloc(&s.p, bytes));
-  s.cap = bytes;
   return MJX_OK;
 }
 }  // namespace
@@ -477,38 +471,36 @@ int mjx_bl_gram(int kind, const double* obs, const int32_t* tpos, const double* 
   FeatTableCache* ft;
   if (int rc = get_feat_table(kind, n, &ft)) return rc;
   const int F = ft->F, FA = F + 1, nbt = (FA + GT - 1) / GT, npairs = nbt * (nbt + 1) / 2;
-  static thread_local Scratch part;
+  double* part = nullptr;
   const int T16 = (FA + 15) / 16;
-  const char* no_mfma = getenv("MJX_GRAM_FMA");
-  if (T16 <= GM_TMAX && n <= 24 && !(no_mfma && no_mfma[0] == '1')) {
+  const bool no_mfma = env_flag("MJX_GRAM_FMA", false);
+  if (T16 <= GM_TMAX && n <= 24 && !no_mfma) {
     // fp64 matrix cores: one persistent workgroup per sample range, all features generated once per chunk
     int Z = (int)((N + 2047) / 2048);
     if (Z > 512) Z = 512;
     if (Z < 1) Z = 1;
-    if (int rc = get_scratch(part, (size_t)Z * FA * FA * sizeof(double))) return rc;
-    HIPCHK(hipMemsetAsync(part.p, 0, (size_t)Z * FA * FA * sizeof(double), (hipStream_t)stream));
+    if (int rc = dev_scratch(SITE_GRAM, stream, (size_t)Z * FA * FA * sizeof(double), &part)) return rc;
+    HIPCHK(hipMemsetAsync(part, 0, (size_t)Z * FA * FA * sizeof(double), (hipStream_t)stream));
     const size_t lds = ((size_t)32 * (n + 7) + (size_t)32 * 16 * (T16 | 1)) * sizeof(double);
-    static thread_local bool attr_set = false;
-    if (!attr_set) { HIPCHK(hipFuncSetAttribute((const void*)k_bl_gram_mfma, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024)); attr_set = true; }
-    if (lds > 64 * 1024) return fail(MJX_ERR_UNSUPPORTED, "Gram kernel LDS staging");
-    hipLaunchKernelGGL(k_bl_gram_mfma, dim3(Z), dim3(256), lds, (hipStream_t)stream, ft->dev, F, n, obs, tpos, y, N, (double*)part.p);
-    hipLaunchKernelGGL(k_bl_gram_reduce, dim3(LayerwiseWS::ew_grid((int64_t)FA * FA)), dim3(256), 0, (hipStream_t)stream, (const double*)part.p, Z, FA, G, 16);
+    if (lds > LDS_DEFAULT) return fail(MJX_ERR_UNSUPPORTED, "Gram kernel LDS staging");
+    if (int rc = lds_limit((const void*)k_bl_gram_mfma, lds)) return rc;
+    hipLaunchKernelGGL(k_bl_gram_mfma, dim3(Z), dim3(256), lds, (hipStream_t)stream, ft->dev, F, n, obs, tpos, y, N, part);
+    hipLaunchKernelGGL(k_bl_gram_reduce, dim3(LayerwiseWS::ew_grid((int64_t)FA * FA)), dim3(256), 0, (hipStream_t)stream, (const double*)part, Z, FA, G, 16);
     HIPCHK(hipGetLastError());
     return MJX_OK;
   }
-  if (!(no_mfma && no_mfma[0] == '1') && n <= 64) {
+  if (!no_mfma && n <= 64) {
     // fp64 matrix cores, 128 x 128 feature blocks: one workgroup per (block pair, sample range)
     const int nb = (FA + GB_F - 1) / GB_F, nbp = nb * (nb + 1) / 2;
     int Z = (int)((N + 2047) / 2048);
     int maxz = (768 + nbp - 1) / nbp;                  // ~3 rounds of workgroups on the chip
     if (Z > maxz) Z = maxz;
     if (Z < 1) Z = 1;
-    if (int rc = get_scratch(part, (size_t)Z * FA * FA * sizeof(double))) return rc;
+    if (int rc = dev_scratch(SITE_GRAM, stream, (size_t)Z * FA * FA * sizeof(double), &part)) return rc;
     const size_t lds = (size_t)(32 * (n + 7) + 2 * 32 * GB_FS) * sizeof(double);
-    static thread_local bool attr_blk = false;
-    if (!attr_blk) { HIPCHK(hipFuncSetAttribute((const void*)k_bl_gram_mfma_blk, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024)); attr_blk = true; }
-    hipLaunchKernelGGL(k_bl_gram_mfma_blk, dim3(nbp, Z), dim3(256), lds, (hipStream_t)stream, nb, ft->dev, F, n, obs, tpos, y, N, (double*)part.p);
-    hipLaunchKernelGGL(k_bl_gram_reduce, dim3(LayerwiseWS::ew_grid((int64_t)FA * FA)), dim3(256), 0, (hipStream_t)stream, (const double*)part.p, Z, FA, G, GB_F);
+    if (int rc = lds_limit((const void*)k_bl_gram_mfma_blk, lds)) return rc;
+    hipLaunchKernelGGL(k_bl_gram_mfma_blk, dim3(nbp, Z), dim3(256), lds, (hipStream_t)stream, nb, ft->dev, F, n, obs, tpos, y, N, part);
+    hipLaunchKernelGGL(k_bl_gram_reduce, dim3(LayerwiseWS::ew_grid((int64_t)FA * FA)), dim3(256), 0, (hipStream_t)stream, (const double*)part, Z, FA, G, GB_F);
     HIPCHK(hipGetLastError());
     return MJX_OK;
   }
@@ -516,12 +508,13 @@ int mjx_bl_gram(int kind, const double* obs, const int32_t* tpos, const double* 
   int maxz = (2048 + npairs - 1) / npairs;
   if (Z > maxz) Z = maxz;
   if (Z < 1) Z = 1;
-  if (int rc = get_scratch(part, (size_t)Z * FA * FA * sizeof(double))) return rc;
-  HIPCHK(hipMemsetAsync(part.p, 0, (size_t)Z * FA * FA * sizeof(double), (hipStream_t)stream));
+  if (int rc = dev_scratch(SITE_GRAM, stream, (size_t)Z * FA * FA * sizeof(double), &part)) return rc;
+  HIPCHK(hipMemsetAsync(part, 0, (size_t)Z * FA * FA * sizeof(double), (hipStream_t)stream));
   size_t lds = ((size_t)GKS * n + 2 * (size_t)GKS * (GT + 1)) * sizeof(double);
-  if (lds > 64 * 1024) return fail(MJX_ERR_UNSUPPORTED, "obs dim too large for the Gram kernel's LDS staging");
-  hipLaunchKernelGGL(k_bl_gram, dim3(npairs, Z), dim3(256), lds, (hipStream_t)stream, nbt, ft->dev, F, n, obs, tpos, y, N, (double*)part.p);
-  hipLaunchKernelGGL(k_bl_gram_reduce, dim3(LayerwiseWS::ew_grid((int64_t)FA * FA)), dim3(256), 0, (hipStream_t)stream, (const double*)part.p, Z, FA, G, GT);
+  if (lds > LDS_DEFAULT) return fail(MJX_ERR_UNSUPPORTED, "obs dim too large for the Gram kernel's LDS staging");
+  if (int rc = lds_limit((const void*)k_bl_gram, lds)) return rc;
+  hipLaunchKernelGGL(k_bl_gram, dim3(npairs, Z), dim3(256), lds, (hipStream_t)stream, nbt, ft->dev, F, n, obs, tpos, y, N, part);
+  hipLaunchKernelGGL(k_bl_gram_reduce, dim3(LayerwiseWS::ew_grid((int64_t)FA * FA)), dim3(256), 0, (hipStream_t)stream, (const double*)part, Z, FA, G, GT);
   HIPCHK(hipGetLastError());
   return MJX_OK;
 }
@@ -532,9 +525,10 @@ int mjx_bl_predict(int kind, const double* obs, const int32_t* tpos, int64_t N, 
   FeatTableCache* ft;
   if (int rc = get_feat_table(kind, n, &ft)) return rc;
   int nth = 256;                                          // one observation row per thread in LDS: fewer threads for wide observations
-  while (nth > 64 && (size_t)nth * n * sizeof(double) > 64 * 1024) nth >>= 1;
+  while (nth > 64 && (size_t)nth * n * sizeof(double) > LDS_DEFAULT) nth >>= 1;
   size_t lds = (size_t)nth * n * sizeof(double);
-  if (lds > 64 * 1024) return fail(MJX_ERR_UNSUPPORTED, "obs dim too large for the predict kernel's LDS staging");
+  if (lds > LDS_DEFAULT) return fail(MJX_ERR_UNSUPPORTED, "obs dim too large for the predict kernel's LDS staging");
+  if (int rc = lds_limit((const void*)k_bl_predict, lds)) return rc;
   int grid = (int)((N + nth - 1) / nth); if (grid > 8192) grid = 8192;
   hipLaunchKernelGGL(k_bl_predict, dim3(grid), dim3(nth), lds, (hipStream_t)stream, ft->dev, ft->F, n, obs, tpos, coef, N, out);
   HIPCHK(hipGetLastError());
@@ -546,18 +540,11 @@ int mjx_mlp_predict(const float* feat, int64_t N, int d_in, const int* hidden, i
   if (N == 0) return MJX_OK;
   {
     // the reference's default value network (128 x 128 ReLU) in one launch: csrc/baseline.h k_mlp_predict128 (MJX_MLP_PREDICT_FUSED=0: A/B)
-    const char* e = getenv("MJX_MLP_PREDICT_FUSED");
-    if (!(e && e[0] == '0') && n_hidden == 2 && hidden[0] == 128 && hidden[1] == 128 && d_in <= 64 && (((uintptr_t)params) & 15) == 0 &&
-        mlp_predict_lds_bytes(d_in) <= (size_t)160 * 1024) {
-      int dev = 0, ncu = 256;
-      HIPCHK(hipGetDevice(&dev));
-      (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-      static thread_local std::vector<std::pair<int, size_t>> configured;      // (device, bytes): the dynamic-LDS limit is per device
-      const size_t bytes = mlp_predict_lds_bytes(d_in);
-      size_t* have = nullptr;
-      for (auto& c : configured) if (c.first == dev) have = &c.second;
-      if (!have) { configured.push_back({dev, 0}); have = &configured.back().second; }
-      if (*have < bytes) { HIPCHK(hipFuncSetAttribute((const void*)k_mlp_predict128, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes)); *have = bytes; }
+    const size_t bytes = mlp_predict_lds_bytes(d_in);
+    if (env_flag("MJX_MLP_PREDICT_FUSED", true) && n_hidden == 2 && hidden[0] == 128 && hidden[1] == 128 && d_in <= 64 &&
+        (((uintptr_t)params) & 15) == 0 && bytes <= LDS_MAX) {
+      if (int rc = lds_limit((const void*)k_mlp_predict128, bytes)) return rc;
+      const int ncu = cu_count();
       const int64_t ntiles = (N + 31) / 32;
       const int64_t want = (ntiles + 7) / 8;
       MlpPredictArgs pa{feat, params, out, N, d_in};
@@ -569,29 +556,17 @@ int mjx_mlp_predict(const float* feat, int64_t N, int d_in, const int* hidden, i
   MlpRegressor net; net.init(d_in, hidden, n_hidden);
   const int64_t CH = 1 << 17;
   size_t per_row = 0; for (int i = 0; i < n_hidden; ++i) per_row += hidden[i];
-  // the activation scratch is kept PER STREAM: MLPBaseline.fit_async runs its before / after forwards on a side stream while the
-  // caller's stream may be predicting with another baseline -- one shared block would be written by both at once
-  static thread_local std::vector<std::pair<void*, Scratch>> by_stream;
-  Scratch* scp = nullptr;
-  for (auto& e : by_stream) if (e.first == stream) scp = &e.second;
-  if (!scp) {
-    if (by_stream.size() >= 8) {                 // (streams come and go: forget the oldest block once nothing can still be using it)
-      HIPCHK(hipDeviceSynchronize());
-      if (by_stream.front().second.p) (void)hipFree(by_stream.front().second.p);
-      by_stream.erase(by_stream.begin());
-    }
-    by_stream.push_back({stream, Scratch{}});
-    scp = &by_stream.back().second;
-  }
-  Scratch& sc = *scp;
-  if (int rc = get_scratch(sc, (size_t)CH * (per_row ? per_row : 1) * sizeof(float))) return rc;
+  // (the activation scratch is per stream: MLPBaseline.fit_async runs its before / after forwards on a side stream while the
+  //  caller's stream may be predicting with another baseline -- one shared block would be written by both at once)
+  float* sc = nullptr;
+  if (int rc = dev_scratch(SITE_MLP_PREDICT, stream, (size_t)CH * (per_row ? per_row : 1) * sizeof(float), &sc)) return rc;
   std::vector<float*> acts(n_hidden);
-  { float* q = (float*)sc.p; for (int i = 0; i < n_hidden; ++i) { acts[i] = q; q += (size_t)CH * hidden[i]; } }
+  { float* q = sc; for (int i = 0; i < n_hidden; ++i) { acts[i] = q; q += (size_t)CH * hidden[i]; } }
   for (int64_t r0 = 0; r0 < N; r0 += CH) {
     int64_t rows = (N - r0 < CH) ? N - r0 : CH;
     net.forward(params, feat + r0 * d_in, rows, acts, out + r0, (hipStream_t)stream);
   }
-  HIPCHK(hipGetLastError());
+  HIPCHK(lw_status());
   return MJX_OK;
 }
 
@@ -603,90 +578,54 @@ int mjx_mlp_fit_adam(const float* feat, const float* y, int64_t N, int d_in, con
   hipStream_t st = (hipStream_t)stream;
   HIPCHK(hipMemsetAsync(epoch_loss_out, 0, sizeof(double) * (epochs > 0 ? epochs : 1), st));
   {
-    // persistent single-workgroup trainer (csrc/mlp_fit.h) for the reference's default baseline shape
-    const char* force = getenv("MJX_MLP_FIT_LAUNCHES");
+    // persistent trainers (csrc/mlp_fit.h) for the reference's default baseline shape, 128 x 128 at minibatches of 64: ONE
+    // workgroup while the layout of d_in inputs fits its LDS (d_in <= 55); r05: wider inputs (Ant 111 + 4, Humanoid 376 + 4 =
+    // BASELINE configs[3]) on SEVERAL workgroups of the same trainer -- feature slices of 48, one workgroup (= one CU) per slice,
+    // one grid barrier per 32-sample half (k_mlp_fit<.., MULTI>).  MJX_MLP_FIT_LAUNCHES=1 / MJX_FIT_WIDE=0: the launch route below
+    constexpr int FS = 48, GMAX = 16;
     const int64_t steps_ = N / batch - 1;
-    MlpFitLayout<128> L(d_in, d_in > 31);
-    if (!(force && force[0] == '1') && n_hidden == 2 && hidden[0] == 128 && hidden[1] == 128 && batch == 64 && d_in <= 63 &&
-        L.bytes() <= (size_t)160 * 1024 && steps_ > 0 && epochs > 0) {
-      static thread_local Scratch mvws;
+    const int G = (d_in + FS - 1) / FS;
+    const MlpFitLayout<128> L(d_in, d_in > 31), Lw(FS, true);
+    const MlpFit1pLayout<128> L1(d_in);
+    const bool shape = !env_flag("MJX_MLP_FIT_LAUNCHES", false) && n_hidden == 2 && hidden[0] == 128 && hidden[1] == 128 && batch == 64 &&
+                       steps_ > 0 && epochs > 0;
+    const bool one_wg = shape && d_in <= 63 && L.bytes() <= LDS_MAX;
+    const bool wide = shape && !one_wg && env_flag("MJX_FIT_WIDE", true) && d_in > 48 && G <= GMAX;
+    if (one_wg || wide) {
       const int64_t P = (int64_t)128 * d_in + 128 + 128 * 128 + 128 + 128 + 1;
-      if (int rc = get_scratch(mvws, (size_t)P * 2 * sizeof(float))) return rc;
-      MlpFitArgs a{feat, y, perm, N, d_in, epochs, steps_, params, m, v, (float*)mvws.p, step0, lr, wd, epoch_loss_out};
-      static thread_local bool configured = false;
-      if (!configured) {
-        HIPCHK(hipFuncSetAttribute((const void*)k_mlp_fit<128, 1, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024)));
-        HIPCHK(hipFuncSetAttribute((const void*)k_mlp_fit<128, 2, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024)));
-        HIPCHK(hipFuncSetAttribute((const void*)k_mlp_fit<128, 1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024)));
-        HIPCHK(hipFuncSetAttribute((const void*)k_mlp_fit<128, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024)));
-        HIPCHK(hipFuncSetAttribute((const void*)k_mlp_fit1p<128>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024)));
-        configured = true;
+      float* mvws = nullptr;
+      if (int rc = dev_scratch(wide ? SITE_MLP_FIT_WIDE : SITE_MLP_FIT, stream, (size_t)(wide ? G : 1) * P * 2 * sizeof(float), &mvws)) return rc;
+      MlpFitArgs a{feat, y, perm, N, d_in, epochs, steps_, params, m, v, mvws, step0, lr, wd, epoch_loss_out};
+      if (wide) {
+        // the exchange block and the arrival counter: UNCACHED device memory (stores are acknowledged by memory, loads bypass the
+        // per-XCD L2s -- the workgroups of one grid sit on different XCDs), allocated once per thread and device
+        static thread_local PerDevice<char*> xch_of;
+        char*& xch = xch_of.here();
+        const size_t xbytes = (size_t)2 * GMAX * 128 * 32 * sizeof(float);
+        if (!xch) HIPCHK(hipExtMallocWithFlags((void**)&xch, xbytes + 256, hipDeviceMallocUncached));
+        HIPCHK(hipMemsetAsync(xch + xbytes, 0, 256, st));                       // the counter (the exchange block needs no clearing)
+        a.xch = (float*)xch; a.bar = (unsigned*)(xch + xbytes); a.G = G; a.FS = FS;
+        { const char* f = getenv("MJX_FIT_FAULT"); a.fault = (f && !strcmp(f, "straggler")) ? 1 : 0; }      // (tests/test_gpu_lifecycle.py)
       }
       // r04: the Adam moments a thread owns stay in its registers for the whole run (REGMOM, mlp_fit.h); MJX_FIT_REGMOM=0: the r03
-      // kernels, which stream them through L2 in every step (same arithmetic, same bits)
-      const char* rm = getenv("MJX_FIT_REGMOM");            // (read per call: the tests compare the two in one process)
-      const bool regmom = !(rm && rm[0] == '0');
-      // ... and up to 23 inputs a step is ONE pass over its 64 rows (k_mlp_fit1p: two accumulator chains, every weight fragment
-      // fetched once, 6 barriers instead of 11); MJX_FIT_ONEPASS=0: the two-halves kernel
-      const char* op = getenv("MJX_FIT_ONEPASS");
-      const MlpFit1pLayout<128> L1(d_in);
-      if (d_in <= 23 && regmom && !(op && op[0] == '0') && L1.bytes() <= (size_t)160 * 1024) {
-        hipLaunchKernelGGL((k_mlp_fit1p<128>), dim3(1), dim3(256), L1.bytes(), st, a);
-      } else if (d_in <= 31) {
-        if (regmom) hipLaunchKernelGGL((k_mlp_fit<128, 1, true>), dim3(1), dim3(256), L.bytes(), st, a);
-        else hipLaunchKernelGGL((k_mlp_fit<128, 1, false>), dim3(1), dim3(256), L.bytes(), st, a);
-      } else {                                                // (32 <= d_in <= 55: what 160 KB of LDS hold)
-        if (regmom) hipLaunchKernelGGL((k_mlp_fit<128, 2, true>), dim3(1), dim3(256), L.bytes(), st, a);
-        else hipLaunchKernelGGL((k_mlp_fit<128, 2, false>), dim3(1), dim3(256), L.bytes(), st, a);
-      }
-      HIPCHK(hipGetLastError());
-      return MJX_OK;
-    }
-  }
-  {
-    // r05: wider inputs (Ant 111 + 4, Humanoid 376 + 4 = BASELINE configs[3]) on SEVERAL workgroups of the same persistent trainer:
-    // feature slices of 48, one workgroup (= one CU) per slice, one grid barrier per 32-sample half (k_mlp_fit<.., MULTI>, mlp_fit.h)
-    const char* force = getenv("MJX_MLP_FIT_LAUNCHES");
-    const char* wide = getenv("MJX_FIT_WIDE");
-    const int64_t steps_ = N / batch - 1;
-    constexpr int FS = 48, GMAX = 16;
-    const int G = (d_in + FS - 1) / FS;
-    if (!(force && force[0] == '1') && !(wide && wide[0] == '0') && n_hidden == 2 && hidden[0] == 128 && hidden[1] == 128 && batch == 64 &&
-        d_in > 48 && G <= GMAX && steps_ > 0 && epochs > 0) {
-      MlpFitLayout<128> Lw(FS, true);
-      static thread_local Scratch mvws;
-      const int64_t P = (int64_t)128 * d_in + 128 + 128 * 128 + 128 + 128 + 1;
-      if (int rc = get_scratch(mvws, (size_t)G * P * 2 * sizeof(float))) return rc;
-      // the exchange block and the arrival counter: UNCACHED device memory (stores are acknowledged by memory, loads bypass the
-      // per-XCD L2s -- the workgroups of one grid sit on different XCDs), allocated once per thread and device
-      static thread_local std::vector<std::pair<int, char*>> xch_by_dev;
-      int dev = 0;
-      HIPCHK(hipGetDevice(&dev));
-      char* xch = nullptr;
-      for (auto& e : xch_by_dev) if (e.first == dev) xch = e.second;
-      const size_t xbytes = (size_t)2 * GMAX * 128 * 32 * sizeof(float);
-      if (!xch) {
-        void* q = nullptr;
-        HIPCHK(hipExtMallocWithFlags(&q, xbytes + 256, hipDeviceMallocUncached));
-        xch = (char*)q;
-        xch_by_dev.push_back({dev, xch});
-      }
-      HIPCHK(hipMemsetAsync(xch + xbytes, 0, 256, st));                       // the counter (the exchange block needs no clearing)
-      MlpFitArgs a{feat, y, perm, N, d_in, epochs, steps_, params, m, v, (float*)mvws.p, step0, lr, wd, epoch_loss_out};
-      a.xch = (float*)xch; a.bar = (unsigned*)(xch + xbytes); a.G = G; a.FS = FS;
-      { const char* f = getenv("MJX_FIT_FAULT"); a.fault = (f && !strcmp(f, "straggler")) ? 1 : 0; }      // (tests/test_gpu_lifecycle.py)
-      static thread_local bool configured = false;
-      if (!configured) {
-        HIPCHK(hipFuncSetAttribute((const void*)k_mlp_fit<128, 2, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024)));
-        HIPCHK(hipFuncSetAttribute((const void*)k_mlp_fit<128, 2, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024)));
-        configured = true;
-      }
-      const char* rm = getenv("MJX_FIT_REGMOM");
-      if (!(rm && rm[0] == '0')) hipLaunchKernelGGL((k_mlp_fit<128, 2, true, true>), dim3(G), dim3(256), Lw.bytes(), st, a);
-      else hipLaunchKernelGGL((k_mlp_fit<128, 2, false, true>), dim3(G), dim3(256), Lw.bytes(), st, a);
+      // kernels, which stream them through L2 in every step (same arithmetic, same bits; read per call: the tests compare the two
+      // in one process) ... and up to 23 inputs a step is ONE pass over its 64 rows (k_mlp_fit1p: two accumulator chains, every
+      // weight fragment fetched once, 6 barriers instead of 11); MJX_FIT_ONEPASS=0: the two-halves kernel
+      const bool regmom = env_flag("MJX_FIT_REGMOM", true);
+      const bool onepass = !wide && d_in <= 23 && regmom && env_flag("MJX_FIT_ONEPASS", true) && L1.bytes() <= LDS_MAX;
+      // (d_in, REGMOM, ONEPASS, wide) -> instance, listed in the order the instances have in the code object (that of their
+      // first mention)
+      void (*k)(MlpFitArgs) = nullptr;
+      if (!wide && !regmom)       k = d_in <= 31 ? k_mlp_fit<128, 1, false> : k_mlp_fit<128, 2, false>;
+      else if (!wide && !onepass) k = d_in <= 31 ? k_mlp_fit<128, 1, true> : k_mlp_fit<128, 2, true>;      // (32 <= d_in <= 55: what 160 KB of LDS hold)
+      else if (!wide)             k = k_mlp_fit1p<128>;                                                    // d_in <= 23, REGMOM and ONEPASS
+      else                        k = regmom ? k_mlp_fit<128, 2, true, true> : k_mlp_fit<128, 2, false, true>;   // one 48-feature slice per workgroup
+      const size_t bytes = wide ? Lw.bytes() : onepass ? L1.bytes() : L.bytes();
+      if (int rc = lds_limit((const void*)k, bytes)) return rc;
+      hipLaunchKernelGGL(k, dim3(wide ? G : 1), dim3(256), bytes, st, a);
       // a barrier wait that timed out (a workgroup without a CU) is recorded in a word of its own; this turns it into NaN epoch
       // losses AFTER every workgroup has left -- the last writer of epoch_loss no longer decides
-      hipLaunchKernelGGL(k_mlp_fit_verdict, dim3(1), dim3(64), 0, st, (const unsigned*)a.bar + 1, epoch_loss_out, epochs);
+      if (wide) hipLaunchKernelGGL(k_mlp_fit_verdict, dim3(1), dim3(64), 0, st, (const unsigned*)a.bar + 1, epoch_loss_out, epochs);
       HIPCHK(hipGetLastError());
       return MJX_OK;
     }
@@ -695,10 +634,9 @@ int mjx_mlp_fit_adam(const float* feat, const float* y, int64_t N, int d_in, con
   const int L = net.nL(), bs = batch;
   size_t hsum = 0; for (int i = 0; i < n_hidden; ++i) hsum += hidden[i];
   // scratch: Xb, yb, yhat, d_out, acts (bs x h_l), deltas (bs x h_l), grads (P)
-  static thread_local Scratch sc;
   size_t fl = (size_t)bs * d_in + 3 * (size_t)bs + 2 * (size_t)bs * hsum + (size_t)net.P;
-  if (int rc = get_scratch(sc, fl * sizeof(float))) return rc;
-  float* q = (float*)sc.p;
+  float* q = nullptr;
+  if (int rc = dev_scratch(SITE_MLP_FIT_LAUNCHES, stream, fl * sizeof(float), &q)) return rc;
   float* Xb = q; q += (size_t)bs * d_in;
   float* yb = q; q += bs;
   float* yhat = q; q += bs;
@@ -743,7 +681,7 @@ int mjx_mlp_fit_adam(const float* feat, const float* y, int64_t N, int d_in, con
       hipLaunchKernelGGL(k_adam, dim3((unsigned)((net.P + 255) / 256)), dim3(256), 0, st, params, grads, m, v, net.P, lr, wd, b1, b2, eps, bc1, bc2s);
     }
   }
-  HIPCHK(hipGetLastError());
+  HIPCHK(lw_status());
   return MJX_OK;
 }
 
@@ -751,26 +689,6 @@ int mjx_mlp_fit_adam(const float* feat, const float* y, int64_t N, int d_in, con
 namespace {
 int dyn_net(const int* sizes, int n_sizes, DynNet& net) {
   if (!sizes || !net.init(sizes, n_sizes)) return fail(MJX_ERR_ARG, "bad layer sizes (2 .. %d entries, all > 0)", DYN_MAXL + 1);
-  return MJX_OK;
-}
-// a kernel's static LDS (its __shared__ arrays: k_dyn_fit's reduction block is 128 B); a workgroup gets static + dynamic bytes
-// out of the 160 KiB, so both count against the limit
-int dyn_static_lds(const void* kern, size_t& bytes) {
-  static thread_local std::vector<std::pair<const void*, size_t>> known;
-  for (const auto& e : known)
-    if (e.first == kern) { bytes = e.second; return MJX_OK; }
-  hipFuncAttributes fa{};
-  HIPCHK(hipFuncGetAttributes(&fa, kern));
-  known.emplace_back(kern, fa.sharedSizeBytes);
-  bytes = fa.sharedSizeBytes;
-  return MJX_OK;
-}
-bool dyn_lds_fits(size_t static_bytes, size_t bytes) { return static_bytes + bytes <= (size_t)160 * 1024; }
-int dyn_lds_limit(const void* kern, size_t bytes) {
-  size_t st = 0;
-  if (int rc = dyn_static_lds(kern, st)) return rc;
-  if (!dyn_lds_fits(st, bytes)) return fail(MJX_ERR_UNSUPPORTED, "needs %zu + %zu static bytes of LDS (> 160 KiB)", bytes, st);
-  if (st + bytes > 64 * 1024) HIPCHK(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
   return MJX_OK;
 }
 }  // namespace
@@ -785,7 +703,7 @@ int mjx_dyn_forward(const float* x, int64_t x_stride, int64_t rows, int K, const
   if (rows == 0) return MJX_OK;
   MJX_DEVICE_ENTRY();
   const size_t bytes = sizeof(float) * 3 * DYN_FT * (size_t)net.maxw;
-  if (int rc = dyn_lds_limit((const void*)k_dyn_forward, bytes)) return rc;
+  if (int rc = lds_limit((const void*)k_dyn_forward, bytes)) return rc;
   DynFwdArgs a{net, x, x_stride, rows, params, tr, act, flags, out};
   hipLaunchKernelGGL(k_dyn_forward, dim3((unsigned)((rows + DYN_FT - 1) / DYN_FT), (unsigned)K), dim3(256), bytes, (hipStream_t)stream, a);
   HIPCHK(hipGetLastError());
@@ -816,7 +734,7 @@ int mjx_model_rollout(const float* s0, int64_t N, int H, int K, const int* pol_s
   a.W = a.dyn.maxw > a.pol.maxw ? a.dyn.maxw : a.pol.maxw;
   const int64_t Ppol = actions ? 0 : a.pol.P + m;
   const size_t bytes = sizeof(float) * (size_t)(((Ppol + 3) & ~3) + DYN_RT * (n + m) + 4 * DYN_RT * (int64_t)a.W);
-  if (int rc = dyn_lds_limit((const void*)k_model_rollout, bytes)) return rc;
+  if (int rc = lds_limit((const void*)k_model_rollout, bytes)) return rc;
   hipLaunchKernelGGL(k_model_rollout, dim3((unsigned)((N + DYN_RT - 1) / DYN_RT), (unsigned)K), dim3(256), bytes, (hipStream_t)stream, a);
   HIPCHK(hipGetLastError());
   return MJX_OK;
@@ -839,25 +757,24 @@ int mjx_dyn_fit_adam(const float* x, const float* y, int64_t N, const int* sizes
   int wmax = 0; size_t hsum = 0;
   for (int l = 1; l <= net.nl; ++l) { wmax = net.sz[l] > wmax ? net.sz[l] : wmax; hsum += net.sz[l]; }
   const size_t prep = (size_t)N * (din + dout), mb = (size_t)batch * (din + dout + hsum + 2 * (size_t)wmax);
-  static thread_local Scratch sc;
-  if (int rc = get_scratch(sc, (prep + mb) * sizeof(float))) return rc;
-  float* xn = (float*)sc.p; float* tg = xn + (size_t)N * din;
+  float* xn = nullptr;
+  if (int rc = dev_scratch(SITE_DYN_FIT, stream, (prep + mb) * sizeof(float), &xn)) return rc;
+  float* tg = xn + (size_t)N * din;
   {
     const int64_t tot = N * (din > dout ? din : dout);
     const unsigned grid = (unsigned)((tot + 255) / 256 < 4096 ? (tot + 255) / 256 : 4096);
     hipLaunchKernelGGL(k_dyn_prep, dim3(grid), dim3(256), 0, st, x, y, N, din, dout, in_tr, out_tr, target_mode, xn, tg);
   }
   const float* oaff = target_mode == DYN_TGT_AFFINE ? out_tr : nullptr;
-  // persistent single-launch trainer for hidden widths <= 128 and minibatch <= 64 whose activations fit in LDS;
-  // MJX_DYN_FIT_LAUNCHES=1 forces the launch route (read per call: the tests compare the two routes in one process)
-  const char* force = getenv("MJX_DYN_FIT_LAUNCHES");
+  // persistent single-launch trainer for hidden widths <= 128 and minibatch <= 64 whose activations fit in LDS beside the
+  // kernel's static LDS (its reduction block: 128 B); MJX_DYN_FIT_LAUNCHES=1 forces the launch route (read per call: the tests
+  // compare the two routes in one process)
+  const bool force = env_flag("MJX_DYN_FIT_LAUNCHES", false);
   bool narrow = true;
   for (int l = 1; l < net.nl; ++l) narrow = narrow && net.sz[l] <= 128;
   const size_t fbytes = dyn_fit_lds_bytes(net, batch);
-  size_t fstatic = 0;
-  if (int rc = dyn_static_lds((const void*)k_dyn_fit, fstatic)) return rc;
-  if (!(force && force[0] == '1') && narrow && batch <= 64 && dyn_lds_fits(fstatic, fbytes)) {
-    if (int rc = dyn_lds_limit((const void*)k_dyn_fit, fbytes)) return rc;
+  if (!force && narrow && batch <= 64 && lds_fits((const void*)k_dyn_fit, fbytes)) {
+    if (int rc = lds_limit((const void*)k_dyn_fit, fbytes)) return rc;
     DynFitArgs a{net, xn, tg, idx, steps, batch, params, m, v, step0, lr, wd, act, oaff, loss_out};
     hipLaunchKernelGGL(k_dyn_fit, dim3(1), dim3(1024), fbytes, st, a);
     HIPCHK(hipGetLastError());
@@ -1056,7 +973,7 @@ static int fvp_impl(mjx_ctx* c, const float* v, float* out, void* stream, const 
   // alternate sweep direction: K1 filled the cache front to back, so the first product of a solve starts at the back, the
   // next at the front, ... -- the lines the previous sweep touched last are the ones most likely still held by the
   // memory-side cache (the 592 MB image does not fit; a one-directional walk would evict every line before its reuse)
-  const bool sweep_on = [] { const char* e = getenv("MJX_FVP_SWEEP"); return !(e && e[0] == '0'); }();
+  const bool sweep_on = env_flag("MJX_FVP_SWEEP", true);
   a.reverse = (a.hcache && sweep_on) ? (int)((c->fvp_seq++ & 1u) ^ 1u) : 0;
   if (int rc = dispatch_fused(c, MODE_FVP, a, st)) return rc;
   if (prof) { HIPCHK(hipEventRecord(c->prof_ev[c->prof_used + 1], st)); c->prof_used += 2; }
@@ -1091,7 +1008,7 @@ static int eval_impl(mjx_ctx* c, double* scal_out, void* stream, const PeerPush*
   if (c->ocache_valid && c->N_local <= c->ocache_rows) { a.ocache = c->ocache; a.snap = c->snap; a.snap_trusted = (old_ok && c->lw_old_ok) ? 1 : 0; }
   // K1's normalised-observation image of this batch (same rows, same observations; the kernel checks the input transform
   // against the snapshot before it trusts it) spares K3 the staging and normalisation of the raw observations
-  const bool ximg_on = [] { const char* e = getenv("MJX_K3_XIMG"); return !(e && e[0] == '0'); }();
+  const bool ximg_on = env_flag("MJX_K3_XIMG", true);
   if (ximg_on && a.ocache && c->ximg_ok && c->hcache && c->N_local <= c->ximg_rows && c->obs == c->hcache_obs) a.hcache = c->hcache;
   if (int rc = dispatch_fused(c, MODE_EVAL, a, st)) return rc;
   hipLaunchKernelGGL(k_reduce_scalars, dim3(1), dim3(256), 0, st, c->spartials, 2 * c->grid, scal_out, pp ? *pp : PeerPush{});
@@ -1167,7 +1084,7 @@ int mjx_cg_step(mjx_ctx* c, const float* Ap, float damping, double tol, void* st
     hipLaunchKernelGGL(k_cg_step_reg<8>, dim3(1), dim3(1024), 0, (hipStream_t)stream, Ap, damping, tol, c->cg_x, c->cg_r, c->cg_p,
                        c->cg_scal, (int)c->d);
   else {
-    static const bool multi = [] { const char* e = getenv("MJX_CG_MULTI"); return !(e && e[0] == '0'); }();
+    static const bool multi = env_flag("MJX_CG_MULTI", true);
     hipStream_t st = (hipStream_t)stream;
     if (multi && c->d >= 4 * CGM_G) {                   // (the partials fit c->cg_z: d floats >= 2 x CGM_G doubles)
       // large d: three launches of CGM_G workgroups (vecops.h); c->cg_z serves as their 2 x CGM_G fp64 partials
@@ -1576,9 +1493,9 @@ int mjx_gae(const double* rewards, const double* baseline, const int64_t* offset
 
 int mjx_sum_stats(const double* x, int64_t N, double shift, double* stats_out, void* stream) {
   if (!x || !stats_out || N < 0) return fail(MJX_ERR_ARG, "bad arguments");
-  static thread_local double* part = nullptr;
   const int G = 512;
-  if (!part) HIPCHK(hipMalloc(&part, G * 2 * sizeof(double)));
+  double* part = nullptr;
+  if (int rc = dev_scratch(SITE_SUM_STATS, stream, G * 2 * sizeof(double), &part)) return rc;
   hipLaunchKernelGGL(k_sum_stats_partial, dim3(G), dim3(256), 0, (hipStream_t)stream, x, N, shift, part);
   hipLaunchKernelGGL(k_sum_stats_final, dim3(1), dim3(256), 0, (hipStream_t)stream, part, G, N, stats_out);
   HIPCHK(hipGetLastError());
@@ -1601,7 +1518,7 @@ int mjx_policy_forward(mjx_ctx* c, const float* obs, int64_t N, const float* the
   if (c->lw.cap < N) { if (int rc = c->lw.reserve(N)) return fail(rc, "layer-wise workspace allocation failed"); }
   c->lw.invalidate();                           // the hidden activations of the bound policy are overwritten (scratch)
   c->lw.forward(theta, tr ? tr : c->ident_tr, obs, N, c->lw.T, mean_out, (hipStream_t)stream);
-  HIPCHK(hipGetLastError());
+  HIPCHK(lw_status());
   return MJX_OK;
 }
 
@@ -1618,18 +1535,17 @@ int mjx_policy_minibatch_adam(mjx_ctx* c, int loss, const float* obs, const floa
   const float* trn0 = tr ? tr : c->ident_tr;
   const float* tro0 = tr_old ? tr_old : c->ident_tr;
   // small two-layer nets, minibatches of up to 64 rows: the whole chain of steps in ONE launch (policy_fit.h)
-  const char* no_fit_env = getenv("MJX_NO_POLICY_FIT");      // read per call: the tests run both paths in one process
-  const bool no_fit = no_fit_env && no_fit_env[0] == '1';
+  const bool no_fit = env_flag("MJX_NO_POLICY_FIT", false);      // read per call: the tests run both paths in one process
   if (!no_fit && c->hidden.size() == 2 && c->hidden[0] == c->hidden[1] && (c->hidden[0] == 64 || c->hidden[0] == 32) &&
       B % 4 == 0 && B >= 8 && B <= 64 && c->n <= c->hidden[0] && c->n <= 63 && c->m <= 16) {
     const bool old_net = (loss == 2) && !old_tracks_new;
     const int H = c->hidden[0];
     const size_t bytes = 4 * (H == 64 ? PolicyFitLayout<64>(c->n, c->m).lds_floats(B, old_net) : PolicyFitLayout<32>(c->n, c->m).lds_floats(B, old_net));
-    if (bytes <= 160 * 1024) {
+    if (bytes <= LDS_MAX) {
       PolicyFitArgs a{obs, act, adv, idx, steps, B, c->n, c->m, theta, theta_old, trn0, tro0, loss, old_tracks_new, adam_m, adam_v,
                       step0, lr, clip, loss_trace, (int)(bytes / 4)};
       void (*k)(PolicyFitArgs) = (H == 64) ? k_policy_fit<64> : k_policy_fit<32>;
-      HIPCHK(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+      if (int rc = lds_limit((const void*)k, bytes)) return rc;
       hipLaunchKernelGGL(k, dim3(1), dim3(PFIT_THREADS), bytes, st, a);
       HIPCHK(hipGetLastError());
       return MJX_OK;
@@ -1662,7 +1578,7 @@ int mjx_policy_minibatch_adam(mjx_ctx* c, int loss, const float* obs, const floa
     hipLaunchKernelGGL(k_adam, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, theta, c->mb_grad, adam_m, adam_v, cnt, lr, 0.f,
                        0.9f, 0.999f, 1e-8f, bc1, bc2s);
   }
-  HIPCHK(hipGetLastError());
+  HIPCHK(lw_status());
   return MJX_OK;
 }
 

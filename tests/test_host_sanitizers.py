@@ -13,10 +13,12 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tests", "c", "host_san.cpp")
+SRC_LS = os.path.join(ROOT, "tests", "c", "launch_state_san.cpp")
+HIP_INC = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "include")
+SAN = [("asan_ubsan", ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer"]), ("tsan", ["-fsanitize=thread"])]
 
 
-@pytest.mark.parametrize("name,flags", [("asan_ubsan", ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer"]),
-                                        ("tsan", ["-fsanitize=thread"])])
+@pytest.mark.parametrize("name,flags", SAN)
 def test_host_ingestion_under_sanitizers(tmp_path, name, flags):
     cxx = os.environ.get("CXX", "g++")
     if shutil.which(cxx) is None:
@@ -30,3 +32,26 @@ def test_host_ingestion_under_sanitizers(tmp_path, name, flags):
     r = subprocess.run([exe, "3"], capture_output=True, text=True, timeout=600, env=env)
     # (the pools are leaked on purpose -- no joins in static destructors -- hence detect_leaks=0)
     assert r.returncode == 0 and "host_san ok" in r.stdout and "Sanitizer" not in r.stderr, (r.stdout[-500:], r.stderr[-4000:])
+
+
+@pytest.mark.parametrize("name,flags", SAN)
+def test_launch_state_under_sanitizers(tmp_path, name, flags):
+    """mjrl_amd/csrc/launch_state.h -- the dynamic-LDS attribute per (device, kernel), CU counts, scratch blocks per (site, device,
+    stream) -- is plain host C++ over a handful of HIP runtime calls; tests/c/launch_state_san.cpp supplies those calls itself (a
+    fake runtime with TWO devices, no HIP library) and runs every rule of the layer from four threads at once.  Only the HIP
+    headers are needed, for the types."""
+    cxx = os.environ.get("CXX", "g++")
+    if shutil.which(cxx) is None:
+        pytest.skip("no C++ compiler")
+    if not os.path.exists(os.path.join(HIP_INC, "hip", "hip_runtime_api.h")):
+        pytest.skip("no HIP headers under %s" % HIP_INC)
+    exe = str(tmp_path / ("launch_state_" + name))
+    b = subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-pthread", "-D__HIP_PLATFORM_AMD__", "-I" + HIP_INC] + flags + [SRC_LS, "-o", exe],
+                       capture_output=True, text=True, cwd=os.path.dirname(SRC_LS))
+    if b.returncode != 0 and "sanitize" in b.stderr and ("cannot find" in b.stderr or "unrecognized" in b.stderr):
+        pytest.skip("this toolchain has no %s runtime" % name)
+    assert b.returncode == 0, b.stderr[-3000:]
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:abort_on_error=0", TSAN_OPTIONS="halt_on_error=1 exitcode=66")
+    r = subprocess.run([exe, "3"], capture_output=True, text=True, timeout=600, env=env)
+    # (the tables and the scratch blocks live as long as the process, like the state they stand for -- hence detect_leaks=0)
+    assert r.returncode == 0 and "launch_state_san ok" in r.stdout and "Sanitizer" not in r.stderr, (r.stdout[-500:], r.stderr[-4000:])
