@@ -432,6 +432,31 @@ int mjx_dyn_fit_adam(const float* x, const float* y, int64_t N, const int* sizes
 int mjx_dyn_pred_error(const float* pred, int K, int64_t rows, int n, const float* s_next, const int64_t* seg_off,
                        int nseg, double lim, float* err_out, int32_t* first_out, void* stream);
 
+/* ---- MPC planning on learned-model ensembles (mjrl/algos/model_accel/model_learning_mpc.py) ---- */
+/* Which route mjx_plan_rollout takes for a net dyn_sizes = [n + act_dim, h..., n]: 1 = the register-resident MFMA rollout
+ * (exactly two hidden layers, both widths multiples of 32 up to 128, n <= 64, act_dim <= 32, its LDS image within
+ * 160 KiB; csrc/plan.h), 0 = the generic rollout of mjx_model_rollout, < 0 = bad sizes.  Arithmetic only: no device
+ * work and no runtime call.  MJX_PLAN_MFMA=0 (read by mjx_plan_rollout per call) forces the generic route. */
+int mjx_plan_route(const int* dyn_sizes, int dyn_n_sizes, int act_dim);
+/* trajectory_rollout (model_accel/sampling.py:96-123) of the SAME action sequences (N x H x act_dim, fp32) through K
+ * members in one launch, as MPCPolicy.get_action runs it once per member (model_learning_mpc.py:53-56).  s0: one state
+ * (s0_stride 0; np.tile, sampling.py:108-109) or N x n (s0_stride n).  Parameters, transforms, act and flags as for
+ * mjx_dyn_forward; no clamps, as in the reference.  obs_out[k] (N x H x n) holds the state BEFORE step t.  N = 0 or
+ * H = 0 returns MJX_OK without a launch.  The generic route uses per-host-thread scratch. */
+int mjx_plan_rollout(const float* s0, int64_t s0_stride, int64_t N, int H, int K, const float* actions,
+                     const int* dyn_sizes, int dyn_n_sizes, const float* dyn_params, const float* dyn_tr, int act,
+                     int flags, float* obs_out, void* stream);
+/* score_trajectory_ensemble (model_learning_mpc.py:85-99) and the softmax weighting (:70-74) in fp64 with fixed
+ * summation orders.  obs: K x N x H x n fp32 (mjx_plan_rollout's output), rewards: K x N x H fp64, actions: N x H x m
+ * fp64.  disagreement[i] = sum over (t, j) of the population standard deviation over the K members;
+ * R_out[k N + i] = omega * disagreement[idx] + sum_t gamma^t rewards[k][i][t] with idx = (k N + i) / N = k as the
+ * reference writes it (idx_mode 0; needs K <= N) or idx = i (idx_mode 1); S_out = exp(kappa (R - max R));
+ * seq_out (H x m) = sum S a / (sum S + 1e-6).  obs NULL: no disagreement term (score_trajectory, :101-110).  Uses
+ * per-host-thread scratch. */
+int mjx_plan_score(const float* obs, const double* rewards, const double* actions, int K, int64_t N, int H, int n,
+                   int m, double kappa, double gamma, double omega, int idx_mode, double* R_out, double* S_out,
+                   double* seq_out, void* stream);
+
 /* ---- in-library kernel timing (bench.py roofline) ------------------------- */
 /* While enabled (on = k >= 1), every k-th launch of the dominant Fisher-vector-product kernel
  * (fused k_fused MODE_FVP, or the whole layer-wise FVP chain) is bracketed by hipEvents recorded

@@ -1,0 +1,198 @@
+"""MPC planning on learned-model ensembles, on the GPU.
+
+Mirrors ``mjrl.algos.model_accel.model_learning_mpc`` (reference model_learning_mpc.py:5-110): ``MPCPolicy`` with the same
+constructor arguments, attributes and ``get_action`` semantics, the warm-start shift included.  One ``get_action`` is
+
+1. ``plan_paths`` perturbed action sequences from NumPy's global stream: one ``np.random.normal(size=(N, H, m))`` and the
+   three-tap filter vectorised over N, which gives the numbers of the reference's N ``generate_perturbed_actions`` calls bit
+   for bit and leaves the stream where they leave it;
+2. one upload of the fp64 actions, cast to fp32 on the device (the reference's ``.float()``);
+3. ``mjx_plan_rollout``: all K members in one launch (csrc/plan.h; the register-resident MFMA rollout where the net's shape
+   allows it -- ``mjx_plan_route`` -- and the generic persistent rollout otherwise);
+4. one read-back of the (K, N, H, n) observations and K calls of ``env.env.env.compute_path_rewards(paths)``, the reference's
+   reward contract, which stays a host callback: it gets a dict of that member's fp32 observations and the fp64 actions;
+5. one upload of the (K, N, H) rewards, ``mjx_plan_score`` (disagreement, discounted returns, softmax weights and the weighted
+   sequence in fp64), one read-back of the (H, m) sequence.
+
+The members' parameters and transforms are packed on the device once per planner and again when a member changed: each net
+carries a generation counter that this package's own writes bump (``fit_dynamics`` / ``fit_model``, ``set_params``,
+``set_transformations``), and the key also holds every parameter and transform tensor with its ``_version`` and storage
+(:meth:`MPCPolicy._pack_key`).  A write to ``p.data`` from outside the package is the one change it cannot see:
+:meth:`MPCPolicy.invalidate`.
+
+``fitted_model`` is a list of ``WorldModel`` (a list of one works: its disagreement is 0) or a bare ``WorldModel``.  For a
+bare model the reference raises ``TypeError`` (it calls ``generate_paths(fitted_model=...)``, which has no such argument);
+this class does what that branch evidently intends: the same draws, one rollout, ``score_trajectory`` (no disagreement term).
+
+``reference_indexing``: score_trajectory_ensemble adds ``disagreement[i // num_traj]`` (model_learning_mpc.py:95), which is
+the MEMBER index of row i, so the disagreement of trajectories 0 .. K-1 is what every member's rows get.  True (default)
+reproduces that; False uses the evidently intended per-trajectory index ``i % num_traj``.
+"""
+import numpy as np
+import torch
+
+from ..._lib import check, load, ptr
+from .nn_dynamics import _act_code, _device, _flags, _flat_params, _ints, _packed_transforms, _stream
+
+
+def perturbed_action_batch(num_traj, base_act, filter_coefs):
+    """num_traj consecutive generate_perturbed_actions(base_act, filter_coefs) calls (sampling.py:204-215) as one draw
+    -> (num_traj, H, m) fp64.  normal(size=(N, H, m)) consumes the stream exactly as N draws of (H, m) do."""
+    sigma, b0, b1, b2 = filter_coefs
+    eps = np.random.normal(loc=0, scale=1.0, size=(int(num_traj),) + base_act.shape) * sigma
+    u = base_act + eps
+    u[:, 0] = u[:, 0] * (b0 + b1 + b2)
+    u[:, 1] = b0 * u[:, 1] + (b1 + b2) * u[:, 0]
+    for t in range(2, u.shape[1]):
+        u[:, t] = b0 * u[:, t] + b1 * u[:, t - 1] + b2 * u[:, t - 2]
+    return u
+
+
+class MPCPolicy(object):
+    def __init__(self, env,
+                 plan_horizon,
+                 plan_paths=10,
+                 kappa=1.0,
+                 gamma=1.0,
+                 mean=None,
+                 filter_coefs=None,
+                 seed=123,
+                 warmstart=True,
+                 fitted_model=None,
+                 omega=5.0,
+                 reference_indexing=True,
+                 **kwargs,
+                 ):
+        """Arguments as in the reference (model_learning_mpc.py:6-40), plus reference_indexing (module docstring)."""
+        self.env, self.seed = env, seed
+        self.n, self.m = env.observation_dim, env.action_dim
+        self.plan_horizon, self.num_traj = plan_horizon, plan_paths
+        if fitted_model is None:
+            print("Policy requires a fitted dynamics model")
+            raise SystemExit
+        self.fitted_model = fitted_model
+        self.mean, self.filter_coefs, self.kappa, self.gamma = mean, filter_coefs, kappa, gamma
+        if mean is None:
+            self.mean = np.zeros(self.m)
+        if filter_coefs is None:
+            self.filter_coefs = [np.ones(self.m), 1.0, 0.0, 0.0]
+        self.act_sequence = np.ones((self.plan_horizon, self.m)) * self.mean
+        self.init_act_sequence = self.act_sequence.copy()
+        self.warmstart = warmstart
+        self.omega = omega
+        self.reference_indexing = reference_indexing
+        self._pack = None           # (key, device blocks) of the members' parameters and transforms
+        self._last = None           # device blocks of the last call's scores
+
+    # ---- device state
+    def __getstate__(self):
+        d = dict(self.__dict__)
+        d["_pack"], d["_last"] = None, None
+        return d
+
+    def _members(self):
+        return self.fitted_model if type(self.fitted_model) == list else [self.fitted_model]
+
+    def _pack_key(self, dev):
+        """What the device copy of the members was made from -> (key, the tensors the key names).  Per member: the net's
+        generation counter, which every write path of this package bumps (the fit's write-back through ``p.data.copy_``, which
+        leaves ``p._version`` alone, ``set_params``, ``set_transformations``); per parameter and transform tensor its identity,
+        ``_version`` (in-place edits) and storage; activation and flags.  The tensors are returned to be HELD beside the key, so
+        that an id() in it cannot come back as another tensor's."""
+        nets = [mdl.dynamics_net for mdl in self._members()]
+        held = [t for net in nets for t in list(net.parameters()) + list(net.get_params()["transforms"])]
+        key = (str(dev),) + tuple((id(net), getattr(net, "_generation", 0), _act_code(net), _flags(net)) for net in nets) + \
+            tuple((id(t), t._version, t.data_ptr()) for t in held)
+        return key, held
+
+    def _packed(self, dev):
+        key, held = self._pack_key(dev)
+        if self._pack is None or self._pack[0] != key:
+            nets = [mdl.dynamics_net for mdl in self._members()]
+            sizes = tuple(nets[0].layer_sizes)
+            for net in nets:
+                assert tuple(net.layer_sizes) == sizes, "ensemble members must share one shape"
+            assert len(set((_act_code(net), _flags(net)) for net in nets)) == 1, \
+                "ensemble members must share activation and output transforms"
+            assert (nets[0].state_dim, nets[0].act_dim) == (self.n, self.m), "the models' dims are not the environment's"
+            P = torch.stack([_flat_params(net, dev) for net in nets])
+            tr = torch.stack([_packed_transforms(net, dev) for net in nets])
+            self._pack = (key, dict(sizes=sizes, P=P, tr=tr, act=_act_code(nets[0]), flags=_flags(nets[0])), held)
+        return self._pack[1]
+
+    def invalidate(self):
+        """drop the device copy of the members (after a write to ``p.data`` that went round this package's own functions)"""
+        self._pack = None
+
+    def route(self):
+        """1: the register-resident MFMA rollout serves these members, 0: the generic rollout (mjx_plan_route)"""
+        sizes = tuple(self._members()[0].dynamics_net.layer_sizes)
+        return int(load().mjx_plan_route(_ints(sizes), len(sizes), int(self.m)))
+
+    # ---- the planner
+    def get_action(self, obs):
+        ensemble = type(self.fitted_model) == list
+        dev = _device()
+        lib = load()
+        pk = self._packed(dev)
+        K, N, H, n, m = len(self._members()), int(self.num_traj), int(self.plan_horizon), int(self.n), int(self.m)
+        actions = perturbed_action_batch(N, self.act_sequence, self.filter_coefs)
+        st = _stream(dev)
+        a64 = torch.from_numpy(np.ascontiguousarray(actions)).to(dev)
+        a32 = torch.empty((N, H, m), dtype=torch.float32, device=dev)
+        check(lib.mjx_cast_f64_f32(ptr(a64), N * H * m, ptr(a32), st))
+        s0 = np.asarray(obs)
+        s0_d = torch.from_numpy(np.ascontiguousarray(s0)).to(dev, torch.float32)
+        assert s0.shape in ((n,), (N, n)), "obs is one state (n) or one per trajectory (N, n)"
+        obs_d = torch.empty((K, N, H, n), dtype=torch.float32, device=dev)
+        check(lib.mjx_plan_rollout(ptr(s0_d), 0 if s0.ndim == 1 else n, N, H, K, ptr(a32), _ints(pk["sizes"]), len(pk["sizes"]),
+                                   ptr(pk["P"]), ptr(pk["tr"]), pk["act"], pk["flags"], ptr(obs_d), st))
+        obs_h = obs_d.cpu().numpy()
+        rewards = np.empty((K, N, H), np.float64)
+        for k in range(K):
+            paths = dict(observations=obs_h[k], actions=actions)
+            self.env.env.env.compute_path_rewards(paths)        # populates paths['rewards']
+            rewards[k] = paths["rewards"]
+        r_d = torch.from_numpy(rewards).to(dev)
+        out = torch.empty(H * m + 2 * K * N, dtype=torch.float64, device=dev)
+        seq_d, R_d, S_d = out[:H * m], out[H * m:H * m + K * N], out[H * m + K * N:]
+        check(lib.mjx_plan_score(ptr(obs_d) if ensemble else None, ptr(r_d), ptr(a64), K, N, H, n, m, float(self.kappa),
+                                 float(self.gamma), float(self.omega), 0 if self.reference_indexing else 1, ptr(R_d), ptr(S_d),
+                                 ptr(seq_d), st))
+        act_sequence = seq_d.cpu().numpy().reshape(H, m)
+        self._last = (R_d, S_d)
+        action = act_sequence[0].copy()
+        if self.warmstart:
+            self.act_sequence[:-1] = act_sequence[1:]
+            self.act_sequence[-1] = self.mean.copy()
+        else:
+            self.act_sequence = self.init_act_sequence.copy()
+        return action
+
+    def last_scores(self):
+        """(R, S) of the last get_action: the K N trajectory scores and their softmax weights (fp64, read back on demand)"""
+        if self._last is None:
+            return None
+        return self._last[0].cpu().numpy(), self._last[1].cpu().numpy()
+
+    # ---- the reference's scoring functions, in NumPy, for callers that use them
+    def score_trajectory_ensemble(self, paths, paths_list):
+        """model_learning_mpc.py:85-99; the same per-score summation order (omega * disagreement first, then t ascending)"""
+        total_traj, horizon = paths['rewards'].shape[0], paths['rewards'].shape[1]
+        predictions = [p['observations'] for p in paths_list]
+        disagreement = np.std(predictions, axis=0)
+        disagreement = np.sum(disagreement, axis=(1, 2))
+        idx = np.arange(total_traj) // self.num_traj if self.reference_indexing else np.arange(total_traj) % self.num_traj
+        scores = np.zeros(total_traj)
+        scores += self.omega * disagreement[idx]
+        for t in range(horizon):
+            scores += (self.gamma ** t) * paths["rewards"][:, t]
+        return scores
+
+    def score_trajectory(self, paths):
+        """model_learning_mpc.py:101-110"""
+        num_traj, horizon = paths["rewards"].shape[0], paths["rewards"].shape[1]
+        scores = np.zeros(num_traj)
+        for t in range(horizon):
+            scores += (self.gamma ** t) * paths["rewards"][:, t]
+        return scores

@@ -315,6 +315,7 @@ def _fit(net, opt, X, Y, target_mode, batch_size, epochs, max_steps):
         for p in net.parameters():
             p.data.copy_(P[k:k + p.numel()].view_as(p))
             k += p.numel()
+    net._generation = getattr(net, "_generation", 0) + 1     # (p.data.copy_ leaves p._version as it was)
     return epoch_means(loss.cpu().numpy(), num_steps, ran)
 
 
@@ -342,6 +343,7 @@ class DynamicsNet(nn.Module):
         self.nonlinearity = torch.relu
         self.residual, self.use_mask = residual, use_mask
         self._apply_out_transforms = True
+        self._generation = 0        # bumped by every write of this package to the parameters or transforms (holders of device copies)
         self.set_transformations(s_shift, s_scale, a_shift, a_scale, out_shift, out_scale)
 
     def set_transformations(self, s_shift=None, s_scale=None,
@@ -359,6 +361,7 @@ class DynamicsNet(nn.Module):
         device = next(self.parameters()).data.device
         (self.s_shift, self.s_scale, self.a_shift, self.a_scale, self.out_shift, self.out_scale) = [v.to(device) for v in vals]
         self.mask = self.out_scale >= 1e-8          # output columns without variation are forced to zero
+        self._generation = getattr(self, "_generation", 0) + 1
         self.transformations = dict(s_shift=self.s_shift, s_scale=self.s_scale, a_shift=self.a_shift, a_scale=self.a_scale,
                                     out_shift=self.out_shift, out_scale=self.out_scale)
 
@@ -384,6 +387,7 @@ class DynamicsNet(nn.Module):
         s_shift, s_scale, a_shift, a_scale, out_shift, out_scale = new_params['transforms']
         for idx, p in enumerate(self.parameters()):
             p.data = new_weights[idx]
+        self._generation = getattr(self, "_generation", 0) + 1
         self.set_transformations(s_shift, s_scale, a_shift, a_scale, out_shift, out_scale)
 
 

@@ -5,7 +5,8 @@ ONE persistent launch (``mjx_model_rollout``, csrc/dynamics.h) in which each wor
 ensemble member through all H steps: policy mean, + noise * exp(log_std), action clamp, dynamics, state clamp.  The noise
 is the reference's: ``torch.randn((N, m))`` once per step, drawn on the host from torch's global stream in the same order
 (:func:`draw_rollout_noise`) and uploaded once, so the noisy rollouts see the same numbers.  Real-environment sampling
-(``sample_paths``, ``evaluate_policy``) is out of scope here.
+(``sample_paths``, ``evaluate_policy``) are host loops around ``policy.get_action`` -- for an
+:class:`~mjrl_amd.algos.model_accel.model_learning_mpc.MPCPolicy` that call is where the GPU work happens.
 """
 import numpy as np
 import torch
@@ -140,6 +141,57 @@ def trajectory_rollout(actions, learned_model, init_states):
 
 
 # ===========================================================
+# Rollout policy (parametric or implicit MPC) on real env
+# ===========================================================
+
+def stack_tensor_dict_list(tensor_dict_list):
+    """mjrl.utils.tensor_utils.stack_tensor_dict_list: a list of (nested) dicts -> a (nested) dict of np.array(list)"""
+    out = dict()
+    for k in list(tensor_dict_list[0].keys()):
+        vals = [x[k] for x in tensor_dict_list]
+        out[k] = stack_tensor_dict_list(vals) if isinstance(tensor_dict_list[0][k], dict) else np.array(vals)
+    return out
+
+
+def sample_paths(num_traj,
+                 env,
+                 policy,  # mpc policy on fitted model
+                 horizon=1e6,
+                 eval_mode=True,
+                 base_seed=None,
+                 noise_level=0.1,
+                 ):
+    """sampling.py:131-184: num_traj episodes of `policy` on the real environment.  Exploration noise (eval_mode False, array
+    actions) is np.random.uniform from NumPy's global stream; a list-valued get_action is [action, {'evaluation': ...}]."""
+    env = _as_env(env)
+    if base_seed is not None:
+        env.set_seed(base_seed)
+    horizon = min(horizon, env.horizon)
+    paths = []
+    for ep in range(num_traj):
+        env.reset()
+        observations, actions, rewards, env_infos = [], [], [], []
+        t, done = 0, False
+        while t < horizon and done is False:
+            obs = env.get_obs()
+            ifo = env.get_env_infos()
+            act = policy.get_action(obs)
+            if eval_mode is False and type(act) != list:
+                act = act + np.random.uniform(low=-noise_level, high=noise_level, size=act.shape[0])
+            if type(act) == list:
+                act = act[0] if eval_mode is False else act[1]['evaluation']
+            next_obs, reward, done, _ = env.step(act)
+            t = t + 1
+            observations.append(obs)
+            actions.append(act)
+            rewards.append(reward)
+            env_infos.append(ifo)
+        paths.append(dict(observations=np.array(observations), actions=np.array(actions), rewards=np.array(rewards),
+                          terminated=done, env_infos=stack_tensor_dict_list(env_infos)))
+    return paths
+
+
+# ===========================================================
 # Utility functions
 # ===========================================================
 
@@ -169,6 +221,51 @@ def generate_paths(num_traj, learned_model, start_state, base_act, filter_coefs,
         np.random.seed(base_seed)
     act = np.array([generate_perturbed_actions(base_act, filter_coefs) for _ in range(num_traj)])
     return trajectory_rollout(act, learned_model, start_state)
+
+
+def evaluate_policy(e, policy, learned_model, noise_level=0.0,
+                    real_step=False, num_episodes=10, visualize=False):
+    """sampling.py:235-283: roll `policy` out on e -- on the real simulator (real_step) or by setting the learned model's
+    prediction as the simulator's state -- and record the paths.  Noise is e.env.env.np_random.uniform."""
+    paths = []
+    for ep in range(num_episodes):
+        e.reset()
+        observations, actions, rewards, env_infos = [], [], [], []
+        t, done = 0, False
+        while t < e.horizon and done is False:
+            o = e.get_obs()
+            ifo = e.get_env_infos()
+            a = policy.get_action(o)
+            if type(a) == list:
+                a = a[1]['evaluation']
+            if noise_level > 0.0:
+                a = a + e.env.env.np_random.uniform(low=-noise_level, high=noise_level, size=a.shape[0])
+            if real_step is False:
+                next_s = learned_model.predict(o, a)
+                r = 0.0                                 # (filled in by compute_path_rewards below)
+                e.env.env.set_fitted_state(next_s)
+            else:
+                next_o, r, done, ifo2 = e.step(a)
+                ifo = ifo2 if ifo == {} else ifo
+            if visualize:
+                e.render()
+            t = t + 1
+            observations.append(o)
+            actions.append(a)
+            rewards.append(r)
+            env_infos.append(ifo)
+        path = dict(observations=np.array(observations), actions=np.array(actions), rewards=np.array(rewards),
+                    env_infos=stack_tensor_dict_list(env_infos))
+        if real_step is False:
+            e.env.env.compute_path_rewards(path)
+            try:
+                path = e.env.env.truncate_paths([path])[0]
+            except Exception:
+                pass
+        paths.append(path)
+        if visualize:
+            print("episode score = %f " % np.sum(path['rewards']))
+    return paths
 
 
 def enforce_tensor_bounds(torch_tensor, min_val=None, max_val=None, large_value=float(1e4), device=None):

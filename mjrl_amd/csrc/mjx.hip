@@ -27,6 +27,7 @@
 #include "launch_state.h"
 #include "layerwise.h"
 #include "mlp_fit.h"
+#include "plan.h"
 #include "vecops.h"
 
 namespace {
@@ -57,7 +58,7 @@ int lds_limit(const void* kern, size_t bytes) {
   if (e) return fail(e, "dynamic LDS limit of %zu bytes: %s", bytes, hipGetErrorString((hipError_t)e));
   return MJX_OK;
 }
-enum ScratchSite { SITE_GRAM, SITE_MLP_PREDICT, SITE_MLP_FIT, SITE_MLP_FIT_WIDE, SITE_MLP_FIT_LAUNCHES, SITE_DYN_FIT, SITE_SUM_STATS };
+enum ScratchSite { SITE_GRAM, SITE_MLP_PREDICT, SITE_MLP_FIT, SITE_MLP_FIT_WIDE, SITE_MLP_FIT_LAUNCHES, SITE_DYN_FIT, SITE_SUM_STATS, SITE_PLAN_ROLLOUT, SITE_PLAN_SCORE };
 template <class T>
 int dev_scratch(ScratchSite site, void* stream, size_t bytes, T** out) {
   HIPCHK(mjx::scratch(site, (hipStream_t)stream, bytes, (void**)out));
@@ -736,6 +737,104 @@ int mjx_model_rollout(const float* s0, int64_t N, int H, int K, const int* pol_s
   const size_t bytes = sizeof(float) * (size_t)(((Ppol + 3) & ~3) + DYN_RT * (n + m) + 4 * DYN_RT * (int64_t)a.W);
   if (int rc = lds_limit((const void*)k_model_rollout, bytes)) return rc;
   hipLaunchKernelGGL(k_model_rollout, dim3((unsigned)((N + DYN_RT - 1) / DYN_RT), (unsigned)K), dim3(256), bytes, (hipStream_t)stream, a);
+  HIPCHK(hipGetLastError());
+  return MJX_OK;
+}
+
+// ---------------------------------------------------------------------------- MPC planning on learned models (csrc/plan.h)
+namespace {
+// The k_plan_rollout instance that serves a net, if one does: exactly two hidden layers, both widths multiples of 32 up to 128,
+// n <= 64, actions within the slots a lane keeps ahead, and an LDS image within LDS_MAX (the kernel has no static LDS, so the
+// image is its whole footprint).  Plain arithmetic: no device work, no runtime call.
+struct PlanShape { int HB = 0, NB = 0; size_t bytes = 0; };
+bool plan_shape(const DynNet& net, int m, PlanShape& ps) {
+  if (net.nl != 3) return false;
+  const int n = net.dout(), h1 = net.sz[1], h2 = net.sz[2];
+  if (h1 % 32 || h2 % 32 || h1 > 128 || h2 > 128 || n > 64 || plan_pad8(m) > PLAN_MAX_M8) return false;
+  ps.HB = (h1 > h2 ? h1 : h2) / 32; ps.NB = (n + 31) / 32;
+  ps.bytes = sizeof(float) * plan_lds_floats(ps.HB, ps.NB, n, m);
+  return ps.bytes <= LDS_MAX;
+}
+typedef void (*PlanKernel)(PlanArgs);
+PlanKernel plan_kernel(int HB, int NB) {
+  static const PlanKernel tab[4][2] = {{k_plan_rollout<1, 1>, k_plan_rollout<1, 2>}, {k_plan_rollout<2, 1>, k_plan_rollout<2, 2>},
+                                       {k_plan_rollout<3, 1>, k_plan_rollout<3, 2>}, {k_plan_rollout<4, 1>, k_plan_rollout<4, 2>}};
+  return tab[HB - 1][NB - 1];
+}
+}  // namespace
+
+int mjx_plan_route(const int* dyn_sizes, int dyn_n_sizes, int act_dim) {
+  DynNet net;
+  if (int rc = dyn_net(dyn_sizes, dyn_n_sizes, net)) return rc;
+  if (act_dim <= 0 || net.din() != net.dout() + act_dim) return fail(MJX_ERR_ARG, "dyn_sizes must be [n + m, h..., n] with m = act_dim > 0");
+  PlanShape ps;
+  return plan_shape(net, act_dim, ps) ? 1 : 0;
+}
+
+int mjx_plan_rollout(const float* s0, int64_t s0_stride, int64_t N, int H, int K, const float* actions, const int* dyn_sizes,
+                     int dyn_n_sizes, const float* dyn_params, const float* dyn_tr, int act, int flags, float* obs_out, void* stream) {
+  DynNet net;
+  if (int rc = dyn_net(dyn_sizes, dyn_n_sizes, net)) return rc;
+  const int n = net.dout(), m = net.din() - n;
+  if (!s0 || !actions || !dyn_params || !dyn_tr || !obs_out || N < 0 || H < 0 || K <= 0 || K > 65535 || m <= 0 ||
+      (s0_stride != 0 && s0_stride != n) || (act != DYN_ACT_RELU && act != DYN_ACT_TANH))
+    return fail(MJX_ERR_ARG, "bad arguments");
+  if (N == 0 || H == 0) return MJX_OK;
+  MJX_DEVICE_ENTRY();
+  hipStream_t st = (hipStream_t)stream;
+  PlanShape ps;
+  if (env_flag("MJX_PLAN_MFMA", true) && plan_shape(net, m, ps)) {      // (read per call: A/B runs in one process)
+    const PlanKernel kern = plan_kernel(ps.HB, ps.NB);
+    const int e = mjx::dyn_lds((const void*)kern, ps.bytes);
+    if (e == 0) {
+      PlanArgs a{s0, s0_stride, actions, dyn_params, dyn_tr, obs_out, N, net.P, H, n, m, net.sz[1], net.sz[2], act, flags};
+      hipLaunchKernelGGL(kern, dim3((unsigned)((N + 127) / 128), (unsigned)K), dim3(256), ps.bytes, st, a);
+      HIPCHK(hipGetLastError());
+      return MJX_OK;
+    }
+    if (e != mjx::LDS_OVER) (void)hipGetLastError();                     // a refusal falls back to the generic route
+  }
+  // generic route: k_model_rollout with the actions given, as mjx_model_rollout launches it; its action copy and the tiled
+  // start state go to scratch
+  float* scr = nullptr;
+  const size_t act_floats = (size_t)K * N * H * m, s0_floats = s0_stride ? 0 : (size_t)N * n;
+  if (int rc = dev_scratch(SITE_PLAN_ROLLOUT, stream, (act_floats + s0_floats) * sizeof(float), &scr)) return rc;
+  if (!s0_stride) {
+    const int64_t tot = N * n;
+    hipLaunchKernelGGL(k_plan_tile_s0, dim3((unsigned)((tot + 255) / 256 < 1024 ? (tot + 255) / 256 : 1024)), dim3(256), 0, st, s0, N, n, scr + act_floats);
+    s0 = scr + act_floats;
+  }
+  RolloutArgs a{};
+  a.dyn = net; a.N = N; a.H = H; a.s0 = s0; a.actions = actions; a.dyn_P = dyn_params; a.dyn_tr = dyn_tr; a.act = act; a.flags = flags;
+  a.obs = obs_out; a.act_out = scr; a.W = net.maxw;
+  const size_t bytes = sizeof(float) * (size_t)(DYN_RT * (n + m) + 4 * DYN_RT * (int64_t)a.W);
+  if (int rc = lds_limit((const void*)k_model_rollout, bytes)) return rc;
+  hipLaunchKernelGGL(k_model_rollout, dim3((unsigned)((N + DYN_RT - 1) / DYN_RT), (unsigned)K), dim3(256), bytes, st, a);
+  HIPCHK(hipGetLastError());
+  return MJX_OK;
+}
+
+int mjx_plan_score(const float* obs, const double* rewards, const double* actions, int K, int64_t N, int H, int n, int m, double kappa,
+                   double gamma, double omega, int idx_mode, double* R_out, double* S_out, double* seq_out, void* stream) {
+  if (!rewards || !actions || !R_out || !S_out || !seq_out || K <= 0 || K > 65535 || N <= 0 || H <= 0 || n <= 0 || m <= 0 ||
+      (idx_mode != PLAN_IDX_REFERENCE && idx_mode != PLAN_IDX_TRAJECTORY))
+    return fail(MJX_ERR_ARG, "bad arguments");
+  if (obs && idx_mode == PLAN_IDX_REFERENCE && K > N)
+    return fail(MJX_ERR_ARG, "the reference's index reads disagreement[member]: needs K <= N (model_learning_mpc.py:95)");
+  MJX_DEVICE_ENTRY();
+  hipStream_t st = (hipStream_t)stream;
+  double* scr = nullptr;
+  if (int rc = dev_scratch(SITE_PLAN_SCORE, stream, (size_t)(N + 1) * sizeof(double), &scr)) return rc;
+  double* dis = scr + 1;
+  if (obs) {
+    const int64_t need = idx_mode == PLAN_IDX_REFERENCE ? K : N;         // (the reference reads entries 0 .. K-1 only)
+    hipLaunchKernelGGL(k_plan_disagree, dim3((unsigned)need), dim3(64), 0, st, obs, K, N, (int64_t)H * n, dis);
+  }
+  const int64_t T = K * N;
+  hipLaunchKernelGGL(k_plan_returns, dim3((unsigned)((T + 255) / 256)), dim3(256), 0, st, rewards, obs ? dis : nullptr, K, N, H, gamma, omega,
+                     idx_mode, R_out);
+  hipLaunchKernelGGL(k_plan_softmax, dim3(1), dim3(1024), 0, st, R_out, T, kappa, S_out, scr);
+  hipLaunchKernelGGL(k_plan_sequence, dim3((unsigned)(H * m)), dim3(256), 0, st, S_out, scr, actions, K, N, (int64_t)H * m, seq_out);
   HIPCHK(hipGetLastError());
   return MJX_OK;
 }

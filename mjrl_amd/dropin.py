@@ -36,10 +36,11 @@ def _aliases():
 def _model_accel_aliases():
     """model-based NPG (reference mjrl/algos/model_accel/): bound by install() next to _aliases(), kept apart from its returned
     list, which names the core bindings"""
-    from .algos.model_accel import model_accel_npg, nn_dynamics, sampling
+    from .algos.model_accel import model_accel_npg, model_learning_mpc, nn_dynamics, sampling
     return {
         "mjrl.algos.model_accel.nn_dynamics": nn_dynamics,          # WorldModel / DynamicsNet / RewardNet
-        "mjrl.algos.model_accel.sampling": sampling,                # policy_rollout / trajectory_rollout
+        "mjrl.algos.model_accel.sampling": sampling,                # policy_rollout / trajectory_rollout / sample_paths / evaluate_policy
+        "mjrl.algos.model_accel.model_learning_mpc": model_learning_mpc,   # MPCPolicy
         "mjrl.algos.model_accel.model_accel_npg": model_accel_npg,  # ModelAccelNPG
     }
 
