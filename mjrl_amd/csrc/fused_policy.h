@@ -84,6 +84,11 @@ struct FusedArgs {
 // >= 4 accumulators alternate (gW2, the 4x4x1 form of gW1) or the chain is made of 64-cycle 32x32x2 instructions.
 #define MJX_MFMA_ACC(acc, a, b) asm volatile("v_mfma_f32_32x32x2_f32 %0, %1, %2, %0" : "+a"(acc) : "v"(a), "v"(b))
 #define MJX_MFMA4_ACC(acc, a, b) asm volatile("v_mfma_f32_4x4x1_16b_f32 %0, %1, %2, %0" : "+a"(acc) : "v"(a), "v"(b))
+// The bf16 counterpart (R9 of the bf16x3 cached Fisher-vector product; a, b: four registers of 8 bf16 each).  Its operands are
+// pieces a vector-ALU instruction has just written, and a VGPR written by the VALU needs 2 wait states before an MFMA reads it as
+// SrcA / SrcB; the hazard recogniser pads nothing around inline assembly, so the two states open the statement itself (they
+// pass in the shadow of the MFMA in front: the matrix pipe is busy for 32 cycles per instruction).
+#define MJX_MFMA_BF16_ACC(acc, a, b) asm volatile("s_nop 1\n\tv_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+a"(acc) : "v"(a), "v"(b))
 // 4- and 8-byte LDS accesses of the cached Fisher-vector product.  (Measured, r03: making them volatile LDS-space accesses keeps
 // hipcc from pairing them into ds_read2 / ds_write2 -- whose 8-bit offset fields cost a vector add per pair to re-base the
 // address, 48 per tile -- and saves 2.5 % of the kernel's cycles, but the chip gives the same 2.5 % back in clock: no
@@ -243,18 +248,20 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 #define MJX_MFMA_BF16(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, (a)), __builtin_bit_cast(bf16x8, (b)), (c), 0, 0, 0)
 struct Pc3 { u32x4 p[3]; };                      // hi, mid, lo: 8 bf16 each (one operand of v_mfma_f32_32x32x16_bf16)
+// values 2 k, 2 k + 1 of an operand -> register k of its three pieces (11 vector-ALU instructions)
+__device__ __forceinline__ void split3_pair(Pc3& o, int k, float xa, float xb) {
+  const uint32_t ua = __float_as_uint(xa), ub = __float_as_uint(xb);
+  const float ra = xa - __uint_as_float(ua & 0xffff0000u), rb = xb - __uint_as_float(ub & 0xffff0000u);
+  const uint32_t va = __float_as_uint(ra), vb = __float_as_uint(rb);
+  const float la = ra - __uint_as_float(va & 0xffff0000u), lb = rb - __uint_as_float(vb & 0xffff0000u);
+  o.p[0][k] = __builtin_amdgcn_perm(ub, ua, 0x07060302u);
+  o.p[1][k] = __builtin_amdgcn_perm(vb, va, 0x07060302u);
+  o.p[2][k] = __builtin_amdgcn_perm(__float_as_uint(lb), __float_as_uint(la), 0x07060302u);
+}
 __device__ __forceinline__ Pc3 split3(const float (&x)[8]) {
   Pc3 o;
 #pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const uint32_t ua = __float_as_uint(x[2 * k]), ub = __float_as_uint(x[2 * k + 1]);
-    const float ra = x[2 * k] - __uint_as_float(ua & 0xffff0000u), rb = x[2 * k + 1] - __uint_as_float(ub & 0xffff0000u);
-    const uint32_t va = __float_as_uint(ra), vb = __float_as_uint(rb);
-    const float la = ra - __uint_as_float(va & 0xffff0000u), lb = rb - __uint_as_float(vb & 0xffff0000u);
-    o.p[0][k] = __builtin_amdgcn_perm(ub, ua, 0x07060302u);
-    o.p[1][k] = __builtin_amdgcn_perm(vb, va, 0x07060302u);
-    o.p[2][k] = __builtin_amdgcn_perm(__float_as_uint(lb), __float_as_uint(la), 0x07060302u);
-  }
+  for (int k = 0; k < 4; ++k) split3_pair(o, k, x[2 * k], x[2 * k + 1]);
   return o;
 }
 // the pieces of registers 8 s .. 8 s + 7 of a 32x32 accumulator (K-step s of the next layer's operand)
@@ -390,7 +397,7 @@ struct RawSlab {
   }
 };
 
-template <int H1, int H2, int NT1, int MP, int MODE, bool DBG = false, int NPC = 0, bool CACHED = false, bool BF3 = false>
+template <int H1, int H2, int NT1, int MP, int MODE, bool DBG = false, int NPC = 0, bool CACHED = false, bool BF3 = false, bool BF3R9 = false>
 __global__ __launch_bounds__(256, (MODE == MODE_EVAL && !DBG && MP <= 8) ? 2 : 1) void k_fused(FusedArgs A) {
   using LT = FusedLayout<H1, H2, NT1, MP>;
   constexpr int MT1 = LT::MT1, MT2 = LT::MT2, S2 = LT::S2, S3 = LT::S3, ST = LT::ST;
@@ -410,6 +417,9 @@ __global__ __launch_bounds__(256, (MODE == MODE_EVAL && !DBG && MP <= 8) ? 2 : 1
   // bf16x3 cached Fisher-vector product (64 x 64): R3 (t2 += W2 t1) and R8 (delta1 = W2^T delta2) on v_mfma_f32_32x32x16_bf16
   constexpr bool XBF3 = (MODE == MODE_FVP) && CACHED && BF3;
   static_assert(!BF3 || (CACHED && MODE == MODE_FVP && H1 == 64 && H2 == 64), "bf16x3: the cached 64 x 64 Fisher-vector product only");
+  // ... and R9 (gW2 += delta2^T h1) as well: BF3R9 (MJX_FVP_BF16X3_R9=0 keeps it on fp32 MFMAs)
+  constexpr bool XR9 = XBF3 && BF3R9;
+  static_assert(!BF3R9 || BF3, "bf16x3 R9: an option of the bf16x3 kernel");
   const LT L(NPC ? NPC - 1 : n, EV2, XBF3);
   const int NP = NPC ? NPC : L.NP;                // compile-time when the variant is specialised for the obs dim
   const int S1 = NP + 2;
@@ -1315,11 +1325,82 @@ __global__ __launch_bounds__(256, (MODE == MODE_EVAL && !DBG && MP <= 8) ? 2 : 1
       }
       // ---------------- R9: gW2[u2][u1] += sum_s delta2[s][u2] h1[s][u1]   (B operand: h1^T from bufB, kept for the burst below)
       f32x4 bcs[4][MT1];
+      if constexpr (XR9) {
+        // bf16x3: the K dimension is the sample, and registers 8 s .. 8 s + 7 of dl2u[mt] and of the h1^T fetches (q = 2 s, 2 s + 1)
+        // hold the SAME 8 samples on the same lane half -- K-step s's A and B operands as they lie (any assignment of samples to
+        // the instruction's 16 k-slots is right as long as both operands use the same one).  The accumulator layout is that of
+        // the fp32 instruction.  Pieces outermost, the four accumulators innermost (round-robin, as the fp32 form); K-step 1's
+        // operands are split between K-step 0's MFMAs, one register pair (11 VALU) per gap; the h1^T values VE needs come from
+        // bufB again between K-step 1's MFMAs (free there), so no fp32 operand outlives its split.  The placement is by program
+        // order: the statements are opaque to the scheduler, so every gap ends in a scheduling barrier.
+        f32x4 hq[4][MT1];
 #pragma unroll
-      for (int nt = 0; nt < MT1; ++nt) bcs[0][nt] = *(const f32x4*)&bufB[(32 * nt + j) * ST + 4 * hi];
-      __builtin_amdgcn_sched_barrier(0);
-      MJX_STAMP(8);
-      {
+        for (int q = 0; q < 2; ++q)
+#pragma unroll
+          for (int nt = 0; nt < MT1; ++nt) hq[q][nt] = *(const f32x4*)&bufB[(32 * nt + j) * ST + 8 * q + 4 * hi];
+        __builtin_amdgcn_sched_barrier(0);
+        MJX_STAMP(8);
+        // grad b2 first (the addends and their order are VE's): delta2^T's registers are then dead K-step by K-step
+#pragma unroll
+        for (int nt = 0; nt < MT2; ++nt) {
+          f32x2 s2 = {dl2u[nt][0], dl2u[nt][1]};
+#pragma unroll
+          for (int r = 2; r < 16; r += 2) s2 += f32x2{dl2u[nt][r], dl2u[nt][r + 1]};
+          sb2[nt] += s2.x + s2.y;
+        }
+        Pc3 ac[MT2], bc[MT1], an[MT2], bn[MT1];
+#pragma unroll
+        for (int mt = 0; mt < MT2; ++mt)
+#pragma unroll
+          for (int k = 0; k < 4; ++k) split3_pair(ac[mt], k, dl2u[mt][2 * k], dl2u[mt][2 * k + 1]);
+#pragma unroll
+        for (int nt = 0; nt < MT1; ++nt)
+#pragma unroll
+          for (int k = 0; k < 4; ++k) split3_pair(bc[nt], k, hq[k >> 1][nt][(2 * k) & 3], hq[k >> 1][nt][(2 * k + 1) & 3]);
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+          if (s == 0) {
+#pragma unroll
+            for (int q = 2; q < 4; ++q)
+#pragma unroll
+              for (int nt = 0; nt < MT1; ++nt) hq[q][nt] = *(const f32x4*)&bufB[(32 * nt + j) * ST + 8 * q + 4 * hi];
+          }
+#pragma unroll
+          for (int p = 0; p < 6; ++p) {
+            // mfma_bf3's order, the small products first: (lo, hi) (hi, lo) (mid, mid) (mid, hi) (hi, mid) (hi, hi)
+            const int pa = p == 0 ? 2 : (p == 2 || p == 3) ? 1 : 0, pb = p == 1 ? 2 : (p == 2 || p == 4) ? 1 : 0;
+#pragma unroll
+            for (int mt = 0; mt < MT2; ++mt)
+#pragma unroll
+              for (int nt = 0; nt < MT1; ++nt) {
+                MJX_MFMA_BF16_ACC(gW2[mt][nt], ac[mt].p[pa], bc[nt].p[pb]);
+                const int i = (p * MT2 + mt) * MT1 + nt;
+                if (s == 0) {
+                  if (i < 4 * (MT2 + MT1)) {
+                    const int o = i >> 2, k = i & 3;
+                    if (o < MT2) split3_pair(an[o], k, dl2u[o][8 + 2 * k], dl2u[o][8 + 2 * k + 1]);
+                    else split3_pair(bn[o - MT2], k, hq[2 + (k >> 1)][o - MT2][(2 * k) & 3], hq[2 + (k >> 1)][o - MT2][(2 * k + 1) & 3]);
+                  }
+                } else if (i < 4 * MT1) {
+                  const int q = i / MT1, n2 = i % MT1;
+                  bcs[q][n2] = *(const f32x4*)&bufB[(32 * n2 + j) * ST + 8 * q + 4 * hi];
+                }
+                __builtin_amdgcn_sched_barrier(0);
+              }
+          }
+          if (s == 0) {
+#pragma unroll
+            for (int mt = 0; mt < MT2; ++mt) ac[mt] = an[mt];
+#pragma unroll
+            for (int nt = 0; nt < MT1; ++nt) bc[nt] = bn[nt];
+          }
+        }
+      } else {
+#pragma unroll
+        for (int nt = 0; nt < MT1; ++nt) bcs[0][nt] = *(const f32x4*)&bufB[(32 * nt + j) * ST + 4 * hi];
+        __builtin_amdgcn_sched_barrier(0);
+        MJX_STAMP(8);
 #pragma unroll
         for (int q = 1; q < 4; ++q)
 #pragma unroll
@@ -1349,12 +1430,14 @@ __global__ __launch_bounds__(256, (MODE == MODE_EVAL && !DBG && MP <= 8) ? 2 : 1
             dd *= __builtin_elementwise_fma(-hh, hh, (f32x2)(1.0f));
             dl1u[nt][4 * q + t] = dd.x; dl1u[nt][4 * q + t + 1] = dd.y;
           }
+      if constexpr (!XR9) {
 #pragma unroll
-      for (int nt = 0; nt < MT2; ++nt) {
-        f32x2 s2 = {dl2u[nt][0], dl2u[nt][1]};
+        for (int nt = 0; nt < MT2; ++nt) {
+          f32x2 s2 = {dl2u[nt][0], dl2u[nt][1]};
 #pragma unroll
-        for (int r = 2; r < 16; r += 2) s2 += f32x2{dl2u[nt][r], dl2u[nt][r + 1]};
-        sb2[nt] += s2.x + s2.y;
+          for (int r = 2; r < 16; r += 2) s2 += f32x2{dl2u[nt][r], dl2u[nt][r + 1]};
+          sb2[nt] += s2.x + s2.y;
+        }
       }
       __builtin_amdgcn_sched_barrier(0);
       // ---------------- R10: gW1a[u1][f] += sum_s delta1[s][u1] x~a[s][f]   (column n = bias gradient)

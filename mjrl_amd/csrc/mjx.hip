@@ -170,7 +170,11 @@ int launch_fused(mjx_ctx* c, int mode, const FusedArgs& a, hipStream_t st) {
   if (mode == MODE_VPG) k = k_fused<H1, H2, NT1, MP, MODE_VPG, DBG, NPC>;
   else if (mode == MODE_FVP) k = cached ? k_fused<H1, H2, NT1, MP, MODE_FVP, false, NPC, true> : k_fused<H1, H2, NT1, MP, MODE_FVP, DBG, NPC>;
   else k = k_fused<H1, H2, NT1, MP, MODE_EVAL, false, NPC>;
-  if constexpr (BF3_OK) { if (bf3) k = k_fused<H1, H2, NT1, MP, MODE_FVP, false, NPC, true, true>; }
+  // ... and its W2 gradient (R9) too; MJX_FVP_BF16X3_R9=0 keeps that one product on fp32 MFMAs (read once per process)
+  static const bool bf3_r9_on = env_flag("MJX_FVP_BF16X3_R9", true);
+  if constexpr (BF3_OK) {
+    if (bf3) k = bf3_r9_on ? k_fused<H1, H2, NT1, MP, MODE_FVP, false, NPC, true, true, true> : k_fused<H1, H2, NT1, MP, MODE_FVP, false, NPC, true, true>;
+  }
   if (cached) mode = 3;
   // (FusedLayout::bytes() depends on the runtime observation count: the generic NPC = 0 instances serve many sizes)
   if (int rc = lds_limit((const void*)k, bytes)) return rc;

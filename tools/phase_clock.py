@@ -25,10 +25,10 @@ torch.cuda.synchronize()
 st = dbg.cpu().numpy().view(np.int64)[:14]
 if os.environ.get('CACHED', '1') == '1':
     # the cached instance's own schedule (fused_policy.h, "cached-forward Fisher-vector product")
-    # (stamps 0..9, 13; the phase between two stamps.  bf16x3 build: R2 / R3 / R8 are 48 v_mfma_f32_32x32x16_bf16 = 1536 cycles each)
+    # (stamps 0..9, 13; the phase between two stamps.  bf16x3 build: R2 / R3 / R8, and R9 unless MJX_FVP_BF16X3_R9=0, are 48 v_mfma_f32_32x32x16_bf16 = 1536 cycles each)
     names = ["R1 t1 = V1a x~ (20 MFMA = 1280)", "R2 t2 = c2 + V2 h1 (64 = 4096)", "VA t1 *= 1 - h1^2, f2", "R3 t2 += W2 t1 (64 = 4096)",
              "R4 output layer + VB (128 x 4x4x1 = 1024)", "VC d3 epilogue", "R6 delta2 (8 = 512) + R7 gW3 (64 x 4x4x1)",
-             "VD + R8 delta1 + delta2^T trip (64 = 4096)", "R9 gW2 (64 = 4096)", "VE + R10 gW1 (160 x 4x4x1 = 1280)"]
+             "VD + R8 delta1 + delta2^T trip (64 = 4096)", "R9 gW2 (fp32: 64 = 4096; bf16x3: b2 sums, K-step 0's split, 48 = 1536)", "VE + R10 gW1 (160 x 4x4x1 = 1280)"]
     st = np.concatenate([st[:10], st[13:14]])
 else:
     names = ["0 stage x", "1 L1 fwd+tan MFMAs (40)", "2 (tanh z1, sunk)", "3 tanh z1 + bias init + pass A (128)", "4 pass B (64) + tanh z2 + transposes", "5 -", "6 out_small (128 x 4x4)",

@@ -6,12 +6,15 @@ formed from the piece products that matter, accumulated in fp32.  Before any ker
 emulated exactly on the CPU (bf16 x bf16 is exact in fp32, the accumulation is fp32 like the MFMA's), for one Fisher-vector
 product and one 10-iteration CG solve at the BASELINE configs[1] shapes, against fp64 truth, next to native fp32's.
 
-    python tools/probe_split_error.py [N=100000] [mode,mode,...]
+    python tools/probe_split_error.py [N=100000] [mode,mode,...] [chunk=4096]
 
 modes: f32 (native), bf16x3 (3 pieces, the 6 products with i + j <= 2), bf16x3_all9, bf16x2 (2 pieces, 3 products -- what a
 "cheaper" split would give: lower precision than the reference, listed for contrast only), bf16x3_kernel (what the bf16x3 cached
 kernel does: R3 / R8 alone on the exact truncation split, per 16-deep K-step, small piece products first onto the fp32
-accumulator; every other product fp32).
+accumulator; R9 as the fp32 kernel runs it, 2 samples per MFMA onto one running fp32 accumulator per chunk; every other product
+fp32), bf16x3_kernel_r9 (the same with R9 too: gW2 += delta2^T h1 with BOTH operands on the
+truncation split, per 16-sample K-step, the six products onto one fp32 accumulator that runs over all of a chunk's samples --
+a wave's tiles).  Every mode also reports the W2 block's error alone.
 (Nothing here imports oracle/: tools are measurement infrastructure, the FVP is restated inline.)
 """
 import json
@@ -23,6 +26,7 @@ sys.path.insert(0, __file__.rsplit("/", 2)[0])
 from tools._synth import init_params, perturbed_params  # noqa: E402
 
 n, m, H = 17, 6, (64, 64)
+CHUNK = int(sys.argv[3]) if len(sys.argv) > 3 else 4096      # samples per accumulator (1 024 waves share bench.py's 1M rows: ~ 1 000 each)
 
 
 def bf16_round(x):
@@ -84,6 +88,14 @@ def mm_kernel(a, b, acc):
     return acc
 
 
+def mm_seq2(a, b, acc):
+    """acc + a @ b the way the fp32 R9 runs: one v_mfma_f32_32x32x2_f32 per 2 of the K values (samples), each onto the fp32 accumulator"""
+    a, b, acc = a.astype(np.float32), b.astype(np.float32), acc.astype(np.float32)
+    for k0 in range(0, a.shape[1], 2):
+        acc = acc + a[:, k0:k0 + 2] @ b[k0:k0 + 2, :]
+    return acc
+
+
 def unflatten(th):
     sizes = (n,) + H + (m,)
     Ws, bs, o = [], [], 0
@@ -94,11 +106,13 @@ def unflatten(th):
     return Ws, bs, th[o:]
 
 
-def fvp(th, obs, v, mode, chunk=4096):
+def fvp(th, obs, v, mode, chunk=None):
     """Gauss-Newton Fisher-vector product of mean_kl at theta_new == theta_old (mjrl/algos/npg_cg.py:62-81 restated: SURVEY 8a-a9);
     weight gradients accumulate per `chunk` samples in the mode's arithmetic and across chunks in fp64 (the kernel: per wave in MFMA
     accumulators, then fp64)"""
-    kern = mode == "bf16x3_kernel"               # the kernel: R3 / R8 on bf16x3 (truncation split), every other product fp32
+    chunk = chunk or CHUNK
+    kern = mode in ("bf16x3_kernel", "bf16x3_kernel_r9")   # the kernel: R3 / R8 on bf16x3 (truncation split), every other product fp32
+    kern_r9 = mode == "bf16x3_kernel_r9"                   # ... and R9
     if kern:
         mode = "f32"
     dt = np.float64 if mode == "f64" else np.float32
@@ -125,7 +139,10 @@ def fvp(th, obs, v, mode, chunk=4096):
         d2 = (mm(d3, Ws[2], mode) * (1 - h2 * h2)).astype(dt)
         d1 = ((mm_kernel(d2, Ws[1], np.zeros((d2.shape[0], Ws[1].shape[1]), dt)) if kern else mm(d2, Ws[1], mode)) * (1 - h1 * h1)).astype(dt)
         for l, (d_, a_) in enumerate(((d1, x), (d2, h1), (d3, h2))):
-            gW[l] += mm(d_.T, a_, mode).astype(np.float64)
+            if kern and l == 1:                  # R9 over a wave's tiles: one running fp32 accumulator either way
+                gW[l] += (mm_kernel if kern_r9 else mm_seq2)(d_.T, a_, np.zeros(gW[l].shape, dt)).astype(np.float64)
+            else:
+                gW[l] += mm(d_.T, a_, mode).astype(np.float64)
             gb[l] += d_.sum(axis=0, dtype=np.float64)
     c = 16.0 * u * u / (2.0 * u + eps) ** 2 - 4.0 * u / (2.0 * u + eps)
     return np.concatenate([np.concatenate([gW[l].ravel(), gb[l]]) for l in range(3)] + [(c * vs).astype(np.float64)]).astype(dt)
@@ -159,14 +176,15 @@ def main():
     g = rng.randn(th.size).astype(np.float32)
     g *= 1.0 / np.linalg.norm(g)
     damping = 1e-4
-    out = {"N": N, "shapes": "obs 17, act 6, 64x64 (BASELINE configs[1])", "cg_iters": 10, "damping": damping}
+    out = {"N": N, "chunk": CHUNK, "shapes": "obs 17, act 6, 64x64 (BASELINE configs[1])", "cg_iters": 10, "damping": damping}
     h64 = fvp(th, obs, g, "f64")
     x64 = cg(lambda p: fvp(th, obs, p, "f64") + damping * p, g.astype(np.float64))
-    modes = sys.argv[2].split(",") if len(sys.argv) > 2 else ("f32", "bf16x3", "bf16x3_all9", "bf16x2", "bf16x3_kernel")
+    modes = sys.argv[2].split(",") if len(sys.argv) > 2 else ("f32", "bf16x3", "bf16x3_all9", "bf16x2", "bf16x3_kernel", "bf16x3_kernel_r9")
+    w2 = slice(n * H[0] + H[0], n * H[0] + H[0] + H[1] * H[0])
     for mode in modes:
         h = fvp(th, obs, g, mode)
         x = cg(lambda p: fvp(th, obs, p, mode) + np.float32(damping) * p, g.astype(np.float32))
-        out[mode] = {"fvp_rel_l2_vs_f64": rel(h, h64), "cg10_rel_l2_vs_f64": rel(x, x64)}
+        out[mode] = {"fvp_rel_l2_vs_f64": rel(h, h64), "w2_block_rel_l2_vs_f64": rel(h[w2], h64[w2]), "cg10_rel_l2_vs_f64": rel(x, x64)}
         print(mode, out[mode], flush=True)
     print(json.dumps(out))
 
