@@ -425,6 +425,22 @@ int mjx_model_rollout(const float* s0, int64_t N, int H, int K, const int* pol_s
 int mjx_dyn_fit_adam(const float* x, const float* y, int64_t N, const int* sizes, int n_sizes, const float* in_tr,
                      const float* out_tr, int target_mode, int act, float* params, float* m, float* v, int64_t step0,
                      const int32_t* idx, int64_t steps, int batch, float lr, float wd, float* loss_out, void* stream);
+/* Which route mjx_dyn_fit_ensemble takes for nets of `sizes` at minibatch `batch`: 1 = the ensemble kernel (one persistent
+ * launch, a workgroup per member, products on fp32 MFMAs; csrc/dyn_fit_ens.h): exactly two hidden layers, each width a
+ * multiple of 32 from 32 to 256, batch <= 64, d_in <= 128, d_out <= 64, target_mode 1 or 2; 0 = member by member on the
+ * routes of mjx_dyn_fit_adam; < 0 = bad sizes.  Arithmetic only: no device work and no runtime call. */
+int mjx_dyn_fit_route(const int* sizes, int n_sizes, int batch, int target_mode);
+/* The fit of mjx_dyn_fit_adam for K members of one shape at once (the driver's `for model in ensemble:
+ * model.fit_dynamics(...)`, run_model_accel_npg.py:168-177).  Member k reads x + k * x_stride and y + k * y_stride
+ * (a stride of 0: the same rows for all members), in_tr + k * 2 d_in, out_tr + k * 2 d_out, idx + k * steps * batch and
+ * step0[k] (a HOST array of K counts), updates params / m / v + k * P in place and writes loss_out + k * steps.
+ * *route_out (a host int, may be NULL) receives the route taken (mjx_dyn_fit_route; MJX_DYN_FIT_ENS=0, read per call,
+ * forces 0).  On route 0 the call is exactly K mjx_dyn_fit_adam calls in member order.  Bad arguments return MJX_ERR_ARG
+ * and touch nothing; steps == 0 returns MJX_OK without a launch.  Uses per-host-thread scratch. */
+int mjx_dyn_fit_ensemble(const float* x, int64_t x_stride, const float* y, int64_t y_stride, int64_t N, int K,
+                         const int* sizes, int n_sizes, const float* in_tr, const float* out_tr, int target_mode, int act,
+                         float* params, float* m, float* v, const int64_t* step0, const int32_t* idx, int64_t steps,
+                         int batch, float lr, float wd, float* loss_out, int* route_out, void* stream);
 /* ensemble-disagreement truncation (model_accel_npg.py:137-155): pred = K x rows x n model predictions, s_next the
  * rows' next states; err_out[r] = max_k mean_j (s_next - pred)^2, NaN if any member's is NaN (np.maximum);
  * segment g = rows [seg_off[g], seg_off[g+1]) (one path); first_out[g] = the first row of the segment whose error

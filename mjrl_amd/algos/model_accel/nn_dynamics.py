@@ -10,7 +10,9 @@ global torch stream are the reference's) and transforms.  What runs where:
   permutations are drawn from NumPy's global stream exactly where ``fit_model`` draws them, and every Adam step runs in
   libmjx (``mjx_dyn_fit_adam``: one persistent launch for nets up to 128 wide at minibatch <= 64, a launch per layer and
   phase otherwise).  The optimiser state (``dynamics_opt`` / ``reward_opt``) is torch.optim.Adam's -- step count and
-  both moments -- kept as flat fp32 vectors.
+  both moments -- kept as flat fp32 vectors;
+* :func:`fit_ensemble`: the driver's ``for model in ensemble: model.fit_dynamics(...)`` with every member's Adam chain in one
+  persistent launch (``mjx_dyn_fit_ensemble``, a workgroup per member on fp32 MFMAs for two hidden layers up to 256 wide).
 
 The module parameters stay ordinary torch tensors (CPU by default, as in the reference): ``get_params`` /
 ``set_params`` / ``to`` / ``is_cuda`` / pickling behave as the reference's.  There is no CPU path: without a GPU the
@@ -317,6 +319,95 @@ def _fit(net, opt, X, Y, target_mode, batch_size, epochs, max_steps):
             k += p.numel()
     net._generation = getattr(net, "_generation", 0) + 1     # (p.data.copy_ leaves p._version as it was)
     return epoch_means(loss.cpu().numpy(), num_steps, ran)
+
+
+def ensemble_fit_indices(K, num_samples, batch_size, epochs, max_steps=1e10):
+    """the host side of K successive fits of one data set: member 0's permutations from NumPy's global stream, then member
+    1's, ... exactly as K calls of :func:`fit_permutations` draw them (the early-stop message comes per member)
+    -> (K x (steps * batch) int32 row indices, steps per epoch, epochs run)"""
+    draws = [fit_permutations(num_samples, batch_size, epochs, max_steps) for _ in range(K)]
+    if not draws:
+        return np.zeros((0, 0), np.int32), int(num_samples // batch_size), 0
+    return np.stack([d[0] for d in draws]), draws[0][1], draws[0][2]
+
+
+def _same_fit(models):
+    """may K WorldModels share one mjx_dyn_fit_ensemble call: one shape, activation, residual flag and optimiser setting"""
+    n0, g0 = models[0].dynamics_net, models[0].dynamics_opt.param_groups[0]
+    for mdl in models[1:]:
+        n, g = mdl.dynamics_net, mdl.dynamics_opt.param_groups[0]
+        if (tuple(n.layer_sizes) != tuple(n0.layer_sizes) or _act_code(n) != _act_code(n0) or bool(n.residual) != bool(n0.residual)
+                or g['lr'] != g0['lr'] or g['weight_decay'] != g0['weight_decay']):
+            return False
+    return True
+
+
+def fit_ensemble(models, s, a, sp, fit_mb_size, fit_epochs, max_steps=1e4, set_transformations=True):
+    """``[mdl.fit_dynamics(s, a, sp, fit_mb_size, fit_epochs, max_steps, set_transformations) for mdl in models]`` (the
+    driver's loop, run_model_accel_npg.py:168-177) with every member's Adam chain in ONE launch (``mjx_dyn_fit_ensemble``:
+    a workgroup per member; shapes it does not serve run member by member inside the same call).  Per member the same
+    transform expressions, the same draws from NumPy's global stream in the same order, the same optimiser state carried
+    and advanced, the parameters written back and ``_generation`` bumped.  -> a list of K epoch-loss lists.  Members that
+    differ in layer sizes, activation, ``residual`` or optimiser settings run the plain loop."""
+    models = list(models)
+    if not models:
+        return []
+    if not _same_fit(models):
+        return [mdl.fit_dynamics(s, a, sp, fit_mb_size, fit_epochs, max_steps=max_steps, set_transformations=set_transformations)
+                for mdl in models]
+    assert type(s) == type(a) == type(sp)
+    assert s.shape[0] == a.shape[0] == sp.shape[0]
+    if type(s) == np.ndarray:
+        s = torch.from_numpy(s).float()
+        a = torch.from_numpy(a).float()
+        sp = torch.from_numpy(sp).float()
+    if set_transformations:
+        for mdl in models:
+            # the reference's transform expressions, on each member's device (nn_dynamics.py:99-104), as fit_dynamics forms them
+            net = mdl.dynamics_net
+            s_, a_, sp_ = s.to(mdl.device), a.to(mdl.device), sp.to(mdl.device)
+            s_shift, a_shift = torch.mean(s_, dim=0), torch.mean(a_, dim=0)
+            s_scale, a_scale = torch.mean(torch.abs(s_ - s_shift), dim=0), torch.mean(torch.abs(a_ - a_shift), dim=0)
+            out_shift = torch.mean(sp_ - s_, dim=0) if net.residual else torch.mean(sp_, dim=0)
+            out_scale = torch.mean(torch.abs(sp_ - s_ - out_shift), dim=0) if net.residual else torch.mean(torch.abs(sp_ - out_shift), dim=0)
+            net.set_transformations(s_shift, s_scale, a_shift, a_scale, out_shift, out_scale)
+    dev = _device()
+    K, N = len(models), int(sp.shape[0])
+    nets, opts = [mdl.dynamics_net for mdl in models], [mdl.dynamics_opt for mdl in models]
+    idx, num_steps, ran = ensemble_fit_indices(K, N, fit_mb_size, fit_epochs, max_steps)
+    steps = ran * num_steps
+    if steps == 0:
+        return [epoch_means([], num_steps, ran) for _ in models]
+    sizes = nets[0].layer_sizes
+    din, dout = sizes[0], sizes[-1]
+    X, Y = _f32(torch.cat([s, a], -1), dev), _f32(sp.reshape(N, -1), dev)
+    P = torch.stack([_flat_params(net, dev) for net in nets])
+    tr = torch.stack([_packed_transforms(net, dev) for net in nets])
+    in_tr, out_tr = tr[:, :2 * din].contiguous(), tr[:, 2 * din:].contiguous()
+    state = [opt._state(dev) for opt in opts]
+    m, v = torch.stack([st[0] for st in state]), torch.stack([st[1] for st in state])
+    g = opts[0].param_groups[0]
+    step0 = (ctypes.c_int64 * K)(*[int(opt.step_count) for opt in opts])
+    idx_d = torch.from_numpy(np.ascontiguousarray(idx)).to(dev)
+    loss = torch.empty((K, steps), dtype=torch.float32, device=dev)
+    route = ctypes.c_int(-1)
+    check(load().mjx_dyn_fit_ensemble(ptr(X), 0, ptr(Y), 0, N, K, _ints(sizes), len(sizes), ptr(in_tr), ptr(out_tr),
+                                      TGT_RESIDUAL if nets[0].residual else TGT_PLAIN, _act_code(nets[0]), ptr(P), ptr(m), ptr(v), step0,
+                                      ptr(idx_d), steps, int(fit_mb_size), float(g['lr']), float(g['weight_decay']), ptr(loss),
+                                      ctypes.byref(route), _stream(dev)))
+    losses = loss.cpu().numpy()
+    out = []
+    with torch.no_grad():
+        for i, (net, opt) in enumerate(zip(nets, opts)):
+            opt.exp_avg.copy_(m[i]); opt.exp_avg_sq.copy_(v[i])
+            opt.step_count += steps
+            k = 0
+            for p in net.parameters():
+                p.data.copy_(P[i, k:k + p.numel()].view_as(p))
+                k += p.numel()
+            net._generation = getattr(net, "_generation", 0) + 1     # (an MPCPolicy repacks its device copy)
+            out.append(epoch_means(losses[i], num_steps, ran))
+    return out
 
 
 class DynamicsNet(nn.Module):

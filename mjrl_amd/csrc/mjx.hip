@@ -21,6 +21,7 @@
 
 #include "baseline.h"
 #include "dynamics.h"
+#include "dyn_fit_ens.h"
 #include "fused_policy.h"
 #include "policy_fit.h"
 #include "rccl_dyn.h"
@@ -58,7 +59,7 @@ int lds_limit(const void* kern, size_t bytes) {
   if (e) return fail(e, "dynamic LDS limit of %zu bytes: %s", bytes, hipGetErrorString((hipError_t)e));
   return MJX_OK;
 }
-enum ScratchSite { SITE_GRAM, SITE_MLP_PREDICT, SITE_MLP_FIT, SITE_MLP_FIT_WIDE, SITE_MLP_FIT_LAUNCHES, SITE_DYN_FIT, SITE_SUM_STATS, SITE_PLAN_ROLLOUT, SITE_PLAN_SCORE };
+enum ScratchSite { SITE_GRAM, SITE_MLP_PREDICT, SITE_MLP_FIT, SITE_MLP_FIT_WIDE, SITE_MLP_FIT_LAUNCHES, SITE_DYN_FIT, SITE_SUM_STATS, SITE_PLAN_ROLLOUT, SITE_PLAN_SCORE, SITE_DYN_FIT_ENS };
 template <class T>
 int dev_scratch(ScratchSite site, void* stream, size_t bytes, T** out) {
   HIPCHK(mjx::scratch(site, (hipStream_t)stream, bytes, (void**)out));
@@ -904,6 +905,69 @@ int mjx_dyn_fit_adam(const float* x, const float* y, int64_t N, const int* sizes
                          step0 + s + 1, lr, wd);
       cur ^= 1;
     }
+  }
+  HIPCHK(hipGetLastError());
+  return MJX_OK;
+}
+
+// ---- the whole ensemble's fit (csrc/dyn_fit_ens.h)
+int mjx_dyn_fit_route(const int* sizes, int n_sizes, int batch, int target_mode) {
+  DynNet net;
+  if (int rc = dyn_net(sizes, n_sizes, net)) return rc;
+  if (batch <= 0 || target_mode < DYN_TGT_AFFINE || target_mode > DYN_TGT_RESIDUAL) return fail(MJX_ERR_ARG, "bad batch or target mode");
+  return dfe_serves(net, batch, target_mode) ? 1 : 0;
+}
+
+int mjx_dyn_fit_ensemble(const float* x, int64_t x_stride, const float* y, int64_t y_stride, int64_t N, int K, const int* sizes, int n_sizes,
+                         const float* in_tr, const float* out_tr, int target_mode, int act, float* params, float* m, float* v,
+                         const int64_t* step0, const int32_t* idx, int64_t steps, int batch, float lr, float wd, float* loss_out,
+                         int* route_out, void* stream) {
+  DynNet net;
+  if (int rc = dyn_net(sizes, n_sizes, net)) return rc;
+  const int din = net.din(), dout = net.dout();
+  if (!x || !y || !in_tr || !out_tr || !params || !m || !v || !step0 || (steps > 0 && (!idx || !loss_out)) || N <= 0 || K <= 0 || K > 65535 ||
+      x_stride < 0 || y_stride < 0 || batch <= 0 || batch > N || steps < 0 || target_mode < DYN_TGT_AFFINE || target_mode > DYN_TGT_RESIDUAL ||
+      (act != DYN_ACT_RELU && act != DYN_ACT_TANH) || (target_mode == DYN_TGT_RESIDUAL && dout > din))
+    return fail(MJX_ERR_ARG, "bad arguments");
+  for (int k = 0; k < K; ++k) if (step0[k] < 0) return fail(MJX_ERR_ARG, "bad arguments");
+  // (read per call: the tests and tools/bench_dyn_fit.py compare the two routes in one process)
+  const int route = env_flag("MJX_DYN_FIT_ENS", true) && dfe_serves(net, batch, target_mode) ? 1 : 0;
+  if (route_out) *route_out = route;
+  if (steps == 0) return MJX_OK;
+  if (route == 0) {                                        // member by member on the routes of mjx_dyn_fit_adam
+    for (int k = 0; k < K; ++k)
+      if (int rc = mjx_dyn_fit_adam(x + k * x_stride, y + k * y_stride, N, sizes, n_sizes, in_tr + (int64_t)k * 2 * din, out_tr + (int64_t)k * 2 * dout,
+                                    target_mode, act, params + k * net.P, m + k * net.P, v + k * net.P, step0[k], idx + (int64_t)k * steps * batch,
+                                    steps, batch, lr, wd, loss_out + (int64_t)k * steps, stream))
+        return rc;
+    return MJX_OK;
+  }
+  MJX_DEVICE_ENTRY();
+  hipStream_t st = (hipStream_t)stream;
+  const DfeLayout L(net, batch);
+  // scratch, per member: normalised inputs and targets (every member has its own transforms), and the X tile where LDS has no room
+  const size_t xt = L.x_in_lds ? 0 : L.xtile;
+  float* scr = nullptr;
+  if (int rc = dev_scratch(SITE_DYN_FIT_ENS, stream, ((size_t)K * (size_t)N * (din + dout) + 4 + (size_t)K * xt) * sizeof(float), &scr)) return rc;
+  float* xn = scr; float* tg = xn + (size_t)K * N * din;
+  float* xscr = xt ? scr + (((size_t)K * N * (din + dout) + 3) & ~(size_t)3) : nullptr;
+  {
+    const int64_t tot = N * (din > dout ? din : dout);
+    const unsigned grid = (unsigned)((tot + 255) / 256 < 4096 ? (tot + 255) / 256 : 4096);
+    for (int k = 0; k < K; ++k)
+      hipLaunchKernelGGL(k_dyn_prep, dim3(grid), dim3(256), 0, st, x + k * x_stride, y + k * y_stride, N, din, dout, in_tr + (int64_t)k * 2 * din,
+                         out_tr + (int64_t)k * 2 * dout, target_mode, xn + (size_t)k * N * din, tg + (size_t)k * N * dout);
+  }
+  if (int rc = lds_limit((const void*)k_dyn_fit_ens, L.lds_bytes())) return rc;
+  DynFitEnsArgs a{};
+  a.din = din; a.h1 = net.sz[1]; a.h2 = net.sz[2]; a.dout = dout; a.B = batch; a.act = act;
+  a.P = net.P; a.N = N; a.steps = steps; a.xn = xn; a.tg = tg; a.idx = idx; a.W = params; a.m = m; a.v = v; a.loss = loss_out; a.xscr = xscr;
+  a.lr = lr; a.wd = wd;
+  for (int k0 = 0; k0 < K; k0 += DFE_CHUNK) {               // one launch for K <= DFE_CHUNK members
+    const int kn = K - k0 < DFE_CHUNK ? K - k0 : DFE_CHUNK;
+    a.k0 = k0;
+    for (int q = 0; q < kn; ++q) a.step0[q] = step0[k0 + q];
+    hipLaunchKernelGGL(k_dyn_fit_ens, dim3((unsigned)kn), dim3(DFE_THREADS), L.lds_bytes(), st, a);
   }
   HIPCHK(hipGetLastError());
   return MJX_OK;
