@@ -64,6 +64,12 @@ int64_t mjx_num_params(const mjx_ctx* ctx);
 /* 1 if the fused single-kernel path serves this network shape, 0 if the
  * layer-wise path does */
 int mjx_uses_fused_path(const mjx_ctx* ctx);
+/* Which fused instance serves the context (read-only; tests assert that a case reached the instance it is named for):
+ * out4[0] = variant id (1: 64x64 / 8 actions, 2: 32x32 / 8, 3: 64x64 / 16, 4: 32x32 / 16, 5: 32x32 / 8 with up to 63 observations,
+ * 6: 32x32 / 32), out4[1] = compile-time feature count of the instance (8, 12 or 20; 0 = the generic instance),
+ * out4[2] = columns of the accumulator-order partial slab (0 = the flat-order epilogue), out4[3] = workgroups per launch (K3 with
+ * up to 8 actions launches twice as many).  A layer-wise context returns 0 in all four. */
+int mjx_fused_info(const mjx_ctx* ctx, int32_t* out4);
 
 /* ---- plain device-memory helpers (so a C / cgo / JNI caller needs no torch; tests/c/c_caller.c) -- */
 /* hipMalloc of bytes + 16: an observation block allocated here can never fault on the up-to-12-byte tail read documented at

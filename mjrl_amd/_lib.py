@@ -25,6 +25,7 @@ PROTOTYPES = {
     "mjx_destroy": (None, [c_void_p]),
     "mjx_num_params": (c_int64, [c_void_p]),
     "mjx_uses_fused_path": (c_int, [c_void_p]),
+    "mjx_fused_info": (c_int, [c_void_p, ctypes.POINTER(ctypes.c_int32)]),
     "mjx_malloc": (c_int, [ctypes.POINTER(c_void_p), c_int64]),
     "mjx_free": (c_int, [c_void_p]),
     "mjx_memcpy_h2d": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),

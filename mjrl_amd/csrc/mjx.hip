@@ -379,6 +379,16 @@ void mjx_destroy(mjx_ctx* c) {
 
 int64_t mjx_num_params(const mjx_ctx* c) { return c ? c->d : -1; }
 int mjx_uses_fused_path(const mjx_ctx* c) { return c ? (c->fused != 0) : 0; }
+int mjx_fused_info(const mjx_ctx* c, int32_t* out) {
+  if (!c || !out) return fail(MJX_ERR_ARG, "bad arguments");
+  out[0] = out[1] = out[2] = out[3] = 0;
+  if (!c->fused) return MJX_OK;
+  out[0] = c->fused;
+  out[1] = npc_of(c->fused, c->n);
+  out[2] = c->raw_perm ? c->raw_dr : 0;
+  out[3] = c->grid;
+  return MJX_OK;
+}
 
 int mjx_malloc(void** p, int64_t bytes) {
   MJX_DEVICE_ENTRY();

@@ -1,0 +1,313 @@
+"""Every instance of the fused policy kernels (k_fused, csrc/fused_policy.h) that dispatch_fused / launch_fused (csrc/mjx.hip) can
+pick, in every launch arm and at every row edge, against the fp64 oracle (oracle/npg_oracle.py, pinned to the reference by
+tests/test_oracle_golden.py) -- block by block, row by row, column by column and entry by entry (tests/_lw_check.fine_errors).
+
+The device runs go through tests/_fused_matrix_worker.py in child processes, one per arm, with the arm's switches in the child's
+environment (MJX_FVP_BF16X3 is read once per process; MJX_RAW_SLAB and MJX_NO_HCACHE when a context is created).  Each worker
+asserts, for every case, that the fused path serves it and that mjx_fused_info reports the instance the case is named for
+(variant id, compile-time feature count NPC, raw slab on / off).  Inputs: tests/_dispatch_matrix_worker.head_inputs -- every
+action with its own log_std, out_scale and out_shift (permuted), non-identity input transforms, on-policy actions.
+
+Instances (hidden sizes, NT1 = 32-column blocks of the first layer, MP = padded action count) and the shapes (n, m) of each:
+
+    variant 1   64 x 64, NT1 1, MP 8    generic (NPC 0)   (1,1) (3,8) (12,3) (15,8) (20,2) (23,8)
+                                         NPC 8             (4,8) (5,2) (6,3) (7,1)
+                                         NPC 12            (8,8) (9,5) (10,2) (11,1)
+                                         NPC 20            (16,1) (17,6) (18,7) (19,8)
+    variant 3   64 x 64, NT1 1, MP 16                      (1,9) (8,12) (17,9) (17,16): the last at exactly 163 840 bytes of LDS
+    variant 2   32 x 32, NT1 1, MP 8                       (1,1) (16,5) (31,8)
+    variant 4   32 x 32, NT1 1, MP 16                      (1,9) (12,13) (31,16)
+    variant 5   32 x 32, NT1 2, MP 8                       (32,1) (45,4) (63,8)
+    variant 6   32 x 32, NT1 2, MP 32                      (5,17) (31,32) (32,9) (45,24) (59,32)
+
+Sizes: N = 3000 + n for every shape ("base"); on one edge shape per family -- (23,8), (4,8), (11,1), (16,1), (19,8), (17,16) of
+64 x 64 and (31,8), (1,9), (63,8), (59,32) of 32 x 32 -- also N in {1, 31, 32, 33} and N_big = 2 x grid x 128 + 33 (grid from
+mjx_fused_info: 65 569 rows on 256 CUs), where K3 with MP <= 8 (two workgroups per CU) gives one wave a partial second tile and
+every other launch gives its waves a second or third.
+
+Per case, in this call order (the worker's run_case):
+
+    hv_rc          the recompute product (k_fused<MODE_FVP>, CACHED = false): mjx_fvp before any K1
+    g, surr        K1 at old == new (fills the activation cache, the old-policy outputs, the parameter snapshot)
+    hv, hv_fwd     two cached products of the same direction: tiles walked back to front, then front to back; each against
+                   fp64, and within 1e-6 of each other
+    hv_pre         (edge shapes at base N and N_big) mjx_bind_rows(N - 40), a cached product walked in reverse over the prefix
+    hv_a*          output-row probes: the direction restricted to output row 0, m - 2, m - 1
+    s1, kl1        K3 (1) with K1's old-policy outputs and observation image;  s_pre, kl_pre: the same over the prefix
+    s2, kl2        K3 (2) after theta_old changed in place (the kernel's snapshot compare must notice)
+    s3, kl3        K3 (3) after the new policy's input transform changed in place (the image no longer applies)
+    s4, kl4        K3 (4) after a fresh mjx_bind_batch (nothing stored)
+    g2             K1 at old != new
+
+Arms (one worker each):
+
+    default                 every case above                              fp64 bars
+    MJX_RAW_SLAB=0          every base and N_big case                     raw_dr == 0 (flat-order epilogue; m odd: d % 4 != 0, so
+                                                                          k_reduce_partials + k_reduce_scalars); g, surr, hv, hv_fwd
+                                                                          bit-identical to the default arm
+    MJX_FVP_BF16X3=0        variant-1 shapes: base, edges, N_big          the fp32 cached product: fp64 bars; bits differ from the
+                                                                          default arm's bf16x3 product, within 1e-6 of it
+    MJX_NO_HCACHE=1         the ten edge shapes at every size             no caches: K1, the (recompute) products, K3 at fp64 bars
+
+tests/test_fused_matrix_checks.py shows on the CPU that the fine bars flag a dropped row, a dropped tile, swapped output rows, a
+zeroed bias entry and a misplaced log_std entry, and pass the fp32 oracle.
+"""
+import functools
+import json
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+from oracle import npg_oracle as O
+from tests._dispatch_matrix_worker import probe_actions, probe_direction
+from tests._fused_matrix_worker import PREFIX_CUT, fused_inputs
+from tests._lw_check import fine_errors, over_bars, rel
+
+pytestmark = pytest.mark.gpu
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+
+# the project's whole-vector and scalar bars (tests/test_gpu_parity.py, test_other_shapes_vs_oracle)
+TOL_VPG = 3e-6
+TOL_FVP = 3e-6
+TOL_STEP = 1e-5
+TOL_SAME = 1e-6          # two products of one direction that sum other tile sets, or run on other MFMAs
+
+# (variant, NPC, hidden) -> shapes (n, m)
+INSTANCES = [
+    (1, 0, (64, 64), [(1, 1), (3, 8), (12, 3), (15, 8), (20, 2), (23, 8)]),
+    (1, 8, (64, 64), [(4, 8), (5, 2), (6, 3), (7, 1)]),
+    (1, 12, (64, 64), [(8, 8), (9, 5), (10, 2), (11, 1)]),
+    (1, 20, (64, 64), [(16, 1), (17, 6), (18, 7), (19, 8)]),
+    (3, 0, (64, 64), [(1, 9), (8, 12), (17, 9), (17, 16)]),
+    (2, 0, (32, 32), [(1, 1), (16, 5), (31, 8)]),
+    (4, 0, (32, 32), [(1, 9), (12, 13), (31, 16)]),
+    (5, 0, (32, 32), [(32, 1), (45, 4), (63, 8)]),
+    (6, 0, (32, 32), [(5, 17), (31, 32), (32, 9), (45, 24), (59, 32)]),
+]
+EDGE_SHAPES = [((64, 64), 23, 8), ((64, 64), 4, 8), ((64, 64), 11, 1), ((64, 64), 16, 1), ((64, 64), 19, 8), ((64, 64), 17, 16),
+               ((32, 32), 31, 8), ((32, 32), 1, 9), ((32, 32), 63, 8), ((32, 32), 59, 32)]
+EDGE_N = (1, 31, 32, 33)
+PROBES = 3               # output-row probes per case (0, m - 2, m - 1)
+
+
+def _shape_name(hid, n, m):
+    return "h%d_%dx%d" % (hid[0], n, m)
+
+
+SHAPE = {_shape_name(hid, n, m): dict(variant=v, npc=npc, hid=hid, n=n, m=m) for v, npc, hid, shapes in INSTANCES for n, m in shapes}
+assert len(SHAPE) == 36 and all(_shape_name(*e) in SHAPE for e in EDGE_SHAPES)
+EDGE = [_shape_name(*e) for e in EDGE_SHAPES]
+
+BASE_CASES = [s + "_base" for s in SHAPE]
+EDGE_CASES = ["%s_N%d" % (s, N) for s in EDGE for N in EDGE_N]
+BIG_CASES = [s + "_big" for s in EDGE]
+V1 = [s for s in SHAPE if SHAPE[s]["variant"] == 1]
+
+ARMS = {
+    "default": ({}, BASE_CASES + EDGE_CASES + BIG_CASES),
+    "raw0": ({"MJX_RAW_SLAB": "0"}, BASE_CASES + BIG_CASES),
+    "bf3_0": ({"MJX_FVP_BF16X3": "0"}, [s + "_base" for s in V1] + [c for c in EDGE_CASES + BIG_CASES if c.rsplit("_", 1)[0] in V1]),
+    "nohcache": ({"MJX_NO_HCACHE": "1"}, [s + "_base" for s in EDGE] + EDGE_CASES + BIG_CASES),
+}
+
+# Fine bars (fine_errors keys) per result kind: 3x the largest error measured on MI355X (256 CUs) over the default-arm cases -- every
+# instance above is one test_other_shapes_vs_oracle already gates by whole-vector norm at N = 3000 + n ((22,8) generic, (6,2) and
+# (4,1) NPC 8, (11,3) and (8,2) NPC 12, (19,6) NPC 20, (17,12) variant 3, (31,1) variant 2, (9,10) variant 4, (40,4) variant 5,
+# (39,28) / (46,26) / (7,20) variant 6), so all default-arm cases count, their row edges included.  No bar may exceed 1e-4: a
+# dropped row 32 of 33 measures 7e-2 or more (tests/test_fused_matrix_checks.py).  Measured maxima, default arm (case, place):
+#   K1 (g)          block 5.68e-6 (h64_16x1_N33 log_std)   row 1.12e-6 (h64_17x16_N1 W1)   col 1.34e-6 (h64_7x1_base W3)
+#                   entry 9.61e-6 (h64_11x1_N31 b3[0])
+#   products (hv*)  block = row = entry 3.74e-6 (h32_59x32_N1, output row 19; recompute product 3.36e-6)   col 1.02e-6 (same case)
+#                   at N >= 31: block 8.7e-7, row 1.1e-6, col 9.0e-7, entry 1.7e-6
+#   K1 old != new   block = entry 7.81e-5 (h32_1x1_base log_std[0], see below; next: 7.49e-6 h32_59x32_N32 row 18, 2.00e-5
+#   (g2)            h32_59x32_N32 log_std[18])   row 6.33e-6 (h32_59x32_N32 W3)   col 7.21e-6 (h32_59x32_N32 W1)
+# The other arms stay at or below these (MJX_RAW_SLAB=0: the same bits; MJX_FVP_BF16X3=0: products block 8.7e-7, row 1.1e-6,
+# col 8.4e-7, entry 1.7e-6; MJX_NO_HCACHE=1: products 3.36e-6 at h32_59x32_N1, g2 entry 2.00e-5).
+# The two g2 bars that 3x would put at 2.3e-4 stand at the cap.  Their maximum is one number: with m = 1 the log_std block has one
+# entry, so "block" and "entry" are the plain relative error of one sum over the samples, and at (1,1) / 32 x 32 that sum cancels
+# to 2.97e-4 where its neighbour b3[0] is 8.7e-2.  The fp32 NumPy oracle is 9.2e-5 off on the same entry (the kernel 7.8e-5):
+# rounding of a cancelling sum, not a defect of the instance (h64_1x1_base, the same code at 64 x 64: 2.9e-6).
+MEASURED = {
+    "g": {"block": 5.69e-6, "row": 1.13e-6, "col": 1.34e-6, "entry": 9.61e-6},
+    "hv": {"block": 3.75e-6, "row": 3.75e-6, "col": 1.03e-6, "entry": 3.75e-6},
+    "g2": {"block": 7.82e-5, "row": 6.34e-6, "col": 7.21e-6, "entry": 7.82e-5},
+}
+BAR_CAP = 1e-4
+BARS = {kind: {key: min(float("%.3g" % (3.0 * v)), BAR_CAP) for key, v in worst.items()} for kind, worst in MEASURED.items()}
+# Whole-vector figures, default arm (all at the project's bars above): K1 4.2e-7, products 7.9e-7 (N = 1; 1.9e-7 at base N), prefix
+# product 1.9e-7, probes 2.5e-6 (h64_4x8_N1 action 6; 2.5e-7 at N >= 31), K1 old != new 3.9e-6 (m = 32; 2.0e-6 at m <= 16), K3
+# surrogate 2.1e-6 (N = 1; 1.7e-7 at base N), K3 KL 0.70 of its bar, forward against reverse sweep 4.4e-8, fp32 against bf16x3
+# product 6.4e-7.
+
+
+def spec(name, arm="default"):
+    shape, size = name.rsplit("_", 1)
+    s = SHAPE[shape]
+    n, m = s["n"], s["m"]
+    N = 3000 + n if size == "base" else 0 if size == "big" else int(size[1:])
+    return dict(name=name, n=n, m=m, hid=list(s["hid"]), N=N, seed=n * 100 + m + (N if size != "big" else 7), variant=s["variant"],
+                npc=s["npc"], raw=arm != "raw0", prefix=arm == "default" and shape in EDGE and size in ("base", "big"), probes=PROBES)
+
+
+# ---------------------------------------------------------------------------------------------------------------- oracle
+@functools.lru_cache(maxsize=None)
+def oracle(name, N):
+    """fp64 values of everything a default-arm case returns; computed once per (case, N) and shared by the arms"""
+    c = spec(name)
+    n, m, hid = c["n"], c["m"], tuple(c["hid"])
+    inp = fused_inputs(n, m, hid, N, c["seed"])
+    th, t2, t3 = (inp[k].astype(np.float64) for k in ("th", "th2", "th3"))
+    tr, tr2 = inp["tr"], inp["tr2"]
+    obs, act, adv, v = (inp[k].astype(np.float64) for k in ("obs", "act", "adv", "v"))
+    r = dict(g=O.vpg(th, th, obs, act, adv, n, m, hid, tr, tr), surr=O.surrogate(th, th, obs, act, adv, n, m, hid, tr, tr),
+             hv=O.fvp(th, obs, v, n, m, hid, tr), g2=O.vpg(t2, th, obs, act, adv, n, m, hid, tr, tr))
+    for a in probe_actions(m):
+        r["hv_a%d" % a] = O.fvp(th, obs, probe_direction(v, n, m, hid, a), n, m, hid, tr)
+    for k, (tn, to, trn) in {"1": (t2, th, tr), "2": (t2, t3, tr), "3": (t2, th, tr2)}.items():
+        r["s" + k] = O.surrogate(tn, to, obs, act, adv, n, m, hid, trn, tr)
+        r["kl" + k] = O.mean_kl(tn, to, obs, n, m, hid, trn, tr)
+    r["s4"], r["kl4"] = r["s1"], r["kl1"]
+    if N > PREFIX_CUT:
+        P = N - PREFIX_CUT
+        r["hv_pre"] = O.fvp(th, obs[:P], v, n, m, hid, tr)
+        r["s_pre"] = O.surrogate(t2, th, obs[:P], act[:P], adv[:P], n, m, hid, tr, tr)
+        r["kl_pre"] = O.mean_kl(t2, th, obs[:P], n, m, hid, tr, tr)
+    return r
+
+
+def errors(name, r):
+    """-> every error figure of one case's device results: {"fine": {key: fine_errors}, "whole": {key: rel}, "scal": {key: |d|},
+    "kl": {key: (|d|, ref)}}"""
+    c = spec(name)
+    n, m, hid = c["n"], c["m"], tuple(c["hid"])
+    ref = oracle(name, int(r["N"]))
+    out = dict(fine={}, whole={}, scal={}, kl={})
+    for k in ("g", "hv_rc", "hv", "hv_fwd", "hv_pre", "g2"):
+        if k in r:
+            kr = "hv" if k in ("hv_rc", "hv_fwd") else k
+            out["fine"][k] = fine_errors(r[k], ref[kr], n, m, hid)
+            out["whole"][k] = rel(r[k], ref[kr])
+    for a in probe_actions(m):
+        if "hv_a%d" % a in r:
+            out["whole"]["hv_a%d" % a] = rel(r["hv_a%d" % a], ref["hv_a%d" % a])
+    out["scal"]["surr"] = abs(float(r["surr"]) - ref["surr"])
+    for k in ("1", "2", "3", "4", "_pre"):
+        if "s" + k in r:
+            out["scal"]["s" + k] = abs(float(r["s" + k]) - ref["s" + k])
+            out["kl"]["kl" + k] = (abs(float(r["kl" + k]) - ref["kl" + k]), ref["kl" + k])
+    return out
+
+
+def bar_kind(k):
+    return "hv" if k.startswith("hv") else k
+
+
+# ---------------------------------------------------------------------------------------------------------------- runs
+def _run_worker(arm, specs, out_dir):
+    os.makedirs(out_dir, exist_ok=True)
+    path = os.path.join(out_dir, "spec.json")
+    with open(path, "w") as f:
+        json.dump({"cases": specs}, f)
+    env = dict(os.environ, **ARMS[arm][0])
+    for k in ("MJX_FORCE_LAYERWISE", "MJX_RAW_SLAB", "MJX_FVP_BF16X3", "MJX_NO_HCACHE", "MJX_FVP_SWEEP", "MJX_K3_XIMG"):
+        if k not in ARMS[arm][0]:
+            env.pop(k, None)
+    subprocess.run([sys.executable, os.path.join(HERE, "_fused_matrix_worker.py"), path, out_dir], check=True, env=env, timeout=600)
+    return {c["name"]: dict(np.load(os.path.join(out_dir, c["name"] + ".npz"))) for c in specs}
+
+
+@pytest.fixture(scope="module")
+def runs(tmp_path_factory):
+    """arm -> {case name: device results}; each arm's worker runs once, on first use.  A worker that fails (an error, a fault,
+    a timeout) is never started again: the failure is kept, and every later request -- for that arm or any other, since the
+    GPU may be left in a bad state -- fails at once without starting a process."""
+    cache, failed = {}, []
+
+    def get(arm):
+        if failed:
+            pytest.fail("not started: the %s worker failed earlier in this module (%s)" % failed[0])
+        if arm not in cache:
+            d = str(tmp_path_factory.mktemp(arm))
+            try:
+                cache[arm] = _run_worker(arm, [spec(nm, arm) for nm in ARMS[arm][1]], d)
+            except (subprocess.SubprocessError, OSError) as e:
+                failed.append((arm, e))
+                raise
+        return cache[arm]
+    return get
+
+
+# ---------------------------------------------------------------------------------------------------------------- checks
+def check_case(name, r, arm="default"):
+    c = spec(name, arm)
+    m = c["m"]
+    assert (int(r["variant"]), int(r["npc"])) == (c["variant"], c["npc"]) and (int(r["raw_dr"]) > 0) == c["raw"]
+    if name.endswith("_big"):
+        assert int(r["N"]) == 2 * int(r["grid"]) * 128 + 33
+    if c["prefix"]:
+        assert "hv_pre" in r and "s_pre" in r
+    e = errors(name, r)
+    print(name, arm, json.dumps({k: v for k, v in e.items() if k != "fine"}), {k: v for k, v in e["fine"].items()})
+    # whole-vector and scalar bars of test_other_shapes_vs_oracle
+    assert e["whole"]["g"] < TOL_VPG, ("K1", e["whole"]["g"])
+    for k in ("hv_rc", "hv", "hv_fwd", "hv_pre"):
+        if k in e["whole"]:
+            assert e["whole"][k] < TOL_FVP, (k, e["whole"][k])
+    for a in probe_actions(m):                  # only output row a of the direction is non-zero: a dropped or misplaced action is O(1)
+        assert e["whole"]["hv_a%d" % a] < TOL_FVP, ("probe", a, e["whole"]["hv_a%d" % a])
+    assert e["whole"]["g2"] < (5e-6 if m <= 16 else TOL_STEP), ("K1 old != new", e["whole"]["g2"])
+    assert e["scal"]["surr"] < 5e-6, ("K1 surrogate", e["scal"]["surr"])
+    for k, d in e["scal"].items():
+        assert d < 5e-6, (k, d)
+    for k, (d, kl) in e["kl"].items():
+        assert d < 2e-5 * kl + 1e-7, (k, d, kl)
+    # the finer measures
+    for k, worst in e["fine"].items():
+        bad = over_bars(worst, BARS[bar_kind(k)])
+        assert not bad, (k, bad)
+    # the two sweep directions sum other tile sets per workgroup
+    assert rel(r["hv"], r["hv_fwd"]) < TOL_SAME, rel(r["hv"], r["hv_fwd"])
+
+
+@pytest.mark.parametrize("name", BASE_CASES)
+def test_fused_vs_oracle(runs, name):
+    check_case(name, runs("default")[name])
+
+
+@pytest.mark.parametrize("name", EDGE_CASES + BIG_CASES)
+def test_fused_row_edges_vs_oracle(runs, name):
+    check_case(name, runs("default")[name])
+
+
+@pytest.mark.parametrize("name", ARMS["raw0"][1])
+def test_flat_order_epilogue_is_bit_identical(runs, name):
+    """MJX_RAW_SLAB=0: the workgroup partials in flat parameter order, reduced by k_reduce_partials4 -- or, where d % 4 != 0 (m
+    odd), by k_reduce_partials + k_reduce_scalars: "the same bits" (fused_policy.h, RawSlab); also the fallback when fill_perm
+    rejects a table"""
+    a, b = runs("default")[name], runs("raw0")[name]
+    assert int(a["raw_dr"]) > 0 and int(b["raw_dr"]) == 0
+    assert int(a["N"]) == int(b["N"])
+    for k in ("g", "hv", "hv_fwd", "surr"):
+        assert np.array_equal(a[k], b[k]), k
+    check_case(name, b, "raw0")
+
+
+@pytest.mark.parametrize("name", ARMS["bf3_0"][1])
+def test_fp32_cached_product_vs_oracle(runs, name):
+    """MJX_FVP_BF16X3=0: the 64 x 64 / 8-action instances' cached product on fp32 MFMAs, the fallback of the bf16x3 kernel"""
+    a, b = runs("default")[name], runs("bf3_0")[name]
+    check_case(name, b, "bf3_0")
+    for k in ("hv", "hv_fwd"):
+        assert not np.array_equal(a[k], b[k]), (k, "the switch selected no other kernel")
+        assert rel(b[k], a[k]) < TOL_SAME, (k, rel(b[k], a[k]))
+
+
+@pytest.mark.parametrize("name", ARMS["nohcache"][1])
+def test_no_cache_arm_vs_oracle(runs, name):
+    """MJX_NO_HCACHE=1: no activation cache, no stored old-policy outputs: every product recomputes the forward pass, every K3
+    both policies"""
+    check_case(name, runs("nohcache")[name], "nohcache")
