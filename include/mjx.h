@@ -70,6 +70,11 @@ int mjx_uses_fused_path(const mjx_ctx* ctx);
  * out4[2] = columns of the accumulator-order partial slab (0 = the flat-order epilogue), out4[3] = workgroups per launch (K3 with
  * up to 8 actions launches twice as many).  A layer-wise context returns 0 in all four. */
 int mjx_fused_info(const mjx_ctx* ctx, int32_t* out4);
+/* What would serve a shape, from the same instance table (arithmetic only: no context, no device, no runtime call):
+ * out4[0] = variant id as above (0 = the layer-wise path), out4[1] = compile-time feature count, out4[2] = columns of that
+ * instance's accumulator-order slab (0 = the flat-order epilogue), out4[3] = bytes of LDS of its layout.  mjx_create's
+ * environment switches (MJX_FORCE_LAYERWISE, MJX_RAW_SLAB) are not looked at.  MJX_ERR_ARG: null pointers, sizes <= 0. */
+int mjx_fused_route(int n, int m, const int* hidden, int n_hidden, int32_t* out4);
 
 /* ---- plain device-memory helpers (so a C / cgo / JNI caller needs no torch; tests/c/c_caller.c) -- */
 /* hipMalloc of bytes + 16: an observation block allocated here can never fault on the up-to-12-byte tail read documented at

@@ -26,6 +26,7 @@ PROTOTYPES = {
     "mjx_num_params": (c_int64, [c_void_p]),
     "mjx_uses_fused_path": (c_int, [c_void_p]),
     "mjx_fused_info": (c_int, [c_void_p, ctypes.POINTER(ctypes.c_int32)]),
+    "mjx_fused_route": (c_int, [c_int, c_int, ctypes.POINTER(c_int), c_int, ctypes.POINTER(ctypes.c_int32)]),
     "mjx_malloc": (c_int, [ctypes.POINTER(c_void_p), c_int64]),
     "mjx_free": (c_int, [c_void_p]),
     "mjx_memcpy_h2d": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),

@@ -89,41 +89,27 @@ struct ForkGuardInit { ForkGuardInit() { pthread_atfork(nullptr, nullptr, atfork
 
 }  // namespace
 
+#include "fused_host.h"
+
 struct mjx_ctx {
   int device = 0;
   int n = 0, m = 0;
   std::vector<int> hidden;
   int64_t d = 0;
   int oS = 0;                      // offset of log_std in the flat vector
-  int n_cu = 256;
-  // fused path
-  int fused = 0;                   // 0 = layer-wise, else variant id
-  int grid = 256;
-  size_t lds_bytes = 0;
   // bound inputs
   const float *obs = nullptr, *act = nullptr, *adv = nullptr;
   int64_t N_local = 0, N_global = 0;
   const float *theta_new = nullptr, *theta_old = nullptr, *tr_new = nullptr, *tr_old = nullptr;
   int old_is_new = 1;
   bool batch_bound = false;
-  float* hcache = nullptr; size_t hcache_bytes = 0;   // forward-activation cache of the fused path
-  bool hcache_valid = false; const float* hcache_obs = nullptr; int64_t hcache_rows = 0;
-  bool ximg_ok = false; int64_t ximg_rows = 0;        // the cache's normalised-observation image outlives a parameter change (K3 reads it)
-  int use_hcache = 1;
-  float* ocache = nullptr; size_t ocache_bytes = 0;   // old-policy outputs of the batch (K1 -> K3)
-  float* snap = nullptr;                              // parameters + transforms they were computed with
-  bool ocache_valid = false; int64_t ocache_rows = 0;
   int64_t rows_bound = 0;                             // rows handed to the last mjx_bind_batch
   // workspace (device)
-  float* partials = nullptr;       // [grid][max(d, raw_dr)]
-  int raw_dr = 0; int* raw_perm = nullptr;   // fused path: workgroup partials in accumulator order + the column -> flat index table (fused_policy.h RawSlab)
-  double* spartials = nullptr;     // [grid][4]
   float* ident_tr = nullptr;       // identity transforms
   float *cg_x = nullptr, *cg_r = nullptr, *cg_p = nullptr, *cg_z = nullptr, *cg_Ap = nullptr;
   double* cg_scal = nullptr;       // 8 doubles
   float* dbg = nullptr;
   long long* clk = nullptr;        // launch clock stamps (mjx_set_clock_buffer)
-  unsigned fvp_seq = 0;            // products since the cache was filled / the last solve began: alternate sweep direction
   bool lw_old_ok = false;          // K1's outputs are the OLD policy's (old == new at K1; theta_old, its transform and the batch untouched since by this
                                    // library): set by mjx_surr_vpg, cleared by the public binding calls, consumed by the one-call updates' evaluations
                                    // (layer-wise path: reuse of the output block; fused path: the snapshot compare of K3's prologue is skipped)
@@ -146,6 +132,7 @@ struct mjx_ctx {
     int fault = 0;                                     // MJX_PEER_FAULT (tests): 1 = "slot" (vectors land in the wrong slot at the peers), 2 = "flag" (arrival flags never raised)
   } peer;
   unsigned* ticket = nullptr;                      // workgroup ticket of the producer kernels (ordinary device memory, zero between launches)
+  mjx::FusedWS fz;                 // fused path workspace (fz.variant != 0: it serves this context)
   mjx::LayerwiseWS lw;             // layer-wise path workspace
   mjx::LayerwiseWS lwmb;           // minibatch trainer workspace (mjx_policy_minibatch_adam)
   float *mb_x = nullptr, *mb_a = nullptr, *mb_adv = nullptr, *mb_grad = nullptr; int mb_cap = 0;
@@ -155,131 +142,26 @@ namespace {
 
 using namespace mjx;
 
-template <int H1, int H2, int NT1, int MP, bool DBG = false, int NPC = 0>
-int launch_fused(mjx_ctx* c, int mode, const FusedArgs& a, hipStream_t st) {
-  const bool ev2 = (mode == MODE_EVAL) && MP <= 8;   // MODE_EVAL (always the non-debug instance): small layout, two workgroups per CU (fused_policy.h)
-  const bool cached = (mode == MODE_FVP) && a.hcache != nullptr && !DBG;
-  // the cached 64 x 64 product with up to 8 actions runs its 64x64 products on bf16x3 MFMAs (k_fused<..., BF3 = true>);
-  // MJX_FVP_BF16X3=0 selects the fp32 kernel (read once per process)
-  static const bool bf3_on = env_flag("MJX_FVP_BF16X3", true);
-  // (64 x 64 with up to 8 actions only, and only while its layout -- two 24 KB piece images -- fits 160 KB: up to 23 observations)
-  constexpr bool BF3_OK = H1 == 64 && H2 == 64 && MP == 8;
-  const bool bf3 = BF3_OK && cached && bf3_on && FusedLayout<H1, H2, NT1, MP>(NPC ? NPC - 1 : c->n, false, true).bytes() <= LDS_MAX;
-  FusedLayout<H1, H2, NT1, MP> L(NPC ? NPC - 1 : c->n, ev2, bf3);  // (the kernel's rule: fused_policy.h)
-  size_t bytes = L.bytes();
-  void (*k)(FusedArgs) = nullptr;
-  if (mode == MODE_VPG) k = k_fused<H1, H2, NT1, MP, MODE_VPG, DBG, NPC>;
-  else if (mode == MODE_FVP) k = cached ? k_fused<H1, H2, NT1, MP, MODE_FVP, false, NPC, true> : k_fused<H1, H2, NT1, MP, MODE_FVP, DBG, NPC>;
-  else k = k_fused<H1, H2, NT1, MP, MODE_EVAL, false, NPC>;
-  // ... and its W2 gradient (R9) too; MJX_FVP_BF16X3_R9=0 keeps that one product on fp32 MFMAs (read once per process)
-  static const bool bf3_r9_on = env_flag("MJX_FVP_BF16X3_R9", true);
-  if constexpr (BF3_OK) {
-    if (bf3) k = bf3_r9_on ? k_fused<H1, H2, NT1, MP, MODE_FVP, false, NPC, true, true, true> : k_fused<H1, H2, NT1, MP, MODE_FVP, false, NPC, true, true>;
-  }
-  if (cached) mode = 3;
-  // (FusedLayout::bytes() depends on the runtime observation count: the generic NPC = 0 instances serve many sizes)
-  if (int rc = lds_limit((const void*)k, bytes)) return rc;
-  hipLaunchKernelGGL(k, dim3(ev2 ? 2 * c->grid : c->grid), dim3(256), bytes, st, a);
-  HIPCHK(hipGetLastError());
-  return MJX_OK;
-}
+const float* tr_new_or_ident(const mjx_ctx* c) { return c->tr_new ? c->tr_new : c->ident_tr; }
+const float* tr_old_or_ident(const mjx_ctx* c) { return c->tr_old ? c->tr_old : c->ident_tr; }
 
-// variant table: id -> (H1, H2, NT1, MP)
-// the compile-time feature count a shape is served with (dispatch_fused's rule): 64 x 64 x <= 8 actions with 4..7 / 8..11 / 16..19 observations
-int npc_of(int fused, int n) {
-  const int NPr = (n + 1 + 3) & ~3;
-#ifdef MJX_PHASE_CLOCK
-  return (fused == 1 && NPr == 20) ? 20 : 0;       // (the timing build: NPC = 20 or the generic instance, debug buffer or not)
-#else
-  return (fused == 1 && (NPr == 20 || NPr == 12 || NPr == 8)) ? NPr : 0;
-#endif
-}
-// -> RawSlab<...>::DR of the instance (variant id, NPC) and, with perm != nullptr, its column -> flat index table; 0: unknown instance / bad table
-int raw_slab(int fused, int npc, int n, int m, std::vector<int>* perm) {
-  auto one = [&](auto rs) -> int {
-    using RS = decltype(rs);
-    if (perm) { perm->assign(RS::DR, -1); if (!RS::fill_perm(perm->data(), n, m)) return 0; }
-    return RS::DR;
-  };
-  switch (fused) {
-    case 1: return npc == 20 ? one(RawSlab<64, 64, 1, 8, 20>{}) : npc == 12 ? one(RawSlab<64, 64, 1, 8, 12>{}) : npc == 8 ? one(RawSlab<64, 64, 1, 8, 8>{})
-                                                                                                                             : one(RawSlab<64, 64, 1, 8, 0>{});
-    case 2: return one(RawSlab<32, 32, 1, 8, 0>{});
-    case 3: return one(RawSlab<64, 64, 1, 16, 0>{});
-    case 4: return one(RawSlab<32, 32, 1, 16, 0>{});
-    case 5: return one(RawSlab<32, 32, 2, 8, 0>{});
-    case 6: return one(RawSlab<32, 32, 2, 32, 0>{});
-  }
-  return 0;
-}
-
-template <int H1, int H2, int NT1, int MP>
-bool variant_fits(int n, int m, int h1, int h2, int64_t d, size_t* bytes) {
-  if (h1 != H1 || h2 != H2 || m > MP || n + 1 > 32 * NT1) return false;
-  FusedLayout<H1, H2, NT1, MP> L(n);
-  if (L.bytes() > LDS_MAX) return false;
-  if ((size_t)(4 * d + 64) * 4 > L.bytes()) return false;   // end-of-kernel reduction region
-  *bytes = L.bytes();
-  return true;
-}
-
-int pick_variant(int n, int m, const std::vector<int>& hid, int64_t d, size_t* bytes) {
-  if (hid.size() != 2) return 0;
-  int h1 = hid[0], h2 = hid[1];
-  if (variant_fits<64, 64, 1, 8>(n, m, h1, h2, d, bytes)) return 1;
-  if (variant_fits<32, 32, 1, 8>(n, m, h1, h2, d, bytes)) return 2;
-  if (variant_fits<64, 64, 1, 16>(n, m, h1, h2, d, bytes)) return 3;
-  if (variant_fits<32, 32, 1, 16>(n, m, h1, h2, d, bytes)) return 4;
-  if (variant_fits<32, 32, 2, 8>(n, m, h1, h2, d, bytes)) return 5;
-  if (variant_fits<32, 32, 2, 32>(n, m, h1, h2, d, bytes)) return 6;      // Adroit-class: 39-46 observations, 24-30 actions, 32 x 32 (hand_dapg)
-  return 0;
-}
-
-int dispatch_fused(mjx_ctx* c, int mode, const FusedArgs& a, hipStream_t st) {
-  // shape-specialised instances (compile-time feature count => fully unrolled first layer)
-  const int NPr = (c->n + 1 + 3) & ~3;
-#ifdef MJX_PHASE_CLOCK
-  if (c->fused == 1 && NPr == 20) return launch_fused<64, 64, 1, 8, false, 20>(c, mode, a, st);
-#endif
-  if (c->fused == 1 && NPr == 20 && !c->dbg) return launch_fused<64, 64, 1, 8, false, 20>(c, mode, a, st);   // obs 16..19 (HalfCheetah 17)
-  if (c->fused == 1 && NPr == 12 && !c->dbg) return launch_fused<64, 64, 1, 8, false, 12>(c, mode, a, st);   // obs 8..11 (Hopper 11, Reacher 11, Swimmer 8)
-  if (c->fused == 1 && NPr == 8 && !c->dbg) return launch_fused<64, 64, 1, 8, false, 8>(c, mode, a, st);     // obs 4..7 (InvertedPendulum 4, point_mass 6)
-  switch (c->fused) {
-#ifdef MJX_PHASE_CLOCK
-    case 1: return launch_fused<64, 64, 1, 8>(c, mode, a, st);          // stamps go to the debug buffer of the production kernel
-#else
-    case 1: return c->dbg ? launch_fused<64, 64, 1, 8, true>(c, mode, a, st) : launch_fused<64, 64, 1, 8>(c, mode, a, st);
-#endif
-    case 2: return launch_fused<32, 32, 1, 8>(c, mode, a, st);
-    case 3: return launch_fused<64, 64, 1, 16>(c, mode, a, st);
-    case 4: return launch_fused<32, 32, 1, 16>(c, mode, a, st);
-    case 5: return launch_fused<32, 32, 2, 8>(c, mode, a, st);
-    case 6: return launch_fused<32, 32, 2, 32>(c, mode, a, st);
-  }
-  return fail(MJX_ERR_STATE, "no fused variant");
-}
-
-FusedArgs make_args(mjx_ctx* c, const float* thetaB) {
-  FusedArgs a;
-  a.obs = c->obs; a.act = c->act; a.adv = c->adv;
-  a.N = c->N_local;
+// the bound inputs as the fused kernels take them; FusedWS adds its own part (fused_host.h complete())
+FusedArgs bound_args(const mjx_ctx* c, const float* thetaB) {
+  FusedArgs a{};
+  a.obs = c->obs; a.act = c->act; a.adv = c->adv; a.N = c->N_local;
   a.inv_N = (float)(1.0 / (double)c->N_global);
-  a.thetaA = c->theta_new; a.thetaB = thetaB;
-  a.trA = c->tr_new ? c->tr_new : c->ident_tr;
-  a.trB = c->tr_old ? c->tr_old : c->ident_tr;
+  a.thetaA = c->theta_new; a.thetaB = thetaB; a.trA = tr_new_or_ident(c); a.trB = tr_old_or_ident(c);
   a.old_is_new = c->old_is_new;
-  a.partials = c->partials; a.spartials = c->spartials;
-  a.dbg = c->dbg;
-  a.clk = c->clk;
-  a.reverse = 0;
-  a.hcache = nullptr; a.ocache = nullptr; a.snap = nullptr; a.snap_out = nullptr; a.snap_trusted = 0;
+  a.dbg = c->dbg; a.clk = c->clk;
   a.n = c->n; a.m = c->m;
-#ifdef MJX_PHASE_CLOCK
-  a.raw_dr = c->raw_perm ? c->raw_dr : 0;
-#else
-  a.raw_dr = (c->raw_perm && !c->dbg) ? c->raw_dr : 0;      // (the debug instances may be another NPC: flat-order partials)
-#endif
   return a;
+}
+
+// f(integral_constant<W>) with the compile-time rank count of the folded kernels that covers `world`: 2, 4, 8 or 16
+template <class F>
+void with_world_width(int world, F&& f) {
+  if (world <= 2) f(std::integral_constant<int, 2>{}); else if (world <= 4) f(std::integral_constant<int, 4>{});
+  else if (world <= 8) f(std::integral_constant<int, 8>{}); else f(std::integral_constant<int, 16>{});
 }
 
 int check_bound(mjx_ctx* c, bool need_act) {
@@ -326,25 +208,7 @@ int mjx_create(mjx_ctx** out, int device, int n, int m, const int* hidden, int n
   c->oS = (int)d;
   d += m;
   c->d = d;
-  c->n_cu = cu_count();
-  c->grid = c->n_cu;
-  c->fused = pick_variant(n, m, c->hidden, d, &c->lds_bytes);
-  if (env_flag("MJX_FORCE_LAYERWISE", false)) c->fused = 0;
-  if (env_flag("MJX_NO_HCACHE", false)) c->use_hcache = 0;
-  if (c->fused) {
-    // workgroup partials in accumulator order (RawSlab): the table is made here, once; any doubt about it (an instance this
-    // switch does not know, a table that does not hit every flat index exactly once, no room for the four copies in LDS) keeps
-    // the flat-order epilogue.  MJX_RAW_SLAB=0: A/B.
-    std::vector<int> perm;
-    const int dr = !env_flag("MJX_RAW_SLAB", true) ? 0 : raw_slab(c->fused, npc_of(c->fused, n), n, m, &perm);
-    if (dr > 0 && (size_t)(4 * dr + 64) * 4 <= c->lds_bytes) {
-      HIPCHK(hipMalloc((void**)&c->raw_perm, (size_t)dr * sizeof(int)));
-      HIPCHK(hipMemcpy(c->raw_perm, perm.data(), (size_t)dr * sizeof(int), hipMemcpyHostToDevice));
-      c->raw_dr = dr;
-    }
-  }
-  HIPCHK(hipMalloc(&c->partials, (size_t)c->grid * (size_t)(c->raw_dr > d ? c->raw_dr : d) * sizeof(float)));
-  HIPCHK(hipMalloc(&c->spartials, (size_t)2 * c->grid * 4 * sizeof(double)));       // (MODE_EVAL launches 2 workgroups per CU)
+  if (int rc = c->fz.init(n, m, d, c->oS, c->hidden, cu_count(), env_flag("MJX_FORCE_LAYERWISE", false))) return rc;
   HIPCHK(hipMalloc(&c->cg_x, d * 4)); HIPCHK(hipMalloc(&c->cg_r, d * 4)); HIPCHK(hipMalloc(&c->cg_p, d * 4));
   HIPCHK(hipMalloc(&c->cg_z, d * 4)); HIPCHK(hipMalloc(&c->cg_Ap, d * 4));
   HIPCHK(hipMalloc((void**)&c->ticket, 256)); HIPCHK(hipMemset(c->ticket, 0, 256));
@@ -354,7 +218,7 @@ int mjx_create(mjx_ctx** out, int device, int n, int m, const int* hidden, int n
   for (int i = 0; i < m; ++i) id[2 * n + m + i] = 1.f;
   HIPCHK(hipMalloc(&c->ident_tr, id.size() * 4));
   HIPCHK(hipMemcpy(c->ident_tr, id.data(), id.size() * 4, hipMemcpyHostToDevice));
-  HIPCHK(hipMemset(c->spartials, 0, (size_t)2 * c->grid * 4 * sizeof(double)));
+  HIPCHK(hipMemset(c->fz.spartials, 0, c->fz.spartials_bytes()));
   c->lw.init(n, m, c->hidden);
   c->lwmb.init(n, m, c->hidden);
   *out = c;
@@ -369,24 +233,24 @@ void mjx_destroy(mjx_ctx* c) {
   c->lwmb.release();
   hipFree(c->mb_x); hipFree(c->mb_a); hipFree(c->mb_adv); hipFree(c->mb_grad);
   for (auto& e : c->prof_ev) hipEventDestroy(e);
-  hipFree(c->hcache);
-  hipFree(c->ocache);
-  hipFree(c->snap);
-  hipFree(c->partials); hipFree(c->spartials); hipFree(c->ident_tr); hipFree(c->raw_perm);
+  c->fz.release();
+  hipFree(c->ident_tr);
   hipFree(c->cg_x); hipFree(c->cg_r); hipFree(c->cg_p); hipFree(c->cg_z); hipFree(c->cg_Ap); hipFree(c->ticket); hipFree(c->cg_scal);
   delete c;
 }
 
 int64_t mjx_num_params(const mjx_ctx* c) { return c ? c->d : -1; }
-int mjx_uses_fused_path(const mjx_ctx* c) { return c ? (c->fused != 0) : 0; }
+int mjx_uses_fused_path(const mjx_ctx* c) { return c ? (c->fz.variant != 0) : 0; }
 int mjx_fused_info(const mjx_ctx* c, int32_t* out) {
   if (!c || !out) return fail(MJX_ERR_ARG, "bad arguments");
-  out[0] = out[1] = out[2] = out[3] = 0;
-  if (!c->fused) return MJX_OK;
-  out[0] = c->fused;
-  out[1] = npc_of(c->fused, c->n);
-  out[2] = c->raw_perm ? c->raw_dr : 0;
-  out[3] = c->grid;
+  c->fz.info(out);
+  return MJX_OK;
+}
+int mjx_fused_route(int n, int m, const int* hidden, int n_hidden, int32_t* out4) {
+  if (!out4 || n <= 0 || m <= 0 || n_hidden < 0 || (n_hidden > 0 && !hidden)) return fail(MJX_ERR_ARG, "bad arguments");
+  for (int i = 0; i < n_hidden; ++i) if (hidden[i] <= 0) return fail(MJX_ERR_ARG, "bad hidden size");
+  const FusedRoute r = fused_route(n, m, std::vector<int>(hidden, hidden + n_hidden));
+  out4[0] = r.variant; out4[1] = r.npc; out4[2] = r.raw_dr; out4[3] = (int32_t)r.bytes;
   return MJX_OK;
 }
 
@@ -409,12 +273,10 @@ int mjx_bind_batch(mjx_ctx* c, const float* obs, const float* act, const float* 
   c->obs = obs; c->act = act; c->adv = adv; c->N_local = N_local; c->N_global = N_global;
   c->batch_bound = true;
   c->rows_bound = N_local;
-  c->hcache_valid = false;                      // a new batch: nothing cached from earlier calls applies
-  c->ocache_valid = false;
-  c->ximg_ok = false;
+  c->fz.on_batch();                             // a new batch: nothing cached from earlier calls applies
   c->lw.invalidate();
   c->lw_old_ok = false;
-  if (!c->fused) {
+  if (!c->fz.variant) {
     // the layer-wise launches put one 128-row tile per grid row: gridDim.y <= 65 535 -> 8 388 480 rows per context (BASELINE
     // configs[4] at its full 8M + demonstrations fits; beyond that, shard the batch -- element and byte offsets are 64-bit throughout)
     if (N_local > (int64_t)65535 * 128) return fail(MJX_ERR_ARG, "layer-wise path: at most %lld rows per context (got %lld): bind the batch in shards", (long long)65535 * 128, (long long)N_local);
@@ -428,16 +290,11 @@ int mjx_bind_rows(mjx_ctx* c, int64_t N_local, int64_t N_global, const float* ad
   if (N_local < 0 || N_local > c->rows_bound || N_global < N_local || N_global <= 0) return fail(MJX_ERR_ARG, "bad row count");
   c->N_local = N_local; c->N_global = N_global;
   if (adv) c->adv = adv;
-  c->lw.narrow(N_local);                        // (r06: a prefix of the bound rows keeps the activations cached for it -- DAPG's on-policy prefix)
+  c->lw.narrow(N_local);                        // (a prefix of the bound rows keeps the activations cached for it -- DAPG's on-policy prefix;
+                                                //  the fused caches are valid for any prefix of the rows they were filled for)
   return MJX_OK;
 }
 
-static int bind_policy_impl(mjx_ctx* c, const float* theta_new, const float* theta_old, const float* tr_new,
-                            const float* tr_old, int old_is_new, bool keep_old_outputs);
-int mjx_bind_policy(mjx_ctx* c, const float* theta_new, const float* theta_old, const float* tr_new,
-                    const float* tr_old, int old_is_new) {
-  return bind_policy_impl(c, theta_new, theta_old, tr_new, tr_old, old_is_new, false);
-}
 // keep_old_outputs: the one-call updates re-bind (stepped parameters, the SAME old parameters) between their K1 and their
 // evaluations -- the old policy's cached outputs stay usable; a caller's own binding may come with new contents under the same pointers
 static int bind_policy_impl(mjx_ctx* c, const float* theta_new, const float* theta_old, const float* tr_new,
@@ -448,8 +305,11 @@ static int bind_policy_impl(mjx_ctx* c, const float* theta_new, const float* the
   c->theta_new = theta_new; c->theta_old = theta_old; c->tr_new = tr_new; c->tr_old = tr_old;
   c->old_is_new = old_is_new ? 1 : 0;
   c->lw.invalidate();
-  c->hcache_valid = false;
+  c->fz.on_policy();
   return MJX_OK;
+}
+int mjx_bind_policy(mjx_ctx* c, const float* theta_new, const float* theta_old, const float* tr_new, const float* tr_old, int old_is_new) {
+  return bind_policy_impl(c, theta_new, theta_old, tr_new, tr_old, old_is_new, false);
 }
 
 // ---------------------------------------------------------------------------- K6 baselines
@@ -1064,59 +924,10 @@ static int surr_vpg_impl(mjx_ctx* c, float* grad_out, double* scal_out, void* st
     HIPCHK(hipMemsetAsync(scal_out, 0, 4 * sizeof(double), st));
     return MJX_OK;
   }
-  if (!c->fused) {
-    if (c->lw.surr_vpg(c->obs, c->act, c->adv, c->N_local, c->N_global, c->theta_new, c->theta_old,
-                       c->tr_new ? c->tr_new : c->ident_tr, c->tr_old ? c->tr_old : c->ident_tr, c->old_is_new,
-                       grad_out, scal_out, st)) return fail(MJX_ERR_STATE, "layer-wise surr_vpg failed");
-    c->lw_old_ok = c->old_is_new != 0;          // its output block now holds the old policy's means for the bound rows
-    return MJX_OK;
-  }
-  FusedArgs a = make_args(c, c->theta_old);
-  c->hcache_valid = false;
-  c->ximg_ok = false;
-  c->fvp_seq = 0;
-  if (c->use_hcache && c->old_is_new && c->hidden.size() == 2) {
-    // keep h1 / h2 of every sample for the Fisher-vector products of this update (theta is fixed during CG)
-    // per 32-sample tile: h1, h2 (sample-lane accumulator image) + the normalised observations (layer-1 operand image)
-    const size_t need = (size_t)((c->N_local + 31) / 32) *
-                        ((size_t)(c->hidden[0] / 32 + c->hidden[1] / 32) * 1024 + (size_t)(((c->n + 1 + 3) & ~3) / 4) * 128) * sizeof(float);
-    if (need > c->hcache_bytes) {
-      if (c->hcache) hipFree(c->hcache);
-      c->hcache = nullptr; c->hcache_bytes = 0;
-      if (hipMalloc(&c->hcache, need) == hipSuccess) c->hcache_bytes = need; else (void)hipGetLastError();
-    }
-    if (c->hcache) { a.hcache = c->hcache; c->hcache_valid = true; c->hcache_obs = c->obs; c->hcache_rows = c->N_local;
-                     c->ximg_ok = true; c->ximg_rows = c->N_local; }
-    // ... and the old policy's means / log-likelihoods for mjx_eval_surr_kl (old == new here), with a snapshot of
-    // the parameters they belong to (the EVAL kernel compares before trusting them)
-    const size_t oneed = (size_t)((c->N_local + 31) / 32) * 33 * 32 * sizeof(float);     // [tile][MP + 1][32] with MP <= 32 (largest fused variant)
-    if (oneed > c->ocache_bytes) {
-      if (c->ocache) hipFree(c->ocache);
-      c->ocache = nullptr; c->ocache_bytes = 0;
-      if (hipMalloc(&c->ocache, oneed) == hipSuccess) c->ocache_bytes = oneed; else (void)hipGetLastError();
-    }
-    if (!c->snap && hipMalloc(&c->snap, (size_t)(c->d + 2 * (c->n + c->m)) * sizeof(float)) != hipSuccess) { c->snap = nullptr; (void)hipGetLastError(); }
-    c->ocache_valid = false;
-    if (c->ocache && c->snap) {
-      a.snap_out = c->snap;                      // written by the kernel itself (no separate copies on the stream)
-      a.ocache = c->ocache; c->ocache_valid = true; c->ocache_rows = c->N_local;
-    }
-  }
-  // (the one-call updates' evaluations may trust the snapshot without comparing: they run before anything outside the library can)
-  c->lw_old_ok = c->old_is_new != 0 && a.ocache != nullptr;
-  if (int rc = dispatch_fused(c, MODE_VPG, a, st)) return rc;
-  if ((c->d & 3) == 0 || a.raw_dr > 0) {
-    // the 4 sums are reduced by one extra workgroup of the vector reduction (r06: no launch of their own)
-    const int cols = a.raw_dr > 0 ? a.raw_dr : (int)c->d;
-    hipLaunchKernelGGL(k_reduce_partials4, dim3((cols + 31) / 32 + 1), dim3(256), 0, st, c->partials, c->grid, cols,
-                       grad_out, (const float*)nullptr, (const float*)nullptr, c->oS, 0.f, pp ? *pp : PeerPush{},
-                       ScalTail{c->spartials, c->grid, scal_out, pp ? scal_off : -1}, a.raw_dr > 0 ? (const int*)c->raw_perm : (const int*)nullptr);
-  } else {
-    hipLaunchKernelGGL(k_reduce_partials, dim3((c->d + 15) / 16), dim3(256), 0, st, c->partials, c->grid, (int)c->d,
-                       grad_out, (const float*)nullptr, (const float*)nullptr, c->oS, 0.f);
-    hipLaunchKernelGGL(k_reduce_scalars, dim3(1), dim3(256), 0, st, c->spartials, c->grid, scal_out, PeerPush{});
-  }
-  HIPCHK(hipGetLastError());
+  if (c->fz.variant) return c->fz.surr_vpg(bound_args(c, c->theta_old), grad_out, scal_out, pp, scal_off, st, &c->lw_old_ok);
+  if (c->lw.surr_vpg(c->obs, c->act, c->adv, c->N_local, c->N_global, c->theta_new, c->theta_old, tr_new_or_ident(c), tr_old_or_ident(c),
+                     c->old_is_new, grad_out, scal_out, st)) return fail(MJX_ERR_STATE, "layer-wise surr_vpg failed");
+  c->lw_old_ok = c->old_is_new != 0;            // its output block now holds the old policy's means for the bound rows
   return MJX_OK;
 }
 
@@ -1126,44 +937,24 @@ int mjx_surr_vpg(mjx_ctx* c, float* grad_out, double* scal_out, void* stream) { 
 static int fvp_impl(mjx_ctx* c, const float* v, float* out, void* stream, const PeerPush* pp) {
   if (int rc = check_bound(c, false)) return rc;
   if (!v || !out) return fail(MJX_ERR_ARG, "null vector");
-  if (c->fused && (((uintptr_t)v) & 15)) return fail(MJX_ERR_ARG, "v must be 16-byte aligned (fused path)");   // (the layer-wise path takes any 4-byte aligned v)
+  if (c->fz.variant && (((uintptr_t)v) & 15)) return fail(MJX_ERR_ARG, "v must be 16-byte aligned (fused path)");   // (the layer-wise path takes any 4-byte aligned v)
   hipStream_t st = (hipStream_t)stream;
   HIPCHK(hipSetDevice(c->device));
   if (c->N_local == 0) { HIPCHK(hipMemsetAsync(out, 0, c->d * sizeof(float), st)); return MJX_OK; }
   if (!c->old_is_new) {
     // general position (e.g. input_normalization, npg_cg.py:101-107): exact Pearlmutter product on the layer-wise path
     if (c->lw.cap < c->N_local) { if (int rc = c->lw.reserve(c->N_local)) return fail(rc, "layer-wise workspace allocation failed"); }
-    int rc = c->lw.hvp_general(c->obs, c->N_local, c->N_global, c->theta_new, c->theta_old, c->tr_new ? c->tr_new : c->ident_tr,
-                               c->tr_old ? c->tr_old : c->ident_tr, v, out, st);
+    int rc = c->lw.hvp_general(c->obs, c->N_local, c->N_global, c->theta_new, c->theta_old, tr_new_or_ident(c), tr_old_or_ident(c), v, out, st);
     return rc ? fail(MJX_ERR_STATE, "general Hessian-vector product failed (%d)", rc) : MJX_OK;
   }
-  const float frac = (float)((double)c->N_local / (double)c->N_global);
   const bool prof = c->prof_on && !c->prof_iter && (c->prof_seen++ % (size_t)c->prof_stride == 0) && c->prof_used + 2 <= c->prof_ev.size();
   if (prof) HIPCHK(hipEventRecord(c->prof_ev[c->prof_used], st));
-  if (!c->fused) {
-    int rc = c->lw.fvp(c->obs, c->N_local, c->N_global, c->theta_new, c->tr_new ? c->tr_new : c->ident_tr, v, out, st);
-    if (prof) { HIPCHK(hipEventRecord(c->prof_ev[c->prof_used + 1], st)); c->prof_used += 2; }
-    return rc ? fail(MJX_ERR_STATE, "layer-wise fvp failed") : MJX_OK;
-  }
-  FusedArgs a = make_args(c, v);
-  if (c->hcache_valid && c->N_local <= c->hcache_rows) a.hcache = c->hcache;
-  // alternate sweep direction: K1 filled the cache front to back, so the first product of a solve starts at the back, the
-  // next at the front, ... -- the lines the previous sweep touched last are the ones most likely still held by the
-  // memory-side cache (the 592 MB image does not fit; a one-directional walk would evict every line before its reuse)
-  const bool sweep_on = env_flag("MJX_FVP_SWEEP", true);
-  a.reverse = (a.hcache && sweep_on) ? (int)((c->fvp_seq++ & 1u) ^ 1u) : 0;
-  if (int rc = dispatch_fused(c, MODE_FVP, a, st)) return rc;
-  if (prof) { HIPCHK(hipEventRecord(c->prof_ev[c->prof_used + 1], st)); c->prof_used += 2; }
-  if ((c->d & 3) == 0 || a.raw_dr > 0) {
-    const int cols = a.raw_dr > 0 ? a.raw_dr : (int)c->d;
-    hipLaunchKernelGGL(k_reduce_partials4, dim3((cols + 31) / 32), dim3(256), 0, st, c->partials, c->grid, cols,
-                       out, c->theta_new, v, c->oS, frac, pp ? *pp : PeerPush{}, ScalTail{nullptr, 0, nullptr, -1},
-                       a.raw_dr > 0 ? (const int*)c->raw_perm : (const int*)nullptr);
-  } else
-    hipLaunchKernelGGL(k_reduce_partials, dim3((c->d + 15) / 16), dim3(256), 0, st, c->partials, c->grid, (int)c->d,
-                       out, c->theta_new, v, c->oS, frac);
-  HIPCHK(hipGetLastError());
-  return MJX_OK;
+  // (the bracket closes behind the product itself: the fused path's reduction of the partials stays outside it)
+  auto prof_end = [&]() -> int { if (prof) { HIPCHK(hipEventRecord(c->prof_ev[c->prof_used + 1], st)); c->prof_used += 2; } return MJX_OK; };
+  if (c->fz.variant) return c->fz.fvp(bound_args(c, v), out, (float)((double)c->N_local / (double)c->N_global), pp, st, prof_end);
+  const int rc = c->lw.fvp(c->obs, c->N_local, c->N_global, c->theta_new, tr_new_or_ident(c), v, out, st);
+  if (int e = prof_end()) return e;
+  return rc ? fail(MJX_ERR_STATE, "layer-wise fvp failed") : MJX_OK;
 }
 
 int mjx_fvp(mjx_ctx* c, const float* v, float* out, void* stream) { return fvp_impl(c, v, out, stream, nullptr); }
@@ -1176,21 +967,10 @@ static int eval_impl(mjx_ctx* c, double* scal_out, void* stream, const PeerPush*
   hipStream_t st = (hipStream_t)stream;
   HIPCHK(hipSetDevice(c->device));
   if (c->N_local == 0) { HIPCHK(hipMemsetAsync(scal_out, 0, 4 * sizeof(double), st)); return MJX_OK; }
-  if (!c->fused)
-    return c->lw.eval(c->obs, c->act, c->adv, c->N_local, c->theta_new, c->theta_old,
-                      c->tr_new ? c->tr_new : c->ident_tr, c->tr_old ? c->tr_old : c->ident_tr, scal_out, st,
-                      old_ok && c->lw_old_ok, c->old_is_new != 0)
-               ? fail(MJX_ERR_STATE, "layer-wise eval failed") : MJX_OK;
-  FusedArgs a = make_args(c, c->theta_old);
-  if (c->ocache_valid && c->N_local <= c->ocache_rows) { a.ocache = c->ocache; a.snap = c->snap; a.snap_trusted = (old_ok && c->lw_old_ok) ? 1 : 0; }
-  // K1's normalised-observation image of this batch (same rows, same observations; the kernel checks the input transform
-  // against the snapshot before it trusts it) spares K3 the staging and normalisation of the raw observations
-  const bool ximg_on = env_flag("MJX_K3_XIMG", true);
-  if (ximg_on && a.ocache && c->ximg_ok && c->hcache && c->N_local <= c->ximg_rows && c->obs == c->hcache_obs) a.hcache = c->hcache;
-  if (int rc = dispatch_fused(c, MODE_EVAL, a, st)) return rc;
-  hipLaunchKernelGGL(k_reduce_scalars, dim3(1), dim3(256), 0, st, c->spartials, 2 * c->grid, scal_out, pp ? *pp : PeerPush{});
-  HIPCHK(hipGetLastError());
-  return MJX_OK;
+  if (c->fz.variant) return c->fz.eval(bound_args(c, c->theta_old), scal_out, pp, old_ok && c->lw_old_ok, st);
+  return c->lw.eval(c->obs, c->act, c->adv, c->N_local, c->theta_new, c->theta_old, tr_new_or_ident(c), tr_old_or_ident(c), scal_out, st,
+                    old_ok && c->lw_old_ok, c->old_is_new != 0)
+             ? fail(MJX_ERR_STATE, "layer-wise eval failed") : MJX_OK;
 }
 
 int mjx_eval_surr_kl(mjx_ctx* c, double* scal_out, void* stream) { return eval_impl(c, scal_out, stream, nullptr); }
@@ -1231,17 +1011,23 @@ PeerSlots peer_slots(const mjx_ctx* c, int par, uint32_t seq) {
   ps.ticks = c->peer.timeout_ticks;
   return ps;
 }
+// the next exchange: its number, this rank's slot in the own buffer, the producer's and the consumer's view of it
+struct PeerRound { uint32_t seq; char* own; PeerPush push; PeerSlots slots; };
+PeerRound next_round(mjx_ctx* c) {
+  const uint32_t seq = ++c->peer.seq;
+  const int par = (int)(seq & 1u);
+  return PeerRound{seq, peer_slot(c, c->peer.rank, par, c->peer.rank), peer_push(c, par, seq), peer_slots(c, par, seq)};
+}
 int peer_allreduce(mjx_ctx* c, void* buf, int64_t count, int dtype, hipStream_t st) {
   const size_t bytes = (size_t)count * (dtype ? 8 : 4);
   if (bytes > c->peer.slot_bytes) return fail(MJX_ERR_ARG, "peer all-reduce of %zu bytes exceeds the slot (%zu)", bytes, c->peer.slot_bytes);
-  const uint32_t seq = ++c->peer.seq;
-  const int par = (int)(seq & 1u);
+  const PeerRound r = next_round(c);
   const unsigned grid = (unsigned)((count + 255) / 256);
-  if (dtype) hipLaunchKernelGGL(k_peer_push<double>, dim3(grid), dim3(256), 0, st, (const double*)buf, peer_push(c, par, seq), count);
-  else hipLaunchKernelGGL(k_peer_push<float>, dim3(grid), dim3(256), 0, st, (const float*)buf, peer_push(c, par, seq), count);
+  if (dtype) hipLaunchKernelGGL(k_peer_push<double>, dim3(grid), dim3(256), 0, st, (const double*)buf, r.push, count);
+  else hipLaunchKernelGGL(k_peer_push<float>, dim3(grid), dim3(256), 0, st, (const float*)buf, r.push, count);
   HIPCHK(hipGetLastError());
-  if (dtype) hipLaunchKernelGGL(k_peer_sum<double>, dim3(grid), dim3(256), 0, st, peer_slots(c, par, seq), (double*)buf, count);
-  else hipLaunchKernelGGL(k_peer_sum<float>, dim3(grid), dim3(256), 0, st, peer_slots(c, par, seq), (float*)buf, count);
+  if (dtype) hipLaunchKernelGGL(k_peer_sum<double>, dim3(grid), dim3(256), 0, st, r.slots, (double*)buf, count);
+  else hipLaunchKernelGGL(k_peer_sum<float>, dim3(grid), dim3(256), 0, st, r.slots, (float*)buf, count);
   HIPCHK(hipGetLastError());
   return MJX_OK;
 }
@@ -1249,7 +1035,7 @@ int peer_allreduce(mjx_ctx* c, void* buf, int64_t count, int dtype, hipStream_t 
 
 int mjx_cg_init(mjx_ctx* c, const float* b, void* stream) {
   if (!c || !b) return fail(MJX_ERR_ARG, "bad arguments");
-  c->fvp_seq = 0;                              // every solve walks the cache in the same sequence of directions (reproducible bits)
+  c->fz.on_solve();
   hipLaunchKernelGGL(k_cg_init, dim3(1), dim3(1024), 0, (hipStream_t)stream, b, c->cg_x, c->cg_r, c->cg_p, c->cg_scal, (int)c->d);
   HIPCHK(hipGetLastError());
   return MJX_OK;
@@ -1286,7 +1072,7 @@ int mjx_cg_finish(mjx_ctx* c, const float* b, float* x_out, double* bdotx_out, v
 }  // extern "C"  (internal helpers with C++ types follow)
 namespace {
 // d-float vectors the peer exchange folds into the loop's own kernels (k_reduce_partials4 / k_cg_step_reg<8, W>)
-bool peer_folded(const mjx_ctx* c) { return c->peer.on && c->fused && (c->d & 3) == 0 && c->d <= 8 * 1024; }
+bool peer_folded(const mjx_ctx* c) { return c->peer.on && c->fz.variant && (c->d & 3) == 0 && c->d <= 8 * 1024; }
 // where the 4 doubles that travel with a gradient sit in a slot (mjx_peer_export sizes the slots for it)
 int peer_scal_off(const mjx_ctx* c) { return (int)(((size_t)c->d * sizeof(float) + 15) & ~(size_t)15); }
 
@@ -1299,11 +1085,11 @@ int cg_solve_impl(mjx_ctx* c, float* b, int iters, float damping, double tol, fl
                   void* user, void* stream, const PeerSlots* b_slots, double* s4_out, CgFin fin) {
   hipStream_t st = (hipStream_t)stream;
   if (b_slots) {
-    c->fvp_seq = 0;
+    c->fz.on_solve();
     const int off = peer_scal_off(c);
-#define MJX_INIT_W(W) hipLaunchKernelGGL((k_cg_init_w<W>), dim3(1), dim3(1024), 0, st, *b_slots, off, b, s4_out, c->cg_x, c->cg_r, c->cg_p, c->cg_scal, (int)c->d)
-    if (c->peer.world <= 2) MJX_INIT_W(2); else if (c->peer.world <= 4) MJX_INIT_W(4); else if (c->peer.world <= 8) MJX_INIT_W(8); else MJX_INIT_W(16);
-#undef MJX_INIT_W
+    with_world_width(c->peer.world, [&](auto w) {
+      hipLaunchKernelGGL((k_cg_init_w<decltype(w)::value>), dim3(1), dim3(1024), 0, st, *b_slots, off, b, s4_out, c->cg_x, c->cg_r, c->cg_p, c->cg_scal, (int)c->d);
+    });
     HIPCHK(hipGetLastError());
   } else if (int rc = mjx_cg_init(c, b, stream)) return rc;
   const bool reg = c->d <= 8 * 1024;
@@ -1320,15 +1106,12 @@ int cg_solve_impl(mjx_ctx* c, float* b, int iters, float damping, double tol, fl
       // EVERY rank's buffer and raises its arrival flags, the vector-update kernel waits on the own flags and sums its local
       // slots (rank order): per iteration FVP -> reduction -> step -- exactly the launches of the one-rank loop, no host round trip.
       // (A rank on another route -- empty shard -- runs the same exchange through mjx_comm_allreduce.)
-      const uint32_t seq = ++c->peer.seq;
-      const int par = (int)(seq & 1u);
-      const PeerPush pp = peer_push(c, par, seq);
-      if (int rc = fvp_impl(c, c->cg_p, (float*)peer_slot(c, c->peer.rank, par, c->peer.rank), stream, &pp)) return rc;
-      const PeerSlots ps = peer_slots(c, par, seq);
-#define MJX_STEP_W(W) hipLaunchKernelGGL((k_cg_step_reg<8, W>), dim3(1), dim3(1024), 0, st, (const float*)nullptr, damping, tol, \
-                                         c->cg_x, c->cg_r, c->cg_p, c->cg_scal, (int)c->d, ps, f)
-      if (c->peer.world <= 2) MJX_STEP_W(2); else if (c->peer.world <= 4) MJX_STEP_W(4); else if (c->peer.world <= 8) MJX_STEP_W(8); else MJX_STEP_W(16);
-#undef MJX_STEP_W
+      const PeerRound r = next_round(c);
+      if (int rc = fvp_impl(c, c->cg_p, (float*)r.own, stream, &r.push)) return rc;
+      with_world_width(c->peer.world, [&](auto w) {
+        hipLaunchKernelGGL((k_cg_step_reg<8, decltype(w)::value>), dim3(1), dim3(1024), 0, st, (const float*)nullptr, damping, tol,
+                           c->cg_x, c->cg_r, c->cg_p, c->cg_scal, (int)c->d, r.slots, f);
+      });
       HIPCHK(hipGetLastError());
       fin_done = f.mode != 0;
       continue;
@@ -1366,20 +1149,17 @@ int vpg_and_rank_sums(mjx_ctx* c, float* grad_out, double* s4, bool need_s4_sum,
   *folded = false;
   hipStream_t st = (hipStream_t)stream;
   if (peer_folded(c) && need_s4_sum) {
-    const uint32_t seq = ++c->peer.seq;
-    const int par = (int)(seq & 1u);
-    const PeerPush pp = peer_push(c, par, seq);
+    const PeerRound r = next_round(c);
     const int off = peer_scal_off(c);
-    char* own = peer_slot(c, c->peer.rank, par, c->peer.rank);
     if (c->N_local > 0) {
-      if (int rc = surr_vpg_impl(c, (float*)own, (double*)(own + off), stream, &pp, off)) return rc;
+      if (int rc = surr_vpg_impl(c, (float*)r.own, (double*)(r.own + off), stream, &r.push, off)) return rc;
     } else {                                     // a rank without samples: zeros, through the same exchange
       HIPCHK(hipMemsetAsync(grad_out, 0, c->d * sizeof(float), st));
       HIPCHK(hipMemsetAsync(s4, 0, 4 * sizeof(double), st));
-      hipLaunchKernelGGL(k_peer_push_vs, dim3((unsigned)((c->d + 255) / 256)), dim3(256), 0, st, (const float*)grad_out, (const double*)s4, pp, (int)c->d, off);
+      hipLaunchKernelGGL(k_peer_push_vs, dim3((unsigned)((c->d + 255) / 256)), dim3(256), 0, st, (const float*)grad_out, (const double*)s4, r.push, (int)c->d, off);
       HIPCHK(hipGetLastError());
     }
-    *slots_out = peer_slots(c, par, seq);
+    *slots_out = r.slots;
     *folded = true;
     return MJX_OK;
   }
@@ -1403,12 +1183,10 @@ int vpg_and_rank_sums(mjx_ctx* c, float* grad_out, double* s4, bool need_s4_sum,
 // (one-call updates only: their evaluations may use the old policy's outputs K1 left -- nothing outside the library ran in between)
 int eval_and_rank_sum(mjx_ctx* c, double* res4, void* stream) {
   hipStream_t st = (hipStream_t)stream;
-  if (c->peer.on && c->fused && c->N_local > 0) {
-    const uint32_t seq = ++c->peer.seq;
-    const int par = (int)(seq & 1u);
-    const PeerPush pp = peer_push(c, par, seq);
-    if (int rc = eval_impl(c, (double*)peer_slot(c, c->peer.rank, par, c->peer.rank), stream, &pp, true)) return rc;
-    hipLaunchKernelGGL(k_peer_sum<double>, dim3(1), dim3(256), 0, st, peer_slots(c, par, seq), res4, (int64_t)4);
+  if (c->peer.on && c->fz.variant && c->N_local > 0) {
+    const PeerRound r = next_round(c);
+    if (int rc = eval_impl(c, (double*)r.own, stream, &r.push, true)) return rc;
+    hipLaunchKernelGGL(k_peer_sum<double>, dim3(1), dim3(256), 0, st, r.slots, res4, (int64_t)4);
     HIPCHK(hipGetLastError());
     return MJX_OK;
   }
@@ -1736,8 +1514,7 @@ int mjx_policy_minibatch_adam(mjx_ctx* c, int loss, const float* obs, const floa
     c->mb_cap = B;
   }
   if (!c->mb_grad) HIPCHK(hipMalloc(&c->mb_grad, (size_t)c->d * 4));
-  const float* trn = tr ? tr : c->ident_tr;
-  const float* tro = tr_old ? tr_old : c->ident_tr;
+  const float *trn = trn0, *tro = tro0;
   const int64_t cnt = (loss == 0) ? (int64_t)c->oS : c->d;       // MSE: log_std has no gradient -> untouched (like torch's grad None)
   const int ggrid = (B * (c->n > c->m ? c->n : c->m) + 255) / 256;
   for (int64_t s = 0; s < steps; ++s) {

@@ -49,6 +49,13 @@ def fused_info(eng):
     return [int(x) for x in out]
 
 
+def fused_route(eng, n, m, hid):
+    out = (ctypes.c_int32 * 4)()
+    rc = eng.lib.mjx_fused_route(n, m, (ctypes.c_int * len(hid))(*hid), len(hid), out)
+    assert rc == 0, rc
+    return [int(x) for x in out]
+
+
 def run_case(c):
     import torch
     from mjrl_amd.engine import UpdateEngine
@@ -58,6 +65,10 @@ def run_case(c):
     assert eng.fused, (c["name"], "layer-wise")
     assert (variant, npc) == (c["variant"], c["npc"]), (c["name"], variant, npc)
     assert (raw_dr > 0) == bool(c["raw"]), (c["name"], raw_dr)
+    # the context's instance is the one the table's route names for the shape (MJX_RAW_SLAB=0 is mjx_create's decision alone)
+    route = fused_route(eng, n, m, hid)
+    assert [variant, npc] == route[:2], (c["name"], variant, npc, route)
+    assert raw_dr == (0 if os.environ.get("MJX_RAW_SLAB") == "0" else route[2]), (c["name"], raw_dr, route)
     N = c["N"] if c["N"] > 0 else n_big(grid)
     inp = fused_inputs(n, m, hid, N, c["seed"])
     th, th2, pk = inp["th"], inp["th2"], inp["pk"]

@@ -1,5 +1,5 @@
-"""Every instance of the fused policy kernels (k_fused, csrc/fused_policy.h) that dispatch_fused / launch_fused (csrc/mjx.hip) can
-pick, in every launch arm and at every row edge, against the fp64 oracle (oracle/npg_oracle.py, pinned to the reference by
+"""Every instance of the fused policy kernels (k_fused, csrc/fused_policy.h) in the table of csrc/fused_host.h (MJX_FUSED_INSTANCES;
+FusedWS::dispatch / launch pick among them), in every launch arm and at every row edge, against the fp64 oracle (oracle/npg_oracle.py, pinned to the reference by
 tests/test_oracle_golden.py) -- block by block, row by row, column by column and entry by entry (tests/_lw_check.fine_errors).
 
 The device runs go through tests/_fused_matrix_worker.py in child processes, one per arm, with the arm's switches in the child's
