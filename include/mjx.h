@@ -322,6 +322,10 @@ int mjx_policy_minibatch_adam(mjx_ctx* ctx, int loss, const float* obs, const fl
                               int64_t steps, int B, float* theta, const float* tr, const float* theta_old, const float* tr_old,
                               int old_tracks_new, float* adam_m, float* adam_v, int64_t step0, float lr, float clip,
                               double* loss_trace, void* stream);
+/* What would serve such a call on a context of (n, m, hidden): out2 = {H, bytes of dynamic LDS} of the one-launch trainer
+ * (csrc/policy_fit.h), or {0, 0} = per-step launches (MJX_NO_POLICY_FIT=1, read per call, forces them).  Arithmetic only: no
+ * device work and no runtime call. */
+int mjx_policy_fit_route(int n, int m, const int* hidden, int n_hidden, int B, int loss, int old_tracks_new, int32_t* out2);
 
 /* Host-side gather for rollout ingestion: copies blocks [first, first + count) of a list of
  * per-trajectory arrays -- src[i] is rows(i) x row_bytes, C-contiguous -- to their place in one staging block,
@@ -398,6 +402,11 @@ int mjx_mlp_predict(const float* feat, int64_t N, int d_in, const int* hidden, i
 int mjx_mlp_fit_adam(const float* feat, const float* y, int64_t N, int d_in, const int* hidden, int n_hidden,
                      float* params, float* m, float* v, int64_t step0, const int32_t* perm, int epochs, int batch,
                      float lr, float wd, double* epoch_loss_out, void* stream);
+/* What would serve such a fit, from the same table and the same switches (MJX_MLP_FIT_LAUNCHES, MJX_FIT_WIDE, MJX_FIT_REGMOM,
+ * MJX_FIT_ONEPASS, read per call): out6 = {kind (0 per-step launches, 1 one workgroup in two halves, 2 one workgroup in one pass,
+ * 3 several workgroups), NF1, REGMOM, workgroups, bytes of dynamic LDS, scratch site}.  Arithmetic only: no device work and no
+ * runtime call (tests/test_aux_routes_cpu.py). */
+int mjx_mlp_fit_route(int d_in, const int* hidden, int n_hidden, int batch, int64_t N, int epochs, int32_t* out6);
 
 /* ---- model-based NPG (mjrl/algos/model_accel/) ----------------------------- */
 /* Nets: sizes = [d_in, h..., d_out] (n_sizes entries, at most 9); per member a flat parameter vector in

@@ -69,6 +69,7 @@ PROTOTYPES = {
     "mjx_policy_forward": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "mjx_policy_minibatch_adam": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p,
                                           c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int64, c_float, c_float, c_void_p, c_void_p]),
+    "mjx_policy_fit_route": (c_int, [c_int, c_int, ctypes.POINTER(c_int), c_int, c_int, c_int, c_int, ctypes.POINTER(ctypes.c_int32)]),
     "mjx_host_gather": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int]),
     "mjx_host_gather_f64_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int]),
     "mjx_host_segment_sums": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int]),
@@ -85,6 +86,7 @@ PROTOTYPES = {
     "mjx_mlp_predict": (c_int, [c_void_p, c_int64, c_int, ctypes.POINTER(c_int), c_int, c_void_p, c_void_p, c_void_p]),
     "mjx_mlp_fit_adam": (c_int, [c_void_p, c_void_p, c_int64, c_int, ctypes.POINTER(c_int), c_int, c_void_p, c_void_p, c_void_p,
                                  c_int64, c_void_p, c_int, c_int, c_float, c_float, c_void_p, c_void_p]),
+    "mjx_mlp_fit_route": (c_int, [c_int, ctypes.POINTER(c_int), c_int, c_int, c_int64, c_int, ctypes.POINTER(ctypes.c_int32)]),
     "mjx_dyn_forward": (c_int, [c_void_p, c_int64, c_int64, c_int, ctypes.POINTER(c_int), c_int, c_void_p, c_void_p, c_int, c_int, c_void_p,
                                 c_void_p]),
     "mjx_model_rollout": (c_int, [c_void_p, c_int64, c_int, c_int, ctypes.POINTER(c_int), c_int, c_void_p, c_void_p, c_void_p, c_void_p,

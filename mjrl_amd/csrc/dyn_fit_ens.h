@@ -50,14 +50,6 @@ constexpr size_t DFE_STATIC_LDS = 8 * sizeof(double) + 64 * sizeof(int);
 
 typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));     // four weights of a row (member blocks are 4-byte aligned)
 
-// The shapes k_dyn_fit_ens serves.  Plain arithmetic.
-__host__ inline bool dfe_serves(const DynNet& net, int batch, int target_mode) {
-  if (net.nl != 3 || batch < 1 || batch > DFE_MAXB) return false;
-  if (target_mode != DYN_TGT_PLAIN && target_mode != DYN_TGT_RESIDUAL) return false;
-  for (int l = 1; l <= 2; ++l) if (net.sz[l] % 32 || net.sz[l] < 32 || net.sz[l] > DFE_MAXH) return false;
-  return net.din() <= DFE_MAXIN && net.dout() <= DFE_MAXOUT;
-}
-
 struct DfeLayout {
   int Bp, ST, K0, ZR;
   size_t tiles, xtile;                                      // floats of H1 + H2 + Z3; of X

@@ -352,13 +352,6 @@ __global__ __launch_bounds__(1024) void k_dyn_fit(DynFitArgs a) {
   }
 }
 
-__host__ inline size_t dyn_fit_lds_bytes(const DynNet& net, int B) {
-  int wmax = 0; size_t acts = 0;
-  for (int l = 0; l <= net.nl; ++l) acts += net.sz[l];
-  for (int l = 1; l <= net.nl; ++l) wmax = net.sz[l] > wmax ? net.sz[l] : wmax;
-  return sizeof(float) * (size_t)B * (acts + net.dout() + 2 * (size_t)wmax);
-}
-
 // launch-based route: one thread per output element
 __global__ void k_dl_gather(const float* __restrict__ xn, const float* __restrict__ tg, const int32_t* __restrict__ ix, int B, int din,
                             int dout, float* __restrict__ X, float* __restrict__ T) {

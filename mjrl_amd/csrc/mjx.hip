@@ -65,6 +65,8 @@ int dev_scratch(ScratchSite site, void* stream, size_t bytes, T** out) {
   HIPCHK(mjx::scratch(site, (hipStream_t)stream, bytes, (void**)out));
   return MJX_OK;
 }
+// blocks of `per` elements that cover `elems` > 0, at most `cap` (grid-stride kernels)
+unsigned capped_grid(int64_t elems, int per, int cap) { const int64_t g = (elems + per - 1) / per; return (unsigned)(g < cap ? g : cap); }
 
 // ---- fork guard.  Sampler workers are FORKED from the training process (mjrl/samplers/core.py:189-210: mp.Pool under a parent
 // that holds an mjx_ctx, page-locked staging blocks and libmjx's gather threads).  None of that survives a fork in a usable
@@ -90,6 +92,8 @@ struct ForkGuardInit { ForkGuardInit() { pthread_atfork(nullptr, nullptr, atfork
 }  // namespace
 
 #include "fused_host.h"
+#include "model_host.h"
+#include "fit_host.h"
 
 struct mjx_ctx {
   int device = 0;
@@ -312,26 +316,7 @@ int mjx_bind_policy(mjx_ctx* c, const float* theta_new, const float* theta_old, 
   return bind_policy_impl(c, theta_new, theta_old, tr_new, tr_old, old_is_new, false);
 }
 
-// ---------------------------------------------------------------------------- K6 baselines
-namespace {
-struct FeatTableCache { int kind = -1, n = -1, F = 0; FeatDesc* dev = nullptr; };
-struct FeatTables { FeatTableCache kind[3]; };
-int get_feat_table(int kind, int n, FeatTableCache** out) {
-  static thread_local PerDevice<FeatTables> cache;         // the last table of each kind, per device
-  if (kind < 0 || kind > 2 || n <= 0 || n > 4096) return fail(MJX_ERR_ARG, "bad feature kind / obs dim");
-  FeatTableCache& c = cache.here().kind[kind];
-  if (c.n != n) {
-    std::vector<FeatDesc> t = build_feat_table(kind, n);
-    if (c.dev) hipFree(c.dev);
-    HIPCHK(hipMalloc(&c.dev, t.size() * sizeof(FeatDesc)));
-    HIPCHK(hipMemcpy(c.dev, t.data(), t.size() * sizeof(FeatDesc), hipMemcpyHostToDevice));
-    c.kind = kind; c.n = n; c.F = (int)t.size();
-  }
-  *out = &c;
-  return MJX_OK;
-}
-}  // namespace
-
+// ---------------------------------------------------------------------------- K6 baselines (host side: csrc/fit_host.h)
 int mjx_bl_num_features(int kind, int n) { return (kind < 0 || kind > 2 || n <= 0) ? -1 : bl_num_features(kind, n); }
 
 int mjx_bl_features_f32(const double* obs, const int32_t* tpos, int64_t N, int n, float* out, void* stream) {
@@ -346,51 +331,21 @@ int mjx_bl_gram(int kind, const double* obs, const int32_t* tpos, const double* 
   if (!obs || !tpos || !y || !G || N <= 0) return fail(MJX_ERR_ARG, "bad arguments");
   FeatTableCache* ft;
   if (int rc = get_feat_table(kind, n, &ft)) return rc;
-  const int F = ft->F, FA = F + 1, nbt = (FA + GT - 1) / GT, npairs = nbt * (nbt + 1) / 2;
+  const int F = ft->F, FA = F + 1;
+  const GramRoute r = gram_route(F, n, N, env_flag("MJX_GRAM_FMA", false));
+  const size_t pbytes = (size_t)r.Z * FA * FA * sizeof(double);
   double* part = nullptr;
-  const int T16 = (FA + 15) / 16;
-  const bool no_mfma = env_flag("MJX_GRAM_FMA", false);
-  if (T16 <= GM_TMAX && n <= 24 && !no_mfma) {
-    // fp64 matrix cores: one persistent workgroup per sample range, all features generated once per chunk
-    int Z = (int)((N + 2047) / 2048);
-    if (Z > 512) Z = 512;
-    if (Z < 1) Z = 1;
-    if (int rc = dev_scratch(SITE_GRAM, stream, (size_t)Z * FA * FA * sizeof(double), &part)) return rc;
-    HIPCHK(hipMemsetAsync(part, 0, (size_t)Z * FA * FA * sizeof(double), (hipStream_t)stream));
-    const size_t lds = ((size_t)32 * (n + 7) + (size_t)32 * 16 * (T16 | 1)) * sizeof(double);
-    if (lds > LDS_DEFAULT) return fail(MJX_ERR_UNSUPPORTED, "Gram kernel LDS staging");
-    if (int rc = lds_limit((const void*)k_bl_gram_mfma, lds)) return rc;
-    hipLaunchKernelGGL(k_bl_gram_mfma, dim3(Z), dim3(256), lds, (hipStream_t)stream, ft->dev, F, n, obs, tpos, y, N, part);
-    hipLaunchKernelGGL(k_bl_gram_reduce, dim3(LayerwiseWS::ew_grid((int64_t)FA * FA)), dim3(256), 0, (hipStream_t)stream, (const double*)part, Z, FA, G, 16);
-    HIPCHK(hipGetLastError());
-    return MJX_OK;
-  }
-  if (!no_mfma && n <= 64) {
-    // fp64 matrix cores, 128 x 128 feature blocks: one workgroup per (block pair, sample range)
-    const int nb = (FA + GB_F - 1) / GB_F, nbp = nb * (nb + 1) / 2;
-    int Z = (int)((N + 2047) / 2048);
-    int maxz = (768 + nbp - 1) / nbp;                  // ~3 rounds of workgroups on the chip
-    if (Z > maxz) Z = maxz;
-    if (Z < 1) Z = 1;
-    if (int rc = dev_scratch(SITE_GRAM, stream, (size_t)Z * FA * FA * sizeof(double), &part)) return rc;
-    const size_t lds = (size_t)(32 * (n + 7) + 2 * 32 * GB_FS) * sizeof(double);
-    if (int rc = lds_limit((const void*)k_bl_gram_mfma_blk, lds)) return rc;
-    hipLaunchKernelGGL(k_bl_gram_mfma_blk, dim3(nbp, Z), dim3(256), lds, (hipStream_t)stream, nb, ft->dev, F, n, obs, tpos, y, N, part);
-    hipLaunchKernelGGL(k_bl_gram_reduce, dim3(LayerwiseWS::ew_grid((int64_t)FA * FA)), dim3(256), 0, (hipStream_t)stream, (const double*)part, Z, FA, G, GB_F);
-    HIPCHK(hipGetLastError());
-    return MJX_OK;
-  }
-  int Z = (int)((N + 4095) / 4096);
-  int maxz = (2048 + npairs - 1) / npairs;
-  if (Z > maxz) Z = maxz;
-  if (Z < 1) Z = 1;
-  if (int rc = dev_scratch(SITE_GRAM, stream, (size_t)Z * FA * FA * sizeof(double), &part)) return rc;
-  HIPCHK(hipMemsetAsync(part, 0, (size_t)Z * FA * FA * sizeof(double), (hipStream_t)stream));
-  size_t lds = ((size_t)GKS * n + 2 * (size_t)GKS * (GT + 1)) * sizeof(double);
-  if (lds > LDS_DEFAULT) return fail(MJX_ERR_UNSUPPORTED, "obs dim too large for the Gram kernel's LDS staging");
-  if (int rc = lds_limit((const void*)k_bl_gram, lds)) return rc;
-  hipLaunchKernelGGL(k_bl_gram, dim3(npairs, Z), dim3(256), lds, (hipStream_t)stream, nbt, ft->dev, F, n, obs, tpos, y, N, part);
-  hipLaunchKernelGGL(k_bl_gram_reduce, dim3(LayerwiseWS::ew_grid((int64_t)FA * FA)), dim3(256), 0, (hipStream_t)stream, (const double*)part, Z, FA, G, GT);
+  if (int rc = dev_scratch(SITE_GRAM, stream, pbytes, &part)) return rc;
+  const bool blk = r.arm == GRAM_MFMA_BLK;                 // that arm writes every partial it owns and may take LDS beyond the default
+  if (!blk) HIPCHK(hipMemsetAsync(part, 0, pbytes, (hipStream_t)stream));
+  if (!blk && r.lds > LDS_DEFAULT) return fail(MJX_ERR_UNSUPPORTED, "obs dim too large for the Gram kernel's LDS staging");
+  auto launch = [&](auto kern, dim3 grid, auto... lead) {
+    if (int rc = lds_limit((const void*)kern, r.lds)) return rc;
+    hipLaunchKernelGGL(kern, grid, dim3(256), r.lds, (hipStream_t)stream, lead..., ft->dev, F, n, obs, tpos, y, N, part);
+    return (int)MJX_OK;
+  };
+  if (int rc = r.arm == GRAM_MFMA ? launch(k_bl_gram_mfma, dim3(r.Z)) : launch(blk ? k_bl_gram_mfma_blk : k_bl_gram, dim3(r.gx, r.Z), r.nblk)) return rc;
+  hipLaunchKernelGGL(k_bl_gram_reduce, dim3(LayerwiseWS::ew_grid((int64_t)FA * FA)), dim3(256), 0, (hipStream_t)stream, (const double*)part, r.Z, FA, G, r.blk);
   HIPCHK(hipGetLastError());
   return MJX_OK;
 }
@@ -405,8 +360,7 @@ int mjx_bl_predict(int kind, const double* obs, const int32_t* tpos, int64_t N, 
   size_t lds = (size_t)nth * n * sizeof(double);
   if (lds > LDS_DEFAULT) return fail(MJX_ERR_UNSUPPORTED, "obs dim too large for the predict kernel's LDS staging");
   if (int rc = lds_limit((const void*)k_bl_predict, lds)) return rc;
-  int grid = (int)((N + nth - 1) / nth); if (grid > 8192) grid = 8192;
-  hipLaunchKernelGGL(k_bl_predict, dim3(grid), dim3(nth), lds, (hipStream_t)stream, ft->dev, ft->F, n, obs, tpos, coef, N, out);
+  hipLaunchKernelGGL(k_bl_predict, dim3(capped_grid(N, nth, 8192)), dim3(nth), lds, (hipStream_t)stream, ft->dev, ft->F, n, obs, tpos, coef, N, out);
   HIPCHK(hipGetLastError());
   return MJX_OK;
 }
@@ -446,6 +400,14 @@ int mjx_mlp_predict(const float* feat, int64_t N, int d_in, const int* hidden, i
   return MJX_OK;
 }
 
+int mjx_mlp_fit_route(int d_in, const int* hidden, int n_hidden, int batch, int64_t N, int epochs, int32_t* out6) {
+  if (!out6 || d_in <= 0 || n_hidden < 0 || (n_hidden && !hidden) || batch <= 0 || N <= 0 || epochs < 0) return fail(MJX_ERR_ARG, "bad arguments");
+  for (int i = 0; i < n_hidden; ++i) if (hidden[i] <= 0) return fail(MJX_ERR_ARG, "bad hidden size");
+  const MlpFitRoute r = mlp_fit_route(d_in, hidden, n_hidden, batch, N, epochs, mlp_fit_switches());
+  out6[0] = r.kind; out6[1] = r.nf1; out6[2] = r.regmom; out6[3] = r.G; out6[4] = (int32_t)r.bytes; out6[5] = r.site;
+  return MJX_OK;
+}
+
 int mjx_mlp_fit_adam(const float* feat, const float* y, int64_t N, int d_in, const int* hidden, int n_hidden, float* params,
                      float* m, float* v, int64_t step0, const int32_t* perm, int epochs, int batch, float lr, float wd,
                      double* epoch_loss_out, void* stream) {
@@ -453,60 +415,33 @@ int mjx_mlp_fit_adam(const float* feat, const float* y, int64_t N, int d_in, con
     return fail(MJX_ERR_ARG, "bad arguments");
   hipStream_t st = (hipStream_t)stream;
   HIPCHK(hipMemsetAsync(epoch_loss_out, 0, sizeof(double) * (epochs > 0 ? epochs : 1), st));
-  {
-    // persistent trainers (csrc/mlp_fit.h) for the reference's default baseline shape, 128 x 128 at minibatches of 64: ONE
-    // workgroup while the layout of d_in inputs fits its LDS (d_in <= 55); r05: wider inputs (Ant 111 + 4, Humanoid 376 + 4 =
-    // BASELINE configs[3]) on SEVERAL workgroups of the same trainer -- feature slices of 48, one workgroup (= one CU) per slice,
-    // one grid barrier per 32-sample half (k_mlp_fit<.., MULTI>).  MJX_MLP_FIT_LAUNCHES=1 / MJX_FIT_WIDE=0: the launch route below
-    constexpr int FS = 48, GMAX = 16;
-    const int64_t steps_ = N / batch - 1;
-    const int G = (d_in + FS - 1) / FS;
-    const MlpFitLayout<128> L(d_in, d_in > 31), Lw(FS, true);
-    const MlpFit1pLayout<128> L1(d_in);
-    const bool shape = !env_flag("MJX_MLP_FIT_LAUNCHES", false) && n_hidden == 2 && hidden[0] == 128 && hidden[1] == 128 && batch == 64 &&
-                       steps_ > 0 && epochs > 0;
-    const bool one_wg = shape && d_in <= 63 && L.bytes() <= LDS_MAX;
-    const bool wide = shape && !one_wg && env_flag("MJX_FIT_WIDE", true) && d_in > 48 && G <= GMAX;
-    if (one_wg || wide) {
-      const int64_t P = (int64_t)128 * d_in + 128 + 128 * 128 + 128 + 128 + 1;
-      float* mvws = nullptr;
-      if (int rc = dev_scratch(wide ? SITE_MLP_FIT_WIDE : SITE_MLP_FIT, stream, (size_t)(wide ? G : 1) * P * 2 * sizeof(float), &mvws)) return rc;
-      MlpFitArgs a{feat, y, perm, N, d_in, epochs, steps_, params, m, v, mvws, step0, lr, wd, epoch_loss_out};
-      if (wide) {
-        // the exchange block and the arrival counter: UNCACHED device memory (stores are acknowledged by memory, loads bypass the
-        // per-XCD L2s -- the workgroups of one grid sit on different XCDs), allocated once per thread and device
-        static thread_local PerDevice<char*> xch_of;
-        char*& xch = xch_of.here();
-        const size_t xbytes = (size_t)2 * GMAX * 128 * 32 * sizeof(float);
-        if (!xch) HIPCHK(hipExtMallocWithFlags((void**)&xch, xbytes + 256, hipDeviceMallocUncached));
-        HIPCHK(hipMemsetAsync(xch + xbytes, 0, 256, st));                       // the counter (the exchange block needs no clearing)
-        a.xch = (float*)xch; a.bar = (unsigned*)(xch + xbytes); a.G = G; a.FS = FS;
-        { const char* f = getenv("MJX_FIT_FAULT"); a.fault = (f && !strcmp(f, "straggler")) ? 1 : 0; }      // (tests/test_gpu_lifecycle.py)
-      }
-      // r04: the Adam moments a thread owns stay in its registers for the whole run (REGMOM, mlp_fit.h); MJX_FIT_REGMOM=0: the r03
-      // kernels, which stream them through L2 in every step (same arithmetic, same bits; read per call: the tests compare the two
-      // in one process) ... and up to 23 inputs a step is ONE pass over its 64 rows (k_mlp_fit1p: two accumulator chains, every
-      // weight fragment fetched once, 6 barriers instead of 11); MJX_FIT_ONEPASS=0: the two-halves kernel
-      const bool regmom = env_flag("MJX_FIT_REGMOM", true);
-      const bool onepass = !wide && d_in <= 23 && regmom && env_flag("MJX_FIT_ONEPASS", true) && L1.bytes() <= LDS_MAX;
-      // (d_in, REGMOM, ONEPASS, wide) -> instance, listed in the order the instances have in the code object (that of their
-      // first mention)
-      void (*k)(MlpFitArgs) = nullptr;
-      if (!wide && !regmom)       k = d_in <= 31 ? k_mlp_fit<128, 1, false> : k_mlp_fit<128, 2, false>;
-      else if (!wide && !onepass) k = d_in <= 31 ? k_mlp_fit<128, 1, true> : k_mlp_fit<128, 2, true>;      // (32 <= d_in <= 55: what 160 KB of LDS hold)
-      else if (!wide)             k = k_mlp_fit1p<128>;                                                    // d_in <= 23, REGMOM and ONEPASS
-      else                        k = regmom ? k_mlp_fit<128, 2, true, true> : k_mlp_fit<128, 2, false, true>;   // one 48-feature slice per workgroup
-      const size_t bytes = wide ? Lw.bytes() : onepass ? L1.bytes() : L.bytes();
-      if (int rc = lds_limit((const void*)k, bytes)) return rc;
-      hipLaunchKernelGGL(k, dim3(wide ? G : 1), dim3(256), bytes, st, a);
-      // a barrier wait that timed out (a workgroup without a CU) is recorded in a word of its own; this turns it into NaN epoch
-      // losses AFTER every workgroup has left -- the last writer of epoch_loss no longer decides
-      if (wide) hipLaunchKernelGGL(k_mlp_fit_verdict, dim3(1), dim3(64), 0, st, (const unsigned*)a.bar + 1, epoch_loss_out, epochs);
-      HIPCHK(hipGetLastError());
-      return MJX_OK;
-    }
-  }
   MlpRegressor net; net.init(d_in, hidden, n_hidden);
+  const MlpFitRoute r = mlp_fit_route(d_in, hidden, n_hidden, batch, N, epochs, mlp_fit_switches());
+  if (r.kind != MLPFIT_LAUNCHES) {
+    const bool wide = r.kind == MLPFIT_WIDE;
+    float* mvws = nullptr;
+    if (int rc = dev_scratch((ScratchSite)r.site, stream, (size_t)r.G * net.P * 2 * sizeof(float), &mvws)) return rc;
+    MlpFitArgs a{feat, y, perm, N, d_in, epochs, N / batch - 1, params, m, v, mvws, step0, lr, wd, epoch_loss_out};
+    if (wide) {
+      // the exchange block and the arrival counter: UNCACHED device memory (stores are acknowledged by memory, loads bypass the
+      // per-XCD L2s -- the workgroups of one grid sit on different XCDs), allocated once per thread and device
+      static thread_local PerDevice<char*> xch_of;
+      char*& xch = xch_of.here();
+      const size_t xbytes = (size_t)2 * MLPFIT_GMAX * 128 * 32 * sizeof(float);
+      if (!xch) HIPCHK(hipExtMallocWithFlags((void**)&xch, xbytes + 256, hipDeviceMallocUncached));
+      HIPCHK(hipMemsetAsync(xch + xbytes, 0, 256, st));                       // the counter (the exchange block needs no clearing)
+      a.xch = (float*)xch; a.bar = (unsigned*)(xch + xbytes); a.G = r.G; a.FS = MLPFIT_FS;
+      { const char* f = getenv("MJX_FIT_FAULT"); a.fault = (f && !strcmp(f, "straggler")) ? 1 : 0; }      // (tests/test_gpu_lifecycle.py)
+    }
+    const MlpFitKernel k = mlp_fit_kernel(r);
+    if (int rc = lds_limit((const void*)k, r.bytes)) return rc;
+    hipLaunchKernelGGL(k, dim3(r.G), dim3(256), r.bytes, st, a);
+    // a barrier wait that timed out (a workgroup without a CU) is recorded in a word of its own; this turns it into NaN epoch
+    // losses AFTER every workgroup has left -- the last writer of epoch_loss no longer decides
+    if (wide) hipLaunchKernelGGL(k_mlp_fit_verdict, dim3(1), dim3(64), 0, st, (const unsigned*)a.bar + 1, epoch_loss_out, epochs);
+    HIPCHK(hipGetLastError());
+    return MJX_OK;
+  }
   const int L = net.nL(), bs = batch;
   size_t hsum = 0; for (int i = 0; i < n_hidden; ++i) hsum += hidden[i];
   // scratch: Xb, yb, yhat, d_out, acts (bs x h_l), deltas (bs x h_l), grads (P)
@@ -523,7 +458,7 @@ int mjx_mlp_fit_adam(const float* feat, const float* y, int64_t N, int d_in, con
   float* grads = q;
   const int64_t steps = N / bs - 1;                 // optimize_model.py:24
   int64_t t = step0;
-  const float b1 = 0.9f, b2 = 0.999f, eps = 1e-8f;
+  const float b1 = 0.9f, b2 = 0.999f, eps = 1e-8f;                  // (fp32 betas, in the corrections too)
   for (int ep = 0; ep < epochs; ++ep) {
     for (int64_t mb = 0; mb < steps; ++mb) {
       hipLaunchKernelGGL(k_gather_rows, dim3((bs * d_in + 255) / 256), dim3(256), 0, st, feat, y, perm + (int64_t)ep * N + mb * bs, bs, d_in, Xb, yb);
@@ -551,31 +486,20 @@ int mjx_mlp_fit_adam(const float* feat, const float* y, int64_t N, int d_in, con
           delta = dl[l - 1];
         }
       }
-      ++t;
-      const float bc1 = (float)(1.0 - std::pow((double)b1, (double)t));
-      const float bc2s = (float)std::sqrt(1.0 - std::pow((double)b2, (double)t));
-      hipLaunchKernelGGL(k_adam, dim3((unsigned)((net.P + 255) / 256)), dim3(256), 0, st, params, grads, m, v, net.P, lr, wd, b1, b2, eps, bc1, bc2s);
+      const AdamBias bc = adam_bias(b1, b2, ++t);
+      hipLaunchKernelGGL(k_adam, dim3((unsigned)((net.P + 255) / 256)), dim3(256), 0, st, params, grads, m, v, net.P, lr, wd, b1, b2, eps, bc.bc1, bc.bc2s);
     }
   }
   HIPCHK(lw_status());
   return MJX_OK;
 }
 
-// ---------------------------------------------------------------------------- model-based NPG (csrc/dynamics.h)
-namespace {
-int dyn_net(const int* sizes, int n_sizes, DynNet& net) {
-  if (!sizes || !net.init(sizes, n_sizes)) return fail(MJX_ERR_ARG, "bad layer sizes (2 .. %d entries, all > 0)", DYN_MAXL + 1);
-  return MJX_OK;
-}
-}  // namespace
-
+// ---------------------------------------------------------------------------- model-based NPG (csrc/dynamics.h; host side: csrc/model_host.h)
 int mjx_dyn_forward(const float* x, int64_t x_stride, int64_t rows, int K, const int* sizes, int n_sizes, const float* params,
                     const float* tr, int act, int flags, float* out, void* stream) {
   DynNet net;
   if (int rc = dyn_net(sizes, n_sizes, net)) return rc;
-  if (!x || !params || !tr || !out || rows < 0 || K <= 0 || K > 65535 || (act != DYN_ACT_RELU && act != DYN_ACT_TANH) ||
-      ((flags & DYN_RESIDUAL) && net.dout() > net.din()))
-    return fail(MJX_ERR_ARG, "bad arguments");
+  if (!x || !params || !tr || !out || rows < 0 || !dyn_args_ok(net, K, act, DYN_TGT_PLAIN, flags & DYN_RESIDUAL)) return fail(MJX_ERR_ARG, "bad arguments");
   if (rows == 0) return MJX_OK;
   MJX_DEVICE_ENTRY();
   const size_t bytes = sizeof(float) * 3 * DYN_FT * (size_t)net.maxw;
@@ -593,8 +517,8 @@ int mjx_model_rollout(const float* s0, int64_t N, int H, int K, const int* pol_s
   RolloutArgs a{};
   if (int rc = dyn_net(dyn_sizes, dyn_n_sizes, a.dyn)) return rc;
   const int n = a.dyn.dout(), m = a.dyn.din() - n;
-  if (!s0 || !dyn_params || !dyn_tr || !obs_out || !act_out || N < 0 || H < 0 || K <= 0 || K > 65535 || m <= 0 ||
-      (act != DYN_ACT_RELU && act != DYN_ACT_TANH) || (!a_min) != (!a_max) || (!s_min) != (!s_max))
+  if (!s0 || !dyn_params || !dyn_tr || !obs_out || !act_out || N < 0 || H < 0 || m <= 0 || !dyn_args_ok(a.dyn, K, act) ||
+      (!a_min) != (!a_max) || (!s_min) != (!s_max))
     return fail(MJX_ERR_ARG, "bad arguments");
   if (actions) {
     if (pol_sizes || noise) return fail(MJX_ERR_ARG, "given actions: no policy, no noise");
@@ -604,40 +528,11 @@ int mjx_model_rollout(const float* s0, int64_t N, int H, int K, const int* pol_s
   }
   if (N == 0 || H == 0) return MJX_OK;
   MJX_DEVICE_ENTRY();
-  a.N = N; a.H = H; a.s0 = s0; a.actions = actions; a.pol_P = pol_params; a.pol_tr = pol_tr; a.noise = noise;
-  a.dyn_P = dyn_params; a.dyn_tr = dyn_tr; a.act = act; a.flags = flags;
-  a.a_lo = a_min; a.a_hi = a_max; a.s_lo = s_min; a.s_hi = s_max; a.obs = obs_out; a.act_out = act_out;
-  a.W = a.dyn.maxw > a.pol.maxw ? a.dyn.maxw : a.pol.maxw;
-  const int64_t Ppol = actions ? 0 : a.pol.P + m;
-  const size_t bytes = sizeof(float) * (size_t)(((Ppol + 3) & ~3) + DYN_RT * (n + m) + 4 * DYN_RT * (int64_t)a.W);
-  if (int rc = lds_limit((const void*)k_model_rollout, bytes)) return rc;
-  hipLaunchKernelGGL(k_model_rollout, dim3((unsigned)((N + DYN_RT - 1) / DYN_RT), (unsigned)K), dim3(256), bytes, (hipStream_t)stream, a);
-  HIPCHK(hipGetLastError());
-  return MJX_OK;
+  a.pol_P = pol_params; a.pol_tr = pol_tr; a.noise = noise; a.a_lo = a_min; a.a_hi = a_max; a.s_lo = s_min; a.s_hi = s_max;
+  return launch_model_rollout(a, s0, N, H, K, actions, dyn_params, dyn_tr, act, flags, obs_out, act_out, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------- MPC planning on learned models (csrc/plan.h)
-namespace {
-// The k_plan_rollout instance that serves a net, if one does: exactly two hidden layers, both widths multiples of 32 up to 128,
-// n <= 64, actions within the slots a lane keeps ahead, and an LDS image within LDS_MAX (the kernel has no static LDS, so the
-// image is its whole footprint).  Plain arithmetic: no device work, no runtime call.
-struct PlanShape { int HB = 0, NB = 0; size_t bytes = 0; };
-bool plan_shape(const DynNet& net, int m, PlanShape& ps) {
-  if (net.nl != 3) return false;
-  const int n = net.dout(), h1 = net.sz[1], h2 = net.sz[2];
-  if (h1 % 32 || h2 % 32 || h1 > 128 || h2 > 128 || n > 64 || plan_pad8(m) > PLAN_MAX_M8) return false;
-  ps.HB = (h1 > h2 ? h1 : h2) / 32; ps.NB = (n + 31) / 32;
-  ps.bytes = sizeof(float) * plan_lds_floats(ps.HB, ps.NB, n, m);
-  return ps.bytes <= LDS_MAX;
-}
-typedef void (*PlanKernel)(PlanArgs);
-PlanKernel plan_kernel(int HB, int NB) {
-  static const PlanKernel tab[4][2] = {{k_plan_rollout<1, 1>, k_plan_rollout<1, 2>}, {k_plan_rollout<2, 1>, k_plan_rollout<2, 2>},
-                                       {k_plan_rollout<3, 1>, k_plan_rollout<3, 2>}, {k_plan_rollout<4, 1>, k_plan_rollout<4, 2>}};
-  return tab[HB - 1][NB - 1];
-}
-}  // namespace
-
 int mjx_plan_route(const int* dyn_sizes, int dyn_n_sizes, int act_dim) {
   DynNet net;
   if (int rc = dyn_net(dyn_sizes, dyn_n_sizes, net)) return rc;
@@ -651,8 +546,8 @@ int mjx_plan_rollout(const float* s0, int64_t s0_stride, int64_t N, int H, int K
   DynNet net;
   if (int rc = dyn_net(dyn_sizes, dyn_n_sizes, net)) return rc;
   const int n = net.dout(), m = net.din() - n;
-  if (!s0 || !actions || !dyn_params || !dyn_tr || !obs_out || N < 0 || H < 0 || K <= 0 || K > 65535 || m <= 0 ||
-      (s0_stride != 0 && s0_stride != n) || (act != DYN_ACT_RELU && act != DYN_ACT_TANH))
+  if (!s0 || !actions || !dyn_params || !dyn_tr || !obs_out || N < 0 || H < 0 || m <= 0 || (s0_stride != 0 && s0_stride != n) ||
+      !dyn_args_ok(net, K, act))
     return fail(MJX_ERR_ARG, "bad arguments");
   if (N == 0 || H == 0) return MJX_OK;
   MJX_DEVICE_ENTRY();
@@ -675,18 +570,12 @@ int mjx_plan_rollout(const float* s0, int64_t s0_stride, int64_t N, int H, int K
   const size_t act_floats = (size_t)K * N * H * m, s0_floats = s0_stride ? 0 : (size_t)N * n;
   if (int rc = dev_scratch(SITE_PLAN_ROLLOUT, stream, (act_floats + s0_floats) * sizeof(float), &scr)) return rc;
   if (!s0_stride) {
-    const int64_t tot = N * n;
-    hipLaunchKernelGGL(k_plan_tile_s0, dim3((unsigned)((tot + 255) / 256 < 1024 ? (tot + 255) / 256 : 1024)), dim3(256), 0, st, s0, N, n, scr + act_floats);
+    hipLaunchKernelGGL(k_plan_tile_s0, dim3(capped_grid(N * n, 256, 1024)), dim3(256), 0, st, s0, N, n, scr + act_floats);
     s0 = scr + act_floats;
   }
   RolloutArgs a{};
-  a.dyn = net; a.N = N; a.H = H; a.s0 = s0; a.actions = actions; a.dyn_P = dyn_params; a.dyn_tr = dyn_tr; a.act = act; a.flags = flags;
-  a.obs = obs_out; a.act_out = scr; a.W = net.maxw;
-  const size_t bytes = sizeof(float) * (size_t)(DYN_RT * (n + m) + 4 * DYN_RT * (int64_t)a.W);
-  if (int rc = lds_limit((const void*)k_model_rollout, bytes)) return rc;
-  hipLaunchKernelGGL(k_model_rollout, dim3((unsigned)((N + DYN_RT - 1) / DYN_RT), (unsigned)K), dim3(256), bytes, st, a);
-  HIPCHK(hipGetLastError());
-  return MJX_OK;
+  a.dyn = net;
+  return launch_model_rollout(a, s0, N, H, K, actions, dyn_params, dyn_tr, act, flags, obs_out, scr, st);
 }
 
 int mjx_plan_score(const float* obs, const double* rewards, const double* actions, int K, int64_t N, int H, int n, int m, double kappa,
@@ -721,8 +610,7 @@ int mjx_dyn_fit_adam(const float* x, const float* y, int64_t N, const int* sizes
   if (int rc = dyn_net(sizes, n_sizes, net)) return rc;
   const int din = net.din(), dout = net.dout();
   if (!x || !y || !in_tr || !out_tr || !params || !m || !v || (steps > 0 && (!idx || !loss_out)) || N <= 0 || batch <= 0 || batch > N ||
-      steps < 0 || step0 < 0 || target_mode < DYN_TGT_AFFINE || target_mode > DYN_TGT_RESIDUAL || (act != DYN_ACT_RELU && act != DYN_ACT_TANH) ||
-      (target_mode == DYN_TGT_RESIDUAL && dout > din))
+      steps < 0 || step0 < 0 || !dyn_args_ok(net, 1, act, target_mode))
     return fail(MJX_ERR_ARG, "bad arguments");
   if (steps == 0) return MJX_OK;
   MJX_DEVICE_ENTRY();
@@ -734,20 +622,10 @@ int mjx_dyn_fit_adam(const float* x, const float* y, int64_t N, const int* sizes
   float* xn = nullptr;
   if (int rc = dev_scratch(SITE_DYN_FIT, stream, (prep + mb) * sizeof(float), &xn)) return rc;
   float* tg = xn + (size_t)N * din;
-  {
-    const int64_t tot = N * (din > dout ? din : dout);
-    const unsigned grid = (unsigned)((tot + 255) / 256 < 4096 ? (tot + 255) / 256 : 4096);
-    hipLaunchKernelGGL(k_dyn_prep, dim3(grid), dim3(256), 0, st, x, y, N, din, dout, in_tr, out_tr, target_mode, xn, tg);
-  }
+  launch_dyn_prep(x, y, N, din, dout, in_tr, out_tr, target_mode, xn, tg, st);
   const float* oaff = target_mode == DYN_TGT_AFFINE ? out_tr : nullptr;
-  // persistent single-launch trainer for hidden widths <= 128 and minibatch <= 64 whose activations fit in LDS beside the
-  // kernel's static LDS (its reduction block: 128 B); MJX_DYN_FIT_LAUNCHES=1 forces the launch route (read per call: the tests
-  // compare the two routes in one process)
-  const bool force = env_flag("MJX_DYN_FIT_LAUNCHES", false);
-  bool narrow = true;
-  for (int l = 1; l < net.nl; ++l) narrow = narrow && net.sz[l] <= 128;
   const size_t fbytes = dyn_fit_lds_bytes(net, batch);
-  if (!force && narrow && batch <= 64 && lds_fits((const void*)k_dyn_fit, fbytes)) {
+  if (dyn_fit_shape(net, batch, env_flag("MJX_DYN_FIT_LAUNCHES", false)) && dyn_fit_persistent(fbytes, static_lds((const void*)k_dyn_fit))) {
     if (int rc = lds_limit((const void*)k_dyn_fit, fbytes)) return rc;
     DynFitArgs a{net, xn, tg, idx, steps, batch, params, m, v, step0, lr, wd, act, oaff, loss_out};
     hipLaunchKernelGGL(k_dyn_fit, dim3(1), dim3(1024), fbytes, st, a);
@@ -759,7 +637,7 @@ int mjx_dyn_fit_adam(const float* x, const float* y, int64_t N, const int* sizes
   for (int l = 0; l <= net.nl; ++l) { A[l] = q; q += (size_t)batch * net.sz[l]; }
   float* T = q; q += (size_t)batch * dout;
   float* D[2] = {q, q + (size_t)batch * wmax};
-  auto blocks = [](int64_t e) { return dim3((unsigned)((e + 255) / 256 < 2048 ? (e + 255) / 256 : 2048)); };
+  auto blocks = [](int64_t e) { return dim3(capped_grid(e, 256, 2048)); };
   for (int64_t s = 0; s < steps; ++s) {
     hipLaunchKernelGGL(k_dl_gather, blocks((int64_t)batch * (din + dout)), dim3(256), 0, st, xn, tg, idx + s * batch, batch, din, dout, A[0], T);
     for (int l = 0; l < net.nl; ++l)
@@ -795,9 +673,8 @@ int mjx_dyn_fit_ensemble(const float* x, int64_t x_stride, const float* y, int64
   DynNet net;
   if (int rc = dyn_net(sizes, n_sizes, net)) return rc;
   const int din = net.din(), dout = net.dout();
-  if (!x || !y || !in_tr || !out_tr || !params || !m || !v || !step0 || (steps > 0 && (!idx || !loss_out)) || N <= 0 || K <= 0 || K > 65535 ||
-      x_stride < 0 || y_stride < 0 || batch <= 0 || batch > N || steps < 0 || target_mode < DYN_TGT_AFFINE || target_mode > DYN_TGT_RESIDUAL ||
-      (act != DYN_ACT_RELU && act != DYN_ACT_TANH) || (target_mode == DYN_TGT_RESIDUAL && dout > din))
+  if (!x || !y || !in_tr || !out_tr || !params || !m || !v || !step0 || (steps > 0 && (!idx || !loss_out)) || N <= 0 ||
+      x_stride < 0 || y_stride < 0 || batch <= 0 || batch > N || steps < 0 || !dyn_args_ok(net, K, act, target_mode))
     return fail(MJX_ERR_ARG, "bad arguments");
   for (int k = 0; k < K; ++k) if (step0[k] < 0) return fail(MJX_ERR_ARG, "bad arguments");
   // (read per call: the tests and tools/bench_dyn_fit.py compare the two routes in one process)
@@ -806,9 +683,9 @@ int mjx_dyn_fit_ensemble(const float* x, int64_t x_stride, const float* y, int64
   if (steps == 0) return MJX_OK;
   if (route == 0) {                                        // member by member on the routes of mjx_dyn_fit_adam
     for (int k = 0; k < K; ++k)
-      if (int rc = mjx_dyn_fit_adam(x + k * x_stride, y + k * y_stride, N, sizes, n_sizes, in_tr + (int64_t)k * 2 * din, out_tr + (int64_t)k * 2 * dout,
-                                    target_mode, act, params + k * net.P, m + k * net.P, v + k * net.P, step0[k], idx + (int64_t)k * steps * batch,
-                                    steps, batch, lr, wd, loss_out + (int64_t)k * steps, stream))
+      if (int rc = mjx_dyn_fit_adam(x + k * x_stride, y + k * y_stride, N, sizes, n_sizes, in_tr + (int64_t)k * 2 * din, out_tr + (int64_t)k * 2 * dout, target_mode, act, params + k * net.P,
+                                    m + k * net.P, v + k * net.P, step0[k], idx + (int64_t)k * steps * batch, steps, batch, lr, wd,
+                                    loss_out + (int64_t)k * steps, stream))
         return rc;
     return MJX_OK;
   }
@@ -821,13 +698,9 @@ int mjx_dyn_fit_ensemble(const float* x, int64_t x_stride, const float* y, int64
   if (int rc = dev_scratch(SITE_DYN_FIT_ENS, stream, ((size_t)K * (size_t)N * (din + dout) + 4 + (size_t)K * xt) * sizeof(float), &scr)) return rc;
   float* xn = scr; float* tg = xn + (size_t)K * N * din;
   float* xscr = xt ? scr + (((size_t)K * N * (din + dout) + 3) & ~(size_t)3) : nullptr;
-  {
-    const int64_t tot = N * (din > dout ? din : dout);
-    const unsigned grid = (unsigned)((tot + 255) / 256 < 4096 ? (tot + 255) / 256 : 4096);
-    for (int k = 0; k < K; ++k)
-      hipLaunchKernelGGL(k_dyn_prep, dim3(grid), dim3(256), 0, st, x + k * x_stride, y + k * y_stride, N, din, dout, in_tr + (int64_t)k * 2 * din,
-                         out_tr + (int64_t)k * 2 * dout, target_mode, xn + (size_t)k * N * din, tg + (size_t)k * N * dout);
-  }
+  for (int k = 0; k < K; ++k)
+    launch_dyn_prep(x + k * x_stride, y + k * y_stride, N, din, dout, in_tr + (int64_t)k * 2 * din, out_tr + (int64_t)k * 2 * dout, target_mode,
+                    xn + (size_t)k * N * din, tg + (size_t)k * N * dout, st);
   if (int rc = lds_limit((const void*)k_dyn_fit_ens, L.lds_bytes())) return rc;
   DynFitEnsArgs a{};
   a.din = din; a.h1 = net.sz[1]; a.h2 = net.sz[2]; a.dout = dout; a.B = batch; a.act = act;
@@ -1460,8 +1333,7 @@ int mjx_sum_stats(const double* x, int64_t N, double shift, double* stats_out, v
 int mjx_whiten_cast(const double* adv, int64_t N, double mean, double std, double eps, float* out32, void* stream) {
   if (!adv || !out32 || N < 0) return fail(MJX_ERR_ARG, "bad arguments");
   if (N == 0) return MJX_OK;
-  int grid = (int)((N + 255) / 256); if (grid > 4096) grid = 4096;
-  hipLaunchKernelGGL(k_whiten_cast, dim3(grid), dim3(256), 0, (hipStream_t)stream, adv, N, mean, std + eps, out32);
+  hipLaunchKernelGGL(k_whiten_cast, dim3(capped_grid(N, 256, 4096)), dim3(256), 0, (hipStream_t)stream, adv, N, mean, std + eps, out32);
   HIPCHK(hipGetLastError());
   return MJX_OK;
 }
@@ -1477,6 +1349,14 @@ int mjx_policy_forward(mjx_ctx* c, const float* obs, int64_t N, const float* the
   return MJX_OK;
 }
 
+int mjx_policy_fit_route(int n, int m, const int* hidden, int n_hidden, int B, int loss, int old_tracks_new, int32_t* out2) {
+  if (!out2 || n <= 0 || m <= 0 || n_hidden < 0 || (n_hidden && !hidden) || B <= 0 || loss < 0 || loss > 2) return fail(MJX_ERR_ARG, "bad arguments");
+  for (int i = 0; i < n_hidden; ++i) if (hidden[i] <= 0) return fail(MJX_ERR_ARG, "bad hidden size");
+  const PolicyFitRoute r = policy_fit_route(n, m, std::vector<int>(hidden, hidden + n_hidden), B, loss, old_tracks_new, env_flag("MJX_NO_POLICY_FIT", false));
+  out2[0] = r.H; out2[1] = (int32_t)r.bytes;
+  return MJX_OK;
+}
+
 int mjx_policy_minibatch_adam(mjx_ctx* c, int loss, const float* obs, const float* act, const float* adv, const int32_t* idx,
                               int64_t steps, int B, float* theta, const float* tr, const float* theta_old, const float* tr_old,
                               int old_tracks_new, float* adam_m, float* adam_v, int64_t step0, float lr, float clip,
@@ -1489,22 +1369,15 @@ int mjx_policy_minibatch_adam(mjx_ctx* c, int loss, const float* obs, const floa
   HIPCHK(hipSetDevice(c->device));
   const float* trn0 = tr ? tr : c->ident_tr;
   const float* tro0 = tr_old ? tr_old : c->ident_tr;
-  // small two-layer nets, minibatches of up to 64 rows: the whole chain of steps in ONE launch (policy_fit.h)
-  const bool no_fit = env_flag("MJX_NO_POLICY_FIT", false);      // read per call: the tests run both paths in one process
-  if (!no_fit && c->hidden.size() == 2 && c->hidden[0] == c->hidden[1] && (c->hidden[0] == 64 || c->hidden[0] == 32) &&
-      B % 4 == 0 && B >= 8 && B <= 64 && c->n <= c->hidden[0] && c->n <= 63 && c->m <= 16) {
-    const bool old_net = (loss == 2) && !old_tracks_new;
-    const int H = c->hidden[0];
-    const size_t bytes = 4 * (H == 64 ? PolicyFitLayout<64>(c->n, c->m).lds_floats(B, old_net) : PolicyFitLayout<32>(c->n, c->m).lds_floats(B, old_net));
-    if (bytes <= LDS_MAX) {
-      PolicyFitArgs a{obs, act, adv, idx, steps, B, c->n, c->m, theta, theta_old, trn0, tro0, loss, old_tracks_new, adam_m, adam_v,
-                      step0, lr, clip, loss_trace, (int)(bytes / 4)};
-      void (*k)(PolicyFitArgs) = (H == 64) ? k_policy_fit<64> : k_policy_fit<32>;
-      if (int rc = lds_limit((const void*)k, bytes)) return rc;
-      hipLaunchKernelGGL(k, dim3(1), dim3(PFIT_THREADS), bytes, st, a);
-      HIPCHK(hipGetLastError());
-      return MJX_OK;
-    }
+  const PolicyFitRoute r = policy_fit_route(c->n, c->m, c->hidden, B, loss, old_tracks_new, env_flag("MJX_NO_POLICY_FIT", false));   // (read per call)
+  if (r.H) {
+    PolicyFitArgs a{obs, act, adv, idx, steps, B, c->n, c->m, theta, theta_old, trn0, tro0, loss, old_tracks_new, adam_m, adam_v,
+                    step0, lr, clip, loss_trace, (int)(r.bytes / 4)};
+    void (*k)(PolicyFitArgs) = (r.H == 64) ? k_policy_fit<64> : k_policy_fit<32>;
+    if (int rc = lds_limit((const void*)k, r.bytes)) return rc;
+    hipLaunchKernelGGL(k, dim3(1), dim3(PFIT_THREADS), r.bytes, st, a);
+    HIPCHK(hipGetLastError());
+    return MJX_OK;
   }
   LayerwiseWS& w = c->lwmb;
   if (w.cap < B) { if (int rc = w.reserve(B)) return fail(rc, "minibatch workspace allocation failed"); }
@@ -1516,9 +1389,9 @@ int mjx_policy_minibatch_adam(mjx_ctx* c, int loss, const float* obs, const floa
   if (!c->mb_grad) HIPCHK(hipMalloc(&c->mb_grad, (size_t)c->d * 4));
   const float *trn = trn0, *tro = tro0;
   const int64_t cnt = (loss == 0) ? (int64_t)c->oS : c->d;       // MSE: log_std has no gradient -> untouched (like torch's grad None)
-  const int ggrid = (B * (c->n > c->m ? c->n : c->m) + 255) / 256;
+  const unsigned ggrid = capped_grid(B * (c->n > c->m ? c->n : c->m), 256, 1024);
   for (int64_t s = 0; s < steps; ++s) {
-    hipLaunchKernelGGL(k_gather_minibatch, dim3(ggrid < 1 ? 1 : (ggrid > 1024 ? 1024 : ggrid)), dim3(256), 0, st, obs, act,
+    hipLaunchKernelGGL(k_gather_minibatch, dim3(ggrid), dim3(256), 0, st, obs, act,
                        (loss == 2) ? adv : (const float*)nullptr, idx + s * B, B, c->n, c->m, c->mb_x, c->mb_a, c->mb_adv);
     const bool old_fwd = (loss == 2) && !old_tracks_new;
     if (old_fwd) w.forward(theta_old, tro, c->mb_x, B, w.T, w.mu2, st);          // old policy on the minibatch (activations are scratch)
@@ -1527,10 +1400,9 @@ int mjx_policy_minibatch_adam(mjx_ctx* c, int loss, const float* obs, const floa
                        c->mb_adv, B, c->m, theta + c->oS, (loss == 2) ? theta_old + c->oS : (const float*)nullptr, trn + 2 * c->n + c->m,
                        clip, w.d3, c->mb_grad + c->oS, loss_trace ? loss_trace + s : (double*)nullptr);
     if (int rc = w.backward(theta, B, c->mb_grad, st)) return fail(MJX_ERR_STATE, "minibatch backward failed (%d)", rc);
-    const double t = (double)(step0 + s + 1);
-    const float bc1 = (float)(1.0 - std::pow(0.9, t)), bc2s = (float)std::sqrt(1.0 - std::pow(0.999, t));
+    const AdamBias bc = adam_bias(0.9, 0.999, step0 + s + 1);
     hipLaunchKernelGGL(k_adam, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, theta, c->mb_grad, adam_m, adam_v, cnt, lr, 0.f,
-                       0.9f, 0.999f, 1e-8f, bc1, bc2s);
+                       0.9f, 0.999f, 1e-8f, bc.bc1, bc.bc2s);
   }
   HIPCHK(lw_status());
   return MJX_OK;
@@ -1558,8 +1430,7 @@ __global__ void k_pull_f64(const double* __restrict__ host, int64_t n, double* _
 }
 inline int mjx_hi_pull_f64(const double* host, int64_t n, double* raw, float* o32, void* stream) {
   if (n <= 0) return MJX_OK;
-  int grid = (int)((n + 255) / 256); if (grid > 2048) grid = 2048;
-  hipLaunchKernelGGL(k_pull_f64, dim3(grid), dim3(256), 0, (hipStream_t)stream, host, n, raw, o32);
+  hipLaunchKernelGGL(k_pull_f64, dim3(capped_grid(n, 256, 2048)), dim3(256), 0, (hipStream_t)stream, host, n, raw, o32);
   HIPCHK(hipGetLastError());
   return MJX_OK;
 }
@@ -1575,8 +1446,7 @@ extern "C" {
 int mjx_cast_f64_f32(const double* x, int64_t count, float* out32, void* stream) {
   if (!x || !out32 || count < 0) return fail(MJX_ERR_ARG, "bad arguments");
   if (count == 0) return MJX_OK;
-  int grid = (int)((count + 255) / 256); if (grid > 8192) grid = 8192;
-  hipLaunchKernelGGL(k_cast_f64_f32, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, count, out32);
+  hipLaunchKernelGGL(k_cast_f64_f32, dim3(capped_grid(count, 256, 8192)), dim3(256), 0, (hipStream_t)stream, x, count, out32);
   HIPCHK(hipGetLastError());
   return MJX_OK;
 }

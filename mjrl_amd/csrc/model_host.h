@@ -1,0 +1,74 @@
+// model_host.h -- host side of the learned-model kernels (dynamics.h, dyn_fit_ens.h, plan.h): their shared argument check, their routes as
+// plain arithmetic, and the launches more than one entry makes.  Included by mjx.hip after fail / HIPCHK / lds_limit / capped_grid.
+#pragma once
+namespace mjx {
+
+inline int dyn_net(const int* sizes, int n_sizes, DynNet& net) {
+  if (!sizes || !net.init(sizes, n_sizes)) return fail(MJX_ERR_ARG, "bad layer sizes (2 .. %d entries, all > 0)", DYN_MAXL + 1);
+  return MJX_OK;
+}
+// K members on gridDim.y (1: a single net), a known activation and target mode, and d_out <= d_in wherever the output is added to the input
+inline bool dyn_args_ok(const DynNet& net, int K, int act, int target_mode = DYN_TGT_PLAIN, bool residual = false) {
+  return K > 0 && K <= 65535 && (act == DYN_ACT_RELU || act == DYN_ACT_TANH) && target_mode >= DYN_TGT_AFFINE && target_mode <= DYN_TGT_RESIDUAL &&
+         !((residual || target_mode == DYN_TGT_RESIDUAL) && net.dout() > net.din());
+}
+inline void launch_dyn_prep(const float* x, const float* y, int64_t N, int din, int dout, const float* in_tr, const float* out_tr,
+                            int target_mode, float* xn, float* tg, hipStream_t st) {
+  hipLaunchKernelGGL(k_dyn_prep, dim3(capped_grid(N * (din > dout ? din : dout), 256, 4096)), dim3(256), 0, st, x, y, N, din, dout, in_tr,
+                     out_tr, target_mode, xn, tg);
+}
+// k_model_rollout on K x ceil(N / DYN_RT) workgroups.  The caller has set a.dyn and, where a policy acts, a.pol with its
+// parameters, transform, noise and clamps; `actions` given means no policy (a.pol stays empty).
+inline int launch_model_rollout(RolloutArgs a, const float* s0, int64_t N, int H, int K, const float* actions, const float* dyn_params,
+                                const float* dyn_tr, int act, int flags, float* obs_out, float* act_out, hipStream_t st) {
+  const int n = a.dyn.dout(), m = a.dyn.din() - n;
+  a.N = N; a.H = H; a.s0 = s0; a.actions = actions; a.dyn_P = dyn_params; a.dyn_tr = dyn_tr; a.act = act; a.flags = flags; a.obs = obs_out; a.act_out = act_out;
+  a.W = a.dyn.maxw > a.pol.maxw ? a.dyn.maxw : a.pol.maxw;
+  const int64_t Ppol = actions ? 0 : a.pol.P + m;
+  const size_t bytes = sizeof(float) * (size_t)(((Ppol + 3) & ~3) + DYN_RT * (n + m) + 4 * DYN_RT * (int64_t)a.W);
+  if (int rc = lds_limit((const void*)k_model_rollout, bytes)) return rc;
+  hipLaunchKernelGGL(k_model_rollout, dim3((unsigned)((N + DYN_RT - 1) / DYN_RT), (unsigned)K), dim3(256), bytes, st, a);
+  HIPCHK(hipGetLastError());
+  return MJX_OK;
+}
+
+// ---- plan rollout.  The k_plan_rollout instance that serves a net, if one does: exactly two hidden layers, both widths multiples
+// of 32 up to 128, n <= 64, actions within the slots a lane keeps ahead, and an LDS image within LDS_MAX (the kernel has no static
+// LDS, so the image is its whole footprint).  MJX_PLAN_MFMA=0 (read per call by mjx_plan_rollout): the generic route.
+struct PlanShape { int HB = 0, NB = 0; size_t bytes = 0; };
+inline bool plan_shape(const DynNet& net, int m, PlanShape& ps) {
+  if (net.nl != 3) return false;
+  const int n = net.dout(), h1 = net.sz[1], h2 = net.sz[2];
+  if (h1 % 32 || h2 % 32 || h1 > 128 || h2 > 128 || n > 64 || plan_pad8(m) > PLAN_MAX_M8) return false;
+  ps.HB = (h1 > h2 ? h1 : h2) / 32; ps.NB = (n + 31) / 32;
+  ps.bytes = sizeof(float) * plan_lds_floats(ps.HB, ps.NB, n, m);
+  return ps.bytes <= LDS_MAX;
+}
+typedef void (*PlanKernel)(PlanArgs);
+inline PlanKernel plan_kernel(int HB, int NB) {
+  static const PlanKernel tab[4][2] = {{k_plan_rollout<1, 1>, k_plan_rollout<1, 2>}, {k_plan_rollout<2, 1>, k_plan_rollout<2, 2>},
+                                       {k_plan_rollout<3, 1>, k_plan_rollout<3, 2>}, {k_plan_rollout<4, 1>, k_plan_rollout<4, 2>}};
+  return tab[HB - 1][NB - 1];
+}
+
+// ---- dynamics fit.  k_dyn_fit, the persistent trainer, serves hidden widths <= 128 at minibatches <= 64 (shape) whose activations fit in LDS beside
+// its static LDS (128 B; asked of the runtime only where the shape leaves the question open); MJX_DYN_FIT_LAUNCHES=1, read per call: the launch route.
+inline size_t dyn_fit_lds_bytes(const DynNet& net, int B) {
+  int wmax = 0; size_t acts = 0;
+  for (int l = 0; l <= net.nl; ++l) acts += net.sz[l];
+  for (int l = 1; l <= net.nl; ++l) wmax = net.sz[l] > wmax ? net.sz[l] : wmax;
+  return sizeof(float) * (size_t)B * (acts + net.dout() + 2 * (size_t)wmax);
+}
+inline bool dyn_fit_shape(const DynNet& net, int batch, bool force_launches) {
+  for (int l = 1; l < net.nl; ++l) if (net.sz[l] > 128) return false;
+  return !force_launches && batch <= 64;
+}
+inline bool dyn_fit_persistent(size_t bytes, size_t static_bytes) { return static_bytes + bytes <= LDS_MAX; }
+// The shapes k_dyn_fit_ens serves (MJX_DYN_FIT_ENS=0, read per call: none).  Plain arithmetic.
+inline bool dfe_serves(const DynNet& net, int batch, int target_mode) {
+  if (net.nl != 3 || batch < 1 || batch > DFE_MAXB) return false;
+  if (target_mode != DYN_TGT_PLAIN && target_mode != DYN_TGT_RESIDUAL) return false;
+  for (int l = 1; l <= 2; ++l) if (net.sz[l] % 32 || net.sz[l] < 32 || net.sz[l] > DFE_MAXH) return false;
+  return net.din() <= DFE_MAXIN && net.dout() <= DFE_MAXOUT;
+}
+}  // namespace mjx
