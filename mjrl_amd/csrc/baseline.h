@@ -382,13 +382,14 @@ __global__ void k_mse_grad(const float* __restrict__ yhat, const float* __restri
   if (threadIdx.x == 0) loss_acc[0] += l / (double)bs;
 }
 
-// torch.optim.Adam (non-amsgrad, L2 weight decay folded into the gradient), fp32 state
+// torch.optim.Adam (non-amsgrad, L2 weight decay folded into the gradient), fp32 state.  c1 = 1 - beta1, c2 = 1 - beta2 as the caller
+// forms them (vecops.h: ADAM_C1 / ADAM_C2 are torch's), bc1 / bc2_sqrt: adam_bias of the betas the caller corrects with
 __global__ void k_adam(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
-                       int64_t cnt, float lr, float wd, float b1, float b2, float eps, float bc1, float bc2_sqrt) {
+                       int64_t cnt, float lr, float wd, float c1, float b2, float c2, float eps, float bc1, float bc2_sqrt) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < cnt; i += (int64_t)gridDim.x * blockDim.x) {
     float gi = g[i] + wd * p[i];
-    float mi = m[i] + (gi - m[i]) * (1.0f - b1);
-    float vi = v[i] * b2 + gi * gi * (1.0f - b2);
+    float mi = m[i] + (gi - m[i]) * c1;
+    float vi = v[i] * b2 + gi * gi * c2;
     m[i] = mi; v[i] = vi;
     float denom = sqrtf(vi) / bc2_sqrt + eps;
     p[i] = p[i] - (lr / bc1) * (mi / denom);

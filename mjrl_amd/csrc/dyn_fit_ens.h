@@ -40,6 +40,7 @@
 #include "dynamics.h"
 #include "fused_policy.h"
 #include "launch_state.h"
+#include "vecops.h"
 
 namespace mjx {
 
@@ -79,13 +80,13 @@ struct DynFitEnsArgs {
 // torch.optim.Adam as dyn_adam, with the two divisions as v_rcp_f32 + one Newton step (mlp_fit.h: <= 1 ulp from IEEE)
 // and 1 - beta rounded once
 __device__ __forceinline__ void dfe_adam_math(float& p, float& m, float& v, float g, float lr_bc1, float inv_bc2s, float wd) {
-  // 1 - beta as torch hands it to its fp32 kernels: formed in double, then cast (0.1f, 0.001f).  `1.0f - 0.999f` is
-  // 0.0009999871, 1.3e-5 low: a bias of the same sign in every second moment, which alone moved a weight of the
-  // [13, 256, 256, 11] batch-16 test case by 2e-2 lr from the fp64 chain in ten steps.
+  // 1 - beta as torch hands it to its fp32 kernels (vecops.h: 0.1f, 0.001f).  `1.0f - 0.999f` is 0.0009999871, 1.3e-5 low: a
+  // bias of the same sign in every second moment, which alone moved a weight of the [13, 256, 256, 11] batch-16 test case by
+  // 2e-2 lr from the fp64 chain in ten steps.
   const float gi = g + wd * p;
-  m = m + (gi - m) * 0.1f;
-  v = v * 0.999f + gi * gi * 0.001f;
-  const float denom = fmaf(__builtin_amdgcn_sqrtf(v), inv_bc2s, 1e-8f);
+  m = m + (gi - m) * ADAM_C1;
+  v = v * ADAM_B2 + gi * gi * ADAM_C2;
+  const float denom = fmaf(__builtin_amdgcn_sqrtf(v), inv_bc2s, ADAM_EPS);
   float r = __builtin_amdgcn_rcpf(denom);
   r = r * fmaf(-denom, r, 2.0f);
   p = fmaf(-lr_bc1 * m, r, p);

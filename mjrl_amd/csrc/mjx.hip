@@ -458,7 +458,9 @@ int mjx_mlp_fit_adam(const float* feat, const float* y, int64_t N, int d_in, con
   float* grads = q;
   const int64_t steps = N / bs - 1;                 // optimize_model.py:24
   int64_t t = step0;
-  const float b1 = 0.9f, b2 = 0.999f, eps = 1e-8f;                  // (fp32 betas, in the corrections too)
+  // fp32 betas, in 1 - beta (1.0f - 0.999f is 1.3e-5 below torch's 0.001f) and in the corrections too: the arithmetic of the persistent
+  // trainers (mlp_fit.h), self-consistent -- the steps stay within 1e-6 lr of torch's, v itself is 1.3e-5 low (tests/test_gpu_fit_matrix.py)
+  const float b1 = 0.9f, b2 = 0.999f, eps = 1e-8f;
   for (int ep = 0; ep < epochs; ++ep) {
     for (int64_t mb = 0; mb < steps; ++mb) {
       hipLaunchKernelGGL(k_gather_rows, dim3((bs * d_in + 255) / 256), dim3(256), 0, st, feat, y, perm + (int64_t)ep * N + mb * bs, bs, d_in, Xb, yb);
@@ -487,7 +489,7 @@ int mjx_mlp_fit_adam(const float* feat, const float* y, int64_t N, int d_in, con
         }
       }
       const AdamBias bc = adam_bias(b1, b2, ++t);
-      hipLaunchKernelGGL(k_adam, dim3((unsigned)((net.P + 255) / 256)), dim3(256), 0, st, params, grads, m, v, net.P, lr, wd, b1, b2, eps, bc.bc1, bc.bc2s);
+      hipLaunchKernelGGL(k_adam, dim3((unsigned)((net.P + 255) / 256)), dim3(256), 0, st, params, grads, m, v, net.P, lr, wd, 1.0f - b1, b2, 1.0f - b2, eps, bc.bc1, bc.bc2s);
     }
   }
   HIPCHK(lw_status());
@@ -1400,9 +1402,9 @@ int mjx_policy_minibatch_adam(mjx_ctx* c, int loss, const float* obs, const floa
                        c->mb_adv, B, c->m, theta + c->oS, (loss == 2) ? theta_old + c->oS : (const float*)nullptr, trn + 2 * c->n + c->m,
                        clip, w.d3, c->mb_grad + c->oS, loss_trace ? loss_trace + s : (double*)nullptr);
     if (int rc = w.backward(theta, B, c->mb_grad, st)) return fail(MJX_ERR_STATE, "minibatch backward failed (%d)", rc);
-    const AdamBias bc = adam_bias(0.9, 0.999, step0 + s + 1);
+    const AdamBias bc = adam_bias(ADAM_B1D, ADAM_B2D, step0 + s + 1);      // torch's constants, as k_policy_fit takes them (vecops.h)
     hipLaunchKernelGGL(k_adam, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, theta, c->mb_grad, adam_m, adam_v, cnt, lr, 0.f,
-                       0.9f, 0.999f, 1e-8f, bc.bc1, bc.bc2s);
+                       ADAM_C1, ADAM_B2, ADAM_C2, ADAM_EPS, bc.bc1, bc.bc2s);
   }
   HIPCHK(lw_status());
   return MJX_OK;

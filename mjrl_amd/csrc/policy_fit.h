@@ -271,8 +271,8 @@ __global__ __launch_bounds__(PFIT_THREADS) void k_policy_fit(PolicyFitArgs A) {
   }
   __syncthreads();
 
-  const float b1c = 0.9f, b2c = 0.999f, eps = 1e-8f;
-  double pw1 = pow((double)b1c, (double)A.step0), pw2 = pow((double)b2c, (double)A.step0);
+  const float eps = ADAM_EPS;                     // (Adam's constants: vecops.h)
+  double pw1 = pow(ADAM_B1D, (double)A.step0), pw2 = pow(ADAM_B2D, (double)A.step0);
   const float invB = 1.0f / (float)B;
   const float llc = 0.5f * (float)m * 1.8378770664093453f;
 
@@ -307,7 +307,7 @@ __global__ __launch_bounds__(PFIT_THREADS) void k_policy_fit(PolicyFitArgs A) {
     PFIT_STAMP(0);
     int next_row = 0;
     if (tid == 0) {                                        // this step's bias corrections, in double like torch's Python scalars
-      pw1 *= (double)b1c; pw2 *= (double)b2c;
+      pw1 *= ADAM_B1D; pw2 *= ADAM_B2D;
       ((float*)sh)[0] = 1.0f / (float)sqrt(1.0 - pw2);
       ((float*)sh)[1] = A.lr / (float)(1.0 - pw1);
     }
@@ -434,8 +434,8 @@ __global__ __launch_bounds__(PFIT_THREADS) void k_policy_fit(PolicyFitArgs A) {
       const int i = tid + PFIT_THREADS * e;
       if (i < dlim) {
         const float gi = G[poff[e]];
-        const float mi = am[e] + (gi - am[e]) * (1.0f - b1c);
-        const float vi = av[e] * b2c + gi * gi * (1.0f - b2c);
+        const float mi = am[e] + (gi - am[e]) * ADAM_C1;
+        const float vi = av[e] * ADAM_B2 + gi * gi * ADAM_C2;
         am[e] = mi; av[e] = vi;
         const float denom = fmaf(__builtin_amdgcn_sqrtf(vi), inv_bc2s, eps);
         W[poff[e]] = fmaf(-step_size, fast_div(mi, denom), W[poff[e]]);

@@ -7,6 +7,13 @@
 
 namespace mjx {
 
+// torch.optim.Adam's constants as torch hands them to its fp32 kernels, one definition for the policy fit on both of its routes
+// (policy_fit.h, k_adam as mjx_policy_minibatch_adam launches it) and the ensemble fit (dyn_fit_ens.h): beta and 1 - beta are each
+// formed in double and rounded ONCE -- `1.0f - 0.999f` is 0.0009999871, 1.3e-5 low, a bias of one sign in every second moment --
+// and the bias corrections come from the DOUBLE betas.  (The MLP-baseline trainers keep fp32 betas throughout: mjx_mlp_fit_adam.)
+constexpr float ADAM_B1 = 0.9f, ADAM_C1 = 0.1f, ADAM_B2 = 0.999f, ADAM_C2 = 0.001f, ADAM_EPS = 1e-8f;
+constexpr double ADAM_B1D = 0.9, ADAM_B2D = 0.999;
+
 // Sum over the 64 lanes of a wave, every lane gets the total.  Register-level cross-lane moves only (DPP inside the
 // 16-lane rows, v_permlane16_swap / v_permlane32_swap across them): the ds_bpermute butterfly this replaces cost
 // twelve LDS-crossbar round trips per fp64 sum.  Fixed order, identical on every lane.

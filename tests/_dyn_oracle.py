@@ -5,6 +5,11 @@ ensemble-disagreement truncation (model_accel_npg.py:139-150)."""
 import numpy as np
 
 AFF, MASK, RES = 1, 2, 4
+# Adam's coefficients (beta1, 1 - beta1, beta2, 1 - beta2) and the betas of the bias corrections.  ADAM_F64: the Python scalars;
+# ADAM_TORCH: what torch.optim.Adam hands its fp32 kernels -- each double rounded ONCE to fp32 -- with the corrections still
+# from the double betas (tests/_fit_oracle.py)
+ADAM_F64 = (0.9, 0.1, 0.999, 0.001, 0.9, 0.999)
+ADAM_TORCH = tuple(float(np.float32(c)) for c in (0.9, 0.1, 0.999, 0.001)) + (0.9, 0.999)
 
 
 def unflatten(theta, sizes):
@@ -20,11 +25,17 @@ def act_fn(x, act):
 
 
 def forward(theta, sizes, tr, x, act, flags, keep=False):
-    """tr = [in_shift, in_scale, out_shift, out_scale] over the concatenated input"""
-    theta, tr, x = (np.asarray(v, np.float64) for v in (theta, tr, x))
+    """tr = [in_shift, in_scale, out_shift, out_scale] over the concatenated input; None: the exact identity (no 1e-8), flags 0"""
+    theta, x = np.asarray(theta, np.float64), np.asarray(x, np.float64)
     din, dout = sizes[0], sizes[-1]
     Ws, bs = unflatten(theta, sizes)
-    h = (x - tr[:din]) / (tr[din:2 * din] + 1e-8)
+    if tr is None:
+        assert flags == 0
+        tr = np.zeros(2 * (din + dout))
+        h = x
+    else:
+        tr = np.asarray(tr, np.float64)
+        h = (x - tr[:din]) / (tr[din:2 * din] + 1e-8)
     hs = [h]
     for i, (W, b) in enumerate(zip(Ws, bs)):
         h = h @ W.T + b
@@ -41,14 +52,19 @@ def forward(theta, sizes, tr, x, act, flags, keep=False):
     return (h, hs) if keep else h
 
 
-def adam_steps(theta, sizes, tr, x, y, idx, batch, act, tmode, lr, wd, m=None, v=None, t0=0, g_first=None):
+def adam_steps(theta, sizes, tr, x, y, idx, batch, act, tmode, lr, wd, m=None, v=None, t0=0, g_first=None, coef=ADAM_F64):
     """fit_model's Adam steps in fp64: tmode 0 = loss through the output affine on raw y, 1 = (y - out_shift) /
     (out_scale + 1e-8), 2 = residual targets.  -> (theta, m, v, per-step losses).  g_first: an array that takes |gradient|
-    (weight decay included) of the first step"""
+    (weight decay included) of the first step.  tr None (tmode 0): no transforms at all, the plain MSE of the net's output"""
     theta = np.array(theta, np.float64)
-    x, y, tr = np.asarray(x, np.float64), np.asarray(y, np.float64).reshape(len(x), -1), np.asarray(tr, np.float64)
+    x, y = np.asarray(x, np.float64), np.asarray(y, np.float64).reshape(len(x), -1)
     din, dout = sizes[0], sizes[-1]
-    osh, osc = tr[2 * din:2 * din + dout], tr[2 * din + dout:]
+    if tr is None:
+        assert tmode == 0
+        osh, osc = np.zeros(dout), None
+    else:
+        tr = np.asarray(tr, np.float64)
+        osh, osc = tr[2 * din:2 * din + dout], tr[2 * din + dout:]
     if tmode == 2:
         tg = (y - x[:, :dout] - osh) / (osc + 1e-8)
     elif tmode == 1:
@@ -63,7 +79,7 @@ def adam_steps(theta, sizes, tr, x, y, idx, batch, act, tmode, lr, wd, m=None, v
         rows = idx[s * batch:(s + 1) * batch]
         _, hs = forward(theta, sizes, tr, x[rows], act, 0, keep=True)
         z = hs[-1]
-        sc = (osc + 1e-8) if tmode == 0 else 1.0
+        sc = (osc + 1e-8) if tmode == 0 and osc is not None else 1.0
         yh = z * sc + (osh if tmode == 0 else 0.0)
         err = yh - tg[rows]
         losses.append(np.mean(err ** 2))
@@ -81,10 +97,16 @@ def adam_steps(theta, sizes, tr, x, y, idx, batch, act, tmode, lr, wd, m=None, v
         g = g + wd * theta
         if g_first is not None and s == 0:
             g_first[...] = np.abs(g)
-        m = 0.9 * m + 0.1 * g
-        v = 0.999 * v + 0.001 * g * g
-        theta = theta - lr / (1 - 0.9 ** t) * m / (np.sqrt(v) / np.sqrt(1 - 0.999 ** t) + 1e-8)
+        theta, m, v = adam_update(theta, g, m, v, t, lr, coef)
     return theta, m, v, np.array(losses)
+
+
+def adam_update(theta, g, m, v, t, lr, coef=ADAM_F64):
+    """step t (1-based) of torch.optim.Adam (eps 1e-8; weight decay already in g) -> (theta, m, v)"""
+    b1, c1, b2, c2, bb1, bb2 = coef
+    m = b1 * m + c1 * g
+    v = b2 * v + c2 * g * g
+    return theta - lr / (1 - bb1 ** t) * m / (np.sqrt(v) / np.sqrt(1 - bb2 ** t) + 1e-8), m, v
 
 
 def policy_mean(pol_theta, pol_sizes, pol_tr, s):
