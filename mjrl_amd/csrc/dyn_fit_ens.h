@@ -77,19 +77,11 @@ struct DynFitEnsArgs {
   int64_t step0[DFE_CHUNK];             // Adam steps taken before this call, members k0 ..
 };
 
-// torch.optim.Adam as dyn_adam, with the two divisions as v_rcp_f32 + one Newton step (mlp_fit.h: <= 1 ulp from IEEE)
-// and 1 - beta rounded once
+// torch.optim.Adam as dyn_adam, in the v_rcp_f32 + Newton form (vecops.h: AdamRcp) with torch's constants: 1 - beta rounded
+// once (0.1f, 0.001f).  `1.0f - 0.999f` is 0.0009999871, 1.3e-5 low: a bias of the same sign in every second moment, which alone
+// moved a weight of the [13, 256, 256, 11] batch-16 test case by 2e-2 lr from the fp64 chain in ten steps.
 __device__ __forceinline__ void dfe_adam_math(float& p, float& m, float& v, float g, float lr_bc1, float inv_bc2s, float wd) {
-  // 1 - beta as torch hands it to its fp32 kernels (vecops.h: 0.1f, 0.001f).  `1.0f - 0.999f` is 0.0009999871, 1.3e-5 low: a
-  // bias of the same sign in every second moment, which alone moved a weight of the [13, 256, 256, 11] batch-16 test case by
-  // 2e-2 lr from the fp64 chain in ten steps.
-  const float gi = g + wd * p;
-  m = m + (gi - m) * ADAM_C1;
-  v = v * ADAM_B2 + gi * gi * ADAM_C2;
-  const float denom = fmaf(__builtin_amdgcn_sqrtf(v), inv_bc2s, ADAM_EPS);
-  float r = __builtin_amdgcn_rcpf(denom);
-  r = r * fmaf(-denom, r, 2.0f);
-  p = fmaf(-lr_bc1 * m, r, p);
+  p = AdamRcp<AdamTorch>{wd, lr_bc1, inv_bc2s}.one(p, g, m, v);
 }
 __device__ __forceinline__ void dfe_adam(float* p, float* m, float* v, int64_t i, float g, float lr_bc1, float inv_bc2s, float wd) {
   float p_ = p[i], m_ = m[i], v_ = v[i];

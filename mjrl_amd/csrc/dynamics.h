@@ -32,6 +32,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "vecops.h"
+
 namespace mjx {
 
 enum { DYN_ACT_RELU = 0, DYN_ACT_TANH = 1 };
@@ -265,14 +267,15 @@ struct DynFitArgs {
   float* loss;                        // per step: the minibatch MSE
 };
 
-// torch.optim.Adam (amsgrad off, L2 weight decay folded into the gradient, bias-corrected, eps 1e-8), as k_adam in baseline.h
+// torch.optim.Adam (amsgrad off, L2 weight decay folded into the gradient, bias-corrected, eps 1e-8), as k_adam in baseline.h,
+// exact divides, the fp32-beta constants (vecops.h)
 __device__ __forceinline__ void dyn_adam(float* p, float* m, float* v, int64_t i, float g, float lr_bc1, float bc2s, float wd) {
   const float pi = p[i];
   const float gi = g + wd * pi;
-  const float mi = m[i] + (gi - m[i]) * (1.0f - 0.9f);
-  const float vi = v[i] * 0.999f + gi * gi * (1.0f - 0.999f);
+  const float mi = m[i] + (gi - m[i]) * ADAM32_C1;
+  const float vi = v[i] * ADAM32_B2 + gi * gi * ADAM32_C2;
   m[i] = mi; v[i] = vi;
-  const float denom = sqrtf(vi) / bc2s + 1e-8f;
+  const float denom = sqrtf(vi) / bc2s + ADAM_EPS;
   p[i] = pi - lr_bc1 * (mi / denom);
 }
 __device__ __forceinline__ void dyn_bias_corr(int64_t t, float lr, float& lr_bc1, float& bc2s) {

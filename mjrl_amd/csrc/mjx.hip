@@ -458,9 +458,8 @@ int mjx_mlp_fit_adam(const float* feat, const float* y, int64_t N, int d_in, con
   float* grads = q;
   const int64_t steps = N / bs - 1;                 // optimize_model.py:24
   int64_t t = step0;
-  // fp32 betas, in 1 - beta (1.0f - 0.999f is 1.3e-5 below torch's 0.001f) and in the corrections too: the arithmetic of the persistent
-  // trainers (mlp_fit.h), self-consistent -- the steps stay within 1e-6 lr of torch's, v itself is 1.3e-5 low (tests/test_gpu_fit_matrix.py)
-  const float b1 = 0.9f, b2 = 0.999f, eps = 1e-8f;
+  // the fp32-beta set (vecops.h: ADAM32_*), in 1 - beta and in the corrections too: the arithmetic of the persistent trainers
+  // (mlp_fit.h), self-consistent -- the steps stay within 1e-6 lr of torch's, v itself is 1.3e-5 low (tests/test_gpu_fit_matrix.py)
   for (int ep = 0; ep < epochs; ++ep) {
     for (int64_t mb = 0; mb < steps; ++mb) {
       hipLaunchKernelGGL(k_gather_rows, dim3((bs * d_in + 255) / 256), dim3(256), 0, st, feat, y, perm + (int64_t)ep * N + mb * bs, bs, d_in, Xb, yb);
@@ -488,8 +487,8 @@ int mjx_mlp_fit_adam(const float* feat, const float* y, int64_t N, int d_in, con
           delta = dl[l - 1];
         }
       }
-      const AdamBias bc = adam_bias(b1, b2, ++t);
-      hipLaunchKernelGGL(k_adam, dim3((unsigned)((net.P + 255) / 256)), dim3(256), 0, st, params, grads, m, v, net.P, lr, wd, 1.0f - b1, b2, 1.0f - b2, eps, bc.bc1, bc.bc2s);
+      const AdamBias bc = adam_bias(ADAM32_B1, ADAM32_B2, ++t);
+      hipLaunchKernelGGL(k_adam, dim3((unsigned)((net.P + 255) / 256)), dim3(256), 0, st, params, grads, m, v, net.P, lr, wd, ADAM32_C1, ADAM32_B2, ADAM32_C2, ADAM_EPS, bc.bc1, bc.bc2s);
     }
   }
   HIPCHK(lw_status());

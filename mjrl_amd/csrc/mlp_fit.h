@@ -15,6 +15,7 @@
 #include <stdint.h>
 
 #include "fused_policy.h"
+#include "vecops.h"
 
 namespace mjx {
 
@@ -88,17 +89,133 @@ struct MlpFitArgs {
   int fault = 0;           // tests (MJX_FIT_FAULT=straggler): workgroup 0 starts 2.6 s late -- the others give up on the first barrier
 };
 
+// ---------------------------------------------------------------------------------------------------------------------------
+// The pieces both trainers below are built from.  Their step bodies differ on purpose (k_mlp_fit: two 32-sample halves,
+// k_mlp_fit1p: one 64-row pass); what surrounds the MFMA phases -- the weight image in LDS, the way in and out of that
+// image, the Adam rule, the LDS accessors -- is written once, here.  The minibatch gather and the description of the weights a
+// thread owns (with its register-resident moments) are still written per kernel: as shared structs they cost the default-route
+// instances registers (k_mlp_fit<128, 1, true> 400 -> 404 and 410 VGPRs, <128, 2, true, true> 72 -> 88 bytes of scratch).
+
+// torch.optim.Adam with the fp32-beta constants these trainers keep (vecops.h says why), and its state for step t: the powers
+// b1^t, b2^t advance in double, from them the bias corrections of the step
+using MlpFitAdam = AdamRcp<AdamFp32Betas>;
+__device__ __forceinline__ MlpFitAdam mlp_fit_adam_step(double& pw1, double& pw2, float lr, float wd) {
+  pw1 *= (double)ADAM32_B1; pw2 *= (double)ADAM32_B2;
+  const float bc1 = (float)(1.0 - pw1), bc2s = (float)sqrt(1.0 - pw2);
+  return MlpFitAdam{wd, lr / bc1, 1.0f / bc2s};
+}
+
+// LDS reads at `byte address + compile-time element offset`.  (LD1 volatile: keeps the load a single ds_read_b32 with its 16-bit
+// byte offset.  Paired into ds_read2_b32 -- 8-bit offsets, 1 020 bytes of reach -- every k-group of the MFMA loops needed a
+// v_add_u32 to re-base: 33 + 64 per step of the one-pass trainer between MFMAs)
+typedef __attribute__((address_space(3))) f32x4 lds_f4;
+typedef __attribute__((address_space(3))) f32x2 lds_f2;
+#define FIT_LD1(base, off) (*(const volatile lds_float*)(uintptr_t)((base) + (uint32_t)((off) * 4)))
+#define FIT_LD2(base, off) (*(const lds_f2*)(uintptr_t)((base) + (uint32_t)((off) * 4)))
+#define FIT_LD4(base, off) (*(const lds_f4*)(uintptr_t)((base) + (uint32_t)((off) * 4)))
+// One lane's window on an LDS tile: element tile[at + off], `off` a compile-time constant at every use.  PIN: the byte address
+// of tile[at] is laundered into a register (lds_pin) and every access is `base + immediate` -- left to the compiler, the row
+// addresses were hoisted out of the step loop as invariants, parked in AGPRs and fetched back with v_accvgpr_read + s_nop in
+// front of every store, and every fragment read of the MFMA phases re-derived `lane offset + buffer base + constant` with a
+// v_add_u32 (k_mlp_fit1p: ~75 + 41 + 114 isolated vector-ALU instructions per step that fp32 MFMAs do not hide).  Windows are
+// re-made every half / step for that reason.  !PIN (k_mlp_fit<128, 2, false>, one workgroup or several): tile[at + off] with the
+// compiler's addressing -- those two spill, and pinned bases are ten more live registers.
+template <bool PIN>
+struct FitLane {
+  uint32_t pin; float* tile; int at;
+  __device__ __forceinline__ FitLane(float* tile_, int at_) : pin(lds_pin(&tile_[at_])), tile(tile_), at(at_) {}
+  __device__ __forceinline__ float ld1(int off) const { if constexpr (PIN) return FIT_LD1(pin, off); else return tile[at + off]; }
+  __device__ __forceinline__ f32x2 ld2(int off) const { if constexpr (PIN) return FIT_LD2(pin, off); else return *(const f32x2*)&tile[at + off]; }
+  __device__ __forceinline__ f32x4 ld4(int off) const { if constexpr (PIN) return FIT_LD4(pin, off); else return *(const f32x4*)&tile[at + off]; }
+  __device__ __forceinline__ void st(int off, float v) const { if constexpr (PIN) LDS_AT(pin)[off] = v; else tile[at + off] = v; }
+};
+
+// The weight image at the front of both trainers' LDS blocks: W1 with b1 as its "ones" column ([H][S1], K1 = d_in + 1 rounded
+// up to 4), W2 [H][S2], W3, b2, b3 behind b2.  The tiles of a trainer start at tiles().
 template <int H>
-struct MlpFitLayout {
-  static constexpr int ST = 36, S2 = H + 4;
+struct MlpFitImage {
+  static constexpr int S2 = H + 4;
   int K1, S1;
-  int oW1, oW2, oW3, oB2, oXS, oXT, oH1, oH2, oD2, oY, oPART, oDY, TOTAL;
-  // wide (more than 31 inputs): no sample-major copy of the minibatch (layer 1 reads its operand from the transposed tile):
-  // 7 KB that let 50 inputs -- the 46-wide Adroit hammer observations -- fit the 160 KB
-  __host__ __device__ explicit MlpFitLayout(int d_in, bool wide = false) {
+  int oW1, oW2, oW3, oB2;
+  __host__ __device__ explicit MlpFitImage(int d_in) {
     K1 = (d_in + 1 + 3) & ~3; S1 = K1 + 2;
     oW1 = 0; oW2 = oW1 + H * S1; oW3 = oW2 + H * S2; oB2 = oW3 + H;
-    oXS = ((oB2 + H + 4 + 3) / 4) * 4;            // [32][S1]  (b3 sits at oB2 + H)
+  }
+  __host__ __device__ int tiles() const { return ((oB2 + H + 4 + 3) / 4) * 4; }      // (b3 sits at oB2 + H)
+};
+
+// The flat block params / m / v share in global memory, [W1 (H x dG), b1, W2 (H x H), b2, W3 (H), b3], and the part of it one
+// workgroup holds: the d_in features from f_off of every W1 row, b1 if has_b1, and (replicated under MULTI) the rest.
+// One workgroup: (d_in, 0, d_in, true).
+template <int H>
+struct MlpFitBlock {
+  int dG, f_off, d_in;
+  bool has_b1;
+  int64_t oW1, oB1, oW2, oB2, oW3, oB3, P;
+  __device__ __forceinline__ MlpFitBlock(int dG_, int f_off_, int d_in_, bool has_b1_) : dG(dG_), f_off(f_off_), d_in(d_in_), has_b1(has_b1_) {
+    oW1 = 0; oB1 = (int64_t)H * dG; oW2 = oB1 + H; oB2 = oW2 + (int64_t)H * H; oW3 = oB2 + H; oB3 = oW3 + H; P = oB3 + 1;
+  }
+};
+
+// parameter block -> the zeroed LDS block's weight image (b1 rides as the "ones" column of W1) ...
+template <int H, class LT>
+__device__ __forceinline__ void mlp_fit_load_params(const MlpFitArgs& A, const MlpFitBlock<H>& B, const LT& L, float* lds, int tid) {
+  float* sW1 = lds + L.oW1; float* sW2 = lds + L.oW2; float* sW3 = lds + L.oW3; float* sB2 = lds + L.oB2;
+  const int d_in = B.d_in, S1 = L.S1, S2 = LT::S2;
+  for (int i = tid; i < L.TOTAL; i += 256) lds[i] = 0.f;
+  __syncthreads();
+  for (int i = tid; i < H * (d_in + 1); i += 256) {
+    int u = i / (d_in + 1), f = i - u * (d_in + 1);
+    sW1[u * S1 + f] = (f < d_in) ? A.params[B.oW1 + (int64_t)u * B.dG + B.f_off + f] : (B.has_b1 ? A.params[B.oB1 + u] : 0.f);
+  }
+  for (int i = tid; i < H * H; i += 256) sW2[(i / H) * S2 + (i % H)] = A.params[B.oW2 + i];
+  for (int i = tid; i < H; i += 256) { sW3[i] = A.params[B.oW3 + i]; sB2[i] = A.params[B.oB2 + i]; }
+  if (tid == 0) sB2[H] = A.params[B.oB3];
+}
+// ... and back.  (MULTI: a workgroup writes what it alone holds -- its W1 slice, b1 on the last one -- and workgroup 0 the
+// replicated rest; the same rule for the moments below)
+template <int H, bool MULTI, class LT>
+__device__ __forceinline__ void mlp_fit_store_params(const MlpFitArgs& A, const MlpFitBlock<H>& B, const LT& L, const float* lds, int g_id, int tid) {
+  const float* sW1 = lds + L.oW1; const float* sW2 = lds + L.oW2; const float* sW3 = lds + L.oW3; const float* sB2 = lds + L.oB2;
+  const int d_in = B.d_in, S1 = L.S1, S2 = LT::S2;
+  for (int i = tid; i < H * (d_in + 1); i += 256) {
+    int u = i / (d_in + 1), f = i - u * (d_in + 1);
+    if (f < d_in) A.params[B.oW1 + (int64_t)u * B.dG + B.f_off + f] = sW1[u * S1 + f];
+    else if (B.has_b1) A.params[B.oB1 + u] = sW1[u * S1 + d_in];
+  }
+  if (!MULTI || g_id == 0) {
+    for (int i = tid; i < H * H; i += 256) A.params[B.oW2 + i] = sW2[(i / H) * S2 + (i % H)];
+    for (int i = tid; i < H; i += 256) { A.params[B.oW3 + i] = sW3[i]; A.params[B.oB2 + i] = sB2[i]; }
+    if (tid == 0) A.params[B.oB3] = sB2[H];
+  }
+}
+// moments m, v -> the workgroup's interleaved (m, v) pairs `mv` and back
+template <int H>
+__device__ __forceinline__ void mlp_fit_load_moments(const MlpFitArgs& A, const MlpFitBlock<H>& B, float* mv, int tid) {
+  for (int64_t i = tid; i < B.P; i += 256) { mv[2 * i] = A.m[i]; mv[2 * i + 1] = A.v[i]; }
+}
+template <int H, bool MULTI>
+__device__ __forceinline__ void mlp_fit_store_moments(const MlpFitArgs& A, const MlpFitBlock<H>& B, const float* mv, int g_id, int tid) {
+  for (int64_t i = tid; i < B.P; i += 256) {
+    bool mine = true;
+    if constexpr (MULTI) {
+      if (i < B.oB1) { const int f = (int)(i % B.dG); mine = f >= B.f_off && f < B.f_off + B.d_in; }
+      else if (i < B.oW2) mine = B.has_b1;
+      else mine = g_id == 0;
+    }
+    if (mine) { A.m[i] = mv[2 * i]; A.v[i] = mv[2 * i + 1]; }
+  }
+}
+
+template <int H>
+struct MlpFitLayout : MlpFitImage<H> {
+  static constexpr int ST = 36;
+  int oXS, oXT, oH1, oH2, oD2, oY, oPART, oDY, TOTAL;
+  // wide (more than 31 inputs): no sample-major copy of the minibatch (layer 1 reads its operand from the transposed tile):
+  // 7 KB that let 50 inputs -- the 46-wide Adroit hammer observations -- fit the 160 KB
+  __host__ __device__ explicit MlpFitLayout(int d_in, bool wide = false) : MlpFitImage<H>(d_in) {
+    const int K1 = this->K1, S1 = this->S1;
+    oXS = this->tiles();                          // [32][S1]
     oXT = wide ? oXS : ((oXS + 32 * S1 + 3) / 4) * 4;          // [K1][ST]
     oH1 = oXT + K1 * ST;                          // [H][ST]
     oH2 = oH1 + H * ST;
@@ -162,26 +279,16 @@ __global__ __launch_bounds__(256, 1) void k_mlp_fit(MlpFitArgs A) {
   float* sB3 = sB2 + H;
   float* xs = lds + L.oXS; float* xT = lds + L.oXT; float* h1T = lds + L.oH1; float* h2T = lds + L.oH2; float* d2T = lds + L.oD2;
   float* sY = lds + L.oY; float* sPart = lds + L.oPART; float* sDY = lds + L.oDY;
-  const int64_t oW1g = 0, oB1g = (int64_t)H * dG, oW2g = oB1g + H, oB2g = oW2g + (int64_t)H * H, oW3g = oB2g + H, oB3g = oW3g + H;
+  const MlpFitBlock<H> B(dG, f_off, d_in, has_b1);
 
-  // ---- load parameters into LDS (b1 rides as the "ones" column of W1)
-  for (int i = tid; i < L.TOTAL; i += 256) lds[i] = 0.f;
-  __syncthreads();
-  for (int i = tid; i < H * (d_in + 1); i += 256) {
-    int u = i / (d_in + 1), f = i - u * (d_in + 1);
-    sW1[u * S1 + f] = (f < d_in) ? A.params[oW1g + (int64_t)u * dG + f_off + f] : (has_b1 ? A.params[oB1g + u] : 0.f);
-  }
-  for (int i = tid; i < H * H; i += 256) sW2[(i / H) * S2 + (i % H)] = A.params[oW2g + i];
-  for (int i = tid; i < H; i += 256) { sW3[i] = A.params[oW3g + i]; sB2[i] = A.params[oB2g + i]; }
-  if (tid == 0) sB3[0] = A.params[oB3g];
+  // ---- parameters into LDS, moments into the interleaved workspace (MULTI: every workgroup its own copy of the pairs)
+  mlp_fit_load_params<H>(A, B, L, lds, tid);
   if (tid < 32) { if (NF1 == 1) xs[tid * S1 + d_in] = 1.0f; xT[d_in * ST + tid] = has_b1 ? 1.0f : 0.f; }
-  const int64_t Ptot = oB3g + 1;
-  float* const mvbase = A.mv + (MULTI ? (int64_t)g_id * 2 * Ptot : 0);          // (MULTI: every workgroup its own copy of the pairs)
-  for (int64_t i = tid; i < Ptot; i += 256) { mvbase[2 * i] = A.m[i]; mvbase[2 * i + 1] = A.v[i]; }
+  float* const mvbase = A.mv + (MULTI ? (int64_t)g_id * 2 * B.P : 0);          // (MULTI: every workgroup its own copy of the pairs)
+  mlp_fit_load_moments<H>(A, B, mvbase, tid);
   __syncthreads();
 
-  const float b1c = 0.9f, b2c = 0.999f, eps = 1e-8f;
-  double pw1 = pow((double)b1c, (double)A.step0), pw2 = pow((double)b2c, (double)A.step0);
+  double pw1 = pow((double)ADAM32_B1, (double)A.step0), pw2 = pow((double)ADAM32_B2, (double)A.step0);
   constexpr int GL = (32 * 32 * NF1 + 255) / 256;   // gather elements per thread (d_in <= 32 NF1 - 1)
   float gx[GL];
   float gy = 0.f;
@@ -223,7 +330,7 @@ __global__ __launch_bounds__(256, 1) void k_mlp_fit(MlpFitArgs A) {
   // registers are free by then), so the L2 latency is paid once per step and not once per block; then update, write the weight to
   // LDS and the pair back.  Threads that do not own an entry of a block read a valid dummy pair and store nothing.
   f32x2* __restrict__ MV = (f32x2*)mvbase;
-  const int64_t gbase2 = oW2g + (int64_t)(32 * w + 4 * hi) * H + j;
+  const int64_t gbase2 = B.oW2 + (int64_t)(32 * w + 4 * hi) * H + j;
   f32x2* __restrict__ mvW2 = MV + gbase2;
   float* pW2 = sW2 + (32 * w + 4 * hi) * S2 + j;
   // W1 rows of this wave (feature f = 32 fb + j < d_in) and b1 (f == d_in): one base pointer + a small per-register stride
@@ -237,12 +344,12 @@ __global__ __launch_bounds__(256, 1) void k_mlp_fit(MlpFitArgs A) {
     const bool isw = f < d_in;
     own1[fb] = isw || (f == d_in && has_b1);
     stg[fb] = isw ? dG : 1;
-    const int64_t gbase1 = isw ? oW1g + (int64_t)(32 * w + 4 * hi) * dG + f_off + f : oB1g + 32 * w + 4 * hi;
+    const int64_t gbase1 = isw ? B.oW1 + (int64_t)(32 * w + 4 * hi) * dG + f_off + f : B.oB1 + 32 * w + 4 * hi;
     mvW1[fb] = MV + (own1[fb] ? gbase1 : 0);
     pW1[fb] = sW1 + (32 * w + 4 * hi) * S1 + (isw ? f : d_in);
   }
   const bool ownb2 = hi == 0, ownw3 = tid < H, ownb3 = tid == 0;
-  const int64_t gb2i = oB2g + 32 * w + j, gw3i = oW3g + (ownw3 ? tid : 0), gb3i = oB3g;
+  const int64_t gb2i = B.oB2 + 32 * w + j, gw3i = B.oW3 + (ownw3 ? tid : 0), gb3i = B.oB3;
   f32x2 q2[NT][16], q1[NF1][16], qb2, qw3, qb3;
   if constexpr (REGMOM) {
     // the pairs this thread owns, for the whole run (MV was filled above, barrier passed), re-paired for packed math:
@@ -284,18 +391,15 @@ __global__ __launch_bounds__(256, 1) void k_mlp_fit(MlpFitArgs A) {
 #pragma unroll 1
       for (int hb = 0; hb < 2; ++hb) {
         MJX_FIT_STAMP(0);
-        // (r04, REGMOM builds) this lane's byte address per tile and use, re-laundered every half: every LDS access of the MFMA phases
-        // below is then `base + immediate` -- no hoisted address parked in an AGPR, no v_add_u32 re-basing ds_read2 pairs between
-        // MFMAs (k_mlp_fit1p tells the story; the r03 kernels, REGMOM = false, keep the compiler's addressing)
-        const uint32_t h1w = lds_pin(&h1T[(32 * w + 4 * hi) * ST + j]), d2w = lds_pin(&d2T[(32 * w + 4 * hi) * ST + j]);
-        const uint32_t h2w = lds_pin(&h2T[(32 * w + 4 * hi) * ST + j]);
-        const uint32_t h1c = lds_pin(&h1T[(4 * hi) * ST + j]), d2c = lds_pin(&d2T[(4 * hi) * ST + j]);
-        const uint32_t h1r = lds_pin(&h1T[(32 * w + j) * ST + 4 * hi]), d2r = lds_pin(&d2T[(32 * w + j) * ST + 4 * hi]);
-        const uint32_t h1n = lds_pin(&h1T[j * ST + 4 * hi]);
-        const uint32_t w2r = lds_pin(&sW2[(32 * w + j) * S2 + 4 * hi]), w2c = lds_pin(&sW2[(4 * hi) * S2 + 32 * w + j]);
-        typedef __attribute__((address_space(3))) f32x4 lds_f4;
-#define FIT2_LD1(base, off) (*(const volatile lds_float*)(uintptr_t)((base) + (uint32_t)((off) * 4)))
-#define FIT2_LD4(base, off) (*(const lds_f4*)(uintptr_t)((base) + (uint32_t)((off) * 4)))
+        // this lane's windows on the tiles, per use, re-made every half (FitLane).  Pinned in the REGMOM builds (r04) and in the
+        // one-block build without REGMOM; the two-block builds without REGMOM keep the compiler's addressing (they spill)
+        constexpr bool PIN = REGMOM || NF1 == 1;
+        const FitLane<PIN> h1w(h1T, (32 * w + 4 * hi) * ST + j), d2w(d2T, (32 * w + 4 * hi) * ST + j);   // row group 32 w + 4 hi, sample j
+        const FitLane<PIN> h2w(h2T, (32 * w + 4 * hi) * ST + j);
+        const FitLane<PIN> h1c(h1T, (4 * hi) * ST + j), d2c(d2T, (4 * hi) * ST + j);                     // rows k (+ const), sample j
+        const FitLane<PIN> h1r(h1T, (32 * w + j) * ST + 4 * hi), d2r(d2T, (32 * w + j) * ST + 4 * hi);   // row = this lane's unit, 4 samples per read
+        const FitLane<PIN> h1n(h1T, j * ST + 4 * hi);                                                    // rows 32 nt + j
+        const FitLane<PIN> w2r(sW2, (32 * w + j) * S2 + 4 * hi), w2c(sW2, (4 * hi) * S2 + 32 * w + j);
         gather_store();
         __syncthreads();
         // prefetch the next half's rows while this half computes
@@ -364,10 +468,7 @@ __global__ __launch_bounds__(256, 1) void k_mlp_fit(MlpFitArgs A) {
           ++phase;
         }
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          if constexpr (REGMOM) LDS_AT(h1w)[unit_of(r, 0) * ST] = fmaxf(z1[r], 0.f);
-          else h1T[(32 * w + unit_of(r, hi)) * ST + j] = fmaxf(z1[r], 0.f);
-        }
+        for (int r = 0; r < 16; ++r) h1w.st(unit_of(r, 0) * ST, fmaxf(z1[r], 0.f));         // row 32 w + unit_of(r, hi)
         __syncthreads();
         MJX_FIT_STAMP(2);
         // ---- layer 2: K = all 128 h1 units (B operand from the shared h1^T tile)
@@ -381,17 +482,16 @@ __global__ __launch_bounds__(256, 1) void k_mlp_fit(MlpFitArgs A) {
         {
           f32x4 ac, an;
           float bc[4], bn[4];
-          if constexpr (REGMOM) ac = FIT2_LD4(w2r, 0); else ac = *(const f32x4*)&sW2[(32 * w + j) * S2 + 4 * hi];
+          ac = w2r.ld4(0);                                                  // W2[32 w + j][4 hi ..]
 #pragma unroll
-          for (int t = 0; t < 4; ++t) { if constexpr (REGMOM) bc[t] = FIT2_LD1(h1c, t * ST); else bc[t] = h1T[(4 * hi + t) * ST + j]; }
+          for (int t = 0; t < 4; ++t) bc[t] = h1c.ld1(t * ST);
 #pragma unroll
           for (int g = 0; g < 16; ++g) {
             if (g + 1 < 16) {
-              const int k1 = 32 * ((g + 1) >> 2) + 8 * ((g + 1) & 3) + 4 * hi;
-              const int k1c = 32 * ((g + 1) >> 2) + 8 * ((g + 1) & 3);
-              if constexpr (REGMOM) an = FIT2_LD4(w2r, k1c); else an = *(const f32x4*)&sW2[(32 * w + j) * S2 + k1];
+              const int k1c = 32 * ((g + 1) >> 2) + 8 * ((g + 1) & 3);          // (+ 4 hi: in the windows)
+              an = w2r.ld4(k1c);
 #pragma unroll
-              for (int t = 0; t < 4; ++t) { if constexpr (REGMOM) bn[t] = FIT2_LD1(h1c, (k1c + t) * ST); else bn[t] = h1T[(k1 + t) * ST + j]; }
+              for (int t = 0; t < 4; ++t) bn[t] = h1c.ld1((k1c + t) * ST);
             }
 #pragma unroll
             for (int t = 0; t < 4; ++t) z2 = MJX_MFMA(ac[t], bc[t], z2);
@@ -413,7 +513,7 @@ __global__ __launch_bounds__(256, 1) void k_mlp_fit(MlpFitArgs A) {
         for (int r = 0; r < 16; ++r) {
           float hv = fmaxf(z2[r], 0.f);
           z2[r] = hv;
-          if constexpr (REGMOM) LDS_AT(h2w)[unit_of(r, 0) * ST] = hv; else h2T[(32 * w + unit_of(r, hi)) * ST + j] = hv;
+          h2w.st(unit_of(r, 0) * ST, hv);
           part = fmaf(w3v[r], hv, part);
         }
         part = half_sum(part);                            // (+ the other lane half: v_permlane32_swap, the bits of part + shfl_xor(part, 32))
@@ -431,11 +531,7 @@ __global__ __launch_bounds__(256, 1) void k_mlp_fit(MlpFitArgs A) {
         }
         // delta2 (lane = sample) -> d2T [unit][sample]
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int u = 32 * w + unit_of(r, hi);
-          if constexpr (REGMOM) LDS_AT(d2w)[unit_of(r, 0) * ST] = (z2[r] > 0.f) ? w3v[r] * dy : 0.f;
-          else d2T[u * ST + j] = (z2[r] > 0.f) ? w3v[r] * dy : 0.f;
-        }
+        for (int r = 0; r < 16; ++r) d2w.st(unit_of(r, 0) * ST, (z2[r] > 0.f) ? w3v[r] * dy : 0.f);
         __syncthreads();
         MJX_FIT_STAMP(4);
         // ---- grad W3 / b3 (thread = unit), grad b2, delta2 in lane = unit layout straight from d2T
@@ -453,8 +549,7 @@ __global__ __launch_bounds__(256, 1) void k_mlp_fit(MlpFitArgs A) {
         f32x16 d2u;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-          f32x4 t4;
-          if constexpr (REGMOM) t4 = FIT2_LD4(d2r, 8 * q); else t4 = *(const f32x4*)&d2T[(32 * w + j) * ST + 8 * q + 4 * hi];
+          const f32x4 t4 = d2r.ld4(8 * q);
           d2u[4 * q] = t4.x; d2u[4 * q + 1] = t4.y; d2u[4 * q + 2] = t4.z; d2u[4 * q + 3] = t4.w;
         }
         {
@@ -468,12 +563,12 @@ __global__ __launch_bounds__(256, 1) void k_mlp_fit(MlpFitArgs A) {
         {
           f32x4 bc[NT], bn[NT];
 #pragma unroll
-          for (int nt = 0; nt < NT; ++nt) { if constexpr (REGMOM) bc[nt] = FIT2_LD4(h1n, 32 * nt * ST); else bc[nt] = *(const f32x4*)&h1T[(32 * nt + j) * ST + 4 * hi]; }
+          for (int nt = 0; nt < NT; ++nt) bc[nt] = h1n.ld4(32 * nt * ST);
 #pragma unroll
           for (int q = 0; q < 4; ++q) {
             if (q + 1 < 4) {
 #pragma unroll
-              for (int nt = 0; nt < NT; ++nt) { if constexpr (REGMOM) bn[nt] = FIT2_LD4(h1n, 32 * nt * ST + 8 * (q + 1)); else bn[nt] = *(const f32x4*)&h1T[(32 * nt + j) * ST + 8 * (q + 1) + 4 * hi]; }
+              for (int nt = 0; nt < NT; ++nt) bn[nt] = h1n.ld4(32 * nt * ST + 8 * (q + 1));
             }
 #pragma unroll
             for (int t = 0; t < 4; ++t)
@@ -490,20 +585,13 @@ __global__ __launch_bounds__(256, 1) void k_mlp_fit(MlpFitArgs A) {
         {
           float ac[4], an[4], bc[4], bn[4];
 #pragma unroll
-          for (int t = 0; t < 4; ++t) {
-            if constexpr (REGMOM) { ac[t] = FIT2_LD1(d2c, t * ST); bc[t] = FIT2_LD1(w2c, t * S2); }
-            else { ac[t] = d2T[(4 * hi + t) * ST + j]; bc[t] = sW2[(4 * hi + t) * S2 + 32 * w + j]; }
-          }
+          for (int t = 0; t < 4; ++t) { ac[t] = d2c.ld1(t * ST); bc[t] = w2c.ld1(t * S2); }
 #pragma unroll
           for (int g = 0; g < 16; ++g) {
             if (g + 1 < 16) {
-              const int k1 = 32 * ((g + 1) >> 2) + 8 * ((g + 1) & 3) + 4 * hi;
+              const int k1c = 32 * ((g + 1) >> 2) + 8 * ((g + 1) & 3);
 #pragma unroll
-              for (int t = 0; t < 4; ++t) {
-                const int k1c = 32 * ((g + 1) >> 2) + 8 * ((g + 1) & 3);
-                if constexpr (REGMOM) { an[t] = FIT2_LD1(d2c, (k1c + t) * ST); bn[t] = FIT2_LD1(w2c, (k1c + t) * S2); }
-                else { an[t] = d2T[(k1 + t) * ST + j]; bn[t] = sW2[(k1 + t) * S2 + 32 * w + j]; }
-              }
+              for (int t = 0; t < 4; ++t) { an[t] = d2c.ld1((k1c + t) * ST); bn[t] = w2c.ld1((k1c + t) * S2); }
             }
 #pragma unroll
             for (int t = 0; t < 4; ++t) d1u = MJX_MFMA(ac[t], bc[t], d1u);
@@ -520,8 +608,7 @@ __global__ __launch_bounds__(256, 1) void k_mlp_fit(MlpFitArgs A) {
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int q = 0; q < 4; ++q) {                       // relu'(z1) mask from h1^T (same layout)
-          f32x4 hv;
-          if constexpr (REGMOM) hv = FIT2_LD4(h1r, 8 * q); else hv = *(const f32x4*)&h1T[(32 * w + j) * ST + 8 * q + 4 * hi];
+          const f32x4 hv = h1r.ld4(8 * q);
           d1u[4 * q] = hv.x > 0.f ? d1u[4 * q] : 0.f; d1u[4 * q + 1] = hv.y > 0.f ? d1u[4 * q + 1] : 0.f;
           d1u[4 * q + 2] = hv.z > 0.f ? d1u[4 * q + 2] : 0.f; d1u[4 * q + 3] = hv.w > 0.f ? d1u[4 * q + 3] : 0.f;
         }
@@ -542,46 +629,7 @@ __global__ __launch_bounds__(256, 1) void k_mlp_fit(MlpFitArgs A) {
       }
       { const int hb = 0; MJX_FIT_STAMP(9); }
       // ---- Adam (torch.optim.Adam: L2 weight decay folded into the gradient, bias-corrected)
-      pw1 *= (double)b1c; pw2 *= (double)b2c;
-      const float bc1 = (float)(1.0 - pw1), bc2s = (float)sqrt(1.0 - pw2);
-      const float step_size = A.lr / bc1;
-      // torch.optim.Adam's update; the two divides use v_rcp_f32 + one Newton step (<= 1 ulp from IEEE),
-      // which keeps the 19 457-weight update at ~18 VALU ops per weight
-      const float inv_bc2s = 1.0f / bc2s;
-      auto adam_math = [&](float p, float g, f32x2& q) {
-        g += A.wd * p;
-        float mi = q.x, vi = q.y;
-        mi = mi + (g - mi) * (1.0f - b1c);
-        vi = vi * b2c + g * g * (1.0f - b2c);
-        q = f32x2{mi, vi};
-        const float denom = fmaf(__builtin_amdgcn_sqrtf(vi), inv_bc2s, eps);
-        float r = __builtin_amdgcn_rcpf(denom);
-        r = r * fmaf(-denom, r, 2.0f);
-        return fmaf(-step_size * mi, r, p);
-      };
-      // the same update on TWO weights per instruction (packed fp32): the arithmetic of adam_math element by element -- the
-      // vector ALU is paid in full on this chip (fp32 MFMAs hide none of it), the 19 457-weight update is ~12 instructions per weight
-      auto adam_math2 = [&](f32x2 p, f32x2 g, f32x2& qa, f32x2& qb) {
-        g = __builtin_elementwise_fma((f32x2)(A.wd), p, g);
-        f32x2 mi = {qa.x, qb.x}, vi = {qa.y, qb.y};
-        mi = __builtin_elementwise_fma(g - mi, (f32x2)(1.0f - b1c), mi);
-        vi = __builtin_elementwise_fma(g * g, (f32x2)(1.0f - b2c), vi * (f32x2)(b2c));
-        qa = f32x2{mi.x, vi.x}; qb = f32x2{mi.y, vi.y};
-        const f32x2 denom = __builtin_elementwise_fma(f32x2{__builtin_amdgcn_sqrtf(vi.x), __builtin_amdgcn_sqrtf(vi.y)}, (f32x2)(inv_bc2s), (f32x2)(eps));
-        f32x2 r = {__builtin_amdgcn_rcpf(denom.x), __builtin_amdgcn_rcpf(denom.y)};
-        r = r * __builtin_elementwise_fma(-denom, r, (f32x2)(2.0f));
-        return __builtin_elementwise_fma(mi * (f32x2)(-step_size), r, p);
-      };
-      // ... and on moments that already sit as (m, m) / (v, v) pairs (REGMOM): no re-pairing moves
-      auto adam_math2p = [&](f32x2 p, f32x2 g, f32x2& mi, f32x2& vi) {
-        g = __builtin_elementwise_fma((f32x2)(A.wd), p, g);
-        mi = __builtin_elementwise_fma(g - mi, (f32x2)(1.0f - b1c), mi);
-        vi = __builtin_elementwise_fma(g * g, (f32x2)(1.0f - b2c), vi * (f32x2)(b2c));
-        const f32x2 denom = __builtin_elementwise_fma(f32x2{__builtin_amdgcn_sqrtf(vi.x), __builtin_amdgcn_sqrtf(vi.y)}, (f32x2)(inv_bc2s), (f32x2)(eps));
-        f32x2 r = {__builtin_amdgcn_rcpf(denom.x), __builtin_amdgcn_rcpf(denom.y)};
-        r = r * __builtin_elementwise_fma(-denom, r, (f32x2)(2.0f));
-        return __builtin_elementwise_fma(mi * (f32x2)(-step_size), r, p);
-      };
+      const MlpFitAdam adam = mlp_fit_adam_step(pw1, pw2, A.lr, A.wd);
       {
         if constexpr (!REGMOM) {
 #pragma unroll
@@ -601,14 +649,14 @@ __global__ __launch_bounds__(256, 1) void k_mlp_fit(MlpFitArgs A) {
             const int o0 = unit_of(r, 0) * H + 32 * nt, l0 = unit_of(r, 0) * S2 + 32 * nt;
             const int o1 = unit_of(r + 1, 0) * H + 32 * nt, l1 = unit_of(r + 1, 0) * S2 + 32 * nt;
             if constexpr (REGMOM) {
-              const f32x2 pn = adam_math2p(f32x2{pW2[l0], pW2[l1]}, f32x2{gW2[nt][r], gW2[nt][r + 1]}, q2[nt][r], q2[nt][r + 1]);
+              const f32x2 pn = adam.pairp(f32x2{pW2[l0], pW2[l1]}, f32x2{gW2[nt][r], gW2[nt][r + 1]}, q2[nt][r], q2[nt][r + 1]);
               pW2[l0] = pn.x; pW2[l1] = pn.y;
             } else if constexpr (NF1 == 1) {
-              const f32x2 pn = adam_math2(f32x2{pW2[l0], pW2[l1]}, f32x2{gW2[nt][r], gW2[nt][r + 1]}, q2[nt][r], q2[nt][r + 1]);
+              const f32x2 pn = adam.pair(f32x2{pW2[l0], pW2[l1]}, f32x2{gW2[nt][r], gW2[nt][r + 1]}, q2[nt][r], q2[nt][r + 1]);
               pW2[l0] = pn.x; pW2[l1] = pn.y;
             } else {                                      // (the two-block variant already spills: the packed form's temporaries cost it 2 %)
-              pW2[l0] = adam_math(pW2[l0], gW2[nt][r], q2[nt][r]);
-              pW2[l1] = adam_math(pW2[l1], gW2[nt][r + 1], q2[nt][r + 1]);
+              pW2[l0] = adam.one(pW2[l0], gW2[nt][r], q2[nt][r]);
+              pW2[l1] = adam.one(pW2[l1], gW2[nt][r + 1], q2[nt][r + 1]);
             }
             if constexpr (!REGMOM) { mvW2[o0] = q2[nt][r]; mvW2[o1] = q2[nt][r + 1]; }
           }
@@ -619,21 +667,21 @@ __global__ __launch_bounds__(256, 1) void k_mlp_fit(MlpFitArgs A) {
             for (int r = 0; r < 16; r += 2) {
               const int o0 = unit_of(r, 0) * stg[fb], l0 = unit_of(r, 0) * S1, o1 = unit_of(r + 1, 0) * stg[fb], l1 = unit_of(r + 1, 0) * S1;
               if constexpr (REGMOM) {
-                const f32x2 pn = adam_math2p(f32x2{pW1[fb][l0], pW1[fb][l1]}, f32x2{gW1[fb][r], gW1[fb][r + 1]}, q1[fb][r], q1[fb][r + 1]);
+                const f32x2 pn = adam.pairp(f32x2{pW1[fb][l0], pW1[fb][l1]}, f32x2{gW1[fb][r], gW1[fb][r + 1]}, q1[fb][r], q1[fb][r + 1]);
                 pW1[fb][l0] = pn.x; pW1[fb][l1] = pn.y;
               } else if constexpr (NF1 == 1) {
-                const f32x2 pn = adam_math2(f32x2{pW1[fb][l0], pW1[fb][l1]}, f32x2{gW1[fb][r], gW1[fb][r + 1]}, q1[fb][r], q1[fb][r + 1]);
+                const f32x2 pn = adam.pair(f32x2{pW1[fb][l0], pW1[fb][l1]}, f32x2{gW1[fb][r], gW1[fb][r + 1]}, q1[fb][r], q1[fb][r + 1]);
                 pW1[fb][l0] = pn.x; pW1[fb][l1] = pn.y;
               } else {
-                pW1[fb][l0] = adam_math(pW1[fb][l0], gW1[fb][r], q1[fb][r]);
-                pW1[fb][l1] = adam_math(pW1[fb][l1], gW1[fb][r + 1], q1[fb][r + 1]);
+                pW1[fb][l0] = adam.one(pW1[fb][l0], gW1[fb][r], q1[fb][r]);
+                pW1[fb][l1] = adam.one(pW1[fb][l1], gW1[fb][r + 1], q1[fb][r + 1]);
               }
               if constexpr (!REGMOM) { mvW1[fb][o0] = q1[fb][r]; mvW1[fb][o1] = q1[fb][r + 1]; }
             }
           }
-        if (ownb2) { sB2[32 * w + j] = adam_math(sB2[32 * w + j], gb2, qb2); if constexpr (!REGMOM) MV[gb2i] = qb2; }
-        if (ownw3) { sW3[tid] = adam_math(sW3[tid], gw3, qw3); if constexpr (!REGMOM) MV[gw3i] = qw3; }
-        if (ownb3) { sB3[0] = adam_math(sB3[0], gb3, qb3); if constexpr (!REGMOM) MV[gb3i] = qb3; }
+        if (ownb2) { sB2[32 * w + j] = adam.one(sB2[32 * w + j], gb2, qb2); if constexpr (!REGMOM) MV[gb2i] = qb2; }
+        if (ownw3) { sW3[tid] = adam.one(sW3[tid], gw3, qw3); if constexpr (!REGMOM) MV[gw3i] = qw3; }
+        if (ownb3) { sB3[0] = adam.one(sB3[0], gb3, qb3); if constexpr (!REGMOM) MV[gb3i] = qb3; }
       }
       __syncthreads();
       { const int hb = 0; MJX_FIT_STAMP(10); }
@@ -664,26 +712,8 @@ __global__ __launch_bounds__(256, 1) void k_mlp_fit(MlpFitArgs A) {
     if (ownb3) MV[gb3i] = qb3;
   }
   __syncthreads();
-  // (MULTI: a workgroup writes what it alone holds -- its W1 slice, b1 on the last one -- and workgroup 0 the replicated rest)
-  for (int64_t i = tid; i < Ptot; i += 256) {
-    bool mine = true;
-    if constexpr (MULTI) {
-      if (i < oB1g) { const int f = (int)(i % dG); mine = f >= f_off && f < f_off + d_in; }
-      else if (i < oW2g) mine = has_b1;
-      else mine = g_id == 0;
-    }
-    if (mine) { A.m[i] = mvbase[2 * i]; A.v[i] = mvbase[2 * i + 1]; }
-  }
-  for (int i = tid; i < H * (d_in + 1); i += 256) {
-    int u = i / (d_in + 1), f = i - u * (d_in + 1);
-    if (f < d_in) A.params[oW1g + (int64_t)u * dG + f_off + f] = sW1[u * S1 + f];
-    else if (has_b1) A.params[oB1g + u] = sW1[u * S1 + d_in];
-  }
-  if (!MULTI || g_id == 0) {
-    for (int i = tid; i < H * H; i += 256) A.params[oW2g + i] = sW2[(i / H) * S2 + (i % H)];
-    for (int i = tid; i < H; i += 256) { A.params[oW3g + i] = sW3[i]; A.params[oB2g + i] = sB2[i]; }
-    if (tid == 0) A.params[oB3g] = sB3[0];
-  }
+  mlp_fit_store_moments<H, MULTI>(A, B, mvbase, g_id, tid);
+  mlp_fit_store_params<H, MULTI>(A, B, L, lds, g_id, tid);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -697,15 +727,12 @@ __global__ __launch_bounds__(256, 1) void k_mlp_fit(MlpFitArgs A) {
 // (REGMOM above).  Same minibatches, same update rule; the gradient sums run in a different order than the per-half kernel's
 // (both halves interleaved per k-group), so parameters agree with it to round-off, not bit for bit.
 template <int H>
-struct MlpFit1pLayout {
-  static constexpr int ST = 68, S2 = H + 4;
-  int K1, S1;
-  int oW1, oW2, oW3, oB2, oXT, oH1, oD2, oY, oPART, oGW3, TOTAL;
-  __host__ __device__ explicit MlpFit1pLayout(int d_in) {
-    K1 = (d_in + 1 + 3) & ~3; S1 = K1 + 2;
-    oW1 = 0; oW2 = oW1 + H * S1; oW3 = oW2 + H * S2; oB2 = oW3 + H;
-    oXT = ((oB2 + H + 4 + 3) / 4) * 4;            // [K1][ST]   (b3 sits at oB2 + H)
-    oH1 = oXT + K1 * ST;                          // [H][ST]
+struct MlpFit1pLayout : MlpFitImage<H> {
+  static constexpr int ST = 68;
+  int oXT, oH1, oD2, oY, oPART, oGW3, TOTAL;
+  __host__ __device__ explicit MlpFit1pLayout(int d_in) : MlpFitImage<H>(d_in) {
+    oXT = this->tiles();                          // [K1][ST]
+    oH1 = oXT + this->K1 * ST;                    // [H][ST]
     oD2 = oH1 + H * ST;
     oY = oD2 + H * ST;                            // [64]
     oPART = oY + 64;                              // [4][64]
@@ -728,25 +755,15 @@ __global__ __launch_bounds__(256, 1) void k_mlp_fit1p(MlpFitArgs A) {
   float* sB3 = sB2 + H;
   float* xT = lds + L.oXT; float* h1T = lds + L.oH1; float* d2T = lds + L.oD2;
   float* sY = lds + L.oY; float* sPart = lds + L.oPART; float* sGW3 = lds + L.oGW3;
-  const int64_t oW1g = 0, oB1g = (int64_t)H * d_in, oW2g = oB1g + H, oB2g = oW2g + (int64_t)H * H, oW3g = oB2g + H, oB3g = oW3g + H;
+  const MlpFitBlock<H> B(d_in, 0, d_in, true);
 
-  // ---- parameters into LDS (b1 rides as the "ones" column of W1), moments into the interleaved workspace
-  for (int i = tid; i < L.TOTAL; i += 256) lds[i] = 0.f;
-  __syncthreads();
-  for (int i = tid; i < H * (d_in + 1); i += 256) {
-    int u = i / (d_in + 1), f = i - u * (d_in + 1);
-    sW1[u * S1 + f] = (f < d_in) ? A.params[oW1g + (int64_t)u * d_in + f] : A.params[oB1g + u];
-  }
-  for (int i = tid; i < H * H; i += 256) sW2[(i / H) * S2 + (i % H)] = A.params[oW2g + i];
-  for (int i = tid; i < H; i += 256) { sW3[i] = A.params[oW3g + i]; sB2[i] = A.params[oB2g + i]; }
-  if (tid == 0) sB3[0] = A.params[oB3g];
+  // ---- parameters into LDS, moments into the interleaved workspace
+  mlp_fit_load_params<H>(A, B, L, lds, tid);
   if (tid < 64) xT[d_in * ST + tid] = 1.0f;
-  const int64_t Ptot = oB3g + 1;
-  for (int64_t i = tid; i < Ptot; i += 256) { A.mv[2 * i] = A.m[i]; A.mv[2 * i + 1] = A.v[i]; }
+  mlp_fit_load_moments<H>(A, B, A.mv, tid);
   __syncthreads();
 
-  const float b1c = 0.9f, b2c = 0.999f, eps = 1e-8f;
-  double pw1 = pow((double)b1c, (double)A.step0), pw2 = pow((double)b2c, (double)A.step0);
+  double pw1 = pow((double)ADAM32_B1, (double)A.step0), pw2 = pow((double)ADAM32_B2, (double)A.step0);
   constexpr int GL = (64 * 24 + 255) / 256;          // gather elements per thread (d_in <= 23)
   float gx[GL];
   float gy = 0.f;
@@ -779,14 +796,14 @@ __global__ __launch_bounds__(256, 1) void k_mlp_fit1p(MlpFitArgs A) {
   // ---- Adam ownership (as k_mlp_fit): the 64 W2 weights, 16 W1 / b1 entries and the b2 / W3 / b3 entry of this thread, their
   // moments in registers for the whole run as (m, m) / (v, v) pairs of neighbouring weights
   f32x2* __restrict__ MV = (f32x2*)A.mv;
-  f32x2* __restrict__ mvW2 = MV + oW2g + (int64_t)(32 * w + 4 * hi) * H + j;
+  f32x2* __restrict__ mvW2 = MV + B.oW2 + (int64_t)(32 * w + 4 * hi) * H + j;
   float* pW2 = sW2 + (32 * w + 4 * hi) * S2 + j;
   const bool isw1 = j < d_in, own1 = j <= d_in;
   const int stg = isw1 ? d_in : 1;
-  f32x2* mvW1 = MV + (own1 ? (isw1 ? oW1g + (int64_t)(32 * w + 4 * hi) * d_in + j : oB1g + 32 * w + 4 * hi) : 0);
+  f32x2* mvW1 = MV + (own1 ? (isw1 ? B.oW1 + (int64_t)(32 * w + 4 * hi) * d_in + j : B.oB1 + 32 * w + 4 * hi) : 0);
   float* pW1 = sW1 + (32 * w + 4 * hi) * S1 + (isw1 ? j : d_in);
   const bool ownb2 = hi == 0, ownw3 = tid < H, ownb3 = tid == 0;
-  const int64_t gb2i = oB2g + 32 * w + j, gw3i = oW3g + (ownw3 ? tid : 0), gb3i = oB3g;
+  const int64_t gb2i = B.oB2 + 32 * w + j, gw3i = B.oW3 + (ownw3 ? tid : 0), gb3i = B.oB3;
   f32x2 q2[NT][16], q1[16], qb2, qw3, qb3;
 #pragma unroll
   for (int nt = 0; nt < NT; ++nt)
@@ -814,26 +831,14 @@ __global__ __launch_bounds__(256, 1) void k_mlp_fit1p(MlpFitArgs A) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) w3v[r] = sW3[32 * w + unit_of(r, hi)];
       const int hb = 0;
-      // this lane's byte address in row group (32 w + 4 hi) of the two [unit][sample] tiles, re-laundered every step: every access
-      // below is then `base + immediate`.  (Left to the compiler, the 16 + 32 row addresses of the h1^T / delta2^T stores were hoisted
-      // out of the step loop as invariants, parked in AGPRs by the register allocator and fetched back with v_accvgpr_read + s_nop
-      // in front of every store: ~75 isolated vector-ALU instructions per step that fp32 MFMAs do not hide.)
-      uint32_t h1w = lds_pin(&h1T[(32 * w + 4 * hi) * ST + j]), d2w = lds_pin(&d2T[(32 * w + 4 * hi) * ST + j]);
-      // ... and of every fragment read of the MFMA phases (the same story: 41 + 114 v_add_u32 between the MFMAs of layer 2 and of the
-      // backward pass, re-deriving `lane offset + buffer base + constant`)
-      const uint32_t h1c = lds_pin(&h1T[(4 * hi) * ST + j]), d2c = lds_pin(&d2T[(4 * hi) * ST + j]);                 // rows k (+ const), sample 32 h + j
-      const uint32_t h1r = lds_pin(&h1T[(32 * w + j) * ST + 4 * hi]), d2r = lds_pin(&d2T[(32 * w + j) * ST + 4 * hi]); // row = this lane's unit, 4 samples per read
-      const uint32_t h1n = lds_pin(&h1T[j * ST + 4 * hi]);                                                           // rows 32 nt + j
-      const uint32_t w2r = lds_pin(&sW2[(32 * w + j) * S2 + 4 * hi]), w2c = lds_pin(&sW2[(4 * hi) * S2 + 32 * w + j]);
-      const uint32_t x1c = lds_pin(&xT[(2 * hi) * ST + j]), w1r = lds_pin(&sW1[(32 * w + j) * S1 + 2 * hi]);
-      const uint32_t xgr = lds_pin(&xT[(j < K1 ? j : 0) * ST + 4 * hi]);
-      typedef __attribute__((address_space(3))) f32x4 lds_f4;
-      typedef __attribute__((address_space(3))) f32x2 lds_f2;
-// (volatile: keeps the load a single ds_read_b32 with its 16-bit byte offset.  Paired into ds_read2_b32 -- 8-bit offsets, 1 020
-//  bytes of reach -- every k-group of the MFMA loops needed a v_add_u32 to re-base: 33 + 64 per step between MFMAs)
-#define FIT_LD1(base, off) (*(const volatile lds_float*)(uintptr_t)((base) + (uint32_t)((off) * 4)))
-#define FIT_LD2(base, off) (*(const lds_f2*)(uintptr_t)((base) + (uint32_t)((off) * 4)))
-#define FIT_LD4(base, off) (*(const lds_f4*)(uintptr_t)((base) + (uint32_t)((off) * 4)))
+      // this lane's windows on the tiles and the weights, per use, re-made every step (FitLane)
+      const FitLane<true> h1w(h1T, (32 * w + 4 * hi) * ST + j), d2w(d2T, (32 * w + 4 * hi) * ST + j);     // row group 32 w + 4 hi, sample 32 h + j
+      const FitLane<true> h1c(h1T, (4 * hi) * ST + j), d2c(d2T, (4 * hi) * ST + j);                       // rows k (+ const), sample 32 h + j
+      const FitLane<true> h1r(h1T, (32 * w + j) * ST + 4 * hi), d2r(d2T, (32 * w + j) * ST + 4 * hi);     // row = this lane's unit, 4 samples per read
+      const FitLane<true> h1n(h1T, j * ST + 4 * hi);                                                      // rows 32 nt + j
+      const FitLane<true> w2r(sW2, (32 * w + j) * S2 + 4 * hi), w2c(sW2, (4 * hi) * S2 + 32 * w + j);
+      const FitLane<true> x1c(xT, (2 * hi) * ST + j), w1r(sW1, (32 * w + j) * S1 + 2 * hi);
+      const FitLane<true> xgr(xT, (j < K1 ? j : 0) * ST + 4 * hi);
       MJX_FIT_STAMP(0);
       gather_store();
       lds_barrier();                                                                                // (1) minibatch staged
@@ -850,9 +855,9 @@ __global__ __launch_bounds__(256, 1) void k_mlp_fit1p(MlpFitArgs A) {
 #pragma unroll
         for (int q = 0; q < 6; ++q)
           if (q < nq) {
-            a1[q] = FIT_LD2(w1r, 4 * q);                                   // W1[32 w + j][4 q + 2 hi .. + 1]
+            a1[q] = w1r.ld2(4 * q);                                   // W1[32 w + j][4 q + 2 hi .. + 1]
 #pragma unroll
-            for (int h = 0; h < 2; ++h) { b1x[q][h] = FIT_LD1(x1c, (4 * q) * ST + 32 * h); b1y[q][h] = FIT_LD1(x1c, (4 * q + 1) * ST + 32 * h); }
+            for (int h = 0; h < 2; ++h) { b1x[q][h] = x1c.ld1((4 * q) * ST + 32 * h); b1y[q][h] = x1c.ld1((4 * q + 1) * ST + 32 * h); }
           }
 #pragma unroll
         for (int q = 0; q < 6; ++q)
@@ -866,7 +871,7 @@ __global__ __launch_bounds__(256, 1) void k_mlp_fit1p(MlpFitArgs A) {
 #pragma unroll
         for (int h = 0; h < 2; ++h)
 #pragma unroll
-          for (int r = 0; r < 16; ++r) LDS_AT(h1w)[unit_of(r, 0) * ST + 32 * h] = fmaxf(z1[h][r], 0.f);     // row 32 w + unit_of(r, hi)
+          for (int r = 0; r < 16; ++r) h1w.st(unit_of(r, 0) * ST + 32 * h, fmaxf(z1[h][r], 0.f));     // row 32 w + unit_of(r, hi)
       }
       lds_barrier();                                                                                // (2) h1^T complete
       MJX_FIT_STAMP(2);
@@ -880,21 +885,21 @@ __global__ __launch_bounds__(256, 1) void k_mlp_fit1p(MlpFitArgs A) {
       }
       __builtin_amdgcn_sched_barrier(0);
       {
-        f32x4 ac = FIT_LD4(w2r, 0), an;
+        f32x4 ac = w2r.ld4(0), an;
         float bc[2][4], bn[2][4];
 #pragma unroll
         for (int h = 0; h < 2; ++h)
 #pragma unroll
-          for (int t = 0; t < 4; ++t) bc[h][t] = FIT_LD1(h1c, t * ST + 32 * h);
+          for (int t = 0; t < 4; ++t) bc[h][t] = h1c.ld1(t * ST + 32 * h);
 #pragma unroll
         for (int g = 0; g < 16; ++g) {
           if (g + 1 < 16) {
             const int k1c = 32 * ((g + 1) >> 2) + 8 * ((g + 1) & 3);          // (+ 4 hi: in the pinned bases)
-            an = FIT_LD4(w2r, k1c);
+            an = w2r.ld4(k1c);
 #pragma unroll
             for (int h = 0; h < 2; ++h)
 #pragma unroll
-              for (int t = 0; t < 4; ++t) bn[h][t] = FIT_LD1(h1c, (k1c + t) * ST + 32 * h);
+              for (int t = 0; t < 4; ++t) bn[h][t] = h1c.ld1((k1c + t) * ST + 32 * h);
           }
 #pragma unroll
           for (int t = 0; t < 4; ++t) { z2[0] = MJX_MFMA(ac[t], bc[0][t], z2[0]); z2[1] = MJX_MFMA(ac[t], bc[1][t], z2[1]); }
@@ -941,8 +946,8 @@ __global__ __launch_bounds__(256, 1) void k_mlp_fit1p(MlpFitArgs A) {
       // 32 lanes (= samples j, both halves folded first) of h2 * dy, per accumulator register (= unit)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        LDS_AT(d2w)[unit_of(r, 0) * ST] = (z2[0][r] > 0.f) ? w3v[r] * dy[0] : 0.f;                          // row 32 w + unit_of(r, hi)
-        LDS_AT(d2w)[unit_of(r, 0) * ST + 32] = (z2[1][r] > 0.f) ? w3v[r] * dy[1] : 0.f;
+        d2w.st(unit_of(r, 0) * ST, (z2[0][r] > 0.f) ? w3v[r] * dy[0] : 0.f);                          // row 32 w + unit_of(r, hi)
+        d2w.st(unit_of(r, 0) * ST + 32, (z2[1][r] > 0.f) ? w3v[r] * dy[1] : 0.f);
         gw3p[r] = fmaf(z2[1][r], dy[1], z2[0][r] * dy[0]);
       }
       sum32_lane0_x16(gw3p);                                  // valid in lane 0 of each half
@@ -960,7 +965,7 @@ __global__ __launch_bounds__(256, 1) void k_mlp_fit1p(MlpFitArgs A) {
       for (int h = 0; h < 2; ++h)
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-          const f32x4 t4 = FIT_LD4(d2r, 32 * h + 8 * q);
+          const f32x4 t4 = d2r.ld4(32 * h + 8 * q);
           d2u[h][4 * q] = t4.x; d2u[h][4 * q + 1] = t4.y; d2u[h][4 * q + 2] = t4.z; d2u[h][4 * q + 3] = t4.w;
         }
       float gb2;
@@ -976,12 +981,12 @@ __global__ __launch_bounds__(256, 1) void k_mlp_fit1p(MlpFitArgs A) {
       for (int h = 0; h < 2; ++h) {
         f32x4 bc[NT], bn[NT];
 #pragma unroll
-        for (int nt = 0; nt < NT; ++nt) bc[nt] = FIT_LD4(h1n, 32 * nt * ST + 32 * h);
+        for (int nt = 0; nt < NT; ++nt) bc[nt] = h1n.ld4(32 * nt * ST + 32 * h);
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
           if (q + 1 < 4) {
 #pragma unroll
-            for (int nt = 0; nt < NT; ++nt) bn[nt] = FIT_LD4(h1n, 32 * nt * ST + 32 * h + 8 * (q + 1));
+            for (int nt = 0; nt < NT; ++nt) bn[nt] = h1n.ld4(32 * nt * ST + 32 * h + 8 * (q + 1));
           }
 #pragma unroll
           for (int t = 0; t < 4; ++t)
@@ -999,8 +1004,8 @@ __global__ __launch_bounds__(256, 1) void k_mlp_fit1p(MlpFitArgs A) {
         float ac[2][4], an[2][4], bc[4], bn[4];
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
-          bc[t] = FIT_LD1(w2c, t * S2);
-          ac[0][t] = FIT_LD1(d2c, t * ST); ac[1][t] = FIT_LD1(d2c, t * ST + 32);
+          bc[t] = w2c.ld1(t * S2);
+          ac[0][t] = d2c.ld1(t * ST); ac[1][t] = d2c.ld1(t * ST + 32);
         }
 #pragma unroll
         for (int g = 0; g < 16; ++g) {
@@ -1008,8 +1013,8 @@ __global__ __launch_bounds__(256, 1) void k_mlp_fit1p(MlpFitArgs A) {
             const int k1c = 32 * ((g + 1) >> 2) + 8 * ((g + 1) & 3);
 #pragma unroll
             for (int t = 0; t < 4; ++t) {
-              bn[t] = FIT_LD1(w2c, (k1c + t) * S2);
-              an[0][t] = FIT_LD1(d2c, (k1c + t) * ST); an[1][t] = FIT_LD1(d2c, (k1c + t) * ST + 32);
+              bn[t] = w2c.ld1((k1c + t) * S2);
+              an[0][t] = d2c.ld1((k1c + t) * ST); an[1][t] = d2c.ld1((k1c + t) * ST + 32);
             }
           }
 #pragma unroll
@@ -1029,7 +1034,7 @@ __global__ __launch_bounds__(256, 1) void k_mlp_fit1p(MlpFitArgs A) {
       for (int h = 0; h < 2; ++h)
 #pragma unroll
         for (int q = 0; q < 4; ++q) {                       // relu'(z1) mask from h1^T (same layout)
-          const f32x4 hv = FIT_LD4(h1r, 32 * h + 8 * q);
+          const f32x4 hv = h1r.ld4(32 * h + 8 * q);
           d1u[h][4 * q] = hv.x > 0.f ? d1u[h][4 * q] : 0.f; d1u[h][4 * q + 1] = hv.y > 0.f ? d1u[h][4 * q + 1] : 0.f;
           d1u[h][4 * q + 2] = hv.z > 0.f ? d1u[h][4 * q + 2] : 0.f; d1u[h][4 * q + 3] = hv.w > 0.f ? d1u[h][4 * q + 3] : 0.f;
         }
@@ -1041,7 +1046,7 @@ __global__ __launch_bounds__(256, 1) void k_mlp_fit1p(MlpFitArgs A) {
         for (int h = 0; h < 2; ++h)
 #pragma unroll
           for (int q = 0; q < 4; ++q) {
-            b4[h][q] = FIT_LD4(xgr, 32 * h + 8 * q);
+            b4[h][q] = xgr.ld4(32 * h + 8 * q);
             if (j >= K1) b4[h][q] = (f32x4)(0.f);
           }
 #pragma unroll
@@ -1055,49 +1060,26 @@ __global__ __launch_bounds__(256, 1) void k_mlp_fit1p(MlpFitArgs A) {
       lds_barrier();                                                                                // (5) tiles are rewritten by the next step
       MJX_FIT_STAMP(8);
       // ---- Adam (torch.optim.Adam: L2 weight decay folded into the gradient, bias-corrected), moments in registers
-      pw1 *= (double)b1c; pw2 *= (double)b2c;
-      const float bc1 = (float)(1.0 - pw1), bc2s = (float)sqrt(1.0 - pw2);
-      const float step_size = A.lr / bc1;
-      const float inv_bc2s = 1.0f / bc2s;
-      auto adam_math = [&](float p, float g, f32x2& q) {
-        g += A.wd * p;
-        float mi = q.x, vi = q.y;
-        mi = mi + (g - mi) * (1.0f - b1c);
-        vi = vi * b2c + g * g * (1.0f - b2c);
-        q = f32x2{mi, vi};
-        const float denom = fmaf(__builtin_amdgcn_sqrtf(vi), inv_bc2s, eps);
-        float r = __builtin_amdgcn_rcpf(denom);
-        r = r * fmaf(-denom, r, 2.0f);
-        return fmaf(-step_size * mi, r, p);
-      };
-      auto adam_math2p = [&](f32x2 p, f32x2 g, f32x2& mi, f32x2& vi) {
-        g = __builtin_elementwise_fma((f32x2)(A.wd), p, g);
-        mi = __builtin_elementwise_fma(g - mi, (f32x2)(1.0f - b1c), mi);
-        vi = __builtin_elementwise_fma(g * g, (f32x2)(1.0f - b2c), vi * (f32x2)(b2c));
-        const f32x2 denom = __builtin_elementwise_fma(f32x2{__builtin_amdgcn_sqrtf(vi.x), __builtin_amdgcn_sqrtf(vi.y)}, (f32x2)(inv_bc2s), (f32x2)(eps));
-        f32x2 r = {__builtin_amdgcn_rcpf(denom.x), __builtin_amdgcn_rcpf(denom.y)};
-        r = r * __builtin_elementwise_fma(-denom, r, (f32x2)(2.0f));
-        return __builtin_elementwise_fma(mi * (f32x2)(-step_size), r, p);
-      };
+      const MlpFitAdam adam = mlp_fit_adam_step(pw1, pw2, A.lr, A.wd);
 #pragma unroll
       for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
         for (int r = 0; r < 16; r += 2) {
           const int l0 = unit_of(r, 0) * S2 + 32 * nt, l1 = unit_of(r + 1, 0) * S2 + 32 * nt;
-          const f32x2 pn = adam_math2p(f32x2{pW2[l0], pW2[l1]}, f32x2{gW2[nt][r], gW2[nt][r + 1]}, q2[nt][r], q2[nt][r + 1]);
+          const f32x2 pn = adam.pairp(f32x2{pW2[l0], pW2[l1]}, f32x2{gW2[nt][r], gW2[nt][r + 1]}, q2[nt][r], q2[nt][r + 1]);
           pW2[l0] = pn.x; pW2[l1] = pn.y;
         }
       if (own1) {
 #pragma unroll
         for (int r = 0; r < 16; r += 2) {
           const int l0 = unit_of(r, 0) * S1, l1 = unit_of(r + 1, 0) * S1;
-          const f32x2 pn = adam_math2p(f32x2{pW1[l0], pW1[l1]}, f32x2{gW1[r], gW1[r + 1]}, q1[r], q1[r + 1]);
+          const f32x2 pn = adam.pairp(f32x2{pW1[l0], pW1[l1]}, f32x2{gW1[r], gW1[r + 1]}, q1[r], q1[r + 1]);
           pW1[l0] = pn.x; pW1[l1] = pn.y;
         }
       }
-      if (ownb2) sB2[32 * w + j] = adam_math(sB2[32 * w + j], gb2, qb2);
-      if (ownw3) sW3[tid] = adam_math(sW3[tid], gw3, qw3);
-      if (ownb3) sB3[0] = adam_math(sB3[0], gb3, qb3);
+      if (ownb2) sB2[32 * w + j] = adam.one(sB2[32 * w + j], gb2, qb2);
+      if (ownw3) sW3[tid] = adam.one(sW3[tid], gw3, qw3);
+      if (ownb3) sB3[0] = adam.one(sB3[0], gb3, qb3);
       lds_barrier();                                                                                // (6) weights updated
       MJX_FIT_STAMP(9);
     }
@@ -1122,14 +1104,8 @@ __global__ __launch_bounds__(256, 1) void k_mlp_fit1p(MlpFitArgs A) {
   if (ownw3) MV[gw3i] = qw3;
   if (ownb3) MV[gb3i] = qb3;
   __syncthreads();
-  for (int64_t i = tid; i < Ptot; i += 256) { A.m[i] = A.mv[2 * i]; A.v[i] = A.mv[2 * i + 1]; }
-  for (int i = tid; i < H * (d_in + 1); i += 256) {
-    int u = i / (d_in + 1), f = i - u * (d_in + 1);
-    if (f < d_in) A.params[oW1g + (int64_t)u * d_in + f] = sW1[u * S1 + f]; else A.params[oB1g + u] = sW1[u * S1 + d_in];
-  }
-  for (int i = tid; i < H * H; i += 256) A.params[oW2g + i] = sW2[(i / H) * S2 + (i % H)];
-  for (int i = tid; i < H; i += 256) { A.params[oW3g + i] = sW3[i]; A.params[oB2g + i] = sB2[i]; }
-  if (tid == 0) A.params[oB3g] = sB3[0];
+  mlp_fit_store_moments<H, false>(A, B, A.mv, 0, tid);
+  mlp_fit_store_params<H, false>(A, B, L, lds, 0, tid);
 }
 
 }  // namespace mjx

@@ -10,9 +10,66 @@ namespace mjx {
 // torch.optim.Adam's constants as torch hands them to its fp32 kernels, one definition for the policy fit on both of its routes
 // (policy_fit.h, k_adam as mjx_policy_minibatch_adam launches it) and the ensemble fit (dyn_fit_ens.h): beta and 1 - beta are each
 // formed in double and rounded ONCE -- `1.0f - 0.999f` is 0.0009999871, 1.3e-5 low, a bias of one sign in every second moment --
-// and the bias corrections come from the DOUBLE betas.  (The MLP-baseline trainers keep fp32 betas throughout: mjx_mlp_fit_adam.)
+// and the bias corrections come from the DOUBLE betas.
 constexpr float ADAM_B1 = 0.9f, ADAM_C1 = 0.1f, ADAM_B2 = 0.999f, ADAM_C2 = 0.001f, ADAM_EPS = 1e-8f;
 constexpr double ADAM_B1D = 0.9, ADAM_B2D = 0.999;
+// The fp32-beta set of the MLP-baseline trainers on all their routes (mlp_fit.h, mjx_mlp_fit_adam) and of dyn_adam: 1 - beta formed
+// in fp32 -- ADAM32_C2 is the 0.0009999871 above -- and the bias corrections from the fp32 betas too, so the steps stay within
+// 1e-6 lr of torch's while v sits 1.3e-5 low.  Kept on purpose: torch's set was measured there as well (v 2.4e-6, parameters
+// unchanged), but it moves every ReLU trajectory by 1e-5, and the persistent and the launch route of the baseline fit, compared
+// after 80 chaotic steps, then differ by one unit's sign at 27 inputs.
+constexpr float ADAM32_B1 = 0.9f, ADAM32_C1 = 1.0f - 0.9f, ADAM32_B2 = 0.999f, ADAM32_C2 = 1.0f - 0.999f;
+struct AdamTorch { static constexpr float C1 = ADAM_C1, B2 = ADAM_B2, C2 = ADAM_C2; };
+struct AdamFp32Betas { static constexpr float C1 = ADAM32_C1, B2 = ADAM32_B2, C2 = ADAM32_C2; };
+
+typedef float f32x2 __attribute__((ext_vector_type(2)));      // (fused_policy.h's; the packed fp32 forms below)
+
+// torch.optim.Adam's update of one step (L2 weight decay folded into the gradient, bias-corrected) with the constant set K and
+// the two divides as v_rcp_f32 + one Newton step (<= 1 ulp from IEEE): ~18 vector-ALU instructions per weight, ~12 in the
+// packed forms (two weights per instruction; the arithmetic of one() element by element).  Each returns the new weight.
+template <class K>
+struct AdamRcp {
+  float wd, step_size, inv_bc2s;      // weight decay, lr / (1 - b1^t), 1 / sqrt(1 - b2^t)
+  __device__ __forceinline__ float one(float p, float g, float& m, float& v) const {
+    g += wd * p;
+    m = m + (g - m) * K::C1;
+    v = v * K::B2 + g * g * K::C2;
+    const float denom = fmaf(__builtin_amdgcn_sqrtf(v), inv_bc2s, ADAM_EPS);
+    float r = __builtin_amdgcn_rcpf(denom);
+    r = r * fmaf(-denom, r, 2.0f);
+    return fmaf(-step_size * m, r, p);
+  }
+  // ... the moments as one (m, v) pair
+  __device__ __forceinline__ float one(float p, float g, f32x2& q) const {
+    float m = q.x, v = q.y;
+    p = one(p, g, m, v);
+    q = f32x2{m, v};
+    return p;
+  }
+  // two weights whose moments sit as (m, m) / (v, v)
+  __device__ __forceinline__ f32x2 pairp(f32x2 p, f32x2 g, f32x2& m, f32x2& v) const {
+    g = __builtin_elementwise_fma((f32x2)(wd), p, g);
+    m = __builtin_elementwise_fma(g - m, (f32x2)(K::C1), m);
+    v = __builtin_elementwise_fma(g * g, (f32x2)(K::C2), v * (f32x2)(K::B2));
+    const f32x2 denom = __builtin_elementwise_fma(f32x2{__builtin_amdgcn_sqrtf(v.x), __builtin_amdgcn_sqrtf(v.y)}, (f32x2)(inv_bc2s), (f32x2)(ADAM_EPS));
+    f32x2 r = {__builtin_amdgcn_rcpf(denom.x), __builtin_amdgcn_rcpf(denom.y)};
+    r = r * __builtin_elementwise_fma(-denom, r, (f32x2)(2.0f));
+    return __builtin_elementwise_fma(m * (f32x2)(-step_size), r, p);
+  }
+  // two weights with (m, v) pairs qa, qb.  (Written out, not a wrapper of pairp: with the pairs re-made after the divide the
+  // register allocation of k_mlp_fit<128, 1, false> changes)
+  __device__ __forceinline__ f32x2 pair(f32x2 p, f32x2 g, f32x2& qa, f32x2& qb) const {
+    g = __builtin_elementwise_fma((f32x2)(wd), p, g);
+    f32x2 m = {qa.x, qb.x}, v = {qa.y, qb.y};
+    m = __builtin_elementwise_fma(g - m, (f32x2)(K::C1), m);
+    v = __builtin_elementwise_fma(g * g, (f32x2)(K::C2), v * (f32x2)(K::B2));
+    qa = f32x2{m.x, v.x}; qb = f32x2{m.y, v.y};
+    const f32x2 denom = __builtin_elementwise_fma(f32x2{__builtin_amdgcn_sqrtf(v.x), __builtin_amdgcn_sqrtf(v.y)}, (f32x2)(inv_bc2s), (f32x2)(ADAM_EPS));
+    f32x2 r = {__builtin_amdgcn_rcpf(denom.x), __builtin_amdgcn_rcpf(denom.y)};
+    r = r * __builtin_elementwise_fma(-denom, r, (f32x2)(2.0f));
+    return __builtin_elementwise_fma(m * (f32x2)(-step_size), r, p);
+  }
+};
 
 // Sum over the 64 lanes of a wave, every lane gets the total.  Register-level cross-lane moves only (DPP inside the
 // 16-lane rows, v_permlane16_swap / v_permlane32_swap across them): the ds_bpermute butterfly this replaces cost
