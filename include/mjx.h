@@ -384,7 +384,13 @@ int mjx_bl_features_f32(const double* obs, const int32_t* tpos, int64_t N, int n
  * (featmat.T.dot(featmat), featmat.T.dot(returns): quadratic_baseline.py:57-60, linear_baseline.py:48-51). */
 int mjx_bl_gram(int kind, const double* obs, const int32_t* tpos, const double* y, int64_t N, int n,
                 double* G_aug_out, void* stream);
-/* out[s] = features(s) . coef   (fp64; quadratic_baseline.py:71-74) */
+/* Which Gram kernel would serve such a call, from the same function and the same switch (MJX_GRAM_FMA, read per call): out6 = {arm
+ * (0 fp64 matrix cores with one workgroup per sample range, 1 matrix cores by 128 x 128 feature blocks, 2 FMA 64 x 64 tiles), Z sample
+ * ranges, feature blocks a side (0 for arm 0), grid x, features a side of a reduce tile, bytes of dynamic LDS}.  mjx_bl_gram refuses
+ * arms 0 and 2 beyond 64 KiB of LDS (MJX_ERR_UNSUPPORTED).  Arithmetic only: no device work and no runtime call
+ * (tests/test_aux_routes_cpu.py). */
+int mjx_bl_gram_route(int kind, int n, int64_t N, int32_t* out6);
+/* out[s] = features(s) . coef  (fp64; quadratic_baseline.py:71-74) */
 int mjx_bl_predict(int kind, const double* obs, const int32_t* tpos, int64_t N, int n, const double* coef,
                    double* out, void* stream);
 /* ReLU MLP regressor d_in -> hidden... -> 1 (mlp_baseline.py:21-28), flat params [W1,b1,...]:

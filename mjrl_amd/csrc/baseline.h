@@ -119,7 +119,7 @@ __global__ __launch_bounds__(256) void k_bl_gram(int nbt, const FeatDesc* __rest
 
 // The same on the fp64 matrix cores for up to 176 augmented features (obs dim <= 17 quadratic, any linear baseline of that
 // size): v_mfma_f64_16x16x4_f64, lane l supplies A[i = l & 15][k = l >> 4] and B[k = l >> 4][j = l & 15] and receives
-// D[4 r + (l >> 4)][l & 15] in register r (probed: not the 4 (l >> 4) + r of the fp32 16x16x4 form).  One workgroup walks its own sample range in chunks of 32: ALL features of a chunk are
+// D[4 r + (l >> 4)][l & 15] in register r (probed, and held by every case of tests/test_gpu_ridge_matrix.py: not the 4 (l >> 4) + r of the fp32 16x16x4 form).  One workgroup walks its own sample range in chunks of 32: ALL features of a chunk are
 // generated once into LDS ([sample][feature], row stride == 16 (mod 32) doubles: the 8-byte operand reads of the two
 // 32-lane halves hit disjoint banks), then the 4 waves update the upper-triangle 16 x 16 tiles they own (round-robin,
 // <= 17 accumulator tiles per wave, registers for the whole run).  The FMA kernel above re-generates a 64-column block

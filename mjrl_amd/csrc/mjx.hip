@@ -327,6 +327,13 @@ int mjx_bl_features_f32(const double* obs, const int32_t* tpos, int64_t N, int n
   return MJX_OK;
 }
 
+int mjx_bl_gram_route(int kind, int n, int64_t N, int32_t* out6) {
+  if (!out6 || kind < 0 || kind > 2 || n <= 0 || n > 4096 || N <= 0) return fail(MJX_ERR_ARG, "bad arguments");     // (get_feat_table's limits)
+  const GramRoute r = gram_route(bl_num_features(kind, n), n, N, env_flag("MJX_GRAM_FMA", false));
+  out6[0] = r.arm; out6[1] = r.Z; out6[2] = r.nblk; out6[3] = r.gx; out6[4] = r.blk; out6[5] = (int32_t)r.lds;
+  return MJX_OK;
+}
+
 int mjx_bl_gram(int kind, const double* obs, const int32_t* tpos, const double* y, int64_t N, int n, double* G, void* stream) {
   if (!obs || !tpos || !y || !G || N <= 0) return fail(MJX_ERR_ARG, "bad arguments");
   FeatTableCache* ft;
@@ -336,7 +343,7 @@ int mjx_bl_gram(int kind, const double* obs, const int32_t* tpos, const double* 
   const size_t pbytes = (size_t)r.Z * FA * FA * sizeof(double);
   double* part = nullptr;
   if (int rc = dev_scratch(SITE_GRAM, stream, pbytes, &part)) return rc;
-  const bool blk = r.arm == GRAM_MFMA_BLK;                 // that arm writes every partial it owns and may take LDS beyond the default
+  const bool blk = r.arm == GRAM_MFMA_BLK;                 // that arm writes every partial it owns (tests/test_gpu_ridge_matrix.py: after a call with y x 1e6) and may take LDS beyond the default
   if (!blk) HIPCHK(hipMemsetAsync(part, 0, pbytes, (hipStream_t)stream));
   if (!blk && r.lds > LDS_DEFAULT) return fail(MJX_ERR_UNSUPPORTED, "obs dim too large for the Gram kernel's LDS staging");
   auto launch = [&](auto kern, dim3 grid, auto... lead) {

@@ -1,4 +1,4 @@
-"""The routes of the baseline, minibatch, dynamics and planning entries, host side (no GPU): mjx_mlp_fit_route,
+"""The routes of the baseline, minibatch, dynamics and planning entries, host side (no GPU): mjx_bl_gram_route, mjx_mlp_fit_route,
 mjx_policy_fit_route, mjx_dyn_fit_route and mjx_plan_route answer "which kernel serves this shape" by arithmetic alone, from the
 tables of csrc/fit_host.h and csrc/model_host.h.  Every boundary below was read off the build before those headers existed
 (the same conditions, then inline in mjx_mlp_fit_adam / mjx_policy_minibatch_adam), not off the tables."""
@@ -162,10 +162,124 @@ def test_dyn_fit_and_plan_routes_still_answer(default_switches):
     assert plan([8, 64, 64, 64, 6], 2) == 0 and plan([8, 64, 64, 6], 3) == ERR_ARG and plan([8], 2) == ERR_ARG
 
 
+GRAM_MFMA, GRAM_BLK, GRAM_FMA = 0, 1, 2              # out6[0] of mjx_bl_gram_route
+
+
+def _gram(kind, n, N=1000):
+    out = (ctypes.c_int32 * 6)()
+    rc = _lib().mjx_bl_gram_route(kind, n, N, out)
+    assert rc == 0, rc
+    return [int(x) for x in out]
+
+
+def _feats(kind, n):
+    return n + 4 if kind == 0 else n + 5 if kind == 1 else n + n * (n + 1) // 2 + 5
+
+
+def test_gram_route_arms_by_shape(default_switches):
+    """csrc/fit_host.h gram_route, read off its conditions: the one-workgroup matrix-core kernel while the augmented features fill at
+    most 11 tiles of 16 (176 columns) and 32 n observations fit its 3 x 256 staging slots (n <= 24); the 128 x 128 block kernel while
+    they fit its 8 x 256 slots (n <= 64); the FMA kernel beyond, and for every shape under MJX_GRAM_FMA=1 (read per call).
+    out6 = {arm, Z, blocks a side, grid x, features a side of a reduce tile, bytes of LDS}."""
+    default_switches.delenv("MJX_GRAM_FMA", raising=False)
+    assert _feats(2, 17) + 1 == 176 and _feats(2, 18) + 1 == 195
+    for kind in (0, 1, 2):
+        for n in range(1, 140):
+            FA = _feats(kind, n) + 1
+            want = GRAM_MFMA if FA <= 176 and n <= 24 else GRAM_BLK if n <= 64 else GRAM_FMA
+            r = _gram(kind, n)
+            assert r[0] == want, (kind, n, r)
+            if want == GRAM_MFMA:
+                assert r[2:5] == [0, 1, 16], (kind, n, r)
+            elif want == GRAM_BLK:
+                nb = -(-FA // 128)
+                assert r[2:5] == [nb, nb * (nb + 1) // 2, 128], (kind, n, r)
+            else:
+                nbt = -(-FA // 64)
+                assert r[2:5] == [nbt, nbt * (nbt + 1) // 2, 64], (kind, n, r)
+    # the landmarks by name: quadratic 17 / 18, linear and MLP features 24 / 25 and 64 / 65
+    assert _gram(2, 17)[0] == GRAM_MFMA and _gram(2, 18)[0] == GRAM_BLK
+    for kind in (0, 1):
+        assert _gram(kind, 24)[0] == GRAM_MFMA and _gram(kind, 25)[0] == GRAM_BLK
+    for kind in (0, 1, 2):
+        assert _gram(kind, 64)[0] == GRAM_BLK and _gram(kind, 65)[0] == GRAM_FMA
+    assert _gram(2, 64)[2:4] == [17, 153] and _gram(2, 18)[2:4] == [2, 3] and _gram(2, 21)[2:4] == [3, 6]      # 2150, 195, 258 columns
+    assert _gram(2, 65)[2:4] == [35, 630]
+    default_switches.setenv("MJX_GRAM_FMA", "1")
+    for kind in (0, 1, 2):
+        for n in (1, 3, 17, 18, 24, 25, 64, 65):
+            assert _gram(kind, n)[0] == GRAM_FMA and _gram(kind, n)[4] == 64, (kind, n)
+    default_switches.setenv("MJX_GRAM_FMA", "0")
+    assert _gram(2, 17)[0] == GRAM_MFMA
+    default_switches.delenv("MJX_GRAM_FMA")
+    assert _gram(2, 17)[0] == GRAM_MFMA                      # read per call
+
+
+def test_gram_route_sample_ranges(default_switches):
+    """Z = clamp(ceil(N / per), 1, cap): 2048 rows a range and at most 512 on the one-workgroup arm; 2048 and ceil(768 / block pairs)
+    on the block arm; 4096 and ceil(2048 / tile pairs) on the FMA arm"""
+    mp = default_switches
+    mp.delenv("MJX_GRAM_FMA", raising=False)
+
+    def z(per, cap, N):
+        return max(1, min(cap, -(-N // per)))
+
+    Ns = (1, 2047, 2048, 2049, 4096, 4097, 8193, 2048 * 255 + 1, 2048 * 256, 2048 * 256 + 1, 2048 * 512, 2048 * 512 + 1, 4096 * 683 + 1,
+          2000000, 10 ** 9, 2 ** 40)
+    for N in Ns:
+        assert _gram(2, 17, N)[1] == z(2048, 512, N) and _gram(1, 1, N)[1] == z(2048, 512, N), N
+        assert _gram(1, 25, N)[1] == z(2048, 768, N), N                     # 31 columns: one diagonal block
+        assert _gram(2, 18, N)[1] == z(2048, 256, N), N                     # 3 block pairs
+        assert _gram(2, 21, N)[1] == z(2048, 128, N), N                     # 6 block pairs
+        assert _gram(2, 64, N)[1] == z(2048, 6, N), N                       # 153 block pairs: ceil(768 / 153) = 6
+        assert _gram(1, 65, N)[1] == z(4096, 683, N), N                     # 71 columns: 3 tile pairs, ceil(2048 / 3) = 683
+        assert _gram(2, 65, N)[1] == z(4096, 4, N), N                       # 630 tile pairs
+    assert _gram(2, 17, 2048)[1] == 1 and _gram(2, 17, 2049)[1] == 2 and _gram(2, 17, 4097)[1] == 3
+    assert _gram(1, 1, 2000000)[1] == 512 and _gram(2, 18, 530000)[1] == 256
+    mp.setenv("MJX_GRAM_FMA", "1")
+    for N in Ns:
+        assert _gram(2, 3, N)[1] == z(4096, 2048, N), N                     # 15 columns: one tile pair
+        assert _gram(2, 17, N)[1] == z(4096, 342, N), N                     # 176 columns: 3 tiles a side, 6 pairs
+        assert _gram(1, 59, N)[1] == z(4096, 683, N), N                     # 65 columns: 2 tiles a side, 3 pairs
+    assert _gram(1, 58, 1)[2:4] == [1, 1] and _gram(1, 59, 1)[2:4] == [2, 3]
+
+
+def test_gram_route_lds_bytes_at_the_ends_of_each_arm(default_switches):
+    """one workgroup: 32 extended vectors of n + 7 doubles and 32 feature rows of 16 (T | 1); blocks: the vectors and two 32 x 144
+    feature blocks; FMA: 32 x n observations and two 32 x 65 tiles (its 32 tau values are static)"""
+    mp = default_switches
+    mp.delenv("MJX_GRAM_FMA", raising=False)
+    assert _gram(0, 1)[5] == 8 * (32 * 8 + 32 * 16 * 1)                     # 6 columns: one tile                      6 144
+    assert _gram(2, 1)[5] == 8 * (32 * 8 + 32 * 16 * 1) == 6144
+    assert _gram(2, 4)[5] == 8 * (32 * 11 + 32 * 16 * 3)                    # 20 columns: 2 tiles, stride 3 x 16
+    assert _gram(2, 17)[5] == 8 * (32 * 24 + 32 * 16 * 11) == 51200         # the arm's last quadratic shape
+    assert _gram(1, 24)[5] == 8 * (32 * 31 + 32 * 16 * 3) == 20224          # ... and last linear one
+    assert _gram(1, 25)[5] == 8 * (32 * 32 + 2 * 32 * 144) == 81920         # first and last shape of the block arm
+    assert _gram(2, 18)[5] == 8 * (32 * 25 + 2 * 32 * 144) == 80128
+    assert _gram(2, 64)[5] == 8 * (32 * 71 + 2 * 32 * 144) == 91904
+    assert _gram(1, 65)[5] == 8 * (32 * 65 + 2 * 32 * 65) == 49920          # first shape only the FMA arm serves
+    assert _gram(1, 126)[5] == 65536                                        # the last it serves: 64 KiB exactly
+    assert _gram(1, 127)[5] == 65792                                        # mjx_bl_gram refuses this one
+    assert _gram(2, 65)[5] == 49920                                         # (whatever the feature count)
+    mp.setenv("MJX_GRAM_FMA", "1")
+    assert _gram(2, 1)[5] == 8 * (32 * 1 + 2 * 32 * 65) == 33536
+    assert _gram(2, 17)[5] == 8 * (32 * 17 + 2 * 32 * 65) == 37632
+
+
+def test_gram_route_refuses_bad_arguments(default_switches):
+    lib = _lib()
+    out6 = (ctypes.c_int32 * 6)()
+    assert lib.mjx_bl_gram_route(2, 17, 1000, out6) == 0
+    assert lib.mjx_bl_gram_route(2, 17, 1000, None) == ERR_ARG
+    for kind, n, N in ((-1, 17, 1000), (3, 17, 1000), (2, 0, 1000), (2, -5, 1000), (2, 4097, 1000), (2, 17, 0), (2, 17, -1)):
+        assert lib.mjx_bl_gram_route(kind, n, N, out6) == ERR_ARG, (kind, n, N)
+
+
 def test_route_entries_refuse_bad_arguments_without_device_work(default_switches):
     lib = _lib()
     before = (ctypes.c_int64 * 2)()
     lib.mjx_process_state(before)
+    assert lib.mjx_bl_gram_route(2, 17, 1000, (ctypes.c_int32 * 6)()) == 0 and lib.mjx_bl_gram_route(7, 17, 1000, None) == ERR_ARG
     out6, out2, hid = (ctypes.c_int32 * 6)(), (ctypes.c_int32 * 2)(), _ints((128, 128))
     assert lib.mjx_mlp_fit_route(5, hid, 2, 64, 192, 2, None) == ERR_ARG
     assert lib.mjx_mlp_fit_route(5, None, 2, 64, 192, 2, out6) == ERR_ARG
