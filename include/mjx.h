@@ -467,6 +467,27 @@ int mjx_dyn_fit_ensemble(const float* x, int64_t x_stride, const float* y, int64
                          const int* sizes, int n_sizes, const float* in_tr, const float* out_tr, int target_mode, int act,
                          float* params, float* m, float* v, const int64_t* step0, const int32_t* idx, int64_t steps,
                          int batch, float lr, float wd, float* loss_out, int* route_out, void* stream);
+/* Which route mjx_reward_fit_ensemble takes for nets of `sizes` at minibatch `batch`: 1 = the ensemble kernel's instance for
+ * ragged widths and the affine head (csrc/dyn_fit_ens.h): exactly two hidden layers, each width 1 .. 256, batch <= 64,
+ * d_in <= 128, d_out <= 64; 0 = member by member on the routes of mjx_dyn_fit_adam; < 0 = bad sizes or batch <= 0.
+ * Arithmetic only: no device work and no runtime call (MJX_REWARD_FIT_ENS does not change the answer). */
+int mjx_reward_fit_route(const int* sizes, int n_sizes, int batch);
+/* The LDS layout of the ensemble kernel (both instances) for a served shape, read-only: info[0] = dynamic LDS bytes of a
+ * workgroup (the [unit][sample] tiles of H1, H2 and Z3 with the unit rows padded to 32, and the gathered inputs where they
+ * fit beside them), info[1] = 1 where the gathered inputs are in LDS (0: per-member scratch), info[2] = the tiles' row stride
+ * in floats, info[3] = floats of the gathered-input tile.  MJX_ERR_ARG for a shape mjx_reward_fit_route does not answer 1
+ * for.  Arithmetic only. */
+int mjx_dyn_fit_ens_layout(const int* sizes, int n_sizes, int batch, int64_t* info);
+/* The reward fits of K members at once (the driver's `model.fit_reward(...)`, run_model_accel_npg.py:170-178): mjx_dyn_fit_adam
+ * with target_mode 0 -- yhat = z (out_scale + 1e-8) + out_shift against raw y -- for K nets of one shape.  Arguments,
+ * strides (member k reads x + k * x_stride: its own [s, a, s'] rows; y_stride 0: one reward column for all), step0 (a HOST
+ * array of K counts), route_out, steps == 0 and scratch as mjx_dyn_fit_ensemble.  *route_out receives the route taken
+ * (mjx_reward_fit_route; MJX_REWARD_FIT_ENS=0, read per call, forces 0).  On route 0 the call is exactly K
+ * mjx_dyn_fit_adam(..., target_mode 0, ...) calls in member order.  Bad arguments return MJX_ERR_ARG and touch nothing. */
+int mjx_reward_fit_ensemble(const float* x, int64_t x_stride, const float* y, int64_t y_stride, int64_t N, int K,
+                            const int* sizes, int n_sizes, const float* in_tr, const float* out_tr, int act, float* params,
+                            float* m, float* v, const int64_t* step0, const int32_t* idx, int64_t steps, int batch, float lr,
+                            float wd, float* loss_out, int* route_out, void* stream);
 /* ensemble-disagreement truncation (model_accel_npg.py:137-155): pred = K x rows x n model predictions, s_next the
  * rows' next states; err_out[r] = max_k mean_j (s_next - pred)^2, NaN if any member's is NaN (np.maximum);
  * segment g = rows [seg_off[g], seg_off[g+1]) (one path); first_out[g] = the first row of the segment whose error

@@ -99,6 +99,11 @@ PROTOTYPES = {
     "mjx_dyn_fit_ensemble": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int, ctypes.POINTER(c_int), c_int, c_void_p, c_void_p,
                                      c_int, c_int, c_void_p, c_void_p, c_void_p, ctypes.POINTER(c_int64), c_void_p, c_int64, c_int, c_float,
                                      c_float, c_void_p, ctypes.POINTER(c_int), c_void_p]),
+    "mjx_reward_fit_route": (c_int, [ctypes.POINTER(c_int), c_int, c_int]),
+    "mjx_dyn_fit_ens_layout": (c_int, [ctypes.POINTER(c_int), c_int, c_int, ctypes.POINTER(c_int64)]),
+    "mjx_reward_fit_ensemble": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int, ctypes.POINTER(c_int), c_int, c_void_p, c_void_p,
+                                        c_int, c_void_p, c_void_p, c_void_p, ctypes.POINTER(c_int64), c_void_p, c_int64, c_int, c_float,
+                                        c_float, c_void_p, ctypes.POINTER(c_int), c_void_p]),
     "mjx_dyn_pred_error": (c_int, [c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p, c_int, c_double, c_void_p, c_void_p, c_void_p]),
     "mjx_plan_route": (c_int, [ctypes.POINTER(c_int), c_int, c_int]),
     "mjx_plan_rollout": (c_int, [c_void_p, c_int64, c_int64, c_int, c_int, c_void_p, ctypes.POINTER(c_int), c_int, c_void_p, c_void_p, c_int,

@@ -14,7 +14,7 @@ import torch
 from ..._lib import check, load, ptr
 from ...utils import process_samples
 from ..npg_cg import NPG
-from .nn_dynamics import WorldModel, _device, _stream, ensemble_forward
+from .nn_dynamics import WorldModel, _device, _stream, ensemble_forward, ensemble_path_rewards
 from .sampling import _as_env, draw_rollout_noise, rollout_models
 
 
@@ -112,9 +112,13 @@ class ModelAccelNPG(NPG):
         obs_all, act_all = rollout_models(self.learned_model, self.policy, np.array(init_states), horizon, noise)
         paths = []
         obs = None
+        # every member's learned rewards in one batched call (one upload, two launches, one read-back) when all members learn them
+        rew_all = ensemble_path_rewards(self.learned_model, obs_all, act_all) if all(mdl.learn_reward for mdl in self.learned_model) else None
         for k, model in enumerate(self.learned_model):
             rollouts = dict(observations=obs_all[k], actions=act_all[k])
-            if model.learn_reward:
+            if rew_all is not None:
+                rollouts['rewards'] = rew_all[k]
+            elif model.learn_reward:
                 model.compute_path_rewards(rollouts)
             else:
                 rollouts = reward_function(rollouts)

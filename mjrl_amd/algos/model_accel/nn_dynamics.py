@@ -12,7 +12,11 @@ global torch stream are the reference's) and transforms.  What runs where:
   phase otherwise).  The optimiser state (``dynamics_opt`` / ``reward_opt``) is torch.optim.Adam's -- step count and
   both moments -- kept as flat fp32 vectors;
 * :func:`fit_ensemble`: the driver's ``for model in ensemble: model.fit_dynamics(...)`` with every member's Adam chain in one
-  persistent launch (``mjx_dyn_fit_ensemble``, a workgroup per member on fp32 MFMAs for two hidden layers up to 256 wide).
+  persistent launch (``mjx_dyn_fit_ensemble``, a workgroup per member on fp32 MFMAs for two hidden layers up to 256 wide);
+* :func:`fit_reward_ensemble`: the same for the K reward nets (``mjx_reward_fit_ensemble``: any two hidden widths up to 256, the
+  loss through the output affine); :func:`fit_world_models`: the driver's interleaved loop (dynamics, reward, next member) as
+  two such calls; :func:`ensemble_path_rewards`: every member's ``compute_path_rewards`` in one upload, two launches and one
+  read-back.
 
 The module parameters stay ordinary torch tensors (CPU by default, as in the reference): ``get_params`` /
 ``set_params`` / ``to`` / ``is_cuda`` / pickling behave as the reference's.  There is no CPU path: without a GPU the
@@ -88,10 +92,13 @@ def _flags(net):
 
 def ensemble_forward(nets, x, dev=None):
     """K nets of one shape over the same rows x (rows x d_in, the concatenated raw input) in one launch -> K x rows x d_out
-    (device tensor).  Each net's own activation, transforms and flags apply (one launch per distinct (activation, flags))."""
+    (device tensor).  Each net's own activation, transforms and flags apply (one launch per distinct (activation, flags)).
+    x of shape K x rows x d_in: member k reads its own rows x[k] (a per-member x_stride)."""
     dev = dev or _device()
     x = _f32(x, dev)
-    rows = x.shape[0]
+    own = x.dim() == 3
+    assert not own or x.shape[0] == len(nets), "per-member rows: one block per net"
+    rows = x.shape[-2]
     sizes = nets[0].layer_sizes
     out = torch.empty((len(nets), rows, sizes[-1]), dtype=torch.float32, device=dev)
     groups = {}
@@ -103,7 +110,8 @@ def ensemble_forward(nets, x, dev=None):
         P = torch.stack([_flat_params(nets[i], dev) for i in ids])
         tr = torch.stack([_packed_transforms(nets[i], dev) for i in ids])
         o = out if len(ids) == len(nets) else torch.empty((len(ids), rows, sizes[-1]), dtype=torch.float32, device=dev)
-        check(lib.mjx_dyn_forward(ptr(x), 0, rows, len(ids), _ints(sizes), len(sizes), ptr(P), ptr(tr), act, flags, ptr(o),
+        xg = x if not own or len(ids) == len(nets) else x[ids].contiguous()
+        check(lib.mjx_dyn_forward(ptr(xg), rows * sizes[0] if own else 0, rows, len(ids), _ints(sizes), len(sizes), ptr(P), ptr(tr), act, flags, ptr(o),
                                   _stream(dev)))
         if o is not out:
             out[ids] = o
@@ -342,17 +350,18 @@ def _same_fit(models):
     return True
 
 
-def fit_ensemble(models, s, a, sp, fit_mb_size, fit_epochs, max_steps=1e4, set_transformations=True):
+def fit_ensemble(models, s, a, sp, fit_mb_size, fit_epochs, max_steps=1e4, set_transformations=True, _draws=None):
     """``[mdl.fit_dynamics(s, a, sp, fit_mb_size, fit_epochs, max_steps, set_transformations) for mdl in models]`` (the
     driver's loop, run_model_accel_npg.py:168-177) with every member's Adam chain in ONE launch (``mjx_dyn_fit_ensemble``:
     a workgroup per member; shapes it does not serve run member by member inside the same call).  Per member the same
     transform expressions, the same draws from NumPy's global stream in the same order, the same optimiser state carried
     and advanced, the parameters written back and ``_generation`` bumped.  -> a list of K epoch-loss lists.  Members that
-    differ in layer sizes, activation, ``residual`` or optimiser settings run the plain loop."""
+    differ in layer sizes, activation, ``residual`` or optimiser settings run the plain loop.  (_draws: the index draws made
+    ahead by :func:`fit_world_models`.)"""
     models = list(models)
     if not models:
         return []
-    if not _same_fit(models):
+    if _draws is None and not _same_fit(models):
         return [mdl.fit_dynamics(s, a, sp, fit_mb_size, fit_epochs, max_steps=max_steps, set_transformations=set_transformations)
                 for mdl in models]
     assert type(s) == type(a) == type(sp)
@@ -374,7 +383,7 @@ def fit_ensemble(models, s, a, sp, fit_mb_size, fit_epochs, max_steps=1e4, set_t
     dev = _device()
     K, N = len(models), int(sp.shape[0])
     nets, opts = [mdl.dynamics_net for mdl in models], [mdl.dynamics_opt for mdl in models]
-    idx, num_steps, ran = ensemble_fit_indices(K, N, fit_mb_size, fit_epochs, max_steps)
+    idx, num_steps, ran = _draws if _draws is not None else ensemble_fit_indices(K, N, fit_mb_size, fit_epochs, max_steps)
     steps = ran * num_steps
     if steps == 0:
         return [epoch_means([], num_steps, ran) for _ in models]
@@ -408,6 +417,167 @@ def fit_ensemble(models, s, a, sp, fit_mb_size, fit_epochs, max_steps=1e4, set_t
             net._generation = getattr(net, "_generation", 0) + 1     # (an MPCPolicy repacks its device copy)
             out.append(epoch_means(losses[i], num_steps, ran))
     return out
+
+
+def _same_reward_fit(models):
+    """:func:`_same_fit`'s rule for the reward nets: every member learns its reward, one shape, activation and optimiser setting"""
+    if not all(mdl.learn_reward for mdl in models):
+        return False
+    n0, g0 = models[0].reward_net, models[0].reward_opt.param_groups[0]
+    for mdl in models[1:]:
+        n, g = mdl.reward_net, mdl.reward_opt.param_groups[0]
+        if (tuple(n.layer_sizes) != tuple(n0.layer_sizes) or _act_code(n) != _act_code(n0) or g['lr'] != g0['lr']
+                or g['weight_decay'] != g0['weight_decay']):
+            return False
+    return True
+
+
+def _write_back(nets, opts, P, m, v, steps, losses, num_steps, ran):
+    out = []
+    with torch.no_grad():
+        for i, (net, opt) in enumerate(zip(nets, opts)):
+            opt.exp_avg.copy_(m[i]); opt.exp_avg_sq.copy_(v[i])
+            opt.step_count += steps
+            k = 0
+            for p in net.parameters():
+                p.data.copy_(P[i, k:k + p.numel()].view_as(p))
+                k += p.numel()
+            net._generation = getattr(net, "_generation", 0) + 1
+            out.append(epoch_means(losses[i], num_steps, ran))
+    return out
+
+
+def fit_reward_ensemble(models, s, a, r, fit_mb_size, fit_epochs, max_steps=1e4, set_transformations=True, _draws=None):
+    """``[mdl.fit_reward(s, a, r, fit_mb_size, fit_epochs, max_steps, set_transformations) for mdl in models]`` with every
+    member's Adam chain in ONE launch (``mjx_reward_fit_ensemble``: a workgroup per member; shapes it does not serve run member by
+    member inside the same call).  Per member the same transform expressions on the member's device, s' = the bits of
+    ``mdl.dynamics_net.forward(s, a)`` (one :func:`ensemble_forward` over the K dynamics nets on the shared rows), the same draws
+    from NumPy's global stream in member order, ``reward_opt`` carried and advanced, the parameters written back and
+    ``_generation`` bumped.  -> a list of K epoch-loss lists.  Members that differ in layer sizes, activation or optimiser
+    settings, or any member with ``learn_reward=False``, run the plain loop.  (_draws: as in :func:`fit_ensemble`.)"""
+    models = list(models)
+    if not models:
+        return []
+    if _draws is None and not _same_reward_fit(models):
+        return [mdl.fit_reward(s, a, r, fit_mb_size, fit_epochs, max_steps=max_steps, set_transformations=set_transformations)
+                for mdl in models]
+    assert type(s) == type(a) == type(r)
+    assert len(r.shape) == 2 and r.shape[1] == 1
+    assert s.shape[0] == a.shape[0] == r.shape[0]
+    if type(s) == np.ndarray:
+        s = torch.from_numpy(s).float()
+        a = torch.from_numpy(a).float()
+        r = torch.from_numpy(r).float()
+    if set_transformations:
+        for mdl in models:
+            # the reference's transform expressions, on each member's device (nn_dynamics.py:135-139), as fit_reward forms them
+            s_, a_, r_ = s.to(mdl.device), a.to(mdl.device), r.to(mdl.device)
+            s_shift, a_shift = torch.mean(s_, dim=0), torch.mean(a_, dim=0)
+            s_scale, a_scale = torch.mean(torch.abs(s_ - s_shift), dim=0), torch.mean(torch.abs(a_ - a_shift), dim=0)
+            r_shift, r_scale = torch.mean(r_, dim=0), torch.mean(torch.abs(r_ - r_shift), dim=0)
+            mdl.reward_net.set_transformations(s_shift, s_scale, a_shift, a_scale, r_shift, r_scale)
+    dev = _device()
+    K, N = len(models), int(r.shape[0])
+    nets, opts = [mdl.reward_net for mdl in models], [mdl.reward_opt for mdl in models]
+    idx, num_steps, ran = _draws if _draws is not None else ensemble_fit_indices(K, N, fit_mb_size, fit_epochs, max_steps)
+    steps = ran * num_steps
+    if steps == 0:
+        return [epoch_means([], num_steps, ran) for _ in models]
+    sizes = nets[0].layer_sizes
+    din = sizes[0]
+    sa = _f32(torch.cat([s, a], -1), dev)
+    # s'_k = dynamics_net_k.forward(s, a): k_dyn_forward computes each row by itself, so the batched launch gives the same bits
+    dyn = [mdl.dynamics_net for mdl in models]
+    if len({tuple(d.layer_sizes) for d in dyn}) == 1:
+        sp = ensemble_forward(dyn, sa, dev)
+    else:
+        sp = torch.stack([ensemble_forward([d], sa, dev)[0] for d in dyn])
+    X = torch.cat([sa.unsqueeze(0).expand(K, -1, -1), sp], -1).contiguous()          # K x N x (2 n + m)
+    Y = _f32(r.reshape(N, -1), dev)
+    P = torch.stack([_flat_params(net, dev) for net in nets])
+    tr = torch.stack([_packed_transforms(net, dev) for net in nets])
+    in_tr, out_tr = tr[:, :2 * din].contiguous(), tr[:, 2 * din:].contiguous()
+    state = [opt._state(dev) for opt in opts]
+    m, v = torch.stack([st[0] for st in state]), torch.stack([st[1] for st in state])
+    g = opts[0].param_groups[0]
+    step0 = (ctypes.c_int64 * K)(*[int(opt.step_count) for opt in opts])
+    idx_d = torch.from_numpy(np.ascontiguousarray(idx)).to(dev)
+    loss = torch.empty((K, steps), dtype=torch.float32, device=dev)
+    route = ctypes.c_int(-1)
+    check(load().mjx_reward_fit_ensemble(ptr(X), N * din, ptr(Y), 0, N, K, _ints(sizes), len(sizes), ptr(in_tr), ptr(out_tr),
+                                         _act_code(nets[0]), ptr(P), ptr(m), ptr(v), step0, ptr(idx_d), steps, int(fit_mb_size),
+                                         float(g['lr']), float(g['weight_decay']), ptr(loss), ctypes.byref(route), _stream(dev)))
+    return _write_back(nets, opts, P, m, v, steps, loss.cpu().numpy(), num_steps, ran)
+
+
+def world_model_fit_indices(K, num_samples, batch_size, epochs, max_steps=1e10, learn_reward=True):
+    """the host side of the driver's loop (run_model_accel_npg.py:170-178): member 0's dynamics permutations from NumPy's global
+    stream, member 0's reward permutations, member 1's dynamics permutations, ... -> (dynamics draws, reward draws), each as
+    :func:`ensemble_fit_indices` returns them; with learn_reward False: (``ensemble_fit_indices(...)``, None)"""
+    if not learn_reward:
+        return ensemble_fit_indices(K, num_samples, batch_size, epochs, max_steps), None
+    dyn, rew = [], []
+    for _ in range(K):
+        dyn.append(fit_permutations(num_samples, batch_size, epochs, max_steps))
+        rew.append(fit_permutations(num_samples, batch_size, epochs, max_steps))
+    if not dyn:
+        none = (np.zeros((0, 0), np.int32), int(num_samples // batch_size), 0)
+        return none, none
+    return tuple((np.stack([d[0] for d in draws]), draws[0][1], draws[0][2]) for draws in (dyn, rew))
+
+
+def fit_world_models(models, s, a, sp, r, fit_mb_size, fit_epochs, max_steps=1e4, set_transformations=True):
+    """the driver's fit loop (run_model_accel_npg.py:170-178, without the logging) --
+    ``for mdl in models: mdl.fit_dynamics(s, a, sp, ...); mdl.fit_reward(s, a, r, ...)`` -- as two launches: all index draws
+    first, in the driver's order (:func:`world_model_fit_indices`), then the dynamics ensemble fit, then the reward ensemble fit
+    (it reads the fitted dynamics; stream order gives it that).  -> (K dynamics epoch-loss lists, K reward epoch-loss lists or
+    None).  With no learned rewards it is :func:`fit_ensemble`; members that cannot share a call run the driver's loop."""
+    models = list(models)
+    if not models:
+        return [], []
+    if not any(mdl.learn_reward for mdl in models):
+        return fit_ensemble(models, s, a, sp, fit_mb_size, fit_epochs, max_steps=max_steps, set_transformations=set_transformations), None
+    if not (_same_fit(models) and _same_reward_fit(models)):
+        dl, rl = [], []
+        for mdl in models:
+            dl.append(mdl.fit_dynamics(s, a, sp, fit_mb_size, fit_epochs, max_steps=max_steps, set_transformations=set_transformations))
+            rl.append(mdl.fit_reward(s, a, r, fit_mb_size, fit_epochs, max_steps=max_steps, set_transformations=set_transformations)
+                      if mdl.learn_reward else None)
+        return dl, rl
+    dyn_draws, rew_draws = world_model_fit_indices(len(models), int(sp.shape[0]), fit_mb_size, fit_epochs, max_steps, True)
+    dl = fit_ensemble(models, s, a, sp, fit_mb_size, fit_epochs, max_steps=max_steps, set_transformations=set_transformations,
+                      _draws=dyn_draws)
+    rl = fit_reward_ensemble(models, s, a, r, fit_mb_size, fit_epochs, max_steps=max_steps, set_transformations=set_transformations,
+                             _draws=rew_draws)
+    return dl, rl
+
+
+def ensemble_path_rewards(models, observations, actions):
+    """``mdl.compute_path_rewards(dict(observations=observations[k], actions=actions[k]))`` for every member k: observations
+    (K, N, H, n) and actions (K, N, H, m), as arrays or per-member lists -> rewards (K, N, H) float32.  One upload, one
+    ``mjx_dyn_forward`` launch per (activation, flags) group over the K dynamics nets with per-member rows, one over the K
+    reward nets, one read-back.  k_dyn_forward computes each row by itself: the result is the K single calls' bit for bit."""
+    models = list(models)
+    assert models and all(mdl.learn_reward for mdl in models), "every member must learn its reward"
+    dev = _device()
+    obs = np.ascontiguousarray(np.stack([np.asarray(o) for o in observations]) if isinstance(observations, (list, tuple)) else observations)
+    act = np.ascontiguousarray(np.stack([np.asarray(o) for o in actions]) if isinstance(actions, (list, tuple)) else actions)
+    K, N, H, n = obs.shape
+    m = act.shape[-1]
+    assert K == len(models) and act.shape[:3] == (K, N, H)
+    if len({tuple(mdl.dynamics_net.layer_sizes) for mdl in models}) > 1 or len({tuple(mdl.reward_net.layer_sizes) for mdl in models}) > 1:
+        out = []                                             # members of different shapes: one by one
+        for k, mdl in enumerate(models):
+            paths = dict(observations=obs[k], actions=act[k])
+            mdl.compute_path_rewards(paths)
+            out.append(paths['rewards'])
+        return np.stack(out)
+    # (compute_path_rewards: torch.from_numpy(s).float() on the host, then the copy)
+    sa = np.concatenate([obs.reshape(K, N * H, n), act.reshape(K, N * H, m)], -1)
+    sa = _f32(torch.from_numpy(sa).float(), dev)
+    sp = ensemble_forward([mdl.dynamics_net for mdl in models], sa, dev)
+    r = ensemble_forward([mdl.reward_net for mdl in models], torch.cat([sa, sp], -1), dev)
+    return r.to('cpu').data.numpy().reshape(K, N, H)
 
 
 class DynamicsNet(nn.Module):

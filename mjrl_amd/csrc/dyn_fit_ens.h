@@ -1,4 +1,5 @@
-// dyn_fit_ens.h -- k_dyn_fit_ens: the minibatch-Adam fit of a whole dynamics ensemble in ONE persistent launch.
+// dyn_fit_ens.h -- k_dyn_fit_ens: the minibatch-Adam fit of a whole ensemble of dynamics nets, or of its reward nets, in ONE
+// persistent launch.
 //
 // The reference's driver fits its K models one after the other, every outer iteration (run_model_accel_npg.py:168-177:
 // `for model in ensemble: model.fit_dynamics(...)`), at hidden_size (256, 256) in both configs it ships -- the shape that
@@ -15,14 +16,28 @@
 //                           160 KiB of LDS nor the 512 KiB register file holds W2 beside anything else).  A workgroup stays on one
 //                           CU, so its weights come back from that CU's L1 / the XCD's L2.
 //   activations             LDS, as [unit][sample] tiles with the sample dimension padded to the MFMA tile (Bp = 32 or 64, row
-//                           stride Bp + 4): H1, H2, the output block Z3 (rows padded to 32) and the gathered inputs X (rows
-//                           padded to 8).  (256 + 256 + 64) x 68 x 4 B = 153 KiB is the most H1 + H2 + Z3 take; when X no longer
+//                           stride Bp + 4): H1, H2 (unit rows padded to 32: nothing for the aligned widths), the output block Z3
+//                           (rows padded to 32) and the gathered inputs X (rows padded to 8).  (256 + 256 + 64) x 68 x 4 B = 153 KiB is the most H1 + H2 + Z3 take; when X no longer
 //                           fits beside them (B > 32 with d_in + h1 + h2 + d_out near the limits) X goes to a per-member global
 //                           scratch tile instead, the only operand it changes.
 //   deltas                  in place: dMSE/dz3 over Z3; delta2 and delta1 are formed in registers (two 32 x 32 tiles a wave),
 //                           held there while the weight gradient that still needs the activations runs, then written over H2 / H1.
 // Padded sample columns (>= B) carry x = 0 forward and delta = 0 backward (the head writes exact zeros there), so they add
 // exactly 0 to every gradient sum; padded rows of Z3 and X are zeros, and weight rows beyond a layer's width are never read.
+//
+// Two instances.  k_dyn_fit_ens<false>: the dynamics nets -- hidden widths multiples of 32, targets as k_dyn_prep forms them
+// (modes 1 / 2), plain MSE head; its arithmetic is the kernel's from before the second instance existed, bit for bit.
+// k_dyn_fit_ens<true> (RAG): any two hidden widths 1 .. 256 and the affine head of target mode 0, the RewardNet fit
+// (mjx_reward_fit_ensemble; the reference's reward nets are (100, 100)).  What it adds:
+//   ragged widths   the padded unit rows of H1 / H2 hold exact zeros forward (dfe_forward writes zeros for rows >= dj).  Backward
+//                   dfe_delta covers the partial last tile, reads the weight columns >= di as zeros AND sets the padded rows of
+//                   its result to zero outright -- tanh'(0) = 1, so the activation derivative would pass a stray product on --
+//                   and dfe_delta_store writes those zeros over the padded rows.  They then add exactly 0 to every later
+//                   delta, weight gradient and bias sum (the bias sums run over the real units only).  The four-weight loads
+//                   of dfe_forward serve di % 4 == 0 with the groups at and beyond di masked (no load reaches past its row);
+//                   other widths take the scalar arm.
+//   affine head     c = out_scale + 1e-8: yhat = z c + out_shift, err = yhat - y_raw, loss = mean(err^2) over B x d_out,
+//                   delta3 = (2 / (B d_out)) err c (dyn_loss_head's expressions); the per-member out_tr travels in the arguments.
 //
 // A step, with a workgroup barrier between the phases (8 waves = 2 a SIMD: fp32 MFMAs run at the vector ALU's rate and the
 // two exclude each other, so the second wave is there to cover LDS / L2 latency, not to overlap VALU with MFMA):
@@ -31,8 +46,8 @@
 // Every delta is formed before the layer it reads is updated.  A weight-gradient tile (32 x 32, 16 accumulator registers) goes
 // straight from the MFMA chain into the Adam update of the 16 weights the lane holds: gradients never touch memory.
 //
-// Out of scope: teams of several workgroups per member, bf16x3 products, RewardNet fits (target mode 0; (100, 100) is no
-// multiple of 32) and more than two hidden layers: mjx_dyn_fit_route sends them to mjx_dyn_fit_adam member by member.
+// Out of scope: teams of several workgroups per member, bf16x3 products and more than two hidden layers: mjx_dyn_fit_route /
+// mjx_reward_fit_route send them to mjx_dyn_fit_adam member by member.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -50,6 +65,7 @@ constexpr int DFE_CHUNK = 64;                                // members per laun
 constexpr size_t DFE_STATIC_LDS = 8 * sizeof(double) + 64 * sizeof(int);
 
 typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));     // four weights of a row (member blocks are 4-byte aligned)
+__host__ __device__ constexpr int dfe_pad32(int d) { return (d + 31) & ~31; }      // the unit rows of a hidden layer's LDS tile
 
 struct DfeLayout {
   int Bp, ST, K0, ZR;
@@ -58,7 +74,7 @@ struct DfeLayout {
   __host__ DfeLayout(const DynNet& net, int batch) {
     Bp = batch > 32 ? 64 : 32; ST = Bp + 4;
     K0 = (net.din() + 7) & ~7; ZR = (net.dout() + 31) & ~31;
-    tiles = (size_t)(net.sz[1] + net.sz[2] + ZR) * ST; xtile = (size_t)K0 * ST;
+    tiles = (size_t)(dfe_pad32(net.sz[1]) + dfe_pad32(net.sz[2]) + ZR) * ST; xtile = (size_t)K0 * ST;
     x_in_lds = (tiles + xtile) * sizeof(float) + DFE_STATIC_LDS <= LDS_MAX;
   }
   __host__ size_t lds_bytes() const { return (tiles + (x_in_lds ? xtile : 0)) * sizeof(float); }
@@ -72,6 +88,7 @@ struct DynFitEnsArgs {
   float* W; float* m; float* v;         // K x P parameters and Adam moments, updated in place
   float* loss;                          // K x steps minibatch losses
   float* xscr;                          // null: the X tile is in LDS; else K x (K0 x ST) floats of scratch
+  const float* otr;                     // the affine head (RAG instance): K x [out_shift (d_out), out_scale (d_out)]; else unused
   float lr, wd;
   int k0;                               // member of workgroup 0
   int64_t step0[DFE_CHUNK];             // Adam steps taken before this call, members k0 ..
@@ -95,9 +112,11 @@ __device__ __forceinline__ void dfe_adam(float* p, float* m, float* v, int64_t i
 __device__ __forceinline__ void dfe_fresh(int& w, int& j, int& hi) { asm volatile("" : "+s"(w), "+v"(j), "+v"(hi)); }
 
 // out[u][s] = act(b[u] + sum_k W[u][k] in[k][s]) over the (ceil(dj / 32) x NS) tiles, a wave per tile.  W: dj x di row-major
-// (global); Kp = di rounded up to 8, `in` has Kp rows (zeros beyond di); vec: di % 8 == 0 (the hidden widths), four weights per
-// load.  in(k, s) reads the input tile.  Rows u >= dj of the last tile come out as zeros.
-template <class LdIn>
+// (global); Kp = di rounded up to 8, `in` has Kp rows (zeros beyond di); vec: four weights per load -- di % 8 == 0 (the
+// aligned hidden widths), or, RAG, di % 4 == 0 with the groups at and beyond di masked (a group of four lies wholly inside the
+// row or wholly beyond it, so no load reaches past the row).  in(k, s) reads the input tile.  Rows u >= dj of the last tile come
+// out as zeros.
+template <bool RAG, class LdIn>
 __device__ __forceinline__ void dfe_forward(const float* __restrict__ W, const float* __restrict__ b, int dj, int di, int Kp, bool vec,
                                             LdIn in, float* out, int ST, int NS, int act, int w, int j, int hi) {
   dfe_fresh(w, j, hi);
@@ -111,9 +130,10 @@ __device__ __forceinline__ void dfe_forward(const float* __restrict__ W, const f
     // operands of group k0 + 8 are requested before the four MFMAs of group k0 (the last trip re-reads its own group)
     auto lda = [&](int kk, float (&av)[4]) {
       if (vec) {
-        const f32x4u a4 = *(const f32x4u*)(wr + kk);
+        const bool ok = RAG ? rok && kk < di : rok;
+        const f32x4u a4 = *(const f32x4u*)(wr + (RAG ? (ok ? kk : 0) : kk));
 #pragma unroll
-        for (int q = 0; q < 4; ++q) av[q] = rok ? a4[q] : 0.f;
+        for (int q = 0; q < 4; ++q) av[q] = ok ? a4[q] : 0.f;
       } else {
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
@@ -147,23 +167,27 @@ __device__ __forceinline__ void dfe_forward(const float* __restrict__ W, const f
   }
 }
 
-// dreg[q] = (sum_{jj < dj} W[jj][u] D[jj][s]) * act'(H[u][s]) for the wave's tiles q = 0, 1 of the (di / 32 x NS) tiles of H
-// (di a multiple of 32).  D: the [dj rounded up to 8][sample] delta tile, zeros beyond dj.
+// dreg[q] = (sum_{jj < dj} W[jj][u] D[jj][s]) * act'(H[u][s]) for the wave's tiles q = 0, 1 of the MT x NS tiles of H
+// (MT = di / 32; RAG: ceil(di / 32), where the columns u >= di of W read as zeros and the unit rows u >= di of the last tile
+// come out as exact zeros whatever act'(0) is: tanh' (0) = 1 would pass a stray product on).  D: the [dj rounded up to
+// 8][sample] delta tile, zeros beyond dj.
+template <bool RAG>
 __device__ __forceinline__ void dfe_delta(const float* __restrict__ W, int dj, int di, const float* D, const float* H, int ST, int NS,
                                           int act, int w, int j, int hi, f32x16 (&dreg)[2]) {
   dfe_fresh(w, j, hi);
-  const int MT = di >> 5, Kp = (dj + 7) & ~7;
+  const int MT = RAG ? (di + 31) >> 5 : di >> 5, Kp = (dj + 7) & ~7;
 #pragma unroll
   for (int q2 = 0; q2 < 2; ++q2) {
     const int t = w + DFE_WAVES * q2;
     if (t < MT * NS) {
       const int mt = t % MT, nt = t / MT;
-      const float* wc = W + 32 * mt + j;
+      const bool cok = !RAG || 32 * mt + j < di;
+      const float* wc = W + (cok ? 32 * mt + j : 0);
       f32x16 acc = (f32x16)(0.f);
       auto ld = [&](int kk, float (&av)[4], float (&bv)[4]) {
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-          const bool ok = kk + q < dj;
+          const bool ok = kk + q < dj && cok;
           const float x = wc[(int64_t)(ok ? kk + q : 0) * di];
           av[q] = ok ? x : 0.f;
           bv[q] = D[(kk + q) * ST + 32 * nt + j];
@@ -179,14 +203,18 @@ __device__ __forceinline__ void dfe_delta(const float* __restrict__ W, int dj, i
         for (int q = 0; q < 4; ++q) { ac[q] = an[q]; bc[q] = bn[q]; }
       }
 #pragma unroll
-      for (int r = 0; r < 16; ++r) acc[r] *= dyn_dact(H[(32 * mt + unit_of(r, hi)) * ST + 32 * nt + j], act);
+      for (int r = 0; r < 16; ++r) {
+        acc[r] *= dyn_dact(H[(32 * mt + unit_of(r, hi)) * ST + 32 * nt + j], act);
+        if (RAG && 32 * mt + unit_of(r, hi) >= di) acc[r] = 0.f;
+      }
       dreg[q2] = acc;
     }
   }
 }
 
+template <bool RAG>
 __device__ __forceinline__ void dfe_delta_store(const f32x16 (&dreg)[2], int di, float* H, int ST, int NS, int w, int j, int hi) {
-  const int MT = di >> 5;
+  const int MT = RAG ? (di + 31) >> 5 : di >> 5;
 #pragma unroll
   for (int q2 = 0; q2 < 2; ++q2) {
     const int t = w + DFE_WAVES * q2;
@@ -249,6 +277,9 @@ __device__ __forceinline__ void dfe_grad_adam(const float* D, int dj, int di, Ld
   }
 }
 
+// RAG = false: the instance of the dynamics ensembles (hidden widths multiples of 32, targets formed by k_dyn_prep, plain MSE).
+// RAG = true: any hidden width 1 .. 256 (tiles padded to 32 unit rows) and the affine head of target mode 0 (RewardNet).
+template <bool RAG>
 __global__ __launch_bounds__(DFE_THREADS) void k_dyn_fit_ens(DynFitEnsArgs a) {
   extern __shared__ __attribute__((aligned(16))) float els[];
   __shared__ double red[DFE_WAVES];
@@ -258,13 +289,15 @@ __global__ __launch_bounds__(DFE_THREADS) void k_dyn_fit_ens(DynFitEnsArgs a) {
   const int din = a.din, h1 = a.h1, h2 = a.h2, dout = a.dout, B = a.B, act = a.act;
   const int Bp = B > 32 ? 64 : 32, NS = Bp >> 5, ST = Bp + 4;
   const int K0 = (din + 7) & ~7, ZR = (dout + 31) & ~31;
-  float* H1 = els; float* H2 = H1 + h1 * ST; float* Z3 = H2 + h2 * ST; float* XL = Z3 + ZR * ST;
+  const int h1p = RAG ? dfe_pad32(h1) : h1, h2p = RAG ? dfe_pad32(h2) : h2;
+  float* H1 = els; float* H2 = H1 + h1p * ST; float* Z3 = H2 + h2p * ST; float* XL = Z3 + ZR * ST;
   const bool xg = a.xscr != nullptr;
   float* XG = xg ? a.xscr + (int64_t)k * K0 * ST : nullptr;
   const int64_t oW1 = 0, ob1 = (int64_t)h1 * din, oW2 = ob1 + h1, ob2 = oW2 + (int64_t)h2 * h1, oW3 = ob2 + h2, ob3 = oW3 + (int64_t)dout * h2;
   float* P = a.W + k * a.P; float* Pm = a.m + k * a.P; float* Pv = a.v + k * a.P;
   const float* xn = a.xn + (int64_t)k * a.N * din;
   const float* tg = a.tg + (int64_t)k * a.N * dout;
+  const float* otr = RAG ? a.otr + (int64_t)k * 2 * dout : nullptr;
   const int32_t* idx = a.idx + (int64_t)k * a.steps * B;
   float* loss = a.loss + (int64_t)k * a.steps;
   const int64_t step0 = a.step0[blockIdx.x];
@@ -286,11 +319,11 @@ __global__ __launch_bounds__(DFE_THREADS) void k_dyn_fit_ens(DynFitEnsArgs a) {
     }
     __syncthreads();
     // ---- forward
-    dfe_forward(P + oW1, P + ob1, h1, din, K0, false, ldx, H1, ST, NS, act, w, j, hi);
+    dfe_forward<RAG>(P + oW1, P + ob1, h1, din, K0, false, ldx, H1, ST, NS, act, w, j, hi);
     __syncthreads();
-    dfe_forward(P + oW2, P + ob2, h2, h1, h1, true, [&](int r, int c) { return H1[r * ST + c]; }, H2, ST, NS, act, w, j, hi);
+    dfe_forward<RAG>(P + oW2, P + ob2, h2, h1, RAG ? (h1 + 7) & ~7 : h1, RAG ? h1 % 4 == 0 : true, [&](int r, int c) { return H1[r * ST + c]; }, H2, ST, NS, act, w, j, hi);
     __syncthreads();
-    dfe_forward(P + oW3, P + ob3, dout, h2, h2, true, [&](int r, int c) { return H2[r * ST + c]; }, Z3, ST, NS, -1, w, j, hi);
+    dfe_forward<RAG>(P + oW3, P + ob3, dout, h2, RAG ? (h2 + 7) & ~7 : h2, RAG ? h2 % 4 == 0 : true, [&](int r, int c) { return H2[r * ST + c]; }, Z3, ST, NS, -1, w, j, hi);
     __syncthreads();
     // ---- MSE head: delta3 over Z3 (exact zeros in the padding), the step's loss
     double part = 0.0;
@@ -299,8 +332,11 @@ __global__ __launch_bounds__(DFE_THREADS) void k_dyn_fit_ens(DynFitEnsArgs a) {
       const int u = e / Bp, r = e - u * Bp;
       float d = 0.f;
       if (u < dout && r < B) {
-        const float err = Z3[u * ST + r] - tg[(int64_t)sIx[r] * dout + u];
+        float z = Z3[u * ST + r], c = 1.f;
+        if (RAG) { c = otr[dout + u] + 1e-8f; z = z * c + otr[u]; }                  // yhat = z c + out_shift, on raw y
+        const float err = z - tg[(int64_t)sIx[r] * dout + u];
         d = dscale * err;
+        if (RAG) d *= c;
         part += (double)err * (double)err;
       }
       Z3[u * ST + r] = d;
@@ -318,20 +354,20 @@ __global__ __launch_bounds__(DFE_THREADS) void k_dyn_fit_ens(DynFitEnsArgs a) {
     const float inv_bc2s = 1.0f / bc2s;
     // ---- layer 3: delta2 with W3 as it is, then W3's own update
     f32x16 dreg[2];
-    dfe_delta(P + oW3, dout, h2, Z3, H2, ST, NS, act, w, j, hi, dreg);
+    dfe_delta<RAG>(P + oW3, dout, h2, Z3, H2, ST, NS, act, w, j, hi, dreg);
     __syncthreads();
     dfe_grad_adam(Z3, dout, h2, [&](int r, int c) { return *(const f32x4*)&H2[r * ST + c]; }, Bp, ST, P, Pm, Pv, oW3, ob3, lr_bc1,
                   inv_bc2s, a.wd, tid, w, j, hi);
     __syncthreads();
-    dfe_delta_store(dreg, h2, H2, ST, NS, w, j, hi);
+    dfe_delta_store<RAG>(dreg, h2, H2, ST, NS, w, j, hi);
     __syncthreads();
     // ---- layer 2
-    dfe_delta(P + oW2, h2, h1, H2, H1, ST, NS, act, w, j, hi, dreg);
+    dfe_delta<RAG>(P + oW2, h2, h1, H2, H1, ST, NS, act, w, j, hi, dreg);
     __syncthreads();
     dfe_grad_adam(H2, h2, h1, [&](int r, int c) { return *(const f32x4*)&H1[r * ST + c]; }, Bp, ST, P, Pm, Pv, oW2, ob2, lr_bc1,
                   inv_bc2s, a.wd, tid, w, j, hi);
     __syncthreads();
-    dfe_delta_store(dreg, h1, H1, ST, NS, w, j, hi);
+    dfe_delta_store<RAG>(dreg, h1, H1, ST, NS, w, j, hi);
     __syncthreads();
     // ---- layer 1
     dfe_grad_adam(H1, h1, din, ldx4, Bp, ST, P, Pm, Pv, oW1, ob1, lr_bc1, inv_bc2s, a.wd, tid, w, j, hi);

@@ -666,6 +666,41 @@ int mjx_dyn_fit_adam(const float* x, const float* y, int64_t N, const int* sizes
   return MJX_OK;
 }
 
+// route 1 of both ensemble entries: per-member prep into scratch, then one k_dyn_fit_ens<RAG> launch per DFE_CHUNK members
+extern "C++" {
+template <bool RAG>
+static int dfe_run(const float* x, int64_t x_stride, const float* y, int64_t y_stride, int64_t N, int K, const DynNet& net, const float* in_tr,
+                   const float* out_tr, int target_mode, int act, float* params, float* m, float* v, const int64_t* step0,
+                   const int32_t* idx, int64_t steps, int batch, float lr, float wd, float* loss_out, void* stream) {
+  const int din = net.din(), dout = net.dout();
+  MJX_DEVICE_ENTRY();
+  hipStream_t st = (hipStream_t)stream;
+  const DfeLayout L(net, batch);
+  // scratch, per member: normalised inputs and targets (every member has its own transforms), and the X tile where LDS has no room
+  const size_t xt = L.x_in_lds ? 0 : L.xtile;
+  float* scr = nullptr;
+  if (int rc = dev_scratch(SITE_DYN_FIT_ENS, stream, ((size_t)K * (size_t)N * (din + dout) + 4 + (size_t)K * xt) * sizeof(float), &scr)) return rc;
+  float* xn = scr; float* tg = xn + (size_t)K * N * din;
+  float* xscr = xt ? scr + (((size_t)K * N * (din + dout) + 3) & ~(size_t)3) : nullptr;
+  for (int k = 0; k < K; ++k)
+    launch_dyn_prep(x + k * x_stride, y + k * y_stride, N, din, dout, in_tr + (int64_t)k * 2 * din, out_tr + (int64_t)k * 2 * dout, target_mode,
+                    xn + (size_t)k * N * din, tg + (size_t)k * N * dout, st);
+  if (int rc = lds_limit((const void*)k_dyn_fit_ens<RAG>, L.lds_bytes())) return rc;
+  DynFitEnsArgs a{};
+  a.din = din; a.h1 = net.sz[1]; a.h2 = net.sz[2]; a.dout = dout; a.B = batch; a.act = act;
+  a.P = net.P; a.N = N; a.steps = steps; a.xn = xn; a.tg = tg; a.idx = idx; a.W = params; a.m = m; a.v = v; a.loss = loss_out; a.xscr = xscr;
+  a.lr = lr; a.wd = wd; a.otr = RAG ? out_tr : nullptr;
+  for (int k0 = 0; k0 < K; k0 += DFE_CHUNK) {               // one launch for K <= DFE_CHUNK members
+    const int kn = K - k0 < DFE_CHUNK ? K - k0 : DFE_CHUNK;
+    a.k0 = k0;
+    for (int q = 0; q < kn; ++q) a.step0[q] = step0[k0 + q];
+    hipLaunchKernelGGL(k_dyn_fit_ens<RAG>, dim3((unsigned)kn), dim3(DFE_THREADS), L.lds_bytes(), st, a);
+  }
+  HIPCHK(hipGetLastError());
+  return MJX_OK;
+}
+}  // extern "C++"
+
 // ---- the whole ensemble's fit (csrc/dyn_fit_ens.h)
 int mjx_dyn_fit_route(const int* sizes, int n_sizes, int batch, int target_mode) {
   DynNet net;
@@ -697,31 +732,52 @@ int mjx_dyn_fit_ensemble(const float* x, int64_t x_stride, const float* y, int64
         return rc;
     return MJX_OK;
   }
-  MJX_DEVICE_ENTRY();
-  hipStream_t st = (hipStream_t)stream;
+  return dfe_run<false>(x, x_stride, y, y_stride, N, K, net, in_tr, out_tr, target_mode, act, params, m, v, step0, idx, steps, batch, lr, wd,
+                        loss_out, stream);
+}
+
+// ---- the reward nets of the whole ensemble (target mode 0: the loss runs through the output affine on raw r)
+int mjx_reward_fit_route(const int* sizes, int n_sizes, int batch) {
+  DynNet net;
+  if (int rc = dyn_net(sizes, n_sizes, net)) return rc;
+  if (batch <= 0) return fail(MJX_ERR_ARG, "bad batch");
+  return reward_fit_serves(net, batch) ? 1 : 0;
+}
+
+int mjx_dyn_fit_ens_layout(const int* sizes, int n_sizes, int batch, int64_t* info) {
+  DynNet net;
+  if (int rc = dyn_net(sizes, n_sizes, net)) return rc;
+  if (!info || batch <= 0 || !reward_fit_serves(net, batch)) return fail(MJX_ERR_ARG, "not a shape of the ensemble kernel");
   const DfeLayout L(net, batch);
-  // scratch, per member: normalised inputs and targets (every member has its own transforms), and the X tile where LDS has no room
-  const size_t xt = L.x_in_lds ? 0 : L.xtile;
-  float* scr = nullptr;
-  if (int rc = dev_scratch(SITE_DYN_FIT_ENS, stream, ((size_t)K * (size_t)N * (din + dout) + 4 + (size_t)K * xt) * sizeof(float), &scr)) return rc;
-  float* xn = scr; float* tg = xn + (size_t)K * N * din;
-  float* xscr = xt ? scr + (((size_t)K * N * (din + dout) + 3) & ~(size_t)3) : nullptr;
-  for (int k = 0; k < K; ++k)
-    launch_dyn_prep(x + k * x_stride, y + k * y_stride, N, din, dout, in_tr + (int64_t)k * 2 * din, out_tr + (int64_t)k * 2 * dout, target_mode,
-                    xn + (size_t)k * N * din, tg + (size_t)k * N * dout, st);
-  if (int rc = lds_limit((const void*)k_dyn_fit_ens, L.lds_bytes())) return rc;
-  DynFitEnsArgs a{};
-  a.din = din; a.h1 = net.sz[1]; a.h2 = net.sz[2]; a.dout = dout; a.B = batch; a.act = act;
-  a.P = net.P; a.N = N; a.steps = steps; a.xn = xn; a.tg = tg; a.idx = idx; a.W = params; a.m = m; a.v = v; a.loss = loss_out; a.xscr = xscr;
-  a.lr = lr; a.wd = wd;
-  for (int k0 = 0; k0 < K; k0 += DFE_CHUNK) {               // one launch for K <= DFE_CHUNK members
-    const int kn = K - k0 < DFE_CHUNK ? K - k0 : DFE_CHUNK;
-    a.k0 = k0;
-    for (int q = 0; q < kn; ++q) a.step0[q] = step0[k0 + q];
-    hipLaunchKernelGGL(k_dyn_fit_ens, dim3((unsigned)kn), dim3(DFE_THREADS), L.lds_bytes(), st, a);
-  }
-  HIPCHK(hipGetLastError());
+  info[0] = (int64_t)L.lds_bytes(); info[1] = L.x_in_lds ? 1 : 0; info[2] = L.ST; info[3] = (int64_t)L.xtile;
   return MJX_OK;
+}
+
+int mjx_reward_fit_ensemble(const float* x, int64_t x_stride, const float* y, int64_t y_stride, int64_t N, int K, const int* sizes,
+                            int n_sizes, const float* in_tr, const float* out_tr, int act, float* params, float* m, float* v,
+                            const int64_t* step0, const int32_t* idx, int64_t steps, int batch, float lr, float wd, float* loss_out,
+                            int* route_out, void* stream) {
+  DynNet net;
+  if (int rc = dyn_net(sizes, n_sizes, net)) return rc;
+  const int din = net.din(), dout = net.dout();
+  if (!x || !y || !in_tr || !out_tr || !params || !m || !v || !step0 || (steps > 0 && (!idx || !loss_out)) || N <= 0 ||
+      x_stride < 0 || y_stride < 0 || batch <= 0 || batch > N || steps < 0 || !dyn_args_ok(net, K, act, DYN_TGT_AFFINE))
+    return fail(MJX_ERR_ARG, "bad arguments");
+  for (int k = 0; k < K; ++k) if (step0[k] < 0) return fail(MJX_ERR_ARG, "bad arguments");
+  // (read per call: the tests and tools/bench_dyn_fit.py compare the two routes in one process)
+  const int route = env_flag("MJX_REWARD_FIT_ENS", true) && reward_fit_serves(net, batch) ? 1 : 0;
+  if (route_out) *route_out = route;
+  if (steps == 0) return MJX_OK;
+  if (route == 0) {                                        // member by member on the routes of mjx_dyn_fit_adam
+    for (int k = 0; k < K; ++k)
+      if (int rc = mjx_dyn_fit_adam(x + k * x_stride, y + k * y_stride, N, sizes, n_sizes, in_tr + (int64_t)k * 2 * din, out_tr + (int64_t)k * 2 * dout,
+                                    DYN_TGT_AFFINE, act, params + k * net.P, m + k * net.P, v + k * net.P, step0[k],
+                                    idx + (int64_t)k * steps * batch, steps, batch, lr, wd, loss_out + (int64_t)k * steps, stream))
+        return rc;
+    return MJX_OK;
+  }
+  return dfe_run<true>(x, x_stride, y, y_stride, N, K, net, in_tr, out_tr, DYN_TGT_AFFINE, act, params, m, v, step0, idx, steps, batch, lr, wd,
+                       loss_out, stream);
 }
 
 int mjx_dyn_pred_error(const float* pred, int K, int64_t rows, int n, const float* s_next, const int64_t* seg_off, int nseg, double lim,

@@ -71,4 +71,11 @@ inline bool dfe_serves(const DynNet& net, int batch, int target_mode) {
   for (int l = 1; l <= 2; ++l) if (net.sz[l] % 32 || net.sz[l] < 32 || net.sz[l] > DFE_MAXH) return false;
   return net.din() <= DFE_MAXIN && net.dout() <= DFE_MAXOUT;
 }
+// The shapes k_dyn_fit_ens<true> serves for mjx_reward_fit_ensemble (target mode 0; MJX_REWARD_FIT_ENS=0, read per call: none): any two
+// hidden widths the padded tiles hold.  Plain arithmetic.
+inline bool reward_fit_serves(const DynNet& net, int batch) {
+  if (net.nl != 3 || batch < 1 || batch > DFE_MAXB) return false;
+  for (int l = 1; l <= 2; ++l) if (net.sz[l] < 1 || net.sz[l] > DFE_MAXH) return false;
+  return net.din() <= DFE_MAXIN && net.dout() <= DFE_MAXOUT;
+}
 }  // namespace mjx
