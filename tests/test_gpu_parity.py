@@ -629,6 +629,30 @@ def test_scans_on_edge_lengths_vs_oracle():
         np.testing.assert_allclose(p["advantages"], p["returns"] - b, rtol=1e-12, atol=1e-12)
 
 
+@pytest.mark.parametrize("terminal", [0.0, 2.5, -1e3])
+def test_discount_sum_with_a_terminal_value_vs_oracle(terminal):
+    """process_samples.discount_sum(x, gamma, terminal) (process_samples.py:37-44) folds the terminal value in as one more trailing
+    element of the device scan: lengths 1, 256, 257 at gamma 0.9 against the oracle's recurrence started from `terminal`, in
+    long double, with the mode-0 bound of tests/test_gpu_samplepath_matrix.py -- |y - ref| <= (2 rem + 4) 2^-53 A[t] with the
+    terminal counted as one more step; the fp64 oracle lies within the same bound."""
+    from mjrl_amd.utils import process_samples
+    from tests import _samplepath_cases as K
+    for T in (1, 256, 257):
+        x = np.random.RandomState(T).randn(T)
+        y = process_samples.discount_sum(x, 0.9, terminal)
+        assert y.shape == (T,) and y.dtype == np.float64
+        xs = np.append(x, terminal)
+        off = K.offsets_of((T + 1,))
+        ref, A = K.scan0_reference(xs, off, 0.9)
+        for name, got in (("device", y), ("oracle", O.discount_sum(x, 0.9, terminal))):
+            buf = K.new_out(T + 1)
+            K.body(buf)[:T] = got
+            K.body(buf)[T] = terminal
+            res = K.scan_check(buf, off, ref, A, 4)
+            print("[discount_sum] terminal %g T %d %s ratio %.3f at %d" % (terminal, T, name, res["ratio"], res["at"]))
+            assert K.scan_ok(res), (name, T, terminal, res)
+
+
 def test_vector_valued_rewards_and_baselines_vs_reference():
     """process_samples.py:26-27 (b.ndim == 2): (T, K) rewards against a (T, K) baseline -- K independent scans, column by column on
     the device -- against the UNMODIFIED reference's compute_returns / compute_advantages (oracle/ref_loader: sources or staged
