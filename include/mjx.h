@@ -519,6 +519,28 @@ int mjx_plan_rollout(const float* s0, int64_t s0_stride, int64_t N, int H, int K
 int mjx_plan_score(const float* obs, const double* rewards, const double* actions, int K, int64_t N, int H, int n,
                    int m, double kappa, double gamma, double omega, int idx_mode, double* R_out, double* S_out,
                    double* seq_out, void* stream);
+/* Which route mjx_path_rewards takes for a dynamics net dyn_sizes = [n + m, h..., n] and a reward net rew_sizes =
+ * [2 n + m, g..., 1]: 1 = the MFMA kernel that keeps both nets in LDS (csrc/path_reward.h): a dynamics net as
+ * mjx_plan_route serves it, exactly two reward hidden layers of 1 .. 128 units each (1 .. 64 beside a dynamics width of 128;
+ * each padded to a multiple of 32 in LDS), and the two LDS images together within 160 KiB -- (17, 6), 64 x 64 beside
+ * 100 x 100: 133.7 KiB; 128 x 128 beside 100 x 100: 200.2 KiB, route 0; 0 = mjx_dyn_forward's kernel twice; < 0 = bad sizes (the two nets do not fit each other included).  Arithmetic
+ * only: no device work and no runtime call.  MJX_PATH_REWARDS_MFMA=0 (read by mjx_path_rewards per call) forces route 0. */
+int mjx_path_rewards_route(const int* dyn_sizes, int dyn_n_sizes, const int* rew_sizes, int rew_n_sizes);
+/* WorldModel.compute_path_rewards / WorldModel.reward (nn_dynamics.py:65-77, 149-164) of K members at once, on device
+ * data: member k reads its own rows obs + k * rows * n (rows x n fp32) and the actions act + k * act_stride (rows x m fp32;
+ * act_stride 0: one block for all members, the planner's case, or rows * m).  s' = DynamicsNet_k.forward(s, a)
+ * (:230-245; recomputed, not clamped, not read from the next stored observation), r = RewardNet_k.forward(s, a, s')
+ * (:313-328: inputs [s, a, s'], out * (out_scale + 1e-8) + out_shift).  Parameters and transforms of both nets as for
+ * mjx_dyn_forward (the reward transforms over [s, a, s'] with the s entries repeated for s'); dyn_flags as its flags, the
+ * reward net always applies its output affine.  r32_out (K x rows fp32) and r64_out (K x rows fp64, the same values widened:
+ * what mjx_plan_score takes) may each be NULL, not both.  *route_out (may be NULL) receives the route taken
+ * (mjx_path_rewards_route).  On route 0 r32_out holds the bits of two mjx_dyn_forward calls over [s, a] and [s, a, s'].
+ * Bad arguments return MJX_ERR_ARG and touch nothing; rows == 0 returns MJX_OK without a launch.  Route 0 uses
+ * per-host-thread scratch. */
+int mjx_path_rewards(const float* obs, const float* act, int64_t act_stride, int64_t rows, int K, const int* dyn_sizes,
+                     int dyn_n_sizes, const float* dyn_params, const float* dyn_tr, int dyn_act, int dyn_flags,
+                     const int* rew_sizes, int rew_n_sizes, const float* rew_params, const float* rew_tr, int rew_act,
+                     float* r32_out, double* r64_out, int* route_out, void* stream);
 
 /* ---- in-library kernel timing (bench.py roofline) ------------------------- */
 /* While enabled (on = k >= 1), every k-th launch of the dominant Fisher-vector-product kernel

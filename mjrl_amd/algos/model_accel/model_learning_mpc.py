@@ -24,6 +24,12 @@ carries a generation counter that this package's own writes bump (``fit_dynamics
 bare model the reference raises ``TypeError`` (it calls ``generate_paths(fitted_model=...)``, which has no such argument);
 this class does what that branch evidently intends: the same draws, one rollout, ``score_trajectory`` (no disagreement term).
 
+``reward='learned'`` (the reference's driver switches to learned rewards where the environment has no reward function,
+run_model_accel_npg.py:106-108; its MPCPolicy has no such switch): steps 4 and 5 become ``mjx_path_rewards`` -- every member's
+``WorldModel.compute_path_rewards`` on its own device observations and the shared fp32 actions, written as fp64
+(csrc/path_reward.h) -- and ``mjx_plan_score``: one upload of the actions, three device calls, one read-back of (H, m).  The
+environment is never asked for rewards, so it needs no ``compute_path_rewards``.
+
 ``reference_indexing``: score_trajectory_ensemble adds ``disagreement[i // num_traj]`` (model_learning_mpc.py:95), which is
 the MEMBER index of row i, so the disagreement of trajectories 0 .. K-1 is what every member's rows get.  True (default)
 reproduces that; False uses the evidently intended per-trajectory index ``i % num_traj``.
@@ -32,7 +38,8 @@ import numpy as np
 import torch
 
 from ..._lib import check, load, ptr
-from .nn_dynamics import _act_code, _device, _flags, _flat_params, _ints, _packed_transforms, _stream
+from .nn_dynamics import (_act_code, _device, _flags, _flat_params, _ints, _packed_transforms, _stream, pack_reward_members,
+                          path_rewards_call)
 
 
 def perturbed_action_batch(num_traj, base_act, filter_coefs):
@@ -49,6 +56,8 @@ def perturbed_action_batch(num_traj, base_act, filter_coefs):
 
 
 class MPCPolicy(object):
+    reward = 'env'              # (an instance pickled before the keyword existed plans as it did)
+
     def __init__(self, env,
                  plan_horizon,
                  plan_paths=10,
@@ -61,9 +70,11 @@ class MPCPolicy(object):
                  fitted_model=None,
                  omega=5.0,
                  reference_indexing=True,
+                 reward='env',
                  **kwargs,
                  ):
-        """Arguments as in the reference (model_learning_mpc.py:6-40), plus reference_indexing (module docstring)."""
+        """Arguments as in the reference (model_learning_mpc.py:6-40), plus reference_indexing and reward ('env': the
+        environment's compute_path_rewards on the host; 'learned': the members' reward nets on the device; module docstring)."""
         self.env, self.seed = env, seed
         self.n, self.m = env.observation_dim, env.action_dim
         self.plan_horizon, self.num_traj = plan_horizon, plan_paths
@@ -81,8 +92,13 @@ class MPCPolicy(object):
         self.warmstart = warmstart
         self.omega = omega
         self.reference_indexing = reference_indexing
+        if reward not in ('env', 'learned'):
+            raise ValueError("reward is 'env' or 'learned'")
+        if reward == 'learned' and not all(getattr(mdl, "learn_reward", False) for mdl in self._members()):
+            raise ValueError("reward='learned' needs every member to be a WorldModel(learn_reward=True)")
+        self.reward = reward
         self._pack = None           # (key, device blocks) of the members' parameters and transforms
-        self._last = None           # device blocks of the last call's scores
+        self._last = None           # device blocks of the last call's scores (and, on learned rewards, the rewards)
 
     # ---- device state
     def __getstate__(self):
@@ -97,11 +113,21 @@ class MPCPolicy(object):
         """What the device copy of the members was made from -> (key, the tensors the key names).  Per member: the net's
         generation counter, which every write path of this package bumps (the fit's write-back through ``p.data.copy_``, which
         leaves ``p._version`` alone, ``set_params``, ``set_transformations``); per parameter and transform tensor its identity,
-        ``_version`` (in-place edits) and storage; activation and flags.  The tensors are returned to be HELD beside the key, so
-        that an id() in it cannot come back as another tensor's."""
+        ``_version`` (in-place edits) and storage; activation and flags.  On reward='learned' the same for every member's reward
+        net (``fit_reward``'s write-back bumps its counter), with output transforms that are plain numbers by value.  The tensors
+        are returned to be HELD beside the key, so that an id() in it cannot come back as another tensor's."""
         nets = [mdl.dynamics_net for mdl in self._members()]
         held = [t for net in nets for t in list(net.parameters()) + list(net.get_params()["transforms"])]
-        key = (str(dev),) + tuple((id(net), getattr(net, "_generation", 0), _act_code(net), _flags(net)) for net in nets) + \
+        if self.reward == 'learned':
+            # the reward nets too; their out_shift / out_scale are plain numbers or tensors (nn_dynamics.py:281-311)
+            rnets = [mdl.reward_net for mdl in self._members()]
+            nets = nets + rnets
+            held += [t for net in rnets for t in list(net.parameters()) + list(net.get_params()["transforms"]) +
+                     [v for v in (net.out_shift, net.out_scale) if isinstance(v, torch.Tensor)]]
+            outs = tuple(float(v) for net in rnets for v in (net.out_shift, net.out_scale) if not isinstance(v, torch.Tensor))
+        else:
+            outs = ()
+        key = (str(dev),) + outs + tuple((id(net), getattr(net, "_generation", 0), _act_code(net), _flags(net)) for net in nets) + \
             tuple((id(t), t._version, t.data_ptr()) for t in held)
         return key, held
 
@@ -117,7 +143,10 @@ class MPCPolicy(object):
             assert (nets[0].state_dim, nets[0].act_dim) == (self.n, self.m), "the models' dims are not the environment's"
             P = torch.stack([_flat_params(net, dev) for net in nets])
             tr = torch.stack([_packed_transforms(net, dev) for net in nets])
-            self._pack = (key, dict(sizes=sizes, P=P, tr=tr, act=_act_code(nets[0]), flags=_flags(nets[0])), held)
+            pk = dict(sizes=sizes, P=P, tr=tr, act=_act_code(nets[0]), flags=_flags(nets[0]))
+            if self.reward == 'learned':
+                pk["rew"] = pack_reward_members(self._members(), dev)
+            self._pack = (key, pk, held)
         return self._pack[1]
 
     def invalidate(self):
@@ -147,20 +176,25 @@ class MPCPolicy(object):
         obs_d = torch.empty((K, N, H, n), dtype=torch.float32, device=dev)
         check(lib.mjx_plan_rollout(ptr(s0_d), 0 if s0.ndim == 1 else n, N, H, K, ptr(a32), _ints(pk["sizes"]), len(pk["sizes"]),
                                    ptr(pk["P"]), ptr(pk["tr"]), pk["act"], pk["flags"], ptr(obs_d), st))
-        obs_h = obs_d.cpu().numpy()
-        rewards = np.empty((K, N, H), np.float64)
-        for k in range(K):
-            paths = dict(observations=obs_h[k], actions=actions)
-            self.env.env.env.compute_path_rewards(paths)        # populates paths['rewards']
-            rewards[k] = paths["rewards"]
-        r_d = torch.from_numpy(rewards).to(dev)
+        if self.reward == 'learned':
+            # r = RewardNet_k(s, a, DynamicsNet_k(s, a)) on the device, widened to fp64 for the scoring
+            r_d = torch.empty((K, N, H), dtype=torch.float64, device=dev)
+            path_rewards_call(pk["rew"], obs_d, a32, True, N * H, K, None, r_d, dev)
+        else:
+            obs_h = obs_d.cpu().numpy()
+            rewards = np.empty((K, N, H), np.float64)
+            for k in range(K):
+                paths = dict(observations=obs_h[k], actions=actions)
+                self.env.env.env.compute_path_rewards(paths)        # populates paths['rewards']
+                rewards[k] = paths["rewards"]
+            r_d = torch.from_numpy(rewards).to(dev)
         out = torch.empty(H * m + 2 * K * N, dtype=torch.float64, device=dev)
         seq_d, R_d, S_d = out[:H * m], out[H * m:H * m + K * N], out[H * m + K * N:]
         check(lib.mjx_plan_score(ptr(obs_d) if ensemble else None, ptr(r_d), ptr(a64), K, N, H, n, m, float(self.kappa),
                                  float(self.gamma), float(self.omega), 0 if self.reference_indexing else 1, ptr(R_d), ptr(S_d),
                                  ptr(seq_d), st))
         act_sequence = seq_d.cpu().numpy().reshape(H, m)
-        self._last = (R_d, S_d)
+        self._last = (R_d, S_d, r_d if self.reward == 'learned' else None)
         action = act_sequence[0].copy()
         if self.warmstart:
             self.act_sequence[:-1] = act_sequence[1:]
@@ -174,6 +208,21 @@ class MPCPolicy(object):
         if self._last is None:
             return None
         return self._last[0].cpu().numpy(), self._last[1].cpu().numpy()
+
+    def last_rewards(self):
+        """the (K, N, H) learned rewards of the last get_action (the fp32 net outputs as fp64, read back on demand); None on
+        reward='env', where the rewards were the environment's"""
+        if self._last is None or self._last[2] is None:
+            return None
+        return self._last[2].cpu().numpy()
+
+    def reward_route(self):
+        """1: the MFMA path-reward kernel serves these members, 0: the generic route (mjx_path_rewards_route); None on reward='env'"""
+        if self.reward != 'learned':
+            return None
+        mdl = self._members()[0]
+        ds, rs = tuple(mdl.dynamics_net.layer_sizes), tuple(mdl.reward_net.layer_sizes)
+        return int(load().mjx_path_rewards_route(_ints(ds), len(ds), _ints(rs), len(rs)))
 
     # ---- the reference's scoring functions, in NumPy, for callers that use them
     def score_trajectory_ensemble(self, paths, paths_list):

@@ -16,7 +16,8 @@ global torch stream are the reference's) and transforms.  What runs where:
 * :func:`fit_reward_ensemble`: the same for the K reward nets (``mjx_reward_fit_ensemble``: any two hidden widths up to 256, the
   loss through the output affine); :func:`fit_world_models`: the driver's interleaved loop (dynamics, reward, next member) as
   two such calls; :func:`ensemble_path_rewards`: every member's ``compute_path_rewards`` in one upload, two launches and one
-  read-back.
+  read-back; :func:`ensemble_path_rewards_device`: the same on device tensors in one ``mjx_path_rewards`` call, which is what
+  ``MPCPolicy(reward='learned')`` plans on.
 
 The module parameters stay ordinary torch tensors (CPU by default, as in the reference): ``get_params`` /
 ``set_params`` / ``to`` / ``is_cuda`` / pickling behave as the reference's.  There is no CPU path: without a GPU the
@@ -578,6 +579,57 @@ def ensemble_path_rewards(models, observations, actions):
     sp = ensemble_forward([mdl.dynamics_net for mdl in models], sa, dev)
     r = ensemble_forward([mdl.reward_net for mdl in models], torch.cat([sa, sp], -1), dev)
     return r.to('cpu').data.numpy().reshape(K, N, H)
+
+
+def pack_reward_members(models, dev):
+    """the device blocks ``mjx_path_rewards`` reads, for K members that share shapes, activation and flags (asserted, as
+    ``rollout_models`` does): dict(dyn_sizes, dyn_P, dyn_tr, dyn_act, dyn_flags, rew_sizes, rew_P, rew_tr, rew_act)"""
+    models = list(models)
+    assert models and all(mdl.learn_reward for mdl in models), "every member must learn its reward"
+    dyn, rew = [mdl.dynamics_net for mdl in models], [mdl.reward_net for mdl in models]
+    for nets in (dyn, rew):
+        assert len({tuple(net.layer_sizes) for net in nets}) == 1, "ensemble members must share one shape"
+        assert len({(_act_code(net), _flags(net)) for net in nets}) == 1, "ensemble members must share activation and output transforms"
+    return dict(dyn_sizes=tuple(dyn[0].layer_sizes), dyn_P=torch.stack([_flat_params(net, dev) for net in dyn]),
+                dyn_tr=torch.stack([_packed_transforms(net, dev) for net in dyn]), dyn_act=_act_code(dyn[0]), dyn_flags=_flags(dyn[0]),
+                rew_sizes=tuple(rew[0].layer_sizes), rew_P=torch.stack([_flat_params(net, dev) for net in rew]),
+                rew_tr=torch.stack([_packed_transforms(net, dev) for net in rew]), rew_act=_act_code(rew[0]))
+
+
+def path_rewards_call(pk, obs_d, act_d, shared, rows, K, r32, r64, dev):
+    """one ``mjx_path_rewards`` over packed members (:func:`pack_reward_members`) -> the route taken"""
+    route = ctypes.c_int(-1)
+    m = pk["dyn_sizes"][0] - pk["dyn_sizes"][-1]
+    check(load().mjx_path_rewards(ptr(obs_d), ptr(act_d), 0 if shared else rows * m, rows, K, _ints(pk["dyn_sizes"]), len(pk["dyn_sizes"]),
+                                  ptr(pk["dyn_P"]), ptr(pk["dyn_tr"]), pk["dyn_act"], pk["dyn_flags"], _ints(pk["rew_sizes"]),
+                                  len(pk["rew_sizes"]), ptr(pk["rew_P"]), ptr(pk["rew_tr"]), pk["rew_act"],
+                                  None if r32 is None else ptr(r32), None if r64 is None else ptr(r64), ctypes.byref(route), _stream(dev)))
+    return route.value
+
+
+def ensemble_path_rewards_device(models, obs_d, act_d, want64=False, packed=None):
+    """:func:`ensemble_path_rewards` on device data: obs_d (K, N, H, n) and act_d (K, N, H, m), or (N, H, m) shared by all members,
+    fp32 device tensors -> rewards (K, N, H) fp32 on the device, with ``want64`` (fp32, the same values as fp64).  One
+    ``mjx_path_rewards`` call (csrc/path_reward.h: both nets of a member in LDS on MFMAs where ``mjx_path_rewards_route`` says so,
+    ``mjx_dyn_forward``'s kernel twice otherwise).  Members must share shapes, activation and flags.  The DATA make no host copy;
+    the members' parameters and transforms are flattened and uploaded on every call unless ``packed`` carries the blocks of an
+    earlier :func:`pack_reward_members` of the same, unchanged members on this device (``MPCPolicy`` keeps its own, keyed on the
+    members' state)."""
+    models = list(models)
+    dev = obs_d.device
+    assert obs_d.is_cuda and act_d.device == dev and obs_d.dtype == act_d.dtype == torch.float32, "fp32 device tensors"
+    pk = packed if packed is not None else pack_reward_members(models, dev)
+    assert pk["dyn_P"].device == dev and pk["dyn_P"].shape[0] == len(models), "packed blocks of these members on this device"
+    K, N, H, n = obs_d.shape
+    m = act_d.shape[-1]
+    shared = act_d.dim() == 3
+    assert K == len(models) and tuple(act_d.shape) == ((N, H, m) if shared else (K, N, H, m))
+    assert (n + m, n) == (pk["dyn_sizes"][0], pk["dyn_sizes"][-1]), "the models' dims are not the data's"
+    obs_d, act_d = obs_d.contiguous(), act_d.contiguous()
+    r32 = torch.empty((K, N, H), dtype=torch.float32, device=dev)
+    r64 = torch.empty((K, N, H), dtype=torch.float64, device=dev) if want64 else None
+    path_rewards_call(pk, obs_d, act_d, shared, N * H, K, r32, r64, dev)
+    return (r32, r64) if want64 else r32
 
 
 class DynamicsNet(nn.Module):

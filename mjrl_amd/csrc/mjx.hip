@@ -28,6 +28,7 @@
 #include "launch_state.h"
 #include "layerwise.h"
 #include "mlp_fit.h"
+#include "path_reward.h"
 #include "plan.h"
 #include "vecops.h"
 
@@ -59,7 +60,7 @@ int lds_limit(const void* kern, size_t bytes) {
   if (e) return fail(e, "dynamic LDS limit of %zu bytes: %s", bytes, hipGetErrorString((hipError_t)e));
   return MJX_OK;
 }
-enum ScratchSite { SITE_GRAM, SITE_MLP_PREDICT, SITE_MLP_FIT, SITE_MLP_FIT_WIDE, SITE_MLP_FIT_LAUNCHES, SITE_DYN_FIT, SITE_SUM_STATS, SITE_PLAN_ROLLOUT, SITE_PLAN_SCORE, SITE_DYN_FIT_ENS };
+enum ScratchSite { SITE_GRAM, SITE_MLP_PREDICT, SITE_MLP_FIT, SITE_MLP_FIT_WIDE, SITE_MLP_FIT_LAUNCHES, SITE_DYN_FIT, SITE_SUM_STATS, SITE_PLAN_ROLLOUT, SITE_PLAN_SCORE, SITE_DYN_FIT_ENS, SITE_PATH_REWARDS };
 template <class T>
 int dev_scratch(ScratchSite site, void* stream, size_t bytes, T** out) {
   HIPCHK(mjx::scratch(site, (hipStream_t)stream, bytes, (void**)out));
@@ -608,6 +609,71 @@ int mjx_plan_score(const float* obs, const double* rewards, const double* action
   hipLaunchKernelGGL(k_plan_softmax, dim3(1), dim3(1024), 0, st, R_out, T, kappa, S_out, scr);
   hipLaunchKernelGGL(k_plan_sequence, dim3((unsigned)(H * m)), dim3(256), 0, st, S_out, scr, actions, K, N, (int64_t)H * m, seq_out);
   HIPCHK(hipGetLastError());
+  return MJX_OK;
+}
+
+// ---------------------------------------------------------------------------- learned path rewards (csrc/path_reward.h)
+int mjx_path_rewards_route(const int* dyn_sizes, int dyn_n_sizes, const int* rew_sizes, int rew_n_sizes) {
+  DynNet dyn, rew;
+  if (int rc = dyn_net(dyn_sizes, dyn_n_sizes, dyn)) return rc;
+  if (int rc = dyn_net(rew_sizes, rew_n_sizes, rew)) return rc;
+  if (!path_rew_nets_ok(dyn, rew)) return fail(MJX_ERR_ARG, "sizes must be [n + m, h..., n] and [2 n + m, g..., 1] with m > 0");
+  PathRewShape ps;
+  return path_rew_shape(dyn, rew, ps) ? 1 : 0;
+}
+
+int mjx_path_rewards(const float* obs, const float* act, int64_t act_stride, int64_t rows, int K, const int* dyn_sizes, int dyn_n_sizes,
+                     const float* dyn_params, const float* dyn_tr, int dyn_act, int dyn_flags, const int* rew_sizes, int rew_n_sizes,
+                     const float* rew_params, const float* rew_tr, int rew_act, float* r32_out, double* r64_out, int* route_out,
+                     void* stream) {
+  DynNet dyn, rew;
+  if (int rc = dyn_net(dyn_sizes, dyn_n_sizes, dyn)) return rc;
+  if (int rc = dyn_net(rew_sizes, rew_n_sizes, rew)) return rc;
+  if (!path_rew_nets_ok(dyn, rew)) return fail(MJX_ERR_ARG, "sizes must be [n + m, h..., n] and [2 n + m, g..., 1] with m > 0");
+  const int n = dyn.dout(), m = dyn.din() - n;
+  if (!obs || !act || !dyn_params || !dyn_tr || !rew_params || !rew_tr || (!r32_out && !r64_out) || rows < 0 ||
+      (act_stride != 0 && act_stride != rows * m) || (dyn_flags & ~(DYN_OUT_AFFINE | DYN_MASK | DYN_RESIDUAL)) ||
+      !dyn_args_ok(dyn, K, dyn_act, DYN_TGT_PLAIN, dyn_flags & DYN_RESIDUAL) || !dyn_args_ok(rew, K, rew_act))
+    return fail(MJX_ERR_ARG, "bad arguments");
+  PathRewShape ps;
+  const bool served = env_flag("MJX_PATH_REWARDS_MFMA", true) && path_rew_shape(dyn, rew, ps);     // (read per call: A/B runs in one process)
+  if (rows == 0) { if (route_out) *route_out = served ? 1 : 0; return MJX_OK; }
+  MJX_DEVICE_ENTRY();
+  hipStream_t st = (hipStream_t)stream;
+  if (served) {
+    const PathRewKernel kern = path_rew_kernel(ps.HB, ps.NB);
+    const int e = mjx::dyn_lds((const void*)kern, ps.bytes);
+    if (e == 0) {
+      PathRewArgs a{obs, act, act_stride, dyn_params, dyn_tr, rew_params, rew_tr, r32_out, r64_out, rows, dyn.P, rew.P,
+                    n, m, dyn.sz[1], dyn.sz[2], dyn_act, dyn_flags, rew.sz[1], rew.sz[2], rew_act};
+      // a wave owns tiles of 32 rows; one workgroup per CU holds the image, so the K members share the CUs and a wave walks the
+      // tiles beyond that (the staging prologue is paid once per workgroup)
+      const int64_t groups = (rows + 127) / 128, cap = (cu_count() + K - 1) / K;
+      hipLaunchKernelGGL(kern, dim3((unsigned)(groups < cap ? groups : cap), (unsigned)K), dim3(256), ps.bytes, st, a);
+      HIPCHK(hipGetLastError());
+      if (route_out) *route_out = 1;
+      return MJX_OK;
+    }
+    if (e != mjx::LDS_OVER) (void)hipGetLastError();                     // a refusal falls back to the generic route
+  }
+  // generic route: mjx_dyn_forward's kernel twice, over [s, a] and over [s, a, s'], both assembled in scratch
+  const int din = n + m, rin = din + n;
+  const int64_t kr = (int64_t)K * rows;
+  float* scr = nullptr;
+  if (int rc = dev_scratch(SITE_PATH_REWARDS, stream, (size_t)kr * (din + rin + n + 1) * sizeof(float), &scr)) return rc;
+  float* X1 = scr; float* X2 = X1 + kr * din; float* sp = X2 + kr * rin; float* r32 = r32_out ? r32_out : sp + kr * n;
+  const size_t b1 = sizeof(float) * 3 * DYN_FT * (size_t)dyn.maxw, b2 = sizeof(float) * 3 * DYN_FT * (size_t)rew.maxw;
+  if (int rc = lds_limit((const void*)k_dyn_forward, b1 > b2 ? b1 : b2)) return rc;
+  const dim3 grid((unsigned)((rows + DYN_FT - 1) / DYN_FT), (unsigned)K);
+  hipLaunchKernelGGL(k_pr_gather_sa, dim3(capped_grid(kr * din, 256, 4096)), dim3(256), 0, st, obs, act, act_stride, rows, K, n, m, X1, X2);
+  DynFwdArgs fa{dyn, X1, rows * din, rows, dyn_params, dyn_tr, dyn_act, dyn_flags, sp};
+  hipLaunchKernelGGL(k_dyn_forward, grid, dim3(256), b1, st, fa);
+  hipLaunchKernelGGL(k_pr_gather_sp, dim3(capped_grid(kr * n, 256, 4096)), dim3(256), 0, st, sp, kr, n, m, X2);
+  DynFwdArgs fr{rew, X2, rows * rin, rows, rew_params, rew_tr, rew_act, DYN_OUT_AFFINE, r32};
+  hipLaunchKernelGGL(k_dyn_forward, grid, dim3(256), b2, st, fr);
+  if (r64_out) hipLaunchKernelGGL(k_pr_widen, dim3(capped_grid(kr, 256, 4096)), dim3(256), 0, st, r32, kr, r64_out);
+  HIPCHK(hipGetLastError());
+  if (route_out) *route_out = 0;
   return MJX_OK;
 }
 

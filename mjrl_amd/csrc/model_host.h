@@ -51,6 +51,36 @@ inline PlanKernel plan_kernel(int HB, int NB) {
   return tab[HB - 1][NB - 1];
 }
 
+// ---- learned path rewards.  The k_path_rewards instance that serves a (dynamics, reward) pair, if one does: a dynamics net as
+// plan_shape accepts it, a reward net [2 n + m, g1, g2, 1] with 1 <= g1, g2 <= 128, and BOTH images together within LDS_MAX (the
+// kernel has no static LDS).  Each reward width is padded to whole 32-blocks in the image (W2's K dimension to the first width's
+// blocks) and the kernel runs the blocks in use, so one instance per dynamics instance serves every reward width (eight in all, as
+// many as the plan rollout has): up to four reward blocks beside HB <= 3, up to two (widths <= 64) beside the 128-wide dynamics
+// nets, where four would spill registers to scratch and 100 x 100 (205 KB together) would not fit anyway.
+// MJX_PATH_REWARDS_MFMA=0 (read per call by mjx_path_rewards): the generic route.
+struct PathRewShape { int HB = 0, NB = 0, RB = 0; size_t bytes = 0; };
+inline bool path_rew_shape(const DynNet& dyn, const DynNet& rew, PathRewShape& ps) {
+  const int n = dyn.dout(), m = dyn.din() - n;
+  PlanShape dp;
+  if (!plan_shape(dyn, m, dp) || rew.nl != 3) return false;
+  const int g1 = rew.sz[1], g2 = rew.sz[2];
+  ps.HB = dp.HB; ps.NB = dp.NB; ps.RB = dp.HB == 4 ? 2 : 4;
+  if (g1 > 32 * ps.RB || g2 > 32 * ps.RB) return false;
+  ps.bytes = dp.bytes + sizeof(float) * path_rew_lds_floats(g1, g2, n, m);
+  return ps.bytes <= LDS_MAX;
+}
+typedef void (*PathRewKernel)(PathRewArgs);
+inline PathRewKernel path_rew_kernel(int HB, int NB) {
+  static const PathRewKernel tab[4][2] = {{k_path_rewards<1, 1, 4>, k_path_rewards<1, 2, 4>}, {k_path_rewards<2, 1, 4>, k_path_rewards<2, 2, 4>},
+                                          {k_path_rewards<3, 1, 4>, k_path_rewards<3, 2, 4>}, {k_path_rewards<4, 1, 2>, k_path_rewards<4, 2, 2>}};
+  return tab[HB - 1][NB - 1];
+}
+// the two nets of one call: sizes that fit each other ([n + m, h..., n] and [2 n + m, g..., 1])
+inline bool path_rew_nets_ok(const DynNet& dyn, const DynNet& rew) {
+  const int n = dyn.dout(), m = dyn.din() - n;
+  return m > 0 && rew.dout() == 1 && rew.din() == 2 * n + m;
+}
+
 // ---- dynamics fit.  k_dyn_fit, the persistent trainer, serves hidden widths <= 128 at minibatches <= 64 (shape) whose activations fit in LDS beside
 // its static LDS (128 B; asked of the runtime only where the shape leaves the question open); MJX_DYN_FIT_LAUNCHES=1, read per call: the launch route.
 inline size_t dyn_fit_lds_bytes(const DynNet& net, int B) {

@@ -24,11 +24,12 @@ for k in re.split(r"\n\s+- \.agpr_count:", txt)[1:]:
                      max_flat_workgroup_size=int(g("max_flat_workgroup_size"))))
 names = subprocess.run(["c++filt"], input="\n".join(r["mangled"] for r in rows), capture_output=True, text=True).stdout.splitlines()
 for r, n in zip(rows, names):
-    r["kernel"] = re.sub(r"\(.*$", "", n.replace("void ", "").replace("mjx::", ""))
+    r["kernel"] = re.sub(r"\(.*$", "", n.replace("void ", "").replace("(anonymous namespace)::", "").replace("mjx::", ""))
     del r["mangled"]
 rows.sort(key=lambda r: r["kernel"])
 json.dump(rows, open(out_json, "w"), indent=0)
-hot = ("k_fused<64, 64, 1, 8", "k_gemm", "k_lw_head", "k_mlp_fit", "k_policy_fit", "k_bl_gram", "k_cg_", "k_reduce_partials4", "k_dyn_fit")
+hot = ("k_fused<64, 64, 1, 8", "k_gemm", "k_lw_head", "k_mlp_fit", "k_policy_fit", "k_bl_gram", "k_cg_", "k_reduce_partials4", "k_dyn_fit", "k_plan_rollout",
+       "k_path_rewards", "k_pr_")
 with open(out_md, "w") as f:
     f.write("# Register / scratch / static-LDS use per kernel (gfx950 code object of csrc/mjx.hip, `tools/kernel_resources.py`)\n\n"
             "`vgpr` = architectural VGPRs + AGPRs allocated (the unified file: 512 per lane at one wave per SIMD, 256 at two); `scratch` > 0 = spilled registers "
