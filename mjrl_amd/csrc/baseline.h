@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "layerwise.h"
+#include "mfma_chain.h"
 #include "vecops.h"
 
 namespace mjx {
@@ -428,10 +429,9 @@ struct MlpRegressor {
 // ---- the value network of mjrl's MLPBaseline, (n + 4) -> 128 -> 128 -> 1 ReLU (mjrl/baselines/mlp_baseline.py:21-28), evaluated in
 // ONE launch (r06).  The layer-by-layer route (MlpRegressor::forward: 3 GEMM launches per 131 072-row chunk) spent 1.3 ms per 1M
 // timesteps, most of it in the K = 21 first layer (rows of 84 bytes: neither 16-byte granules nor a whole 32-wide k-tile, i.e. the
-// general kernel's element-wise loads) -- and baseline.predict sits on train_step's critical path (compute_advantages).  Same scheme as
-// the fused policy kernels: units on the MFMA M / K dims, the tile's 32 samples on N, so layer 1's accumulators ARE layer 2's B
-// operands; weights in LDS, read as one ds_read_b128 per four k-steps in the k-permuted order (k-slot `hi` of step (q, t) carries
-// k = 8 q + 4 hi + t).  One wave = one 32-sample tile at a time; 8 waves per workgroup (two per SIMD), one workgroup per CU.
+// general kernel's element-wise loads) -- and baseline.predict sits on train_step's critical path (compute_advantages).  The scheme of
+// mfma_chain.h: units on the MFMA M / K dims, the tile's 32 samples on N, so layer 1's accumulators ARE layer 2's B operands (its dense
+// block); weights in LDS.  Layer 1 is this kernel's own: features from global memory, not normalised.  One wave = one 32-sample tile at a time; 8 waves per workgroup (two per SIMD), one workgroup per CU.
 // Per tile: 4 x K1 / 2 + 256 MFMAs of 32x32x2; 1M timesteps: 8.9 GF on the matrix pipe.  d_in <= 64.
 struct MlpPredictArgs { const float* feat; const float* params; float* out; int64_t N; int d_in; };
 constexpr int MP_H = 128, MP_S2 = MP_H + 4;
@@ -487,16 +487,7 @@ __global__ __launch_bounds__(512, 1) void k_mlp_predict128(MlpPredictArgs a) {
     float ysum = 0.f;
 #pragma unroll 1
     for (int ob = 0; ob < 4; ++ob) {
-      f32x16 acc = (f32x16)(0.f);
-      const float* wrow = &W2s[(32 * ob + j) * MP_S2 + 4 * hi];
-#pragma unroll
-      for (int mb = 0; mb < 4; ++mb)
-#pragma unroll
-        for (int rq = 0; rq < 4; ++rq) {
-          const f32x4 a4 = *(const f32x4*)(wrow + 32 * mb + 8 * rq);
-#pragma unroll
-          for (int t = 0; t < 4; ++t) acc = MJX_MFMA(a4[t], h1[mb][4 * rq + t], acc);
-        }
+      const f32x16 acc = chain_dense(W2s, MP_S2, ob, ChainLane{j, hi}, h1, 4);
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int u = 32 * ob + unit_of(r, hi);

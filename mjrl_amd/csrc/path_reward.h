@@ -9,11 +9,10 @@
 //                               the pieces of the generic route, which runs k_dyn_forward twice: [s, a] and [s, a, s'] rows assembled
 //                               in scratch, and the fp64 copy of the result
 //
-// The scheme is k_plan_rollout's (plan.h): units on the MFMA M / K dimensions, the tile's 32 rows on N, v_mfma_f32_32x32x2_f32 chained
-// through registers (register r = 4 q + t of lane half `hi` holds unit 8 q + 4 hi + t, unit_of).  One step further than the rollout:
-// the dynamics net's OUTPUT accumulator -- s' -- is the s' part of the reward net's layer-1 B operand as it lies, the s registers that
-// fed the dynamics layer 1 feed the reward layer 1 again (with the reward net's own shift and scale), and so do the action slots.
-// No activation passes through LDS and there is no barrier after the prologue.
+// A register-chained MFMA MLP twice over (mfma_chain.h: the scheme, the dynamics net's LDS image and the pieces of a forward).  One step
+// further than the rollout of plan.h: the dynamics net's OUTPUT accumulator -- s' -- is the s' part of the reward net's layer-1 B operand
+// as it lies, the s registers that fed the dynamics layer 1 feed the reward layer 1 again (with the reward net's own shift and scale), and
+// so do the action slots.  No activation passes through LDS and there is no barrier after the prologue.
 //
 // The reward net's input features are laid out [s padded to n8 | a padded to m8 | s' padded to n8]; its W1's columns are permuted and
 // zero-padded to that layout when they are staged.  Each hidden width is padded to whole 32-blocks, R1 = 32 g1b and R2 = 32 g2b units,
@@ -22,14 +21,14 @@
 // instance's RB (2 or 4): the image and the MFMA count follow the net, not the instance, and W2's K dimension is R1, not 32 RB.  The head (d_out = 1) is no MFMA: each lane dots its 16 RB registers of h2
 // with the head's weights and the two lane halves are added once.
 //
-// LDS image (floats): the dynamics image of plan.h (plan_lds_floats), then
+// LDS image (floats): the dynamics image (DynImage, plan_lds_floats), then
 //   V1s R1 x (K1r + 4) | V2s R2 x (R1 + 4) | c1 R1 | c2 R2 | w3 R2 | in_shift K1r | in_scale + 1e-8 K1r | b3, out_scale + 1e-8, out_shift, 0
 // with K1r = 2 n8 + m8.  (17, 6) at dynamics 64 x 64, reward 100 x 100: 35.8 + 98.0 = 133.7 KiB of the 160 KiB.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "plan.h"
+#include "mfma_chain.h"
 
 namespace mjx {
 
@@ -52,50 +51,26 @@ __host__ __device__ inline size_t path_rew_lds_floats(int g1, int g2, int n, int
 template <int HB, int NB, int RB>
 __global__ __launch_bounds__(256, 1) void k_path_rewards(PathRewArgs a) {
   extern __shared__ __attribute__((aligned(16))) float prs[];
-  constexpr int HW = 32 * HB, S2 = HW + 4, NS = 32 * NB;
-  const int n = a.n, m = a.m, h1 = a.h1, h2 = a.h2, g1 = a.g1, g2 = a.g2;
+  const int n = a.n, m = a.m, g1 = a.g1, g2 = a.g2;
   const int g1b = (g1 + 31) >> 5, g2b = (g2 + 31) >> 5, R1 = 32 * g1b, R2 = 32 * g2b, T2 = R1 + 4;      // blocks in use: g1b, g2b <= RB
-  const int n8 = plan_pad8(n), m8 = plan_pad8(m), K1 = n8 + m8, S1 = K1 + 4, din = n + m, K1r = K1 + n8, T1 = K1r + 4, rin = din + n;
-  float* W1s = prs; float* W2s = W1s + HW * S1; float* W3s = W2s + HW * S2;
-  float* b1s = W3s + NS * S2; float* b2s = b1s + HW; float* b3s = b2s + HW;
-  float* ish = b3s + NS; float* irs = ish + K1; float* osc = irs + K1; float* osh = osc + NS; float* msk = osh + NS;
-  float* V1s = msk + NS; float* V2s = V1s + R1 * T1; float* c1s = V2s + R2 * T2; float* c2s = c1s + R1; float* w3s = c2s + R2;
+  DynImage<HB, NB> im;
+  float* V1s = im.carve(prs, n, m);
+  const int K1 = im.K1, din = n + m, K1r = K1 + im.n8, T1 = K1r + 4, rin = din + n;
+  float* V2s = V1s + R1 * T1; float* c1s = V2s + R2 * T2; float* c2s = c1s + R1; float* w3s = c2s + R2;
   float* rsh = w3s + R2; float* rrs = rsh + K1r; float* hd = rrs + K1r;
   const int tid = threadIdx.x, lane = tid & 63, j = lane & 31, hi = lane >> 5, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const ChainLane L{j, hi};
+  const ChainL1 rl1{V1s, T1, rsh, rrs};
   const int k = blockIdx.y;
-  const float* __restrict__ P = a.dP + k * a.dPstride;
-  const float* __restrict__ tr = a.dtr + (int64_t)k * (2 * din + 2 * n);
   const float* __restrict__ Q = a.rP + k * a.rPstride;
   const float* __restrict__ qtr = a.rtr + (int64_t)k * (2 * rin + 2);
-  const int64_t oB1 = (int64_t)h1 * din, oW2 = oB1 + h1, oB2 = oW2 + (int64_t)h2 * h1, oW3 = oB2 + h2, oB3 = oW3 + (int64_t)n * h2;
   const int64_t qB1 = (int64_t)g1 * rin, qW2 = qB1 + g1, qB2 = qW2 + (int64_t)g2 * g1, qW3 = qB2 + g2, qB3 = qW3 + g2;
-  // ---- prologue: a wave stages whole rows (lanes along the row: coalesced reads, no division); the dynamics net as k_plan_rollout does
-  for (int u = tid >> 6; u < HW; u += 4) {
-    for (int c = lane; c < K1; c += 64) {
-      const int f = c < n8 ? (c < n ? c : -1) : (c - n8 < m ? n + c - n8 : -1);
-      W1s[u * S1 + c] = (u < h1 && f >= 0) ? P[(int64_t)u * din + f] : 0.f;
-    }
-    for (int c = lane; c < HW; c += 64) W2s[u * S2 + c] = (u < h2 && c < h1) ? P[oW2 + (int64_t)u * h1 + c] : 0.f;
-  }
-  for (int u = tid >> 6; u < NS; u += 4)
-    for (int c = lane; c < HW; c += 64) W3s[u * S2 + c] = (u < n && c < h2) ? P[oW3 + (int64_t)u * h2 + c] : 0.f;
-  for (int i = tid; i < HW; i += 256) { b1s[i] = i < h1 ? P[oB1 + i] : 0.f; b2s[i] = i < h2 ? P[oB2 + i] : 0.f; }
-  for (int i = tid; i < NS; i += 256) {
-    const float sc = i < n ? tr[2 * din + n + i] : 0.f;
-    b3s[i] = i < n ? P[oB3 + i] : 0.f;
-    osc[i] = i < n ? sc + 1e-8f : 0.f;
-    osh[i] = i < n ? tr[2 * din + i] : 0.f;
-    msk[i] = (i < n && sc >= 1e-8f) ? 1.f : 0.f;
-  }
-  for (int c = tid; c < K1; c += 256) {
-    const int f = c < n8 ? (c < n ? c : -1) : (c - n8 < m ? n + c - n8 : -1);
-    ish[c] = f >= 0 ? tr[f] : 0.f;
-    irs[c] = f >= 0 ? tr[din + f] + 1e-8f : 1.f;
-  }
-  // ... and the reward net: column c of the padded layout is input feature rfeat(c) of [s, a, s'] or none
+  // ---- prologue: the dynamics net as k_plan_rollout stages it ...
+  im.stage(a.dP + k * a.dPstride, a.dtr + (int64_t)k * (2 * din + 2 * n), a.h1, a.h2, tid);
+  // ... and the reward net, a wave staging whole rows: column c of the padded layout is input feature im.feat(c) of [s, a, s'] or none
   for (int u = tid >> 6; u < R1; u += 4)
     for (int c = lane; c < K1r; c += 64) {
-      const int f = c < n8 ? (c < n ? c : -1) : c < K1 ? (c - n8 < m ? n + c - n8 : -1) : (c - K1 < n ? din + c - K1 : -1);
+      const int f = im.feat(c);
       V1s[u * T1 + c] = (u < g1 && f >= 0) ? Q[(int64_t)u * rin + f] : 0.f;
     }
   for (int u = tid >> 6; u < R2; u += 4)
@@ -106,13 +81,13 @@ __global__ __launch_bounds__(256, 1) void k_path_rewards(PathRewArgs a) {
     w3s[i] = i < g2 ? Q[qW3 + i] : 0.f;
   }
   for (int c = tid; c < K1r; c += 256) {
-    const int f = c < n8 ? (c < n ? c : -1) : c < K1 ? (c - n8 < m ? n + c - n8 : -1) : (c - K1 < n ? din + c - K1 : -1);
+    const int f = im.feat(c);
     rsh[c] = f >= 0 ? qtr[f] : 0.f;
     rrs[c] = f >= 0 ? qtr[rin + f] + 1e-8f : 1.f;
   }
   if (tid == 0) { hd[0] = Q[qB3]; hd[1] = qtr[2 * rin + 1] + 1e-8f; hd[2] = qtr[2 * rin]; hd[3] = 0.f; }
   __syncthreads();
-  const int NQS = n8 / 8, NQA = m8 / 8;
+  const int NQS = im.n8 / 8, NQA = im.m8 / 8;
   const float* __restrict__ obase = a.obs + (int64_t)k * a.rows * n;
   const float* __restrict__ abase = a.actions + k * a.act_stride;
   // ---- the tiles of this wave (no barrier from here on)
@@ -139,158 +114,30 @@ __global__ __launch_bounds__(256, 1) void k_path_rewards(PathRewArgs a) {
         const float v = abase[vrow * m + ((q < NQA && f < m) ? f : 0)];
         an[4 * q + tt] = (valid && q < NQA && f < m) ? v : 0.f;
       }
-    // -- dynamics layer 1: normalise; the action part, then the state part
+    // -- the dynamics net: normalise, layer 1 (the action part, then the state part), the rest -> s' (blocks beyond n stay exactly 0)
     f32x16 h1v[HB];
 #pragma unroll
     for (int mb = 0; mb < HB; ++mb) h1v[mb] = (f32x16)(0.f);
-#pragma unroll
-    for (int q = 0; q < PLAN_MAX_M8 / 8; ++q) {
-      if (q < NQA) {
-        const int c0 = n8 + 8 * q + 4 * hi;
-        float xb[4];
-#pragma unroll
-        for (int tt = 0; tt < 4; ++tt) xb[tt] = (an[4 * q + tt] - ish[c0 + tt]) / irs[c0 + tt];
-#pragma unroll
-        for (int mb = 0; mb < HB; ++mb) {
-          const f32x4 a4 = *(const f32x4*)&W1s[(32 * mb + j) * S1 + c0];
-#pragma unroll
-          for (int tt = 0; tt < 4; ++tt) h1v[mb] = MJX_MFMA(a4[tt], xb[tt], h1v[mb]);
-        }
-      }
-    }
-#pragma unroll
-    for (int b = 0; b < NB; ++b)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        if (4 * b + q < NQS) {
-          const int c0 = 32 * b + 8 * q + 4 * hi;
-          float xb[4];
-#pragma unroll
-          for (int tt = 0; tt < 4; ++tt) xb[tt] = (s[b][4 * q + tt] - ish[c0 + tt]) / irs[c0 + tt];
-#pragma unroll
-          for (int mb = 0; mb < HB; ++mb) {
-            const f32x4 a4 = *(const f32x4*)&W1s[(32 * mb + j) * S1 + c0];
-#pragma unroll
-            for (int tt = 0; tt < 4; ++tt) h1v[mb] = MJX_MFMA(a4[tt], xb[tt], h1v[mb]);
-          }
-        }
-      }
-#pragma unroll
-    for (int mb = 0; mb < HB; ++mb)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) h1v[mb][r] = dyn_act(h1v[mb][r] + b1s[32 * mb + unit_of(r, hi)], a.dact);
-    // -- dynamics layer 2: register r of h1v[mb] holds unit 32 mb + unit_of(r, hi), the B operand of k-step (mb, r) as it lies
-    f32x16 h2v[HB];
-#pragma unroll
-    for (int ob = 0; ob < HB; ++ob) {
-      f32x16 acc = (f32x16)(0.f);
-      const float* wrow = &W2s[(32 * ob + j) * S2 + 4 * hi];
-#pragma unroll
-      for (int mb = 0; mb < HB; ++mb)
-#pragma unroll
-        for (int rq = 0; rq < 4; ++rq) {
-          const f32x4 a4 = *(const f32x4*)(wrow + 32 * mb + 8 * rq);
-#pragma unroll
-          for (int tt = 0; tt < 4; ++tt) acc = MJX_MFMA(a4[tt], h1v[mb][4 * rq + tt], acc);
-        }
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[r] = dyn_act(acc[r] + b2s[32 * ob + unit_of(r, hi)], a.dact);
-      h2v[ob] = acc;
-    }
-    // -- dynamics output: affine, mask, residual as in dyn_net_tile -> s' (blocks beyond n stay exactly 0)
+    chain_l1_actions(h1v, HB, im.l1(), L, im.n8, an, NQA);
+    chain_l1_state(h1v, HB, im.l1(), L, 0, s, NQS);
     f32x16 sp[NB];
-#pragma unroll
-    for (int b = 0; b < NB; ++b) {
-      f32x16 acc = (f32x16)(0.f);
-      const float* wrow = &W3s[(32 * b + j) * S2 + 4 * hi];
-#pragma unroll
-      for (int mb = 0; mb < HB; ++mb)
-#pragma unroll
-        for (int rq = 0; rq < 4; ++rq) {
-          const f32x4 a4 = *(const f32x4*)(wrow + 32 * mb + 8 * rq);
-#pragma unroll
-          for (int tt = 0; tt < 4; ++tt) acc = MJX_MFMA(a4[tt], h2v[mb][4 * rq + tt], acc);
-        }
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int u = 32 * b + unit_of(r, hi);
-        float z = acc[r] + b3s[u];
-        if (a.flags & DYN_OUT_AFFINE) z = z * osc[u] + osh[u];
-        if (a.flags & DYN_MASK) z = z * msk[u];
-        if (a.flags & DYN_RESIDUAL) z = z + s[b][r];
-        sp[b][r] = z;
-      }
-    }
+    im.tail(L, h1v, s, sp, a.dact, a.flags);
     __builtin_amdgcn_sched_barrier(0);
     // -- reward layer 1 over [s | a | s']: the same registers again, under the reward net's own shift and scale
     f32x16 g1v[RB];
 #pragma unroll
     for (int mb = 0; mb < RB; ++mb) g1v[mb] = (f32x16)(0.f);
-#pragma unroll
-    for (int q = 0; q < PLAN_MAX_M8 / 8; ++q) {
-      if (q < NQA) {
-        const int c0 = n8 + 8 * q + 4 * hi;
-        float xb[4];
-#pragma unroll
-        for (int tt = 0; tt < 4; ++tt) xb[tt] = (an[4 * q + tt] - rsh[c0 + tt]) / rrs[c0 + tt];
-#pragma unroll
-        for (int mb = 0; mb < RB; ++mb) {
-          if (mb < g1b) {
-            const f32x4 a4 = *(const f32x4*)&V1s[(32 * mb + j) * T1 + c0];
-#pragma unroll
-            for (int tt = 0; tt < 4; ++tt) g1v[mb] = MJX_MFMA(a4[tt], xb[tt], g1v[mb]);
-          }
-        }
-      }
-    }
-#pragma unroll
-    for (int part = 0; part < 2; ++part)               // 0: s at column 0, 1: s' at column K1
-#pragma unroll
-      for (int b = 0; b < NB; ++b)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          if (4 * b + q < NQS) {
-            const int c0 = (part ? K1 : 0) + 32 * b + 8 * q + 4 * hi;
-            float xb[4];
-#pragma unroll
-            for (int tt = 0; tt < 4; ++tt) xb[tt] = ((part ? sp[b][4 * q + tt] : s[b][4 * q + tt]) - rsh[c0 + tt]) / rrs[c0 + tt];
-#pragma unroll
-            for (int mb = 0; mb < RB; ++mb) {
-              if (mb < g1b) {
-                const f32x4 a4 = *(const f32x4*)&V1s[(32 * mb + j) * T1 + c0];
-#pragma unroll
-                for (int tt = 0; tt < 4; ++tt) g1v[mb] = MJX_MFMA(a4[tt], xb[tt], g1v[mb]);
-              }
-            }
-          }
-        }
-#pragma unroll
-    for (int mb = 0; mb < RB; ++mb) {
-      if (mb < g1b) {                                    // (a block beyond g1b stays exactly 0 and is never read)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) g1v[mb][r] = dyn_act(g1v[mb][r] + c1s[32 * mb + unit_of(r, hi)], a.ract);
-      }
-    }
+    chain_l1_actions(g1v, g1b, rl1, L, im.n8, an, NQA);
+    chain_l1_state(g1v, g1b, rl1, L, 0, s, NQS);
+    chain_l1_state(g1v, g1b, rl1, L, K1, sp, NQS);
+    chain_bias_act(g1v, g1b, c1s, L, a.ract);
     __builtin_amdgcn_sched_barrier(0);
     // -- reward layer 2 and the scalar head: a per-lane dot over the h2 registers, then one add across the lane halves
     float dot = 0.f;
 #pragma unroll
     for (int ob = 0; ob < RB; ++ob) {
       if (ob < g2b) {
-        f32x16 acc = (f32x16)(0.f);
-        const float* wrow = &V2s[(32 * ob + j) * T2 + 4 * hi];
-#pragma unroll
-        for (int mb = 0; mb < RB; ++mb) {
-          if (mb < g1b) {
-#pragma unroll
-            for (int rq = 0; rq < 4; ++rq) {
-              const f32x4 a4 = *(const f32x4*)(wrow + 32 * mb + 8 * rq);
-#pragma unroll
-              for (int tt = 0; tt < 4; ++tt) acc = MJX_MFMA(a4[tt], g1v[mb][4 * rq + tt], acc);
-              if (RB > 2 && (rq & 1)) __builtin_amdgcn_sched_barrier(0);  // (weight loads are not hoisted further ahead than this: registers)
-            }
-          }
-        }
+        const f32x16 acc = chain_dense<RB, (RB > 2)>(V2s, T2, ob, L, g1v, g1b);
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const int u = 32 * ob + unit_of(r, hi);

@@ -9,31 +9,19 @@
 //                           scoring and weighting in fp64 with fixed summation orders (score_trajectory_ensemble
 //                           model_learning_mpc.py:85-99, score_trajectory :101-110, the softmax weighting :70-74)
 //
-// The rollout uses the scheme of k_mlp_predict128 (baseline.h) and the fused policy kernels: units on the MFMA M / K dimensions,
-// the tile's 32 trajectories on N, so the v_mfma_f32_32x32x2_f32 accumulator of layer l is the B operand of layer l + 1 as it
-// lies (register r = 4 q + t of lane half `hi` holds unit 8 q + 4 hi + t, unit_of).  A rollout adds one observation: the OUTPUT
-// layer's accumulator -- the next state -- is the layer-1 B operand of the NEXT time step.  No activation passes through LDS and
-// there is no barrier inside the time loop.
-//
-// Input features are laid out [state padded to n8 = a multiple of 8 | action padded to m8 = a multiple of 8]; W1's columns are
-// permuted and zero-padded to that layout when they are staged.  The state part of the layer-1 operand is the state accumulator
-// itself; the action part is read by each lane for its own trajectory and its own four k-slots, one step ahead of its use.
-// Hidden widths are padded to HW = 32 HB units with zero weights and biases: a padded unit is act(0) = 0 (ReLU and tanh) and
-// meets zero columns downstream.  State blocks beyond n are kept at exactly 0 (zero rows of W_out, zero bias / scale / shift / mask).
-//
-// LDS image (floats, row strides + 4 as in k_mlp_predict128; the kernel has no static LDS):
-//   W1s HW x (K1 + 4) | W2s HW x (HW + 4) | W3s 32 NB x (HW + 4) | b1 HW | b2 HW | b3 32 NB | in_shift K1 | in_scale + 1e-8 K1 |
-//   out_scale + 1e-8, out_shift, mask: 32 NB each                 -- 128 x 128 at n = 64, m = 32: 155.4 KiB of the 160 KiB.
+// The rollout is a register-chained MFMA MLP (mfma_chain.h: the scheme, the dynamics net's LDS image and the pieces of a forward).
+// A rollout adds one observation: the OUTPUT layer's accumulator -- the next state -- is the layer-1 B operand of the NEXT time
+// step, so the tail of a forward writes the state registers in place.  The action part of the layer-1 operand is read by each lane
+// for its own trajectory and its own four k-slots, one step ahead of its use.  There is no barrier inside the time loop, and the
+// kernel has no static LDS.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "dynamics.h"
-#include "fused_policy.h"
+#include "mfma_chain.h"
 
 namespace mjx {
 
-constexpr int PLAN_MAX_M8 = 32;       // action slots a lane keeps one step ahead: 4 k-steps x 4
 enum { PLAN_IDX_REFERENCE = 0, PLAN_IDX_TRAJECTORY = 1 };
 
 struct PlanArgs {
@@ -45,48 +33,16 @@ struct PlanArgs {
   int H, n, m, h1, h2, act, flags;
 };
 
-__host__ __device__ inline int plan_pad8(int v) { return (v + 7) & ~7; }
-__host__ __device__ inline size_t plan_lds_floats(int HB, int NB, int n, int m) {
-  const size_t HW = 32 * (size_t)HB, K1 = (size_t)plan_pad8(n) + plan_pad8(m);
-  return HW * (K1 + 4) + HW * (HW + 4) + 32 * NB * (HW + 4) + 2 * HW + 32 * NB + 2 * K1 + 3 * 32 * NB;
-}
-
 template <int HB, int NB>
 __global__ __launch_bounds__(256, 1) void k_plan_rollout(PlanArgs a) {
   extern __shared__ __attribute__((aligned(16))) float pls[];
-  constexpr int HW = 32 * HB, S2 = HW + 4, NS = 32 * NB;
-  const int n = a.n, m = a.m, h1 = a.h1, h2 = a.h2, n8 = plan_pad8(n), m8 = plan_pad8(m), K1 = n8 + m8, S1 = K1 + 4, din = n + m;
-  float* W1s = pls; float* W2s = W1s + HW * S1; float* W3s = W2s + HW * S2;
-  float* b1s = W3s + NS * S2; float* b2s = b1s + HW; float* b3s = b2s + HW;
-  float* ish = b3s + NS; float* irs = ish + K1; float* osc = irs + K1; float* osh = osc + NS; float* msk = osh + NS;
+  const int n = a.n, m = a.m, din = n + m;
+  DynImage<HB, NB> im;
+  im.carve(pls, n, m);
   const int tid = threadIdx.x, lane = tid & 63, j = lane & 31, hi = lane >> 5, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const ChainLane L{j, hi};
   const int k = blockIdx.y;
-  const float* __restrict__ P = a.P + k * a.Pstride;
-  const float* __restrict__ tr = a.tr + (int64_t)k * (2 * din + 2 * n);
-  const int64_t oB1 = (int64_t)h1 * din, oW2 = oB1 + h1, oB2 = oW2 + (int64_t)h2 * h1, oW3 = oB2 + h2, oB3 = oW3 + (int64_t)n * h2;
-  // ---- prologue: a wave stages whole rows (lanes along the row: coalesced reads, no division)
-  for (int u = tid >> 6; u < HW; u += 4) {
-    for (int c = lane; c < K1; c += 64) {
-      const int f = c < n8 ? (c < n ? c : -1) : (c - n8 < m ? n + c - n8 : -1);
-      W1s[u * S1 + c] = (u < h1 && f >= 0) ? P[(int64_t)u * din + f] : 0.f;
-    }
-    for (int c = lane; c < HW; c += 64) W2s[u * S2 + c] = (u < h2 && c < h1) ? P[oW2 + (int64_t)u * h1 + c] : 0.f;
-  }
-  for (int u = tid >> 6; u < NS; u += 4)
-    for (int c = lane; c < HW; c += 64) W3s[u * S2 + c] = (u < n && c < h2) ? P[oW3 + (int64_t)u * h2 + c] : 0.f;
-  for (int i = tid; i < HW; i += 256) { b1s[i] = i < h1 ? P[oB1 + i] : 0.f; b2s[i] = i < h2 ? P[oB2 + i] : 0.f; }
-  for (int i = tid; i < NS; i += 256) {
-    const float sc = i < n ? tr[2 * din + n + i] : 0.f;
-    b3s[i] = i < n ? P[oB3 + i] : 0.f;
-    osc[i] = i < n ? sc + 1e-8f : 0.f;
-    osh[i] = i < n ? tr[2 * din + i] : 0.f;
-    msk[i] = (i < n && sc >= 1e-8f) ? 1.f : 0.f;
-  }
-  for (int c = tid; c < K1; c += 256) {
-    const int f = c < n8 ? (c < n ? c : -1) : (c - n8 < m ? n + c - n8 : -1);
-    ish[c] = f >= 0 ? tr[f] : 0.f;
-    irs[c] = f >= 0 ? tr[din + f] + 1e-8f : 1.f;
-  }
+  im.stage(a.P + k * a.Pstride, a.tr + (int64_t)k * (2 * din + 2 * n), a.h1, a.h2, tid);
   __syncthreads();
   const int64_t tile = (int64_t)blockIdx.x * 4 + wave, row = tile * 32 + j;
   if (tile * 32 >= a.N) return;                       // (after the only barrier)
@@ -101,7 +57,7 @@ __global__ __launch_bounds__(256, 1) void k_plan_rollout(PlanArgs a) {
       const float v = a.s0[vrow * a.s0_stride + (f < n ? f : 0)];
       s[b][r] = (valid && f < n) ? v : 0.f;
     }
-  const int NQS = n8 / 8, NQA = m8 / 8;
+  const int NQS = im.n8 / 8, NQA = im.m8 / 8;
   const float* __restrict__ arow = a.actions + vrow * a.H * (int64_t)m;
   float* __restrict__ orow = a.obs + ((int64_t)k * a.N + vrow) * a.H * (int64_t)n;
   // this lane's action slots of step t: slot (q, tt) is action 8 q + 4 hi + tt
@@ -125,21 +81,7 @@ __global__ __launch_bounds__(256, 1) void k_plan_rollout(PlanArgs a) {
     f32x16 h1v[HB];
 #pragma unroll
     for (int mb = 0; mb < HB; ++mb) h1v[mb] = (f32x16)(0.f);
-#pragma unroll
-    for (int q = 0; q < PLAN_MAX_M8 / 8; ++q) {
-      if (q < NQA) {
-        const int c0 = n8 + 8 * q + 4 * hi;
-        float xb[4];
-#pragma unroll
-        for (int tt = 0; tt < 4; ++tt) xb[tt] = (an[4 * q + tt] - ish[c0 + tt]) / irs[c0 + tt];
-#pragma unroll
-        for (int mb = 0; mb < HB; ++mb) {
-          const f32x4 a4 = *(const f32x4*)&W1s[(32 * mb + j) * S1 + c0];
-#pragma unroll
-          for (int tt = 0; tt < 4; ++tt) h1v[mb] = MJX_MFMA(a4[tt], xb[tt], h1v[mb]);
-        }
-      }
-    }
+    chain_l1_actions(h1v, HB, im.l1(), L, im.n8, an, NQA);
     if (t + 1 < a.H) {                                // the next step's actions: in flight under the rest of this step
 #pragma unroll
       for (int q = 0; q < PLAN_MAX_M8 / 8; ++q)
@@ -149,68 +91,9 @@ __global__ __launch_bounds__(256, 1) void k_plan_rollout(PlanArgs a) {
           if (q < NQA && f < m) an[4 * q + tt] = arow[(int64_t)(t + 1) * m + f];
         }
     }
-#pragma unroll
-    for (int b = 0; b < NB; ++b)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        if (4 * b + q < NQS) {
-          const int c0 = 32 * b + 8 * q + 4 * hi;
-          float xb[4];
-#pragma unroll
-          for (int tt = 0; tt < 4; ++tt) xb[tt] = (s[b][4 * q + tt] - ish[c0 + tt]) / irs[c0 + tt];
-#pragma unroll
-          for (int mb = 0; mb < HB; ++mb) {
-            const f32x4 a4 = *(const f32x4*)&W1s[(32 * mb + j) * S1 + c0];
-#pragma unroll
-            for (int tt = 0; tt < 4; ++tt) h1v[mb] = MJX_MFMA(a4[tt], xb[tt], h1v[mb]);
-          }
-        }
-      }
-#pragma unroll
-    for (int mb = 0; mb < HB; ++mb)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) h1v[mb][r] = dyn_act(h1v[mb][r] + b1s[32 * mb + unit_of(r, hi)], a.act);
-    // layer 2: register r of h1v[mb] holds unit 32 mb + unit_of(r, hi) -- the B operand of k-step (mb, r) as it lies
-    f32x16 h2v[HB];
-#pragma unroll
-    for (int ob = 0; ob < HB; ++ob) {
-      f32x16 acc = (f32x16)(0.f);
-      const float* wrow = &W2s[(32 * ob + j) * S2 + 4 * hi];
-#pragma unroll
-      for (int mb = 0; mb < HB; ++mb)
-#pragma unroll
-        for (int rq = 0; rq < 4; ++rq) {
-          const f32x4 a4 = *(const f32x4*)(wrow + 32 * mb + 8 * rq);
-#pragma unroll
-          for (int tt = 0; tt < 4; ++tt) acc = MJX_MFMA(a4[tt], h1v[mb][4 * rq + tt], acc);
-        }
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[r] = dyn_act(acc[r] + b2s[32 * ob + unit_of(r, hi)], a.act);
-      h2v[ob] = acc;
-    }
-    // output layer and 4.: affine, mask, residual as in dyn_net_tile; the result is the next step's layer-1 operand
-#pragma unroll
-    for (int b = 0; b < NB; ++b) {
-      f32x16 acc = (f32x16)(0.f);
-      const float* wrow = &W3s[(32 * b + j) * S2 + 4 * hi];
-#pragma unroll
-      for (int mb = 0; mb < HB; ++mb)
-#pragma unroll
-        for (int rq = 0; rq < 4; ++rq) {
-          const f32x4 a4 = *(const f32x4*)(wrow + 32 * mb + 8 * rq);
-#pragma unroll
-          for (int tt = 0; tt < 4; ++tt) acc = MJX_MFMA(a4[tt], h2v[mb][4 * rq + tt], acc);
-        }
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int u = 32 * b + unit_of(r, hi);
-        float z = acc[r] + b3s[u];
-        if (a.flags & DYN_OUT_AFFINE) z = z * osc[u] + osh[u];
-        if (a.flags & DYN_MASK) z = z * msk[u];
-        if (a.flags & DYN_RESIDUAL) z = z + s[b][r];
-        s[b][r] = z;
-      }
-    }
+    chain_l1_state(h1v, HB, im.l1(), L, 0, s, NQS);
+    // the rest of the forward and 4.: the result is the next step's layer-1 operand
+    im.tail(L, h1v, s, s, a.act, a.flags);
   }
 }
 
