@@ -438,6 +438,30 @@ int mjx_model_rollout(const float* s0, int64_t N, int H, int K, const int* pol_s
                       const int* dyn_sizes, int dyn_n_sizes, const float* dyn_params, const float* dyn_tr, int act,
                       int flags, const float* a_min, const float* a_max, const float* s_min, const float* s_max,
                       float* obs_out, float* act_out, void* stream);
+/* Which route mjx_policy_rollout takes for a policy pol_sizes = [n, p..., m] on a dynamics net dyn_sizes = [n + m, h..., n]:
+ * 1 = the register-resident MFMA rollout that keeps both nets in LDS (csrc/policy_rollout.h): a dynamics net as mjx_plan_route
+ * serves it, exactly two policy hidden layers of 1 .. 64 units each (each padded to a multiple of 32 in LDS), and the two LDS
+ * images together within 160 KiB; 0 = the generic rollout of mjx_model_rollout; < 0 = bad sizes (a policy that does not fit
+ * the dynamics net's n and m included).  The policy image in floats, after the dynamics image of mjx_plan_route, with
+ * P1 / P2 = the widths rounded up to 32, n8 = n rounded up to 8 and NB = ceil(n / 32):
+ * P1 (n8 + 4) + P2 (P1 + 4) + 32 (P2 + 4) + P1 + P2 + 32 + 2 n8 + 5 * 32 + 2 * 32 NB.  Arithmetic only: no device work and
+ * no runtime call.  MJX_POLICY_ROLLOUT_MFMA=0 (read by mjx_policy_rollout per call) forces route 0. */
+int mjx_policy_rollout_route(const int* pol_sizes, int pol_n_sizes, const int* dyn_sizes, int dyn_n_sizes);
+/* mjx_model_rollout's policy mode (no given actions) with a start state and noise that the members may share: s0 is one
+ * state for every trajectory (s0_stride 0) or N x n (s0_stride n); noise is one H x N x m block for all members
+ * (noise_stride 0), K of them (noise_stride H N m) or NULL (eval mode).  Everything else as for mjx_model_rollout; the
+ * bounds may be NULL in pairs.  *route_out (a host int, may be NULL) receives the route taken (mjx_policy_rollout_route).
+ * On route 0 the outputs are mjx_model_rollout's bit for bit, on the state tiled to N rows and on K copies of a shared
+ * noise block.  N = 0 or H = 0 returns MJX_OK without a launch (and reports the route); bad arguments return
+ * MJX_ERR_ARG and touch nothing.  Route 0 uses per-host-thread scratch (as mjx_plan_rollout's generic route: the block
+ * of the calling thread for this entry on the current device and stream). */
+int mjx_policy_rollout(const float* s0, int64_t s0_stride, int64_t N, int H, int K, const int* pol_sizes, int pol_n_sizes,
+                       const float* pol_params, const float* pol_tr, const float* noise, int64_t noise_stride,
+                       const int* dyn_sizes, int dyn_n_sizes, const float* dyn_params, const float* dyn_tr, int act,
+                       int flags, const float* a_min, const float* a_max, const float* s_min, const float* s_max,
+                       float* obs_out, float* act_out, int* route_out, void* stream);
+/* dst[i] = (double)src[i] for i < count, on the device (what mjx_plan_score takes for actions a kernel wrote as fp32). */
+int mjx_cast_f32_f64(const float* src, int64_t count, double* dst, void* stream);
 /* fit_model (nn_dynamics.py:344-385) behind fit_dynamics (:87-116) / fit_reward (:118-147): `steps` minibatch steps of
  * torch.optim.Adam(lr, weight_decay=wd) on the MSE over batch x d_out.  x: N x d_in raw inputs, normalised once with
  * in_tr ([shift, scale]); y: N x d_out raw targets; out_tr = [out_shift, out_scale].  target_mode 0: the loss runs

@@ -14,8 +14,11 @@ import torch
 from ..._lib import check, load, ptr
 from ...utils import process_samples
 from ..npg_cg import NPG
-from .nn_dynamics import WorldModel, _device, _stream, ensemble_forward, ensemble_path_rewards
-from .sampling import _as_env, draw_rollout_noise, rollout_models
+from .nn_dynamics import (WorldModel, _device, _ints, _stream, ensemble_forward, ensemble_path_rewards, members_pack_key,
+                          pack_dynamics_members, pack_reward_members, path_rewards_call)
+from .sampling import _as_env, draw_rollout_noise, rollout_bounds, rollout_models, rollout_models_device
+
+REFINE_LARGE_VALUE = float(1e2)     # the refined call's state / action bounds: policy_rollout's default large_value
 
 
 def truncation_points(models, paths, truncate_lim):
@@ -41,6 +44,9 @@ def truncation_points(models, paths, truncate_lim):
 
 
 class ModelAccelNPG(NPG):
+    # (an instance pickled before the refinement existed acts as it did)
+    refine_gamma, refine_omega, _refine_pack, _refine_last, _refine_packs = 1.0, 0.0, None, None, 0
+
     def __init__(self, learned_model=None,
                  refine=False,
                  kappa=5.0,
@@ -48,8 +54,11 @@ class ModelAccelNPG(NPG):
                  plan_paths=100,
                  reward_function=None,
                  termination_function=None,
+                 refine_gamma=1.0,
+                 refine_omega=0.0,
                  **kwargs):
-        """Arguments as in the reference (model_accel_npg.py:24-41)."""
+        """Arguments as in the reference (model_accel_npg.py:24-41), plus refine_gamma and refine_omega: the discount and the
+        weight of the per-trajectory ensemble disagreement in get_refined_action's trajectory scores."""
         super(ModelAccelNPG, self).__init__(**kwargs)
         if learned_model is None:
             raise ValueError("Algorithm requires a (list of) learned dynamics model")
@@ -59,6 +68,10 @@ class ModelAccelNPG(NPG):
             self.learned_model = learned_model
         self.refine, self.kappa, self.plan_horizon, self.plan_paths = refine, kappa, plan_horizon, plan_paths
         self.reward_function, self.termination_function = reward_function, termination_function
+        self.refine_gamma, self.refine_omega = refine_gamma, refine_omega
+        self._refine_pack = None    # (key, device blocks, held tensors) of the members' parameters and transforms
+        self._refine_last = None    # (R, S, route) of the last refined call, on the device
+        self._refine_packs = 0      # how often the members were packed
 
     def to(self, device):
         for model in self.learned_model:
@@ -172,5 +185,100 @@ class ModelAccelNPG(NPG):
             return self.policy.get_action(observation)
         return self.get_refined_action(observation)
 
+    # ---- reward-based refinement around the policy (the reference's stub, model_accel_npg.py:191-196)
+    def __getstate__(self):
+        d = super(ModelAccelNPG, self).__getstate__()          # (device blocks stay with the process that made them)
+        d["_refine_pack"], d["_refine_last"] = None, None
+        return d
+
+    def _refine_learned(self):
+        return all(getattr(mdl, "learn_reward", False) for mdl in self.learned_model)
+
+    def _refine_packed(self, dev):
+        """the members' parameters and transforms on the device, packed once and again when a member changed
+        (nn_dynamics.members_pack_key, the recipe MPCPolicy keys its own copy on)"""
+        learned = self._refine_learned()
+        key, held = members_pack_key(self.learned_model, dev, learned)
+        if self._refine_pack is None or self._refine_pack[0] != key:
+            pk = pack_dynamics_members(self.learned_model, dev)
+            n, m = pk["sizes"][-1], pk["sizes"][0] - pk["sizes"][-1]
+            pk["bnd"], pk["bnd_value"] = rollout_bounds(n, m, dev, large_value=REFINE_LARGE_VALUE), REFINE_LARGE_VALUE
+            if learned:
+                pk["rew"] = pack_reward_members(self.learned_model, dev)
+            self._refine_pack = (key, pk, held)
+            self._refine_packs += 1
+        return self._refine_pack[1]
+
+    def invalidate(self):
+        """drop the device copy of the members (after a write to ``p.data`` that went round this package's own functions)"""
+        self._refine_pack = None
+
+    def refine_route(self):
+        """the route of the last refined call's rollout (1: the register-resident MFMA policy rollout, 0: the generic one);
+        before any call, what ``mjx_policy_rollout_route`` answers for the policy and the members"""
+        if self._refine_last is not None:
+            return self._refine_last[2]
+        net = self.learned_model[0].dynamics_net
+        ds = tuple(net.layer_sizes)
+        ps = (net.state_dim,) + tuple(self.policy.hidden_sizes) + (net.act_dim,)
+        return int(load().mjx_policy_rollout_route(_ints(ps), len(ps), _ints(ds), len(ds)))
+
+    def last_scores(self):
+        """(R, S) of the last refined call: the K N trajectory scores and their softmax weights (fp64, read back on demand)"""
+        if self._refine_last is None:
+            return None
+        return self._refine_last[0].cpu().numpy(), self._refine_last[1].cpu().numpy()
+
     def get_refined_action(self, observation):
-        raise NotImplementedError
+        """Roll ``plan_paths`` noisy policy trajectories of ``plan_horizon`` steps out from ``observation`` on every learned
+        model and return the reward-weighted first action, as ``[action, {'mean': action, 'evaluation': action, 'log_std': ...}]``
+        (the shape ``policy.get_action`` returns, so ``sample_paths`` and ``evaluate_policy`` take it).
+
+        One call, with K = len(learned_model), N = plan_paths, H = plan_horizon:
+
+        1. noise = ``draw_rollout_noise(1, H, N, m)`` from torch's global stream, SHARED by all members: every member starts
+           from the same state with the same noise, so the first action of trajectory i is the same on every member and the
+           members differ only in where their dynamics take it (as ``MPCPolicy``'s members share action sequences);
+        2. ``mjx_policy_rollout`` (one launch; bounds +-1e2 as ``policy_rollout`` defaults);
+        3. rewards: every member's reward net on the device (``mjx_path_rewards``, nothing read back) when all members learn
+           rewards, else one read-back and ``self.reward_function(dict(observations, actions))`` per member as ``train_step``
+           calls it and one upload; with neither, ``ValueError``;
+        4. ``mjx_plan_score`` with ``kappa``, ``refine_gamma`` and ``refine_omega`` (the per-trajectory disagreement term; off
+           at 0) on member 0's actions widened to fp64;
+        5. one read-back of row 0 of the weighted sequence: sum_i (sum_k S[k N + i]) a[i, 0] / (sum S + 1e-6).  Rows t >= 1 are
+           member 0's later actions under the same weights; they are not used.
+
+        ``termination_function`` and ensemble-disagreement truncation play no part: every trajectory counts for all H steps."""
+        learned = self._refine_learned()
+        if not learned and not callable(self.reward_function):
+            raise ValueError("get_refined_action needs members that learn rewards (WorldModel(learn_reward=True)) or a reward_function")
+        dev = _device()
+        lib = load()
+        pk = self._refine_packed(dev)
+        net = self.learned_model[0].dynamics_net
+        K, N, H, n, m = len(self.learned_model), int(self.plan_paths), int(self.plan_horizon), net.state_dim, net.act_dim
+        st = _stream(dev)
+        noise = draw_rollout_noise(1, H, N, m)[0]
+        info = {}
+        s0 = np.ascontiguousarray(np.asarray(observation).reshape(-1))
+        obs_d, act_d = rollout_models_device(self.learned_model, self.policy, s0, H, noise, large_value=REFINE_LARGE_VALUE, num_traj=N,
+                                             packed=pk, info=info)
+        if learned:
+            r_d = torch.empty((K, N, H), dtype=torch.float64, device=dev)
+            path_rewards_call(pk["rew"], obs_d, act_d, False, N * H, K, None, r_d, dev)
+        else:
+            obs_h, act_h = obs_d.cpu().numpy(), act_d.cpu().numpy()
+            rewards = np.empty((K, N, H), np.float64)
+            for k in range(K):
+                rewards[k] = self.reward_function(dict(observations=obs_h[k], actions=act_h[k]))['rewards']
+            r_d = torch.from_numpy(rewards).to(dev)
+        a64 = torch.empty((N, H, m), dtype=torch.float64, device=dev)
+        check(lib.mjx_cast_f32_f64(ptr(act_d), N * H * m, ptr(a64), st))
+        out = torch.empty(H * m + 2 * K * N, dtype=torch.float64, device=dev)
+        seq_d, R_d, S_d = out[:H * m], out[H * m:H * m + K * N], out[H * m + K * N:]
+        omega = float(self.refine_omega)
+        check(lib.mjx_plan_score(ptr(obs_d) if omega != 0.0 else None, ptr(r_d), ptr(a64), K, N, H, n, m, float(self.kappa),
+                                 float(self.refine_gamma), omega, 1, ptr(R_d), ptr(S_d), ptr(seq_d), st))
+        action = seq_d[:m].cpu().numpy()
+        self._refine_last = (R_d, S_d, info["route"])
+        return [action, {'mean': action, 'evaluation': action, 'log_std': self.policy.log_std_val}]

@@ -38,7 +38,7 @@ import numpy as np
 import torch
 
 from ..._lib import check, load, ptr
-from .nn_dynamics import (_act_code, _device, _flags, _flat_params, _ints, _packed_transforms, _stream, pack_reward_members,
+from .nn_dynamics import (_device, _ints, _stream, members_pack_key, pack_dynamics_members, pack_reward_members,
                           path_rewards_call)
 
 
@@ -116,34 +116,14 @@ class MPCPolicy(object):
         ``_version`` (in-place edits) and storage; activation and flags.  On reward='learned' the same for every member's reward
         net (``fit_reward``'s write-back bumps its counter), with output transforms that are plain numbers by value.  The tensors
         are returned to be HELD beside the key, so that an id() in it cannot come back as another tensor's."""
-        nets = [mdl.dynamics_net for mdl in self._members()]
-        held = [t for net in nets for t in list(net.parameters()) + list(net.get_params()["transforms"])]
-        if self.reward == 'learned':
-            # the reward nets too; their out_shift / out_scale are plain numbers or tensors (nn_dynamics.py:281-311)
-            rnets = [mdl.reward_net for mdl in self._members()]
-            nets = nets + rnets
-            held += [t for net in rnets for t in list(net.parameters()) + list(net.get_params()["transforms"]) +
-                     [v for v in (net.out_shift, net.out_scale) if isinstance(v, torch.Tensor)]]
-            outs = tuple(float(v) for net in rnets for v in (net.out_shift, net.out_scale) if not isinstance(v, torch.Tensor))
-        else:
-            outs = ()
-        key = (str(dev),) + outs + tuple((id(net), getattr(net, "_generation", 0), _act_code(net), _flags(net)) for net in nets) + \
-            tuple((id(t), t._version, t.data_ptr()) for t in held)
-        return key, held
+        return members_pack_key(self._members(), dev, self.reward == 'learned')
 
     def _packed(self, dev):
         key, held = self._pack_key(dev)
         if self._pack is None or self._pack[0] != key:
-            nets = [mdl.dynamics_net for mdl in self._members()]
-            sizes = tuple(nets[0].layer_sizes)
-            for net in nets:
-                assert tuple(net.layer_sizes) == sizes, "ensemble members must share one shape"
-            assert len(set((_act_code(net), _flags(net)) for net in nets)) == 1, \
-                "ensemble members must share activation and output transforms"
-            assert (nets[0].state_dim, nets[0].act_dim) == (self.n, self.m), "the models' dims are not the environment's"
-            P = torch.stack([_flat_params(net, dev) for net in nets])
-            tr = torch.stack([_packed_transforms(net, dev) for net in nets])
-            pk = dict(sizes=sizes, P=P, tr=tr, act=_act_code(nets[0]), flags=_flags(nets[0]))
+            pk = pack_dynamics_members(self._members(), dev)
+            net0 = self._members()[0].dynamics_net
+            assert (net0.state_dim, net0.act_dim) == (self.n, self.m), "the models' dims are not the environment's"
             if self.reward == 'learned':
                 pk["rew"] = pack_reward_members(self._members(), dev)
             self._pack = (key, pk, held)

@@ -581,6 +581,18 @@ def ensemble_path_rewards(models, observations, actions):
     return r.to('cpu').data.numpy().reshape(K, N, H)
 
 
+def pack_dynamics_members(models, dev):
+    """the device blocks a rollout over K members reads, for members that share shape, activation and flags (asserted):
+    dict(sizes, P (K x params), tr (K x transforms), act, flags)"""
+    nets = [mdl.dynamics_net for mdl in models]
+    sizes = tuple(nets[0].layer_sizes)
+    for net in nets:
+        assert tuple(net.layer_sizes) == sizes, "ensemble members must share one shape"
+    assert len(set((_act_code(net), _flags(net)) for net in nets)) == 1, "ensemble members must share activation and output transforms"
+    return dict(sizes=sizes, P=torch.stack([_flat_params(net, dev) for net in nets]),
+                tr=torch.stack([_packed_transforms(net, dev) for net in nets]), act=_act_code(nets[0]), flags=_flags(nets[0]))
+
+
 def pack_reward_members(models, dev):
     """the device blocks ``mjx_path_rewards`` reads, for K members that share shapes, activation and flags (asserted, as
     ``rollout_models`` does): dict(dyn_sizes, dyn_P, dyn_tr, dyn_act, dyn_flags, rew_sizes, rew_P, rew_tr, rew_act)"""
@@ -594,6 +606,29 @@ def pack_reward_members(models, dev):
                 dyn_tr=torch.stack([_packed_transforms(net, dev) for net in dyn]), dyn_act=_act_code(dyn[0]), dyn_flags=_flags(dyn[0]),
                 rew_sizes=tuple(rew[0].layer_sizes), rew_P=torch.stack([_flat_params(net, dev) for net in rew]),
                 rew_tr=torch.stack([_packed_transforms(net, dev) for net in rew]), rew_act=_act_code(rew[0]))
+
+
+def members_pack_key(members, dev, with_rewards):
+    """What a device copy of ensemble members is made from -> (key, the tensors the key names).  Per member: the net's
+    generation counter, which every write path of this package bumps (the fit's write-back through ``p.data.copy_``, which
+    leaves ``p._version`` alone, ``set_params``, ``set_transformations``); per parameter and transform tensor its identity,
+    ``_version`` (in-place edits) and storage; activation and flags.  With ``with_rewards`` the same for every member's reward
+    net (``fit_reward``'s write-back bumps its counter), with output transforms that are plain numbers by value.  The tensors
+    are returned to be HELD beside the key, so that an id() in it cannot come back as another tensor's."""
+    nets = [mdl.dynamics_net for mdl in members]
+    held = [t for net in nets for t in list(net.parameters()) + list(net.get_params()["transforms"])]
+    if with_rewards:
+        # the reward nets too; their out_shift / out_scale are plain numbers or tensors (nn_dynamics.py:281-311)
+        rnets = [mdl.reward_net for mdl in members]
+        nets = nets + rnets
+        held += [t for net in rnets for t in list(net.parameters()) + list(net.get_params()["transforms"]) +
+                 [v for v in (net.out_shift, net.out_scale) if isinstance(v, torch.Tensor)]]
+        outs = tuple(float(v) for net in rnets for v in (net.out_shift, net.out_scale) if not isinstance(v, torch.Tensor))
+    else:
+        outs = ()
+    key = (str(dev),) + outs + tuple((id(net), getattr(net, "_generation", 0), _act_code(net), _flags(net)) for net in nets) + \
+        tuple((id(t), t._version, t.data_ptr()) for t in held)
+    return key, held
 
 
 def path_rewards_call(pk, obs_d, act_d, shared, rows, K, r32, r64, dev):

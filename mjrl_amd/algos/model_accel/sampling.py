@@ -8,11 +8,14 @@ is the reference's: ``torch.randn((N, m))`` once per step, drawn on the host fro
 (``sample_paths``, ``evaluate_policy``) are host loops around ``policy.get_action`` -- for an
 :class:`~mjrl_amd.algos.model_accel.model_learning_mpc.MPCPolicy` that call is where the GPU work happens.
 """
+import ctypes
+
 import numpy as np
 import torch
 
 from ..._lib import check, load, ptr
-from .nn_dynamics import _act_code, _device, _f32, _flags, _flat_params, _ints, _packed_transforms, _stream
+from .nn_dynamics import (_act_code, _device, _f32, _flags, _flat_params, _ints, _packed_transforms, _stream,
+                          pack_dynamics_members)
 
 
 def _as_env(env, env_kwargs=None):
@@ -81,6 +84,61 @@ def rollout_models(models, policy, init_states, horizon, noise=None, s_min=None,
         check(lib.mjx_model_rollout(ptr(s0), N, H, K, None, 0, None, None, None, ptr(ad), _ints(sizes), len(sizes), ptr(P),
                                     ptr(tr), act, flags, None, None, None, None, ptr(obs), ptr(act_out), _stream(dev)))
     return obs.cpu().numpy(), act_out.cpu().numpy()
+
+
+def rollout_bounds(n, m, dev, s_min=None, s_max=None, a_min=None, a_max=None, large_value=float(1e2)):
+    """[a_min, a_max, s_min, s_max] as fp32 device vectors (m, m, n, n); None = -/+ large_value (enforce_tensor_bounds)"""
+    return [_bound(a_min, m, -large_value).to(dev), _bound(a_max, m, large_value).to(dev),
+            _bound(s_min, n, -large_value).to(dev), _bound(s_max, n, large_value).to(dev)]
+
+
+def rollout_models_device(models, policy, s0, horizon, noise=None, s_min=None, s_max=None, a_min=None, a_max=None,
+                          large_value=float(1e2), num_traj=None, packed=None, info=None):
+    """The policy on K learned models in one ``mjx_policy_rollout`` launch, results left on the device
+    -> (obs (K, N, H, n), act (K, N, H, m)) fp32 device tensors.
+
+    s0: one state (n,) for every trajectory, or (N, n).  noise: (H, N, m) shared by all members, (K, H, N, m), or None
+    (eval mode).  N comes from s0, else from the noise, else from ``num_traj``.  ``packed``: the members already on the device
+    (``nn_dynamics.pack_dynamics_members``; with ``bnd`` / ``bnd_value`` also the default bound vectors, ``rollout_bounds``);
+    otherwise they are flattened and uploaded here.  The policy's parameters and transforms are uploaded on every call.
+    ``info`` (a dict) receives ``route``: 1 = the register-resident MFMA rollout (csrc/policy_rollout.h), 0 = the generic
+    persistent rollout."""
+    dev = _device()
+    net0 = models[0].dynamics_net
+    n, m = net0.state_dim, net0.act_dim
+    K, H = len(models), int(horizon)
+    if packed is None:
+        packed = pack_dynamics_members(models, dev)
+    sizes = tuple(packed["sizes"])
+    assert (sizes[0], sizes[-1]) == (n + m, n) and packed["P"].shape[0] == K
+    s0_d = _f32(s0, dev)
+    nz = None if noise is None else _f32(noise, dev)
+    if s0_d.dim() == 2:
+        N = s0_d.shape[0]
+    elif nz is not None:
+        N = nz.shape[-2]
+    else:
+        N = int(num_traj)
+    assert tuple(s0_d.shape) in ((n,), (N, n)), "s0 is one state (n) or one per trajectory (N, n)"
+    if nz is not None:
+        assert tuple(nz.shape) in ((H, N, m), (K, H, N, m)), "noise is (H, N, m) or (K, H, N, m)"
+    pol_sizes = (n,) + tuple(policy.hidden_sizes) + (m,)
+    pol_P = _f32(policy.get_param_values(), dev)
+    pol_tr = _f32(policy.model.packed_transforms(), dev)
+    if a_min is None and a_max is None and s_min is None and s_max is None and packed.get("bnd_value") == large_value:
+        bnd = packed["bnd"]                               # the default +-large_value blocks, already on the device
+    else:
+        bnd = rollout_bounds(n, m, dev, s_min, s_max, a_min, a_max, large_value)
+    obs = torch.empty((K, N, H, n), dtype=torch.float32, device=dev)
+    act_out = torch.empty((K, N, H, m), dtype=torch.float32, device=dev)
+    route = ctypes.c_int(-1)
+    check(load().mjx_policy_rollout(ptr(s0_d), n if s0_d.dim() == 2 else 0, N, H, K, _ints(pol_sizes), len(pol_sizes), ptr(pol_P),
+                                    ptr(pol_tr), ptr(nz), H * N * m if (nz is not None and nz.dim() == 4) else 0, _ints(sizes),
+                                    len(sizes), ptr(packed["P"]), ptr(packed["tr"]), packed["act"], packed["flags"], ptr(bnd[0]),
+                                    ptr(bnd[1]), ptr(bnd[2]), ptr(bnd[3]), ptr(obs), ptr(act_out), ctypes.byref(route), _stream(dev)))
+    if info is not None:
+        info["route"] = route.value
+    return obs, act_out
 
 
 # ===========================================================

@@ -178,4 +178,71 @@ struct DynImage {
   }
 };
 
+// ---- 6. a tanh policy [n, p1, p2, m] (FCNetwork with its transforms and log_std) in LDS, for a kernel that lets it act on state
+// accumulators (policy_rollout.h).  Hidden widths padded to P1 = 32 p1b and P2 = 32 p2b (run-time block counts, 1 .. POL_MAX_PB),
+// the output to one block of 32 action units in the action slot layout (unit f of the block is action f).  In floats:
+//   Q1s P1 x (n8 + 4) | Q2s P2 x (P1 + 4) | Q3s 32 x (P2 + 4) | d1 P1 | d2 P2 | d3 32 | in_shift n8 | in_scale + 1e-8 n8 (1 where
+//   padded) | out_scale, out_shift, exp(log_std), a_lo, a_hi: 32 each | s_lo, s_hi: NS = 32 NB each
+// pol_lds_floats sums these terms in carve()'s order: carve(base) - base == pol_lds_floats for the same (p1, p2, n, NB).
+// Padded action units have zero rows of Q3s and zero d3 / out_scale / out_shift / sigma, padded units of either kind the bounds
+// [0, 0]; absent bounds are -inf / +inf.
+constexpr int POL_MAX_PB = 2;
+__host__ __device__ inline size_t pol_lds_floats(int p1, int p2, int n, int NB) {
+  const size_t P1 = 32 * (size_t)((p1 + 31) / 32), P2 = 32 * (size_t)((p2 + 31) / 32), n8 = (size_t)plan_pad8(n);
+  return P1 * (n8 + 4) + P2 * (P1 + 4) + 32 * (P2 + 4) + P1 + P2 + 32 + 2 * n8 + 5 * 32 + 2 * 32 * (size_t)NB;
+}
+
+template <int NB>
+struct PolImage {
+  static constexpr int NS = 32 * NB;
+  float *Q1s, *Q2s, *Q3s, *d1, *d2, *d3, *ish, *irs, *osc, *osh, *sig, *alo, *ahi, *slo, *shi;
+  int n, m, n8, p1, p2, p1b, p2b, P1, P2, U1, U2, U3;
+
+  __device__ __forceinline__ float* carve(float* base, int n_, int m_, int p1_, int p2_) {
+    n = n_; m = m_; n8 = plan_pad8(n); p1 = p1_; p2 = p2_;
+    p1b = (p1 + 31) >> 5; p2b = (p2 + 31) >> 5; P1 = 32 * p1b; P2 = 32 * p2b; U1 = n8 + 4; U2 = P1 + 4; U3 = P2 + 4;
+    Q1s = base; Q2s = Q1s + P1 * U1; Q3s = Q2s + P2 * U2;
+    d1 = Q3s + 32 * U3; d2 = d1 + P1; d3 = d2 + P2;
+    ish = d3 + 32; irs = ish + n8;
+    osc = irs + n8; osh = osc + 32; sig = osh + 32; alo = sig + 32; ahi = alo + 32;
+    slo = ahi + 32; shi = slo + NS;
+    return shi + NS;
+  }
+  __device__ __forceinline__ ChainL1 l1() const { return ChainL1{Q1s, U1, ish, irs}; }
+  // all 256 threads, before the barrier.  P = the policy's flat vector with log_std behind the output bias, tr = [in_shift n,
+  // in_scale n, out_shift m, out_scale m]; the bounds are m / n floats each or null in pairs
+  __device__ __forceinline__ void stage(const float* __restrict__ P, const float* __restrict__ tr, const float* __restrict__ a_lo,
+                                        const float* __restrict__ a_hi, const float* __restrict__ s_lo, const float* __restrict__ s_hi,
+                                        int tid) const {
+    const int lane = tid & 63;
+    const int64_t oB1 = (int64_t)p1 * n, oW2 = oB1 + p1, oB2 = oW2 + (int64_t)p2 * p1, oW3 = oB2 + p2, oB3 = oW3 + (int64_t)m * p2, oLS = oB3 + m;
+    for (int u = tid >> 6; u < P1; u += 4)
+      for (int c = lane; c < n8; c += 64) Q1s[u * U1 + c] = (u < p1 && c < n) ? P[(int64_t)u * n + c] : 0.f;
+    for (int u = tid >> 6; u < P2; u += 4)
+      for (int c = lane; c < P1; c += 64) Q2s[u * U2 + c] = (u < p2 && c < p1) ? P[oW2 + (int64_t)u * p1 + c] : 0.f;
+    for (int u = tid >> 6; u < 32; u += 4)
+      for (int c = lane; c < P2; c += 64) Q3s[u * U3 + c] = (u < m && c < p2) ? P[oW3 + (int64_t)u * p2 + c] : 0.f;
+    for (int i = tid; i < P1; i += 256) d1[i] = i < p1 ? P[oB1 + i] : 0.f;
+    for (int i = tid; i < P2; i += 256) d2[i] = i < p2 ? P[oB2 + i] : 0.f;
+    for (int i = tid; i < 32; i += 256) {
+      const bool on = i < m;
+      d3[i] = on ? P[oB3 + i] : 0.f;
+      osh[i] = on ? tr[2 * n + i] : 0.f;
+      osc[i] = on ? tr[2 * n + m + i] : 0.f;
+      sig[i] = on ? expf(P[oLS + i]) : 0.f;
+      alo[i] = on ? (a_lo ? a_lo[i] : -INFINITY) : 0.f;
+      ahi[i] = on ? (a_hi ? a_hi[i] : INFINITY) : 0.f;
+    }
+    for (int i = tid; i < NS; i += 256) {
+      const bool on = i < n;
+      slo[i] = on ? (s_lo ? s_lo[i] : -INFINITY) : 0.f;
+      shi[i] = on ? (s_hi ? s_hi[i] : INFINITY) : 0.f;
+    }
+    for (int c = tid; c < n8; c += 256) {
+      ish[c] = c < n ? tr[c] : 0.f;
+      irs[c] = c < n ? tr[n + c] + 1e-8f : 1.f;
+    }
+  }
+};
+
 }  // namespace mjx

@@ -30,6 +30,7 @@
 #include "mlp_fit.h"
 #include "path_reward.h"
 #include "plan.h"
+#include "policy_rollout.h"
 #include "vecops.h"
 
 namespace {
@@ -60,7 +61,7 @@ int lds_limit(const void* kern, size_t bytes) {
   if (e) return fail(e, "dynamic LDS limit of %zu bytes: %s", bytes, hipGetErrorString((hipError_t)e));
   return MJX_OK;
 }
-enum ScratchSite { SITE_GRAM, SITE_MLP_PREDICT, SITE_MLP_FIT, SITE_MLP_FIT_WIDE, SITE_MLP_FIT_LAUNCHES, SITE_DYN_FIT, SITE_SUM_STATS, SITE_PLAN_ROLLOUT, SITE_PLAN_SCORE, SITE_DYN_FIT_ENS, SITE_PATH_REWARDS };
+enum ScratchSite { SITE_GRAM, SITE_MLP_PREDICT, SITE_MLP_FIT, SITE_MLP_FIT_WIDE, SITE_MLP_FIT_LAUNCHES, SITE_DYN_FIT, SITE_SUM_STATS, SITE_PLAN_ROLLOUT, SITE_PLAN_SCORE, SITE_DYN_FIT_ENS, SITE_PATH_REWARDS, SITE_POLICY_ROLLOUT };
 template <class T>
 int dev_scratch(ScratchSite site, void* stream, size_t bytes, T** out) {
   HIPCHK(mjx::scratch(site, (hipStream_t)stream, bytes, (void**)out));
@@ -674,6 +675,80 @@ int mjx_path_rewards(const float* obs, const float* act, int64_t act_stride, int
   if (r64_out) hipLaunchKernelGGL(k_pr_widen, dim3(capped_grid(kr, 256, 4096)), dim3(256), 0, st, r32, kr, r64_out);
   HIPCHK(hipGetLastError());
   if (route_out) *route_out = 0;
+  return MJX_OK;
+}
+
+// ---------------------------------------------------------------------------- policy rollout on learned models (csrc/policy_rollout.h)
+int mjx_policy_rollout_route(const int* pol_sizes, int pol_n_sizes, const int* dyn_sizes, int dyn_n_sizes) {
+  DynNet pol, dyn;
+  if (int rc = dyn_net(pol_sizes, pol_n_sizes, pol)) return rc;
+  if (int rc = dyn_net(dyn_sizes, dyn_n_sizes, dyn)) return rc;
+  if (!pol_roll_nets_ok(dyn, pol)) return fail(MJX_ERR_ARG, "sizes must be [n, p..., m] and [n + m, h..., n] with m > 0");
+  PolRollShape ps;
+  return pol_roll_shape(dyn, pol, ps) ? 1 : 0;
+}
+
+int mjx_policy_rollout(const float* s0, int64_t s0_stride, int64_t N, int H, int K, const int* pol_sizes, int pol_n_sizes,
+                       const float* pol_params, const float* pol_tr, const float* noise, int64_t noise_stride, const int* dyn_sizes,
+                       int dyn_n_sizes, const float* dyn_params, const float* dyn_tr, int act, int flags, const float* a_min,
+                       const float* a_max, const float* s_min, const float* s_max, float* obs_out, float* act_out, int* route_out,
+                       void* stream) {
+  RolloutArgs a{};
+  if (int rc = dyn_net(dyn_sizes, dyn_n_sizes, a.dyn)) return rc;
+  if (int rc = dyn_net(pol_sizes, pol_n_sizes, a.pol)) return rc;
+  if (!pol_roll_nets_ok(a.dyn, a.pol)) return fail(MJX_ERR_ARG, "policy does not match the state / action dims");
+  const int n = a.dyn.dout(), m = a.dyn.din() - n;
+  if (!s0 || !pol_params || !pol_tr || !dyn_params || !dyn_tr || !obs_out || !act_out || N < 0 || H < 0 || !dyn_args_ok(a.dyn, K, act) ||
+      (flags & ~(DYN_OUT_AFFINE | DYN_MASK | DYN_RESIDUAL)) || (s0_stride != 0 && s0_stride != n) ||
+      (noise_stride != 0 && noise_stride != (int64_t)H * N * m) || (!a_min) != (!a_max) || (!s_min) != (!s_max))
+    return fail(MJX_ERR_ARG, "bad arguments");
+  PolRollShape ps;
+  const bool served = env_flag("MJX_POLICY_ROLLOUT_MFMA", true) && pol_roll_shape(a.dyn, a.pol, ps);   // (read per call: A/B runs in one process)
+  if (N == 0 || H == 0) { if (route_out) *route_out = served ? 1 : 0; return MJX_OK; }
+  MJX_DEVICE_ENTRY();
+  hipStream_t st = (hipStream_t)stream;
+  if (served) {
+    const PolRollKernel kern = pol_roll_kernel(ps.HB, ps.NB);
+    const int e = mjx::dyn_lds((const void*)kern, ps.bytes);
+    if (e == 0) {
+      PolRollArgs p{s0, s0_stride, noise, noise_stride ? (int64_t)H : 0, pol_params, pol_tr, dyn_params, dyn_tr, a_min, a_max, s_min, s_max,
+                    obs_out, act_out, N, a.dyn.P, H, n, m, a.dyn.sz[1], a.dyn.sz[2], act, flags, a.pol.sz[1], a.pol.sz[2]};
+      hipLaunchKernelGGL(kern, dim3((unsigned)((N + 127) / 128), (unsigned)K), dim3(256), ps.bytes, st, p);
+      HIPCHK(hipGetLastError());
+      if (route_out) *route_out = 1;
+      return MJX_OK;
+    }
+    if (e != mjx::LDS_OVER) (void)hipGetLastError();                     // a refusal falls back to the generic route
+  }
+  // generic route: k_model_rollout as mjx_model_rollout launches it; the tiled start state and the K copies of a shared noise
+  // block go to the calling thread's scratch block of this site on (device, stream)
+  const size_t s0_floats = s0_stride ? 0 : (size_t)N * n, nz_floats = (noise && !noise_stride && K > 1) ? (size_t)K * H * N * m : 0;
+  if (s0_floats + nz_floats) {
+    float* scr = nullptr;
+    if (int rc = dev_scratch(SITE_POLICY_ROLLOUT, stream, (s0_floats + nz_floats) * sizeof(float), &scr)) return rc;
+    if (s0_floats) {
+      hipLaunchKernelGGL(k_plan_tile_s0, dim3(capped_grid(N * n, 256, 1024)), dim3(256), 0, st, s0, N, n, scr);
+      s0 = scr;
+    }
+    if (nz_floats) {
+      hipLaunchKernelGGL(k_pol_expand_noise, dim3(capped_grid((int64_t)nz_floats, 256, 4096)), dim3(256), 0, st, noise, (int64_t)H * N * m, K,
+                         scr + s0_floats);
+      noise = scr + s0_floats;
+    }
+    HIPCHK(hipGetLastError());
+  }
+  a.pol_P = pol_params; a.pol_tr = pol_tr; a.noise = noise; a.a_lo = a_min; a.a_hi = a_max; a.s_lo = s_min; a.s_hi = s_max;
+  if (int rc = launch_model_rollout(a, s0, N, H, K, nullptr, dyn_params, dyn_tr, act, flags, obs_out, act_out, st)) return rc;
+  if (route_out) *route_out = 0;
+  return MJX_OK;
+}
+
+int mjx_cast_f32_f64(const float* src, int64_t count, double* dst, void* stream) {
+  if (count < 0 || (count > 0 && (!src || !dst))) return fail(MJX_ERR_ARG, "bad arguments");
+  if (count == 0) return MJX_OK;
+  MJX_DEVICE_ENTRY();
+  hipLaunchKernelGGL(k_pr_widen, dim3(capped_grid(count, 256, 4096)), dim3(256), 0, (hipStream_t)stream, src, count, dst);
+  HIPCHK(hipGetLastError());
   return MJX_OK;
 }
 

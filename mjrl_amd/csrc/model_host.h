@@ -51,6 +51,35 @@ inline PlanKernel plan_kernel(int HB, int NB) {
   return tab[HB - 1][NB - 1];
 }
 
+// ---- policy rollout.  The k_policy_rollout instance that serves a (policy, dynamics) pair, if one does: a dynamics net as
+// plan_shape accepts it, a policy [n, p1, p2, m] with 1 <= p1, p2 <= 64 (each padded to whole 32-blocks in the image; the kernel
+// runs the blocks in use, so one instance per dynamics instance serves every policy width), BOTH images together within LDS_MAX
+// (the kernel has no static LDS), and an instance that is kept (pol_roll_kept).  MJX_POLICY_ROLLOUT_MFMA=0 (read per call by
+// mjx_policy_rollout): the generic route.
+struct PolRollShape { int HB = 0, NB = 0; size_t bytes = 0; };
+inline bool pol_roll_kept(int HB, int NB) { (void)HB; (void)NB; return true; }
+inline bool pol_roll_shape(const DynNet& dyn, const DynNet& pol, PolRollShape& ps) {
+  const int n = dyn.dout(), m = dyn.din() - n;
+  PlanShape dp;
+  if (!plan_shape(dyn, m, dp) || pol.nl != 3) return false;
+  const int p1 = pol.sz[1], p2 = pol.sz[2];
+  if (p1 > 32 * POL_MAX_PB || p2 > 32 * POL_MAX_PB || !pol_roll_kept(dp.HB, dp.NB)) return false;
+  ps.HB = dp.HB; ps.NB = dp.NB;
+  ps.bytes = dp.bytes + sizeof(float) * pol_lds_floats(p1, p2, n, dp.NB);
+  return ps.bytes <= LDS_MAX;
+}
+typedef void (*PolRollKernel)(PolRollArgs);
+inline PolRollKernel pol_roll_kernel(int HB, int NB) {
+  static const PolRollKernel tab[4][2] = {{k_policy_rollout<1, 1>, k_policy_rollout<1, 2>}, {k_policy_rollout<2, 1>, k_policy_rollout<2, 2>},
+                                          {k_policy_rollout<3, 1>, k_policy_rollout<3, 2>}, {k_policy_rollout<4, 1>, k_policy_rollout<4, 2>}};
+  return tab[HB - 1][NB - 1];
+}
+// the two nets of one call: sizes that fit each other ([n, p..., m] and [n + m, h..., n])
+inline bool pol_roll_nets_ok(const DynNet& dyn, const DynNet& pol) {
+  const int n = dyn.dout(), m = dyn.din() - n;
+  return m > 0 && pol.din() == n && pol.dout() == m;
+}
+
 // ---- learned path rewards.  The k_path_rewards instance that serves a (dynamics, reward) pair, if one does: a dynamics net as
 // plan_shape accepts it, a reward net [2 n + m, g1, g2, 1] with 1 <= g1, g2 <= 128, and BOTH images together within LDS_MAX (the
 // kernel has no static LDS).  Each reward width is padded to whole 32-blocks in the image (W2's K dimension to the first width's

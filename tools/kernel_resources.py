@@ -29,7 +29,7 @@ for r, n in zip(rows, names):
 rows.sort(key=lambda r: r["kernel"])
 json.dump(rows, open(out_json, "w"), indent=0)
 hot = ("k_fused<64, 64, 1, 8", "k_gemm", "k_lw_head", "k_mlp_fit", "k_policy_fit", "k_bl_gram", "k_cg_", "k_reduce_partials4", "k_dyn_fit", "k_plan_rollout",
-       "k_path_rewards", "k_pr_")
+       "k_path_rewards", "k_pr_", "k_policy_rollout", "k_pol_")
 with open(out_md, "w") as f:
     f.write("# Register / scratch / static-LDS use per kernel (gfx950 code object of csrc/mjx.hip, `tools/kernel_resources.py`)\n\n"
             "`vgpr` = architectural VGPRs + AGPRs allocated (the unified file: 512 per lane at one wave per SIMD, 256 at two); `scratch` > 0 = spilled registers "
