@@ -1,0 +1,130 @@
+"""GPU worker for tests/test_gpu_plan_matrix.py: every case of tests/_plan_cases.py through mjx_plan_rollout on both routes and through
+mjx_plan_score, and their argument checks, in ONE fresh process; prints one JSON line of measurements (the test module compares them
+with its bars and bounds).  Every output block is prefilled with NaN and carries GUARD NaN elements behind it; that none stays inside
+and none behind is touched is asserted here, per call.
+python tests/_plan_matrix_worker.py"""
+import ctypes
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+import _plan_cases as C  # noqa: E402
+from mjrl_amd._lib import check, load, ptr  # noqa: E402
+
+T0 = time.time()
+dev = torch.device("cuda", 0)
+lib = load()
+SWITCH = "MJX_PLAN_MFMA"
+MJX_ERR_ARG = -1
+_UP = {}
+GUARDED = [0]
+
+
+def ints(v):
+    return (ctypes.c_int * len(v))(*[int(x) for x in v])
+
+
+def up(x, dtype=np.float32):
+    """one upload per host array (the arrays of a case stay alive in _plan_cases' caches, and the device copies here)"""
+    if id(x) not in _UP:
+        _UP[id(x)] = (x, torch.as_tensor(np.ascontiguousarray(x, dtype)).to(dev))
+    return _UP[id(x)][1]
+
+
+def stream():
+    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def block(count, dtype=torch.float32):
+    return torch.full((count + C.GUARD,), float("nan"), dtype=dtype, device=dev)
+
+
+def guarded(buf, count, what):
+    """the block after a call: no NaN inside, every guard element still NaN -> the host copy"""
+    torch.cuda.synchronize()
+    b = buf.cpu().numpy()
+    GUARDED[0] += 1
+    assert not np.isnan(b[:count]).any(), "%s: %d elements never written" % (what, int(np.isnan(b[:count]).sum()))
+    assert np.isnan(b[count:]).all(), "%s: %d guard elements touched" % (what, int((~np.isnan(b[count:])).sum()))
+    return b
+
+
+def members(name, mem):
+    key = "members " + name
+    if key not in _UP:
+        _UP[key] = tuple(torch.as_tensor(np.stack(mem[f])).to(dev) for f in ("thetas", "trs"))
+    return _UP[key]
+
+
+def rollout(route, name, mem, s0, actions):
+    N, H, m = actions.shape
+    K, n, ds = len(mem["thetas"]), mem["sizes"][-1], mem["sizes"]
+    P, tr = members(name, mem)
+    obs = block(K * N * H * n)
+    os.environ[SWITCH] = str(route)
+    check(lib.mjx_plan_rollout(ptr(up(s0)), 0 if s0.ndim == 1 else n, N, H, K, ptr(up(actions)), ints(ds), len(ds), ptr(P), ptr(tr), mem["act"],
+                               mem["flags"], ptr(obs), stream()))
+    os.environ.pop(SWITCH)
+    return guarded(obs, K * N * H * n, "%s rows %d route %d" % (name, N, route))
+
+
+def score(name, mode, obs, rew, acts, c):
+    K, N, H, n, m = c["K"], c["N"], c["H"], c["n"], c["m"]
+    Rd, Sd, qd = block(K * N, torch.float64), block(K * N, torch.float64), block(H * m, torch.float64)
+    check(lib.mjx_plan_score(None if obs is None else ptr(up(obs)), ptr(up(rew, np.float64)), ptr(up(acts, np.float64)), K, N, H, n, m, c["kappa"],
+                             c["gamma"], c["omega"], 1 if mode == "trajectory" else 0, ptr(Rd), ptr(Sd), ptr(qd), stream()))
+    what = "score %s %s" % (name, mode)
+    return guarded(Rd, K * N, what + " R"), guarded(Sd, K * N, what + " S"), guarded(qd, H * m, what + " seq")
+
+
+R = dict(rollout={}, score={}, served={})
+for name in C.ORDER:
+    ds = C.sizes(name)
+    R["served"][name] = lib.mjx_plan_route(ints(ds), len(ds), C.CASES[name]["m"])
+    rec = C.measure(name, rollout)
+    print("\n".join(rec.pop("runs")), flush=True)
+    print("%s routes against each other %.3e  unwritten %d guard %d  [%.1f s]" % (name, rec["routes"], rec["unwritten"], rec["guard"], time.time() - T0),
+          flush=True)
+    R["rollout"][name] = rec
+for name in C.SCORE_ORDER:
+    rec = C.score_measure(name, score)
+    print("\n".join(rec.pop("runs")), flush=True)
+    R["score"][name] = rec
+print("scoring done [%.1f s]" % (time.time() - T0), flush=True)
+
+# ---- argument checks: MJX_ERR_ARG, and a guarded output that stays as it was
+untouched = lambda *bufs: bool(all(torch.isnan(b).all().item() for b in bufs))
+name = "r1"
+mem, data = C.cached_case(name)
+s0, actions = data[(6, "rows")]
+N, H, m = actions.shape
+n, ds = mem["sizes"][-1], mem["sizes"]
+P, tr = members(name, mem)
+obs = block(2 * N * H * n)
+call = lambda s0p=ptr(up(s0)), stride=n, K=2, sz=ds, ap=ptr(up(actions)): lib.mjx_plan_rollout(
+    s0p, stride, N, H, K, ap, ints(sz), len(sz), ptr(P), ptr(tr), mem["act"], mem["flags"], ptr(obs), stream())
+R["rollout_args"] = {"s0_stride": call(stride=n + 1), "m_zero": call(sz=(n, 32, 32, n)), "null_s0": call(s0p=None), "null_actions": call(ap=None),
+                     "K_zero": call(K=0)}
+torch.cuda.synchronize()
+R["rollout_args_untouched"] = untouched(obs)
+c = C.SCORE_CASES["gamh"]
+o, rew, acts = C.score_inputs("gamh")
+K, N, H, n, m = c["K"], c["N"], c["H"], c["n"], c["m"]
+Rd, Sd, qd = block(K * N, torch.float64), block(K * N, torch.float64), block(H * m, torch.float64)
+call = lambda K=K, N=N, idx=0, op=ptr(up(o)): lib.mjx_plan_score(op, ptr(up(rew, np.float64)), ptr(up(acts, np.float64)), K, N, H, n, m, c["kappa"],
+                                                                c["gamma"], c["omega"], idx, ptr(Rd), ptr(Sd), ptr(qd), stream())
+R["score_args"] = {"K_zero": call(K=0), "K_65536": call(K=65536), "N_zero": call(N=0), "idx_mode_2": call(idx=2), "reference_K_gt_N": call(K=4, N=3)}
+torch.cuda.synchronize()
+R["score_args_untouched"] = untouched(Rd, Sd, qd)
+R["err_arg"] = MJX_ERR_ARG
+R["guarded_calls"] = GUARDED[0]
+R["seconds"] = time.time() - T0
+print("%d guarded blocks; %.1f s in all" % (GUARDED[0], R["seconds"]), flush=True)
+print("RESULT " + json.dumps(R))
