@@ -4,7 +4,8 @@
 from torch's global stream in the reference's order, model by model, step by step), hands the rollouts to the host
 reward / termination callables, truncates on ensemble disagreement with the batched forward plus one reduction
 (``mjx_dyn_pred_error``), and then runs the NPG agent's own compute_returns -> compute_advantages -> train_from_paths
--> baseline.fit unchanged.
+-> baseline.fit unchanged.  ``get_refined_action`` keeps the members on the device through ``nn_dynamics.cached_members_pack``, the
+cache ``MPCPolicy`` uses, with the refinement's default bound vectors as its extras.
 """
 import time as timer
 
@@ -14,8 +15,8 @@ import torch
 from ..._lib import check, load, ptr
 from ...utils import process_samples
 from ..npg_cg import NPG
-from .nn_dynamics import (WorldModel, _device, _ints, _stream, ensemble_forward, ensemble_path_rewards, members_pack_key,
-                          pack_dynamics_members, pack_reward_members, path_rewards_call)
+from .nn_dynamics import (WorldModel, _device, _ints, _stream, cached_members_pack, ensemble_forward, ensemble_path_rewards,
+                          path_rewards_call)
 from .sampling import _as_env, draw_rollout_noise, rollout_bounds, rollout_models, rollout_models_device
 
 REFINE_LARGE_VALUE = float(1e2)     # the refined call's state / action bounds: policy_rollout's default large_value
@@ -196,17 +197,13 @@ class ModelAccelNPG(NPG):
 
     def _refine_packed(self, dev):
         """the members' parameters and transforms on the device, packed once and again when a member changed
-        (nn_dynamics.members_pack_key, the recipe MPCPolicy keys its own copy on)"""
-        learned = self._refine_learned()
-        key, held = members_pack_key(self.learned_model, dev, learned)
-        if self._refine_pack is None or self._refine_pack[0] != key:
-            pk = pack_dynamics_members(self.learned_model, dev)
+        (nn_dynamics.cached_members_pack, as MPCPolicy keeps its own copy), with the default bound vectors beside them"""
+        def bounds(pk):
             n, m = pk["sizes"][-1], pk["sizes"][0] - pk["sizes"][-1]
             pk["bnd"], pk["bnd_value"] = rollout_bounds(n, m, dev, large_value=REFINE_LARGE_VALUE), REFINE_LARGE_VALUE
-            if learned:
-                pk["rew"] = pack_reward_members(self.learned_model, dev)
-            self._refine_pack = (key, pk, held)
-            self._refine_packs += 1
+
+        self._refine_pack, fresh = cached_members_pack(self._refine_pack, self.learned_model, dev, self._refine_learned(), bounds)
+        self._refine_packs += fresh
         return self._refine_pack[1]
 
     def invalidate(self):

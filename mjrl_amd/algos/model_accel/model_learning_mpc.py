@@ -14,11 +14,10 @@ constructor arguments, attributes and ``get_action`` semantics, the warm-start s
 5. one upload of the (K, N, H) rewards, ``mjx_plan_score`` (disagreement, discounted returns, softmax weights and the weighted
    sequence in fp64), one read-back of the (H, m) sequence.
 
-The members' parameters and transforms are packed on the device once per planner and again when a member changed: each net
-carries a generation counter that this package's own writes bump (``fit_dynamics`` / ``fit_model``, ``set_params``,
-``set_transformations``), and the key also holds every parameter and transform tensor with its ``_version`` and storage
-(:meth:`MPCPolicy._pack_key`).  A write to ``p.data`` from outside the package is the one change it cannot see:
-:meth:`MPCPolicy.invalidate`.
+The members' parameters and transforms are packed on the device once per planner and again when a member changed.  The cache is
+``nn_dynamics.cached_members_pack`` (``ModelAccelNPG``'s refinement keeps its copy through the same function) and its key is
+``nn_dynamics.members_pack_key``, which says what it sees.  A write to ``p.data`` from outside the package is the one change it
+cannot see: :meth:`MPCPolicy.invalidate`.
 
 ``fitted_model`` is a list of ``WorldModel`` (a list of one works: its disagreement is 0) or a bare ``WorldModel``.  For a
 bare model the reference raises ``TypeError`` (it calls ``generate_paths(fitted_model=...)``, which has no such argument);
@@ -38,8 +37,7 @@ import numpy as np
 import torch
 
 from ..._lib import check, load, ptr
-from .nn_dynamics import (_device, _ints, _stream, members_pack_key, pack_dynamics_members, pack_reward_members,
-                          path_rewards_call)
+from .nn_dynamics import _device, _ints, _stream, cached_members_pack, members_pack_key, path_rewards_call
 
 
 def perturbed_action_batch(num_traj, base_act, filter_coefs):
@@ -110,23 +108,15 @@ class MPCPolicy(object):
         return self.fitted_model if type(self.fitted_model) == list else [self.fitted_model]
 
     def _pack_key(self, dev):
-        """What the device copy of the members was made from -> (key, the tensors the key names).  Per member: the net's
-        generation counter, which every write path of this package bumps (the fit's write-back through ``p.data.copy_``, which
-        leaves ``p._version`` alone, ``set_params``, ``set_transformations``); per parameter and transform tensor its identity,
-        ``_version`` (in-place edits) and storage; activation and flags.  On reward='learned' the same for every member's reward
-        net (``fit_reward``'s write-back bumps its counter), with output transforms that are plain numbers by value.  The tensors
-        are returned to be HELD beside the key, so that an id() in it cannot come back as another tensor's."""
+        """(key, held tensors) of the members' device copy: ``nn_dynamics.members_pack_key``, the reward nets too on reward='learned'"""
         return members_pack_key(self._members(), dev, self.reward == 'learned')
 
+    def _dims_are_the_envs(self, pk):
+        net0 = self._members()[0].dynamics_net
+        assert (net0.state_dim, net0.act_dim) == (self.n, self.m), "the models' dims are not the environment's"
+
     def _packed(self, dev):
-        key, held = self._pack_key(dev)
-        if self._pack is None or self._pack[0] != key:
-            pk = pack_dynamics_members(self._members(), dev)
-            net0 = self._members()[0].dynamics_net
-            assert (net0.state_dim, net0.act_dim) == (self.n, self.m), "the models' dims are not the environment's"
-            if self.reward == 'learned':
-                pk["rew"] = pack_reward_members(self._members(), dev)
-            self._pack = (key, pk, held)
+        self._pack, _ = cached_members_pack(self._pack, self._members(), dev, self.reward == 'learned', self._dims_are_the_envs)
         return self._pack[1]
 
     def invalidate(self):

@@ -19,6 +19,12 @@ global torch stream are the reference's) and transforms.  What runs where:
   read-back; :func:`ensemble_path_rewards_device`: the same on device tensors in one ``mjx_path_rewards`` call, which is what
   ``MPCPolicy(reward='learned')`` plans on.
 
+What every one of these shares stands once: :func:`pack_members` (K nets of one shape as the device blocks ``P`` and ``tr``, under
+every forward, rollout, fit and under ``pack_dynamics_members`` / ``pack_reward_members``), :func:`_dynamics_transforms` /
+:func:`_reward_transforms` (the reference's transform expressions), :func:`_fit_members` (the one fit body: index draws, X, stacked
+state, the entry, :func:`_write_back`) and :func:`cached_members_pack` (the device cache of a planner's members, keyed by
+:func:`members_pack_key`).
+
 The module parameters stay ordinary torch tensors (CPU by default, as in the reference): ``get_params`` /
 ``set_params`` / ``to`` / ``is_cuda`` / pickling behave as the reference's.  There is no CPU path: without a GPU the
 operations raise.
@@ -91,6 +97,27 @@ def _flags(net):
     return OUT_AFFINE | (MASK if net.use_mask else 0) | (RESIDUAL if net.residual else 0)
 
 
+def _one_shape(nets):
+    sizes = tuple(nets[0].layer_sizes)
+    assert all(tuple(net.layer_sizes) == sizes for net in nets), "ensemble members must share one shape"
+    return sizes
+
+
+def _stack(blocks):
+    """K blocks as K rows; one block is its own row (a view: what writes to the row writes to the block)"""
+    return blocks[0][None] if len(blocks) == 1 else torch.stack(blocks)
+
+
+def pack_members(nets, dev, one_kind=True):
+    """THE packer: K nets of one shape (asserted) as the device blocks every entry reads -> dict(sizes, P (K x params), tr (K x
+    transforms, :func:`_packed_transforms`), act, flags).  ``one_kind``: the nets share (activation, flags) as well (asserted), as a
+    launch over all of them needs; without it ``act`` and ``flags`` are the first net's."""
+    sizes = _one_shape(nets)
+    assert not one_kind or len({(_act_code(net), _flags(net)) for net in nets}) == 1, "ensemble members must share activation and output transforms"
+    return dict(sizes=sizes, P=_stack([_flat_params(net, dev) for net in nets]), tr=_stack([_packed_transforms(net, dev) for net in nets]),
+                act=_act_code(nets[0]), flags=_flags(nets[0]))
+
+
 def ensemble_forward(nets, x, dev=None):
     """K nets of one shape over the same rows x (rows x d_in, the concatenated raw input) in one launch -> K x rows x d_out
     (device tensor).  Each net's own activation, transforms and flags apply (one launch per distinct (activation, flags)).
@@ -100,20 +127,18 @@ def ensemble_forward(nets, x, dev=None):
     own = x.dim() == 3
     assert not own or x.shape[0] == len(nets), "per-member rows: one block per net"
     rows = x.shape[-2]
-    sizes = nets[0].layer_sizes
+    sizes = _one_shape(nets)
     out = torch.empty((len(nets), rows, sizes[-1]), dtype=torch.float32, device=dev)
     groups = {}
     for i, net in enumerate(nets):
-        assert tuple(net.layer_sizes) == tuple(sizes), "ensemble members must share one shape"
         groups.setdefault((_act_code(net), _flags(net)), []).append(i)
     lib = load()
     for (act, flags), ids in groups.items():
-        P = torch.stack([_flat_params(nets[i], dev) for i in ids])
-        tr = torch.stack([_packed_transforms(nets[i], dev) for i in ids])
+        pk = pack_members([nets[i] for i in ids], dev)
         o = out if len(ids) == len(nets) else torch.empty((len(ids), rows, sizes[-1]), dtype=torch.float32, device=dev)
         xg = x if not own or len(ids) == len(nets) else x[ids].contiguous()
-        check(lib.mjx_dyn_forward(ptr(xg), rows * sizes[0] if own else 0, rows, len(ids), _ints(sizes), len(sizes), ptr(P), ptr(tr), act, flags, ptr(o),
-                                  _stream(dev)))
+        check(lib.mjx_dyn_forward(ptr(xg), rows * sizes[0] if own else 0, rows, len(ids), _ints(sizes), len(sizes), ptr(pk["P"]), ptr(pk["tr"]), act, flags,
+                                  ptr(o), _stream(dev)))
         if o is not out:
             out[ids] = o
     return out
@@ -140,6 +165,26 @@ class _DeviceAdam:
             self.exp_avg_sq = torch.zeros(self.num_params, dtype=torch.float32, device=dev)
         self.to(dev)
         return self.exp_avg, self.exp_avg_sq
+
+
+def _dynamics_transforms(residual, s, a, sp):
+    """the reference's transform expressions for a dynamics net (nn_dynamics.py:99-104) on tensors of one device -> the six
+    arguments of ``DynamicsNet.set_transformations``"""
+    s_shift, a_shift = torch.mean(s, dim=0), torch.mean(a, dim=0)
+    s_scale, a_scale = torch.mean(torch.abs(s - s_shift), dim=0), torch.mean(torch.abs(a - a_shift), dim=0)
+    out_shift = torch.mean(sp - s, dim=0) if residual else torch.mean(sp, dim=0)
+    out_scale = torch.mean(torch.abs(sp - s - out_shift), dim=0) if residual else torch.mean(torch.abs(sp - out_shift), dim=0)
+    return s_shift, s_scale, a_shift, a_scale, out_shift, out_scale
+
+
+def _reward_transforms(s, a, r):
+    """the reference's transform expressions for a reward net (nn_dynamics.py:135-139) on tensors of one device -> the six arguments
+    of ``RewardNet.set_transformations``.  As the reference writes it, the last pair reads ``r_shift`` before it is bound: it
+    raises ``UnboundLocalError`` there and here, so reward fits are run with ``set_transformations=False``."""
+    s_shift, a_shift = torch.mean(s, dim=0), torch.mean(a, dim=0)
+    s_scale, a_scale = torch.mean(torch.abs(s - s_shift), dim=0), torch.mean(torch.abs(a - a_shift), dim=0)
+    r_shift, r_scale = torch.mean(r, dim=0), torch.mean(torch.abs(r - r_shift), dim=0)
+    return s_shift, s_scale, a_shift, a_scale, r_shift, r_scale
 
 
 class WorldModel:
@@ -226,13 +271,8 @@ class WorldModel:
             sp = torch.from_numpy(sp).float()
         s = s.to(self.device); a = a.to(self.device); sp = sp.to(self.device)
         net = self.dynamics_net
-        # the reference's transform expressions, on the reference's device (nn_dynamics.py:99-104)
-        if set_transformations:
-            s_shift, a_shift = torch.mean(s, dim=0), torch.mean(a, dim=0)
-            s_scale, a_scale = torch.mean(torch.abs(s - s_shift), dim=0), torch.mean(torch.abs(a - a_shift), dim=0)
-            out_shift = torch.mean(sp - s, dim=0) if net.residual else torch.mean(sp, dim=0)
-            out_scale = torch.mean(torch.abs(sp - s - out_shift), dim=0) if net.residual else torch.mean(torch.abs(sp - out_shift), dim=0)
-            net.set_transformations(s_shift, s_scale, a_shift, a_scale, out_shift, out_scale)
+        if set_transformations:                  # (on the reference's device)
+            net.set_transformations(*_dynamics_transforms(net.residual, s, a, sp))
         # targets (sp [- s] - out_shift) / (out_scale + 1e-8) are formed on the GPU (k_dyn_prep); the fit runs in the
         # transformed space (the reference's _apply_out_transforms = False, nn_dynamics.py:107-115)
         return _fit(net, self.dynamics_opt, torch.cat([s, a], -1), sp, TGT_RESIDUAL if net.residual else TGT_PLAIN,
@@ -252,10 +292,7 @@ class WorldModel:
             r = torch.from_numpy(r).float()
         s = s.to(self.device); a = a.to(self.device); r = r.to(self.device)
         if set_transformations:
-            s_shift, a_shift = torch.mean(s, dim=0), torch.mean(a, dim=0)
-            s_scale, a_scale = torch.mean(torch.abs(s - s_shift), dim=0), torch.mean(torch.abs(a - a_shift), dim=0)
-            r_shift, r_scale = torch.mean(r, dim=0), torch.mean(torch.abs(r - r_shift), dim=0)
-            self.reward_net.set_transformations(s_shift, s_scale, a_shift, a_scale, r_shift, r_scale)
+            self.reward_net.set_transformations(*_reward_transforms(s, a, r))
         sp = self.dynamics_net.forward(s, a).detach().clone()
         sp = sp.to(s.device)
         return _fit(self.reward_net, self.reward_opt, torch.cat([s, a, sp], -1), r, TGT_AFFINE, fit_mb_size, fit_epochs,
@@ -300,34 +337,62 @@ def epoch_means(step_losses, num_steps, epochs):
     return out
 
 
-def _fit(net, opt, X, Y, target_mode, batch_size, epochs, max_steps):
+def _write_back(nets, opts, P, m, v, steps, losses, num_steps, ran):
+    """THE write-back of a fit: per member the moments and parameters copied back, the optimiser advanced, ``_generation`` bumped
+    (``p.data.copy_`` leaves ``p._version`` as it was; holders of device copies key on the counter) -> K epoch-loss lists"""
+    out = []
+    with torch.no_grad():
+        for i, (net, opt) in enumerate(zip(nets, opts)):
+            if m.shape[0] > 1:                   # (a single member's moments were updated in place, see _stack)
+                opt.exp_avg.copy_(m[i]); opt.exp_avg_sq.copy_(v[i])
+            opt.step_count += steps
+            k = 0
+            for p in net.parameters():
+                p.data.copy_(P[i, k:k + p.numel()].view_as(p))
+                k += p.numel()
+            net._generation = getattr(net, "_generation", 0) + 1
+            out.append(epoch_means(losses[i], num_steps, ran))
+    return out
+
+
+def _fit_members(nets, opts, make_x, Y, target_mode, batch_size, epochs, max_steps, entry, draws=None):
+    """THE fit body: K nets (one shape, activation and optimiser setting) on N rows through ``entry`` -- ``mjx_dyn_fit_adam`` (K = 1),
+    ``mjx_dyn_fit_ensemble`` or ``mjx_reward_fit_ensemble``.  The index draws (``draws``, or member by member from NumPy's global
+    stream here), then ``make_x(dev)`` -> (X on the device, its member stride), then the members' parameters, transforms and
+    optimiser state stacked, the call, the write-back.  -> K epoch-loss lists."""
     dev = _device()
-    N = int(Y.shape[0])
-    idx, num_steps, ran = fit_permutations(N, batch_size, epochs, max_steps)
+    K, N = len(nets), int(Y.shape[0])
+    idx, num_steps, ran = draws if draws is not None else ensemble_fit_indices(K, N, batch_size, epochs, max_steps)
     steps = ran * num_steps
     if steps == 0:
-        return epoch_means([], num_steps, ran)
-    X, Y = _f32(X, dev), _f32(Y.reshape(N, -1), dev)
-    P = _flat_params(net, dev)
-    tr = _packed_transforms(net, dev)
-    din, dout = net.layer_sizes[0], net.layer_sizes[-1]
-    in_tr = torch.cat([tr[:din], tr[din:2 * din]])
-    out_tr = tr[2 * din:]
-    m, v = opt._state(dev)
-    g = opt.param_groups[0]
-    idx_d = torch.from_numpy(idx).to(dev)
-    loss = torch.empty(steps, dtype=torch.float32, device=dev)
-    check(load().mjx_dyn_fit_adam(ptr(X), ptr(Y), N, _ints(net.layer_sizes), len(net.layer_sizes), ptr(in_tr), ptr(out_tr),
-                                  target_mode, _act_code(net), ptr(P), ptr(m), ptr(v), opt.step_count, ptr(idx_d), steps,
-                                  int(batch_size), float(g['lr']), float(g['weight_decay']), ptr(loss), _stream(dev)))
-    opt.step_count += steps
-    k = 0
-    with torch.no_grad():
-        for p in net.parameters():
-            p.data.copy_(P[k:k + p.numel()].view_as(p))
-            k += p.numel()
-    net._generation = getattr(net, "_generation", 0) + 1     # (p.data.copy_ leaves p._version as it was)
-    return epoch_means(loss.cpu().numpy(), num_steps, ran)
+        return [epoch_means([], num_steps, ran) for _ in nets]
+    X, x_stride = make_x(dev)
+    Y = _f32(Y.reshape(N, -1), dev)
+    pk = pack_members(nets, dev, one_kind=False)
+    sizes, P, act = pk["sizes"], pk["P"], pk["act"]
+    in_tr, out_tr = pk["tr"][:, :2 * sizes[0]].contiguous(), pk["tr"][:, 2 * sizes[0]:].contiguous()
+    state = [opt._state(dev) for opt in opts]
+    m, v = _stack([st[0] for st in state]), _stack([st[1] for st in state])      # (one member: the optimiser's own blocks)
+    g = opts[0].param_groups[0]
+    idx_d = torch.from_numpy(np.ascontiguousarray(idx)).to(dev)
+    loss = torch.empty((K, steps), dtype=torch.float32, device=dev)
+    net_args = (_ints(sizes), len(sizes), ptr(in_tr), ptr(out_tr))
+    step_args = (ptr(idx_d), steps, int(batch_size), float(g['lr']), float(g['weight_decay']), ptr(loss))
+    if entry == "mjx_dyn_fit_adam":
+        check(load().mjx_dyn_fit_adam(ptr(X), ptr(Y), N, *net_args, target_mode, act, ptr(P), ptr(m), ptr(v), opts[0].step_count, *step_args,
+                                      _stream(dev)))
+    else:
+        mode = () if entry == "mjx_reward_fit_ensemble" else (target_mode,)      # (the reward entry's target mode is its own)
+        step0 = (ctypes.c_int64 * K)(*[int(opt.step_count) for opt in opts])
+        route = ctypes.c_int(-1)
+        check(getattr(load(), entry)(ptr(X), x_stride, ptr(Y), 0, N, K, *net_args, *mode, act, ptr(P), ptr(m), ptr(v), step0, *step_args,
+                                     ctypes.byref(route), _stream(dev)))
+    return _write_back(nets, opts, P, m, v, steps, loss.cpu().numpy(), num_steps, ran)
+
+
+def _fit(net, opt, X, Y, target_mode, batch_size, epochs, max_steps):
+    """one net through ``mjx_dyn_fit_adam`` (a one-member ensemble call runs another kernel and other bits)"""
+    return _fit_members([net], [opt], lambda dev: (_f32(X, dev), 0), Y, target_mode, batch_size, epochs, max_steps, "mjx_dyn_fit_adam")[0]
 
 
 def ensemble_fit_indices(K, num_samples, batch_size, epochs, max_steps=1e10):
@@ -371,53 +436,12 @@ def fit_ensemble(models, s, a, sp, fit_mb_size, fit_epochs, max_steps=1e4, set_t
         s = torch.from_numpy(s).float()
         a = torch.from_numpy(a).float()
         sp = torch.from_numpy(sp).float()
-    if set_transformations:
-        for mdl in models:
-            # the reference's transform expressions, on each member's device (nn_dynamics.py:99-104), as fit_dynamics forms them
-            net = mdl.dynamics_net
-            s_, a_, sp_ = s.to(mdl.device), a.to(mdl.device), sp.to(mdl.device)
-            s_shift, a_shift = torch.mean(s_, dim=0), torch.mean(a_, dim=0)
-            s_scale, a_scale = torch.mean(torch.abs(s_ - s_shift), dim=0), torch.mean(torch.abs(a_ - a_shift), dim=0)
-            out_shift = torch.mean(sp_ - s_, dim=0) if net.residual else torch.mean(sp_, dim=0)
-            out_scale = torch.mean(torch.abs(sp_ - s_ - out_shift), dim=0) if net.residual else torch.mean(torch.abs(sp_ - out_shift), dim=0)
-            net.set_transformations(s_shift, s_scale, a_shift, a_scale, out_shift, out_scale)
-    dev = _device()
-    K, N = len(models), int(sp.shape[0])
     nets, opts = [mdl.dynamics_net for mdl in models], [mdl.dynamics_opt for mdl in models]
-    idx, num_steps, ran = _draws if _draws is not None else ensemble_fit_indices(K, N, fit_mb_size, fit_epochs, max_steps)
-    steps = ran * num_steps
-    if steps == 0:
-        return [epoch_means([], num_steps, ran) for _ in models]
-    sizes = nets[0].layer_sizes
-    din, dout = sizes[0], sizes[-1]
-    X, Y = _f32(torch.cat([s, a], -1), dev), _f32(sp.reshape(N, -1), dev)
-    P = torch.stack([_flat_params(net, dev) for net in nets])
-    tr = torch.stack([_packed_transforms(net, dev) for net in nets])
-    in_tr, out_tr = tr[:, :2 * din].contiguous(), tr[:, 2 * din:].contiguous()
-    state = [opt._state(dev) for opt in opts]
-    m, v = torch.stack([st[0] for st in state]), torch.stack([st[1] for st in state])
-    g = opts[0].param_groups[0]
-    step0 = (ctypes.c_int64 * K)(*[int(opt.step_count) for opt in opts])
-    idx_d = torch.from_numpy(np.ascontiguousarray(idx)).to(dev)
-    loss = torch.empty((K, steps), dtype=torch.float32, device=dev)
-    route = ctypes.c_int(-1)
-    check(load().mjx_dyn_fit_ensemble(ptr(X), 0, ptr(Y), 0, N, K, _ints(sizes), len(sizes), ptr(in_tr), ptr(out_tr),
-                                      TGT_RESIDUAL if nets[0].residual else TGT_PLAIN, _act_code(nets[0]), ptr(P), ptr(m), ptr(v), step0,
-                                      ptr(idx_d), steps, int(fit_mb_size), float(g['lr']), float(g['weight_decay']), ptr(loss),
-                                      ctypes.byref(route), _stream(dev)))
-    losses = loss.cpu().numpy()
-    out = []
-    with torch.no_grad():
-        for i, (net, opt) in enumerate(zip(nets, opts)):
-            opt.exp_avg.copy_(m[i]); opt.exp_avg_sq.copy_(v[i])
-            opt.step_count += steps
-            k = 0
-            for p in net.parameters():
-                p.data.copy_(P[i, k:k + p.numel()].view_as(p))
-                k += p.numel()
-            net._generation = getattr(net, "_generation", 0) + 1     # (an MPCPolicy repacks its device copy)
-            out.append(epoch_means(losses[i], num_steps, ran))
-    return out
+    if set_transformations:
+        for mdl, net in zip(models, nets):       # on each member's device, as fit_dynamics forms them
+            net.set_transformations(*_dynamics_transforms(net.residual, s.to(mdl.device), a.to(mdl.device), sp.to(mdl.device)))
+    return _fit_members(nets, opts, lambda dev: (_f32(torch.cat([s, a], -1), dev), 0), sp, TGT_RESIDUAL if nets[0].residual else TGT_PLAIN,
+                        fit_mb_size, fit_epochs, max_steps, "mjx_dyn_fit_ensemble", _draws)
 
 
 def _same_reward_fit(models):
@@ -431,21 +455,6 @@ def _same_reward_fit(models):
                 or g['weight_decay'] != g0['weight_decay']):
             return False
     return True
-
-
-def _write_back(nets, opts, P, m, v, steps, losses, num_steps, ran):
-    out = []
-    with torch.no_grad():
-        for i, (net, opt) in enumerate(zip(nets, opts)):
-            opt.exp_avg.copy_(m[i]); opt.exp_avg_sq.copy_(v[i])
-            opt.step_count += steps
-            k = 0
-            for p in net.parameters():
-                p.data.copy_(P[i, k:k + p.numel()].view_as(p))
-                k += p.numel()
-            net._generation = getattr(net, "_generation", 0) + 1
-            out.append(epoch_means(losses[i], num_steps, ran))
-    return out
 
 
 def fit_reward_ensemble(models, s, a, r, fit_mb_size, fit_epochs, max_steps=1e4, set_transformations=True, _draws=None):
@@ -470,45 +479,22 @@ def fit_reward_ensemble(models, s, a, r, fit_mb_size, fit_epochs, max_steps=1e4,
         a = torch.from_numpy(a).float()
         r = torch.from_numpy(r).float()
     if set_transformations:
-        for mdl in models:
-            # the reference's transform expressions, on each member's device (nn_dynamics.py:135-139), as fit_reward forms them
-            s_, a_, r_ = s.to(mdl.device), a.to(mdl.device), r.to(mdl.device)
-            s_shift, a_shift = torch.mean(s_, dim=0), torch.mean(a_, dim=0)
-            s_scale, a_scale = torch.mean(torch.abs(s_ - s_shift), dim=0), torch.mean(torch.abs(a_ - a_shift), dim=0)
-            r_shift, r_scale = torch.mean(r_, dim=0), torch.mean(torch.abs(r_ - r_shift), dim=0)
-            mdl.reward_net.set_transformations(s_shift, s_scale, a_shift, a_scale, r_shift, r_scale)
-    dev = _device()
-    K, N = len(models), int(r.shape[0])
+        for mdl in models:                       # on each member's device, as fit_reward forms them
+            mdl.reward_net.set_transformations(*_reward_transforms(s.to(mdl.device), a.to(mdl.device), r.to(mdl.device)))
     nets, opts = [mdl.reward_net for mdl in models], [mdl.reward_opt for mdl in models]
-    idx, num_steps, ran = _draws if _draws is not None else ensemble_fit_indices(K, N, fit_mb_size, fit_epochs, max_steps)
-    steps = ran * num_steps
-    if steps == 0:
-        return [epoch_means([], num_steps, ran) for _ in models]
-    sizes = nets[0].layer_sizes
-    din = sizes[0]
-    sa = _f32(torch.cat([s, a], -1), dev)
-    # s'_k = dynamics_net_k.forward(s, a): k_dyn_forward computes each row by itself, so the batched launch gives the same bits
-    dyn = [mdl.dynamics_net for mdl in models]
-    if len({tuple(d.layer_sizes) for d in dyn}) == 1:
-        sp = ensemble_forward(dyn, sa, dev)
-    else:
-        sp = torch.stack([ensemble_forward([d], sa, dev)[0] for d in dyn])
-    X = torch.cat([sa.unsqueeze(0).expand(K, -1, -1), sp], -1).contiguous()          # K x N x (2 n + m)
-    Y = _f32(r.reshape(N, -1), dev)
-    P = torch.stack([_flat_params(net, dev) for net in nets])
-    tr = torch.stack([_packed_transforms(net, dev) for net in nets])
-    in_tr, out_tr = tr[:, :2 * din].contiguous(), tr[:, 2 * din:].contiguous()
-    state = [opt._state(dev) for opt in opts]
-    m, v = torch.stack([st[0] for st in state]), torch.stack([st[1] for st in state])
-    g = opts[0].param_groups[0]
-    step0 = (ctypes.c_int64 * K)(*[int(opt.step_count) for opt in opts])
-    idx_d = torch.from_numpy(np.ascontiguousarray(idx)).to(dev)
-    loss = torch.empty((K, steps), dtype=torch.float32, device=dev)
-    route = ctypes.c_int(-1)
-    check(load().mjx_reward_fit_ensemble(ptr(X), N * din, ptr(Y), 0, N, K, _ints(sizes), len(sizes), ptr(in_tr), ptr(out_tr),
-                                         _act_code(nets[0]), ptr(P), ptr(m), ptr(v), step0, ptr(idx_d), steps, int(fit_mb_size),
-                                         float(g['lr']), float(g['weight_decay']), ptr(loss), ctypes.byref(route), _stream(dev)))
-    return _write_back(nets, opts, P, m, v, steps, loss.cpu().numpy(), num_steps, ran)
+
+    def make_x(dev):
+        sa = _f32(torch.cat([s, a], -1), dev)
+        # s'_k = dynamics_net_k.forward(s, a): k_dyn_forward computes each row by itself, so the batched launch gives the same bits
+        dyn = [mdl.dynamics_net for mdl in models]
+        if len({tuple(d.layer_sizes) for d in dyn}) == 1:
+            sp = ensemble_forward(dyn, sa, dev)
+        else:
+            sp = torch.stack([ensemble_forward([d], sa, dev)[0] for d in dyn])
+        X = torch.cat([sa.unsqueeze(0).expand(len(models), -1, -1), sp], -1).contiguous()          # K x N x (2 n + m)
+        return X, X.shape[1] * X.shape[2]
+
+    return _fit_members(nets, opts, make_x, r, TGT_AFFINE, fit_mb_size, fit_epochs, max_steps, "mjx_reward_fit_ensemble", _draws)
 
 
 def world_model_fit_indices(K, num_samples, batch_size, epochs, max_steps=1e10, learn_reward=True):
@@ -584,13 +570,7 @@ def ensemble_path_rewards(models, observations, actions):
 def pack_dynamics_members(models, dev):
     """the device blocks a rollout over K members reads, for members that share shape, activation and flags (asserted):
     dict(sizes, P (K x params), tr (K x transforms), act, flags)"""
-    nets = [mdl.dynamics_net for mdl in models]
-    sizes = tuple(nets[0].layer_sizes)
-    for net in nets:
-        assert tuple(net.layer_sizes) == sizes, "ensemble members must share one shape"
-    assert len(set((_act_code(net), _flags(net)) for net in nets)) == 1, "ensemble members must share activation and output transforms"
-    return dict(sizes=sizes, P=torch.stack([_flat_params(net, dev) for net in nets]),
-                tr=torch.stack([_packed_transforms(net, dev) for net in nets]), act=_act_code(nets[0]), flags=_flags(nets[0]))
+    return pack_members([mdl.dynamics_net for mdl in models], dev)
 
 
 def pack_reward_members(models, dev):
@@ -598,14 +578,26 @@ def pack_reward_members(models, dev):
     ``rollout_models`` does): dict(dyn_sizes, dyn_P, dyn_tr, dyn_act, dyn_flags, rew_sizes, rew_P, rew_tr, rew_act)"""
     models = list(models)
     assert models and all(mdl.learn_reward for mdl in models), "every member must learn its reward"
-    dyn, rew = [mdl.dynamics_net for mdl in models], [mdl.reward_net for mdl in models]
-    for nets in (dyn, rew):
-        assert len({tuple(net.layer_sizes) for net in nets}) == 1, "ensemble members must share one shape"
-        assert len({(_act_code(net), _flags(net)) for net in nets}) == 1, "ensemble members must share activation and output transforms"
-    return dict(dyn_sizes=tuple(dyn[0].layer_sizes), dyn_P=torch.stack([_flat_params(net, dev) for net in dyn]),
-                dyn_tr=torch.stack([_packed_transforms(net, dev) for net in dyn]), dyn_act=_act_code(dyn[0]), dyn_flags=_flags(dyn[0]),
-                rew_sizes=tuple(rew[0].layer_sizes), rew_P=torch.stack([_flat_params(net, dev) for net in rew]),
-                rew_tr=torch.stack([_packed_transforms(net, dev) for net in rew]), rew_act=_act_code(rew[0]))
+    dyn, rew = pack_members([mdl.dynamics_net for mdl in models], dev), pack_members([mdl.reward_net for mdl in models], dev)
+    out = {"dyn_" + k: v for k, v in dyn.items()}
+    out.update(("rew_" + k, v) for k, v in rew.items() if k != "flags")          # (a reward net's flags are OUT_AFFINE, always)
+    return out
+
+
+def cached_members_pack(stored, members, dev, with_rewards, extras=None):
+    """THE device cache of ensemble members.  ``stored``: the (key, blocks, held) of an earlier call, or None -> (the tuple to store,
+    whether the members were packed anew).  They are when :func:`members_pack_key` no longer gives the stored key: fresh blocks of
+    :func:`pack_dynamics_members`, then ``extras(blocks)`` (a holder's own additions), then with ``with_rewards`` the blocks of
+    :func:`pack_reward_members` under ``"rew"``."""
+    key, held = members_pack_key(members, dev, with_rewards)
+    if stored is not None and stored[0] == key:
+        return stored, False
+    pk = pack_dynamics_members(members, dev)
+    if extras is not None:
+        extras(pk)
+    if with_rewards:
+        pk["rew"] = pack_reward_members(members, dev)
+    return (key, pk, held), True
 
 
 def members_pack_key(members, dev, with_rewards):

@@ -4,7 +4,8 @@ Mirrors ``mjrl.algos.model_accel.sampling`` (reference sampling.py): ``policy_ro
 ONE persistent launch (``mjx_model_rollout``, csrc/dynamics.h) in which each workgroup walks a tile of trajectories of one
 ensemble member through all H steps: policy mean, + noise * exp(log_std), action clamp, dynamics, state clamp.  The noise
 is the reference's: ``torch.randn((N, m))`` once per step, drawn on the host from torch's global stream in the same order
-(:func:`draw_rollout_noise`) and uploaded once, so the noisy rollouts see the same numbers.  Real-environment sampling
+(:func:`draw_rollout_noise`) and uploaded once, so the noisy rollouts see the same numbers.  Both rollouts read the members as
+``nn_dynamics.pack_dynamics_members`` packs them and their bounds as :func:`rollout_bounds` forms them.  Real-environment sampling
 (``sample_paths``, ``evaluate_policy``) are host loops around ``policy.get_action`` -- for an
 :class:`~mjrl_amd.algos.model_accel.model_learning_mpc.MPCPolicy` that call is where the GPU work happens.
 """
@@ -14,8 +15,7 @@ import numpy as np
 import torch
 
 from ..._lib import check, load, ptr
-from .nn_dynamics import (_act_code, _device, _f32, _flags, _flat_params, _ints, _packed_transforms, _stream,
-                          pack_dynamics_members)
+from .nn_dynamics import _device, _f32, _ints, _stream, pack_dynamics_members
 
 
 def _as_env(env, env_kwargs=None):
@@ -51,20 +51,14 @@ def rollout_models(models, policy, init_states, horizon, noise=None, s_min=None,
     """K learned models (WorldModel) from the same N initial states in one launch -> (obs (K, N, H, n), act (K, N, H, m))
     as NumPy fp32.  noise: (K, H, N, m) or None (eval_mode); actions (N, H, m): trajectory_rollout (no policy, no clamp)."""
     dev = _device()
-    nets = [mdl.dynamics_net for mdl in models]
-    sizes = nets[0].layer_sizes
-    for net in nets:
-        assert tuple(net.layer_sizes) == tuple(sizes), "ensemble members must share one shape"
-    n, m = nets[0].state_dim, nets[0].act_dim
-    K = len(nets)
+    net0 = models[0].dynamics_net
+    n, m = net0.state_dim, net0.act_dim
+    K = len(models)
     s0 = _f32(init_states, dev).reshape(-1, n)
     N = s0.shape[0]
     H = int(horizon)
-    acts = set((_act_code(net), _flags(net)) for net in nets)
-    assert len(acts) == 1, "ensemble members must share activation and output transforms"
-    act, flags = acts.pop()
-    P = torch.stack([_flat_params(net, dev) for net in nets])
-    tr = torch.stack([_packed_transforms(net, dev) for net in nets])
+    pk = pack_dynamics_members(models, dev)
+    sizes, P, tr, act, flags = pk["sizes"], pk["P"], pk["tr"], pk["act"], pk["flags"]
     obs = torch.empty((K, N, H, n), dtype=torch.float32, device=dev)
     act_out = torch.empty((K, N, H, m), dtype=torch.float32, device=dev)
     lib = load()
@@ -73,9 +67,7 @@ def rollout_models(models, policy, init_states, horizon, noise=None, s_min=None,
         pol_P = _f32(policy.get_param_values(), dev)
         pol_tr = _f32(policy.model.packed_transforms(), dev)
         nz = None if noise is None else _f32(noise, dev)
-        bnd = [_bound(a_min, m, -large_value), _bound(a_max, m, large_value),
-               _bound(s_min, n, -large_value), _bound(s_max, n, large_value)]
-        bnd = [b.to(dev) for b in bnd]
+        bnd = rollout_bounds(n, m, dev, s_min, s_max, a_min, a_max, large_value)
         check(lib.mjx_model_rollout(ptr(s0), N, H, K, _ints(pol_sizes), len(pol_sizes), ptr(pol_P), ptr(pol_tr), ptr(nz), None,
                                     _ints(sizes), len(sizes), ptr(P), ptr(tr), act, flags, ptr(bnd[0]), ptr(bnd[1]),
                                     ptr(bnd[2]), ptr(bnd[3]), ptr(obs), ptr(act_out), _stream(dev)))

@@ -547,7 +547,7 @@ int mjx_plan_route(const int* dyn_sizes, int dyn_n_sizes, int act_dim) {
   DynNet net;
   if (int rc = dyn_net(dyn_sizes, dyn_n_sizes, net)) return rc;
   if (act_dim <= 0 || net.din() != net.dout() + act_dim) return fail(MJX_ERR_ARG, "dyn_sizes must be [n + m, h..., n] with m = act_dim > 0");
-  PlanShape ps;
+  ChainShape ps;
   return plan_shape(net, act_dim, ps) ? 1 : 0;
 }
 
@@ -562,27 +562,19 @@ int mjx_plan_rollout(const float* s0, int64_t s0_stride, int64_t N, int H, int K
   if (N == 0 || H == 0) return MJX_OK;
   MJX_DEVICE_ENTRY();
   hipStream_t st = (hipStream_t)stream;
-  PlanShape ps;
+  ChainShape ps;
   if (env_flag("MJX_PLAN_MFMA", true) && plan_shape(net, m, ps)) {      // (read per call: A/B runs in one process)
-    const PlanKernel kern = plan_kernel(ps.HB, ps.NB);
-    const int e = mjx::dyn_lds((const void*)kern, ps.bytes);
-    if (e == 0) {
-      PlanArgs a{s0, s0_stride, actions, dyn_params, dyn_tr, obs_out, N, net.P, H, n, m, net.sz[1], net.sz[2], act, flags};
-      hipLaunchKernelGGL(kern, dim3((unsigned)((N + 127) / 128), (unsigned)K), dim3(256), ps.bytes, st, a);
-      HIPCHK(hipGetLastError());
-      return MJX_OK;
-    }
-    if (e != mjx::LDS_OVER) (void)hipGetLastError();                     // a refusal falls back to the generic route
+    const PlanArgs a{s0, s0_stride, actions, dyn_params, dyn_tr, obs_out, N, net.P, H, n, m, net.sz[1], net.sz[2], act, flags};
+    bool launched;
+    if (int rc = launch_chained(plan_kernel(ps.HB, ps.NB), ps.bytes, dim3((unsigned)((N + 127) / 128), (unsigned)K), a, st, launched)) return rc;
+    if (launched) return MJX_OK;
   }
   // generic route: k_model_rollout with the actions given, as mjx_model_rollout launches it; its action copy and the tiled
   // start state go to scratch
   float* scr = nullptr;
   const size_t act_floats = (size_t)K * N * H * m, s0_floats = s0_stride ? 0 : (size_t)N * n;
   if (int rc = dev_scratch(SITE_PLAN_ROLLOUT, stream, (act_floats + s0_floats) * sizeof(float), &scr)) return rc;
-  if (!s0_stride) {
-    hipLaunchKernelGGL(k_plan_tile_s0, dim3(capped_grid(N * n, 256, 1024)), dim3(256), 0, st, s0, N, n, scr + act_floats);
-    s0 = scr + act_floats;
-  }
+  if (!s0_stride) s0 = tile_s0(s0, N, n, scr + act_floats, st);
   RolloutArgs a{};
   a.dyn = net;
   return launch_model_rollout(a, s0, N, H, K, actions, dyn_params, dyn_tr, act, flags, obs_out, scr, st);
@@ -616,10 +608,8 @@ int mjx_plan_score(const float* obs, const double* rewards, const double* action
 // ---------------------------------------------------------------------------- learned path rewards (csrc/path_reward.h)
 int mjx_path_rewards_route(const int* dyn_sizes, int dyn_n_sizes, const int* rew_sizes, int rew_n_sizes) {
   DynNet dyn, rew;
-  if (int rc = dyn_net(dyn_sizes, dyn_n_sizes, dyn)) return rc;
-  if (int rc = dyn_net(rew_sizes, rew_n_sizes, rew)) return rc;
-  if (!path_rew_nets_ok(dyn, rew)) return fail(MJX_ERR_ARG, "sizes must be [n + m, h..., n] and [2 n + m, g..., 1] with m > 0");
-  PathRewShape ps;
+  if (int rc = path_rew_nets(dyn_sizes, dyn_n_sizes, rew_sizes, rew_n_sizes, dyn, rew)) return rc;
+  ChainShape ps;
   return path_rew_shape(dyn, rew, ps) ? 1 : 0;
 }
 
@@ -628,34 +618,26 @@ int mjx_path_rewards(const float* obs, const float* act, int64_t act_stride, int
                      const float* rew_params, const float* rew_tr, int rew_act, float* r32_out, double* r64_out, int* route_out,
                      void* stream) {
   DynNet dyn, rew;
-  if (int rc = dyn_net(dyn_sizes, dyn_n_sizes, dyn)) return rc;
-  if (int rc = dyn_net(rew_sizes, rew_n_sizes, rew)) return rc;
-  if (!path_rew_nets_ok(dyn, rew)) return fail(MJX_ERR_ARG, "sizes must be [n + m, h..., n] and [2 n + m, g..., 1] with m > 0");
+  if (int rc = path_rew_nets(dyn_sizes, dyn_n_sizes, rew_sizes, rew_n_sizes, dyn, rew)) return rc;
   const int n = dyn.dout(), m = dyn.din() - n;
   if (!obs || !act || !dyn_params || !dyn_tr || !rew_params || !rew_tr || (!r32_out && !r64_out) || rows < 0 ||
       (act_stride != 0 && act_stride != rows * m) || (dyn_flags & ~(DYN_OUT_AFFINE | DYN_MASK | DYN_RESIDUAL)) ||
       !dyn_args_ok(dyn, K, dyn_act, DYN_TGT_PLAIN, dyn_flags & DYN_RESIDUAL) || !dyn_args_ok(rew, K, rew_act))
     return fail(MJX_ERR_ARG, "bad arguments");
-  PathRewShape ps;
+  ChainShape ps;
   const bool served = env_flag("MJX_PATH_REWARDS_MFMA", true) && path_rew_shape(dyn, rew, ps);     // (read per call: A/B runs in one process)
   if (rows == 0) { if (route_out) *route_out = served ? 1 : 0; return MJX_OK; }
   MJX_DEVICE_ENTRY();
   hipStream_t st = (hipStream_t)stream;
   if (served) {
-    const PathRewKernel kern = path_rew_kernel(ps.HB, ps.NB);
-    const int e = mjx::dyn_lds((const void*)kern, ps.bytes);
-    if (e == 0) {
-      PathRewArgs a{obs, act, act_stride, dyn_params, dyn_tr, rew_params, rew_tr, r32_out, r64_out, rows, dyn.P, rew.P,
-                    n, m, dyn.sz[1], dyn.sz[2], dyn_act, dyn_flags, rew.sz[1], rew.sz[2], rew_act};
-      // a wave owns tiles of 32 rows; one workgroup per CU holds the image, so the K members share the CUs and a wave walks the
-      // tiles beyond that (the staging prologue is paid once per workgroup)
-      const int64_t groups = (rows + 127) / 128, cap = (cu_count() + K - 1) / K;
-      hipLaunchKernelGGL(kern, dim3((unsigned)(groups < cap ? groups : cap), (unsigned)K), dim3(256), ps.bytes, st, a);
-      HIPCHK(hipGetLastError());
-      if (route_out) *route_out = 1;
-      return MJX_OK;
-    }
-    if (e != mjx::LDS_OVER) (void)hipGetLastError();                     // a refusal falls back to the generic route
+    const PathRewArgs a{obs, act, act_stride, dyn_params, dyn_tr, rew_params, rew_tr, r32_out, r64_out, rows, dyn.P, rew.P,
+                        n, m, dyn.sz[1], dyn.sz[2], dyn_act, dyn_flags, rew.sz[1], rew.sz[2], rew_act};
+    // a wave owns tiles of 32 rows; one workgroup per CU holds the image, so the K members share the CUs and a wave walks the
+    // tiles beyond that (the staging prologue is paid once per workgroup)
+    const int64_t groups = (rows + 127) / 128, cap = (cu_count() + K - 1) / K;
+    bool launched;
+    if (int rc = launch_chained(path_rew_kernel(ps.HB, ps.NB), ps.bytes, dim3((unsigned)(groups < cap ? groups : cap), (unsigned)K), a, st, launched)) return rc;
+    if (launched) { if (route_out) *route_out = 1; return MJX_OK; }
   }
   // generic route: mjx_dyn_forward's kernel twice, over [s, a] and over [s, a, s'], both assembled in scratch
   const int din = n + m, rin = din + n;
@@ -681,10 +663,8 @@ int mjx_path_rewards(const float* obs, const float* act, int64_t act_stride, int
 // ---------------------------------------------------------------------------- policy rollout on learned models (csrc/policy_rollout.h)
 int mjx_policy_rollout_route(const int* pol_sizes, int pol_n_sizes, const int* dyn_sizes, int dyn_n_sizes) {
   DynNet pol, dyn;
-  if (int rc = dyn_net(pol_sizes, pol_n_sizes, pol)) return rc;
-  if (int rc = dyn_net(dyn_sizes, dyn_n_sizes, dyn)) return rc;
-  if (!pol_roll_nets_ok(dyn, pol)) return fail(MJX_ERR_ARG, "sizes must be [n, p..., m] and [n + m, h..., n] with m > 0");
-  PolRollShape ps;
+  if (int rc = pol_roll_nets(pol_sizes, pol_n_sizes, dyn_sizes, dyn_n_sizes, pol, dyn)) return rc;
+  ChainShape ps;
   return pol_roll_shape(dyn, pol, ps) ? 1 : 0;
 }
 
@@ -694,31 +674,23 @@ int mjx_policy_rollout(const float* s0, int64_t s0_stride, int64_t N, int H, int
                        const float* a_max, const float* s_min, const float* s_max, float* obs_out, float* act_out, int* route_out,
                        void* stream) {
   RolloutArgs a{};
-  if (int rc = dyn_net(dyn_sizes, dyn_n_sizes, a.dyn)) return rc;
-  if (int rc = dyn_net(pol_sizes, pol_n_sizes, a.pol)) return rc;
-  if (!pol_roll_nets_ok(a.dyn, a.pol)) return fail(MJX_ERR_ARG, "policy does not match the state / action dims");
+  if (int rc = pol_roll_nets(pol_sizes, pol_n_sizes, dyn_sizes, dyn_n_sizes, a.pol, a.dyn)) return rc;
   const int n = a.dyn.dout(), m = a.dyn.din() - n;
   if (!s0 || !pol_params || !pol_tr || !dyn_params || !dyn_tr || !obs_out || !act_out || N < 0 || H < 0 || !dyn_args_ok(a.dyn, K, act) ||
       (flags & ~(DYN_OUT_AFFINE | DYN_MASK | DYN_RESIDUAL)) || (s0_stride != 0 && s0_stride != n) ||
       (noise_stride != 0 && noise_stride != (int64_t)H * N * m) || (!a_min) != (!a_max) || (!s_min) != (!s_max))
     return fail(MJX_ERR_ARG, "bad arguments");
-  PolRollShape ps;
+  ChainShape ps;
   const bool served = env_flag("MJX_POLICY_ROLLOUT_MFMA", true) && pol_roll_shape(a.dyn, a.pol, ps);   // (read per call: A/B runs in one process)
   if (N == 0 || H == 0) { if (route_out) *route_out = served ? 1 : 0; return MJX_OK; }
   MJX_DEVICE_ENTRY();
   hipStream_t st = (hipStream_t)stream;
   if (served) {
-    const PolRollKernel kern = pol_roll_kernel(ps.HB, ps.NB);
-    const int e = mjx::dyn_lds((const void*)kern, ps.bytes);
-    if (e == 0) {
-      PolRollArgs p{s0, s0_stride, noise, noise_stride ? (int64_t)H : 0, pol_params, pol_tr, dyn_params, dyn_tr, a_min, a_max, s_min, s_max,
-                    obs_out, act_out, N, a.dyn.P, H, n, m, a.dyn.sz[1], a.dyn.sz[2], act, flags, a.pol.sz[1], a.pol.sz[2]};
-      hipLaunchKernelGGL(kern, dim3((unsigned)((N + 127) / 128), (unsigned)K), dim3(256), ps.bytes, st, p);
-      HIPCHK(hipGetLastError());
-      if (route_out) *route_out = 1;
-      return MJX_OK;
-    }
-    if (e != mjx::LDS_OVER) (void)hipGetLastError();                     // a refusal falls back to the generic route
+    const PolRollArgs p{s0, s0_stride, noise, noise_stride ? (int64_t)H : 0, pol_params, pol_tr, dyn_params, dyn_tr, a_min, a_max, s_min, s_max,
+                        obs_out, act_out, N, a.dyn.P, H, n, m, a.dyn.sz[1], a.dyn.sz[2], act, flags, a.pol.sz[1], a.pol.sz[2]};
+    bool launched;
+    if (int rc = launch_chained(pol_roll_kernel(ps.HB, ps.NB), ps.bytes, dim3((unsigned)((N + 127) / 128), (unsigned)K), p, st, launched)) return rc;
+    if (launched) { if (route_out) *route_out = 1; return MJX_OK; }
   }
   // generic route: k_model_rollout as mjx_model_rollout launches it; the tiled start state and the K copies of a shared noise
   // block go to the calling thread's scratch block of this site on (device, stream)
@@ -726,10 +698,7 @@ int mjx_policy_rollout(const float* s0, int64_t s0_stride, int64_t N, int H, int
   if (s0_floats + nz_floats) {
     float* scr = nullptr;
     if (int rc = dev_scratch(SITE_POLICY_ROLLOUT, stream, (s0_floats + nz_floats) * sizeof(float), &scr)) return rc;
-    if (s0_floats) {
-      hipLaunchKernelGGL(k_plan_tile_s0, dim3(capped_grid(N * n, 256, 1024)), dim3(256), 0, st, s0, N, n, scr);
-      s0 = scr;
-    }
+    if (s0_floats) s0 = tile_s0(s0, N, n, scr, st);
     if (nz_floats) {
       hipLaunchKernelGGL(k_pol_expand_noise, dim3(capped_grid((int64_t)nz_floats, 256, 4096)), dim3(256), 0, st, noise, (int64_t)H * N * m, K,
                          scr + s0_floats);
@@ -840,6 +809,34 @@ static int dfe_run(const float* x, int64_t x_stride, const float* y, int64_t y_s
   HIPCHK(hipGetLastError());
   return MJX_OK;
 }
+
+// the body of both ensemble entries, after the sizes are parsed: the argument check, the route (the entry's switch, read per call -- the
+// tests and tools/bench_dyn_fit.py compare the two routes in one process -- and what its shape predicate answered) written to route_out,
+// then route 0, member by member on the routes of mjx_dyn_fit_adam, or route 1, dfe_run<RAG>
+template <bool RAG>
+static int dfe_entry(const float* x, int64_t x_stride, const float* y, int64_t y_stride, int64_t N, int K, const int* sizes, int n_sizes,
+                     const DynNet& net, const float* in_tr, const float* out_tr, int target_mode, int act, float* params, float* m, float* v,
+                     const int64_t* step0, const int32_t* idx, int64_t steps, int batch, float lr, float wd, float* loss_out,
+                     const char* switch_name, bool shape_served, int* route_out, void* stream) {
+  const int din = net.din(), dout = net.dout();
+  if (!x || !y || !in_tr || !out_tr || !params || !m || !v || !step0 || (steps > 0 && (!idx || !loss_out)) || N <= 0 ||
+      x_stride < 0 || y_stride < 0 || batch <= 0 || batch > N || steps < 0 || !dyn_args_ok(net, K, act, target_mode))
+    return fail(MJX_ERR_ARG, "bad arguments");
+  for (int k = 0; k < K; ++k) if (step0[k] < 0) return fail(MJX_ERR_ARG, "bad arguments");
+  const int route = env_flag(switch_name, true) && shape_served ? 1 : 0;
+  if (route_out) *route_out = route;
+  if (steps == 0) return MJX_OK;
+  if (route == 0) {
+    for (int k = 0; k < K; ++k)
+      if (int rc = mjx_dyn_fit_adam(x + k * x_stride, y + k * y_stride, N, sizes, n_sizes, in_tr + (int64_t)k * 2 * din, out_tr + (int64_t)k * 2 * dout,
+                                    target_mode, act, params + k * net.P, m + k * net.P, v + k * net.P, step0[k],
+                                    idx + (int64_t)k * steps * batch, steps, batch, lr, wd, loss_out + (int64_t)k * steps, stream))
+        return rc;
+    return MJX_OK;
+  }
+  return dfe_run<RAG>(x, x_stride, y, y_stride, N, K, net, in_tr, out_tr, target_mode, act, params, m, v, step0, idx, steps, batch, lr, wd,
+                      loss_out, stream);
+}
 }  // extern "C++"
 
 // ---- the whole ensemble's fit (csrc/dyn_fit_ens.h)
@@ -856,25 +853,8 @@ int mjx_dyn_fit_ensemble(const float* x, int64_t x_stride, const float* y, int64
                          int* route_out, void* stream) {
   DynNet net;
   if (int rc = dyn_net(sizes, n_sizes, net)) return rc;
-  const int din = net.din(), dout = net.dout();
-  if (!x || !y || !in_tr || !out_tr || !params || !m || !v || !step0 || (steps > 0 && (!idx || !loss_out)) || N <= 0 ||
-      x_stride < 0 || y_stride < 0 || batch <= 0 || batch > N || steps < 0 || !dyn_args_ok(net, K, act, target_mode))
-    return fail(MJX_ERR_ARG, "bad arguments");
-  for (int k = 0; k < K; ++k) if (step0[k] < 0) return fail(MJX_ERR_ARG, "bad arguments");
-  // (read per call: the tests and tools/bench_dyn_fit.py compare the two routes in one process)
-  const int route = env_flag("MJX_DYN_FIT_ENS", true) && dfe_serves(net, batch, target_mode) ? 1 : 0;
-  if (route_out) *route_out = route;
-  if (steps == 0) return MJX_OK;
-  if (route == 0) {                                        // member by member on the routes of mjx_dyn_fit_adam
-    for (int k = 0; k < K; ++k)
-      if (int rc = mjx_dyn_fit_adam(x + k * x_stride, y + k * y_stride, N, sizes, n_sizes, in_tr + (int64_t)k * 2 * din, out_tr + (int64_t)k * 2 * dout, target_mode, act, params + k * net.P,
-                                    m + k * net.P, v + k * net.P, step0[k], idx + (int64_t)k * steps * batch, steps, batch, lr, wd,
-                                    loss_out + (int64_t)k * steps, stream))
-        return rc;
-    return MJX_OK;
-  }
-  return dfe_run<false>(x, x_stride, y, y_stride, N, K, net, in_tr, out_tr, target_mode, act, params, m, v, step0, idx, steps, batch, lr, wd,
-                        loss_out, stream);
+  return dfe_entry<false>(x, x_stride, y, y_stride, N, K, sizes, n_sizes, net, in_tr, out_tr, target_mode, act, params, m, v, step0, idx, steps,
+                          batch, lr, wd, loss_out, "MJX_DYN_FIT_ENS", dfe_serves(net, batch, target_mode), route_out, stream);
 }
 
 // ---- the reward nets of the whole ensemble (target mode 0: the loss runs through the output affine on raw r)
@@ -900,25 +880,8 @@ int mjx_reward_fit_ensemble(const float* x, int64_t x_stride, const float* y, in
                             int* route_out, void* stream) {
   DynNet net;
   if (int rc = dyn_net(sizes, n_sizes, net)) return rc;
-  const int din = net.din(), dout = net.dout();
-  if (!x || !y || !in_tr || !out_tr || !params || !m || !v || !step0 || (steps > 0 && (!idx || !loss_out)) || N <= 0 ||
-      x_stride < 0 || y_stride < 0 || batch <= 0 || batch > N || steps < 0 || !dyn_args_ok(net, K, act, DYN_TGT_AFFINE))
-    return fail(MJX_ERR_ARG, "bad arguments");
-  for (int k = 0; k < K; ++k) if (step0[k] < 0) return fail(MJX_ERR_ARG, "bad arguments");
-  // (read per call: the tests and tools/bench_dyn_fit.py compare the two routes in one process)
-  const int route = env_flag("MJX_REWARD_FIT_ENS", true) && reward_fit_serves(net, batch) ? 1 : 0;
-  if (route_out) *route_out = route;
-  if (steps == 0) return MJX_OK;
-  if (route == 0) {                                        // member by member on the routes of mjx_dyn_fit_adam
-    for (int k = 0; k < K; ++k)
-      if (int rc = mjx_dyn_fit_adam(x + k * x_stride, y + k * y_stride, N, sizes, n_sizes, in_tr + (int64_t)k * 2 * din, out_tr + (int64_t)k * 2 * dout,
-                                    DYN_TGT_AFFINE, act, params + k * net.P, m + k * net.P, v + k * net.P, step0[k],
-                                    idx + (int64_t)k * steps * batch, steps, batch, lr, wd, loss_out + (int64_t)k * steps, stream))
-        return rc;
-    return MJX_OK;
-  }
-  return dfe_run<true>(x, x_stride, y, y_stride, N, K, net, in_tr, out_tr, DYN_TGT_AFFINE, act, params, m, v, step0, idx, steps, batch, lr, wd,
-                       loss_out, stream);
+  return dfe_entry<true>(x, x_stride, y, y_stride, N, K, sizes, n_sizes, net, in_tr, out_tr, DYN_TGT_AFFINE, act, params, m, v, step0, idx, steps,
+                         batch, lr, wd, loss_out, "MJX_REWARD_FIT_ENS", reward_fit_serves(net, batch), route_out, stream);
 }
 
 int mjx_dyn_pred_error(const float* pred, int K, int64_t rows, int n, const float* s_next, const int64_t* seg_off, int nseg, double lim,

@@ -1,5 +1,6 @@
-// model_host.h -- host side of the learned-model kernels (dynamics.h, dyn_fit_ens.h, plan.h): their shared argument check, their routes as
-// plain arithmetic, and the launches more than one entry makes.  Included by mjx.hip after fail / HIPCHK / lds_limit / capped_grid.
+// model_host.h -- host side of the learned-model kernels (dynamics.h, dyn_fit_ens.h, plan.h, path_reward.h, policy_rollout.h): their shared
+// argument checks, their routes as plain arithmetic, and the launches more than one entry makes.  Included by mjx.hip after fail / HIPCHK /
+// lds_limit / capped_grid.
 #pragma once
 namespace mjx {
 
@@ -31,12 +32,36 @@ inline int launch_model_rollout(RolloutArgs a, const float* s0, int64_t N, int H
   HIPCHK(hipGetLastError());
   return MJX_OK;
 }
+// the one start state of a call tiled to N rows at dst, for k_model_rollout, which reads a state per trajectory -> dst
+inline const float* tile_s0(const float* s0, int64_t N, int n, float* dst, hipStream_t st) {
+  hipLaunchKernelGGL(k_plan_tile_s0, dim3(capped_grid(N * n, 256, 1024)), dim3(256), 0, st, s0, N, n, dst);
+  return dst;
+}
+
+// ---- the three register-chained MFMA routes (k_plan_rollout, k_path_rewards, k_policy_rollout; csrc/mfma_chain.h).  What serves a
+// call: the instance's block counts (RB: the reward blocks, path rewards only) and the bytes of its LDS image.
+struct ChainShape { int HB = 0, NB = 0, RB = 0; size_t bytes = 0; };
+// One launch of such a kernel: 256 threads, the image as its dynamic LDS.  -> MJX_OK with `launched` set, or the launch's error.
+// Not launched: the device refused the image and the caller takes its generic route.  A refusal that is not LDS_OVER came from the
+// runtime, whose error is cleared here so that the generic route's own check does not report it.
+template <class Args>
+inline int launch_chained(void (*kern)(Args), size_t lds_bytes, dim3 grid, const Args& a, hipStream_t st, bool& launched) {
+  launched = false;
+  const int e = dyn_lds((const void*)kern, lds_bytes);
+  if (e != 0) {
+    if (e != LDS_OVER) (void)hipGetLastError();
+    return MJX_OK;
+  }
+  hipLaunchKernelGGL(kern, grid, dim3(256), lds_bytes, st, a);
+  HIPCHK(hipGetLastError());
+  launched = true;
+  return MJX_OK;
+}
 
 // ---- plan rollout.  The k_plan_rollout instance that serves a net, if one does: exactly two hidden layers, both widths multiples
 // of 32 up to 128, n <= 64, actions within the slots a lane keeps ahead, and an LDS image within LDS_MAX (the kernel has no static
 // LDS, so the image is its whole footprint).  MJX_PLAN_MFMA=0 (read per call by mjx_plan_rollout): the generic route.
-struct PlanShape { int HB = 0, NB = 0; size_t bytes = 0; };
-inline bool plan_shape(const DynNet& net, int m, PlanShape& ps) {
+inline bool plan_shape(const DynNet& net, int m, ChainShape& ps) {
   if (net.nl != 3) return false;
   const int n = net.dout(), h1 = net.sz[1], h2 = net.sz[2];
   if (h1 % 32 || h2 % 32 || h1 > 128 || h2 > 128 || n > 64 || plan_pad8(m) > PLAN_MAX_M8) return false;
@@ -56,11 +81,10 @@ inline PlanKernel plan_kernel(int HB, int NB) {
 // runs the blocks in use, so one instance per dynamics instance serves every policy width), BOTH images together within LDS_MAX
 // (the kernel has no static LDS), and an instance that is kept (pol_roll_kept).  MJX_POLICY_ROLLOUT_MFMA=0 (read per call by
 // mjx_policy_rollout): the generic route.
-struct PolRollShape { int HB = 0, NB = 0; size_t bytes = 0; };
 inline bool pol_roll_kept(int HB, int NB) { (void)HB; (void)NB; return true; }
-inline bool pol_roll_shape(const DynNet& dyn, const DynNet& pol, PolRollShape& ps) {
+inline bool pol_roll_shape(const DynNet& dyn, const DynNet& pol, ChainShape& ps) {
   const int n = dyn.dout(), m = dyn.din() - n;
-  PlanShape dp;
+  ChainShape dp;
   if (!plan_shape(dyn, m, dp) || pol.nl != 3) return false;
   const int p1 = pol.sz[1], p2 = pol.sz[2];
   if (p1 > 32 * POL_MAX_PB || p2 > 32 * POL_MAX_PB || !pol_roll_kept(dp.HB, dp.NB)) return false;
@@ -74,10 +98,13 @@ inline PolRollKernel pol_roll_kernel(int HB, int NB) {
                                           {k_policy_rollout<3, 1>, k_policy_rollout<3, 2>}, {k_policy_rollout<4, 1>, k_policy_rollout<4, 2>}};
   return tab[HB - 1][NB - 1];
 }
-// the two nets of one call: sizes that fit each other ([n, p..., m] and [n + m, h..., n])
-inline bool pol_roll_nets_ok(const DynNet& dyn, const DynNet& pol) {
+// the two nets of one call, parsed: sizes that fit each other ([n, p..., m] and [n + m, h..., n])
+inline int pol_roll_nets(const int* pol_sizes, int pol_n_sizes, const int* dyn_sizes, int dyn_n_sizes, DynNet& pol, DynNet& dyn) {
+  if (int rc = dyn_net(dyn_sizes, dyn_n_sizes, dyn)) return rc;
+  if (int rc = dyn_net(pol_sizes, pol_n_sizes, pol)) return rc;
   const int n = dyn.dout(), m = dyn.din() - n;
-  return m > 0 && pol.din() == n && pol.dout() == m;
+  if (m <= 0 || pol.din() != n || pol.dout() != m) return fail(MJX_ERR_ARG, "sizes must be [n, p..., m] and [n + m, h..., n] with m > 0");
+  return MJX_OK;
 }
 
 // ---- learned path rewards.  The k_path_rewards instance that serves a (dynamics, reward) pair, if one does: a dynamics net as
@@ -87,10 +114,9 @@ inline bool pol_roll_nets_ok(const DynNet& dyn, const DynNet& pol) {
 // many as the plan rollout has): up to four reward blocks beside HB <= 3, up to two (widths <= 64) beside the 128-wide dynamics
 // nets, where four would spill registers to scratch and 100 x 100 (205 KB together) would not fit anyway.
 // MJX_PATH_REWARDS_MFMA=0 (read per call by mjx_path_rewards): the generic route.
-struct PathRewShape { int HB = 0, NB = 0, RB = 0; size_t bytes = 0; };
-inline bool path_rew_shape(const DynNet& dyn, const DynNet& rew, PathRewShape& ps) {
+inline bool path_rew_shape(const DynNet& dyn, const DynNet& rew, ChainShape& ps) {
   const int n = dyn.dout(), m = dyn.din() - n;
-  PlanShape dp;
+  ChainShape dp;
   if (!plan_shape(dyn, m, dp) || rew.nl != 3) return false;
   const int g1 = rew.sz[1], g2 = rew.sz[2];
   ps.HB = dp.HB; ps.NB = dp.NB; ps.RB = dp.HB == 4 ? 2 : 4;
@@ -104,10 +130,13 @@ inline PathRewKernel path_rew_kernel(int HB, int NB) {
                                           {k_path_rewards<3, 1, 4>, k_path_rewards<3, 2, 4>}, {k_path_rewards<4, 1, 2>, k_path_rewards<4, 2, 2>}};
   return tab[HB - 1][NB - 1];
 }
-// the two nets of one call: sizes that fit each other ([n + m, h..., n] and [2 n + m, g..., 1])
-inline bool path_rew_nets_ok(const DynNet& dyn, const DynNet& rew) {
+// the two nets of one call, parsed: sizes that fit each other ([n + m, h..., n] and [2 n + m, g..., 1])
+inline int path_rew_nets(const int* dyn_sizes, int dyn_n_sizes, const int* rew_sizes, int rew_n_sizes, DynNet& dyn, DynNet& rew) {
+  if (int rc = dyn_net(dyn_sizes, dyn_n_sizes, dyn)) return rc;
+  if (int rc = dyn_net(rew_sizes, rew_n_sizes, rew)) return rc;
   const int n = dyn.dout(), m = dyn.din() - n;
-  return m > 0 && rew.dout() == 1 && rew.din() == 2 * n + m;
+  if (m <= 0 || rew.dout() != 1 || rew.din() != 2 * n + m) return fail(MJX_ERR_ARG, "sizes must be [n + m, h..., n] and [2 n + m, g..., 1] with m > 0");
+  return MJX_OK;
 }
 
 // ---- dynamics fit.  k_dyn_fit, the persistent trainer, serves hidden widths <= 128 at minibatches <= 64 (shape) whose activations fit in LDS beside
