@@ -281,6 +281,44 @@ __device__ __forceinline__ f32x16 mfma_bf3(const Pc3& a, const Pc3& b, f32x16 c)
   c = MJX_MFMA_BF16(a.p[0], b.p[0], c);
   return c;
 }
+// ... and one of the six at a time (p = 0 .. 5 in mfma_bf3's order), for schedules that place every MFMA by hand
+__device__ __forceinline__ f32x16 mfma_bf3_step(const Pc3& a, const Pc3& b, f32x16 c, int p) {
+  const int pa = p == 0 ? 2 : (p == 2 || p == 3) ? 1 : 0, pb = p == 1 ? 2 : (p == 2 || p == 4) ? 1 : 0;
+  return MJX_MFMA_BF16(a.p[pa], b.p[pb], c);
+}
+// split3() one instruction at a time: step idx = 0 .. 43 of the 44 that split eight values, the same operations on the same
+// values as split3_pair.  Two register pairs (four values) advance together, so that four consecutive steps never depend on
+// each other -- what one MFMA gap carries: 4 ands (hi masks), 4 subtractions (r), 2 perms (hi pieces), 4 ands, 4 subtractions
+// (lo), 2 + 2 perms (mid, lo pieces); then the other two pairs.  w holds the intermediate values between the steps.
+// The steps are plain arithmetic, which the compiler places wherever the data flow allows -- scheduling barriers alone left the
+// 44 steps of a group in lumps of 0 .. 10 per gap.  So every step is tied to its gap from both sides: its constant (the mask, the
+// perm selector) comes from the gap's opening statement (SplitGap::open: an empty volatile asm that passes the two constants on
+// in their scalar registers and, as a memory barrier, keeps the gap's LDS accesses behind it), and its result passes through an
+// empty volatile asm of its own before anything uses it.  No instruction comes of either: one wave per SIMD issues in order, and
+// even a scalar move per gap would take an issue slot of the 8 a 32-cycle MFMA gap has.
+// The 44 steps over the 12 gaps of a K-step group: 3 in each of the first four, 4 in the other eight.  (The first gaps of a
+// phase are where the register allocator parks one or two values in AGPRs in the instances with the most registers; with
+// three steps they stay within the five vector instructions a gap hides.)  Steps of one gap never depend on each other.
+__device__ __forceinline__ constexpr int split3_first(int gap) { return gap < 4 ? 3 * gap : 4 * gap - 4; }
+struct Split3Tmp { uint32_t h[8], m[8]; float r[8], l[8]; };
+struct SplitGap {
+  uint32_t mask = 0xffff0000u, sel = 0x07060302u;
+  __device__ __forceinline__ void open() { asm volatile("" : "+s"(mask), "+s"(sel) : : "memory"); }
+};
+// (an MFMA builtin is as free to move as the arithmetic: its result takes the same way)
+__device__ __forceinline__ void mfma_pin(f32x16& c) { asm volatile("" : "+v"(c)); }
+__device__ __forceinline__ uint32_t split3_pin(uint32_t v) { asm volatile("" : "+v"(v)); return v; }
+__device__ __forceinline__ float split3_pin(float v) { asm volatile("" : "+v"(v)); return v; }
+__device__ __forceinline__ void split3_step(Pc3& o, Split3Tmp& w, const float (&x)[8], int idx, const SplitGap& c) {
+  const int b = idx / 22, t = idx % 22;
+  if (t < 4) { const int i = 4 * b + t; w.h[i] = split3_pin(__float_as_uint(x[i]) & c.mask); }
+  else if (t < 8) { const int i = 4 * b + t - 4; w.r[i] = split3_pin(x[i] - __uint_as_float(w.h[i])); }
+  else if (t < 10) { const int k = 2 * b + t - 8; o.p[0][k] = split3_pin(__builtin_amdgcn_perm(__float_as_uint(x[2 * k + 1]), __float_as_uint(x[2 * k]), c.sel)); }
+  else if (t < 14) { const int i = 4 * b + t - 10; w.m[i] = split3_pin(__float_as_uint(w.r[i]) & c.mask); }
+  else if (t < 18) { const int i = 4 * b + t - 14; w.l[i] = split3_pin(w.r[i] - __uint_as_float(w.m[i])); }
+  else if (t < 20) { const int k = 2 * b + t - 18; o.p[1][k] = split3_pin(__builtin_amdgcn_perm(__float_as_uint(w.r[2 * k + 1]), __float_as_uint(w.r[2 * k]), c.sel)); }
+  else { const int k = 2 * b + t - 20; o.p[2][k] = split3_pin(__builtin_amdgcn_perm(__float_as_uint(w.l[2 * k + 1]), __float_as_uint(w.l[2 * k]), c.sel)); }
+}
 
 // compile-time loop: f(std::integral_constant<int, 0>{}), ..., f(std::integral_constant<int, N - 1>{})
 template <int N, int I = 0, class F>
@@ -931,8 +969,14 @@ __global__ __launch_bounds__(256, (MODE == MODE_EVAL && !DBG && MP <= 8) ? 2 : 1
         }
       if constexpr (XBF3) {
         // bf16x3: A = V2's pieces from slot B's image, B = h1's registers 8 s .. 8 s + 7 of block kb (K-step s) as they lie.  Both
-        // are prepared one K-step group ahead: the next group's split (44 single-issue VALU) and its 6 fragment reads go between
-        // this group's 12 MFMAs (<= 4 VALU per gap), with this group's 16 [unit][sample] stores of h1 / h2
+        // are prepared one K-step group ahead, under this group's 12 MFMAs, and the placement is by program order (as in R9: the
+        // sched_group_barrier pipelines this phase had were honoured for the first group only, the rest of the split work came
+        // out as one lump of ~88 instructions between two MFMAs).  Every gap is closed by a scheduling barrier and carries:
+        // 3 or 4 independent steps of the next group's split (split3_first), one of its 6 fragment reads (gaps 3 .. 8: tile 1's first,
+        // then tile 0's into the registers this group's tile 0 has just finished with -- 36 fragment registers instead of 48)
+        // and one (gaps 3 .. 8) or two of this group's 16 [unit][sample] stores of h1 / h2 -- never more than 4 VALU and 2 DS.
+#pragma unroll
+        for (int mt = 0; mt < MT1; ++mt) mfma_pin(t1[mt]);          // (R1's MFMAs stay in front of this phase)
         __builtin_amdgcn_sched_barrier(0);
         const u32x4* vimg = (const u32x4*)(slotB + L.oW2) + lane;
         Pc3 ac[MT2], an[MT2], bc = split3_of(h1[0], 0), bn = bc;
@@ -942,41 +986,40 @@ __global__ __launch_bounds__(256, (MODE == MODE_EVAL && !DBG && MP <= 8) ? 2 : 1
           for (int p = 0; p < 3; ++p) ac[mt].p[p] = vimg[(p * 8 + mt * 4) * 64];
         __builtin_amdgcn_sched_barrier(0);
         constexpr int NG2 = 2 * MT1;
+        SplitGap gap;
 #pragma unroll
         for (int g = 0; g < NG2; ++g) {
-          if (g + 1 < NG2) {
-            const int kb1 = (g + 1) >> 1, s1 = (g + 1) & 1;
+          const bool nxt = g + 1 < NG2;
+          const int kb1 = nxt ? (g + 1) >> 1 : 0, s1 = (g + 1) & 1;
+          Split3Tmp sw;
+          float xn[8];
 #pragma unroll
-            for (int mt = 0; mt < MT2; ++mt)
+          for (int e = 0; e < 8; ++e) xn[e] = h1[kb1][8 * s1 + e];
 #pragma unroll
-              for (int p = 0; p < 3; ++p) an[mt].p[p] = vimg[(p * 8 + (mt * 2 + kb1) * 2 + s1) * 64];
-            bn = split3_of(h1[kb1], s1);
-          }
+          for (int i = 0; i < 6 * MT2; ++i) {
+            gap.open();
+            t2[i / 6] = mfma_bf3_step(ac[i / 6], bc, t2[i / 6], i % 6);
+            mfma_pin(t2[i / 6]);
+            __builtin_amdgcn_sched_barrier(0);          // (the gap's other instructions: behind its MFMA)
+            if (nxt) {
 #pragma unroll
-          for (int mt = 0; mt < MT2; ++mt) t2[mt] = mfma_bf3(ac[mt], bc, t2[mt]);
+              for (int q = split3_first(i); q < split3_first(i + 1); ++q) split3_step(bn, sw, xn, q, gap);
+              if (i >= 3 && i < 9) { const int mt = i < 6 ? 1 : 0, p = i % 3; an[mt].p[p] = vimg[(p * 8 + (mt * 2 + kb1) * 2 + s1) * 64]; }
+            }
+            // stores e0 .. e1 - 1 of the group's 16 (even: h1 -> bufB, odd: h2 -> bufA)
+            const int e0 = !nxt || i < 3 ? 2 * i : i < 9 ? i + 3 : 2 * i - 6, e1 = !nxt || i < 3 ? 2 * i + 2 : i < 9 ? i + 4 : 2 * i - 4;
 #pragma unroll
-          for (int e = 0; e < 8; ++e) {
-            const int idx = g * 8 + e, mt = idx >> 4, r = idx & 15;
-            LDS_AT(pinB[4 * mt + (r >> 2)])[(r & 3) * ST] = h1[mt][r];
-            LDS_AT(pinA[4 * mt + (r >> 2)])[(r & 3) * ST] = h2[mt][r];
+            for (int e = e0; e < e1 && e < 16; ++e) {
+              const int idx = g * 8 + (e >> 1), mt = idx >> 4, r = idx & 15;
+              if (e & 1) LDS_AT(pinA[4 * mt + (r >> 2)])[(r & 3) * ST] = h2[mt][r];
+              else LDS_AT(pinB[4 * mt + (r >> 2)])[(r & 3) * ST] = h1[mt][r];
+            }
+            __builtin_amdgcn_sched_barrier(0);
           }
 #pragma unroll
           for (int mt = 0; mt < MT2; ++mt) ac[mt] = an[mt];
           bc = bn;
         }
-#pragma unroll
-        for (int g = 0; g < NG2; ++g)
-#pragma unroll
-          for (int i = 0; i < 6 * MT2; ++i) {
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-            if (g + 1 < NG2) {
-              __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);
-              if (i < 3 * MT2) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-            }
-            if (i < 4) __builtin_amdgcn_sched_group_barrier(0x200, 2, 0);
-            else __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);
-          }
-        __builtin_amdgcn_sched_barrier(0);
       } else {
         __builtin_amdgcn_sched_barrier(0);
         f32x4 vc[MT2], vn[MT2];
@@ -1207,8 +1250,9 @@ __global__ __launch_bounds__(256, (MODE == MODE_EVAL && !DBG && MP <= 8) ? 2 : 1
       for (int nt = 0; nt < MT1; ++nt) dl1u[nt] = (f32x16)(0.f);
       if constexpr (XBF3) {
         // bf16x3: delta2's registers 8 s .. 8 s + 7 of block kb are K-step s's A operand as they lie; B = W2^T's pieces from slot
-        // A's image.  As in R2, the next K-step group's split and fragment reads go between this group's 12 MFMAs; the transposed
-        // copy of delta2 (first two groups) and its read-back (last two) ride along as before.
+        // A's image.  As in R2, placed by program order with a scheduling barrier closing every gap: 3 or 4 steps of the next K-step
+        // group's split and one of its 6 fragment reads (gaps 3 .. 8) per gap; the transposed copy of delta2 rides along in the
+        // first two groups (one or two stores per gap) and its read-back in four gaps without a fragment read of the last two.
         __builtin_amdgcn_sched_barrier(0);
         load_h(ptile((tile + tstride < ntiles) ? tile + tstride : tile));
         const u32x4* img = (const u32x4*)(slotA + L.oW2) + lane;
@@ -1219,46 +1263,42 @@ __global__ __launch_bounds__(256, (MODE == MODE_EVAL && !DBG && MP <= 8) ? 2 : 1
 #pragma unroll
           for (int p = 0; p < 3; ++p) bc[nt].p[p] = img[(p * 8 + nt * 4) * 64];
         __builtin_amdgcn_sched_barrier(0);
+        SplitGap gap;
 #pragma unroll
         for (int g = 0; g < NG8; ++g) {
-          if (g + 1 < NG8) {
-            const int kb1 = (g + 1) >> 1, s1 = (g + 1) & 1;
+          const bool nxt = g + 1 < NG8;
+          const int kb1 = nxt ? (g + 1) >> 1 : 0, s1 = (g + 1) & 1;
+          Split3Tmp sw;
+          float xn[8];
 #pragma unroll
-            for (int nt = 0; nt < MT1; ++nt)
+          for (int e = 0; e < 8; ++e) xn[e] = dl2s[kb1][8 * s1 + e];
 #pragma unroll
-              for (int p = 0; p < 3; ++p) bn[nt].p[p] = img[(p * 8 + (nt * 2 + kb1) * 2 + s1) * 64];
-            an = split3_of(dl2s[kb1], s1);
-          }
+          for (int i = 0; i < 6 * MT1; ++i) {
+            gap.open();
+            dl1u[i / 6] = mfma_bf3_step(ac, bc[i / 6], dl1u[i / 6], i % 6);
+            mfma_pin(dl1u[i / 6]);
+            __builtin_amdgcn_sched_barrier(0);          // (the gap's other instructions: behind its MFMA)
+            if (nxt) {
 #pragma unroll
-          for (int nt = 0; nt < MT1; ++nt) dl1u[nt] = mfma_bf3(ac, bc[nt], dl1u[nt]);
-          if (g < MT2) {
+              for (int q = split3_first(i); q < split3_first(i + 1); ++q) split3_step(an, sw, xn, q, gap);
+              if (i >= 3 && i < 9) { const int nt = i < 6 ? 1 : 0, p = i % 3; bn[nt].p[p] = img[(p * 8 + (nt * 2 + kb1) * 2 + s1) * 64]; }
+            }
+            if (g < MT2) {
+              // stores r0 .. r1 - 1 of this block's 16: one beside a fragment read (gaps 3 .. 8), two in the other gaps
+              const int r0 = i < 3 ? 2 * i : i < 9 ? i + 3 : 2 * i - 6, r1 = i < 3 ? 2 * i + 2 : i < 9 ? i + 4 : 2 * i - 4;
 #pragma unroll
-            for (int r = 0; r < 16; ++r) LDS_AT(pinA[4 * g + (r >> 2)])[(r & 3) * ST] = dl2s[g][r];
-          } else {
-            const int nt = g - MT2;
-#pragma unroll
-            for (int qq = 0; qq < 4; ++qq) {
+              for (int r = r0; r < r1 && r < 16; ++r) LDS_AT(pinA[4 * g + (r >> 2)])[(r & 3) * ST] = dl2s[g][r];
+            } else if (i < 3 || i == (nxt ? 9 : 3)) {
+              const int nt = g - MT2, qq = i < 3 ? i : 3;
               const f32x4 v = *(const f32x4*)&bufA[(32 * nt + j) * ST + 8 * qq + 4 * hi];
               dl2u[nt][4 * qq] = v.x; dl2u[nt][4 * qq + 1] = v.y; dl2u[nt][4 * qq + 2] = v.z; dl2u[nt][4 * qq + 3] = v.w;
             }
+            __builtin_amdgcn_sched_barrier(0);
           }
           ac = an;
 #pragma unroll
           for (int nt = 0; nt < MT1; ++nt) bc[nt] = bn[nt];
         }
-#pragma unroll
-        for (int g = 0; g < NG8; ++g)
-#pragma unroll
-          for (int i = 0; i < 6 * MT1; ++i) {
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-            if (g + 1 < NG8) {
-              __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);
-              if (i < 3 * MT1) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-            }
-            if (g < MT2) { if (i < 4) __builtin_amdgcn_sched_group_barrier(0x200, 2, 0); else __builtin_amdgcn_sched_group_barrier(0x200, 1, 0); }
-            else if (i < 4) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-          }
-        __builtin_amdgcn_sched_barrier(0);
       } else {
         constexpr int NG = MT2 * 4;                 // groups of 4 k-steps over the h2 units
         constexpr int NGH = NG / 2;
