@@ -566,6 +566,40 @@ int mjx_path_rewards(const float* obs, const float* act, int64_t act_stride, int
                      const int* rew_sizes, int rew_n_sizes, const float* rew_params, const float* rew_tr, int rew_act,
                      float* r32_out, double* r64_out, int* route_out, void* stream);
 
+/* ---- device-resident model rollouts (ModelAccelNPG.train_step(resident=True); csrc/rollout_batch.h) ---- */
+/* Which route mjx_rollout_disagreement takes for a net dyn_sizes = [n + m, h..., n]: 1 = the MFMA kernel k_rollout_disagree
+ * where mjx_plan_route serves the net with act_dim = m = d_in - d_out, 0 = the generic route, < 0 = bad sizes (m <= 0
+ * included).  Arithmetic only: no device work and no runtime call.  MJX_ROLLOUT_DISAGREE_MFMA=0 (read by
+ * mjx_rollout_disagreement per call) forces route 0. */
+int mjx_rollout_disagreement_route(const int* dyn_sizes, int dyn_n_sizes);
+/* The ensemble-disagreement error (model_accel_npg.py:137-147) of rollouts that are already on the device.  obs (P x H x n
+ * fp32) and act (P x H x m fp32) are the stored rollouts of all members back to back (P is any count; train_step passes
+ * K N); the K members are packed as for mjx_dyn_forward.  For t < H - 1:
+ *   err_out[p (H - 1) + t] = max over k of mean over c of (obs[p][t + 1][c] - f_k(obs[p][t], act[p][t])[c])^2
+ * with f_k unclamped; a row where any member's error is NaN is NaN (np.maximum).  Route 1: each lane adds d * d (fp32, fmaf)
+ * for its units 32 b + (r & 3) + 8 (r >> 2) + 4 hi < n in (b, r) order from 0, the two lane halves are added once (lo + hi),
+ * the sum is divided by (float)n; the members' means go to scratch and their maximum is taken in member order (no float
+ * atomics: fixed bits).  Route 0: err_out carries the bits mjx_dyn_forward plus mjx_dyn_pred_error give on the same rows
+ * (fp32 difference and square, fp64 sum over c, / n, cast to fp32).  *route_out (may be NULL) receives the route taken.
+ * P = 0 or H <= 1 returns MJX_OK without a launch (and reports the route); bad arguments return MJX_ERR_ARG and touch
+ * nothing.  Uses per-host-thread scratch. */
+int mjx_rollout_disagreement(const float* obs, const float* act, int64_t P, int H, int K, const int* dyn_sizes,
+                             int dyn_n_sizes, const float* dyn_params, const float* dyn_tr, int dyn_act, int dyn_flags,
+                             float* err_out, int* route_out, void* stream);
+/* The truncation decision (model_accel_npg.py:149-155) and the ragged batch, packed.  obs P x H x n, act P x H x m fp32;
+ * exactly one of rew32 / rew64 (P x H each); err (P x (H - 1), mjx_rollout_disagreement's output) or NULL.  Per path p:
+ * v = the first t in [0, H - 1) with (double)err[p][t] > lim (a NaN never counts; err NULL: none), -1 if none; T = H when
+ * v < 0, else min(H, max(min_len, v + 1)).  off_out (int64, P + 1) = the exclusive prefix sum of T; first_out[p] = v;
+ * term_out[p] = (T != H) as mjx_gae takes it.  Row off[p] + t, t < T, receives obs[p][t], act[p][t] and the reward as fp64;
+ * with v >= 0 row T - 1 carries (double)r + truncate_reward, rounded to fp32 first when the rewards came as fp32.
+ * obs64_out (the packed observations widened to fp64) and tpos_out (int32: t within the path) may each be NULL.  Outputs
+ * hold P H rows; nothing at or beyond row off[P] is written.  No atomics: every output is exact.  Bad arguments return
+ * MJX_ERR_ARG and touch nothing. */
+int mjx_rollout_pack(const float* obs, const float* act, const float* rew32, const double* rew64, const float* err, int64_t P,
+                     int H, int n, int m, double lim, int min_len, double truncate_reward, int64_t* off_out,
+                     int32_t* first_out, uint8_t* term_out, float* obs_out, float* act_out, double* rew_out,
+                     double* obs64_out, int32_t* tpos_out, void* stream);
+
 /* ---- in-library kernel timing (bench.py roofline) ------------------------- */
 /* While enabled (on = k >= 1), every k-th launch of the dominant Fisher-vector-product kernel
  * (fused k_fused MODE_FVP, or the whole layer-wise FVP chain) is bracketed by hipEvents recorded

@@ -119,6 +119,11 @@ PROTOTYPES = {
     "mjx_path_rewards": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int, ctypes.POINTER(c_int), c_int, c_void_p, c_void_p, c_int, c_int,
                                  ctypes.POINTER(c_int), c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, ctypes.POINTER(c_int),
                                  c_void_p]),
+    "mjx_rollout_disagreement_route": (c_int, [ctypes.POINTER(c_int), c_int]),
+    "mjx_rollout_disagreement": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, ctypes.POINTER(c_int), c_int, c_void_p, c_void_p, c_int,
+                                         c_int, c_void_p, ctypes.POINTER(c_int), c_void_p]),
+    "mjx_rollout_pack": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_double, c_int, c_double,
+                                 c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "mjx_profile_enable": (c_int, [c_void_p, c_int]),
     "mjx_profile_read": (c_int, [c_void_p, ctypes.POINTER(c_double)]),
     "mjx_profile_samples": (c_int, [c_void_p, ctypes.POINTER(c_double), c_int, ctypes.POINTER(c_int)]),

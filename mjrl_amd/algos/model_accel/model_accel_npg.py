@@ -4,7 +4,9 @@
 from torch's global stream in the reference's order, model by model, step by step), hands the rollouts to the host
 reward / termination callables, truncates on ensemble disagreement with the batched forward plus one reduction
 (``mjx_dyn_pred_error``), and then runs the NPG agent's own compute_returns -> compute_advantages -> train_from_paths
--> baseline.fit unchanged.  ``get_refined_action`` keeps the members on the device through ``nn_dynamics.cached_members_pack``, the
+-> baseline.fit unchanged.  With ``resident=True`` the rollouts stay on the device from the rollout to ingestion
+(:meth:`ModelAccelNPG._resident_paths`: the MFMA policy rollout on cached members, learned rewards, disagreement, truncation and
+packing in HIP, one read-back for the host ``paths``, the packed blocks registered with utils/ingest).  ``get_refined_action`` keeps the members on the device through ``nn_dynamics.cached_members_pack``, the
 cache ``MPCPolicy`` uses, with the refinement's default bound vectors as its extras.
 """
 import time as timer
@@ -13,13 +15,24 @@ import numpy as np
 import torch
 
 from ..._lib import check, load, ptr
-from ...utils import process_samples
+from ...utils import ingest, process_samples
 from ..npg_cg import NPG
 from .nn_dynamics import (WorldModel, _device, _ints, _stream, cached_members_pack, ensemble_forward, ensemble_path_rewards,
-                          path_rewards_call)
-from .sampling import _as_env, draw_rollout_noise, rollout_bounds, rollout_models, rollout_models_device
+                          members_share_kind, path_rewards_call, rollout_disagreement_device)
+from .sampling import _as_env, draw_rollout_noise, pack_rollouts_device, rollout_bounds, rollout_models, rollout_models_device
 
 REFINE_LARGE_VALUE = float(1e2)     # the refined call's state / action bounds: policy_rollout's default large_value
+TRAIN_LARGE_VALUE = float(1e2)      # train_step's: rollout_models' default (the same number today; each caller names its own)
+MIN_PATH_LEN = 5                    # train_step drops shorter paths (model_accel_npg.py:134)
+MIN_TRUNCATED_LEN = 4               # ... and keeps at least this much of a truncated one (:150)
+
+
+def _gpu_available():
+    return torch.cuda.is_available()
+
+
+def _distributed():
+    return torch.distributed.is_available() and torch.distributed.is_initialized()
 
 
 def truncation_points(models, paths, truncate_lim):
@@ -47,6 +60,7 @@ def truncation_points(models, paths, truncate_lim):
 class ModelAccelNPG(NPG):
     # (an instance pickled before the refinement existed acts as it did)
     refine_gamma, refine_omega, _refine_pack, _refine_last, _refine_packs = 1.0, 0.0, None, None, 0
+    resident, _step_info = False, None
 
     def __init__(self, learned_model=None,
                  refine=False,
@@ -57,9 +71,11 @@ class ModelAccelNPG(NPG):
                  termination_function=None,
                  refine_gamma=1.0,
                  refine_omega=0.0,
+                 resident=False,
                  **kwargs):
         """Arguments as in the reference (model_accel_npg.py:24-41), plus refine_gamma and refine_omega: the discount and the
-        weight of the per-trajectory ensemble disagreement in get_refined_action's trajectory scores."""
+        weight of the per-trajectory ensemble disagreement in get_refined_action's trajectory scores; and resident: whether
+        train_step keeps the model rollouts on the device up to ingestion (off by default; train_step's own keyword overrides it)."""
         super(ModelAccelNPG, self).__init__(**kwargs)
         if learned_model is None:
             raise ValueError("Algorithm requires a (list of) learned dynamics model")
@@ -70,6 +86,8 @@ class ModelAccelNPG(NPG):
         self.refine, self.kappa, self.plan_horizon, self.plan_paths = refine, kappa, plan_horizon, plan_paths
         self.reward_function, self.termination_function = reward_function, termination_function
         self.refine_gamma, self.refine_omega = refine_gamma, refine_omega
+        self.resident = bool(resident)
+        self._step_info = None      # train_step_info() of the last train_step
         self._refine_pack = None    # (key, device blocks, held tensors) of the members' parameters and transforms
         self._refine_last = None    # (R, S, route) of the last refined call, on the device
         self._refine_packs = 0      # how often the members were packed
@@ -103,9 +121,11 @@ class ModelAccelNPG(NPG):
                    termination_function=None,
                    truncate_lim=None,
                    truncate_reward=0.0,
+                   resident=None,
                    **kwargs,
                    ):
-        """model_accel_npg.py:58-183"""
+        """model_accel_npg.py:58-183.  resident (None: the constructor's): the device-resident route of :meth:`_resident_paths`
+        where :meth:`_resident_decline` has no objection, the host route otherwise; :meth:`train_step_info` says which ran."""
         ts = timer.time()
         env = self.env if env is None else _as_env(env, env_kwargs)
         reward_function = self.reward_function if reward_function is None else reward_function
@@ -123,7 +143,39 @@ class ModelAccelNPG(NPG):
         horizon = int(min(horizon, env.horizon))
         m = self.learned_model[0].dynamics_net.act_dim
         noise = draw_rollout_noise(len(self.learned_model), horizon, N, m)
-        obs_all, act_all = rollout_models(self.learned_model, self.policy, np.array(init_states), horizon, noise)
+        resident = self.resident if resident is None else bool(resident)
+        why = self._resident_decline(horizon, termination_function) if resident else "resident=False"
+        self._step_info = dict(resident=why is None, why=why, routes=None, paths=None, rows=None, truncated=None)
+        if why is None:
+            paths = self._resident_paths(np.array(init_states), horizon, noise, reward_function, truncate_lim, truncate_reward)
+        else:
+            paths = self._host_paths(np.array(init_states), horizon, noise, reward_function, termination_function, truncate_lim,
+                                     truncate_reward)
+
+        if self.save_logs:
+            self.logger.log_kv('time_sampling', timer.time() - ts)
+        self.seed = self.seed + N if self.seed is not None else self.seed
+
+        process_samples.compute_returns(paths, gamma)
+        process_samples.compute_advantages(paths, self.baseline, gamma, gae_lambda)
+        eval_statistics = self.train_from_paths(paths)
+        eval_statistics.append(N)
+        if self.save_logs:
+            num_samples = np.sum([p["rewards"].shape[0] for p in paths])
+            self.logger.log_kv('num_samples', num_samples)
+        if self.save_logs:
+            ts = timer.time()
+            error_before, error_after = self.baseline.fit(paths, return_errors=True)
+            self.logger.log_kv('time_VF', timer.time() - ts)
+            self.logger.log_kv('VF_error_before', error_before)
+            self.logger.log_kv('VF_error_after', error_after)
+        else:
+            self.baseline.fit(paths)
+        return eval_statistics
+
+    def _host_paths(self, init_states, horizon, noise, reward_function, termination_function, truncate_lim, truncate_reward):
+        """the host route's paths (model_accel_npg.py:95-155): rollout, rewards, termination, the length filter, truncation"""
+        obs_all, act_all = rollout_models(self.learned_model, self.policy, init_states, horizon, noise)
         paths = []
         obs = None
         # every member's learned rewards in one batched call (one upload, two launches, one read-back) when all members learn them
@@ -159,27 +211,83 @@ class ModelAccelNPG(NPG):
                 if truncated:
                     path["rewards"][-1] += truncate_reward
                 path["terminated"] = False if T == obs.shape[0] else True
+        return paths
 
-        if self.save_logs:
-            self.logger.log_kv('time_sampling', timer.time() - ts)
-        self.seed = self.seed + N if self.seed is not None else self.seed
+    # ---- the device-resident route
+    def train_step_info(self):
+        """what the last ``train_step`` did: dict(resident, why (the reason the host route ran, else None), routes (dict(rollout,
+        rewards, disagreement): 1 = the MFMA kernel, 0 = the generic route, None = no device call), paths, rows, truncated);
+        None before any call.  The last three are filled by the resident route alone."""
+        return None if self._step_info is None else dict(self._step_info)
 
-        process_samples.compute_returns(paths, gamma)
-        process_samples.compute_advantages(paths, self.baseline, gamma, gae_lambda)
-        eval_statistics = self.train_from_paths(paths)
-        eval_statistics.append(N)
-        if self.save_logs:
-            num_samples = np.sum([p["rewards"].shape[0] for p in paths])
-            self.logger.log_kv('num_samples', num_samples)
-        if self.save_logs:
-            ts = timer.time()
-            error_before, error_after = self.baseline.fit(paths, return_errors=True)
-            self.logger.log_kv('time_VF', timer.time() - ts)
-            self.logger.log_kv('VF_error_before', error_before)
-            self.logger.log_kv('VF_error_after', error_after)
+    def _resident_decline(self, horizon, termination_function):
+        """why the resident route does not serve this call, or None"""
+        models = self.learned_model
+        learned = [bool(mdl.learn_reward) for mdl in models]
+        if callable(termination_function):
+            return "termination_function"               # a host callable over the paths, before the truncation
+        if any(learned) and not all(learned):
+            return "mixed rewards"
+        if not members_share_kind(models, all(learned)):
+            return "members differ"
+        if horizon < MIN_PATH_LEN:
+            return "horizon < %d" % MIN_PATH_LEN        # the length filter drops every path
+        if _distributed():
+            return "distributed"
+        if not _gpu_available():
+            return "no gpu"
+        return None
+
+    def _resident_paths(self, init_states, H, noise, reward_function, truncate_lim, truncate_reward):
+        """the same paths with the rollouts left on the device: one upload (start states, noise), ``mjx_policy_rollout`` on the
+        members ``get_refined_action`` caches, ``mjx_path_rewards`` (or one read-back, the host ``reward_function`` per member and
+        one upload), ``mjx_rollout_disagreement``, ``mjx_rollout_pack``, one read-back of the packed blocks.  The host ``paths``
+        are per-path views of that read-back; the packed device blocks are registered for them (utils/ingest.register_device_batch),
+        so returns, advantages, the update and the baseline read those and upload nothing."""
+        dev = _device()
+        models = self.learned_model
+        K, N = len(models), init_states.shape[0]
+        learned = self._refine_learned()
+        pk = self._refine_packed(dev)
+        info, routes = {}, dict(rollout=None, rewards=None, disagreement=None)
+        obs_d, act_d = rollout_models_device(models, self.policy, init_states, H, noise, large_value=TRAIN_LARGE_VALUE, packed=pk, info=info)
+        routes["rollout"] = info["route"]
+        if learned:
+            rew_d = torch.empty((K, N, H), dtype=torch.float32, device=dev)
+            routes["rewards"] = path_rewards_call(pk["rew"], obs_d, act_d, False, N * H, K, rew_d, None, dev)
         else:
-            self.baseline.fit(paths)
-        return eval_statistics
+            obs_h, act_h = obs_d.cpu().numpy(), act_d.cpu().numpy()
+            rew_h = [np.asarray(reward_function(dict(observations=obs_h[k], actions=act_h[k]))['rewards']) for k in range(K)]
+            rew_h = np.stack(rew_h)
+            rew_d = torch.from_numpy(np.ascontiguousarray(rew_h, np.float32 if rew_h.dtype == np.float32 else np.float64)).to(dev)
+        err_d = None
+        if truncate_lim is not None and K > 1:
+            err_d = rollout_disagreement_device(models, obs_d, act_d, packed=pk, info=info)
+            routes["disagreement"] = info["route"]
+        pb = pack_rollouts_device(obs_d, act_d, rew_d, err_d, 0.0 if truncate_lim is None else truncate_lim, MIN_TRUNCATED_LEN,
+                                  truncate_reward)
+        # one read-back: the offsets, then the packed rows
+        off = pb["off"].cpu().numpy()
+        rows = int(off[-1])
+        term = pb["term"].cpu().numpy()
+        blocks = dict(observations=pb["obs"][:rows], actions=pb["act"][:rows], rewards=pb["rew"][:rows])
+        obs_p, act_p = blocks["observations"].cpu().numpy(), blocks["actions"].cpu().numpy()
+        rew_p = blocks["rewards"].cpu().numpy()
+        if rew_d.dtype == torch.float32:
+            rew_p = rew_p.astype(np.float32)                   # (exact: every packed value is an fp32 number)
+        for a in (obs_p, act_p, rew_p):
+            a.setflags(write=False)                            # the device blocks stay registered for these arrays (utils/ingest.py)
+        paths = [dict(observations=obs_p[off[i]:off[i + 1]], actions=act_p[off[i]:off[i + 1]], rewards=rew_p[off[i]:off[i + 1]],
+                      terminated=bool(term[i])) for i in range(K * N)]
+        h = ingest.DeviceHandle(torch, dev, load())
+        shared = dict(offsets_dev=pb["off"], terminated_dev=pb["term"])
+        ingest.register_device_batch(
+            h, paths, dict(observations=dict(f32=blocks["observations"], raw=blocks["observations"]),
+                           actions=dict(f32=blocks["actions"], raw=blocks["actions"]),
+                           rewards=dict(f32=None, raw=blocks["rewards"])),
+            derived=dict(observations=dict(obs64=pb["obs64"][:rows], tpos=pb["tpos"][:rows]), rewards=shared))
+        self._step_info.update(routes=routes, paths=K * N, rows=rows, truncated=int(term.sum()))
+        return paths
 
     def get_action(self, observation):
         if self.refine is False:

@@ -17,7 +17,9 @@ global torch stream are the reference's) and transforms.  What runs where:
   loss through the output affine); :func:`fit_world_models`: the driver's interleaved loop (dynamics, reward, next member) as
   two such calls; :func:`ensemble_path_rewards`: every member's ``compute_path_rewards`` in one upload, two launches and one
   read-back; :func:`ensemble_path_rewards_device`: the same on device tensors in one ``mjx_path_rewards`` call, which is what
-  ``MPCPolicy(reward='learned')`` plans on.
+  ``MPCPolicy(reward='learned')`` plans on;
+* :func:`rollout_disagreement_device`: the ensemble-disagreement error of rollouts that are on the device
+  (``mjx_rollout_disagreement``), which ``ModelAccelNPG.train_step(resident=True)`` truncates on.
 
 What every one of these shares stands once: :func:`pack_members` (K nets of one shape as the device blocks ``P`` and ``tr``, under
 every forward, rollout, fit and under ``pack_dynamics_members`` / ``pack_reward_members``), :func:`_dynamics_transforms` /
@@ -657,6 +659,38 @@ def ensemble_path_rewards_device(models, obs_d, act_d, want64=False, packed=None
     r64 = torch.empty((K, N, H), dtype=torch.float64, device=dev) if want64 else None
     path_rewards_call(pk, obs_d, act_d, shared, N * H, K, r32, r64, dev)
     return (r32, r64) if want64 else r32
+
+
+def members_share_kind(models, with_rewards=False):
+    """do the members share shape, activation and flags (what one launch over all of them needs; with ``with_rewards`` their reward
+    nets too)?  What :func:`pack_members` asserts, as a question."""
+    nets = [[mdl.dynamics_net for mdl in models]] + ([[mdl.reward_net for mdl in models]] if with_rewards else [])
+    return all(len({(tuple(net.layer_sizes), _act_code(net), _flags(net)) for net in group}) == 1 for group in nets)
+
+
+def rollout_disagreement_device(models, obs_d, act_d, packed=None, info=None):
+    """the ensemble-disagreement error (model_accel_npg.py:137-147) of rollouts that are on the device: obs_d (..., H, n) and act_d
+    (..., H, m) fp32 device tensors, the stored rollouts of any number of paths (``train_step``: (K, N, H, .), all members' back to
+    back) -> err (P, H - 1) fp32 on the device, err[p, t] = max over members of mean_c (obs[p, t + 1] - f_k(obs[p, t], act[p, t]))^2.
+    One ``mjx_rollout_disagreement`` call (csrc/rollout_batch.h).  ``packed``: the blocks of :func:`pack_dynamics_members` (a
+    :func:`cached_members_pack` holder's); ``info`` (a dict) receives ``route``."""
+    models = list(models)
+    dev = obs_d.device
+    assert obs_d.is_cuda and act_d.device == dev and obs_d.dtype == act_d.dtype == torch.float32, "fp32 device tensors"
+    pk = packed if packed is not None else pack_dynamics_members(models, dev)
+    sizes = tuple(pk["sizes"])
+    n, m, H = obs_d.shape[-1], act_d.shape[-1], obs_d.shape[-2]
+    assert (n + m, n) == (sizes[0], sizes[-1]) and pk["P"].shape[0] == len(models), "the models' dims are not the data's"
+    assert obs_d.shape[:-1] == act_d.shape[:-1]
+    obs_d, act_d = obs_d.contiguous(), act_d.contiguous()
+    P = obs_d.numel() // (H * n) if H else 0
+    err = torch.empty((P, max(H - 1, 0)), dtype=torch.float32, device=dev)
+    route = ctypes.c_int(-1)
+    check(load().mjx_rollout_disagreement(ptr(obs_d), ptr(act_d), P, H, len(models), _ints(sizes), len(sizes), ptr(pk["P"]), ptr(pk["tr"]),
+                                          pk["act"], pk["flags"], ptr(err), ctypes.byref(route), _stream(dev)))
+    if info is not None:
+        info["route"] = route.value
+    return err
 
 
 class DynamicsNet(nn.Module):

@@ -133,6 +133,29 @@ def rollout_models_device(models, policy, s0, horizon, noise=None, s_min=None, s
     return obs, act_out
 
 
+def pack_rollouts_device(obs_d, act_d, rew_d, err_d=None, lim=0.0, min_len=4, truncate_reward=0.0, obs64=True, tpos=True):
+    """model_accel_npg.py:149-155 for every path at once, on the device (``mjx_rollout_pack``, csrc/rollout_batch.h): obs_d (..., H, n),
+    act_d (..., H, m) fp32, rew_d (..., H) fp32 or fp64, err_d (P, H - 1) fp32 (``rollout_disagreement_device``) or None (nothing is
+    truncated) -> dict(off (P + 1) int64, first (P) int32, term (P) uint8, obs (P H, n) fp32, act (P H, m) fp32, rew (P H) fp64,
+    obs64 (P H, n) fp64 or None, tpos (P H) int32 or None), all on the device; rows [0, off[P]) hold the packed batch."""
+    dev = obs_d.device
+    n, m, H = obs_d.shape[-1], act_d.shape[-1], obs_d.shape[-2]
+    assert obs_d.is_cuda and obs_d.dtype == act_d.dtype == torch.float32 and rew_d.dtype in (torch.float32, torch.float64)
+    assert obs_d.shape[:-1] == act_d.shape[:-1] == rew_d.shape and H >= 1
+    obs_d, act_d, rew_d = obs_d.contiguous(), act_d.contiguous(), rew_d.contiguous()
+    P = rew_d.numel() // H
+    assert err_d is None or (err_d.dtype == torch.float32 and err_d.is_contiguous() and err_d.numel() == P * (H - 1))
+    new = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)        # noqa: E731
+    out = dict(off=new((P + 1,), torch.int64), first=new((P,), torch.int32), term=new((P,), torch.uint8), obs=new((P * H, n), torch.float32),
+               act=new((P * H, m), torch.float32), rew=new((P * H,), torch.float64),
+               obs64=new((P * H, n), torch.float64) if obs64 else None, tpos=new((P * H,), torch.int32) if tpos else None)
+    r32 = rew_d.dtype == torch.float32
+    check(load().mjx_rollout_pack(ptr(obs_d), ptr(act_d), ptr(rew_d) if r32 else None, None if r32 else ptr(rew_d), ptr(err_d), P, H, n, m,
+                                  float(lim), int(min_len), float(truncate_reward), ptr(out["off"]), ptr(out["first"]), ptr(out["term"]),
+                                  ptr(out["obs"]), ptr(out["act"]), ptr(out["rew"]), ptr(out["obs64"]), ptr(out["tpos"]), _stream(dev)))
+    return out
+
+
 # ===========================================================
 # Rollout parameteric policy on learned env to collect data
 # ===========================================================

@@ -70,7 +70,13 @@ class DeviceBlock:
         self.handle = ingest.DeviceHandle(self.torch, self.dev, self.lib)
         self.paths, self.shared = paths, False
         first = paths[0]["observations"] if inp != 'env_features' else None
-        if shared and first is not None and first.ndim == 2 and first.dtype == np.float64:
+        made = self._made_on_device(paths) if shared and first is not None and first.ndim == 2 else None
+        if made is not None:
+            # a batch made on the device (ingest.register_device_batch) with its fp64 observations and time index beside it
+            self.shared = True
+            self.obs, self.tpos = made
+            self.N, self.n = int(self.obs.shape[0]), int(self.obs.shape[1])
+        elif shared and first is not None and first.ndim == 2 and first.dtype == np.float64:
             # the fp64 observation block of this batch: uploaded once per process (page-locked staging), shared with
             # the policy update and the other baseline call of the iteration (utils/ingest.stage_shared); the time index
             # is built once per batch as well
@@ -86,6 +92,12 @@ class DeviceBlock:
 
     def st(self):
         return stream(self.torch, self.dev)
+
+    def _made_on_device(self, paths):
+        """(fp64 observation block, time index) where the registry holds both for these paths, else None"""
+        obs = ingest.derived_lookup(self.handle, paths, "observations", "obs64")
+        tpos = ingest.derived_lookup(self.handle, paths, "observations", "tpos") if obs is not None else None
+        return None if obs is None or tpos is None else (obs, tpos)
 
     def _time_index_dev(self, paths):
         """the time index formed on the device from the trajectory offsets (8 bytes per trajectory cross the bus instead of

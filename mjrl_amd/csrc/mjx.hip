@@ -31,6 +31,7 @@
 #include "path_reward.h"
 #include "plan.h"
 #include "policy_rollout.h"
+#include "rollout_batch.h"
 #include "vecops.h"
 
 namespace {
@@ -61,7 +62,7 @@ int lds_limit(const void* kern, size_t bytes) {
   if (e) return fail(e, "dynamic LDS limit of %zu bytes: %s", bytes, hipGetErrorString((hipError_t)e));
   return MJX_OK;
 }
-enum ScratchSite { SITE_GRAM, SITE_MLP_PREDICT, SITE_MLP_FIT, SITE_MLP_FIT_WIDE, SITE_MLP_FIT_LAUNCHES, SITE_DYN_FIT, SITE_SUM_STATS, SITE_PLAN_ROLLOUT, SITE_PLAN_SCORE, SITE_DYN_FIT_ENS, SITE_PATH_REWARDS, SITE_POLICY_ROLLOUT };
+enum ScratchSite { SITE_GRAM, SITE_MLP_PREDICT, SITE_MLP_FIT, SITE_MLP_FIT_WIDE, SITE_MLP_FIT_LAUNCHES, SITE_DYN_FIT, SITE_SUM_STATS, SITE_PLAN_ROLLOUT, SITE_PLAN_SCORE, SITE_DYN_FIT_ENS, SITE_PATH_REWARDS, SITE_POLICY_ROLLOUT, SITE_ROLLOUT_DISAGREE };
 template <class T>
 int dev_scratch(ScratchSite site, void* stream, size_t bytes, T** out) {
   HIPCHK(mjx::scratch(site, (hipStream_t)stream, bytes, (void**)out));
@@ -709,6 +710,77 @@ int mjx_policy_rollout(const float* s0, int64_t s0_stride, int64_t N, int H, int
   a.pol_P = pol_params; a.pol_tr = pol_tr; a.noise = noise; a.a_lo = a_min; a.a_hi = a_max; a.s_lo = s_min; a.s_hi = s_max;
   if (int rc = launch_model_rollout(a, s0, N, H, K, nullptr, dyn_params, dyn_tr, act, flags, obs_out, act_out, st)) return rc;
   if (route_out) *route_out = 0;
+  return MJX_OK;
+}
+
+// ---------------------------------------------------------------------------- device-resident model rollouts (csrc/rollout_batch.h)
+int mjx_rollout_disagreement_route(const int* dyn_sizes, int dyn_n_sizes) {
+  DynNet dyn;
+  if (int rc = roll_dis_net(dyn_sizes, dyn_n_sizes, dyn)) return rc;
+  ChainShape ps;
+  return plan_shape(dyn, dyn.din() - dyn.dout(), ps) ? 1 : 0;
+}
+
+int mjx_rollout_disagreement(const float* obs, const float* act, int64_t P, int H, int K, const int* dyn_sizes, int dyn_n_sizes,
+                             const float* dyn_params, const float* dyn_tr, int dyn_act, int dyn_flags, float* err_out, int* route_out,
+                             void* stream) {
+  DynNet dyn;
+  if (int rc = roll_dis_net(dyn_sizes, dyn_n_sizes, dyn)) return rc;
+  const int n = dyn.dout(), m = dyn.din() - n;
+  if (!obs || !act || !dyn_params || !dyn_tr || !err_out || P < 0 || H < 0 || (dyn_flags & ~(DYN_OUT_AFFINE | DYN_MASK | DYN_RESIDUAL)) ||
+      !dyn_args_ok(dyn, K, dyn_act, DYN_TGT_PLAIN, dyn_flags & DYN_RESIDUAL))
+    return fail(MJX_ERR_ARG, "bad arguments");
+  ChainShape ps;
+  const bool served = env_flag("MJX_ROLLOUT_DISAGREE_MFMA", true) && plan_shape(dyn, m, ps);     // (read per call: A/B runs in one process)
+  if (P == 0 || H <= 1) { if (route_out) *route_out = served ? 1 : 0; return MJX_OK; }
+  MJX_DEVICE_ENTRY();
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t rows = P * H, R = P * (H - 1);
+  const int din = n + m;
+  // one block serves both routes: member means (K x R) on route 1, [s, a] rows and predictions (R x din, K x R x n) on route 0
+  float* scr = nullptr;
+  if (int rc = dev_scratch(SITE_ROLLOUT_DISAGREE, stream, (size_t)R * (din + (size_t)K * n) * sizeof(float), &scr)) return rc;
+  if (served) {
+    const RollDisArgs a{obs, act, dyn_params, dyn_tr, scr, rows, dyn.P, H, n, m, dyn.sz[1], dyn.sz[2], dyn_act, dyn_flags};
+    // as mjx_path_rewards: a wave owns tiles of 32 rows, one workgroup per CU holds the image, the K members share the CUs
+    const int64_t groups = (rows + 127) / 128, cap = (cu_count() + K - 1) / K;
+    bool launched;
+    if (int rc = launch_chained(roll_dis_kernel(ps.HB, ps.NB), ps.bytes, dim3((unsigned)(groups < cap ? groups : cap), (unsigned)K), a, st, launched)) return rc;
+    if (launched) {
+      hipLaunchKernelGGL(k_rd_max, dim3(capped_grid(R, 256, 4096)), dim3(256), 0, st, scr, K, R, err_out);
+      HIPCHK(hipGetLastError());
+      if (route_out) *route_out = 1;
+      return MJX_OK;
+    }
+  }
+  // generic route: mjx_dyn_forward's kernel over the gathered [s, a] rows (shared by the members), then mjx_dyn_pred_error's arithmetic
+  float* X = scr; float* pred = X + R * din;
+  const size_t bytes = sizeof(float) * 3 * DYN_FT * (size_t)dyn.maxw;
+  if (int rc = lds_limit((const void*)k_dyn_forward, bytes)) return rc;
+  hipLaunchKernelGGL(k_rd_gather, dim3(capped_grid(R * din, 256, 4096)), dim3(256), 0, st, obs, act, R, H, n, m, X);
+  DynFwdArgs fa{dyn, X, 0, R, dyn_params, dyn_tr, dyn_act, dyn_flags, pred};
+  hipLaunchKernelGGL(k_dyn_forward, dim3((unsigned)((R + DYN_FT - 1) / DYN_FT), (unsigned)K), dim3(256), bytes, st, fa);
+  hipLaunchKernelGGL(k_rd_reduce, dim3(capped_grid(R, 256, 4096)), dim3(256), 0, st, pred, obs, K, R, H, n, err_out);
+  HIPCHK(hipGetLastError());
+  if (route_out) *route_out = 0;
+  return MJX_OK;
+}
+
+int mjx_rollout_pack(const float* obs, const float* act, const float* rew32, const double* rew64, const float* err, int64_t P, int H, int n,
+                     int m, double lim, int min_len, double truncate_reward, int64_t* off_out, int32_t* first_out, uint8_t* term_out,
+                     float* obs_out, float* act_out, double* rew_out, double* obs64_out, int32_t* tpos_out, void* stream) {
+  if (!obs || !act || (!rew32) == (!rew64) || P < 0 || H < 1 || n <= 0 || m <= 0 || min_len < 1 || lim != lim || !off_out || !first_out ||
+      !term_out || !obs_out || !act_out || !rew_out)
+    return fail(MJX_ERR_ARG, "bad arguments");
+  MJX_DEVICE_ENTRY();
+  hipStream_t st = (hipStream_t)stream;
+  if (P > 0) hipLaunchKernelGGL(k_rp_first, dim3(capped_grid(P, 256, 4096)), dim3(256), 0, st, err, P, H, lim, min_len, off_out, first_out, term_out);
+  hipLaunchKernelGGL(k_rp_scan, dim3(1), dim3(1024), 0, st, P, off_out);
+  if (P > 0) {
+    const RollPackArgs a{obs, act, rew32, rew64, off_out, first_out, obs_out, act_out, rew_out, obs64_out, tpos_out, P, H, n, m, truncate_reward};
+    hipLaunchKernelGGL(k_rp_rows, dim3(capped_grid(P * H * (n + m + 1), 256, 8192)), dim3(256), 0, st, a);
+  }
+  HIPCHK(hipGetLastError());
   return MJX_OK;
 }
 

@@ -1,4 +1,4 @@
-// model_host.h -- host side of the learned-model kernels (dynamics.h, dyn_fit_ens.h, plan.h, path_reward.h, policy_rollout.h): their shared
+// model_host.h -- host side of the learned-model kernels (dynamics.h, dyn_fit_ens.h, plan.h, path_reward.h, policy_rollout.h, rollout_batch.h): their shared
 // argument checks, their routes as plain arithmetic, and the launches more than one entry makes.  Included by mjx.hip after fail / HIPCHK /
 // lds_limit / capped_grid.
 #pragma once
@@ -136,6 +136,21 @@ inline int path_rew_nets(const int* dyn_sizes, int dyn_n_sizes, const int* rew_s
   if (int rc = dyn_net(rew_sizes, rew_n_sizes, rew)) return rc;
   const int n = dyn.dout(), m = dyn.din() - n;
   if (m <= 0 || rew.dout() != 1 || rew.din() != 2 * n + m) return fail(MJX_ERR_ARG, "sizes must be [n + m, h..., n] and [2 n + m, g..., 1] with m > 0");
+  return MJX_OK;
+}
+
+// ---- disagreement of stored rollouts.  The k_rollout_disagree instance is the one plan_shape names: the kernel holds the dynamics
+// image alone.  MJX_ROLLOUT_DISAGREE_MFMA=0 (read per call by mjx_rollout_disagreement): the generic route.
+typedef void (*RollDisKernel)(RollDisArgs);
+inline RollDisKernel roll_dis_kernel(int HB, int NB) {
+  static const RollDisKernel tab[4][2] = {{k_rollout_disagree<1, 1>, k_rollout_disagree<1, 2>}, {k_rollout_disagree<2, 1>, k_rollout_disagree<2, 2>},
+                                          {k_rollout_disagree<3, 1>, k_rollout_disagree<3, 2>}, {k_rollout_disagree<4, 1>, k_rollout_disagree<4, 2>}};
+  return tab[HB - 1][NB - 1];
+}
+// the net of one call, parsed: [n + m, h..., n] with m > 0
+inline int roll_dis_net(const int* dyn_sizes, int dyn_n_sizes, DynNet& dyn) {
+  if (int rc = dyn_net(dyn_sizes, dyn_n_sizes, dyn)) return rc;
+  if (dyn.din() <= dyn.dout()) return fail(MJX_ERR_ARG, "dyn_sizes must be [n + m, h..., n] with m > 0");
   return MJX_OK;
 }
 

@@ -917,6 +917,25 @@ def publish(backend, paths, key, raw, arrays):
                         f32=None, raw=raw, paths=paths, arrays=list(arrays), probes=_probes(arrays))
 
 
+def register_device_batch(backend, paths, blocks, derived=None):
+    """Register blocks that were MADE on the device (model rollouts packed there: algos/model_accel) as the staged batch of `paths`:
+    ``blocks[key] = dict(f32=..., raw=...)`` for per-timestep keys (observations, actions, rewards) whose host copies are already
+    paths[i][key].  ``f32`` is the fp32 image the policy update binds, ``raw`` the block consumers of the raw dtype read (None where
+    there is none).  stage_shared, lookup and derived then find them by the identity rules of _same_batch, as if the host arrays
+    had been staged -- publish leaves ``f32`` unset, so stage_shared would upload such a batch again.  ``derived[key]``: blocks
+    cached next to that key's entry (the time index, the offsets, an fp64 copy)."""
+    dev = backend.device
+    _release_other_batches(dev, paths, tuple(blocks))
+    with _SHARED_LOCK:
+        reg = _SHARED.setdefault((dev.type, dev.index), {})
+        for key, blk in blocks.items():
+            old = reg.get(key)
+            arrays = [p[key] for p in paths]
+            reg[key] = dict(stager=old.get("stager") if old else None, stager32=old.get("stager32") if old else None, active=None, ready=None,
+                            f32=blk.get("f32"), raw=blk.get("raw"), paths=paths, arrays=arrays, probes=_probes(arrays),
+                            derived=dict((derived or {}).get(key, {})))
+
+
 def lookup(backend, paths, key):
     """the device tensor registered for paths[.][key] (stage_shared upload or publish), or None"""
     dev = backend.device
@@ -961,6 +980,17 @@ def derived(backend, paths, anchor_key, name, build):
         with _SHARED_LOCK:
             ent.setdefault("derived", {})[name] = val
     return val
+
+
+def derived_lookup(backend, paths, anchor_key, name):
+    """what derived() or register_device_batch cached under `name` next to block `anchor_key` of this batch, or None (nothing is built)"""
+    dev = backend.device
+    with _key_lock(dev, anchor_key):
+        with _SHARED_LOCK:
+            ent = _SHARED.get((dev.type, dev.index), {}).get(anchor_key)
+        if ent is None or ent.get("paths") is None or name not in ent.get("derived", {}) or not _same_batch(ent, paths, anchor_key):
+            return None                                # (asked for the name first: a batch without it costs no comparison)
+        return ent["derived"][name]
 
 
 def drop_shared_batch():

@@ -46,6 +46,10 @@ def _stream(h):
 def _rewards_block(h, paths):
     """the concatenated fp64 reward block on the device: one upload per batch (shared registry)"""
     first = paths[0]["rewards"]
+    if isinstance(first, np.ndarray) and first.ndim == 1:
+        r = ingest.lookup(h, paths, "rewards")           # a batch made on the device (ingest.register_device_batch): no host pass
+        if r is not None and r.dtype == h.torch.float64:
+            return r.view(-1)
     if isinstance(first, np.ndarray) and first.dtype == np.float64 and first.ndim == 1:
         return ingest.stage_shared(h, paths, ("rewards",))["rewards"]["raw"].view(-1)
     r = np.concatenate([np.asarray(p["rewards"], np.float64).ravel() for p in paths])

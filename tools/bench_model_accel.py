@@ -3,7 +3,12 @@
 launch route), one policy_rollout over K = 4 models, N = 250, H = 50, and one ModelAccelNPG.train_step (3 models, 250 paths,
 horizon 25) -- on the MI355X (default) or, with --reference, the unmodified reference on the CPU for the same seeded inputs
 (build box only: it imports the reference through tests/golden/_ref_import.py).  Prints one JSON line.
-    python tools/bench_model_accel.py [--reference]"""
+
+On the MI355X the train_step is then timed on both of its routes in one process -- host and resident (train_step(resident=True)),
+five alternations after a warm-up of each, with a host reward_function and with learned rewards: median [min .. max] of the whole
+step and of its sampling part (the logged time_sampling: everything up to the finished paths), and the resident route's routes.
+--step-only: only that.
+    python tools/bench_model_accel.py [--reference] [--step-only]"""
 import json
 import os
 import sys
@@ -65,8 +70,9 @@ if REF:
     Env = type("Env", (GymEnv,), {"__init__": Env.__init__, "horizon": None, "spec": None, "reset": Env.reset, "set_seed": Env.set_seed})
 
 out = {"side": "reference_cpu" if REF else "mi355x"}
+STEP_ONLY = "--step-only" in sys.argv and not REF
 routes = [None] if REF else ["0", "1"]
-for hid in [(64, 64), (256, 256)]:
+for hid in [] if STEP_ONLY else [(64, 64), (256, 256)]:
     for bs in (16, 64):
         for route in routes:
             if route is not None:
@@ -88,14 +94,15 @@ env = Env(50)
 pol = MLP(env.spec, hidden_sizes=(64, 64), seed=2)
 models = [D.WorldModel(n, m, hidden_size=(256, 256), seed=10 + k) for k in range(4)]
 init = np.random.RandomState(3).randn(250, n).astype(np.float32)
-S.policy_rollout(250, env, pol, models[0], init_state=init, eval_mode=False, horizon=2)
-sync()
-t0 = time.perf_counter()
-for mdl in models:
-    S.policy_rollout(250, env, pol, mdl, init_state=init, eval_mode=False, horizon=50)
-sync()
-out["rollout_ms_K4_N250_H50_per_model_calls"] = round((time.perf_counter() - t0) * 1e3, 2)
-if not REF:
+if not STEP_ONLY:
+    S.policy_rollout(250, env, pol, models[0], init_state=init, eval_mode=False, horizon=2)
+    sync()
+    t0 = time.perf_counter()
+    for mdl in models:
+        S.policy_rollout(250, env, pol, mdl, init_state=init, eval_mode=False, horizon=50)
+    sync()
+    out["rollout_ms_K4_N250_H50_per_model_calls"] = round((time.perf_counter() - t0) * 1e3, 2)
+if not REF and not STEP_ONLY:
     noise = S.draw_rollout_noise(4, 50, 250, m)
     sync()
     t0 = time.perf_counter()
@@ -122,4 +129,36 @@ t0 = time.perf_counter()
 agent.train_step(250, env=env, init_states=init, truncate_lim=1.0)
 sync()
 out["train_step_ms_3models_250paths_H25"] = round((time.perf_counter() - t0) * 1e3, 2)
+
+
+def spread(v):
+    return [round(float(np.median(v)), 3), round(float(min(v)), 3), round(float(max(v)), 3)]
+
+
+def both_routes(agent, tag, rounds=5):
+    """host and resident steps in alternation -> median [min, max] of the step and of its sampling part, in ms"""
+    times = {False: ([], []), True: ([], [])}
+    for resident in (False, True):
+        agent.train_step(250, env=env, init_states=init, truncate_lim=1.0, resident=resident)      # warm-up
+    for _ in range(rounds):
+        for resident in (False, True):
+            sync()
+            t0 = time.perf_counter()
+            agent.train_step(250, env=env, init_states=init, truncate_lim=1.0, resident=resident)
+            sync()
+            times[resident][0].append((time.perf_counter() - t0) * 1e3)
+            times[resident][1].append(agent.logger.log["time_sampling"][-1] * 1e3)
+            info = agent.train_step_info()
+            assert info["resident"] is resident, info
+    for resident, name in ((False, "host"), (True, "resident")):
+        out["train_step_%s_%s_ms" % (tag, name)] = spread(times[resident][0])
+        out["train_step_%s_%s_sampling_ms" % (tag, name)] = spread(times[resident][1])
+    out["train_step_%s_resident_info" % tag] = {k: info[k] for k in ("routes", "paths", "rows", "truncated")}
+
+
+if not REF:
+    both_routes(agent, "reward_function")
+    learned = [D.WorldModel(n, m, hidden_size=(64, 64), seed=20 + k, learn_reward=True) for k in range(3)]
+    both_routes(ModelAccelNPG(learned_model=learned, env=env, policy=MLP(env.spec, hidden_sizes=(64, 64), seed=4),
+                              baseline=LinearBaseline(env.spec), normalized_step_size=0.05, seed=0, save_logs=True), "learned_rewards")
 print(json.dumps(out))
