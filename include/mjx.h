@@ -460,6 +460,26 @@ int mjx_policy_rollout(const float* s0, int64_t s0_stride, int64_t N, int H, int
                        const int* dyn_sizes, int dyn_n_sizes, const float* dyn_params, const float* dyn_tr, int act,
                        int flags, const float* a_min, const float* a_max, const float* s_min, const float* s_max,
                        float* obs_out, float* act_out, int* route_out, void* stream);
+/* Whether the wide MFMA policy rollout (csrc/policy_rollout_wide.h: activations as LDS tiles, weights streamed from global
+ * memory, one workgroup per tile of 32 trajectories of one member) serves a policy pol_sizes = [n, p1, p2, m] on a dynamics
+ * net dyn_sizes = [n + m, h1, h2, n]: 1 = served: both nets with exactly two hidden layers, every hidden width 1 .. 256,
+ * n <= 64, m <= 64, n + m <= 128 and the layout -- n + pad8(n + m) + max(pad32(h1) + pad32(h2) + pad32(n), pad8(n) + pad32(p1) +
+ * pad32(p2) + pad32(m)) rows of 36 floats, then p1 + p2 + h1 + h2 + 7 n + 6 m floats of biases and transforms -- within
+ * 160 KiB (it always is: at most 127 232 bytes); 0 = not served; < 0 = bad sizes (as mjx_policy_rollout_route).
+ * Arithmetic only: no device work and no runtime call.  The answer does not depend on mjx_policy_rollout_route's: the shapes
+ * the register-resident kernel takes are served as well. */
+int mjx_policy_rollout_wide_route(const int* pol_sizes, int pol_n_sizes, const int* dyn_sizes, int dyn_n_sizes);
+/* mjx_policy_rollout with the wide kernel in front of it: the same arguments in the same order.  Where
+ * mjx_policy_rollout_wide_route serves the shape it runs k_policy_rollout_wide and reports route 2 in *route_out; otherwise,
+ * under MJX_POLICY_ROLLOUT_WIDE=0, under MJX_POLICY_ROLLOUT_MFMA=0 (both read per call) and after an LDS refusal it IS
+ * mjx_policy_rollout: same routing, same bits, same *route_out (1 or 0).  N = 0 or H = 0 returns MJX_OK without a launch (and
+ * reports the route); bad arguments return MJX_ERR_ARG and touch nothing.  Route 2 uses no scratch, no atomics and no
+ * reductions across lanes: its bits are the same on every run. */
+int mjx_policy_rollout_wide(const float* s0, int64_t s0_stride, int64_t N, int H, int K, const int* pol_sizes, int pol_n_sizes,
+                            const float* pol_params, const float* pol_tr, const float* noise, int64_t noise_stride,
+                            const int* dyn_sizes, int dyn_n_sizes, const float* dyn_params, const float* dyn_tr, int act,
+                            int flags, const float* a_min, const float* a_max, const float* s_min, const float* s_max,
+                            float* obs_out, float* act_out, int* route_out, void* stream);
 /* dst[i] = (double)src[i] for i < count, on the device (what mjx_plan_score takes for actions a kernel wrote as fp32). */
 int mjx_cast_f32_f64(const float* src, int64_t count, double* dst, void* stream);
 /* fit_model (nn_dynamics.py:344-385) behind fit_dynamics (:87-116) / fit_reward (:118-147): `steps` minibatch steps of

@@ -97,6 +97,11 @@ PROTOTYPES = {
     "mjx_policy_rollout": (c_int, [c_void_p, c_int64, c_int64, c_int, c_int, ctypes.POINTER(c_int), c_int, c_void_p, c_void_p, c_void_p,
                                    c_int64, ctypes.POINTER(c_int), c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                    c_void_p, c_void_p, c_void_p, ctypes.POINTER(c_int), c_void_p]),
+    "mjx_policy_rollout_wide_route": (c_int, [ctypes.POINTER(c_int), c_int, ctypes.POINTER(c_int), c_int]),
+    # (mjx_policy_rollout's argument list; route 2 = the wide MFMA kernel, MJX_POLICY_ROLLOUT_WIDE=0: mjx_policy_rollout itself)
+    "mjx_policy_rollout_wide": (c_int, [c_void_p, c_int64, c_int64, c_int, c_int, ctypes.POINTER(c_int), c_int, c_void_p, c_void_p, c_void_p,
+                                        c_int64, ctypes.POINTER(c_int), c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                        c_void_p, c_void_p, c_void_p, ctypes.POINTER(c_int), c_void_p]),
     "mjx_cast_f32_f64": (c_int, [c_void_p, c_int64, c_void_p, c_void_p]),
     "mjx_dyn_fit_adam": (c_int, [c_void_p, c_void_p, c_int64, ctypes.POINTER(c_int), c_int, c_void_p, c_void_p, c_int, c_int, c_void_p,
                                  c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_float, c_float, c_void_p, c_void_p]),

@@ -19,7 +19,8 @@ from ...utils import ingest, process_samples
 from ..npg_cg import NPG
 from .nn_dynamics import (WorldModel, _device, _ints, _stream, cached_members_pack, ensemble_forward, ensemble_path_rewards,
                           members_share_kind, path_rewards_call, rollout_disagreement_device)
-from .sampling import _as_env, draw_rollout_noise, pack_rollouts_device, rollout_bounds, rollout_models, rollout_models_device
+from .sampling import (_as_env, draw_rollout_noise, pack_rollouts_device, rollout_bounds, rollout_models, rollout_models_device,
+                       wide_rollout_shape)
 
 REFINE_LARGE_VALUE = float(1e2)     # the refined call's state / action bounds: policy_rollout's default large_value
 TRAIN_LARGE_VALUE = float(1e2)      # train_step's: rollout_models' default (the same number today; each caller names its own)
@@ -216,7 +217,8 @@ class ModelAccelNPG(NPG):
     # ---- the device-resident route
     def train_step_info(self):
         """what the last ``train_step`` did: dict(resident, why (the reason the host route ran, else None), routes (dict(rollout,
-        rewards, disagreement): 1 = the MFMA kernel, 0 = the generic route, None = no device call), paths, rows, truncated);
+        rewards, disagreement): 1 = the MFMA kernel, 0 = the generic route, None = no device call; rollout may also be 2 = the
+        wide MFMA policy rollout for nets up to 256 wide, csrc/policy_rollout_wide.h), paths, rows, truncated);
         None before any call.  The last three are filled by the resident route alone."""
         return None if self._step_info is None else dict(self._step_info)
 
@@ -319,14 +321,19 @@ class ModelAccelNPG(NPG):
         self._refine_pack = None
 
     def refine_route(self):
-        """the route of the last refined call's rollout (1: the register-resident MFMA policy rollout, 0: the generic one);
-        before any call, what ``mjx_policy_rollout_route`` answers for the policy and the members"""
+        """the route of the last refined call's rollout (2: the wide MFMA policy rollout for nets up to 256 wide, 1: the
+        register-resident MFMA policy rollout, 0: the generic one); before any call, what the route functions answer for the
+        policy and the members: ``mjx_policy_rollout_wide_route`` (served: 2) for the shapes ``sampling.wide_rollout_shape``
+        sends to the wide entry, ``mjx_policy_rollout_route`` for the others and for a wide shape that is not served"""
         if self._refine_last is not None:
             return self._refine_last[2]
         net = self.learned_model[0].dynamics_net
         ds = tuple(net.layer_sizes)
         ps = (net.state_dim,) + tuple(self.policy.hidden_sizes) + (net.act_dim,)
-        return int(load().mjx_policy_rollout_route(_ints(ps), len(ps), _ints(ds), len(ds)))
+        lib = load()
+        if wide_rollout_shape(ps, ds) and int(lib.mjx_policy_rollout_wide_route(_ints(ps), len(ps), _ints(ds), len(ds))) == 1:
+            return 2
+        return int(lib.mjx_policy_rollout_route(_ints(ps), len(ps), _ints(ds), len(ds)))
 
     def last_scores(self):
         """(R, S) of the last refined call: the K N trajectory scores and their softmax weights (fp64, read back on demand)"""
@@ -344,7 +351,8 @@ class ModelAccelNPG(NPG):
         1. noise = ``draw_rollout_noise(1, H, N, m)`` from torch's global stream, SHARED by all members: every member starts
            from the same state with the same noise, so the first action of trajectory i is the same on every member and the
            members differ only in where their dynamics take it (as ``MPCPolicy``'s members share action sequences);
-        2. ``mjx_policy_rollout`` (one launch; bounds +-1e2 as ``policy_rollout`` defaults);
+        2. ``mjx_policy_rollout`` (one launch; bounds +-1e2 as ``policy_rollout`` defaults; ``mjx_policy_rollout_wide`` for
+           nets wider than its MFMA route takes, ``sampling.wide_rollout_shape``: :meth:`refine_route` is then 2);
         3. rewards: every member's reward net on the device (``mjx_path_rewards``, nothing read back) when all members learn
            rewards, else one read-back and ``self.reward_function(dict(observations, actions))`` per member as ``train_step``
            calls it and one upload; with neither, ``ValueError``;

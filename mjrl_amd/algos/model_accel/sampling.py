@@ -84,17 +84,28 @@ def rollout_bounds(n, m, dev, s_min=None, s_max=None, a_min=None, a_max=None, la
             _bound(s_min, n, -large_value).to(dev), _bound(s_max, n, large_value).to(dev)]
 
 
+def wide_rollout_shape(pol_sizes, dyn_sizes):
+    """whether :func:`rollout_models_device` hands a (policy, dynamics) pair to ``mjx_policy_rollout_wide``: both nets with two
+    hidden layers and a dynamics width above 128 or a policy width above 64 -- wider than anything the register-resident route
+    of ``mjx_policy_rollout`` takes.  Plain Python, no library call; narrower on purpose than what the wide kernel serves
+    (``mjx_policy_rollout_wide_route``): the shapes that have a route today keep their call."""
+    if len(pol_sizes) != 4 or len(dyn_sizes) != 4:
+        return False
+    return max(dyn_sizes[1:3]) > 128 or max(pol_sizes[1:3]) > 64
+
+
 def rollout_models_device(models, policy, s0, horizon, noise=None, s_min=None, s_max=None, a_min=None, a_max=None,
                           large_value=float(1e2), num_traj=None, packed=None, info=None):
-    """The policy on K learned models in one ``mjx_policy_rollout`` launch, results left on the device
+    """The policy on K learned models in one ``mjx_policy_rollout`` launch (``mjx_policy_rollout_wide`` with the same arguments
+    where :func:`wide_rollout_shape` says so), results left on the device
     -> (obs (K, N, H, n), act (K, N, H, m)) fp32 device tensors.
 
     s0: one state (n,) for every trajectory, or (N, n).  noise: (H, N, m) shared by all members, (K, H, N, m), or None
     (eval mode).  N comes from s0, else from the noise, else from ``num_traj``.  ``packed``: the members already on the device
     (``nn_dynamics.pack_dynamics_members``; with ``bnd`` / ``bnd_value`` also the default bound vectors, ``rollout_bounds``);
     otherwise they are flattened and uploaded here.  The policy's parameters and transforms are uploaded on every call.
-    ``info`` (a dict) receives ``route``: 1 = the register-resident MFMA rollout (csrc/policy_rollout.h), 0 = the generic
-    persistent rollout."""
+    ``info`` (a dict) receives ``route``: 2 = the wide MFMA rollout (csrc/policy_rollout_wide.h: nets up to 256 wide),
+    1 = the register-resident MFMA rollout (csrc/policy_rollout.h), 0 = the generic persistent rollout."""
     dev = _device()
     net0 = models[0].dynamics_net
     n, m = net0.state_dim, net0.act_dim
@@ -124,10 +135,12 @@ def rollout_models_device(models, policy, s0, horizon, noise=None, s_min=None, s
     obs = torch.empty((K, N, H, n), dtype=torch.float32, device=dev)
     act_out = torch.empty((K, N, H, m), dtype=torch.float32, device=dev)
     route = ctypes.c_int(-1)
-    check(load().mjx_policy_rollout(ptr(s0_d), n if s0_d.dim() == 2 else 0, N, H, K, _ints(pol_sizes), len(pol_sizes), ptr(pol_P),
-                                    ptr(pol_tr), ptr(nz), H * N * m if (nz is not None and nz.dim() == 4) else 0, _ints(sizes),
-                                    len(sizes), ptr(packed["P"]), ptr(packed["tr"]), packed["act"], packed["flags"], ptr(bnd[0]),
-                                    ptr(bnd[1]), ptr(bnd[2]), ptr(bnd[3]), ptr(obs), ptr(act_out), ctypes.byref(route), _stream(dev)))
+    lib = load()
+    entry = lib.mjx_policy_rollout_wide if wide_rollout_shape(pol_sizes, sizes) else lib.mjx_policy_rollout
+    check(entry(ptr(s0_d), n if s0_d.dim() == 2 else 0, N, H, K, _ints(pol_sizes), len(pol_sizes), ptr(pol_P),
+                ptr(pol_tr), ptr(nz), H * N * m if (nz is not None and nz.dim() == 4) else 0, _ints(sizes),
+                len(sizes), ptr(packed["P"]), ptr(packed["tr"]), packed["act"], packed["flags"], ptr(bnd[0]),
+                ptr(bnd[1]), ptr(bnd[2]), ptr(bnd[3]), ptr(obs), ptr(act_out), ctypes.byref(route), _stream(dev)))
     if info is not None:
         info["route"] = route.value
     return obs, act_out

@@ -31,6 +31,7 @@
 #include "path_reward.h"
 #include "plan.h"
 #include "policy_rollout.h"
+#include "policy_rollout_wide.h"
 #include "rollout_batch.h"
 #include "vecops.h"
 
@@ -677,9 +678,8 @@ int mjx_policy_rollout(const float* s0, int64_t s0_stride, int64_t N, int H, int
   RolloutArgs a{};
   if (int rc = pol_roll_nets(pol_sizes, pol_n_sizes, dyn_sizes, dyn_n_sizes, a.pol, a.dyn)) return rc;
   const int n = a.dyn.dout(), m = a.dyn.din() - n;
-  if (!s0 || !pol_params || !pol_tr || !dyn_params || !dyn_tr || !obs_out || !act_out || N < 0 || H < 0 || !dyn_args_ok(a.dyn, K, act) ||
-      (flags & ~(DYN_OUT_AFFINE | DYN_MASK | DYN_RESIDUAL)) || (s0_stride != 0 && s0_stride != n) ||
-      (noise_stride != 0 && noise_stride != (int64_t)H * N * m) || (!a_min) != (!a_max) || (!s_min) != (!s_max))
+  if (!pol_roll_args_ok(a.dyn, s0, s0_stride, N, H, K, pol_params, pol_tr, noise_stride, dyn_params, dyn_tr, act, flags, a_min, a_max, s_min,
+                        s_max, obs_out, act_out))
     return fail(MJX_ERR_ARG, "bad arguments");
   ChainShape ps;
   const bool served = env_flag("MJX_POLICY_ROLLOUT_MFMA", true) && pol_roll_shape(a.dyn, a.pol, ps);   // (read per call: A/B runs in one process)
@@ -711,6 +711,43 @@ int mjx_policy_rollout(const float* s0, int64_t s0_stride, int64_t N, int H, int
   if (int rc = launch_model_rollout(a, s0, N, H, K, nullptr, dyn_params, dyn_tr, act, flags, obs_out, act_out, st)) return rc;
   if (route_out) *route_out = 0;
   return MJX_OK;
+}
+
+// ---------------------------------------------------------------------------- the same for nets up to 256 wide (csrc/policy_rollout_wide.h)
+int mjx_policy_rollout_wide_route(const int* pol_sizes, int pol_n_sizes, const int* dyn_sizes, int dyn_n_sizes) {
+  DynNet pol, dyn;
+  if (int rc = pol_roll_nets(pol_sizes, pol_n_sizes, dyn_sizes, dyn_n_sizes, pol, dyn)) return rc;
+  size_t bytes;
+  return wide_roll_shape(dyn, pol, bytes) ? 1 : 0;
+}
+
+int mjx_policy_rollout_wide(const float* s0, int64_t s0_stride, int64_t N, int H, int K, const int* pol_sizes, int pol_n_sizes,
+                            const float* pol_params, const float* pol_tr, const float* noise, int64_t noise_stride, const int* dyn_sizes,
+                            int dyn_n_sizes, const float* dyn_params, const float* dyn_tr, int act, int flags, const float* a_min,
+                            const float* a_max, const float* s_min, const float* s_max, float* obs_out, float* act_out, int* route_out,
+                            void* stream) {
+  DynNet pol, dyn;
+  if (int rc = pol_roll_nets(pol_sizes, pol_n_sizes, dyn_sizes, dyn_n_sizes, pol, dyn)) return rc;
+  if (!pol_roll_args_ok(dyn, s0, s0_stride, N, H, K, pol_params, pol_tr, noise_stride, dyn_params, dyn_tr, act, flags, a_min, a_max, s_min,
+                        s_max, obs_out, act_out))
+    return fail(MJX_ERR_ARG, "bad arguments");
+  size_t bytes = 0;
+  // (both switches read per call: A/B runs in one process; MJX_POLICY_ROLLOUT_MFMA=0 means no MFMA rollout at all)
+  const bool served = env_flag("MJX_POLICY_ROLLOUT_WIDE", true) && env_flag("MJX_POLICY_ROLLOUT_MFMA", true) && wide_roll_shape(dyn, pol, bytes);
+  if (served) {
+    if (N == 0 || H == 0) { if (route_out) *route_out = 2; return MJX_OK; }
+    MJX_DEVICE_ENTRY();
+    const int n = dyn.dout(), m = dyn.din() - n;
+    const PolRollArgs p{s0, s0_stride, noise, noise_stride ? (int64_t)H : 0, pol_params, pol_tr, dyn_params, dyn_tr, a_min, a_max, s_min, s_max,
+                        obs_out, act_out, N, dyn.P, H, n, m, dyn.sz[1], dyn.sz[2], act, flags, pol.sz[1], pol.sz[2]};
+    bool launched;
+    if (int rc = launch_chained(k_policy_rollout_wide, bytes, dim3((unsigned)((N + 31) / 32), (unsigned)K), p, (hipStream_t)stream, launched,
+                                dim3(DFE_THREADS)))
+      return rc;
+    if (launched) { if (route_out) *route_out = 2; return MJX_OK; }
+  }
+  return mjx_policy_rollout(s0, s0_stride, N, H, K, pol_sizes, pol_n_sizes, pol_params, pol_tr, noise, noise_stride, dyn_sizes, dyn_n_sizes,
+                            dyn_params, dyn_tr, act, flags, a_min, a_max, s_min, s_max, obs_out, act_out, route_out, stream);
 }
 
 // ---------------------------------------------------------------------------- device-resident model rollouts (csrc/rollout_batch.h)

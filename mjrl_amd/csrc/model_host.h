@@ -1,4 +1,4 @@
-// model_host.h -- host side of the learned-model kernels (dynamics.h, dyn_fit_ens.h, plan.h, path_reward.h, policy_rollout.h, rollout_batch.h): their shared
+// model_host.h -- host side of the learned-model kernels (dynamics.h, dyn_fit_ens.h, plan.h, path_reward.h, policy_rollout.h, policy_rollout_wide.h, rollout_batch.h): their shared
 // argument checks, their routes as plain arithmetic, and the launches more than one entry makes.  Included by mjx.hip after fail / HIPCHK /
 // lds_limit / capped_grid.
 #pragma once
@@ -41,18 +41,18 @@ inline const float* tile_s0(const float* s0, int64_t N, int n, float* dst, hipSt
 // ---- the three register-chained MFMA routes (k_plan_rollout, k_path_rewards, k_policy_rollout; csrc/mfma_chain.h).  What serves a
 // call: the instance's block counts (RB: the reward blocks, path rewards only) and the bytes of its LDS image.
 struct ChainShape { int HB = 0, NB = 0, RB = 0; size_t bytes = 0; };
-// One launch of such a kernel: 256 threads, the image as its dynamic LDS.  -> MJX_OK with `launched` set, or the launch's error.
+// One launch of such a kernel: 256 threads (k_policy_rollout_wide: DFE_THREADS), the image as its dynamic LDS.  -> MJX_OK with `launched` set, or the launch's error.
 // Not launched: the device refused the image and the caller takes its generic route.  A refusal that is not LDS_OVER came from the
 // runtime, whose error is cleared here so that the generic route's own check does not report it.
 template <class Args>
-inline int launch_chained(void (*kern)(Args), size_t lds_bytes, dim3 grid, const Args& a, hipStream_t st, bool& launched) {
+inline int launch_chained(void (*kern)(Args), size_t lds_bytes, dim3 grid, const Args& a, hipStream_t st, bool& launched, dim3 block = dim3(256)) {
   launched = false;
   const int e = dyn_lds((const void*)kern, lds_bytes);
   if (e != 0) {
     if (e != LDS_OVER) (void)hipGetLastError();
     return MJX_OK;
   }
-  hipLaunchKernelGGL(kern, grid, dim3(256), lds_bytes, st, a);
+  hipLaunchKernelGGL(kern, grid, block, lds_bytes, st, a);
   HIPCHK(hipGetLastError());
   launched = true;
   return MJX_OK;
@@ -98,6 +98,18 @@ inline PolRollKernel pol_roll_kernel(int HB, int NB) {
                                           {k_policy_rollout<3, 1>, k_policy_rollout<3, 2>}, {k_policy_rollout<4, 1>, k_policy_rollout<4, 2>}};
   return tab[HB - 1][NB - 1];
 }
+// ---- wide policy rollout.  What k_policy_rollout_wide (policy_rollout_wide.h) serves: both nets with exactly two hidden layers,
+// every hidden width 1 .. 256, n <= 64, m <= 64, n + m <= 128, and its LDS layout (the kernel has no static LDS) within LDS_MAX.
+// It does not ask what pol_roll_shape answers: the shapes the chained kernel takes are served as well.  MJX_POLICY_ROLLOUT_WIDE=0
+// or MJX_POLICY_ROLLOUT_MFMA=0 (read per call by mjx_policy_rollout_wide): mjx_policy_rollout.
+inline bool wide_roll_shape(const DynNet& dyn, const DynNet& pol, size_t& bytes) {
+  if (dyn.nl != 3 || pol.nl != 3) return false;
+  const int n = dyn.dout(), m = dyn.din() - n;
+  for (int l = 1; l <= 2; ++l) if (dyn.sz[l] > PRW_MAXH || pol.sz[l] > PRW_MAXH) return false;
+  if (n > PRW_MAXN || m > PRW_MAXM || n + m > PRW_MAXIN) return false;
+  bytes = sizeof(float) * wide_roll_lds_floats(n, m, dyn.sz[1], dyn.sz[2], pol.sz[1], pol.sz[2]);
+  return bytes <= LDS_MAX;
+}
 // the two nets of one call, parsed: sizes that fit each other ([n, p..., m] and [n + m, h..., n])
 inline int pol_roll_nets(const int* pol_sizes, int pol_n_sizes, const int* dyn_sizes, int dyn_n_sizes, DynNet& pol, DynNet& dyn) {
   if (int rc = dyn_net(dyn_sizes, dyn_n_sizes, dyn)) return rc;
@@ -105,6 +117,16 @@ inline int pol_roll_nets(const int* pol_sizes, int pol_n_sizes, const int* dyn_s
   const int n = dyn.dout(), m = dyn.din() - n;
   if (m <= 0 || pol.din() != n || pol.dout() != m) return fail(MJX_ERR_ARG, "sizes must be [n, p..., m] and [n + m, h..., n] with m > 0");
   return MJX_OK;
+}
+// the remaining arguments of mjx_policy_rollout / mjx_policy_rollout_wide
+inline bool pol_roll_args_ok(const DynNet& dyn, const float* s0, int64_t s0_stride, int64_t N, int H, int K, const float* pol_params,
+                             const float* pol_tr, int64_t noise_stride, const float* dyn_params, const float* dyn_tr, int act, int flags,
+                             const float* a_min, const float* a_max, const float* s_min, const float* s_max, const float* obs_out,
+                             const float* act_out) {
+  const int n = dyn.dout(), m = dyn.din() - n;
+  return !(!s0 || !pol_params || !pol_tr || !dyn_params || !dyn_tr || !obs_out || !act_out || N < 0 || H < 0 || !dyn_args_ok(dyn, K, act) ||
+           (flags & ~(DYN_OUT_AFFINE | DYN_MASK | DYN_RESIDUAL)) || (s0_stride != 0 && s0_stride != n) ||
+           (noise_stride != 0 && noise_stride != (int64_t)H * N * m) || (!a_min) != (!a_max) || (!s_min) != (!s_max));
 }
 
 // ---- learned path rewards.  The k_path_rewards instance that serves a (dynamics, reward) pair, if one does: a dynamics net as

@@ -7,7 +7,10 @@ horizon 25) -- on the MI355X (default) or, with --reference, the unmodified refe
 On the MI355X the train_step is then timed on both of its routes in one process -- host and resident (train_step(resident=True)),
 five alternations after a warm-up of each, with a host reward_function and with learned rewards: median [min .. max] of the whole
 step and of its sampling part (the logged time_sampling: everything up to the finished paths), and the resident route's routes.
---step-only: only that.
+Before that, at the reference's own width (256 x 256 dynamics, 64 x 64 policy): rollout_models_device at K = 4, N = 250, H = 50 and
+the resident train_step (3 models, 250 paths, horizon 25) with MJX_POLICY_ROLLOUT_WIDE=1 (route 2, csrc/policy_rollout_wide.h)
+and =0 (route 0) in one process, a warm-up of each and five alternations: median [min .. max] and whether route 2 won every one.
+--step-only: only the train_step rows.
     python tools/bench_model_accel.py [--reference] [--step-only]"""
 import json
 import os
@@ -156,7 +159,66 @@ def both_routes(agent, tag, rounds=5):
     out["train_step_%s_resident_info" % tag] = {k: info[k] for k in ("routes", "paths", "rows", "truncated")}
 
 
+def wide_ab(call, rounds=5):
+    """`call` under MJX_POLICY_ROLLOUT_WIDE=1 and =0 in alternation after a warm-up of each -> {switch: (times in ms, last result)}"""
+    times, last = {"1": [], "0": []}, {}
+    try:
+        for wide in ("1", "0"):
+            os.environ["MJX_POLICY_ROLLOUT_WIDE"] = wide
+            call()
+        for _ in range(rounds):
+            for wide in ("1", "0"):
+                os.environ["MJX_POLICY_ROLLOUT_WIDE"] = wide
+                sync()
+                t0 = time.perf_counter()
+                last[wide] = call()
+                sync()
+                times[wide].append((time.perf_counter() - t0) * 1e3)
+    finally:
+        os.environ.pop("MJX_POLICY_ROLLOUT_WIDE", None)
+    return {wide: (times[wide], last[wide]) for wide in times}
+
+
+def wide_rows():
+    """the wide MFMA policy rollout (mjx_policy_rollout_wide, route 2) against route 0 at the reference's own width, 256 x 256"""
+    wenv = Env(50)
+    wpol = MLP(wenv.spec, hidden_sizes=(64, 64), seed=2)
+    wide = [D.WorldModel(n, m, hidden_size=(256, 256), seed=10 + k) for k in range(4)]
+    s0 = np.random.RandomState(3).randn(250, n).astype(np.float32)
+    if not STEP_ONLY:
+        noise = S.draw_rollout_noise(4, 50, 250, m)
+        pk = D.pack_dynamics_members(wide, D._device())
+        info = {}
+
+        def rollout():
+            S.rollout_models_device(wide, wpol, s0, 50, noise, packed=pk, info=info)
+            return info["route"]
+
+        r = wide_ab(rollout)
+        for sw in ("1", "0"):
+            out["rollout_device_ms_K4_N250_H50_256x256_wide%s" % sw] = spread(r[sw][0])
+            out["rollout_device_route_wide%s" % sw] = r[sw][1]
+        out["rollout_device_wide_faster_in_every_alternation"] = all(a < b for a, b in zip(r["1"][0], r["0"][0]))
+    tenv = Env(25)
+    wagent = ModelAccelNPG(learned_model=wide[:3], env=tenv, policy=MLP(tenv.spec, hidden_sizes=(64, 64), seed=4),
+                           baseline=LinearBaseline(tenv.spec), normalized_step_size=0.05, seed=0, save_logs=True,
+                           reward_function=reward_function)
+
+    def step():
+        wagent.train_step(250, env=tenv, init_states=init, truncate_lim=1.0, resident=True)
+        info = wagent.train_step_info()
+        assert info["resident"] is True, info
+        return [info["routes"]["rollout"], wagent.logger.log["time_sampling"][-1] * 1e3]
+
+    r = wide_ab(step)
+    for sw in ("1", "0"):
+        out["train_step_resident_256x256_ms_wide%s" % sw] = spread(r[sw][0])
+        out["train_step_resident_256x256_rollout_route_wide%s" % sw] = r[sw][1][0]
+    out["train_step_resident_256x256_wide_faster_in_every_alternation"] = all(a < b for a, b in zip(r["1"][0], r["0"][0]))
+
+
 if not REF:
+    wide_rows()
     both_routes(agent, "reward_function")
     learned = [D.WorldModel(n, m, hidden_size=(64, 64), seed=20 + k, learn_reward=True) for k in range(3)]
     both_routes(ModelAccelNPG(learned_model=learned, env=env, policy=MLP(env.spec, hidden_sizes=(64, 64), seed=4),
