@@ -3,7 +3,7 @@ prints one RESULT JSON line of measured errors and counts (the test module compa
 python tests/_dyn_ensemble_worker.py"""
 import copy
 import ctypes
-import json
+import functools
 import os
 import sys
 
@@ -17,11 +17,13 @@ from tests import _dyn_check as C  # noqa: E402
 from tests import _dyn_oracle as O  # noqa: E402
 from tests._dyn_check import rand_theta, rand_tr  # noqa: E402
 from tests._dyn_ensemble_cases import CASES, GRAD_FLOOR, K, LR, NF, ROUTE0, WD, XSCR_CASE, member_data  # noqa: E402
+from tests import _worker_dev as W  # noqa: E402
+from tests._worker_dev import KEEP, emit, ints, stream, switch  # noqa: E402
 
-dev = torch.device("cuda", 0)
+dev = W.device()
 lib = load()
 ERR, CNT, INFO = {}, {}, {}
-KEEP = []
+t32 = functools.partial(W.up, keep=True)
 
 
 def put(key, val, case):
@@ -31,20 +33,6 @@ def put(key, val, case):
 
 def count(key, n):
     CNT[key] = CNT.get(key, 0) + int(n)
-
-
-def ints(v):
-    return (ctypes.c_int * len(v))(*v)
-
-
-def t32(x):
-    t = torch.as_tensor(np.ascontiguousarray(x, np.float32)).to(dev)
-    KEEP.append(t)
-    return t
-
-
-def stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def ens_fit(th, sizes, trs, xs, ys, idxs, steps, batch, act, tmode, m=None, v=None, step0=None, env=None, shared=False):
@@ -61,13 +49,10 @@ def ens_fit(th, sizes, trs, xs, ys, idxs, steps, batch, act, tmode, m=None, v=No
     s0 = (ctypes.c_int64 * k)(*([0] * k if step0 is None else [int(t) for t in step0]))
     route = ctypes.c_int(-9)
     n = xs.shape[-2]
-    if env is not None:
-        os.environ["MJX_DYN_FIT_ENS"] = env
-    check(lib.mjx_dyn_fit_ensemble(ptr(t32(xs)), 0 if shared else n * din, ptr(t32(ys)), 0 if shared else n * dout, n, k, ints(sizes),
-                                   len(sizes), ptr(t32(trs[:, :2 * din])), ptr(t32(trs[:, 2 * din:])), tmode, act, ptr(P), ptr(mm), ptr(vv),
-                                   s0, ptr(ix), steps, batch, LR, WD, ptr(loss), ctypes.byref(route), stream()))
-    if env is not None:
-        os.environ.pop("MJX_DYN_FIT_ENS")
+    with switch("MJX_DYN_FIT_ENS", env):
+        check(lib.mjx_dyn_fit_ensemble(ptr(t32(xs)), 0 if shared else n * din, ptr(t32(ys)), 0 if shared else n * dout, n, k, ints(sizes),
+                                       len(sizes), ptr(t32(trs[:, :2 * din])), ptr(t32(trs[:, 2 * din:])), tmode, act, ptr(P), ptr(mm), ptr(vv),
+                                       s0, ptr(ix), steps, batch, LR, WD, ptr(loss), ctypes.byref(route), stream()))
     p, l = P.cpu().numpy(), loss.cpu().numpy()
     count("unwritten", C.unwritten(l) + C.unwritten(p))
     return p, l, mm.cpu().numpy(), vv.cpu().numpy(), route.value
@@ -214,4 +199,4 @@ count("wm_epochs_bad", int(any(len(l) != 2 for l in ens_losses)))
 count("wm_pack_key_unchanged", int(planner._pack_key(dev)[0] == key0))
 
 torch.cuda.synchronize()
-print("RESULT " + json.dumps({"err": ERR, "count": CNT, "info": INFO}), flush=True)
+emit({"err": ERR, "count": CNT, "info": INFO})

@@ -1,8 +1,7 @@
 """GPU worker for tests/test_gpu_dynamics_matrix.py: every learned-dynamics case of the matrix in ONE fresh process; prints one
 RESULT JSON line of measured errors and counts (the test module compares them with its bars).
 python tests/_dynamics_matrix_worker.py"""
-import ctypes
-import json
+import functools
 import os
 import sys
 
@@ -15,15 +14,17 @@ from mjrl_amd._lib import check, load, ptr  # noqa: E402
 from tests import _dyn_check as C  # noqa: E402
 from tests import _dyn_oracle as O  # noqa: E402
 from tests._dyn_check import rand_theta, rand_tr  # noqa: E402
+from tests import _worker_dev as W  # noqa: E402
+from tests._worker_dev import KEEP, ints, stream, switch  # noqa: E402
 
 FIT_STATIC_LDS = 128          # k_dyn_fit's __shared__ double red[16] (.group_segment_fixed_size of the gfx950 code object)
 LDS = 160 * 1024
 GRAD_FLOOR = 3e-7             # fit_params_over_lr counts the parameters whose first fp64 gradient reached this
 
-dev = torch.device("cuda", 0)
+dev = W.device()
 lib = load()
 ERR, CNT = {}, {}             # key -> [worst error, case];  key -> count of defects (0 when all is well)
-KEEP = []                     # every uploaded block stays alive until the process ends
+t32 = functools.partial(W.up, keep=True)     # every uploaded block stays alive until the process ends (KEEP)
 
 
 def put(key, val, case):
@@ -35,24 +36,10 @@ def count(key, n):
     CNT[key] = CNT.get(key, 0) + int(n)
 
 
-def ints(v):
-    return (ctypes.c_int * len(v))(*v)
-
-
-def t32(x):
-    t = torch.as_tensor(np.ascontiguousarray(x, np.float32)).to(dev)
-    KEEP.append(t)
-    return t
-
-
 def nan_buf(*shape):
     t = torch.full(shape, float("nan"), device=dev)
     KEEP.append(t)
     return t
-
-
-def stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 # ================================================================ 1. batched forward
@@ -227,7 +214,6 @@ def persistent(sizes, batch, launches):
 
 
 def gpu_fit(theta, sizes, tr, x, y, idx, steps, batch, act, tmode, lr, wd, launches, m=None, v=None, step0=0):
-    os.environ["MJX_DYN_FIT_LAUNCHES"] = "1" if launches else "0"
     din = sizes[0]
     P = t32(theta)
     mm = torch.zeros_like(P) if m is None else t32(m)
@@ -235,10 +221,10 @@ def gpu_fit(theta, sizes, tr, x, y, idx, steps, batch, act, tmode, lr, wd, launc
     loss = nan_buf(steps)
     ix = torch.as_tensor(np.ascontiguousarray(idx[:steps * batch], np.int32)).to(dev)
     KEEP.append(ix)
-    check(lib.mjx_dyn_fit_adam(ptr(t32(x)), ptr(t32(y)), x.shape[0], ints(sizes), len(sizes), ptr(t32(tr[:2 * din])),
-                               ptr(t32(tr[2 * din:])), tmode, act, ptr(P), ptr(mm), ptr(vv), step0, ptr(ix), steps, batch, lr, wd,
-                               ptr(loss), stream()))
-    os.environ.pop("MJX_DYN_FIT_LAUNCHES")
+    with switch("MJX_DYN_FIT_LAUNCHES", "1" if launches else "0"):
+        check(lib.mjx_dyn_fit_adam(ptr(t32(x)), ptr(t32(y)), x.shape[0], ints(sizes), len(sizes), ptr(t32(tr[:2 * din])),
+                                   ptr(t32(tr[2 * din:])), tmode, act, ptr(P), ptr(mm), ptr(vv), step0, ptr(ix), steps, batch, lr, wd,
+                                   ptr(loss), stream()))
     if persistent(sizes, batch, launches):
         ROUTES["k_dyn_fit"] += 1
     else:
@@ -385,4 +371,4 @@ sn[200, 1] = np.inf; pred[1, 200, 1] = np.inf              # inf - inf in one me
 pred[0, 399, 0] = np.nan                                    # NaN at a segment's last row
 trunc_case("inf_nan", pred, sn, np.array([0, 30, 41, 50, 100, 130, 150, 170, 190, 210, 400]), 0.05)
 
-print("RESULT " + json.dumps({"err": ERR, "count": CNT, "refused": REFUSED, "routes": ROUTES}), flush=True)
+W.emit({"err": ERR, "count": CNT, "refused": REFUSED, "routes": ROUTES})

@@ -4,7 +4,7 @@ measured errors, counts and routes (the test module compares them with its bars)
 first HIP error ends the process.
 python tests/_fit_matrix_worker.py"""
 import ctypes
-import json
+import functools
 import os
 import sys
 
@@ -18,17 +18,19 @@ from mjrl_amd.engine import UpdateEngine  # noqa: E402
 from tests import _fit_cases as K  # noqa: E402
 from tests import _fit_oracle as F  # noqa: E402
 from tests._fit_cases import CLIP, HALVES, LAUNCHES, LR, N_MLP, ONEPASS  # noqa: E402
+from tests import _worker_dev as W  # noqa: E402
+from tests._worker_dev import ints  # noqa: E402
 
 TAIL = 64                     # NaN floats behind params / theta and both moments
 SENTINEL = -7.0               # behind the last loss entry (an MSE is >= 0; a PPO loss of exactly -7 does not occur)
 SWITCHES = ("MJX_MLP_FIT_LAUNCHES", "MJX_FIT_WIDE", "MJX_FIT_REGMOM", "MJX_FIT_ONEPASS", "MJX_NO_POLICY_FIT")
 
-dev = torch.device("cuda", 0)
+dev = W.device()
 lib = load()
 ERR, ROUTES, BY_ROUTE, PPO, CASES = {}, {}, {}, {}, {}     # CASES: every figure of every case, for reading a failure
 CNT = {k: 0 for k in ("route_mismatch", "mlp_guard_bad", "mlp_cont_not_bitwise", "pol_guard_bad", "pol_cont_not_bitwise",
                       "pol_log_std_touched")}
-KEEP = []                     # every uploaded block stays alive until the process ends
+up = functools.partial(W.up, keep=True)      # every uploaded block stays alive until the process ends
 
 
 def put(key, val, case, route=None):
@@ -42,16 +44,6 @@ def put(key, val, case, route=None):
 
 def count(key, n):
     CNT[key] = CNT.get(key, 0) + int(n)
-
-
-def ints(v):
-    return (ctypes.c_int * max(len(v), 1))(*v)
-
-
-def up(a, dtype=np.float32):
-    t = torch.as_tensor(np.ascontiguousarray(a, dtype)).to(dev)
-    KEEP.append(t)
-    return t
 
 
 def guarded(a):
@@ -236,4 +228,4 @@ def pol_case(n, m, hid, B, env, expect, seed):
 for n, m, hid, B, env, expect, seed in K.POL_CASES:
     pol_case(n, m, hid, B, env, expect, seed)
 
-print("RESULT " + json.dumps({"err": ERR, "count": CNT, "routes": ROUTES, "by_route": BY_ROUTE, "ppo": PPO, "cases": CASES}), flush=True)
+W.emit({"err": ERR, "count": CNT, "routes": ROUTES, "by_route": BY_ROUTE, "ppo": PPO, "cases": CASES})

@@ -1,7 +1,6 @@
 """GPU worker for tests/test_gpu_model_accel.py: every model-based NPG check in ONE fresh process; prints one JSON line of
 measured errors (the test module compares them with its bars).  python tests/_model_accel_worker.py"""
-import ctypes
-import json
+import functools
 import os
 import sys
 import types
@@ -15,24 +14,15 @@ import torch  # noqa: E402
 import _dyn_oracle as O  # noqa: E402
 from mjrl_amd._lib import check, load, ptr  # noqa: E402
 from mjrl_amd.algos.model_accel import nn_dynamics as D  # noqa: E402
+from tests._worker_dev import device, emit, ints, stream, switch, up  # noqa: E402
 
 R = {}
-dev = torch.device("cuda", 0)
+dev = device()
 lib = load()
 G = np.load(os.path.join(ROOT, "tests", "golden", "model_accel.npz"))
 
 
-def ints(v):
-    return (ctypes.c_int * len(v))(*v)
-
-
-KEEP = []          # every uploaded block stays alive until the process ends: no temporary is freed before its kernel ran
-
-
-def t32(x):
-    t = torch.as_tensor(np.ascontiguousarray(x, np.float32)).to(dev)
-    KEEP.append(t)
-    return t
+t32 = functools.partial(up, keep=True)   # every uploaded block stays alive until the process ends: none is freed before its kernel ran
 
 
 def rel(a, b):
@@ -49,10 +39,6 @@ def rand_tr(rng, din, dout, zero_col=None):
     if zero_col is not None:
         tr[2 * din + dout + zero_col] = 0.0
     return tr.astype(np.float32)
-
-
-def stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 # ---- forward: K = 3 members, every flag combination, ReLU / tanh, a masked column
@@ -134,15 +120,14 @@ R["pred_error_first"] = [fv.cpu().numpy().tolist(), fref]
 
 # ---- fit: 1 and 10 Adam steps against fp64, both routes; the routes against each other
 def gpu_fit(theta, sizes, tr, x, y, idx, steps, batch, act, tmode, lr, wd, launches):
-    os.environ["MJX_DYN_FIT_LAUNCHES"] = "1" if launches else "0"
-    din, dout = sizes[0], sizes[-1]
-    P = t32(theta); mm = torch.zeros_like(P); vv = torch.zeros_like(P)
-    loss = torch.empty(steps, device=dev)
-    ix = torch.as_tensor(idx[:steps * batch].astype(np.int32)).to(dev)
-    check(lib.mjx_dyn_fit_adam(ptr(t32(x)), ptr(t32(y)), x.shape[0], ints(sizes), len(sizes), ptr(t32(np.concatenate([tr[:2 * din]]))),
-                               ptr(t32(tr[2 * din:])), tmode, act, ptr(P), ptr(mm), ptr(vv), 0,
-                               ptr(ix), steps, batch, lr, wd, ptr(loss), stream()))
-    os.environ.pop("MJX_DYN_FIT_LAUNCHES")
+    with switch("MJX_DYN_FIT_LAUNCHES", "1" if launches else "0"):
+        din, dout = sizes[0], sizes[-1]
+        P = t32(theta); mm = torch.zeros_like(P); vv = torch.zeros_like(P)
+        loss = torch.empty(steps, device=dev)
+        ix = torch.as_tensor(idx[:steps * batch].astype(np.int32)).to(dev)
+        check(lib.mjx_dyn_fit_adam(ptr(t32(x)), ptr(t32(y)), x.shape[0], ints(sizes), len(sizes), ptr(t32(np.concatenate([tr[:2 * din]]))),
+                                   ptr(t32(tr[2 * din:])), tmode, act, ptr(P), ptr(mm), ptr(vv), 0,
+                                   ptr(ix), steps, batch, lr, wd, ptr(loss), stream()))
     return P.cpu().numpy(), loss.cpu().numpy()
 
 
@@ -301,4 +286,4 @@ R["train_step_policy_rel_l2"] = float(np.linalg.norm(step - rstep) / np.linalg.n
 R["train_step_lens_equal"] = bool(np.array_equal(np.array(lens), G["ts_lens"]))
 R["train_step_keys"] = [sorted(agent.logger.log.keys()), sorted(G["ts_keys"].tolist())]
 R["train_step_seed"] = [int(agent.seed), int(G["ts_seed"])]
-print("RESULT " + json.dumps(R))
+emit(R)

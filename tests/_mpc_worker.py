@@ -1,7 +1,6 @@
 """GPU worker for tests/test_gpu_mpc.py: every MPC planning check in ONE fresh process; prints one JSON line of measured
 errors (the test module compares them with its bars).  python tests/_mpc_worker.py"""
-import ctypes
-import json
+import functools
 import os
 import sys
 
@@ -16,26 +15,14 @@ import _mpc_oracle as M  # noqa: E402
 from mjrl_amd._lib import check, load, ptr  # noqa: E402
 from mjrl_amd.algos.model_accel.model_learning_mpc import MPCPolicy, perturbed_action_batch  # noqa: E402
 from mjrl_amd.algos.model_accel.nn_dynamics import WorldModel  # noqa: E402
+from tests import _worker_dev as W  # noqa: E402
+from tests._worker_dev import emit, ints, stream, switch  # noqa: E402
 
 R = {}
-dev = torch.device("cuda", 0)
+dev = W.device()
 lib = load()
 G = np.load(os.path.join(ROOT, "tests", "golden", "mpc.npz"))
-KEEP = []          # every uploaded block stays alive until the process ends
-
-
-def ints(v):
-    return (ctypes.c_int * len(v))(*[int(x) for x in v])
-
-
-def up(x, dtype=np.float32):
-    t = torch.as_tensor(np.ascontiguousarray(x, dtype)).to(dev)
-    KEEP.append(t)
-    return t
-
-
-def stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+up = functools.partial(W.up, keep=True)          # every uploaded block stays alive until the process ends
 
 
 def rel(a, b):
@@ -44,13 +31,12 @@ def rel(a, b):
 
 
 def gpu_rollout(s0, actions, thetas, sizes, trs, act, flags, mfma):
-    os.environ["MJX_PLAN_MFMA"] = "1" if mfma else "0"
     K, (N, H) = len(thetas), actions.shape[:2]
     n = sizes[-1]
     obs = torch.full((K, N, H, n), float("nan"), device=dev)
-    check(lib.mjx_plan_rollout(ptr(up(s0)), 0 if np.ndim(s0) == 1 else n, N, H, K, ptr(up(actions)), ints(sizes), len(sizes),
-                               ptr(up(np.stack(thetas))), ptr(up(np.stack(trs))), act, flags, ptr(obs), stream()))
-    os.environ.pop("MJX_PLAN_MFMA")
+    with switch("MJX_PLAN_MFMA", "1" if mfma else "0"):
+        check(lib.mjx_plan_rollout(ptr(up(s0)), 0 if np.ndim(s0) == 1 else n, N, H, K, ptr(up(actions)), ints(sizes), len(sizes),
+                                   ptr(up(np.stack(thetas))), ptr(up(np.stack(trs))), act, flags, ptr(obs), stream()))
     return obs.cpu().numpy()
 
 
@@ -200,30 +186,29 @@ for ci, case in enumerate(sorted(M.CASES)):
     n, m, hid, K, N, H, kappa, omega, fc, activation, residual, gamma = M.CASES[case]
     models = case_setup(case)[0]
     for mfma in ((1, 0) if M.ROUTES[case] else (1,)):
-        os.environ["MJX_PLAN_MFMA"] = str(mfma)
-        name = case if mfma else case + "_generic"
-        for chained in (False, True):
-            pol = MPCPolicy(env=M.plan_env(n, m), plan_horizon=H, plan_paths=N, kappa=kappa, gamma=gamma, filter_coefs=list(fc),
-                            warmstart=True, fitted_model=models, omega=omega)
-            assert pol.route() == M.ROUTES[case]
-            np.random.seed(500 + ci)
-            for c in range(M.CALLS):
-                key = "%s_%d_" % (case, c)
-                if not chained:
-                    pol.act_sequence = G[key + "seq_in"].copy()
-                action = pol.get_action(G[key + "obs"])
-                streams = streams and np.random.rand() == float(G[key + "after"])
-                ref_seq = np.concatenate([G[key + "action"][None], G[key + "seq_out"][:-1]])
-                got_seq = np.concatenate([action[None], pol.act_sequence[:-1]])
-                assert np.array_equal(pol.act_sequence[-1], np.zeros(m))
-                if chained:
-                    chain_seq[name] = max(chain_seq.get(name, 0.0), M.rel_l2(got_seq, ref_seq))
-                else:
-                    pol_seq[name] = max(pol_seq.get(name, 0.0), M.rel_l2(got_seq, ref_seq))
-                    pol_act[name] = max(pol_act.get(name, 0.0), M.rel_l2(action, G[key + "action"]))
-                    Rg = pol.last_scores()[0]
-                    pol_R[name] = max(pol_R.get(name, 0.0), float(np.max(np.abs(Rg - G[key + "R"])) / np.max(np.abs(G[key + "R"]))))
-        os.environ.pop("MJX_PLAN_MFMA")
+        with switch("MJX_PLAN_MFMA", mfma):
+            name = case if mfma else case + "_generic"
+            for chained in (False, True):
+                pol = MPCPolicy(env=M.plan_env(n, m), plan_horizon=H, plan_paths=N, kappa=kappa, gamma=gamma, filter_coefs=list(fc),
+                                warmstart=True, fitted_model=models, omega=omega)
+                assert pol.route() == M.ROUTES[case]
+                np.random.seed(500 + ci)
+                for c in range(M.CALLS):
+                    key = "%s_%d_" % (case, c)
+                    if not chained:
+                        pol.act_sequence = G[key + "seq_in"].copy()
+                    action = pol.get_action(G[key + "obs"])
+                    streams = streams and np.random.rand() == float(G[key + "after"])
+                    ref_seq = np.concatenate([G[key + "action"][None], G[key + "seq_out"][:-1]])
+                    got_seq = np.concatenate([action[None], pol.act_sequence[:-1]])
+                    assert np.array_equal(pol.act_sequence[-1], np.zeros(m))
+                    if chained:
+                        chain_seq[name] = max(chain_seq.get(name, 0.0), M.rel_l2(got_seq, ref_seq))
+                    else:
+                        pol_seq[name] = max(pol_seq.get(name, 0.0), M.rel_l2(got_seq, ref_seq))
+                        pol_act[name] = max(pol_act.get(name, 0.0), M.rel_l2(action, G[key + "action"]))
+                        Rg = pol.last_scores()[0]
+                        pol_R[name] = max(pol_R.get(name, 0.0), float(np.max(np.abs(Rg - G[key + "R"])) / np.max(np.abs(G[key + "R"]))))
 R["policy_seq"], R["policy_action"], R["policy_R"], R["chained_seq"], R["streams_equal"] = pol_seq, pol_act, pol_R, chain_seq, bool(streams)
 
 # ---- (4) the packed members are re-packed when a parameter changes, and only then
@@ -280,4 +265,4 @@ for case, bare, ref_idx, kap in (("f", True, True, None), ("a", False, False, 0.
     err_bare = max(err_bare, M.rel_l2(action, r["seq"][0]))
     err_bare_R = max(err_bare_R, float(np.max(np.abs(pol.last_scores()[0] - r["R"])) / np.max(np.abs(r["R"]))))
 R["bare_action"], R["bare_R"], R["bare_min_ess"] = err_bare, err_bare_R, min_ess
-print("RESULT " + json.dumps(R))
+emit(R)

@@ -2,7 +2,6 @@
 routes in ONE fresh process; prints one JSON line of measurements (the test module compares them with its bars).
 python tests/_path_reward_matrix_worker.py"""
 import ctypes
-import json
 import os
 import sys
 import time
@@ -15,28 +14,23 @@ import torch  # noqa: E402
 
 import _path_reward_cases as C  # noqa: E402
 from mjrl_amd._lib import check, load, ptr  # noqa: E402
+from tests import _worker_dev as W  # noqa: E402
+from tests._worker_dev import emit, ints, stream, switch  # noqa: E402
 
 T0 = time.time()
-dev = torch.device("cuda", 0)
+dev = W.device()
 lib = load()
 SWITCH = "MJX_PATH_REWARDS_MFMA"
 CUS = int(torch.cuda.get_device_properties(0).multi_processor_count)
 _UP, LAST = {}, {}
-
-
-def ints(v):
-    return (ctypes.c_int * len(v))(*[int(x) for x in v])
+assert C.GUARD == W.GUARD
 
 
 def up(x):
     """one upload per host array (the arrays of a case stay alive in _path_reward_cases' cache, and the device copies here)"""
     if id(x) not in _UP:
-        _UP[id(x)] = (x, torch.as_tensor(np.ascontiguousarray(x, np.float32)).to(dev))
+        _UP[id(x)] = (x, W.up(x))
     return _UP[id(x)][1]
-
-
-def stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def members(name, mem):
@@ -52,14 +46,12 @@ def run(route, name, mem, obs, act):
     m = act.shape[-1]
     dP, dtr, rP, rtr = members(name, mem)
     ds, rs = mem["dyn_sizes"], mem["rew_sizes"]
-    r32 = torch.full((K * rows + C.GUARD,), float("nan"), device=dev)
-    r64 = torch.full((K * rows + C.GUARD,), float("nan"), dtype=torch.float64, device=dev)
+    r32, r64 = W.nan_block(K * rows), W.nan_block(K * rows, torch.float64)
     taken = ctypes.c_int(-1)
-    os.environ[SWITCH] = str(route)
-    check(lib.mjx_path_rewards(ptr(up(obs)), ptr(up(act)), 0 if act.ndim == 2 else rows * m, rows, K, ints(ds), len(ds), ptr(dP), ptr(dtr),
-                               mem["dact"], mem["dflags"], ints(rs), len(rs), ptr(rP), ptr(rtr), mem["ract"], ptr(r32), ptr(r64),
-                               ctypes.byref(taken), stream()))
-    os.environ.pop(SWITCH)
+    with switch(SWITCH, route):
+        check(lib.mjx_path_rewards(ptr(up(obs)), ptr(up(act)), 0 if act.ndim == 2 else rows * m, rows, K, ints(ds), len(ds), ptr(dP), ptr(dtr),
+                                   mem["dact"], mem["dflags"], ints(rs), len(rs), ptr(rP), ptr(rtr), mem["ract"], ptr(r32), ptr(r64),
+                                   ctypes.byref(taken), stream()))
     torch.cuda.synchronize()
     LAST[(name, route)] = r32
     return r32.cpu().numpy(), r64.cpu().numpy(), taken.value
@@ -94,4 +86,4 @@ torch.cuda.synchronize()
 R["g3_two_forwards_same_bits"] = bool(torch.equal(two.view(torch.int32), LAST[(name, 0)][:K * rows].view(torch.int32)))
 R["seconds"] = time.time() - T0
 print("g3 against two mjx_dyn_forward calls: same bits %s; %d CUs; %.1f s in all" % (R["g3_two_forwards_same_bits"], CUS, R["seconds"]), flush=True)
-print("RESULT " + json.dumps(R))
+emit(R)

@@ -1,7 +1,7 @@
 """GPU worker for tests/test_gpu_path_rewards.py: every learned-path-reward check in ONE fresh process; prints one JSON line of
 measured errors (the test module compares them with its bars).  python tests/_path_reward_worker.py"""
 import ctypes
-import json
+import functools
 import os
 import sys
 
@@ -17,33 +17,20 @@ from mjrl_amd._lib import check, load, ptr  # noqa: E402
 from mjrl_amd.algos.model_accel.model_learning_mpc import MPCPolicy, perturbed_action_batch  # noqa: E402
 from mjrl_amd.algos.model_accel.nn_dynamics import (WorldModel, ensemble_path_rewards, ensemble_path_rewards_device,  # noqa: E402
                                                     pack_reward_members)
+from tests import _worker_dev as W  # noqa: E402
+from tests._worker_dev import emit, ints, stream, switch  # noqa: E402
 
 R = {}
-dev = torch.device("cuda", 0)
+dev = W.device()
 lib = load()
 G = np.load(os.path.join(ROOT, "tests", "golden", "mpc_learned.npz"))
 G0 = np.load(os.path.join(ROOT, "tests", "golden", "mpc.npz"))
-KEEP = []          # every uploaded block stays alive until the process ends
 SWITCH = "MJX_PATH_REWARDS_MFMA"
-
-
-def ints(v):
-    return (ctypes.c_int * len(v))(*[int(x) for x in v])
-
-
-def up(x, dtype=np.float32):
-    t = torch.as_tensor(np.ascontiguousarray(x, dtype)).to(dev)
-    KEEP.append(t)
-    return t
-
-
-def stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+up = functools.partial(W.up, keep=True)          # every uploaded block stays alive until the process ends
 
 
 def gpu_rewards(obs, act, mem, mfma, want32=True, want64=True):
     """mjx_path_rewards -> (r32 (K, N, H) or None, r64 or None, route taken); act (N, H, m): shared, (K, N, H, m): per member"""
-    os.environ[SWITCH] = "1" if mfma else "0"
     K, N, H, n = obs.shape
     m = act.shape[-1]
     rows = N * H
@@ -51,11 +38,11 @@ def gpu_rewards(obs, act, mem, mfma, want32=True, want64=True):
     r64 = torch.full((K, N, H), float("nan"), dtype=torch.float64, device=dev) if want64 else None
     route = ctypes.c_int(-1)
     ds, rs = mem["dyn_sizes"], mem["rew_sizes"]
-    check(lib.mjx_path_rewards(ptr(up(obs)), ptr(up(act)), 0 if act.ndim == 3 else rows * m, rows, K, ints(ds), len(ds),
-                               ptr(up(np.stack(mem["dyn_thetas"]))), ptr(up(np.stack(mem["dyn_trs"]))), mem["dact"], mem["dflags"], ints(rs),
-                               len(rs), ptr(up(np.stack(mem["rew_thetas"]))), ptr(up(np.stack(mem["rew_trs"]))), mem["ract"],
-                               None if r32 is None else ptr(r32), None if r64 is None else ptr(r64), ctypes.byref(route), stream()))
-    os.environ.pop(SWITCH)
+    with switch(SWITCH, "1" if mfma else "0"):
+        check(lib.mjx_path_rewards(ptr(up(obs)), ptr(up(act)), 0 if act.ndim == 3 else rows * m, rows, K, ints(ds), len(ds),
+                                   ptr(up(np.stack(mem["dyn_thetas"]))), ptr(up(np.stack(mem["dyn_trs"]))), mem["dact"], mem["dflags"],
+                                   ints(rs), len(rs), ptr(up(np.stack(mem["rew_thetas"]))), ptr(up(np.stack(mem["rew_trs"]))), mem["ract"],
+                                   ptr(r32), ptr(r64), ctypes.byref(route), stream()))
     return (None if r32 is None else r32.cpu().numpy(), None if r64 is None else r64.cpu().numpy(), route.value)
 
 
@@ -124,9 +111,8 @@ mem, data = L.kernel_case("k1")
 models = world_models(mem, 6, 2)
 (N, H), (obs, shared, own) = next(iter(data.items()))
 want = ensemble_path_rewards(models, obs, own)
-os.environ[SWITCH] = "0"
-got = ensemble_path_rewards_device(models, up(obs), up(own)).cpu().numpy()
-os.environ.pop(SWITCH)
+with switch(SWITCH, "0"):
+    got = ensemble_path_rewards_device(models, up(obs), up(own)).cpu().numpy()
 bits["forced"] = bool(np.array_equal(got, want) and got.dtype == np.float32 and got.shape == (3, N, H))
 got1, got1_64 = ensemble_path_rewards_device(models, up(obs), up(own), want64=True)
 bits["mfma_differs"] = bool(not np.array_equal(got1.cpu().numpy(), want))        # (... and the default route is the other kernel)
@@ -151,34 +137,33 @@ members = L.load_members(WorldModel, torch, G)
 for ci, case in enumerate(sorted(L.PLAN_CASES)):
     N, H, kappa, omega, fc, gamma = L.PLAN_CASES[case]
     for mfma in (1, 0):
-        os.environ[SWITCH] = str(mfma)
-        name = case if mfma else case + "_generic"
-        for chained in (False, True):
-            env = L.plan_env_no_rewards(L.PN, L.PM)
-            assert not hasattr(env.env.env, "compute_path_rewards")
-            pol = MPCPolicy(env=env, plan_horizon=H, plan_paths=N, kappa=kappa, gamma=gamma, filter_coefs=list(fc), warmstart=True,
-                            fitted_model=members, omega=omega, reward='learned')
-            assert pol.route() == 1 and pol.reward_route() == 1
-            np.random.seed(900 + ci)
-            for c in range(L.CALLS):
-                key = "%s_%d_" % (case, c)
-                if not chained:
-                    pol.act_sequence = G[key + "seq_in"].copy()
-                action = pol.get_action(G[key + "obs"])
-                streams = streams and np.random.rand() == float(G[key + "after"])
-                ref_seq = np.concatenate([G[key + "action"][None], G[key + "seq_out"][:-1]])
-                got_seq = np.concatenate([action[None], pol.act_sequence[:-1]])
-                if chained:
-                    chain_seq[name] = max(chain_seq.get(name, 0.0), M.rel_l2(got_seq, ref_seq))
-                else:
-                    Rg, rg = pol.last_scores()[0], pol.last_rewards()
-                    shapes_ok = shapes_ok and rg.shape == (L.PK, N, H) and rg.dtype == np.float64
-                    e_seq, e_R = M.rel_l2(got_seq, ref_seq), float(np.max(np.abs(Rg - G[key + "R"])) / np.ptp(G[key + "R"]))
-                    e_rew = L.rel_max(rg, G[key + "rewards"])
-                    print("planner %s call %d: sequence %.3e  R/spread %.3e  rewards %.3e" % (name, c, e_seq, e_R, e_rew), flush=True)
-                    pol_seq[name], pol_R[name] = max(pol_seq.get(name, 0.0), e_seq), max(pol_R.get(name, 0.0), e_R)
-                    pol_rew[name] = max(pol_rew.get(name, 0.0), e_rew)
-        os.environ.pop(SWITCH)
+        with switch(SWITCH, mfma):
+            name = case if mfma else case + "_generic"
+            for chained in (False, True):
+                env = L.plan_env_no_rewards(L.PN, L.PM)
+                assert not hasattr(env.env.env, "compute_path_rewards")
+                pol = MPCPolicy(env=env, plan_horizon=H, plan_paths=N, kappa=kappa, gamma=gamma, filter_coefs=list(fc), warmstart=True,
+                                fitted_model=members, omega=omega, reward='learned')
+                assert pol.route() == 1 and pol.reward_route() == 1
+                np.random.seed(900 + ci)
+                for c in range(L.CALLS):
+                    key = "%s_%d_" % (case, c)
+                    if not chained:
+                        pol.act_sequence = G[key + "seq_in"].copy()
+                    action = pol.get_action(G[key + "obs"])
+                    streams = streams and np.random.rand() == float(G[key + "after"])
+                    ref_seq = np.concatenate([G[key + "action"][None], G[key + "seq_out"][:-1]])
+                    got_seq = np.concatenate([action[None], pol.act_sequence[:-1]])
+                    if chained:
+                        chain_seq[name] = max(chain_seq.get(name, 0.0), M.rel_l2(got_seq, ref_seq))
+                    else:
+                        Rg, rg = pol.last_scores()[0], pol.last_rewards()
+                        shapes_ok = shapes_ok and rg.shape == (L.PK, N, H) and rg.dtype == np.float64
+                        e_seq, e_R = M.rel_l2(got_seq, ref_seq), float(np.max(np.abs(Rg - G[key + "R"])) / np.ptp(G[key + "R"]))
+                        e_rew = L.rel_max(rg, G[key + "rewards"])
+                        print("planner %s call %d: sequence %.3e  R/spread %.3e  rewards %.3e" % (name, c, e_seq, e_R, e_rew), flush=True)
+                        pol_seq[name], pol_R[name] = max(pol_seq.get(name, 0.0), e_seq), max(pol_R.get(name, 0.0), e_R)
+                        pol_rew[name] = max(pol_rew.get(name, 0.0), e_rew)
 R["policy_seq"], R["policy_R"], R["policy_rewards"], R["chained_seq"] = pol_seq, pol_R, pol_rew, chain_seq
 R["streams_equal"], R["last_rewards_ok"] = bool(streams), bool(shapes_ok)
 
@@ -250,4 +235,4 @@ for c in range(M.CALLS):
     e_seq = max(e_seq, M.rel_l2(np.concatenate([action[None], pol.act_sequence[:-1]]), np.concatenate([G0[key + "action"][None], G0[key + "seq_out"][:-1]])))
     e_R = max(e_R, float(np.max(np.abs(pol.last_scores()[0] - G0[key + "R"])) / np.max(np.abs(G0[key + "R"]))))
 R["env_mode"] = dict(seq=e_seq, R=e_R, streams=bool(env_streams), no_rewards=pol.last_rewards() is None)
-print("RESULT " + json.dumps(R))
+emit(R)

@@ -3,8 +3,6 @@ mjx_plan_score, and their argument checks, in ONE fresh process; prints one JSON
 with its bars and bounds).  Every output block is prefilled with NaN and carries GUARD NaN elements behind it; that none stays inside
 and none behind is touched is asserted here, per call.
 python tests/_plan_matrix_worker.py"""
-import ctypes
-import json
 import os
 import sys
 import time
@@ -17,43 +15,29 @@ import torch  # noqa: E402
 
 import _plan_cases as C  # noqa: E402
 from mjrl_amd._lib import check, load, ptr  # noqa: E402
+from tests import _worker_dev as W  # noqa: E402
+from tests._worker_dev import checked_block, emit, ints, nan_block as block, stream, switch  # noqa: E402
 
 T0 = time.time()
-dev = torch.device("cuda", 0)
+dev = W.device()
 lib = load()
 SWITCH = "MJX_PLAN_MFMA"
 MJX_ERR_ARG = -1
 _UP = {}
-GUARDED = [0]
-
-
-def ints(v):
-    return (ctypes.c_int * len(v))(*[int(x) for x in v])
+assert C.GUARD == W.GUARD
 
 
 def up(x, dtype=np.float32):
     """one upload per host array (the arrays of a case stay alive in _plan_cases' caches, and the device copies here)"""
     if id(x) not in _UP:
-        _UP[id(x)] = (x, torch.as_tensor(np.ascontiguousarray(x, dtype)).to(dev))
+        _UP[id(x)] = (x, W.up(x, dtype))
     return _UP[id(x)][1]
 
 
-def stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def block(count, dtype=torch.float32):
-    return torch.full((count + C.GUARD,), float("nan"), dtype=dtype, device=dev)
-
-
 def guarded(buf, count, what):
-    """the block after a call: no NaN inside, every guard element still NaN -> the host copy"""
-    torch.cuda.synchronize()
-    b = buf.cpu().numpy()
-    GUARDED[0] += 1
-    assert not np.isnan(b[:count]).any(), "%s: %d elements never written" % (what, int(np.isnan(b[:count]).sum()))
-    assert np.isnan(b[count:]).all(), "%s: %d guard elements touched" % (what, int((~np.isnan(b[count:])).sum()))
-    return b
+    """the block after a call: no NaN inside, every guard element still NaN -> the host copy, guard included"""
+    checked_block(buf, count, what)
+    return buf.cpu().numpy()
 
 
 def members(name, mem):
@@ -68,10 +52,9 @@ def rollout(route, name, mem, s0, actions):
     K, n, ds = len(mem["thetas"]), mem["sizes"][-1], mem["sizes"]
     P, tr = members(name, mem)
     obs = block(K * N * H * n)
-    os.environ[SWITCH] = str(route)
-    check(lib.mjx_plan_rollout(ptr(up(s0)), 0 if s0.ndim == 1 else n, N, H, K, ptr(up(actions)), ints(ds), len(ds), ptr(P), ptr(tr), mem["act"],
-                               mem["flags"], ptr(obs), stream()))
-    os.environ.pop(SWITCH)
+    with switch(SWITCH, route):
+        check(lib.mjx_plan_rollout(ptr(up(s0)), 0 if s0.ndim == 1 else n, N, H, K, ptr(up(actions)), ints(ds), len(ds), ptr(P), ptr(tr),
+                                   mem["act"], mem["flags"], ptr(obs), stream()))
     return guarded(obs, K * N * H * n, "%s rows %d route %d" % (name, N, route))
 
 
@@ -124,7 +107,7 @@ R["score_args"] = {"K_zero": call(K=0), "K_65536": call(K=65536), "N_zero": call
 torch.cuda.synchronize()
 R["score_args_untouched"] = untouched(Rd, Sd, qd)
 R["err_arg"] = MJX_ERR_ARG
-R["guarded_calls"] = GUARDED[0]
+R["guarded_calls"] = W.CHECKED[0]
 R["seconds"] = time.time() - T0
-print("%d guarded blocks; %.1f s in all" % (GUARDED[0], R["seconds"]), flush=True)
-print("RESULT " + json.dumps(R))
+print("%d guarded blocks; %.1f s in all" % (W.CHECKED[0], R["seconds"]), flush=True)
+emit(R)

@@ -2,7 +2,6 @@
 Every output block starts as NaN with 64 NaN guard elements behind it; after a call no NaN may stay inside and nothing behind it
 may be touched (asserted here, per call)."""
 import ctypes
-import json
 import os
 import sys
 
@@ -11,41 +10,20 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import numpy as np  # noqa: E402
-import torch  # noqa: E402
 
 import __graft_entry__ as ge  # noqa: E402
 
 ge.build()
 from mjrl_amd import _lib  # noqa: E402
+from mjrl_amd._lib import ptr  # noqa: E402
 import _refine_oracle as F  # noqa: E402
+from tests._worker_dev import checked_block, emit, ints, nan_block as guarded, same_bits as bits, switch, up  # noqa: E402
 
 lib = _lib.load()
-dev = torch.device("cuda", 0)
-GUARD = 64
-
-
-def ints(v):
-    return (ctypes.c_int * len(v))(*[int(x) for x in v])
-
-
-def up(x):
-    return None if x is None else torch.from_numpy(np.ascontiguousarray(x, np.float32)).to(dev)
-
-
-def ptr(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
-
-
-def guarded(numel):
-    return torch.full((numel + GUARD,), float("nan"), dtype=torch.float32, device=dev)
 
 
 def unguard(buf, shape, what):
-    numel = int(np.prod(shape))
-    h = buf.cpu().numpy()
-    assert not np.isnan(h[:numel]).any(), what + ": NaN left inside the block"
-    assert np.isnan(h[numel:]).all(), what + ": the guard behind the block was touched"
-    return h[:numel].reshape(shape).copy()
+    return checked_block(buf, int(np.prod(shape)), what).reshape(shape).copy()
 
 
 def blocks(c):
@@ -62,14 +40,12 @@ def policy_rollout(c, mfma, s0=None, noise="case"):
     s0_d, nz_d = up(s0), up(nz)
     ob, ab = guarded(K * N * H * n), guarded(K * N * H * m)
     route = ctypes.c_int(-9)
-    os.environ["MJX_POLICY_ROLLOUT_MFMA"] = "1" if mfma else "0"
-    rc = lib.mjx_policy_rollout(ptr(s0_d), n if s0.ndim == 2 else 0, N, H, K, ints(c["pol_sizes"]), len(c["pol_sizes"]), ptr(d["pP"]),
-                                ptr(d["ptr"]), ptr(nz_d), H * N * m if (nz is not None and nz.ndim == 4) else 0, ints(c["dyn_sizes"]),
-                                len(c["dyn_sizes"]), ptr(d["P"]), ptr(d["tr"]), c["act"], c["flags"], ptr(d["b"][0]), ptr(d["b"][1]),
-                                ptr(d["b"][2]), ptr(d["b"][3]), ptr(ob), ptr(ab), ctypes.byref(route), None)
-    os.environ.pop("MJX_POLICY_ROLLOUT_MFMA")
+    with switch("MJX_POLICY_ROLLOUT_MFMA", "1" if mfma else "0"):
+        rc = lib.mjx_policy_rollout(ptr(s0_d), n if s0.ndim == 2 else 0, N, H, K, ints(c["pol_sizes"]), len(c["pol_sizes"]), ptr(d["pP"]),
+                                    ptr(d["ptr"]), ptr(nz_d), H * N * m if (nz is not None and nz.ndim == 4) else 0, ints(c["dyn_sizes"]),
+                                    len(c["dyn_sizes"]), ptr(d["P"]), ptr(d["tr"]), c["act"], c["flags"], ptr(d["b"][0]), ptr(d["b"][1]),
+                                    ptr(d["b"][2]), ptr(d["b"][3]), ptr(ob), ptr(ab), ctypes.byref(route), None)
     _lib.check(rc)
-    torch.cuda.synchronize()
     return unguard(ob, (K, N, H, n), "obs"), unguard(ab, (K, N, H, m), "act"), route.value
 
 
@@ -83,12 +59,7 @@ def model_rollout(c):
                                ints(c["dyn_sizes"]), len(c["dyn_sizes"]), ptr(d["P"]), ptr(d["tr"]), c["act"], c["flags"], ptr(d["b"][0]),
                                ptr(d["b"][1]), ptr(d["b"][2]), ptr(d["b"][3]), ptr(ob), ptr(ab), None)
     _lib.check(rc)
-    torch.cuda.synchronize()
     return unguard(ob, (K, N, H, n), "obs"), unguard(ab, (K, N, H, m), "act")
-
-
-def bits(a, b):
-    return bool(np.array_equal(a.view(np.uint32), b.view(np.uint32)))
 
 
 def main():
@@ -127,7 +98,7 @@ def main():
     om, am = model_rollout(c)
     res["bits"]["tiled"] = bits(o0, ot) and bits(a0, at)
     res["bits"]["tiled_model"] = bits(o0, om) and bits(a0, am)
-    print("RESULT " + json.dumps(res))
+    emit(res)
 
 
 if __name__ == "__main__":

@@ -1,6 +1,5 @@
 """GPU worker of tests/test_gpu_refine.py: every check of ModelAccelNPG.get_refined_action in one process; prints one RESULT
 line (JSON)."""
-import json
 import os
 import pickle
 import sys
@@ -24,6 +23,7 @@ from mjrl_amd.policies.gaussian_mlp import MLP  # noqa: E402
 import _mpc_learned_oracle as L  # noqa: E402
 import _mpc_oracle as M  # noqa: E402
 import _refine_oracle as F  # noqa: E402
+from tests._worker_dev import emit, switch  # noqa: E402
 
 torch.cuda.set_device(0)
 G = np.load(os.path.join(ROOT, "tests", "golden", "refine.npz"))
@@ -46,22 +46,21 @@ def main():
     # ---- against the fixture, call by call, on both routes
     for case in sorted(F.RCASES):
         for mfma in ("1", "0"):
-            os.environ["MJX_POLICY_ROLLOUT_MFMA"] = mfma
-            agent, pol = agent_for(case, members)
-            for c in range(F.RCALLS):
-                key = "%s_%d_" % (case, c)
-                torch.manual_seed(int(G[key + "seed"]))
-                out = agent.get_action(G[key + "obs"])
-                after = torch.randn(1).item()
-                assert type(out) == list and set(out[1]) == {"mean", "evaluation", "log_std"} and out[0].shape == (L.PM,)
-                R, S = agent.last_scores()
-                res["fixture"]["%s%s_%d" % (case, mfma, c)] = [M.rel_l2(out[0], G[key + "action"]),
-                                                               float(np.max(np.abs(R - G[key + "R"])) / np.max(np.abs(G[key + "R"])))]
-                res["after"]["%s%s_%d" % (case, mfma, c)] = after == float(G[key + "after"])
-                res["routes"]["%s%s_%d" % (case, mfma, c)] = agent.refine_route()
-            if case == "ra" and mfma == "1":
-                res["packs_two_calls"] = agent._refine_packs
-            os.environ.pop("MJX_POLICY_ROLLOUT_MFMA")
+            with switch("MJX_POLICY_ROLLOUT_MFMA", mfma):
+                agent, pol = agent_for(case, members)
+                for c in range(F.RCALLS):
+                    key = "%s_%d_" % (case, c)
+                    torch.manual_seed(int(G[key + "seed"]))
+                    out = agent.get_action(G[key + "obs"])
+                    after = torch.randn(1).item()
+                    assert type(out) == list and set(out[1]) == {"mean", "evaluation", "log_std"} and out[0].shape == (L.PM,)
+                    R, S = agent.last_scores()
+                    res["fixture"]["%s%s_%d" % (case, mfma, c)] = [M.rel_l2(out[0], G[key + "action"]),
+                                                                   float(np.max(np.abs(R - G[key + "R"])) / np.max(np.abs(G[key + "R"])))]
+                    res["after"]["%s%s_%d" % (case, mfma, c)] = after == float(G[key + "after"])
+                    res["routes"]["%s%s_%d" % (case, mfma, c)] = agent.refine_route()
+                if case == "ra" and mfma == "1":
+                    res["packs_two_calls"] = agent._refine_packs
     # ---- rewards from a host callable: the same rewards (the fp64 chain, member by member) give the same action
     case = "ra"
     N, H, ph, kappa, omega, gamma = F.RCASES[case]
@@ -136,7 +135,7 @@ def main():
     res["pickle"] = bool(q._refine_pack is None and q._refine_last is None and q.refine is True)
     torch.manual_seed(3)
     res["pickle_acts"] = bool(np.all(np.isfinite(q.get_action(G[key + "obs"])[0])))
-    print("RESULT " + json.dumps(res))
+    emit(res)
 
 
 if __name__ == "__main__":

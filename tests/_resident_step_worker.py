@@ -1,7 +1,7 @@
 """GPU worker for tests/test_gpu_resident_train_step.py: ModelAccelNPG.train_step on the resident route against the host route, in ONE
 fresh process; prints one JSON line of what it found (the test module holds the bars).  The end-to-end case and its truncation limit
 come from tests/_rollout_batch_cases.py (e2e_setup, e2e_oracle).  python tests/_resident_step_worker.py"""
-import json
+import contextlib
 import os
 import sys
 import types
@@ -19,6 +19,7 @@ from mjrl_amd.algos.model_accel import nn_dynamics as D  # noqa: E402
 from mjrl_amd.baselines.linear_baseline import LinearBaseline  # noqa: E402
 from mjrl_amd.policies.gaussian_mlp import MLP  # noqa: E402
 from mjrl_amd.utils import ingest  # noqa: E402
+from tests._worker_dev import emit, switch  # noqa: E402
 
 R = {}
 SWITCHES = ("MJX_POLICY_ROLLOUT_MFMA", "MJX_PATH_REWARDS_MFMA", "MJX_ROLLOUT_DISAGREE_MFMA")
@@ -61,25 +62,22 @@ def step(resident, forced0=False, learn_reward=True, change=None, truncate_lim=L
         return fit0(paths, return_errors=return_errors)
 
     agent.baseline.fit = fit
-    for s in SWITCHES:
-        os.environ.pop(s, None)
-        if forced0:
-            os.environ[s] = "0"
     call = lambda: agent.train_step(B.E2E["N"], env=env, init_states=[x for x in init], truncate_lim=truncate_lim,   # noqa: E731
                                     truncate_reward=-1.0, resident=resident)
-    if warm is not None:
-        call()
-        del got[:]
-        warm()
-    torch.manual_seed(B.E2E["noise_seed"])          # (the draws e2e_oracle fixed the limit on)
-    try:
-        stats = call()
-    except Exception as e:                         # (compared between the routes by the caller)
-        return dict(raised=type(e).__name__, info=agent.train_step_info())
-    finally:
+    with contextlib.ExitStack() as held:
         for s in SWITCHES:
-            os.environ.pop(s, None)
-        ingest.drop_shared_batch()
+            held.enter_context(switch(s, "0" if forced0 else None))
+        if warm is not None:
+            call()
+            del got[:]
+            warm()
+        torch.manual_seed(B.E2E["noise_seed"])          # (the draws e2e_oracle fixed the limit on)
+        try:
+            stats = call()
+        except Exception as e:                         # (compared between the routes by the caller)
+            return dict(raised=type(e).__name__, info=agent.train_step_info())
+        finally:
+            ingest.drop_shared_batch()
     return dict(paths=got, stats=[float(v) for v in stats], keys=sorted(agent.logger.log.keys()), theta=pol.get_param_values().astype(np.float64),
                 info=agent.train_step_info())
 
@@ -228,4 +226,4 @@ for name, why, kw, patch in (("termination_function", "termination_function", di
             setattr(A, patch, saved)
     R["e"][name] = dict(info=res["info"], why=why, same=outcome(res) == outcome(host), host=("raised" in host))
 R["f_info"] = step(None)["info"]
-print("RESULT " + json.dumps(R))
+emit(R)

@@ -4,6 +4,7 @@ compares them with its bars).
 python tests/_reward_fit_worker.py"""
 import copy
 import ctypes
+import functools
 import json
 import os
 import sys
@@ -18,11 +19,13 @@ from tests import _dyn_check as C  # noqa: E402
 from tests import _dyn_oracle as O  # noqa: E402
 from tests._reward_fit_cases import (BLOCKS, CASES, GRAD_FLOOR, K, LR, MAX_CASE, ROUTE0, WD, compare_losses, compare_params,  # noqa: E402
                                      fixture_data, member_data)
+from tests import _worker_dev as W  # noqa: E402
+from tests._worker_dev import KEEP, emit, ints, stream, switch  # noqa: E402
 
-dev = torch.device("cuda", 0)
+dev = W.device()
 lib = load()
 ERR, CNT, INFO = {}, {}, {}
-KEEP = []
+t32 = functools.partial(W.up, keep=True)
 
 
 def put(key, val, case):
@@ -32,20 +35,6 @@ def put(key, val, case):
 
 def count(key, n):
     CNT[key] = CNT.get(key, 0) + int(n)
-
-
-def ints(v):
-    return (ctypes.c_int * len(v))(*v)
-
-
-def t32(x):
-    t = torch.as_tensor(np.ascontiguousarray(x, np.float32)).to(dev)
-    KEEP.append(t)
-    return t
-
-
-def stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def ens_fit(th, sizes, trs, xs, ys, idxs, steps, batch, act, m=None, v=None, step0=None, env=None, shared_y=False):
@@ -63,13 +52,10 @@ def ens_fit(th, sizes, trs, xs, ys, idxs, steps, batch, act, m=None, v=None, ste
     s0 = (ctypes.c_int64 * k)(*([0] * k if step0 is None else [int(t) for t in step0]))
     route = ctypes.c_int(-9)
     n = xs.shape[-2]
-    if env is not None:
-        os.environ["MJX_REWARD_FIT_ENS"] = env
-    check(lib.mjx_reward_fit_ensemble(ptr(t32(xs)), n * din, ptr(t32(ys)), 0 if shared_y else n * dout, n, k, ints(sizes), len(sizes),
-                                      ptr(t32(trs[:, :2 * din])), ptr(t32(trs[:, 2 * din:])), act, ptr(P), ptr(mm), ptr(vv), s0, ptr(ix),
-                                      steps, batch, LR, WD, ptr(loss), ctypes.byref(route), stream()))
-    if env is not None:
-        os.environ.pop("MJX_REWARD_FIT_ENS")
+    with switch("MJX_REWARD_FIT_ENS", env):
+        check(lib.mjx_reward_fit_ensemble(ptr(t32(xs)), n * din, ptr(t32(ys)), 0 if shared_y else n * dout, n, k, ints(sizes), len(sizes),
+                                          ptr(t32(trs[:, :2 * din])), ptr(t32(trs[:, 2 * din:])), act, ptr(P), ptr(mm), ptr(vv), s0, ptr(ix),
+                                          steps, batch, LR, WD, ptr(loss), ctypes.byref(route), stream()))
     p, l = P.cpu().numpy(), loss.cpu().numpy()
     count("unwritten", C.unwritten(l) + C.unwritten(p))
     return p, l, mm.cpu().numpy(), vv.cpu().numpy(), route.value
@@ -307,4 +293,4 @@ count("path_rewards_not_bitwise", bad)
 count("path_rewards_members_equal", int(np.array_equal(got[0], got[1])))
 
 torch.cuda.synchronize()
-print("RESULT " + json.dumps({"err": ERR, "count": CNT, "info": INFO}), flush=True)
+emit({"err": ERR, "count": CNT, "info": INFO})

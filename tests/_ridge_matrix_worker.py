@@ -5,7 +5,6 @@ error ends the process.  The device calls run on the main thread, one after the 
 longer than all of them, are formed by a few host threads beside them and judged at the end, in case order.
 python tests/_ridge_matrix_worker.py"""
 import ctypes
-import json
 import os
 import sys
 from concurrent.futures import ThreadPoolExecutor
@@ -17,12 +16,12 @@ import torch  # noqa: E402
 
 from mjrl_amd._lib import check, load, ptr  # noqa: E402
 from tests import _ridge_cases as K  # noqa: E402
+from tests import _worker_dev as W  # noqa: E402
 
 assert np.finfo(np.longdouble).nmant >= 63, "the references need a long double wider than fp64"
 SENTINEL = -7.25              # fills an output that a refused call must leave alone
 TAIL = 64                     # NaNs behind every output
 
-dev = torch.device("cuda", 0)
 lib = load()
 ERR, ROUTES, CASES = {}, {}, {}
 CNT = {k: 0 for k in ("route_mismatch", "gram_not_symmetric", "gram_not_finite", "gram_tail_touched", "gram_refusal_bad",
@@ -49,7 +48,7 @@ def count(key, n):
 
 
 def up(a, dtype=np.float64):
-    return torch.as_tensor(np.ascontiguousarray(a, dtype)).to(dev)
+    return W.up(a, dtype)
 
 
 def out_buf(entries, dtype=np.float64, fill=np.nan):
@@ -173,4 +172,4 @@ for job in JOBS:
     for what, key, *rest in job.result():
         (put if what == "put" else count)(key, *rest)
 
-print("RESULT " + json.dumps({"err": ERR, "count": CNT, "routes": ROUTES, "cases": CASES}), flush=True)
+W.emit({"err": ERR, "count": CNT, "routes": ROUTES, "cases": CASES})

@@ -2,7 +2,7 @@
 routes and through mjx_rollout_pack, in ONE fresh process; prints one JSON line of what it measured (the test module holds the bars).
 python tests/_rollout_batch_worker.py"""
 import ctypes
-import json
+import functools
 import os
 import sys
 
@@ -14,26 +14,14 @@ import torch  # noqa: E402
 
 import _rollout_batch_cases as B  # noqa: E402
 from mjrl_amd._lib import check, load, ptr  # noqa: E402
+from tests import _worker_dev as W  # noqa: E402
+from tests._worker_dev import emit, ints, stream, switch  # noqa: E402
 
 R = dict(dis={}, pack={})
-dev = torch.device("cuda", 0)
+dev = W.device()
 lib = load()
 SWITCH = "MJX_ROLLOUT_DISAGREE_MFMA"
-KEEP = []          # every uploaded block stays alive until the process ends
-
-
-def ints(v):
-    return (ctypes.c_int * len(v))(*v)
-
-
-def up(x):
-    t = torch.from_numpy(np.ascontiguousarray(x)).to(dev)
-    KEEP.append(t)
-    return t
-
-
-def stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+up = functools.partial(W.up, dtype=None, keep=True)          # in its own dtype; every uploaded block stays alive until the process ends
 
 
 def disagreement(mem, obs, act, forced0, P=None, H=None):
@@ -43,13 +31,9 @@ def disagreement(mem, obs, act, forced0, P=None, H=None):
     K, ds = len(mem["thetas"]), mem["sizes"]
     out = up(np.full(max(P * (H - 1), 0) + B.GUARD, np.nan, np.float32))
     route = ctypes.c_int(-1)
-    if forced0:
-        os.environ[SWITCH] = "0"
-    try:
+    with switch(SWITCH, "0" if forced0 else None):
         check(lib.mjx_rollout_disagreement(ptr(up(obs)), ptr(up(act)), P, H, K, ints(ds), len(ds), ptr(up(np.stack(mem["thetas"]))),
                                            ptr(up(np.stack(mem["trs"]))), mem["act"], mem["flags"], ptr(out), ctypes.byref(route), stream()))
-    finally:
-        os.environ.pop(SWITCH, None)
     torch.cuda.synchronize()
     return out.cpu().numpy(), route.value
 
@@ -144,4 +128,4 @@ for name in B.PACK_CASES:
     res["rows"] = [rows, int(np.sum(emu["term"]))]
     R["pack"][name] = res
 
-print("RESULT " + json.dumps(R))
+emit(R)

@@ -2,7 +2,6 @@
 Every output block starts as NaN with 64 NaN guard elements behind it; after a call no NaN may stay inside and nothing behind it
 may be touched (asserted here, per call).  "Route 0" is the same entry under MJX_POLICY_ROLLOUT_WIDE=0."""
 import ctypes
-import json
 import os
 import sys
 import types
@@ -18,34 +17,21 @@ import __graft_entry__ as ge  # noqa: E402
 
 ge.build()
 from mjrl_amd import _lib  # noqa: E402
+from mjrl_amd._lib import ptr  # noqa: E402
 import _refine_oracle as F  # noqa: E402
 import _rollout_wide_cases as W  # noqa: E402
+from tests._worker_dev import checked_block, device, emit, ints, nan_block as guarded, same_bits as bits, switch, up  # noqa: E402
 
 lib = _lib.load()
-dev = torch.device("cuda", 0)
-GUARD = 64
+dev = device()
 SWITCHES = ("MJX_POLICY_ROLLOUT_WIDE", "MJX_POLICY_ROLLOUT_MFMA")
-
-
-def ints(v):
-    return (ctypes.c_int * len(v))(*[int(x) for x in v])
-
-
-def up(x):
-    return None if x is None else torch.from_numpy(np.ascontiguousarray(x, np.float32)).to(dev)
-
-
-def ptr(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
-
-
-def guarded(numel):
-    return torch.full((numel + GUARD,), float("nan"), dtype=torch.float32, device=dev)
 
 
 def unguard(buf, shape, what, nan_rows=()):
     """the block behind its guard; nan_rows: trajectories (axis 1) that may hold NaN"""
     numel = int(np.prod(shape))
+    if not nan_rows:
+        return checked_block(buf, numel, what).reshape(shape).copy()
     h = buf.cpu().numpy()
     assert np.isnan(h[numel:]).all(), what + ": the guard behind the block was touched"
     out = h[:numel].reshape(shape).copy()
@@ -69,24 +55,14 @@ def rollout(c, wide="1", mfma=None, entry="mjx_policy_rollout_wide", s0=None, na
     s0_d, nz_d = up(s0), up(nz)
     ob, ab = guarded(K * N * H * n), guarded(K * N * H * m)
     route = ctypes.c_int(-9)
-    for name, v in zip(SWITCHES, (wide, mfma)):
-        if v is not None:
-            os.environ[name] = v
-    try:
+    with switch(SWITCHES[0], wide), switch(SWITCHES[1], mfma):
         rc = getattr(lib, entry)(ptr(s0_d), n if s0.ndim == 2 else 0, N, H, K, ints(c["pol_sizes"]), len(c["pol_sizes"]), ptr(d["pP"]),
                                  ptr(d["ptr"]), ptr(nz_d), H * N * m if (nz is not None and nz.ndim == 4) else 0, ints(c["dyn_sizes"]),
                                  len(c["dyn_sizes"]), ptr(d["P"]), ptr(d["tr"]), c["act"], c["flags"], ptr(d["b"][0]), ptr(d["b"][1]),
                                  ptr(d["b"][2]), ptr(d["b"][3]), ptr(ob), ptr(ab), ctypes.byref(route), None)
-    finally:
-        for name in SWITCHES:
-            os.environ.pop(name, None)
     _lib.check(rc)
     torch.cuda.synchronize()
     return unguard(ob, (K, N, H, n), "obs", nan_rows), unguard(ab, (K, N, H, m), "act", nan_rows), route.value
-
-
-def bits(a, b):
-    return bool(np.array_equal(a.view(np.uint32), b.view(np.uint32)))
 
 
 def kernel_checks(res):
@@ -211,7 +187,7 @@ def main():
     res = {}
     kernel_checks(res)
     python_checks(res)
-    print("RESULT " + json.dumps(res))
+    emit(res)
 
 
 if __name__ == "__main__":

@@ -6,7 +6,6 @@ error ends the process.  The device calls come first, one after the other; the r
 after the last of them.
 python tests/_samplepath_worker.py"""
 import ctypes
-import json
 import os
 import sys
 import time
@@ -17,12 +16,13 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 from mjrl_amd._lib import check, load  # noqa: E402
+from mjrl_amd._lib import ptr as p  # noqa: E402
 from tests import _samplepath_cases as K  # noqa: E402
+from tests import _worker_dev as W  # noqa: E402
 
 assert np.finfo(np.longdouble).nmant >= 63, "the references need a long double wider than fp64"
 
 T0 = time.time()
-dev = torch.device("cuda", 0)
 lib = load()
 ERR, CASES = {}, {}
 CNT = {k: 0 for k in ("scan_unwritten", "scan_outside_touched", "scan_guard_touched", "scan2_bits_bad", "scan_rc_bad",
@@ -48,10 +48,8 @@ def count(key, n, case=None, first=None):
 
 def up(a):
     """host array -> device tensor; an empty array as one element, so that its pointer is not NULL"""
-    a = np.ascontiguousarray(a)
-    if a.size == 0:
-        a = np.zeros(1, a.dtype)
-    return torch.from_numpy(a).to(dev)
+    a = np.asarray(a)
+    return W.up(np.zeros(1, a.dtype) if a.size == 0 else a, None)
 
 
 def up_out(buf):
@@ -61,10 +59,6 @@ def up_out(buf):
 def down(t):
     a = t.cpu().numpy()
     return a.view(_UINT[a.itemsize])
-
-
-def p(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
 
 
 def pb(t):
@@ -292,5 +286,5 @@ for size, a, buf in CAST:
     count("cast_bad", res["bad"], "cast N %d" % size, res["first"])
     count("cast_guard_touched", res["guard_touched"], "cast N %d" % size)
 
-print("RESULT " + json.dumps({"err": ERR, "count": CNT, "cases": CASES, "first": FIRST, "policies": POLICIES,
-                              "seconds": {"device": round(T_DEVICE, 2), "all": round(time.time() - T0, 2)}}), flush=True)
+W.emit({"err": ERR, "count": CNT, "cases": CASES, "first": FIRST, "policies": POLICIES,
+        "seconds": {"device": round(T_DEVICE, 2), "all": round(time.time() - T0, 2)}})

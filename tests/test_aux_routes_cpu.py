@@ -6,6 +6,8 @@ import ctypes
 
 import pytest
 
+from tests._worker_dev import ints as _ints
+
 ERR_ARG = -1
 LAUNCHES, HALVES, ONEPASS, WIDE = 0, 1, 2, 3       # out6[0] of mjx_mlp_fit_route
 SITE_ONE_WG, SITE_WIDE, SITE_LAUNCHES = 2, 3, 4     # out6[5]: the scratch block of the route (ScratchSite, csrc/mjx.hip)
@@ -22,10 +24,6 @@ SWITCHES = ("MJX_MLP_FIT_LAUNCHES", "MJX_FIT_WIDE", "MJX_FIT_REGMOM", "MJX_FIT_O
 def _lib():
     from mjrl_amd import _lib
     return _lib.load()
-
-
-def _ints(v):
-    return (ctypes.c_int * max(len(v), 1))(*v)
 
 
 def _mlp(d_in, hidden=(128, 128), batch=64, N=192, epochs=2):

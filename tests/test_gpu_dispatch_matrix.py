@@ -44,7 +44,6 @@ log_std entry) and 0.
 import functools
 import json
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -53,6 +52,7 @@ import pytest
 from oracle import npg_oracle as O
 from tests._dispatch_matrix_worker import cg_inputs, head_inputs, probe_actions, probe_direction
 from tests._lw_check import block_errors, rel
+from tests._worker_run import arm_runner, run_child
 
 pytestmark = pytest.mark.gpu
 
@@ -148,36 +148,23 @@ def _run_worker(kind, arm, names, spec_of, out_dir):
     spec = os.path.join(out_dir, "spec.json")
     with open(spec, "w") as f:
         json.dump({"kind": kind, "cases": [spec_of(nm) for nm in names]}, f)
-    env = dict(os.environ, MJX_FORCE_LAYERWISE="1", **ARM_ENV[arm])
-    subprocess.run([sys.executable, os.path.join(HERE, "_dispatch_matrix_worker.py"), spec, out_dir], check=True, env=env,
-                   timeout=900)
+    run_child([sys.executable, os.path.join(HERE, "_dispatch_matrix_worker.py"), spec, out_dir], 900, arm,
+              env=dict(ARM_ENV[arm], MJX_FORCE_LAYERWISE="1"))
     return {nm: dict(np.load(os.path.join(out_dir, nm + ".npz"))) for nm in names}
+
+
+def _start(arm, out_dir):
+    if arm.startswith("head"):
+        names = HEAD_NAMES if arm == "head_four" else HEAD_NAMES + EDGE_NAMES
+        return _run_worker("head", arm, names, _head_spec, out_dir)
+    names = [nm for nm, a in CG_CASES if "cg_" + a == arm]
+    return _run_worker("cg", arm, names, cg_spec, out_dir)
 
 
 @pytest.fixture(scope="module")
 def runs(tmp_path_factory):
-    """arm -> {case name: device results}; each arm's worker runs once, on first use.  A worker that fails (an error, a fault,
-    a timeout) is never started again: the failure is kept, and every later request -- for that arm or any other, since the
-    GPU may be left in a bad state -- fails at once without starting a process."""
-    cache, failed = {}, []
-
-    def get(arm):
-        if failed:
-            pytest.fail("not started: the %s worker failed earlier in this module (%s)" % failed[0])
-        if arm not in cache:
-            d = str(tmp_path_factory.mktemp(arm))
-            try:
-                if arm.startswith("head"):
-                    names = HEAD_NAMES if arm == "head_four" else HEAD_NAMES + EDGE_NAMES
-                    cache[arm] = _run_worker("head", arm, names, _head_spec, d)
-                else:
-                    names = [nm for nm, a in CG_CASES if "cg_" + a == arm]
-                    cache[arm] = _run_worker("cg", arm, names, cg_spec, d)
-            except (subprocess.SubprocessError, OSError) as e:
-                failed.append((arm, e))
-                raise
-        return cache[arm]
-    return get
+    """arm -> {case name: device results}; each arm's worker runs once, on first use, and none after one failed (arm_runner)"""
+    return arm_runner(_start, lambda arm: str(tmp_path_factory.mktemp(arm)))
 
 
 # ---------------------------------------------------------------------------------------------------------------- head

@@ -27,17 +27,10 @@ more, the bar is that cap.
 The member-by-member path is run on the same members for the record (seq_params_over_lr, printed, not asserted): it measures
 2.2e-2 lr on w256_b16, because dyn_adam forms 1 - beta2 as `1.0f - 0.999f` (1.3e-5 low); the ensemble kernel uses torch's
 once-rounded 0.001f."""
-import json
-import os
-import subprocess
-import sys
-
 import pytest
 
 from tests._dyn_ensemble_cases import CASES, ROUTE0
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-_RUN = {}
+from tests._worker_run import worker_result
 
 BARS = {
     "params_over_lr": 3.1e-3,         # [1.03e-3: w256_b16, 10 steps, member 0]
@@ -54,19 +47,7 @@ pytestmark = pytest.mark.gpu
 
 
 def _result():
-    if "r" not in _RUN:
-        try:
-            p = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "_dyn_ensemble_worker.py")], capture_output=True, text=True,
-                               timeout=480, cwd=ROOT)
-            out = p.stdout + p.stderr
-            line = [l for l in p.stdout.splitlines() if l.startswith("RESULT ")]
-            _RUN["r"] = (json.loads(line[-1][7:]) if p.returncode == 0 and line else None, "exit %d\n%s" % (p.returncode, out[-4000:]))
-        except subprocess.TimeoutExpired as e:
-            _RUN["r"] = (None, "timed out: %s" % str(e.stdout)[-2000:])
-    r, log = _RUN["r"]
-    if r is None:
-        pytest.fail("ensemble-fit worker failed (not restarted):\n" + log)
-    return r
+    return worker_result("_dyn_ensemble_worker.py", 480, "ensemble-fit")
 
 
 def _under(r, *keys):

@@ -41,15 +41,9 @@ in model order): K = 4 with 1000 segments of 49 rows; K = 1, n = 1; 700-row segm
 (not a violation); inf and NaN in pred and s_next, in one member and in all.  err with equal_nan, first exactly.
 
 Bars are 3x the errors measured on the MI355X (in brackets)."""
-import json
-import os
-import subprocess
-import sys
-
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-_RUN = {}
+from tests._worker_run import worker_result
 
 BARS = {
     "fwd": 1.4e-6,                    # [4.8e-7]
@@ -70,19 +64,7 @@ pytestmark = pytest.mark.gpu
 
 
 def _result():
-    if "r" not in _RUN:
-        try:
-            p = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "_dynamics_matrix_worker.py")], capture_output=True,
-                               text=True, timeout=600, cwd=ROOT)
-            out = p.stdout + p.stderr
-            line = [l for l in p.stdout.splitlines() if l.startswith("RESULT ")]
-            _RUN["r"] = (json.loads(line[-1][7:]) if p.returncode == 0 and line else None, "exit %d\n%s" % (p.returncode, out[-4000:]))
-        except subprocess.TimeoutExpired as e:
-            _RUN["r"] = (None, "timed out: %s" % str(e.stdout)[-2000:])
-    r, log = _RUN["r"]
-    if r is None:
-        pytest.fail("dynamics matrix worker failed (not restarted):\n" + log)
-    return r
+    return worker_result("_dynamics_matrix_worker.py", 600, "dynamics matrix")
 
 
 def _under(r, *keys):

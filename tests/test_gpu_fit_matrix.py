@@ -34,15 +34,9 @@ chain started from the device's own state (t0 = 5, 12 and 17 for the baseline, 3
 
 Bars are 3x the errors measured on the MI355X against the fp64 oracle (in brackets, with the case), never one route against
 another."""
-import json
-import os
-import subprocess
-import sys
-
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-_RUN = {}
+from tests._worker_run import worker_result
 
 BARS = {
     "mlp_params_over_lr": 1.5e-3,     # [5.2e-4: d_in 768, 2 epochs, W1[:, 0:48] -- as in the dynamics matrix, a first gradient just above
@@ -69,19 +63,7 @@ pytestmark = pytest.mark.gpu
 
 
 def _result():
-    if "r" not in _RUN:
-        try:
-            p = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "_fit_matrix_worker.py")], capture_output=True, text=True,
-                               timeout=600, cwd=ROOT)
-            out = p.stdout + p.stderr
-            line = [l for l in p.stdout.splitlines() if l.startswith("RESULT ")]
-            _RUN["r"] = (json.loads(line[-1][7:]) if p.returncode == 0 and line else None, "exit %d\n%s" % (p.returncode, out[-4000:]))
-        except subprocess.TimeoutExpired as e:
-            _RUN["r"] = (None, "timed out: %s" % str(e.stdout)[-2000:])
-    r, log = _RUN["r"]
-    if r is None:
-        pytest.fail("fit matrix worker failed (not restarted):\n" + log)
-    return r
+    return worker_result("_fit_matrix_worker.py", 600, "fit matrix")
 
 
 def _under(r, *keys):

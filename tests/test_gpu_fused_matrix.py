@@ -55,7 +55,6 @@ zeroed bias entry and a misplaced log_std entry, and pass the fp32 oracle.
 import functools
 import json
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -65,6 +64,7 @@ from oracle import npg_oracle as O
 from tests._dispatch_matrix_worker import probe_actions, probe_direction
 from tests._fused_matrix_worker import PREFIX_CUT, fused_inputs
 from tests._lw_check import fine_errors, over_bars, rel
+from tests._worker_run import arm_runner, run_child
 
 pytestmark = pytest.mark.gpu
 
@@ -207,38 +207,23 @@ def bar_kind(k):
 
 
 # ---------------------------------------------------------------------------------------------------------------- runs
-def _run_worker(arm, specs, out_dir):
+SCRUB = ("MJX_FORCE_LAYERWISE", "MJX_RAW_SLAB", "MJX_FVP_BF16X3", "MJX_NO_HCACHE", "MJX_FVP_SWEEP", "MJX_K3_XIMG")
+
+
+def _run_worker(arm, out_dir):
+    specs = [spec(nm, arm) for nm in ARMS[arm][1]]
     os.makedirs(out_dir, exist_ok=True)
     path = os.path.join(out_dir, "spec.json")
     with open(path, "w") as f:
         json.dump({"cases": specs}, f)
-    env = dict(os.environ, **ARMS[arm][0])
-    for k in ("MJX_FORCE_LAYERWISE", "MJX_RAW_SLAB", "MJX_FVP_BF16X3", "MJX_NO_HCACHE", "MJX_FVP_SWEEP", "MJX_K3_XIMG"):
-        if k not in ARMS[arm][0]:
-            env.pop(k, None)
-    subprocess.run([sys.executable, os.path.join(HERE, "_fused_matrix_worker.py"), path, out_dir], check=True, env=env, timeout=600)
+    run_child([sys.executable, os.path.join(HERE, "_fused_matrix_worker.py"), path, out_dir], 600, arm, scrub=SCRUB, env=ARMS[arm][0])
     return {c["name"]: dict(np.load(os.path.join(out_dir, c["name"] + ".npz"))) for c in specs}
 
 
 @pytest.fixture(scope="module")
 def runs(tmp_path_factory):
-    """arm -> {case name: device results}; each arm's worker runs once, on first use.  A worker that fails (an error, a fault,
-    a timeout) is never started again: the failure is kept, and every later request -- for that arm or any other, since the
-    GPU may be left in a bad state -- fails at once without starting a process."""
-    cache, failed = {}, []
-
-    def get(arm):
-        if failed:
-            pytest.fail("not started: the %s worker failed earlier in this module (%s)" % failed[0])
-        if arm not in cache:
-            d = str(tmp_path_factory.mktemp(arm))
-            try:
-                cache[arm] = _run_worker(arm, [spec(nm, arm) for nm in ARMS[arm][1]], d)
-            except (subprocess.SubprocessError, OSError) as e:
-                failed.append((arm, e))
-                raise
-        return cache[arm]
-    return get
+    """arm -> {case name: device results}; each arm's worker runs once, on first use, and none after one failed (arm_runner)"""
+    return arm_runner(_run_worker, lambda arm: str(tmp_path_factory.mktemp(arm)))
 
 
 # ---------------------------------------------------------------------------------------------------------------- checks

@@ -4,7 +4,6 @@ comparison with the fp32 kernel also asserts that the bits differ, i.e. that the
 instance."""
 import json
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -12,6 +11,7 @@ import pytest
 
 from oracle import npg_oracle as O
 from oracle import synth
+from tests._worker_run import run_child
 
 pytestmark = pytest.mark.gpu
 
@@ -89,8 +89,8 @@ def in_children(tmp_path, specs):
     res = []
     for on in (1, 0):
         path = os.path.join(str(tmp_path), "out_%d.npz" % on)
-        env = dict(os.environ, MJX_FVP_BF16X3=str(on))
-        subprocess.run([sys.executable, "-c", _CHILD, ROOT, json.dumps(specs), path], check=True, env=env, cwd=ROOT, timeout=900)
+        run_child([sys.executable, "-c", _CHILD, ROOT, json.dumps(specs), path], 900, "MJX_FVP_BF16X3 = %d" % on,
+                  env={"MJX_FVP_BF16X3": str(on)}, cwd=ROOT)
         res.append(dict(np.load(path)))
     return res
 

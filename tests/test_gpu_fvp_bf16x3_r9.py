@@ -10,13 +10,13 @@ it.  At the edge sizes (no second kernel to compare with) the W2 block is held t
 contributed anything at N = 1 (31 padded rows beside one real one) would put the block off by its own size."""
 import json
 import os
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 
 from oracle import npg_oracle as O
+from tests._worker_run import run_child
 from tests.test_gpu_fvp_bf16x3 import _CHILD, HID, INSTANCES, ROOT, TOL_FVP, case, rel
 
 pytestmark = pytest.mark.gpu
@@ -55,8 +55,8 @@ def runs(tmp_path_factory):
     tmp, res = tmp_path_factory.mktemp("r9"), []
     for on in (1, 0):
         path = os.path.join(str(tmp), "out_%d.npz" % on)
-        env = dict(os.environ, MJX_FVP_BF16X3="1", MJX_FVP_BF16X3_R9=str(on))
-        subprocess.run([sys.executable, "-c", _CHILD, ROOT, json.dumps(SPECS), path], check=True, env=env, cwd=ROOT, timeout=600)
+        run_child([sys.executable, "-c", _CHILD, ROOT, json.dumps(SPECS), path], 600, "MJX_FVP_BF16X3_R9 = %d" % on,
+                  env={"MJX_FVP_BF16X3": "1", "MJX_FVP_BF16X3_R9": str(on)}, cwd=ROOT)
         res.append(dict(np.load(path)))
     return res
 

@@ -9,18 +9,19 @@ both run).  Each case runs K1 and two consecutive products into NaN-prefilled bu
 One worker process per MJX_FVP_BF16X3_R9 setting (the switch is read once per process).  The fixture holds the CU count it was
 recorded on; the grouping of the workgroup partials follows the grid, so the test skips on a device with another count."""
 import os
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 
 from tests._fvp_bf3_bits_worker import CASES, case_name, decode
+from tests._worker_run import arm_runner, run_child
 
 pytestmark = pytest.mark.gpu
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLD = os.path.join(HERE, "golden", "fvp_bf3_bits.npz")
+SCRUB = ("MJX_FORCE_LAYERWISE", "MJX_RAW_SLAB", "MJX_FVP_BF16X3", "MJX_NO_HCACHE", "MJX_FVP_SWEEP")
 
 
 @pytest.fixture(scope="module")
@@ -32,25 +33,13 @@ def gold():
 @pytest.fixture(scope="module")
 def runs(tmp_path_factory):
     """r9 -> the worker's results; each worker runs once, on first use.  A worker that fails (an error, a fault, a timeout) is
-    never started again, and neither is the other one: the GPU may be left in a bad state."""
-    cache, failed = {}, []
-
-    def get(r9):
-        if failed:
-            pytest.fail("not started: the r9 = %d worker failed earlier in this module (%s)" % failed[0])
-        if r9 not in cache:
-            path = str(tmp_path_factory.mktemp("r9_%d" % r9) / "out.npz")
-            env = dict(os.environ, MJX_FVP_BF16X3_R9=str(r9))
-            for k in ("MJX_FORCE_LAYERWISE", "MJX_RAW_SLAB", "MJX_FVP_BF16X3", "MJX_NO_HCACHE", "MJX_FVP_SWEEP"):
-                env.pop(k, None)
-            try:
-                subprocess.run([sys.executable, os.path.join(HERE, "_fvp_bf3_bits_worker.py"), path], check=True, env=env, timeout=300)
-            except (subprocess.SubprocessError, OSError) as e:
-                failed.append((r9, e))
-                raise
-            cache[r9] = dict(np.load(path))
-        return cache[r9]
-    return get
+    never started again, and neither is the other one: the GPU may be left in a bad state (arm_runner)."""
+    def start(r9, out_dir):
+        path = os.path.join(out_dir, "out.npz")
+        run_child([sys.executable, os.path.join(HERE, "_fvp_bf3_bits_worker.py"), path], 300, "r9 = %d" % r9, scrub=SCRUB,
+                  env={"MJX_FVP_BF16X3_R9": str(r9)})
+        return dict(np.load(path))
+    return arm_runner(start, lambda r9: str(tmp_path_factory.mktemp("r9_%d" % r9)), "r9 = %d")
 
 
 @pytest.mark.parametrize("n,N", CASES, ids=[case_name(n, N) for n, N in CASES])

@@ -51,7 +51,6 @@ Switch arms (test_arm_vs_oracle, same bars; MJX_LW_WT=0 and MJX_LW_FAST=0 are al
 import functools
 import json
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -61,6 +60,7 @@ from oracle import npg_oracle as O
 from oracle.torch_port import TorchPolicy
 from tests._gemm_chain_worker import chain_inputs
 from tests._lw_check import fine_errors, over_bars, rel, row_errors
+from tests._worker_run import arm_runner, run_child
 
 pytestmark = pytest.mark.gpu
 
@@ -182,33 +182,22 @@ def _run_worker(kind, arm, specs, out_dir):
     path = os.path.join(out_dir, "spec.json")
     with open(path, "w") as f:
         json.dump({"kind": kind, "cases": specs}, f)
-    env = dict(os.environ, MJX_FORCE_LAYERWISE="1", **ARMS[arm][0])
-    subprocess.run([sys.executable, os.path.join(HERE, "_gemm_chain_worker.py"), path, out_dir], check=True, env=env, timeout=600)
+    run_child([sys.executable, os.path.join(HERE, "_gemm_chain_worker.py"), path, out_dir], 600, arm,
+              env=dict(ARMS[arm][0], MJX_FORCE_LAYERWISE="1"))
     return {c["name"]: dict(np.load(os.path.join(out_dir, c["name"] + ".npz"))) for c in specs}
+
+
+def _start(arm, out_dir):
+    if arm == "stale":
+        return _run_worker("stale", "default", [stale_spec(s) for s in STALE], out_dir)
+    return _run_worker("cases", arm, [spec(nm) for nm in ARMS[arm][1]], out_dir)
 
 
 @pytest.fixture(scope="module")
 def runs(tmp_path_factory):
-    """arm -> {case name: device results}; each arm's worker runs once, on first use ("stale": the stale-row runs).  A worker
-    that fails (an error, a fault, a timeout) is never started again: the failure is kept, and every later request -- for that
-    arm or any other, since the GPU may be left in a bad state -- fails at once without starting a process."""
-    cache, failed = {}, []
-
-    def get(arm):
-        if failed:
-            pytest.fail("not started: the %s worker failed earlier in this module (%s)" % failed[0])
-        if arm not in cache:
-            d = str(tmp_path_factory.mktemp(arm))
-            try:
-                if arm == "stale":
-                    cache[arm] = _run_worker("stale", "default", [stale_spec(s) for s in STALE], d)
-                else:
-                    cache[arm] = _run_worker("cases", arm, [spec(nm) for nm in ARMS[arm][1]], d)
-            except (subprocess.SubprocessError, OSError) as e:
-                failed.append((arm, e))
-                raise
-        return cache[arm]
-    return get
+    """arm -> {case name: device results}; each arm's worker runs once, on first use ("stale": the stale-row runs), and none
+    after one failed (arm_runner)"""
+    return arm_runner(_start, lambda arm: str(tmp_path_factory.mktemp(arm)))
 
 
 def check_case(name, r):

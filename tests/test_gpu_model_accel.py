@@ -5,31 +5,13 @@ tests/golden/make_golden_model_accel.py).  Every check runs in ONE fresh worker 
 (tests/_model_accel_worker.py); a worker that failed is not started again -- the remaining tests fail with its output.
 
 Bars are 3x the errors measured on the MI355X (in brackets)."""
-import json
-import os
-import subprocess
-import sys
-
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-_RUN = {}
+from tests._worker_run import worker_result
 
 
 def _result():
-    if "r" not in _RUN:
-        try:
-            p = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "_model_accel_worker.py")], capture_output=True, text=True,
-                               timeout=600, cwd=ROOT)
-            out = p.stdout + p.stderr
-            line = [l for l in p.stdout.splitlines() if l.startswith("RESULT ")]
-            _RUN["r"] = (json.loads(line[-1][7:]) if p.returncode == 0 and line else None, "exit %d\n%s" % (p.returncode, out[-4000:]))
-        except subprocess.TimeoutExpired as e:
-            _RUN["r"] = (None, "timed out: %s" % str(e.stdout)[-2000:])
-    r, log = _RUN["r"]
-    if r is None:
-        pytest.fail("model_accel worker failed (not restarted):\n" + log)
-    return r
+    return worker_result("_model_accel_worker.py", 600, "model_accel")
 
 
 @pytest.mark.gpu

@@ -8,18 +8,17 @@ The planned sequence and the returned action must lie within 1e-5 relative L2 of
 update direction; the reference itself is at most 3.1e-6 from the fp64 restatement on these inputs, tests/test_mpc_cpu.py).
 Every other bar is 3x the error measured on the MI355X against the oracle or the fixture (in brackets); BAR_BARE_R and BAR_REFIT_R
 take BAR_R: the same quantity (measured since: in their brackets)."""
-import json
 import os
-import subprocess
 import sys
 
 import pytest
+
+from tests._worker_run import worker_result
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import _mpc_oracle as M  # noqa: E402
 
-_RUN = {}
 TOL_STEP = 1e-5
 BAR_STEP_MFMA = 7.8e-7        # [2.6e-7: case b; the edge shapes 2.4e-7]
 BAR_STEP_GENERIC = 6.9e-7     # [2.3e-7: case b]
@@ -36,19 +35,7 @@ BAR_REFIT_R = 5.9e-7          # as BAR_BARE_R; [3.5e-8]
 
 
 def _result():
-    if "r" not in _RUN:
-        try:
-            p = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "_mpc_worker.py")], capture_output=True, text=True,
-                               timeout=600, cwd=ROOT)
-            out = p.stdout + p.stderr
-            line = [l for l in p.stdout.splitlines() if l.startswith("RESULT ")]
-            _RUN["r"] = (json.loads(line[-1][7:]) if p.returncode == 0 and line else None, "exit %d\n%s" % (p.returncode, out[-4000:]))
-        except subprocess.TimeoutExpired as e:
-            _RUN["r"] = (None, "timed out: %s" % str(e.stdout)[-2000:])
-    r, log = _RUN["r"]
-    if r is None:
-        pytest.fail("mpc worker failed (not restarted):\n" + log)
-    return r
+    return worker_result("_mpc_worker.py", 600, "mpc")
 
 
 MFMA_CASES = sorted(c for c in M.CASES if M.ROUTES[c])

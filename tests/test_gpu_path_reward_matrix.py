@@ -59,37 +59,24 @@ against each other.  Measured on the MI355X [in brackets: route 1 / route 0; the
     g3   yardstick 1.019e-7  bar 3.057e-7  [9.126e-8 / 9.948e-8; 1.511e-7]
 [no unwritten element and no touched guard element in 88 calls; at 256 CUs the walks are g1 (4, 3, 2, 16), g2 (1, 3, 2, 12),
 g3 (4, 33, 32, 16): workgroups per member, most and fewest tiles of a wave that owns any, rows of the last tile.  No defect found.]"""
-import json
 import os
-import subprocess
 import sys
 
 import pytest
+
+from tests._worker_run import worker_result
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import _path_reward_cases as C  # noqa: E402
 
-_RUN = {}
 LIMIT = 120
 
 pytestmark = pytest.mark.gpu
 
 
 def _result():
-    if "r" not in _RUN:
-        try:
-            p = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "_path_reward_matrix_worker.py")], capture_output=True, text=True,
-                               timeout=LIMIT, cwd=ROOT)
-            out = p.stdout + p.stderr
-            line = [l for l in p.stdout.splitlines() if l.startswith("RESULT ")]
-            _RUN["r"] = (json.loads(line[-1][7:]) if p.returncode == 0 and line else None, "exit %d\n%s" % (p.returncode, out[-4000:]))
-        except subprocess.TimeoutExpired as e:
-            _RUN["r"] = (None, "timed out: %s" % str(e.stdout)[-2000:])
-    r, log = _RUN["r"]
-    if r is None:
-        pytest.fail("path-reward matrix worker failed (not restarted):\n" + log)
-    return r
+    return worker_result("_path_reward_matrix_worker.py", LIMIT, "path-reward matrix")
 
 
 def _checks(case):

@@ -25,20 +25,19 @@ score, while mjx_plan_score forms the product in fp64: that rounding, at most 2^
 [R / spread: la 2.9e-7 on the MFMA reward route, 3.2e-7 on the generic one; lb 4.5e-7 / 4.7e-7;
 the planned sequence at most 3.6e-7 call by call and 4.3e-7 over three chained calls; the member rewards against the reference's
 4.6e-7 .. 1.2e-6 of the largest reward: two fp32 chains on two fp32 rollouts]."""
-import json
 import os
-import subprocess
 import sys
 
 import numpy as np
 import pytest
+
+from tests._worker_run import worker_result
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import _mpc_learned_oracle as L  # noqa: E402
 
 G = np.load(os.path.join(ROOT, "tests", "golden", "mpc_learned.npz"))
-_RUN = {}
 TOL_STEP = 1e-5
 BAR_R = 5.9e-7                # tests/test_gpu_mpc.py's BAR_R
 MARGIN = 3.0
@@ -49,19 +48,7 @@ def _bar(case):
 
 
 def _result():
-    if "r" not in _RUN:
-        try:
-            p = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "_path_reward_worker.py")], capture_output=True, text=True,
-                               timeout=600, cwd=ROOT)
-            out = p.stdout + p.stderr
-            line = [l for l in p.stdout.splitlines() if l.startswith("RESULT ")]
-            _RUN["r"] = (json.loads(line[-1][7:]) if p.returncode == 0 and line else None, "exit %d\n%s" % (p.returncode, out[-4000:]))
-        except subprocess.TimeoutExpired as e:
-            _RUN["r"] = (None, "timed out: %s" % str(e.stdout)[-2000:])
-    r, log = _RUN["r"]
-    if r is None:
-        pytest.fail("path-reward worker failed (not restarted):\n" + log)
-    return r
+    return worker_result("_path_reward_worker.py", 600, "path-reward")
 
 
 PLAN_NAMES = set(L.PLAN_CASES) | {c + "_generic" for c in L.PLAN_CASES}

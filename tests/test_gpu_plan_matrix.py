@@ -112,37 +112,24 @@ case (tests/test_plan_checks.py).  Measured on the MI355X, the largest share of 
 [no unwritten element and no touched guard element in 306 guarded blocks: 108 rollout calls and 66 scoring calls with three blocks
 each; every argument check returned MJX_ERR_ARG and wrote nothing; every case is served by route 1 and the routes' bits differ on every
 run of 32 rows or more.  No defect found.]"""
-import json
 import os
-import subprocess
 import sys
 
 import pytest
+
+from tests._worker_run import worker_result
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import _plan_cases as C  # noqa: E402
 
-_RUN = {}
 LIMIT = 120
 
 pytestmark = pytest.mark.gpu
 
 
 def _result():
-    if "r" not in _RUN:
-        try:
-            p = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "_plan_matrix_worker.py")], capture_output=True, text=True,
-                               timeout=LIMIT, cwd=ROOT)
-            out = p.stdout + p.stderr
-            line = [l for l in p.stdout.splitlines() if l.startswith("RESULT ")]
-            _RUN["r"] = (json.loads(line[-1][7:]) if p.returncode == 0 and line else None, "exit %d\n%s" % (p.returncode, out[-4000:]))
-        except subprocess.TimeoutExpired as e:
-            _RUN["r"] = (None, "timed out: %s" % str(e.stdout)[-2000:])
-    r, log = _RUN["r"]
-    if r is None:
-        pytest.fail("plan matrix worker failed (not restarted):\n" + log)
-    return r
+    return worker_result("_plan_matrix_worker.py", LIMIT, "plan matrix")
 
 
 def _checks(case):

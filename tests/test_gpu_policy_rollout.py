@@ -9,36 +9,23 @@ worker measures the kernels (tests/golden/refine.npz: kya_ / kys_ per case, kfre
 under test produced.  An H = 1 case stores s0 only, so its state yardstick is 0 and the stored state must be exact.  Measured on
 the MI355X (route 1 / route 0, largest over the cases, as a share of the bar): action steps 0.42 / 0.43, state steps 0.49 / 0.40,
 routes against each other 0.49, free-running 0.33 / 0.31."""
-import json
 import os
-import subprocess
 import sys
 
 import numpy as np
 import pytest
+
+from tests._worker_run import worker_result
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import _refine_oracle as F  # noqa: E402
 
 G = np.load(os.path.join(ROOT, "tests", "golden", "refine.npz"))
-_RUN = {}
 
 
 def _result():
-    if "r" not in _RUN:
-        try:
-            p = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "_policy_rollout_worker.py")], capture_output=True, text=True,
-                               timeout=300, cwd=ROOT)
-            out = p.stdout + p.stderr
-            line = [l for l in p.stdout.splitlines() if l.startswith("RESULT ")]
-            _RUN["r"] = (json.loads(line[-1][7:]) if p.returncode == 0 and line else None, "exit %d\n%s" % (p.returncode, out[-4000:]))
-        except subprocess.TimeoutExpired as e:
-            _RUN["r"] = (None, "timed out: %s" % str(e.stdout)[-2000:])
-    r, log = _RUN["r"]
-    if r is None:
-        pytest.fail("policy rollout worker failed (not restarted):\n" + log)
-    return r
+    return worker_result("_policy_rollout_worker.py", 300, "policy rollout")
 
 
 def _bars(name):

@@ -6,36 +6,23 @@ the members' pack key, and the neighbours that must not change.  Every check run
 The action must lie within 1e-5 relative L2 of the reference's (the project's TOL_STEP; the reference itself is at most 1.3e-6
 from the fp64 restatement on these inputs, tests/test_refine_cpu.py) and R within tests/test_gpu_mpc.py's BAR_R.  Measured on the
 MI355X: action at most 9.3e-7 (case ra, route 1), R at most 2.8e-7 (case ra, route 0); the host-callable action 3.4e-8 from fp64."""
-import json
 import os
-import subprocess
 import sys
 
 import pytest
+
+from tests._worker_run import worker_result
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import _refine_oracle as F  # noqa: E402
 
-_RUN = {}
 TOL_STEP = 1e-5
 BAR_R = 5.9e-7                # tests/test_gpu_mpc.py's bar on the same quantity
 
 
 def _result():
-    if "r" not in _RUN:
-        try:
-            p = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "_refine_worker.py")], capture_output=True, text=True,
-                               timeout=300, cwd=ROOT)
-            out = p.stdout + p.stderr
-            line = [l for l in p.stdout.splitlines() if l.startswith("RESULT ")]
-            _RUN["r"] = (json.loads(line[-1][7:]) if p.returncode == 0 and line else None, "exit %d\n%s" % (p.returncode, out[-4000:]))
-        except subprocess.TimeoutExpired as e:
-            _RUN["r"] = (None, "timed out: %s" % str(e.stdout)[-2000:])
-    r, log = _RUN["r"]
-    if r is None:
-        pytest.fail("refine worker failed (not restarted):\n" + log)
-    return r
+    return worker_result("_refine_worker.py", 300, "refine")
 
 
 KEYS = ["%s%s_%d" % (case, route, c) for case in sorted(F.RCASES) for route in "10" for c in range(F.RCALLS)]

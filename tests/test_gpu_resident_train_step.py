@@ -2,31 +2,15 @@
 process under a time limit; a worker that failed is not started again).  The case: (n, m) = (6, 2), K = 3, dynamics 64 x 64, reward
 nets 100 x 100, policy 32 x 32, N = 40, H = 8, LinearBaseline, the truncation limit fixed on the CPU from the fp64 oracle
 (tests/_rollout_batch_cases.py: e2e_oracle, fix_lim)."""
-import json
-import os
-import subprocess
-import sys
-
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-_RUN = {}
+from tests._worker_run import worker_result
+
 DECLINES = ("termination_function", "members_differ", "mixed_rewards", "short_horizon", "distributed", "no_gpu")
 
 
 def _result():
-    if "r" not in _RUN:
-        try:
-            p = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "_resident_step_worker.py")], capture_output=True, text=True,
-                               timeout=300, cwd=ROOT)
-            line = [l for l in p.stdout.splitlines() if l.startswith("RESULT ")]
-            _RUN["r"] = (json.loads(line[-1][7:]) if p.returncode == 0 and line else None, "exit %d\n%s" % (p.returncode, (p.stdout + p.stderr)[-4000:]))
-        except subprocess.TimeoutExpired as e:
-            _RUN["r"] = (None, "timed out: %s" % str(e.stdout)[-2000:])
-    r, log = _RUN["r"]
-    if r is None:
-        pytest.fail("resident step worker failed (not restarted):\n" + log)
-    return r
+    return worker_result("_resident_step_worker.py", 300, "resident step")
 
 
 @pytest.mark.gpu

@@ -31,17 +31,10 @@ the dynamics kernel to for the same quantity (6.6e-3 lr, 6.4e-6, 3e-4); where 3x
 cap.  rw_max_b64's 5.05e-3 lr is one entry of W2 (member 1) whose first fp64 gradient is 6.7e-7, just above the floor; an fp32
 NumPy chain of that member (tests/test_reward_fit_checks.chain) is 6.9e-3 lr off at the same entry, and every other block of
 the case is within 1.9e-4."""
-import json
-import os
-import subprocess
-import sys
-
 import pytest
 
 from tests._reward_fit_cases import BLOCKS, CASES, MAX_CASE, ROUTE0
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-_RUN = {}
+from tests._worker_run import worker_result
 
 CAP_PARAMS, CAP_LOSS, CAP_CONT, CAP_FIXTURE = 6.6e-3, 6.4e-6, 3e-4, 2.6e-5
 BARS = {
@@ -72,19 +65,7 @@ pytestmark = pytest.mark.gpu
 
 
 def _result():
-    if "r" not in _RUN:
-        try:
-            p = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "_reward_fit_worker.py")], capture_output=True, text=True,
-                               timeout=300, cwd=ROOT)
-            out = p.stdout + p.stderr
-            line = [l for l in p.stdout.splitlines() if l.startswith("RESULT ")]
-            _RUN["r"] = (json.loads(line[-1][7:]) if p.returncode == 0 and line else None, "exit %d\n%s" % (p.returncode, out[-4000:]))
-        except subprocess.TimeoutExpired as e:
-            _RUN["r"] = (None, "timed out: %s" % str(e.stdout)[-2000:])
-    r, log = _RUN["r"]
-    if r is None:
-        pytest.fail("reward-fit worker failed (not restarted):\n" + log)
-    return r
+    return worker_result("_reward_fit_worker.py", 300, "reward-fit")
 
 
 def _under(r, *keys):

@@ -45,33 +45,15 @@ against the long-double reference.  Measured on the MI355X:
 Features (k_bl_features_f32): n 1, 17, 64 at N 1, 255, 257, and n 1 at N 419 431 (the first element count beyond 8192 x 256).
 Observation columns bit-equal to float32(clip(obs, -10, 10) / 10); time columns within 1 fp32 ulp of the long-double power
 rounded to fp32 [measured: 0 ulp in all ten cases] and exact at tpos 0 and 1000; a NaN tail behind the output stays NaN."""
-import json
-import os
-import subprocess
-import sys
-
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-_RUN = {}
+from tests._worker_run import worker_result
 
 pytestmark = pytest.mark.gpu
 
 
 def _result():
-    if "r" not in _RUN:
-        try:
-            p = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "_ridge_matrix_worker.py")], capture_output=True, text=True,
-                               timeout=600, cwd=ROOT)
-            out = p.stdout + p.stderr
-            line = [l for l in p.stdout.splitlines() if l.startswith("RESULT ")]
-            _RUN["r"] = (json.loads(line[-1][7:]) if p.returncode == 0 and line else None, "exit %d\n%s" % (p.returncode, out[-4000:]))
-        except subprocess.TimeoutExpired as e:
-            _RUN["r"] = (None, "timed out: %s" % str(e.stdout)[-2000:])
-    r, log = _RUN["r"]
-    if r is None:
-        pytest.fail("ridge matrix worker failed (not restarted):\n" + log)
-    return r
+    return worker_result("_ridge_matrix_worker.py", 600, "ridge matrix")
 
 
 def _within_bound(r, key):

@@ -8,33 +8,21 @@ K = 1, 2, 3, 5 and fourteen (P, H) whose P H and P (H - 1) hit 31, 32, 33, 128, 
 against the fp64 oracle, relative to the row's oracle value (rows below 1e-3 of the case's largest against that floor); the bar is
 3 x the yardstick, a plain fp32 torch restatement's distance from the same oracle (tests/golden/rollout_batch.npz), on both routes.
 Pack: every output bit for bit against the NumPy emulation, and nothing written at or behind row off[P]."""
-import json
 import os
-import subprocess
 import sys
 
 import pytest
+
+from tests._worker_run import worker_result
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import _rollout_batch_cases as B  # noqa: E402
 
-_RUN = {}
 
 
 def _result():
-    if "r" not in _RUN:
-        try:
-            p = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "_rollout_batch_worker.py")], capture_output=True, text=True,
-                               timeout=300, cwd=ROOT)
-            line = [l for l in p.stdout.splitlines() if l.startswith("RESULT ")]
-            _RUN["r"] = (json.loads(line[-1][7:]) if p.returncode == 0 and line else None, "exit %d\n%s" % (p.returncode, (p.stdout + p.stderr)[-4000:]))
-        except subprocess.TimeoutExpired as e:
-            _RUN["r"] = (None, "timed out: %s" % str(e.stdout)[-2000:])
-    r, log = _RUN["r"]
-    if r is None:
-        pytest.fail("rollout batch worker failed (not restarted):\n" + log)
-    return r
+    return worker_result("_rollout_batch_worker.py", 300, "rollout batch")
 
 
 @pytest.mark.gpu

@@ -8,13 +8,13 @@ The bars are 3 x the unmodified reference's own fp32 error on the same quantity 
 tests/golden/make_golden_rollout_wide.py), never a multiple of anything the kernel produced.  Measured on the MI355X: every case
 takes between 0.22 and 0.44 of its bar on either route (w3's actions on route 0 the most), the routes against each other at most
 0.40 of theirs (w1's states), free-running w1 at most 0.26 (route 2) and 0.34 (route 0)."""
-import json
 import os
-import subprocess
 import sys
 
 import numpy as np
 import pytest
+
+from tests._worker_run import worker_result
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -22,24 +22,11 @@ import _rollout_wide_cases as W  # noqa: E402
 
 G = np.load(os.path.join(ROOT, "tests", "golden", "rollout_wide.npz"))
 GR = np.load(os.path.join(ROOT, "tests", "golden", "refine.npz"))
-_RUN = {}
 CASES = sorted(W.WCASES)
 
 
 def _result():
-    if "r" not in _RUN:
-        try:
-            p = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "_rollout_wide_worker.py")], capture_output=True, text=True,
-                               timeout=300, cwd=ROOT)
-            out = p.stdout + p.stderr
-            line = [l for l in p.stdout.splitlines() if l.startswith("RESULT ")]
-            _RUN["r"] = (json.loads(line[-1][7:]) if p.returncode == 0 and line else None, "exit %d\n%s" % (p.returncode, out[-4000:]))
-        except subprocess.TimeoutExpired as e:
-            _RUN["r"] = (None, "timed out: %s" % str(e.stdout)[-2000:])
-    r, log = _RUN["r"]
-    if r is None:
-        pytest.fail("wide rollout worker failed (not restarted):\n" + log)
-    return r
+    return worker_result("_rollout_wide_worker.py", 300, "wide rollout")
 
 
 def _bars(name, g=G):

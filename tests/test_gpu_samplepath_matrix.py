@@ -54,33 +54,15 @@ entries planted below, just below, exactly at and just above min_log_std, the la
 1e30; mjx_apply_npg_step with g.x 3.7, -3.7, 0, 1e-300 at step_size 0.05, alpha_out bit-equal to
 np.sqrt(np.abs(step_size / (gdotx + 1e-20))) and accepted as NULL.
     [measured: no mismatch in 120 + 120 calls, alpha_out equal in all 96 that ask for it]"""
-import json
-import os
-import subprocess
-import sys
-
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-_RUN = {}
+from tests._worker_run import worker_result
 
 pytestmark = pytest.mark.gpu
 
 
 def _result():
-    if "r" not in _RUN:
-        try:
-            p = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "_samplepath_worker.py")], capture_output=True, text=True,
-                               timeout=600, cwd=ROOT)
-            out = p.stdout + p.stderr
-            line = [l for l in p.stdout.splitlines() if l.startswith("RESULT ")]
-            _RUN["r"] = (json.loads(line[-1][7:]) if p.returncode == 0 and line else None, "exit %d\n%s" % (p.returncode, out[-4000:]))
-        except subprocess.TimeoutExpired as e:
-            _RUN["r"] = (None, "timed out: %s" % str(e.stdout)[-2000:])
-    r, log = _RUN["r"]
-    if r is None:
-        pytest.fail("sample-path worker failed (not restarted):\n" + log)
-    return r
+    return worker_result("_samplepath_worker.py", 600, "sample-path")
 
 
 def _within(r, key, bar=1.0):

@@ -14,12 +14,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import _mpc_learned_oracle as L  # noqa: E402
 import _mpc_oracle as M  # noqa: E402
+from tests._worker_dev import ints as _ints  # noqa: E402
 
 G = np.load(os.path.join(ROOT, "tests", "golden", "mpc_learned.npz"))
-
-
-def _ints(v):
-    return (ctypes.c_int * len(v))(*[int(x) for x in v])
 
 
 @pytest.mark.parametrize("case", sorted(L.PLAN_CASES))

@@ -16,14 +16,11 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import _mpc_learned_oracle as L  # noqa: E402
 import _mpc_oracle as M  # noqa: E402
 import _refine_oracle as F  # noqa: E402
+from tests._worker_dev import ints as _ints  # noqa: E402
 
 G = np.load(os.path.join(ROOT, "tests", "golden", "refine.npz"))
 TOL_STEP = 1e-5
 LDS_MAX = 160 * 1024
-
-
-def _ints(v):
-    return (ctypes.c_int * len(v))(*v)
 
 
 def _lib():

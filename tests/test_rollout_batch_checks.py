@@ -17,10 +17,7 @@ for p in (ROOT, HERE):
         sys.path.insert(0, p)
 import _plan_cases as C  # noqa: E402
 import _rollout_batch_cases as B  # noqa: E402
-
-
-def _ints(v):
-    return (ctypes.c_int * len(v))(*v)
+from tests._worker_dev import ints as _ints  # noqa: E402
 
 
 def _lib():

@@ -17,13 +17,10 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import _refine_oracle as F  # noqa: E402
 import _rollout_wide_cases as W  # noqa: E402
+from tests._worker_dev import ints as _ints  # noqa: E402
 
 G = np.load(os.path.join(ROOT, "tests", "golden", "rollout_wide.npz"))
 LDS_MAX = 160 * 1024
-
-
-def _ints(v):
-    return (ctypes.c_int * len(v))(*v)
 
 
 def _lib():
