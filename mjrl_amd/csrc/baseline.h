@@ -413,14 +413,9 @@ struct MlpRegressor {
     const float* in = X;
     for (int l = 0; l < nL(); ++l) {
       const bool last = l == nL() - 1;
-      GemmArgs g{};
-      g.M = (int)rows; g.N = sizes[l + 1]; g.npairs = 1; g.K[0] = sizes[l];
-      g.A[0] = in; g.a_rs[0] = sizes[l]; g.a_ks[0] = 1;
-      g.B[0] = params + oW[l]; g.b_cs[0] = sizes[l]; g.b_ks[0] = 1;
-      g.C = last ? out : acts[l]; g.ldc = sizes[l + 1]; g.c_zs = 0;
+      GemmArgs g = gemm_nt((int)rows, sizes[l + 1], sizes[l], in, sizes[l], params + oW[l], sizes[l], last ? out : acts[l], last ? EPI_BIAS : EPI_BIAS_RELU);
       g.bias = params + ob[l];
-      g.epi = last ? EPI_BIAS : EPI_BIAS_RELU;
-      LayerwiseWS::launch_gemm(g, 1, st);
+      lw_launch_gemm(g, 1, st);
       in = g.C;
     }
   }

@@ -28,14 +28,9 @@
 #include <type_traits>
 
 #include "fused_policy.h"
+#include "lw_plan.h"       // GemmArgs, the EPI_* kinds, the GP_* tile geometry and gp_lds_bytes
 
-// (included by layerwise.h after GemmArgs and the EPI_* kinds are declared)
 namespace mjx {
-
-constexpr int GP_BM = 128, GP_BN = 256, GP_BK = 32, GP_LD = GP_BK + 4, GP_NTH = 512;
-constexpr int GP_ASZ = GP_BM * GP_LD;                                                  // [row][k] image of the A tile
-template <int LB> constexpr int gp_bsz() { return LB ? GP_BK * (GP_BN + 4) : GP_BN * GP_LD; }
-template <int LB> constexpr size_t gp_lds_bytes() { return sizeof(float) * (size_t)(2 * GP_ASZ + 2 * gp_bsz<LB>() + 2 * GP_BN); }
 
 template <int LB, int EPI, class Args>
 __global__ __launch_bounds__(GP_NTH, 2) void k_gemm_p(Args g, int row_tiles, int col_blocks, int* __restrict__ ticket) {

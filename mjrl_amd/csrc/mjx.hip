@@ -142,8 +142,7 @@ struct mjx_ctx {
   unsigned* ticket = nullptr;                      // workgroup ticket of the producer kernels (ordinary device memory, zero between launches)
   mjx::FusedWS fz;                 // fused path workspace (fz.variant != 0: it serves this context)
   mjx::LayerwiseWS lw;             // layer-wise path workspace
-  mjx::LayerwiseWS lwmb;           // minibatch trainer workspace (mjx_policy_minibatch_adam)
-  float *mb_x = nullptr, *mb_a = nullptr, *mb_adv = nullptr, *mb_grad = nullptr; int mb_cap = 0;
+  mjx::MinibatchWS lwmb;           // launch-based minibatch trainer's workspace (mjx_policy_minibatch_adam)
 };
 
 namespace {
@@ -228,7 +227,7 @@ int mjx_create(mjx_ctx** out, int device, int n, int m, const int* hidden, int n
   HIPCHK(hipMemcpy(c->ident_tr, id.data(), id.size() * 4, hipMemcpyHostToDevice));
   HIPCHK(hipMemset(c->fz.spartials, 0, c->fz.spartials_bytes()));
   c->lw.init(n, m, c->hidden);
-  c->lwmb.init(n, m, c->hidden);
+  c->lwmb.lw.init(n, m, c->hidden);
   *out = c;
   return MJX_OK;
 }
@@ -239,7 +238,6 @@ void mjx_destroy(mjx_ctx* c) {
   (void)mjx_comm_destroy(c);
   c->lw.release();
   c->lwmb.release();
-  hipFree(c->mb_x); hipFree(c->mb_a); hipFree(c->mb_adv); hipFree(c->mb_grad);
   for (auto& e : c->prof_ev) hipEventDestroy(e);
   c->fz.release();
   hipFree(c->ident_tr);
@@ -326,7 +324,7 @@ int mjx_bl_num_features(int kind, int n) { return (kind < 0 || kind > 2 || n <= 
 int mjx_bl_features_f32(const double* obs, const int32_t* tpos, int64_t N, int n, float* out, void* stream) {
   if (!obs || !tpos || !out || N < 0 || n <= 0) return fail(MJX_ERR_ARG, "bad arguments");
   if (N == 0) return MJX_OK;
-  hipLaunchKernelGGL(k_bl_features_f32, dim3(LayerwiseWS::ew_grid(N * (n + 4))), dim3(256), 0, (hipStream_t)stream, obs, tpos, N, n, out);
+  hipLaunchKernelGGL(k_bl_features_f32, dim3(ew_grid(N * (n + 4))), dim3(256), 0, (hipStream_t)stream, obs, tpos, N, n, out);
   HIPCHK(hipGetLastError());
   return MJX_OK;
 }
@@ -356,7 +354,7 @@ int mjx_bl_gram(int kind, const double* obs, const int32_t* tpos, const double* 
     return (int)MJX_OK;
   };
   if (int rc = r.arm == GRAM_MFMA ? launch(k_bl_gram_mfma, dim3(r.Z)) : launch(blk ? k_bl_gram_mfma_blk : k_bl_gram, dim3(r.gx, r.Z), r.nblk)) return rc;
-  hipLaunchKernelGGL(k_bl_gram_reduce, dim3(LayerwiseWS::ew_grid((int64_t)FA * FA)), dim3(256), 0, (hipStream_t)stream, (const double*)part, r.Z, FA, G, r.blk);
+  hipLaunchKernelGGL(k_bl_gram_reduce, dim3(ew_grid((int64_t)FA * FA)), dim3(256), 0, (hipStream_t)stream, (const double*)part, r.Z, FA, G, r.blk);
   HIPCHK(hipGetLastError());
   return MJX_OK;
 }
@@ -480,21 +478,10 @@ int mjx_mlp_fit_adam(const float* feat, const float* y, int64_t N, int d_in, con
       for (int l = L - 1; l >= 0; --l) {
         const int ho = net.sizes[l + 1], hi_ = net.sizes[l];
         const float* in = (l == 0) ? Xb : acts[l - 1];
-        GemmArgs g{};
-        g.M = ho; g.N = hi_; g.npairs = 1; g.K[0] = bs;
-        g.A[0] = delta; g.a_rs[0] = 1; g.a_ks[0] = ho;
-        g.B[0] = in; g.b_cs[0] = 1; g.b_ks[0] = hi_;
-        g.C = grads + net.oW[l]; g.ldc = hi_; g.c_zs = 0; g.epi = EPI_STORE;
-        LayerwiseWS::launch_gemm(g, 1, st);
+        lw_launch_gemm(gemm_wgrad(bs, ho, hi_, delta, in, hi_, grads + net.oW[l]), 1, st);
         hipLaunchKernelGGL(k_colsum, dim3((ho + 63) / 64, 1), dim3(256), 0, st, delta, (int64_t)bs, ho, (int64_t)ho, grads + net.ob[l]);
         if (l > 0) {
-          GemmArgs b{};
-          b.M = bs; b.N = hi_; b.npairs = 1; b.K[0] = ho;
-          b.A[0] = delta; b.a_rs[0] = ho; b.a_ks[0] = 1;
-          b.B[0] = params + net.oW[l]; b.b_cs[0] = 1; b.b_ks[0] = hi_;
-          b.C = dl[l - 1]; b.ldc = hi_; b.c_zs = 0;
-          b.aux = acts[l - 1]; b.ld_aux = hi_; b.epi = EPI_BACK_RELU;
-          LayerwiseWS::launch_gemm(b, 1, st);
+          lw_launch_gemm(gemm_delta(bs, ho, hi_, delta, params + net.oW[l], false, dl[l - 1], acts[l - 1], EPI_BACK_RELU), 1, st);
           delta = dl[l - 1];
         }
       }
@@ -1093,7 +1080,7 @@ static int fvp_impl(mjx_ctx* c, const float* v, float* out, void* stream, const 
   if (c->N_local == 0) { HIPCHK(hipMemsetAsync(out, 0, c->d * sizeof(float), st)); return MJX_OK; }
   if (!c->old_is_new) {
     // general position (e.g. input_normalization, npg_cg.py:101-107): exact Pearlmutter product on the layer-wise path
-    if (c->lw.cap < c->N_local) { if (int rc = c->lw.reserve(c->N_local)) return fail(rc, "layer-wise workspace allocation failed"); }
+    if (int rc = c->lw.ensure_rows(c->N_local)) return fail(rc, "layer-wise workspace allocation failed");
     int rc = c->lw.hvp_general(c->obs, c->N_local, c->N_global, c->theta_new, c->theta_old, tr_new_or_ident(c), tr_old_or_ident(c), v, out, st);
     return rc ? fail(MJX_ERR_STATE, "general Hessian-vector product failed (%d)", rc) : MJX_OK;
   }
@@ -1619,10 +1606,8 @@ int mjx_policy_forward(mjx_ctx* c, const float* obs, int64_t N, const float* the
   if (!c || N < 0 || (N > 0 && (!obs || !theta || !mean_out))) return fail(MJX_ERR_ARG, "bad arguments");
   if (N == 0) return MJX_OK;
   HIPCHK(hipSetDevice(c->device));
-  if (c->lw.cap < N) { if (int rc = c->lw.reserve(N)) return fail(rc, "layer-wise workspace allocation failed"); }
-  c->lw.invalidate();                           // the hidden activations of the bound policy are overwritten (scratch)
-  c->lw.forward(theta, tr ? tr : c->ident_tr, obs, N, c->lw.T, mean_out, (hipStream_t)stream);
-  HIPCHK(lw_status());
+  if (int rc = c->lw.ensure_rows(N)) return fail(rc, "layer-wise workspace allocation failed");
+  HIPCHK(c->lw.forward_scratch(theta, tr ? tr : c->ident_tr, obs, N, mean_out, (hipStream_t)stream));
   return MJX_OK;
 }
 
@@ -1656,29 +1641,18 @@ int mjx_policy_minibatch_adam(mjx_ctx* c, int loss, const float* obs, const floa
     HIPCHK(hipGetLastError());
     return MJX_OK;
   }
-  LayerwiseWS& w = c->lwmb;
-  if (w.cap < B) { if (int rc = w.reserve(B)) return fail(rc, "minibatch workspace allocation failed"); }
-  if (c->mb_cap < B) {
-    hipFree(c->mb_x); hipFree(c->mb_a); hipFree(c->mb_adv);
-    HIPCHK(hipMalloc(&c->mb_x, (size_t)B * c->n * 4)); HIPCHK(hipMalloc(&c->mb_a, (size_t)B * c->m * 4)); HIPCHK(hipMalloc(&c->mb_adv, (size_t)B * 4));
-    c->mb_cap = B;
-  }
-  if (!c->mb_grad) HIPCHK(hipMalloc(&c->mb_grad, (size_t)c->d * 4));
+  MinibatchWS& w = c->lwmb;
+  if (int rc = w.reserve(B)) return fail(rc, "minibatch workspace allocation failed");
   const float *trn = trn0, *tro = tro0;
   const int64_t cnt = (loss == 0) ? (int64_t)c->oS : c->d;       // MSE: log_std has no gradient -> untouched (like torch's grad None)
   const unsigned ggrid = capped_grid(B * (c->n > c->m ? c->n : c->m), 256, 1024);
   for (int64_t s = 0; s < steps; ++s) {
-    hipLaunchKernelGGL(k_gather_minibatch, dim3(ggrid), dim3(256), 0, st, obs, act,
-                       (loss == 2) ? adv : (const float*)nullptr, idx + s * B, B, c->n, c->m, c->mb_x, c->mb_a, c->mb_adv);
     const bool old_fwd = (loss == 2) && !old_tracks_new;
-    if (old_fwd) w.forward(theta_old, tro, c->mb_x, B, w.T, w.mu2, st);          // old policy on the minibatch (activations are scratch)
-    w.forward(theta, trn, c->mb_x, B, w.H, w.mu, st);
-    hipLaunchKernelGGL(k_minibatch_head, dim3(1), dim3(256), 0, st, loss, w.mu, (loss == 2) ? (old_fwd ? w.mu2 : w.mu) : (const float*)nullptr, c->mb_a,
-                       c->mb_adv, B, c->m, theta + c->oS, (loss == 2) ? theta_old + c->oS : (const float*)nullptr, trn + 2 * c->n + c->m,
-                       clip, w.d3, c->mb_grad + c->oS, loss_trace ? loss_trace + s : (double*)nullptr);
-    if (int rc = w.backward(theta, B, c->mb_grad, st)) return fail(MJX_ERR_STATE, "minibatch backward failed (%d)", rc);
+    if (int rc = w.grad_step(loss, obs, act, adv, idx + s * B, B, theta, trn, theta_old, tro, old_fwd, clip,
+                             loss_trace ? loss_trace + s : (double*)nullptr, ggrid, st))
+      return fail(MJX_ERR_STATE, "minibatch backward failed (%d)", rc);
     const AdamBias bc = adam_bias(ADAM_B1D, ADAM_B2D, step0 + s + 1);      // torch's constants, as k_policy_fit takes them (vecops.h)
-    hipLaunchKernelGGL(k_adam, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, theta, c->mb_grad, adam_m, adam_v, cnt, lr, 0.f,
+    hipLaunchKernelGGL(k_adam, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, theta, w.grad.p, adam_m, adam_v, cnt, lr, 0.f,
                        ADAM_C1, ADAM_B2, ADAM_C2, ADAM_EPS, bc.bc1, bc.bc2s);
   }
   HIPCHK(lw_status());

@@ -1,14 +1,19 @@
-"""Every launch path of the layer-wise hidden-layer chain (LayerwiseWS, csrc/layerwise.h; persistent kernel csrc/lw_gemm_p.h)
-against the fp64 oracle, block by block, row by row and column by column.
+"""Every launch path of the layer-wise hidden-layer chain (LayerwiseWS, csrc/layerwise.h; routes csrc/lw_plan.h, launcher
+csrc/lw_launch.h, kernels csrc/lw_gemm.h and csrc/lw_gemm_p.h) against the fp64 oracle, block by block, row by row and column by
+column.
 
 The device runs go through tests/_gemm_chain_worker.py in child processes, one per arm, with MJX_FORCE_LAYERWISE=1 and the
-arm's switches in the child's environment (most are read once per process).  Each case checks the policy's means
+arm's switches in the child's environment (MJX_LW_WT and MJX_LW_OLD_OUTPUTS are read once per process, every other MJX_LW_*
+switch at the start of each operation: the table in csrc/lw_plan.h).  Each case checks the policy's means
 (mjx_policy_forward) row by row; K1 with an explicit old network, K2 at old == new and the general Hessian (old != new, the new
 network with transforms of its own) against the fp64 oracle per block, per weight row, per weight column and per bias entry
 (tests/_lw_check.fine_errors); K3's surrogate and KL at the bars of test_other_shapes_vs_oracle.
 
 Routes at the default switches (n, m, hidden; N = 3000 + n unless noted).  "fwd" = forward / tangent products (M = N rows,
 N = the layer's units), "delta" = the delta product towards the layer below, "wgrad" = weight gradients split over samples.
+Which product shape reaches which kernel instance, grid and column slice -- at the defaults and under every switch below that
+changes a route -- is asserted without a GPU by tests/test_lw_plan_cpu.py (table in tests/c/lw_plan.cpp); the table here says
+which of those routes each case is there to reach.
 
     case       n, m, hidden            kernels reached (kernel trace of the default worker)
     odd        11, 3, (100, 50)        ldx 12: padded first layer (k_pad_rows, k_unpad_rows); k_gemm<128, 128, 512> forward /

@@ -14,6 +14,7 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tests", "c", "host_san.cpp")
 SRC_LS = os.path.join(ROOT, "tests", "c", "launch_state_san.cpp")
+SRC_LP = os.path.join(ROOT, "tests", "c", "lw_plan.cpp")
 HIP_INC = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "include")
 SAN = [("asan_ubsan", ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer"]), ("tsan", ["-fsanitize=thread"])]
 
@@ -55,3 +56,23 @@ def test_launch_state_under_sanitizers(tmp_path, name, flags):
     r = subprocess.run([exe, "3"], capture_output=True, text=True, timeout=600, env=env)
     # (the tables and the scratch blocks live as long as the process, like the state they stand for -- hence detect_leaks=0)
     assert r.returncode == 0 and "launch_state_san ok" in r.stdout and "Sanitizer" not in r.stderr, (r.stdout[-500:], r.stderr[-4000:])
+
+
+def test_lw_plan_under_sanitizers(tmp_path):
+    """mjrl_amd/csrc/lw_plan.h -- routes, split counts, column slices and GemmArgs builders of the layer-wise path -- is plain
+    host C++ without a HIP call; tests/c/lw_plan.cpp (its route table, tests/test_lw_plan_cpu.py) once more under
+    -fsanitize=address,undefined: the column slices do pointer arithmetic on every operand."""
+    name, flags = SAN[0]
+    cxx = os.environ.get("CXX", "g++")
+    if shutil.which(cxx) is None:
+        pytest.skip("no C++ compiler")
+    if not os.path.exists(os.path.join(HIP_INC, "hip", "hip_runtime_api.h")):
+        pytest.skip("no HIP headers under %s" % HIP_INC)
+    exe = str(tmp_path / ("lw_plan_" + name))
+    b = subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-D__HIP_PLATFORM_AMD__", "-I" + HIP_INC] + flags + [SRC_LP, "-o", exe],
+                       capture_output=True, text=True, cwd=os.path.dirname(SRC_LP))
+    if b.returncode != 0 and "sanitize" in b.stderr and ("cannot find" in b.stderr or "unrecognized" in b.stderr):
+        pytest.skip("this toolchain has no %s runtime" % name)
+    assert b.returncode == 0, b.stderr[-3000:]
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120, env=dict(os.environ, ASAN_OPTIONS="abort_on_error=0"))
+    assert r.returncode == 0 and "lw_plan ok" in r.stdout and "Sanitizer" not in r.stderr, (r.stdout[-2000:], r.stderr[-4000:])
