@@ -585,6 +585,29 @@ int mjx_path_rewards(const float* obs, const float* act, int64_t act_stride, int
                      int dyn_n_sizes, const float* dyn_params, const float* dyn_tr, int dyn_act, int dyn_flags,
                      const int* rew_sizes, int rew_n_sizes, const float* rew_params, const float* rew_tr, int rew_act,
                      float* r32_out, double* r64_out, int* route_out, void* stream);
+/* Whether the wide MFMA path-reward kernel (csrc/rows_wide.h: activations as LDS tiles of 64 stored rows, weights streamed from
+ * global memory, a workgroup per member walking its tiles) serves a dynamics net dyn_sizes = [n + m, h1, h2, n] and a reward
+ * net rew_sizes = [2 n + m, g1, g2, 1]: 1 = served: both nets with exactly two hidden layers, every hidden width 1 .. 256,
+ * n <= 64, m <= 64, n + m <= 128 and the layout -- max(pad32(h1), pad32(n), pad32(g1)) + max(pad8(n + m), pad32(h2),
+ * pad8(2 n + m), pad32(g2)) rows of 68 floats, then h1 + h2 + g1 + 2 g2 + 9 n + 4 m + 3 floats of biases, head weights and
+ * transforms -- within 160 KiB (it always is: at most 139 264 + 8 460 bytes); 0 = not served; < 0 = bad sizes (as
+ * mjx_path_rewards_route).  Arithmetic only: no device work and no runtime call.  The answer does not depend on
+ * mjx_path_rewards_route's: the shapes the register-resident kernel takes are served as well. */
+int mjx_path_rewards_wide_route(const int* dyn_sizes, int dyn_n_sizes, const int* rew_sizes, int rew_n_sizes);
+/* The stored rows a workgroup of the csrc/rows_wide.h kernels takes per tile in this build: 64 (32 in a -DMJX_RW_NS=1 build, which
+ * tools/bench_rows_wide.py times beside it).  A constant of the build. */
+int mjx_rows_wide_tile_rows(void);
+/* mjx_path_rewards with the wide kernel in front of it: the same arguments in the same order.  Where
+ * mjx_path_rewards_wide_route serves the shape it runs k_path_rewards_wide and reports route 2 in *route_out; otherwise, under
+ * MJX_PATH_REWARDS_WIDE=0, under MJX_PATH_REWARDS_MFMA=0 (both read per call) and after an LDS refusal it IS mjx_path_rewards:
+ * same routing, same bits, same *route_out (1 or 0).  rows == 0 returns MJX_OK without a launch (and reports the route); bad
+ * arguments return MJX_ERR_ARG and touch nothing.  Route 2 uses no scratch and no atomics.  Its head (d_out = 1) is summed in a
+ * fixed order: thread (column, q) adds G2[u] w3[u] with fmaf for u = q, q + 8, ... from 0, the column's thread adds the 8
+ * partial dots in q order, then (dot + b3) (out_scale + 1e-8) + out_shift: the bits are the same on every run. */
+int mjx_path_rewards_wide(const float* obs, const float* act, int64_t act_stride, int64_t rows, int K, const int* dyn_sizes,
+                          int dyn_n_sizes, const float* dyn_params, const float* dyn_tr, int dyn_act, int dyn_flags,
+                          const int* rew_sizes, int rew_n_sizes, const float* rew_params, const float* rew_tr, int rew_act,
+                          float* r32_out, double* r64_out, int* route_out, void* stream);
 
 /* ---- device-resident model rollouts (ModelAccelNPG.train_step(resident=True); csrc/rollout_batch.h) ---- */
 /* Which route mjx_rollout_disagreement takes for a net dyn_sizes = [n + m, h..., n]: 1 = the MFMA kernel k_rollout_disagree
@@ -606,6 +629,25 @@ int mjx_rollout_disagreement_route(const int* dyn_sizes, int dyn_n_sizes);
 int mjx_rollout_disagreement(const float* obs, const float* act, int64_t P, int H, int K, const int* dyn_sizes,
                              int dyn_n_sizes, const float* dyn_params, const float* dyn_tr, int dyn_act, int dyn_flags,
                              float* err_out, int* route_out, void* stream);
+/* Whether the wide MFMA disagreement kernel (csrc/rows_wide.h, k_rollout_disagree_wide: the dynamics half of
+ * k_path_rewards_wide) serves a net dyn_sizes = [n + m, h1, h2, n]: 1 = served: exactly two hidden layers, both widths
+ * 1 .. 256, n <= 64, m <= 64, n + m <= 128 and the layout -- max(pad32(h1), pad32(n)) + max(pad8(n + m), pad32(h2)) rows of 68
+ * floats, then h1 + h2 + 5 n + 2 m floats of biases and transforms -- within 160 KiB (it always is); 0 = not served; < 0 =
+ * bad sizes (as mjx_rollout_disagreement_route).  Arithmetic only: no device work and no runtime call.  The shapes
+ * k_rollout_disagree takes are served as well. */
+int mjx_rollout_disagreement_wide_route(const int* dyn_sizes, int dyn_n_sizes);
+/* mjx_rollout_disagreement with the wide kernel in front of it: the same arguments in the same order.  Where
+ * mjx_rollout_disagreement_wide_route serves the shape it runs k_rollout_disagree_wide, then k_rd_max, and reports route 2 in
+ * *route_out; otherwise, under MJX_ROLLOUT_DISAGREE_WIDE=0, under MJX_ROLLOUT_DISAGREE_MFMA=0 (both read per call) and after
+ * an LDS refusal it IS mjx_rollout_disagreement: same routing, same bits, same *route_out (1 or 0).  Route 2's mean: the
+ * thread that owns a stored row adds d * d (d = next - s' and its square in fp32) for c = 0 .. n - 1 in index order from 0 in an
+ * fp64 sum, divides by n and casts to fp32 (route 0's arithmetic; an fp32 sum of 64 terms in one thread misses the fp64 oracle by
+ * more than the tests allow); the members' means go to mjx_rollout_disagreement's scratch block and their maximum is taken in member order (no
+ * float atomics, no reductions across lanes: the same bits on every run).  P = 0 or H <= 1 returns MJX_OK without a launch (and
+ * reports the route); bad arguments return MJX_ERR_ARG and touch nothing. */
+int mjx_rollout_disagreement_wide(const float* obs, const float* act, int64_t P, int H, int K, const int* dyn_sizes,
+                                  int dyn_n_sizes, const float* dyn_params, const float* dyn_tr, int dyn_act, int dyn_flags,
+                                  float* err_out, int* route_out, void* stream);
 /* The truncation decision (model_accel_npg.py:149-155) and the ragged batch, packed.  obs P x H x n, act P x H x m fp32;
  * exactly one of rew32 / rew64 (P x H each); err (P x (H - 1), mjx_rollout_disagreement's output) or NULL.  Per path p:
  * v = the first t in [0, H - 1) with (double)err[p][t] > lim (a NaN never counts; err NULL: none), -1 if none; T = H when

@@ -127,6 +127,15 @@ PROTOTYPES = {
     "mjx_rollout_disagreement_route": (c_int, [ctypes.POINTER(c_int), c_int]),
     "mjx_rollout_disagreement": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, ctypes.POINTER(c_int), c_int, c_void_p, c_void_p, c_int,
                                          c_int, c_void_p, ctypes.POINTER(c_int), c_void_p]),
+    # (the narrow entries' argument lists; route 2 = the wide MFMA kernels of csrc/rows_wide.h, MJX_..._WIDE=0: the narrow entry itself)
+    "mjx_rows_wide_tile_rows": (c_int, []),
+    "mjx_path_rewards_wide_route": (c_int, [ctypes.POINTER(c_int), c_int, ctypes.POINTER(c_int), c_int]),
+    "mjx_path_rewards_wide": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int, ctypes.POINTER(c_int), c_int, c_void_p, c_void_p, c_int, c_int,
+                                      ctypes.POINTER(c_int), c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, ctypes.POINTER(c_int),
+                                      c_void_p]),
+    "mjx_rollout_disagreement_wide_route": (c_int, [ctypes.POINTER(c_int), c_int]),
+    "mjx_rollout_disagreement_wide": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, ctypes.POINTER(c_int), c_int, c_void_p, c_void_p, c_int,
+                                              c_int, c_void_p, ctypes.POINTER(c_int), c_void_p]),
     "mjx_rollout_pack": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_double, c_int, c_double,
                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "mjx_profile_enable": (c_int, [c_void_p, c_int]),

@@ -217,8 +217,9 @@ class ModelAccelNPG(NPG):
     # ---- the device-resident route
     def train_step_info(self):
         """what the last ``train_step`` did: dict(resident, why (the reason the host route ran, else None), routes (dict(rollout,
-        rewards, disagreement): 1 = the MFMA kernel, 0 = the generic route, None = no device call; rollout may also be 2 = the
-        wide MFMA policy rollout for nets up to 256 wide, csrc/policy_rollout_wide.h), paths, rows, truncated);
+        rewards, disagreement): 1 = the MFMA kernel, 0 = the generic route, None = no device call; each may also be 2 = the
+        wide MFMA kernel for nets up to 256 wide: csrc/policy_rollout_wide.h for rollout, csrc/rows_wide.h for rewards and
+        disagreement, where ``nn_dynamics.wide_rows_shape`` sends them to the ``_wide`` entries), paths, rows, truncated);
         None before any call.  The last three are filled by the resident route alone."""
         return None if self._step_info is None else dict(self._step_info)
 
@@ -243,7 +244,8 @@ class ModelAccelNPG(NPG):
     def _resident_paths(self, init_states, H, noise, reward_function, truncate_lim, truncate_reward):
         """the same paths with the rollouts left on the device: one upload (start states, noise), ``mjx_policy_rollout`` on the
         members ``get_refined_action`` caches, ``mjx_path_rewards`` (or one read-back, the host ``reward_function`` per member and
-        one upload), ``mjx_rollout_disagreement``, ``mjx_rollout_pack``, one read-back of the packed blocks.  The host ``paths``
+        one upload), ``mjx_rollout_disagreement`` (both through their ``_wide`` entries for dynamics nets wider than 128,
+        ``nn_dynamics.wide_rows_shape``), ``mjx_rollout_pack``, one read-back of the packed blocks.  The host ``paths``
         are per-path views of that read-back; the packed device blocks are registered for them (utils/ingest.register_device_batch),
         so returns, advantages, the update and the baseline read those and upload nothing."""
         dev = _device()
@@ -256,7 +258,7 @@ class ModelAccelNPG(NPG):
         routes["rollout"] = info["route"]
         if learned:
             rew_d = torch.empty((K, N, H), dtype=torch.float32, device=dev)
-            routes["rewards"] = path_rewards_call(pk["rew"], obs_d, act_d, False, N * H, K, rew_d, None, dev)
+            routes["rewards"] = path_rewards_call(pk["rew"], obs_d, act_d, False, N * H, K, rew_d, None, dev, wide=True)
         else:
             obs_h, act_h = obs_d.cpu().numpy(), act_d.cpu().numpy()
             rew_h = [np.asarray(reward_function(dict(observations=obs_h[k], actions=act_h[k]))['rewards']) for k in range(K)]
@@ -264,7 +266,7 @@ class ModelAccelNPG(NPG):
             rew_d = torch.from_numpy(np.ascontiguousarray(rew_h, np.float32 if rew_h.dtype == np.float32 else np.float64)).to(dev)
         err_d = None
         if truncate_lim is not None and K > 1:
-            err_d = rollout_disagreement_device(models, obs_d, act_d, packed=pk, info=info)
+            err_d = rollout_disagreement_device(models, obs_d, act_d, packed=pk, info=info, wide=True)
             routes["disagreement"] = info["route"]
         pb = pack_rollouts_device(obs_d, act_d, rew_d, err_d, 0.0 if truncate_lim is None else truncate_lim, MIN_TRUNCATED_LEN,
                                   truncate_reward)
@@ -353,7 +355,8 @@ class ModelAccelNPG(NPG):
            members differ only in where their dynamics take it (as ``MPCPolicy``'s members share action sequences);
         2. ``mjx_policy_rollout`` (one launch; bounds +-1e2 as ``policy_rollout`` defaults; ``mjx_policy_rollout_wide`` for
            nets wider than its MFMA route takes, ``sampling.wide_rollout_shape``: :meth:`refine_route` is then 2);
-        3. rewards: every member's reward net on the device (``mjx_path_rewards``, nothing read back) when all members learn
+        3. rewards: every member's reward net on the device (``mjx_path_rewards``, ``mjx_path_rewards_wide`` for dynamics nets
+           wider than 128, ``nn_dynamics.wide_rows_shape``; nothing read back) when all members learn
            rewards, else one read-back and ``self.reward_function(dict(observations, actions))`` per member as ``train_step``
            calls it and one upload; with neither, ``ValueError``;
         4. ``mjx_plan_score`` with ``kappa``, ``refine_gamma`` and ``refine_omega`` (the per-trajectory disagreement term; off
@@ -378,7 +381,7 @@ class ModelAccelNPG(NPG):
                                              packed=pk, info=info)
         if learned:
             r_d = torch.empty((K, N, H), dtype=torch.float64, device=dev)
-            path_rewards_call(pk["rew"], obs_d, act_d, False, N * H, K, None, r_d, dev)
+            path_rewards_call(pk["rew"], obs_d, act_d, False, N * H, K, None, r_d, dev, wide=True)
         else:
             obs_h, act_h = obs_d.cpu().numpy(), act_d.cpu().numpy()
             rewards = np.empty((K, N, H), np.float64)

@@ -19,7 +19,9 @@ global torch stream are the reference's) and transforms.  What runs where:
   read-back; :func:`ensemble_path_rewards_device`: the same on device tensors in one ``mjx_path_rewards`` call, which is what
   ``MPCPolicy(reward='learned')`` plans on;
 * :func:`rollout_disagreement_device`: the ensemble-disagreement error of rollouts that are on the device
-  (``mjx_rollout_disagreement``), which ``ModelAccelNPG.train_step(resident=True)`` truncates on.
+  (``mjx_rollout_disagreement``), which ``ModelAccelNPG.train_step(resident=True)`` truncates on.  Both device passes take
+  ``wide=True``: for dynamics nets wider than 128 (:func:`wide_rows_shape`) they then call the ``_wide`` entries
+  (csrc/rows_wide.h: fp32 MFMAs for nets up to 256 wide, route 2).
 
 What every one of these shares stands once: :func:`pack_members` (K nets of one shape as the device blocks ``P`` and ``tr``, under
 every forward, rollout, fit and under ``pack_dynamics_members`` / ``pack_reward_members``), :func:`_dynamics_transforms` /
@@ -625,25 +627,38 @@ def members_pack_key(members, dev, with_rewards):
     return key, held
 
 
-def path_rewards_call(pk, obs_d, act_d, shared, rows, K, r32, r64, dev):
-    """one ``mjx_path_rewards`` over packed members (:func:`pack_reward_members`) -> the route taken"""
+def wide_rows_shape(dyn_sizes, rew_sizes=None):
+    """whether the passes over stored rollouts hand a dynamics net (and a reward net, where one is given) to the ``_wide`` entries
+    (``mjx_rollout_disagreement_wide``, ``mjx_path_rewards_wide``; csrc/rows_wide.h) when their caller asks for them: every net
+    given with two hidden layers and a dynamics width above 128 -- wider than anything the register-resident routes take.  Plain
+    Python, no library call; narrower on purpose than what the wide kernels serve (``mjx_..._wide_route``): the shapes that have
+    a route today keep their call."""
+    nets = [dyn_sizes] + ([] if rew_sizes is None else [rew_sizes])
+    return all(len(sz) == 4 for sz in nets) and max(dyn_sizes[1:3]) > 128
+
+
+def path_rewards_call(pk, obs_d, act_d, shared, rows, K, r32, r64, dev, wide=False):
+    """one ``mjx_path_rewards`` over packed members (:func:`pack_reward_members`) -> the route taken.  ``wide``: where
+    :func:`wide_rows_shape` says so, ``mjx_path_rewards_wide`` with the same arguments (route 2 = the wide MFMA kernel)"""
     route = ctypes.c_int(-1)
     m = pk["dyn_sizes"][0] - pk["dyn_sizes"][-1]
-    check(load().mjx_path_rewards(ptr(obs_d), ptr(act_d), 0 if shared else rows * m, rows, K, _ints(pk["dyn_sizes"]), len(pk["dyn_sizes"]),
-                                  ptr(pk["dyn_P"]), ptr(pk["dyn_tr"]), pk["dyn_act"], pk["dyn_flags"], _ints(pk["rew_sizes"]),
-                                  len(pk["rew_sizes"]), ptr(pk["rew_P"]), ptr(pk["rew_tr"]), pk["rew_act"],
-                                  None if r32 is None else ptr(r32), None if r64 is None else ptr(r64), ctypes.byref(route), _stream(dev)))
+    lib = load()
+    entry = lib.mjx_path_rewards_wide if wide and wide_rows_shape(pk["dyn_sizes"], pk["rew_sizes"]) else lib.mjx_path_rewards
+    check(entry(ptr(obs_d), ptr(act_d), 0 if shared else rows * m, rows, K, _ints(pk["dyn_sizes"]), len(pk["dyn_sizes"]),
+                ptr(pk["dyn_P"]), ptr(pk["dyn_tr"]), pk["dyn_act"], pk["dyn_flags"], _ints(pk["rew_sizes"]),
+                len(pk["rew_sizes"]), ptr(pk["rew_P"]), ptr(pk["rew_tr"]), pk["rew_act"],
+                None if r32 is None else ptr(r32), None if r64 is None else ptr(r64), ctypes.byref(route), _stream(dev)))
     return route.value
 
 
-def ensemble_path_rewards_device(models, obs_d, act_d, want64=False, packed=None):
+def ensemble_path_rewards_device(models, obs_d, act_d, want64=False, packed=None, wide=False):
     """:func:`ensemble_path_rewards` on device data: obs_d (K, N, H, n) and act_d (K, N, H, m), or (N, H, m) shared by all members,
     fp32 device tensors -> rewards (K, N, H) fp32 on the device, with ``want64`` (fp32, the same values as fp64).  One
     ``mjx_path_rewards`` call (csrc/path_reward.h: both nets of a member in LDS on MFMAs where ``mjx_path_rewards_route`` says so,
     ``mjx_dyn_forward``'s kernel twice otherwise).  Members must share shapes, activation and flags.  The DATA make no host copy;
     the members' parameters and transforms are flattened and uploaded on every call unless ``packed`` carries the blocks of an
     earlier :func:`pack_reward_members` of the same, unchanged members on this device (``MPCPolicy`` keeps its own, keyed on the
-    members' state)."""
+    members' state).  ``wide``: as :func:`path_rewards_call`."""
     models = list(models)
     dev = obs_d.device
     assert obs_d.is_cuda and act_d.device == dev and obs_d.dtype == act_d.dtype == torch.float32, "fp32 device tensors"
@@ -657,7 +672,7 @@ def ensemble_path_rewards_device(models, obs_d, act_d, want64=False, packed=None
     obs_d, act_d = obs_d.contiguous(), act_d.contiguous()
     r32 = torch.empty((K, N, H), dtype=torch.float32, device=dev)
     r64 = torch.empty((K, N, H), dtype=torch.float64, device=dev) if want64 else None
-    path_rewards_call(pk, obs_d, act_d, shared, N * H, K, r32, r64, dev)
+    path_rewards_call(pk, obs_d, act_d, shared, N * H, K, r32, r64, dev, wide=wide)
     return (r32, r64) if want64 else r32
 
 
@@ -668,12 +683,13 @@ def members_share_kind(models, with_rewards=False):
     return all(len({(tuple(net.layer_sizes), _act_code(net), _flags(net)) for net in group}) == 1 for group in nets)
 
 
-def rollout_disagreement_device(models, obs_d, act_d, packed=None, info=None):
+def rollout_disagreement_device(models, obs_d, act_d, packed=None, info=None, wide=False):
     """the ensemble-disagreement error (model_accel_npg.py:137-147) of rollouts that are on the device: obs_d (..., H, n) and act_d
     (..., H, m) fp32 device tensors, the stored rollouts of any number of paths (``train_step``: (K, N, H, .), all members' back to
     back) -> err (P, H - 1) fp32 on the device, err[p, t] = max over members of mean_c (obs[p, t + 1] - f_k(obs[p, t], act[p, t]))^2.
     One ``mjx_rollout_disagreement`` call (csrc/rollout_batch.h).  ``packed``: the blocks of :func:`pack_dynamics_members` (a
-    :func:`cached_members_pack` holder's); ``info`` (a dict) receives ``route``."""
+    :func:`cached_members_pack` holder's); ``info`` (a dict) receives ``route``.  ``wide``: where :func:`wide_rows_shape` says so,
+    ``mjx_rollout_disagreement_wide`` with the same arguments (route 2 = the wide MFMA kernel, csrc/rows_wide.h)."""
     models = list(models)
     dev = obs_d.device
     assert obs_d.is_cuda and act_d.device == dev and obs_d.dtype == act_d.dtype == torch.float32, "fp32 device tensors"
@@ -686,8 +702,10 @@ def rollout_disagreement_device(models, obs_d, act_d, packed=None, info=None):
     P = obs_d.numel() // (H * n) if H else 0
     err = torch.empty((P, max(H - 1, 0)), dtype=torch.float32, device=dev)
     route = ctypes.c_int(-1)
-    check(load().mjx_rollout_disagreement(ptr(obs_d), ptr(act_d), P, H, len(models), _ints(sizes), len(sizes), ptr(pk["P"]), ptr(pk["tr"]),
-                                          pk["act"], pk["flags"], ptr(err), ctypes.byref(route), _stream(dev)))
+    lib = load()
+    entry = lib.mjx_rollout_disagreement_wide if wide and wide_rows_shape(sizes) else lib.mjx_rollout_disagreement
+    check(entry(ptr(obs_d), ptr(act_d), P, H, len(models), _ints(sizes), len(sizes), ptr(pk["P"]), ptr(pk["tr"]),
+                pk["act"], pk["flags"], ptr(err), ctypes.byref(route), _stream(dev)))
     if info is not None:
         info["route"] = route.value
     return err

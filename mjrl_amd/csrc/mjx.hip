@@ -33,6 +33,7 @@
 #include "policy_rollout.h"
 #include "policy_rollout_wide.h"
 #include "rollout_batch.h"
+#include "rows_wide.h"
 #include "vecops.h"
 
 namespace {
@@ -609,9 +610,7 @@ int mjx_path_rewards(const float* obs, const float* act, int64_t act_stride, int
   DynNet dyn, rew;
   if (int rc = path_rew_nets(dyn_sizes, dyn_n_sizes, rew_sizes, rew_n_sizes, dyn, rew)) return rc;
   const int n = dyn.dout(), m = dyn.din() - n;
-  if (!obs || !act || !dyn_params || !dyn_tr || !rew_params || !rew_tr || (!r32_out && !r64_out) || rows < 0 ||
-      (act_stride != 0 && act_stride != rows * m) || (dyn_flags & ~(DYN_OUT_AFFINE | DYN_MASK | DYN_RESIDUAL)) ||
-      !dyn_args_ok(dyn, K, dyn_act, DYN_TGT_PLAIN, dyn_flags & DYN_RESIDUAL) || !dyn_args_ok(rew, K, rew_act))
+  if (!path_rew_args_ok(dyn, rew, obs, act, act_stride, rows, K, dyn_params, dyn_tr, dyn_act, dyn_flags, rew_params, rew_tr, rew_act, r32_out, r64_out))
     return fail(MJX_ERR_ARG, "bad arguments");
   ChainShape ps;
   const bool served = env_flag("MJX_PATH_REWARDS_MFMA", true) && path_rew_shape(dyn, rew, ps);     // (read per call: A/B runs in one process)
@@ -647,6 +646,42 @@ int mjx_path_rewards(const float* obs, const float* act, int64_t act_stride, int
   HIPCHK(hipGetLastError());
   if (route_out) *route_out = 0;
   return MJX_OK;
+}
+
+// ---------------------------------------------------------------------------- the same for nets up to 256 wide (csrc/rows_wide.h)
+int mjx_rows_wide_tile_rows(void) { return 32 * RW_NS; }
+
+int mjx_path_rewards_wide_route(const int* dyn_sizes, int dyn_n_sizes, const int* rew_sizes, int rew_n_sizes) {
+  DynNet dyn, rew;
+  if (int rc = path_rew_nets(dyn_sizes, dyn_n_sizes, rew_sizes, rew_n_sizes, dyn, rew)) return rc;
+  size_t bytes;
+  return wide_rows_shape(dyn, &rew, bytes) ? 1 : 0;
+}
+
+int mjx_path_rewards_wide(const float* obs, const float* act, int64_t act_stride, int64_t rows, int K, const int* dyn_sizes, int dyn_n_sizes,
+                          const float* dyn_params, const float* dyn_tr, int dyn_act, int dyn_flags, const int* rew_sizes, int rew_n_sizes,
+                          const float* rew_params, const float* rew_tr, int rew_act, float* r32_out, double* r64_out, int* route_out,
+                          void* stream) {
+  DynNet dyn, rew;
+  if (int rc = path_rew_nets(dyn_sizes, dyn_n_sizes, rew_sizes, rew_n_sizes, dyn, rew)) return rc;
+  if (!path_rew_args_ok(dyn, rew, obs, act, act_stride, rows, K, dyn_params, dyn_tr, dyn_act, dyn_flags, rew_params, rew_tr, rew_act, r32_out, r64_out))
+    return fail(MJX_ERR_ARG, "bad arguments");
+  size_t bytes = 0;
+  // (both switches read per call: A/B runs in one process; MJX_PATH_REWARDS_MFMA=0 means no MFMA route at all)
+  const bool served = env_flag("MJX_PATH_REWARDS_WIDE", true) && env_flag("MJX_PATH_REWARDS_MFMA", true) && wide_rows_shape(dyn, &rew, bytes);
+  if (served) {
+    if (rows == 0) { if (route_out) *route_out = 2; return MJX_OK; }
+    MJX_DEVICE_ENTRY();
+    const int n = dyn.dout(), m = dyn.din() - n;
+    const PathRewArgs a{obs, act, act_stride, dyn_params, dyn_tr, rew_params, rew_tr, r32_out, r64_out, rows, dyn.P, rew.P,
+                        n, m, dyn.sz[1], dyn.sz[2], dyn_act, dyn_flags, rew.sz[1], rew.sz[2], rew_act};
+    bool launched;
+    if (int rc = launch_chained(k_path_rewards_wide<RW_NS>, bytes, wide_rows_grid(rows, K), a, (hipStream_t)stream, launched, dim3(DFE_THREADS)))
+      return rc;
+    if (launched) { if (route_out) *route_out = 2; return MJX_OK; }
+  }
+  return mjx_path_rewards(obs, act, act_stride, rows, K, dyn_sizes, dyn_n_sizes, dyn_params, dyn_tr, dyn_act, dyn_flags, rew_sizes, rew_n_sizes,
+                          rew_params, rew_tr, rew_act, r32_out, r64_out, route_out, stream);
 }
 
 // ---------------------------------------------------------------------------- policy rollout on learned models (csrc/policy_rollout.h)
@@ -751,9 +786,7 @@ int mjx_rollout_disagreement(const float* obs, const float* act, int64_t P, int 
   DynNet dyn;
   if (int rc = roll_dis_net(dyn_sizes, dyn_n_sizes, dyn)) return rc;
   const int n = dyn.dout(), m = dyn.din() - n;
-  if (!obs || !act || !dyn_params || !dyn_tr || !err_out || P < 0 || H < 0 || (dyn_flags & ~(DYN_OUT_AFFINE | DYN_MASK | DYN_RESIDUAL)) ||
-      !dyn_args_ok(dyn, K, dyn_act, DYN_TGT_PLAIN, dyn_flags & DYN_RESIDUAL))
-    return fail(MJX_ERR_ARG, "bad arguments");
+  if (!roll_dis_args_ok(dyn, obs, act, P, H, K, dyn_params, dyn_tr, dyn_act, dyn_flags, err_out)) return fail(MJX_ERR_ARG, "bad arguments");
   ChainShape ps;
   const bool served = env_flag("MJX_ROLLOUT_DISAGREE_MFMA", true) && plan_shape(dyn, m, ps);     // (read per call: A/B runs in one process)
   if (P == 0 || H <= 1) { if (route_out) *route_out = served ? 1 : 0; return MJX_OK; }
@@ -788,6 +821,45 @@ int mjx_rollout_disagreement(const float* obs, const float* act, int64_t P, int 
   HIPCHK(hipGetLastError());
   if (route_out) *route_out = 0;
   return MJX_OK;
+}
+
+// the same for nets up to 256 wide (csrc/rows_wide.h)
+int mjx_rollout_disagreement_wide_route(const int* dyn_sizes, int dyn_n_sizes) {
+  DynNet dyn;
+  if (int rc = roll_dis_net(dyn_sizes, dyn_n_sizes, dyn)) return rc;
+  size_t bytes;
+  return wide_rows_shape(dyn, nullptr, bytes) ? 1 : 0;
+}
+
+int mjx_rollout_disagreement_wide(const float* obs, const float* act, int64_t P, int H, int K, const int* dyn_sizes, int dyn_n_sizes,
+                                  const float* dyn_params, const float* dyn_tr, int dyn_act, int dyn_flags, float* err_out, int* route_out,
+                                  void* stream) {
+  DynNet dyn;
+  if (int rc = roll_dis_net(dyn_sizes, dyn_n_sizes, dyn)) return rc;
+  if (!roll_dis_args_ok(dyn, obs, act, P, H, K, dyn_params, dyn_tr, dyn_act, dyn_flags, err_out)) return fail(MJX_ERR_ARG, "bad arguments");
+  size_t bytes = 0;
+  // (both switches read per call: A/B runs in one process; MJX_ROLLOUT_DISAGREE_MFMA=0 means no MFMA route at all)
+  const bool served = env_flag("MJX_ROLLOUT_DISAGREE_WIDE", true) && env_flag("MJX_ROLLOUT_DISAGREE_MFMA", true) && wide_rows_shape(dyn, nullptr, bytes);
+  if (served) {
+    if (P == 0 || H <= 1) { if (route_out) *route_out = 2; return MJX_OK; }
+    MJX_DEVICE_ENTRY();
+    hipStream_t st = (hipStream_t)stream;
+    const int n = dyn.dout(), m = dyn.din() - n;
+    const int64_t rows = P * H, R = P * (H - 1);
+    // mjx_rollout_disagreement's block of its scratch site, at its size: the member means (K x R) lie at its start
+    float* scr = nullptr;
+    if (int rc = dev_scratch(SITE_ROLLOUT_DISAGREE, stream, (size_t)R * (n + m + (size_t)K * n) * sizeof(float), &scr)) return rc;
+    const RollDisArgs a{obs, act, dyn_params, dyn_tr, scr, rows, dyn.P, H, n, m, dyn.sz[1], dyn.sz[2], dyn_act, dyn_flags};
+    bool launched;
+    if (int rc = launch_chained(k_rollout_disagree_wide<RW_NS>, bytes, wide_rows_grid(rows, K), a, st, launched, dim3(DFE_THREADS))) return rc;
+    if (launched) {
+      hipLaunchKernelGGL(k_rd_max, dim3(capped_grid(R, 256, 4096)), dim3(256), 0, st, scr, K, R, err_out);
+      HIPCHK(hipGetLastError());
+      if (route_out) *route_out = 2;
+      return MJX_OK;
+    }
+  }
+  return mjx_rollout_disagreement(obs, act, P, H, K, dyn_sizes, dyn_n_sizes, dyn_params, dyn_tr, dyn_act, dyn_flags, err_out, route_out, stream);
 }
 
 int mjx_rollout_pack(const float* obs, const float* act, const float* rew32, const double* rew64, const float* err, int64_t P, int H, int n,

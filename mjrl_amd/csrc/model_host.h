@@ -1,4 +1,4 @@
-// model_host.h -- host side of the learned-model kernels (dynamics.h, dyn_fit_ens.h, plan.h, path_reward.h, policy_rollout.h, policy_rollout_wide.h, rollout_batch.h): their shared
+// model_host.h -- host side of the learned-model kernels (dynamics.h, dyn_fit_ens.h, plan.h, path_reward.h, policy_rollout.h, policy_rollout_wide.h, rollout_batch.h, rows_wide.h): their shared
 // argument checks, their routes as plain arithmetic, and the launches more than one entry makes.  Included by mjx.hip after fail / HIPCHK /
 // lds_limit / capped_grid.
 #pragma once
@@ -174,6 +174,41 @@ inline int roll_dis_net(const int* dyn_sizes, int dyn_n_sizes, DynNet& dyn) {
   if (int rc = dyn_net(dyn_sizes, dyn_n_sizes, dyn)) return rc;
   if (dyn.din() <= dyn.dout()) return fail(MJX_ERR_ARG, "dyn_sizes must be [n + m, h..., n] with m > 0");
   return MJX_OK;
+}
+
+// the remaining arguments of mjx_rollout_disagreement / mjx_rollout_disagreement_wide
+inline bool roll_dis_args_ok(const DynNet& dyn, const float* obs, const float* act, int64_t P, int H, int K, const float* dyn_params,
+                             const float* dyn_tr, int dyn_act, int dyn_flags, const float* err_out) {
+  return !(!obs || !act || !dyn_params || !dyn_tr || !err_out || P < 0 || H < 0 || (dyn_flags & ~(DYN_OUT_AFFINE | DYN_MASK | DYN_RESIDUAL)) ||
+           !dyn_args_ok(dyn, K, dyn_act, DYN_TGT_PLAIN, dyn_flags & DYN_RESIDUAL));
+}
+// ... and of mjx_path_rewards / mjx_path_rewards_wide
+inline bool path_rew_args_ok(const DynNet& dyn, const DynNet& rew, const float* obs, const float* act, int64_t act_stride, int64_t rows, int K,
+                             const float* dyn_params, const float* dyn_tr, int dyn_act, int dyn_flags, const float* rew_params,
+                             const float* rew_tr, int rew_act, const float* r32_out, const double* r64_out) {
+  const int m = dyn.din() - dyn.dout();
+  return !(!obs || !act || !dyn_params || !dyn_tr || !rew_params || !rew_tr || (!r32_out && !r64_out) || rows < 0 ||
+           (act_stride != 0 && act_stride != rows * m) || (dyn_flags & ~(DYN_OUT_AFFINE | DYN_MASK | DYN_RESIDUAL)) ||
+           !dyn_args_ok(dyn, K, dyn_act, DYN_TGT_PLAIN, dyn_flags & DYN_RESIDUAL) || !dyn_args_ok(rew, K, rew_act));
+}
+
+// ---- the wide passes over stored rollouts.  What k_rollout_disagree_wide (rew null) and k_path_rewards_wide (rows_wide.h) serve:
+// every net given with exactly two hidden layers, every hidden width 1 .. 256, n <= 64, m <= 64, n + m <= 128, and the LDS layout
+// (the kernels have no static LDS) within LDS_MAX.  They do not ask what plan_shape / path_rew_shape answer: the shapes the chained
+// kernels take are served as well.  MJX_ROLLOUT_DISAGREE_WIDE=0 / MJX_PATH_REWARDS_WIDE=0 or the matching ..._MFMA=0 (read per call
+// by mjx_rollout_disagreement_wide / mjx_path_rewards_wide): the narrow entry.
+inline bool wide_rows_shape(const DynNet& dyn, const DynNet* rew, size_t& bytes) {
+  if (dyn.nl != 3 || (rew && rew->nl != 3)) return false;
+  const int n = dyn.dout(), m = dyn.din() - n;
+  for (int l = 1; l <= 2; ++l) if (dyn.sz[l] > RW_MAXH || (rew && rew->sz[l] > RW_MAXH)) return false;
+  if (n > RW_MAXN || m > RW_MAXM || n + m > RW_MAXIN) return false;
+  bytes = sizeof(float) * rows_wide_lds_floats(n, m, dyn.sz[1], dyn.sz[2], rew ? rew->sz[1] : 0, rew ? rew->sz[2] : 0);
+  return bytes <= LDS_MAX;
+}
+// the grid of both: a workgroup per tile of 32 RW_NS rows up to one workgroup per CU, the K members sharing the CUs
+inline dim3 wide_rows_grid(int64_t rows, int K) {
+  const int64_t tiles = (rows + 32 * RW_NS - 1) / (32 * RW_NS), cap = (cu_count() + K - 1) / K;
+  return dim3((unsigned)(tiles < cap ? tiles : cap), (unsigned)K);
 }
 
 // ---- dynamics fit.  k_dyn_fit, the persistent trainer, serves hidden widths <= 128 at minibatches <= 64 (shape) whose activations fit in LDS beside
