@@ -45,6 +45,7 @@ constexpr int DYN_MAXL = 8;           // Linear layers per net (hidden + output)
 constexpr int DYN_RT = 8;             // rollout: trajectories per workgroup
 constexpr int DYN_FT = 32;            // forward: rows per workgroup
 constexpr int DYN_RPG = 4;            // rows per thread in a layer product
+__host__ __device__ constexpr int pad8(int d) { return (d + 7) & ~7; }   // a layer's K dimension in whole groups of eight (the MFMA kernels)
 
 struct DynNet {
   int nl = 0;                         // Linear layers
@@ -66,6 +67,15 @@ struct DynNet {
 __device__ __forceinline__ float dyn_act(float x, int act) { return act == DYN_ACT_TANH ? tanhf(x) : fmaxf(x, 0.f); }
 // derivative from the layer's OUTPUT (torch's relu / tanh backward: grad * (y > 0), grad * (1 - y^2))
 __device__ __forceinline__ float dyn_dact(float y, int act) { return act == DYN_ACT_TANH ? 1.f - y * y : (y > 0.f ? 1.f : 0.f); }
+// a dynamics net's raw output z of unit i under the output flags: affine (out_scale + 1e-8, out_shift), the mask of the units whose
+// out_scale is below 1e-8, the residual resid() -- each read only where its flag is set
+template <class Resid>
+__device__ __forceinline__ float dyn_out_flags(float z, int flags, const float* osh, const float* osc, int i, Resid resid) {
+  if (flags & DYN_OUT_AFFINE) z = z * (osc[i] + 1e-8f) + osh[i];
+  if (flags & DYN_MASK) z = z * (osc[i] >= 1e-8f ? 1.f : 0.f);
+  if (flags & DYN_RESIDUAL) z = z + resid();
+  return z;
+}
 
 // out[r][j] = act(b[j] + sum_i in[r][i] W[j][i]) for r < rows, j < dout (act < 0: none).  in / out row strides ldi / ldo; W, b in
 // torch layout, in global memory or LDS.  A thread owns one unit j and DYN_RPG rows: every weight it loads serves DYN_RPG rows,
@@ -116,11 +126,7 @@ __device__ void dyn_net_tile(const DynNet& net, const float* __restrict__ P, con
   const float* osc = osh + dout;
   for (int e = threadIdx.x; e < rows * dout; e += blockDim.x) {
     const int r = e / dout, j = e - r * dout;
-    float z = in[r * W + j];
-    if (flags & DYN_OUT_AFFINE) z = z * (osc[j] + 1e-8f) + osh[j];
-    if (flags & DYN_MASK) z = z * (osc[j] >= 1e-8f ? 1.f : 0.f);
-    if (flags & DYN_RESIDUAL) z = z + x[(int64_t)r * ldx + j];
-    y[(int64_t)r * ldy + j] = z;
+    y[(int64_t)r * ldy + j] = dyn_out_flags(in[r * W + j], flags, osh, osc, j, [&] { return x[(int64_t)r * ldx + j]; });
   }
   __syncthreads();
 }

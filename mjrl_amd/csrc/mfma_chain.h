@@ -22,7 +22,6 @@
 namespace mjx {
 
 constexpr int PLAN_MAX_M8 = 32;       // action slots a lane keeps: 4 k-steps x 4
-__host__ __device__ inline int plan_pad8(int v) { return (v + 7) & ~7; }
 
 struct ChainLane { int j, hi; };      // lane = 32 hi + j: row j of the tile, lane half hi
 // a first layer in LDS: W rows x S (S = padded columns + 4); per padded column the input shift and scale + 1e-8 (1 where padded)
@@ -102,7 +101,7 @@ __device__ __forceinline__ void chain_bias_act(f32x16 (&h)[MB], int mbs, const f
 //   out_scale + 1e-8, out_shift, mask: NS each                    -- 128 x 128 at n = 64, m = 32: 155.4 KiB of the 160 KiB.
 // plan_lds_floats sums these terms in carve()'s order: carve(base) - base == plan_lds_floats for the same (HB, NB, n, m).
 __host__ __device__ inline size_t plan_lds_floats(int HB, int NB, int n, int m) {
-  const size_t HW = 32 * (size_t)HB, K1 = (size_t)plan_pad8(n) + plan_pad8(m);
+  const size_t HW = 32 * (size_t)HB, K1 = (size_t)pad8(n) + pad8(m);
   return HW * (K1 + 4) + HW * (HW + 4) + 32 * NB * (HW + 4) + 2 * HW + 32 * NB + 2 * K1 + 3 * 32 * NB;
 }
 
@@ -113,7 +112,7 @@ struct DynImage {
   int n, m, n8, m8, K1, S1, din;
 
   __device__ __forceinline__ float* carve(float* base, int n_, int m_) {      // returns the end: where a second image may follow
-    n = n_; m = m_; n8 = plan_pad8(n); m8 = plan_pad8(m); K1 = n8 + m8; S1 = K1 + 4; din = n + m;
+    n = n_; m = m_; n8 = pad8(n); m8 = pad8(m); K1 = n8 + m8; S1 = K1 + 4; din = n + m;
     W1s = base; W2s = W1s + HW * S1; W3s = W2s + HW * S2;
     b1s = W3s + NS * S2; b2s = b1s + HW; b3s = b2s + HW;
     ish = b3s + NS; irs = ish + K1; osc = irs + K1; osh = osc + NS; msk = osh + NS;
@@ -188,7 +187,7 @@ struct DynImage {
 // [0, 0]; absent bounds are -inf / +inf.
 constexpr int POL_MAX_PB = 2;
 __host__ __device__ inline size_t pol_lds_floats(int p1, int p2, int n, int NB) {
-  const size_t P1 = 32 * (size_t)((p1 + 31) / 32), P2 = 32 * (size_t)((p2 + 31) / 32), n8 = (size_t)plan_pad8(n);
+  const size_t P1 = 32 * (size_t)((p1 + 31) / 32), P2 = 32 * (size_t)((p2 + 31) / 32), n8 = (size_t)pad8(n);
   return P1 * (n8 + 4) + P2 * (P1 + 4) + 32 * (P2 + 4) + P1 + P2 + 32 + 2 * n8 + 5 * 32 + 2 * 32 * (size_t)NB;
 }
 
@@ -199,7 +198,7 @@ struct PolImage {
   int n, m, n8, p1, p2, p1b, p2b, P1, P2, U1, U2, U3;
 
   __device__ __forceinline__ float* carve(float* base, int n_, int m_, int p1_, int p2_) {
-    n = n_; m = m_; n8 = plan_pad8(n); p1 = p1_; p2 = p2_;
+    n = n_; m = m_; n8 = pad8(n); p1 = p1_; p2 = p2_;
     p1b = (p1 + 31) >> 5; p2b = (p2 + 31) >> 5; P1 = 32 * p1b; P2 = 32 * p2b; U1 = n8 + 4; U2 = P1 + 4; U3 = P2 + 4;
     Q1s = base; Q2s = Q1s + P1 * U1; Q3s = Q2s + P2 * U2;
     d1 = Q3s + 32 * U3; d2 = d1 + P1; d3 = d2 + P2;

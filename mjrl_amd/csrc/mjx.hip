@@ -603,29 +603,37 @@ int mjx_path_rewards_route(const int* dyn_sizes, int dyn_n_sizes, const int* rew
   return path_rew_shape(dyn, rew, ps) ? 1 : 0;
 }
 
-int mjx_path_rewards(const float* obs, const float* act, int64_t act_stride, int64_t rows, int K, const int* dyn_sizes, int dyn_n_sizes,
-                     const float* dyn_params, const float* dyn_tr, int dyn_act, int dyn_flags, const int* rew_sizes, int rew_n_sizes,
-                     const float* rew_params, const float* rew_tr, int rew_act, float* r32_out, double* r64_out, int* route_out,
-                     void* stream) {
+// mjx_path_rewards (wide false) and mjx_path_rewards_wide: route 2 where asked for, then 1, then 0
+static int path_rewards(bool wide, const float* obs, const float* act, int64_t act_stride, int64_t rows, int K, const int* dyn_sizes,
+                        int dyn_n_sizes, const float* dyn_params, const float* dyn_tr, int dyn_act, int dyn_flags, const int* rew_sizes,
+                        int rew_n_sizes, const float* rew_params, const float* rew_tr, int rew_act, float* r32_out, double* r64_out,
+                        int* route_out, void* stream) {
   DynNet dyn, rew;
   if (int rc = path_rew_nets(dyn_sizes, dyn_n_sizes, rew_sizes, rew_n_sizes, dyn, rew)) return rc;
   const int n = dyn.dout(), m = dyn.din() - n;
   if (!path_rew_args_ok(dyn, rew, obs, act, act_stride, rows, K, dyn_params, dyn_tr, dyn_act, dyn_flags, rew_params, rew_tr, rew_act, r32_out, r64_out))
     return fail(MJX_ERR_ARG, "bad arguments");
-  ChainShape ps;
-  const bool served = env_flag("MJX_PATH_REWARDS_MFMA", true) && path_rew_shape(dyn, rew, ps);     // (read per call: A/B runs in one process)
-  if (rows == 0) { if (route_out) *route_out = served ? 1 : 0; return MJX_OK; }
+  // (the switches are read per call: A/B runs in one process; MJX_PATH_REWARDS_MFMA=0 means no MFMA route at all)
+  ChainShape ps; size_t wide_bytes = 0;
+  const bool mfma = env_flag("MJX_PATH_REWARDS_MFMA", true);
+  const bool served2 = wide && env_flag("MJX_PATH_REWARDS_WIDE", true) && mfma && wide_rows_shape(dyn, &rew, wide_bytes);
+  const bool served1 = mfma && path_rew_shape(dyn, rew, ps);
+  auto done = [&](int route) { if (route_out) *route_out = route; return MJX_OK; };
+  if (rows == 0) return done(served2 ? 2 : served1 ? 1 : 0);
   MJX_DEVICE_ENTRY();
   hipStream_t st = (hipStream_t)stream;
-  if (served) {
-    const PathRewArgs a{obs, act, act_stride, dyn_params, dyn_tr, rew_params, rew_tr, r32_out, r64_out, rows, dyn.P, rew.P,
-                        n, m, dyn.sz[1], dyn.sz[2], dyn_act, dyn_flags, rew.sz[1], rew.sz[2], rew_act};
+  const PathRewArgs a{obs, act, act_stride, dyn_params, dyn_tr, rew_params, rew_tr, r32_out, r64_out, rows, dyn.P, rew.P,
+                      n, m, dyn.sz[1], dyn.sz[2], dyn_act, dyn_flags, rew.sz[1], rew.sz[2], rew_act};
+  bool launched;
+  if (served2) {
+    if (int rc = launch_chained(k_path_rewards_wide<RW_NS>, wide_bytes, tile_grid(rows, 32 * RW_NS, K), a, st, launched, dim3(DFE_THREADS))) return rc;
+    if (launched) return done(2);
+  }
+  if (served1) {
     // a wave owns tiles of 32 rows; one workgroup per CU holds the image, so the K members share the CUs and a wave walks the
     // tiles beyond that (the staging prologue is paid once per workgroup)
-    const int64_t groups = (rows + 127) / 128, cap = (cu_count() + K - 1) / K;
-    bool launched;
-    if (int rc = launch_chained(path_rew_kernel(ps.HB, ps.NB), ps.bytes, dim3((unsigned)(groups < cap ? groups : cap), (unsigned)K), a, st, launched)) return rc;
-    if (launched) { if (route_out) *route_out = 1; return MJX_OK; }
+    if (int rc = launch_chained(path_rew_kernel(ps.HB, ps.NB), ps.bytes, tile_grid(rows, 128, K), a, st, launched)) return rc;
+    if (launched) return done(1);
   }
   // generic route: mjx_dyn_forward's kernel twice, over [s, a] and over [s, a, s'], both assembled in scratch
   const int din = n + m, rin = din + n;
@@ -644,8 +652,15 @@ int mjx_path_rewards(const float* obs, const float* act, int64_t act_stride, int
   hipLaunchKernelGGL(k_dyn_forward, grid, dim3(256), b2, st, fr);
   if (r64_out) hipLaunchKernelGGL(k_pr_widen, dim3(capped_grid(kr, 256, 4096)), dim3(256), 0, st, r32, kr, r64_out);
   HIPCHK(hipGetLastError());
-  if (route_out) *route_out = 0;
-  return MJX_OK;
+  return done(0);
+}
+
+int mjx_path_rewards(const float* obs, const float* act, int64_t act_stride, int64_t rows, int K, const int* dyn_sizes, int dyn_n_sizes,
+                     const float* dyn_params, const float* dyn_tr, int dyn_act, int dyn_flags, const int* rew_sizes, int rew_n_sizes,
+                     const float* rew_params, const float* rew_tr, int rew_act, float* r32_out, double* r64_out, int* route_out,
+                     void* stream) {
+  return path_rewards(false, obs, act, act_stride, rows, K, dyn_sizes, dyn_n_sizes, dyn_params, dyn_tr, dyn_act, dyn_flags, rew_sizes, rew_n_sizes,
+                      rew_params, rew_tr, rew_act, r32_out, r64_out, route_out, stream);
 }
 
 // ---------------------------------------------------------------------------- the same for nets up to 256 wide (csrc/rows_wide.h)
@@ -662,26 +677,8 @@ int mjx_path_rewards_wide(const float* obs, const float* act, int64_t act_stride
                           const float* dyn_params, const float* dyn_tr, int dyn_act, int dyn_flags, const int* rew_sizes, int rew_n_sizes,
                           const float* rew_params, const float* rew_tr, int rew_act, float* r32_out, double* r64_out, int* route_out,
                           void* stream) {
-  DynNet dyn, rew;
-  if (int rc = path_rew_nets(dyn_sizes, dyn_n_sizes, rew_sizes, rew_n_sizes, dyn, rew)) return rc;
-  if (!path_rew_args_ok(dyn, rew, obs, act, act_stride, rows, K, dyn_params, dyn_tr, dyn_act, dyn_flags, rew_params, rew_tr, rew_act, r32_out, r64_out))
-    return fail(MJX_ERR_ARG, "bad arguments");
-  size_t bytes = 0;
-  // (both switches read per call: A/B runs in one process; MJX_PATH_REWARDS_MFMA=0 means no MFMA route at all)
-  const bool served = env_flag("MJX_PATH_REWARDS_WIDE", true) && env_flag("MJX_PATH_REWARDS_MFMA", true) && wide_rows_shape(dyn, &rew, bytes);
-  if (served) {
-    if (rows == 0) { if (route_out) *route_out = 2; return MJX_OK; }
-    MJX_DEVICE_ENTRY();
-    const int n = dyn.dout(), m = dyn.din() - n;
-    const PathRewArgs a{obs, act, act_stride, dyn_params, dyn_tr, rew_params, rew_tr, r32_out, r64_out, rows, dyn.P, rew.P,
-                        n, m, dyn.sz[1], dyn.sz[2], dyn_act, dyn_flags, rew.sz[1], rew.sz[2], rew_act};
-    bool launched;
-    if (int rc = launch_chained(k_path_rewards_wide<RW_NS>, bytes, wide_rows_grid(rows, K), a, (hipStream_t)stream, launched, dim3(DFE_THREADS)))
-      return rc;
-    if (launched) { if (route_out) *route_out = 2; return MJX_OK; }
-  }
-  return mjx_path_rewards(obs, act, act_stride, rows, K, dyn_sizes, dyn_n_sizes, dyn_params, dyn_tr, dyn_act, dyn_flags, rew_sizes, rew_n_sizes,
-                          rew_params, rew_tr, rew_act, r32_out, r64_out, route_out, stream);
+  return path_rewards(true, obs, act, act_stride, rows, K, dyn_sizes, dyn_n_sizes, dyn_params, dyn_tr, dyn_act, dyn_flags, rew_sizes, rew_n_sizes,
+                      rew_params, rew_tr, rew_act, r32_out, r64_out, route_out, stream);
 }
 
 // ---------------------------------------------------------------------------- policy rollout on learned models (csrc/policy_rollout.h)
@@ -692,28 +689,38 @@ int mjx_policy_rollout_route(const int* pol_sizes, int pol_n_sizes, const int* d
   return pol_roll_shape(dyn, pol, ps) ? 1 : 0;
 }
 
-int mjx_policy_rollout(const float* s0, int64_t s0_stride, int64_t N, int H, int K, const int* pol_sizes, int pol_n_sizes,
-                       const float* pol_params, const float* pol_tr, const float* noise, int64_t noise_stride, const int* dyn_sizes,
-                       int dyn_n_sizes, const float* dyn_params, const float* dyn_tr, int act, int flags, const float* a_min,
-                       const float* a_max, const float* s_min, const float* s_max, float* obs_out, float* act_out, int* route_out,
-                       void* stream) {
+// mjx_policy_rollout (wide false) and mjx_policy_rollout_wide: route 2 where asked for, then 1, then 0
+static int policy_rollout(bool wide, const float* s0, int64_t s0_stride, int64_t N, int H, int K, const int* pol_sizes, int pol_n_sizes,
+                          const float* pol_params, const float* pol_tr, const float* noise, int64_t noise_stride, const int* dyn_sizes,
+                          int dyn_n_sizes, const float* dyn_params, const float* dyn_tr, int act, int flags, const float* a_min,
+                          const float* a_max, const float* s_min, const float* s_max, float* obs_out, float* act_out, int* route_out,
+                          void* stream) {
   RolloutArgs a{};
   if (int rc = pol_roll_nets(pol_sizes, pol_n_sizes, dyn_sizes, dyn_n_sizes, a.pol, a.dyn)) return rc;
   const int n = a.dyn.dout(), m = a.dyn.din() - n;
   if (!pol_roll_args_ok(a.dyn, s0, s0_stride, N, H, K, pol_params, pol_tr, noise_stride, dyn_params, dyn_tr, act, flags, a_min, a_max, s_min,
                         s_max, obs_out, act_out))
     return fail(MJX_ERR_ARG, "bad arguments");
-  ChainShape ps;
-  const bool served = env_flag("MJX_POLICY_ROLLOUT_MFMA", true) && pol_roll_shape(a.dyn, a.pol, ps);   // (read per call: A/B runs in one process)
-  if (N == 0 || H == 0) { if (route_out) *route_out = served ? 1 : 0; return MJX_OK; }
+  // (the switches are read per call: A/B runs in one process; MJX_POLICY_ROLLOUT_MFMA=0 means no MFMA rollout at all)
+  ChainShape ps; size_t wide_bytes = 0;
+  const bool mfma = env_flag("MJX_POLICY_ROLLOUT_MFMA", true);
+  const bool served2 = wide && env_flag("MJX_POLICY_ROLLOUT_WIDE", true) && mfma && wide_roll_shape(a.dyn, a.pol, wide_bytes);
+  const bool served1 = mfma && pol_roll_shape(a.dyn, a.pol, ps);
+  auto done = [&](int route) { if (route_out) *route_out = route; return MJX_OK; };
+  if (N == 0 || H == 0) return done(served2 ? 2 : served1 ? 1 : 0);
   MJX_DEVICE_ENTRY();
   hipStream_t st = (hipStream_t)stream;
-  if (served) {
-    const PolRollArgs p{s0, s0_stride, noise, noise_stride ? (int64_t)H : 0, pol_params, pol_tr, dyn_params, dyn_tr, a_min, a_max, s_min, s_max,
-                        obs_out, act_out, N, a.dyn.P, H, n, m, a.dyn.sz[1], a.dyn.sz[2], act, flags, a.pol.sz[1], a.pol.sz[2]};
-    bool launched;
+  const PolRollArgs p{s0, s0_stride, noise, noise_stride ? (int64_t)H : 0, pol_params, pol_tr, dyn_params, dyn_tr, a_min, a_max, s_min, s_max,
+                      obs_out, act_out, N, a.dyn.P, H, n, m, a.dyn.sz[1], a.dyn.sz[2], act, flags, a.pol.sz[1], a.pol.sz[2]};
+  bool launched;
+  if (served2) {
+    if (int rc = launch_chained(k_policy_rollout_wide, wide_bytes, dim3((unsigned)((N + 31) / 32), (unsigned)K), p, st, launched, dim3(DFE_THREADS)))
+      return rc;
+    if (launched) return done(2);
+  }
+  if (served1) {
     if (int rc = launch_chained(pol_roll_kernel(ps.HB, ps.NB), ps.bytes, dim3((unsigned)((N + 127) / 128), (unsigned)K), p, st, launched)) return rc;
-    if (launched) { if (route_out) *route_out = 1; return MJX_OK; }
+    if (launched) return done(1);
   }
   // generic route: k_model_rollout as mjx_model_rollout launches it; the tiled start state and the K copies of a shared noise
   // block go to the calling thread's scratch block of this site on (device, stream)
@@ -731,8 +738,16 @@ int mjx_policy_rollout(const float* s0, int64_t s0_stride, int64_t N, int H, int
   }
   a.pol_P = pol_params; a.pol_tr = pol_tr; a.noise = noise; a.a_lo = a_min; a.a_hi = a_max; a.s_lo = s_min; a.s_hi = s_max;
   if (int rc = launch_model_rollout(a, s0, N, H, K, nullptr, dyn_params, dyn_tr, act, flags, obs_out, act_out, st)) return rc;
-  if (route_out) *route_out = 0;
-  return MJX_OK;
+  return done(0);
+}
+
+int mjx_policy_rollout(const float* s0, int64_t s0_stride, int64_t N, int H, int K, const int* pol_sizes, int pol_n_sizes,
+                       const float* pol_params, const float* pol_tr, const float* noise, int64_t noise_stride, const int* dyn_sizes,
+                       int dyn_n_sizes, const float* dyn_params, const float* dyn_tr, int act, int flags, const float* a_min,
+                       const float* a_max, const float* s_min, const float* s_max, float* obs_out, float* act_out, int* route_out,
+                       void* stream) {
+  return policy_rollout(false, s0, s0_stride, N, H, K, pol_sizes, pol_n_sizes, pol_params, pol_tr, noise, noise_stride, dyn_sizes, dyn_n_sizes,
+                        dyn_params, dyn_tr, act, flags, a_min, a_max, s_min, s_max, obs_out, act_out, route_out, stream);
 }
 
 // ---------------------------------------------------------------------------- the same for nets up to 256 wide (csrc/policy_rollout_wide.h)
@@ -748,28 +763,8 @@ int mjx_policy_rollout_wide(const float* s0, int64_t s0_stride, int64_t N, int H
                             int dyn_n_sizes, const float* dyn_params, const float* dyn_tr, int act, int flags, const float* a_min,
                             const float* a_max, const float* s_min, const float* s_max, float* obs_out, float* act_out, int* route_out,
                             void* stream) {
-  DynNet pol, dyn;
-  if (int rc = pol_roll_nets(pol_sizes, pol_n_sizes, dyn_sizes, dyn_n_sizes, pol, dyn)) return rc;
-  if (!pol_roll_args_ok(dyn, s0, s0_stride, N, H, K, pol_params, pol_tr, noise_stride, dyn_params, dyn_tr, act, flags, a_min, a_max, s_min,
-                        s_max, obs_out, act_out))
-    return fail(MJX_ERR_ARG, "bad arguments");
-  size_t bytes = 0;
-  // (both switches read per call: A/B runs in one process; MJX_POLICY_ROLLOUT_MFMA=0 means no MFMA rollout at all)
-  const bool served = env_flag("MJX_POLICY_ROLLOUT_WIDE", true) && env_flag("MJX_POLICY_ROLLOUT_MFMA", true) && wide_roll_shape(dyn, pol, bytes);
-  if (served) {
-    if (N == 0 || H == 0) { if (route_out) *route_out = 2; return MJX_OK; }
-    MJX_DEVICE_ENTRY();
-    const int n = dyn.dout(), m = dyn.din() - n;
-    const PolRollArgs p{s0, s0_stride, noise, noise_stride ? (int64_t)H : 0, pol_params, pol_tr, dyn_params, dyn_tr, a_min, a_max, s_min, s_max,
-                        obs_out, act_out, N, dyn.P, H, n, m, dyn.sz[1], dyn.sz[2], act, flags, pol.sz[1], pol.sz[2]};
-    bool launched;
-    if (int rc = launch_chained(k_policy_rollout_wide, bytes, dim3((unsigned)((N + 31) / 32), (unsigned)K), p, (hipStream_t)stream, launched,
-                                dim3(DFE_THREADS)))
-      return rc;
-    if (launched) { if (route_out) *route_out = 2; return MJX_OK; }
-  }
-  return mjx_policy_rollout(s0, s0_stride, N, H, K, pol_sizes, pol_n_sizes, pol_params, pol_tr, noise, noise_stride, dyn_sizes, dyn_n_sizes,
-                            dyn_params, dyn_tr, act, flags, a_min, a_max, s_min, s_max, obs_out, act_out, route_out, stream);
+  return policy_rollout(true, s0, s0_stride, N, H, K, pol_sizes, pol_n_sizes, pol_params, pol_tr, noise, noise_stride, dyn_sizes, dyn_n_sizes,
+                        dyn_params, dyn_tr, act, flags, a_min, a_max, s_min, s_max, obs_out, act_out, route_out, stream);
 }
 
 // ---------------------------------------------------------------------------- device-resident model rollouts (csrc/rollout_batch.h)
@@ -780,35 +775,44 @@ int mjx_rollout_disagreement_route(const int* dyn_sizes, int dyn_n_sizes) {
   return plan_shape(dyn, dyn.din() - dyn.dout(), ps) ? 1 : 0;
 }
 
-int mjx_rollout_disagreement(const float* obs, const float* act, int64_t P, int H, int K, const int* dyn_sizes, int dyn_n_sizes,
-                             const float* dyn_params, const float* dyn_tr, int dyn_act, int dyn_flags, float* err_out, int* route_out,
-                             void* stream) {
+// mjx_rollout_disagreement (wide false) and mjx_rollout_disagreement_wide: route 2 where asked for, then 1, then 0
+static int rollout_disagreement(bool wide, const float* obs, const float* act, int64_t P, int H, int K, const int* dyn_sizes, int dyn_n_sizes,
+                                const float* dyn_params, const float* dyn_tr, int dyn_act, int dyn_flags, float* err_out, int* route_out,
+                                void* stream) {
   DynNet dyn;
   if (int rc = roll_dis_net(dyn_sizes, dyn_n_sizes, dyn)) return rc;
   const int n = dyn.dout(), m = dyn.din() - n;
   if (!roll_dis_args_ok(dyn, obs, act, P, H, K, dyn_params, dyn_tr, dyn_act, dyn_flags, err_out)) return fail(MJX_ERR_ARG, "bad arguments");
-  ChainShape ps;
-  const bool served = env_flag("MJX_ROLLOUT_DISAGREE_MFMA", true) && plan_shape(dyn, m, ps);     // (read per call: A/B runs in one process)
-  if (P == 0 || H <= 1) { if (route_out) *route_out = served ? 1 : 0; return MJX_OK; }
+  // (the switches are read per call: A/B runs in one process; MJX_ROLLOUT_DISAGREE_MFMA=0 means no MFMA route at all)
+  ChainShape ps; size_t wide_bytes = 0;
+  const bool mfma = env_flag("MJX_ROLLOUT_DISAGREE_MFMA", true);
+  const bool served2 = wide && env_flag("MJX_ROLLOUT_DISAGREE_WIDE", true) && mfma && wide_rows_shape(dyn, nullptr, wide_bytes);
+  const bool served1 = mfma && plan_shape(dyn, m, ps);
+  auto done = [&](int route) { if (route_out) *route_out = route; return MJX_OK; };
+  if (P == 0 || H <= 1) return done(served2 ? 2 : served1 ? 1 : 0);
   MJX_DEVICE_ENTRY();
   hipStream_t st = (hipStream_t)stream;
   const int64_t rows = P * H, R = P * (H - 1);
   const int din = n + m;
-  // one block serves both routes: member means (K x R) on route 1, [s, a] rows and predictions (R x din, K x R x n) on route 0
+  // one block serves every route: member means (K x R) on routes 1 and 2, [s, a] rows and predictions (R x din, K x R x n) on route 0
   float* scr = nullptr;
   if (int rc = dev_scratch(SITE_ROLLOUT_DISAGREE, stream, (size_t)R * (din + (size_t)K * n) * sizeof(float), &scr)) return rc;
-  if (served) {
-    const RollDisArgs a{obs, act, dyn_params, dyn_tr, scr, rows, dyn.P, H, n, m, dyn.sz[1], dyn.sz[2], dyn_act, dyn_flags};
+  const RollDisArgs a{obs, act, dyn_params, dyn_tr, scr, rows, dyn.P, H, n, m, dyn.sz[1], dyn.sz[2], dyn_act, dyn_flags};
+  int route = 0;
+  bool launched;
+  if (served2) {
+    if (int rc = launch_chained(k_rollout_disagree_wide<RW_NS>, wide_bytes, tile_grid(rows, 32 * RW_NS, K), a, st, launched, dim3(DFE_THREADS))) return rc;
+    if (launched) route = 2;
+  }
+  if (!route && served1) {
     // as mjx_path_rewards: a wave owns tiles of 32 rows, one workgroup per CU holds the image, the K members share the CUs
-    const int64_t groups = (rows + 127) / 128, cap = (cu_count() + K - 1) / K;
-    bool launched;
-    if (int rc = launch_chained(roll_dis_kernel(ps.HB, ps.NB), ps.bytes, dim3((unsigned)(groups < cap ? groups : cap), (unsigned)K), a, st, launched)) return rc;
-    if (launched) {
-      hipLaunchKernelGGL(k_rd_max, dim3(capped_grid(R, 256, 4096)), dim3(256), 0, st, scr, K, R, err_out);
-      HIPCHK(hipGetLastError());
-      if (route_out) *route_out = 1;
-      return MJX_OK;
-    }
+    if (int rc = launch_chained(roll_dis_kernel(ps.HB, ps.NB), ps.bytes, tile_grid(rows, 128, K), a, st, launched)) return rc;
+    if (launched) route = 1;
+  }
+  if (route) {                                              // the members' means lie in scratch: their maximum, in member order
+    hipLaunchKernelGGL(k_rd_max, dim3(capped_grid(R, 256, 4096)), dim3(256), 0, st, scr, K, R, err_out);
+    HIPCHK(hipGetLastError());
+    return done(route);
   }
   // generic route: mjx_dyn_forward's kernel over the gathered [s, a] rows (shared by the members), then mjx_dyn_pred_error's arithmetic
   float* X = scr; float* pred = X + R * din;
@@ -819,8 +823,13 @@ int mjx_rollout_disagreement(const float* obs, const float* act, int64_t P, int 
   hipLaunchKernelGGL(k_dyn_forward, dim3((unsigned)((R + DYN_FT - 1) / DYN_FT), (unsigned)K), dim3(256), bytes, st, fa);
   hipLaunchKernelGGL(k_rd_reduce, dim3(capped_grid(R, 256, 4096)), dim3(256), 0, st, pred, obs, K, R, H, n, err_out);
   HIPCHK(hipGetLastError());
-  if (route_out) *route_out = 0;
-  return MJX_OK;
+  return done(0);
+}
+
+int mjx_rollout_disagreement(const float* obs, const float* act, int64_t P, int H, int K, const int* dyn_sizes, int dyn_n_sizes,
+                             const float* dyn_params, const float* dyn_tr, int dyn_act, int dyn_flags, float* err_out, int* route_out,
+                             void* stream) {
+  return rollout_disagreement(false, obs, act, P, H, K, dyn_sizes, dyn_n_sizes, dyn_params, dyn_tr, dyn_act, dyn_flags, err_out, route_out, stream);
 }
 
 // the same for nets up to 256 wide (csrc/rows_wide.h)
@@ -834,32 +843,7 @@ int mjx_rollout_disagreement_wide_route(const int* dyn_sizes, int dyn_n_sizes) {
 int mjx_rollout_disagreement_wide(const float* obs, const float* act, int64_t P, int H, int K, const int* dyn_sizes, int dyn_n_sizes,
                                   const float* dyn_params, const float* dyn_tr, int dyn_act, int dyn_flags, float* err_out, int* route_out,
                                   void* stream) {
-  DynNet dyn;
-  if (int rc = roll_dis_net(dyn_sizes, dyn_n_sizes, dyn)) return rc;
-  if (!roll_dis_args_ok(dyn, obs, act, P, H, K, dyn_params, dyn_tr, dyn_act, dyn_flags, err_out)) return fail(MJX_ERR_ARG, "bad arguments");
-  size_t bytes = 0;
-  // (both switches read per call: A/B runs in one process; MJX_ROLLOUT_DISAGREE_MFMA=0 means no MFMA route at all)
-  const bool served = env_flag("MJX_ROLLOUT_DISAGREE_WIDE", true) && env_flag("MJX_ROLLOUT_DISAGREE_MFMA", true) && wide_rows_shape(dyn, nullptr, bytes);
-  if (served) {
-    if (P == 0 || H <= 1) { if (route_out) *route_out = 2; return MJX_OK; }
-    MJX_DEVICE_ENTRY();
-    hipStream_t st = (hipStream_t)stream;
-    const int n = dyn.dout(), m = dyn.din() - n;
-    const int64_t rows = P * H, R = P * (H - 1);
-    // mjx_rollout_disagreement's block of its scratch site, at its size: the member means (K x R) lie at its start
-    float* scr = nullptr;
-    if (int rc = dev_scratch(SITE_ROLLOUT_DISAGREE, stream, (size_t)R * (n + m + (size_t)K * n) * sizeof(float), &scr)) return rc;
-    const RollDisArgs a{obs, act, dyn_params, dyn_tr, scr, rows, dyn.P, H, n, m, dyn.sz[1], dyn.sz[2], dyn_act, dyn_flags};
-    bool launched;
-    if (int rc = launch_chained(k_rollout_disagree_wide<RW_NS>, bytes, wide_rows_grid(rows, K), a, st, launched, dim3(DFE_THREADS))) return rc;
-    if (launched) {
-      hipLaunchKernelGGL(k_rd_max, dim3(capped_grid(R, 256, 4096)), dim3(256), 0, st, scr, K, R, err_out);
-      HIPCHK(hipGetLastError());
-      if (route_out) *route_out = 2;
-      return MJX_OK;
-    }
-  }
-  return mjx_rollout_disagreement(obs, act, P, H, K, dyn_sizes, dyn_n_sizes, dyn_params, dyn_tr, dyn_act, dyn_flags, err_out, route_out, stream);
+  return rollout_disagreement(true, obs, act, P, H, K, dyn_sizes, dyn_n_sizes, dyn_params, dyn_tr, dyn_act, dyn_flags, err_out, route_out, stream);
 }
 
 int mjx_rollout_pack(const float* obs, const float* act, const float* rew32, const double* rew64, const float* err, int64_t P, int H, int n,

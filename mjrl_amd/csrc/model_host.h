@@ -64,7 +64,7 @@ inline int launch_chained(void (*kern)(Args), size_t lds_bytes, dim3 grid, const
 inline bool plan_shape(const DynNet& net, int m, ChainShape& ps) {
   if (net.nl != 3) return false;
   const int n = net.dout(), h1 = net.sz[1], h2 = net.sz[2];
-  if (h1 % 32 || h2 % 32 || h1 > 128 || h2 > 128 || n > 64 || plan_pad8(m) > PLAN_MAX_M8) return false;
+  if (h1 % 32 || h2 % 32 || h1 > 128 || h2 > 128 || n > 64 || pad8(m) > PLAN_MAX_M8) return false;
   ps.HB = (h1 > h2 ? h1 : h2) / 32; ps.NB = (n + 31) / 32;
   ps.bytes = sizeof(float) * plan_lds_floats(ps.HB, ps.NB, n, m);
   return ps.bytes <= LDS_MAX;
@@ -98,15 +98,28 @@ inline PolRollKernel pol_roll_kernel(int HB, int NB) {
                                           {k_policy_rollout<3, 1>, k_policy_rollout<3, 2>}, {k_policy_rollout<4, 1>, k_policy_rollout<4, 2>}};
   return tab[HB - 1][NB - 1];
 }
-// ---- wide policy rollout.  What k_policy_rollout_wide (policy_rollout_wide.h) serves: both nets with exactly two hidden layers,
-// every hidden width 1 .. 256, n <= 64, m <= 64, n + m <= 128, and its LDS layout (the kernel has no static LDS) within LDS_MAX.
-// It does not ask what pol_roll_shape answers: the shapes the chained kernel takes are served as well.  MJX_POLICY_ROLLOUT_WIDE=0
-// or MJX_POLICY_ROLLOUT_MFMA=0 (read per call by mjx_policy_rollout_wide): mjx_policy_rollout.
-inline bool wide_roll_shape(const DynNet& dyn, const DynNet& pol, size_t& bytes) {
-  if (dyn.nl != 3 || pol.nl != 3) return false;
+// ---- the wide LDS-tile kernels (dfe_tiles.h: policy_rollout_wide.h, rows_wide.h).  A wide kernel takes the dynamics net and the
+// net beside it (a policy or a reward net; null: none): exactly two hidden layers each, every hidden width 1 .. 256, n <= 64,
+// m <= 64, n + m <= 128.  Plain arithmetic; each kernel adds the bytes of its own LDS layout.
+inline bool wide_nets_ok(const DynNet& dyn, const DynNet* other) {
+  if (dyn.nl != 3 || (other && other->nl != 3)) return false;
   const int n = dyn.dout(), m = dyn.din() - n;
-  for (int l = 1; l <= 2; ++l) if (dyn.sz[l] > PRW_MAXH || pol.sz[l] > PRW_MAXH) return false;
-  if (n > PRW_MAXN || m > PRW_MAXM || n + m > PRW_MAXIN) return false;
+  for (int l = 1; l <= 2; ++l) if (dyn.sz[l] > WIDE_MAXH || (other && other->sz[l] > WIDE_MAXH)) return false;
+  return n <= WIDE_MAXN && m <= WIDE_MAXM && n + m <= WIDE_MAXIN;
+}
+// The grid of the kernels that walk tiles of stored rows: a workgroup per tile_rows rows up to one workgroup per CU, the K members
+// (gridDim.y) sharing the CUs
+inline dim3 tile_grid(int64_t rows, int tile_rows, int K) {
+  const int64_t tiles = (rows + tile_rows - 1) / tile_rows, cap = (cu_count() + K - 1) / K;
+  return dim3((unsigned)(tiles < cap ? tiles : cap), (unsigned)K);
+}
+// ---- wide policy rollout.  What k_policy_rollout_wide (policy_rollout_wide.h) serves: nets as wide_nets_ok takes them and its LDS
+// layout (the kernel has no static LDS) within LDS_MAX.  It does not ask what pol_roll_shape answers: the shapes the chained
+// kernel takes are served as well.  MJX_POLICY_ROLLOUT_WIDE=0 or MJX_POLICY_ROLLOUT_MFMA=0 (read per call by
+// mjx_policy_rollout_wide): mjx_policy_rollout's routes.
+inline bool wide_roll_shape(const DynNet& dyn, const DynNet& pol, size_t& bytes) {
+  if (!wide_nets_ok(dyn, &pol)) return false;
+  const int n = dyn.dout(), m = dyn.din() - n;
   bytes = sizeof(float) * wide_roll_lds_floats(n, m, dyn.sz[1], dyn.sz[2], pol.sz[1], pol.sz[2]);
   return bytes <= LDS_MAX;
 }
@@ -193,22 +206,15 @@ inline bool path_rew_args_ok(const DynNet& dyn, const DynNet& rew, const float* 
 }
 
 // ---- the wide passes over stored rollouts.  What k_rollout_disagree_wide (rew null) and k_path_rewards_wide (rows_wide.h) serve:
-// every net given with exactly two hidden layers, every hidden width 1 .. 256, n <= 64, m <= 64, n + m <= 128, and the LDS layout
-// (the kernels have no static LDS) within LDS_MAX.  They do not ask what plan_shape / path_rew_shape answer: the shapes the chained
-// kernels take are served as well.  MJX_ROLLOUT_DISAGREE_WIDE=0 / MJX_PATH_REWARDS_WIDE=0 or the matching ..._MFMA=0 (read per call
-// by mjx_rollout_disagreement_wide / mjx_path_rewards_wide): the narrow entry.
+// nets as wide_nets_ok takes them and the LDS layout (the kernels have no static LDS) within LDS_MAX.  They do not ask what
+// plan_shape / path_rew_shape answer: the shapes the chained kernels take are served as well.  MJX_ROLLOUT_DISAGREE_WIDE=0 /
+// MJX_PATH_REWARDS_WIDE=0 or the matching ..._MFMA=0 (read per call by mjx_rollout_disagreement_wide / mjx_path_rewards_wide): the
+// narrow entry's routes.
 inline bool wide_rows_shape(const DynNet& dyn, const DynNet* rew, size_t& bytes) {
-  if (dyn.nl != 3 || (rew && rew->nl != 3)) return false;
+  if (!wide_nets_ok(dyn, rew)) return false;
   const int n = dyn.dout(), m = dyn.din() - n;
-  for (int l = 1; l <= 2; ++l) if (dyn.sz[l] > RW_MAXH || (rew && rew->sz[l] > RW_MAXH)) return false;
-  if (n > RW_MAXN || m > RW_MAXM || n + m > RW_MAXIN) return false;
   bytes = sizeof(float) * rows_wide_lds_floats(n, m, dyn.sz[1], dyn.sz[2], rew ? rew->sz[1] : 0, rew ? rew->sz[2] : 0);
   return bytes <= LDS_MAX;
-}
-// the grid of both: a workgroup per tile of 32 RW_NS rows up to one workgroup per CU, the K members sharing the CUs
-inline dim3 wide_rows_grid(int64_t rows, int K) {
-  const int64_t tiles = (rows + 32 * RW_NS - 1) / (32 * RW_NS), cap = (cu_count() + K - 1) / K;
-  return dim3((unsigned)(tiles < cap ? tiles : cap), (unsigned)K);
 }
 
 // ---- dynamics fit.  k_dyn_fit, the persistent trainer, serves hidden widths <= 128 at minibatches <= 64 (shape) whose activations fit in LDS beside

@@ -44,7 +44,7 @@ struct PathRewArgs {
 };
 
 __host__ __device__ inline size_t path_rew_lds_floats(int g1, int g2, int n, int m) {
-  const size_t R1 = 32 * (size_t)((g1 + 31) / 32), R2 = 32 * (size_t)((g2 + 31) / 32), K1r = 2 * (size_t)plan_pad8(n) + plan_pad8(m);
+  const size_t R1 = 32 * (size_t)((g1 + 31) / 32), R2 = 32 * (size_t)((g2 + 31) / 32), K1r = 2 * (size_t)pad8(n) + pad8(m);
   return R1 * (K1r + 4) + R2 * (R1 + 4) + R1 + 2 * R2 + 2 * K1r + 4;
 }
 

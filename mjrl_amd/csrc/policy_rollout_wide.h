@@ -43,21 +43,19 @@
 
 namespace mjx {
 
-constexpr int PRW_MAXH = 256, PRW_MAXN = 64, PRW_MAXM = 64, PRW_MAXIN = 128;
 constexpr int PRW_ST = 32 + 4;                              // floats a tile row
-__host__ __device__ constexpr int prw_pad8(int d) { return (d + 7) & ~7; }
 // rows of the region the policy and the dynamics forward take in turn
 __host__ __device__ constexpr int prw_shared_rows(int n, int m, int h1, int h2, int p1, int p2) {
-  return dfe_pad32(h1) + dfe_pad32(h2) + dfe_pad32(n) > prw_pad8(n) + dfe_pad32(p1) + dfe_pad32(p2) + dfe_pad32(m)
+  return dfe_pad32(h1) + dfe_pad32(h2) + dfe_pad32(n) > pad8(n) + dfe_pad32(p1) + dfe_pad32(p2) + dfe_pad32(m)
              ? dfe_pad32(h1) + dfe_pad32(h2) + dfe_pad32(n)
-             : prw_pad8(n) + dfe_pad32(p1) + dfe_pad32(p2) + dfe_pad32(m);
+             : pad8(n) + dfe_pad32(p1) + dfe_pad32(p2) + dfe_pad32(m);
 }
 // floats of the small vectors staged once: the policy's b1, b2, b3, exp(log_std) and transforms, the member's b1, b2, b3 and transforms
 __host__ __device__ constexpr int prw_const_floats(int n, int m, int h1, int h2, int p1, int p2) {
   return p1 + p2 + 2 * m + (2 * n + 2 * m) + h1 + h2 + n + (2 * (n + m) + 2 * n);
 }
 __host__ __device__ constexpr size_t wide_roll_lds_floats(int n, int m, int h1, int h2, int p1, int p2) {
-  return (size_t)(n + prw_pad8(n + m) + prw_shared_rows(n, m, h1, h2, p1, p2)) * PRW_ST + prw_const_floats(n, m, h1, h2, p1, p2);
+  return (size_t)(n + pad8(n + m) + prw_shared_rows(n, m, h1, h2, p1, p2)) * PRW_ST + prw_const_floats(n, m, h1, h2, p1, p2);
 }
 
 // PolRollArgs as mjx_policy_rollout fills them (policy_rollout.h)
@@ -66,33 +64,17 @@ __global__ __launch_bounds__(DFE_THREADS) void k_policy_rollout_wide(PolRollArgs
   constexpr int ST = PRW_ST;
   const int tid = threadIdx.x, w = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, j = lane & 31, hi = lane >> 5;
   const int n = a.n, m = a.m, din = n + m, h1 = a.h1, h2 = a.h2, p1 = a.p1, p2 = a.p2;
-  const int n8 = prw_pad8(n), K0 = prw_pad8(din);
+  const int n8 = pad8(n), K0 = pad8(din);
   float* S = prw; float* XD = S + n * ST; float* U = XD + K0 * ST;
   float* XP = U; float* P1 = XP + n8 * ST; float* P2 = P1 + dfe_pad32(p1) * ST; float* PZ = P2 + dfe_pad32(p2) * ST;
   float* H1 = U; float* H2 = H1 + dfe_pad32(h1) * ST; float* Z3 = H2 + dfe_pad32(h2) * ST;
   const int k = blockIdx.y;
-  // the policy's flat vector and the member's, torch's layout
-  const float* pW1 = a.pP; const float* pb1 = pW1 + (int64_t)p1 * n; const float* pW2 = pb1 + p1; const float* pb2 = pW2 + (int64_t)p2 * p1;
-  const float* pW3 = pb2 + p2; const float* pb3 = pW3 + (int64_t)m * p2; const float* pls = pb3 + m;
-  const float* dP = a.P + k * a.Pstride;
-  const float* dW1 = dP; const float* db1 = dW1 + (int64_t)h1 * din; const float* dW2 = db1 + h1; const float* db2 = dW2 + (int64_t)h2 * h1;
-  const float* dW3 = db2 + h2; const float* db3 = dW3 + (int64_t)n * h2;
-  const float* ptr = a.ptr;                                 // [in_shift n, in_scale n, out_shift m, out_scale m]
-  const float* dtr = a.tr + (int64_t)k * (2 * din + 2 * n); // [in_shift din, in_scale din, out_shift n, out_scale n]
-  // the small vectors go to LDS once (a phase would otherwise wait a round trip to L2 for them, nine times a step); from here on
-  // these names are their copies, and sig is exp(log_std)
+  // the small vectors of the policy and of member k go to LDS once (a phase would otherwise wait a round trip to L2 for them,
+  // nine times a step); pol.tail is exp(log_std)
   float* cst = U + prw_shared_rows(n, m, h1, h2, p1, p2) * ST;
-  auto stage = [&](const float* src, int count, bool exponent) -> const float* {
-    float* dst = cst;
-    for (int e = tid; e < count; e += DFE_THREADS) dst[e] = exponent ? expf(src[e]) : src[e];
-    cst += count;
-    return dst;
-  };
-  pb1 = stage(pb1, p1, false); pb2 = stage(pb2, p2, false); pb3 = stage(pb3, m, false);
-  const float* sig = stage(pls, m, true);
-  ptr = stage(ptr, 2 * n + 2 * m, false);
-  db1 = stage(db1, h1, false); db2 = stage(db2, h2, false); db3 = stage(db3, n, false);
-  dtr = stage(dtr, 2 * din + 2 * n, false);
+  const WideNet pol = dfe_stage_net(cst, a.pP, a.ptr, n, p1, p2, m, DYN_ACT_TANH, m, tid);
+  const WideNet dyn = dfe_stage_net(cst, a.P + k * a.Pstride, a.tr + (int64_t)k * (2 * din + 2 * n), din, h1, h2, n, a.act, 0, tid);
+  const float* ptr = pol.tr; const float* sig = pol.tail; const float* dtr = dyn.tr;
   // a thread's elements of a [rows][32] block: e = tid + DFE_THREADS q is row e / 32, sample column tid % 32
   const int c = tid & 31, u0 = tid >> 5;
   constexpr int UQ = DFE_THREADS / 32;                      // rows between a thread's elements
@@ -104,7 +86,7 @@ __global__ __launch_bounds__(DFE_THREADS) void k_policy_rollout_wide(PolRollArgs
   const bool noisy = a.noise != nullptr;
   const float* __restrict__ zrow = noisy ? a.noise + ((int64_t)k * a.noise_k * a.N + vrow) * m : nullptr;
   const int64_t zstep = a.N * (int64_t)m;
-  constexpr int NZ = PRW_MAXM / UQ;                          // actions a thread forms (m <= 64)
+  constexpr int NZ = WIDE_MAXM / UQ;                         // actions a thread forms (m <= 64)
   float nz[NZ];
 #pragma unroll
   for (int q = 0; q < NZ; ++q) { const int f = u0 + UQ * q; nz[q] = (noisy && valid && f < m) ? zrow[f] : 0.f; }
@@ -125,12 +107,7 @@ __global__ __launch_bounds__(DFE_THREADS) void k_policy_rollout_wide(PolRollArgs
     }
     __syncthreads();
     // ---- the policy mean
-    dfe_forward<true>(pW1, pb1, p1, n, n8, n % 4 == 0, [&](int r, int cc) { return XP[r * ST + cc]; }, P1, ST, 1, DYN_ACT_TANH, w, j, hi);
-    __syncthreads();
-    dfe_forward<true>(pW2, pb2, p2, p1, prw_pad8(p1), p1 % 4 == 0, [&](int r, int cc) { return P1[r * ST + cc]; }, P2, ST, 1, DYN_ACT_TANH, w, j, hi);
-    __syncthreads();
-    dfe_forward<true>(pW3, pb3, m, p2, prw_pad8(p2), p2 % 4 == 0, [&](int r, int cc) { return P2[r * ST + cc]; }, PZ, ST, 1, -1, w, j, hi);
-    __syncthreads();
+    dfe_forward3<1>(pol, XP, P1, P2, PZ, w, j, hi);
     // ---- actions[:, t]: out * out_scale + out_shift, + noise * exp(log_std), clamp; the action rows of the dynamics input
 #pragma unroll
     for (int q = 0; q < NZ; ++q) {
@@ -150,19 +127,11 @@ __global__ __launch_bounds__(DFE_THREADS) void k_policy_rollout_wide(PolRollArgs
     }
     __syncthreads();
     // ---- the dynamics forward of member k
-    dfe_forward<true>(dW1, db1, h1, din, K0, din % 4 == 0, [&](int r, int cc) { return XD[r * ST + cc]; }, H1, ST, 1, a.act, w, j, hi);
-    __syncthreads();
-    dfe_forward<true>(dW2, db2, h2, h1, prw_pad8(h1), h1 % 4 == 0, [&](int r, int cc) { return H1[r * ST + cc]; }, H2, ST, 1, a.act, w, j, hi);
-    __syncthreads();
-    dfe_forward<true>(dW3, db3, n, h2, prw_pad8(h2), h2 % 4 == 0, [&](int r, int cc) { return H2[r * ST + cc]; }, Z3, ST, 1, -1, w, j, hi);
-    __syncthreads();
+    dfe_forward3<1>(dyn, XD, H1, H2, Z3, w, j, hi);
     // ---- flags and the state clamp: the next state over S (element (i, c) belongs to the thread that reads it next)
     const float* osh = dtr + 2 * din; const float* osc = osh + n;
     for (int i = u0; i < n; i += UQ) {
-      float z = Z3[i * ST + c];
-      if (a.flags & DYN_OUT_AFFINE) z = z * (osc[i] + 1e-8f) + osh[i];
-      if (a.flags & DYN_MASK) z = z * (osc[i] >= 1e-8f ? 1.f : 0.f);
-      if (a.flags & DYN_RESIDUAL) z = z + S[i * ST + c];
+      float z = dyn_out_flags(Z3[i * ST + c], a.flags, osh, osc, i, [&] { return S[i * ST + c]; });
       if (a.s_lo) z = dyn_clamp(z, a.s_lo[i], a.s_hi[i]);
       S[i * ST + c] = z;
     }

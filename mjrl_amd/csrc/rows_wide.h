@@ -9,7 +9,8 @@
 //   k_path_rewards_wide<NS>      k_path_rewards' quantity: r[k][row] = RewardNet_k(s, a, s') with s' = DynamicsNet_k(s, a)
 //                                recomputed and unclamped, s = member k's own observation row, a = member k's action row or the
 //                                shared one (act_stride 0).
-// Both run rw_next_state, the dynamics half, and are otherwise apart: either can be taken out without touching the other.
+// Both run rw_next_state, the dynamics half, and are otherwise apart: either can be taken out without touching the other.  The
+// shape limits, the staging of a member's small vectors, the net view (WideNet), its forward and the normaliser are dfe_tiles.h's.
 //
 // The scheme is k_policy_rollout_wide's and k_dyn_fit_ens's (dfe_tiles.h): activations as [unit][sample] LDS tiles, weights
 // streamed row-major from global memory, products on v_mfma_f32_32x32x2_f32 through dfe_forward<true>, DFE_THREADS threads.  Stored
@@ -58,17 +59,15 @@
 
 namespace mjx {
 
-constexpr int RW_MAXH = 256, RW_MAXN = 64, RW_MAXM = 64, RW_MAXIN = 128;
 #ifndef MJX_RW_NS
 #define MJX_RW_NS 2                                         // (-DMJX_RW_NS=1: the 32-row tile, for A/B builds; tools/bench_rows_wide.py)
 #endif
 constexpr int RW_NS = MJX_RW_NS;                            // sample tiles of 32 rows a workgroup's tile holds (the shipped instance)
-__host__ __device__ constexpr int rw_pad8(int d) { return (d + 7) & ~7; }
 __host__ __device__ constexpr int rw_max(int a, int b) { return a > b ? a : b; }
 // rows of the two regions; g1 = g2 = 0: the disagreement kernel, which holds no reward net
 __host__ __device__ constexpr int rw_rows_a(int n, int h1, int g1) { return rw_max(rw_max(dfe_pad32(h1), dfe_pad32(n)), dfe_pad32(g1)); }
 __host__ __device__ constexpr int rw_rows_b(int n, int m, int h2, int g1, int g2) {
-  return rw_max(rw_max(rw_pad8(n + m), dfe_pad32(h2)), g1 > 0 ? rw_max(rw_pad8(2 * n + m), dfe_pad32(g2)) : 0);
+  return rw_max(rw_max(pad8(n + m), dfe_pad32(h2)), g1 > 0 ? rw_max(pad8(2 * n + m), dfe_pad32(g2)) : 0);
 }
 // floats of the small vectors staged once: the member's b1, b2, b3 and 2 (n + m) + 2 n transforms; with a reward net its c1, c2, w3,
 // b3 and 2 (2 n + m) + 2 transforms
@@ -85,68 +84,24 @@ static_assert(rows_wide_lds_floats(11, 2, 256, 256, 0, 0, 2) == 68 * 512 + 571, 
 static_assert(rows_wide_lds_floats(17, 6, 160, 96, 33, 130, 2) == 68 * 320 + 729, "rows_wide_lds_floats");
 static_assert(rows_wide_lds_floats(1, 1, 1, 1, 0, 0, 1) == 36 * 64 + 9, "rows_wide_lds_floats");
 
-// one member's dynamics net as a workgroup reads it: the weights in global memory, the small vectors staged (LDS)
-struct RwDyn {
-  const float* W1; const float* W2; const float* W3;
-  const float* b1; const float* b2; const float* b3;
-  const float* tr;                                          // [in_shift n + m, in_scale n + m, out_shift n, out_scale n]
-  int n, m, h1, h2, act, flags;
-};
-// the next `count` floats of the staged vectors <- src; -> their LDS copy
-__device__ __forceinline__ const float* rw_stage(float*& cst, const float* __restrict__ src, int count, int tid) {
-  float* dst = cst;
-  for (int e = tid; e < count; e += DFE_THREADS) dst[e] = src[e];
-  cst += count;
-  return dst;
-}
-__device__ __forceinline__ RwDyn rw_stage_dyn(float*& cst, const float* __restrict__ P, const float* __restrict__ tr, int n, int m, int h1, int h2,
-                                              int act, int flags, int tid) {
-  const int din = n + m;
-  RwDyn d;
-  d.W1 = P; const float* b1 = d.W1 + (int64_t)h1 * din; d.W2 = b1 + h1; const float* b2 = d.W2 + (int64_t)h2 * h1;
-  d.W3 = b2 + h2; const float* b3 = d.W3 + (int64_t)n * h2;
-  d.b1 = rw_stage(cst, b1, h1, tid); d.b2 = rw_stage(cst, b2, h2, tid); d.b3 = rw_stage(cst, b3, n, tid);
-  d.tr = rw_stage(cst, tr, 2 * din + 2 * n, tid);
-  d.n = n; d.m = m; d.h1 = h1; d.h2 = h2; d.act = act; d.flags = flags;
-  return d;
-}
-
 // The dynamics half for one tile: s' of the tile's rows, unclamped, left in A's first n rows (element [c][col]).  so, sa: the
 // tile's first stored row of observations and actions (rows are contiguous); live: its rows that exist (1 .. 32 NS).  Starts by
 // writing B and ends with a barrier; what the caller last read from B lies behind a barrier of its own.
 template <int NS>
-__device__ __forceinline__ void rw_next_state(const RwDyn& d, const float* __restrict__ so, const float* __restrict__ sa, int live, float* A,
-                                              float* B, int tid, int w, int j, int hi) {
+__device__ __forceinline__ void rw_next_state(const WideNet& d, int flags, const float* __restrict__ so, const float* __restrict__ sa, int live,
+                                              float* A, float* B, int tid, int w, int j, int hi) {
   constexpr int TILE = 32 * NS, ST = TILE + 4;
-  const int n = d.n, m = d.m, din = n + m, K0 = rw_pad8(din);
+  const int n = d.dout, din = d.din, m = din - n;
   const float* tr = d.tr;
-  // element e of the tile's contiguous rows x n block is column e / n, unit e % n
-  for (int e = tid; e < TILE * n; e += DFE_THREADS) {
-    const int c = e / n, i = e - c * n;
-    const float s = c < live ? so[e] : 0.f;
-    B[i * ST + c] = (s - tr[i]) / (tr[din + i] + 1e-8f);
-  }
-  for (int e = tid; e < TILE * m; e += DFE_THREADS) {
-    const int c = e / m, f = e - c * m;
-    const float v = c < live ? sa[e] : 0.f;
-    B[(n + f) * ST + c] = (v - tr[n + f]) / (tr[din + n + f] + 1e-8f);
-  }
-  for (int e = tid; e < (K0 - din) * TILE; e += DFE_THREADS) B[(din + e / TILE) * ST + e % TILE] = 0.f;
+  dfe_norm_rows<NS>(B, 0, n, live, tr, din, tid, [&](int e, int, int) { return so[e]; });
+  dfe_norm_rows<NS>(B, n, m, live, tr, din, tid, [&](int e, int, int) { return sa[e]; });
+  dfe_zero_rows<NS>(B, din, pad8(din), tid);
   __syncthreads();
-  dfe_forward<true>(d.W1, d.b1, d.h1, din, K0, din % 4 == 0, [&](int r, int cc) { return B[r * ST + cc]; }, A, ST, NS, d.act, w, j, hi);
-  __syncthreads();
-  dfe_forward<true>(d.W2, d.b2, d.h2, d.h1, rw_pad8(d.h1), d.h1 % 4 == 0, [&](int r, int cc) { return A[r * ST + cc]; }, B, ST, NS, d.act, w, j, hi);
-  __syncthreads();
-  dfe_forward<true>(d.W3, d.b3, n, d.h2, rw_pad8(d.h2), d.h2 % 4 == 0, [&](int r, int cc) { return B[r * ST + cc]; }, A, ST, NS, -1, w, j, hi);
-  __syncthreads();
+  dfe_forward3<NS>(d, B, A, B, A, w, j, hi);
   const float* osh = tr + 2 * din; const float* osc = osh + n;
   for (int e = tid; e < TILE * n; e += DFE_THREADS) {
     const int c = e / n, i = e - c * n;
-    float z = A[i * ST + c];
-    if (d.flags & DYN_OUT_AFFINE) z = z * (osc[i] + 1e-8f) + osh[i];
-    if (d.flags & DYN_MASK) z = z * (osc[i] >= 1e-8f ? 1.f : 0.f);
-    if (d.flags & DYN_RESIDUAL) z = z + (c < live ? so[e] : 0.f);
-    A[i * ST + c] = z;
+    A[i * ST + c] = dyn_out_flags(A[i * ST + c], flags, osh, osc, i, [&] { return c < live ? so[e] : 0.f; });
   }
   __syncthreads();
 }
@@ -160,13 +115,13 @@ __global__ __launch_bounds__(DFE_THREADS) void k_rollout_disagree_wide(RollDisAr
   const int n = a.n, m = a.m, H = a.H, k = blockIdx.y;
   float* A = rwl; float* B = A + rw_rows_a(n, a.h1, 0) * ST;
   float* cst = B + rw_rows_b(n, m, a.h2, 0, 0) * ST;
-  const RwDyn d = rw_stage_dyn(cst, a.dP + k * a.dPstride, a.dtr + (int64_t)k * (2 * (n + m) + 2 * n), n, m, a.h1, a.h2, a.dact, a.flags, tid);
+  const WideNet d = dfe_stage_net(cst, a.dP + k * a.dPstride, a.dtr + (int64_t)k * (2 * (n + m) + 2 * n), n + m, a.h1, a.h2, n, a.dact, 0, tid);
   __syncthreads();                                          // (the staged vectors)
   const int64_t tiles = (a.rows + TILE - 1) / TILE, R = (a.rows / H) * (H - 1);
   for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
     const int64_t base = tile * TILE;
     const int live = a.rows - base < TILE ? (int)(a.rows - base) : TILE;
-    rw_next_state<NS>(d, a.obs + base * n, a.act + base * m, live, A, B, tid, w, j, hi);
+    rw_next_state<NS>(d, a.flags, a.obs + base * n, a.act + base * m, live, A, B, tid, w, j, hi);
     // the thread that owns a column: its row against the next stored state (the last row of a path has none: never stored)
     if (tid < live) {
       const int64_t row = base + tid, p = row / H;
@@ -191,15 +146,13 @@ __global__ __launch_bounds__(DFE_THREADS) void k_path_rewards_wide(PathRewArgs a
   extern __shared__ __attribute__((aligned(16))) float rwl[];
   constexpr int TILE = 32 * NS, ST = TILE + 4, Q = DFE_THREADS / TILE;
   const int tid = threadIdx.x, w = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, j = lane & 31, hi = lane >> 5;
-  const int n = a.n, m = a.m, din = n + m, rin = din + n, K0r = rw_pad8(rin), g1 = a.g1, g2 = a.g2, k = blockIdx.y;
+  const int n = a.n, m = a.m, din = n + m, rin = din + n, g1 = a.g1, g2 = a.g2, k = blockIdx.y;
   float* A = rwl; float* B = A + rw_rows_a(n, a.h1, g1) * ST;
   float* cst = B + rw_rows_b(n, m, a.h2, g1, g2) * ST;
-  const RwDyn d = rw_stage_dyn(cst, a.dP + k * a.dPstride, a.dtr + (int64_t)k * (2 * din + 2 * n), n, m, a.h1, a.h2, a.dact, a.flags, tid);
-  // the reward net's flat vector, torch's layout, and its transforms [in_shift rin, in_scale rin, out_shift, out_scale]
-  const float* V1 = a.rP + k * a.rPstride; const float* c1 = V1 + (int64_t)g1 * rin; const float* V2 = c1 + g1;
-  const float* c2 = V2 + (int64_t)g2 * g1; const float* w3 = c2 + g2; const float* b3 = w3 + g2;
-  c1 = rw_stage(cst, c1, g1, tid); c2 = rw_stage(cst, c2, g2, tid); w3 = rw_stage(cst, w3, g2, tid); b3 = rw_stage(cst, b3, 1, tid);
-  const float* rtr = rw_stage(cst, a.rtr + (int64_t)k * (2 * rin + 2), 2 * rin + 2, tid);
+  const WideNet d = dfe_stage_net(cst, a.dP + k * a.dPstride, a.dtr + (int64_t)k * (2 * din + 2 * n), din, a.h1, a.h2, n, a.dact, 0, tid);
+  // the reward net: its head w3 (g2 weights, d_out = 1) is staged with the biases
+  const WideNet r = dfe_stage_net<true>(cst, a.rP + k * a.rPstride, a.rtr + (int64_t)k * (2 * rin + 2), rin, g1, g2, 1, a.ract, 0, tid);
+  const float* rtr = r.tr;
   __syncthreads();                                          // (the staged vectors)
   const float* __restrict__ obase = a.obs + (int64_t)k * a.rows * n;
   const float* __restrict__ abase = a.actions + k * a.act_stride;
@@ -210,35 +163,24 @@ __global__ __launch_bounds__(DFE_THREADS) void k_path_rewards_wide(PathRewArgs a
     const int live = a.rows - base < TILE ? (int)(a.rows - base) : TILE;
     const float* __restrict__ so = obase + base * n;
     const float* __restrict__ sa = abase + base * m;
-    rw_next_state<NS>(d, so, sa, live, A, B, tid, w, j, hi);
-    // ---- XR = [s, a, s'] under the reward net's own shift and scale
-    for (int e = tid; e < TILE * n; e += DFE_THREADS) {
-      const int c = e / n, i = e - c * n;
-      const float s = c < live ? so[e] : 0.f;
-      B[i * ST + c] = (s - rtr[i]) / (rtr[rin + i] + 1e-8f);
-      B[(din + i) * ST + c] = (A[i * ST + c] - rtr[din + i]) / (rtr[rin + din + i] + 1e-8f);
-    }
-    for (int e = tid; e < TILE * m; e += DFE_THREADS) {
-      const int c = e / m, f = e - c * m;
-      const float v = c < live ? sa[e] : 0.f;
-      B[(n + f) * ST + c] = (v - rtr[n + f]) / (rtr[rin + n + f] + 1e-8f);
-    }
-    for (int e = tid; e < (K0r - rin) * TILE; e += DFE_THREADS) B[(rin + e / TILE) * ST + e % TILE] = 0.f;
+    rw_next_state<NS>(d, a.flags, so, sa, live, A, B, tid, w, j, hi);
+    // ---- XR = [s, a, s'] under the reward net's own shift and scale (s' of every column, as A holds it)
+    dfe_norm_rows<NS>(B, 0, n, live, rtr, rin, tid, [&](int e, int, int) { return so[e]; });
+    dfe_norm_rows<NS>(B, din, n, TILE, rtr, rin, tid, [&](int, int c, int i) { return A[i * ST + c]; });
+    dfe_norm_rows<NS>(B, n, m, live, rtr, rin, tid, [&](int e, int, int) { return sa[e]; });
+    dfe_zero_rows<NS>(B, rin, pad8(rin), tid);
     __syncthreads();
-    dfe_forward<true>(V1, c1, g1, rin, K0r, rin % 4 == 0, [&](int r, int cc) { return B[r * ST + cc]; }, A, ST, NS, a.ract, w, j, hi);
-    __syncthreads();
-    dfe_forward<true>(V2, c2, g2, g1, rw_pad8(g1), g1 % 4 == 0, [&](int r, int cc) { return A[r * ST + cc]; }, B, ST, NS, a.ract, w, j, hi);
-    __syncthreads();
+    dfe_forward2<NS>(r, B, A, B, w, j, hi);
     // ---- the scalar head (d_out = 1) is no MFMA: Q partial dots per column, then the column's thread adds them in order
     float dot = 0.f;
-    for (int u = q0; u < g2; u += Q) dot = fmaf(B[u * ST + col], w3[u], dot);
+    for (int u = q0; u < g2; u += Q) dot = fmaf(B[u * ST + col], r.W3[u], dot);
     A[q0 * ST + col] = dot;
     __syncthreads();
     if (tid < live) {
       float sum = A[tid];
 #pragma unroll
       for (int q = 1; q < Q; ++q) sum += A[q * ST + tid];
-      const float z = (sum + b3[0]) * (rtr[2 * rin + 1] + 1e-8f) + rtr[2 * rin];     // out * (out_scale + 1e-8) + out_shift
+      const float z = (sum + r.b3[0]) * (rtr[2 * rin + 1] + 1e-8f) + rtr[2 * rin];     // out * (out_scale + 1e-8) + out_shift
       const int64_t row = base + tid;
       if (a.r32) a.r32[(int64_t)k * a.rows + row] = z;
       if (a.r64) a.r64[(int64_t)k * a.rows + row] = (double)z;
