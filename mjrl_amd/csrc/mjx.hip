@@ -99,52 +99,7 @@ struct ForkGuardInit { ForkGuardInit() { pthread_atfork(nullptr, nullptr, atfork
 #include "fused_host.h"
 #include "model_host.h"
 #include "fit_host.h"
-
-struct mjx_ctx {
-  int device = 0;
-  int n = 0, m = 0;
-  std::vector<int> hidden;
-  int64_t d = 0;
-  int oS = 0;                      // offset of log_std in the flat vector
-  // bound inputs
-  const float *obs = nullptr, *act = nullptr, *adv = nullptr;
-  int64_t N_local = 0, N_global = 0;
-  const float *theta_new = nullptr, *theta_old = nullptr, *tr_new = nullptr, *tr_old = nullptr;
-  int old_is_new = 1;
-  bool batch_bound = false;
-  int64_t rows_bound = 0;                             // rows handed to the last mjx_bind_batch
-  // workspace (device)
-  float* ident_tr = nullptr;       // identity transforms
-  float *cg_x = nullptr, *cg_r = nullptr, *cg_p = nullptr, *cg_z = nullptr, *cg_Ap = nullptr;
-  double* cg_scal = nullptr;       // 8 doubles
-  float* dbg = nullptr;
-  long long* clk = nullptr;        // launch clock stamps (mjx_set_clock_buffer)
-  bool lw_old_ok = false;          // K1's outputs are the OLD policy's (old == new at K1; theta_old, its transform and the batch untouched since by this
-                                   // library): set by mjx_surr_vpg, cleared by the public binding calls, consumed by the one-call updates' evaluations
-                                   // (layer-wise path: reuse of the output block; fused path: the snapshot compare of K3's prologue is skipped)
-  bool prof_on = false;
-  std::vector<hipEvent_t> prof_ev;   // pairs
-  size_t prof_used = 0;
-  int prof_stride = 1;               // bracket every prof_stride-th launch
-  bool prof_iter = false;            // bracket whole CG iterations (mjx_profile_enable(ctx, -k)) instead of product launches
-  size_t prof_seen = 0;
-  void* comm = nullptr; int comm_world = 0, comm_rank = 0;   // RCCL communicator (one process per GPU)
-  mjx_reduce_fn reduce_cb = nullptr; void* reduce_user = nullptr;   // transport hook in its place (tests)
-  // peer exchange (mjx_peer_*): one uncached device buffer per rank [2 parities][world slots] | flag block, the peers' mapped
-  // through HIP IPC; every all-reduce = store the vector into slot `rank` of every buffer + raise this rank's flag at every
-  // peer, one bounded in-kernel wait on the own flags, rank-ordered sum of the local slots (vecops.h "Peer exchange")
-  struct Peer {
-    bool on = false, loopback = false; int rank = 0, world = 0;
-    char* buf = nullptr; char* map[16] = {nullptr};
-    size_t slot_bytes = 0; uint32_t seq = 0;
-    unsigned long long timeout_ticks = 500000000ull;   // 100 MHz ticks a consumer waits for a peer (MJX_PEER_TIMEOUT_MS; default 5 s)
-    int fault = 0;                                     // MJX_PEER_FAULT (tests): 1 = "slot" (vectors land in the wrong slot at the peers), 2 = "flag" (arrival flags never raised)
-  } peer;
-  unsigned* ticket = nullptr;                      // workgroup ticket of the producer kernels (ordinary device memory, zero between launches)
-  mjx::FusedWS fz;                 // fused path workspace (fz.variant != 0: it serves this context)
-  mjx::LayerwiseWS lw;             // layer-wise path workspace
-  mjx::MinibatchWS lwmb;           // launch-based minibatch trainer's workspace (mjx_policy_minibatch_adam)
-};
+#include "update_host.h"     // (defines mjx_ctx)
 
 namespace {
 
@@ -163,13 +118,6 @@ FusedArgs bound_args(const mjx_ctx* c, const float* thetaB) {
   a.dbg = c->dbg; a.clk = c->clk;
   a.n = c->n; a.m = c->m;
   return a;
-}
-
-// f(integral_constant<W>) with the compile-time rank count of the folded kernels that covers `world`: 2, 4, 8 or 16
-template <class F>
-void with_world_width(int world, F&& f) {
-  if (world <= 2) f(std::integral_constant<int, 2>{}); else if (world <= 4) f(std::integral_constant<int, 4>{});
-  else if (world <= 8) f(std::integral_constant<int, 8>{}); else f(std::integral_constant<int, 16>{});
 }
 
 int check_bound(mjx_ctx* c, bool need_act) {
@@ -207,20 +155,19 @@ int mjx_create(mjx_ctx** out, int device, int n, int m, const int* hidden, int n
   MJX_DEVICE_ENTRY();
   if (mjx_device_count() <= device) return fail(MJX_ERR_NOGPU, "HIP device %d not available", device);
   HIPCHK(hipSetDevice(device));
-  mjx_ctx* c = new mjx_ctx();
+  struct Guard { mjx_ctx* c; ~Guard() { mjx_destroy(c); } } built{new mjx_ctx()};     // any failure below takes back what was built so far
+  mjx_ctx* c = built.c;
   c->device = device; c->n = n; c->m = m;
   c->hidden.assign(hidden, hidden + n_hidden);
   int prev = n; int64_t d = 0;
-  for (int h : c->hidden) { if (h <= 0) { delete c; return fail(MJX_ERR_ARG, "bad hidden size"); } d += (int64_t)prev * h + h; prev = h; }
+  for (int h : c->hidden) { if (h <= 0) return fail(MJX_ERR_ARG, "bad hidden size"); d += (int64_t)prev * h + h; prev = h; }
   d += (int64_t)prev * m + m;
   c->oS = (int)d;
   d += m;
   c->d = d;
   if (int rc = c->fz.init(n, m, d, c->oS, c->hidden, cu_count(), env_flag("MJX_FORCE_LAYERWISE", false))) return rc;
-  HIPCHK(hipMalloc(&c->cg_x, d * 4)); HIPCHK(hipMalloc(&c->cg_r, d * 4)); HIPCHK(hipMalloc(&c->cg_p, d * 4));
-  HIPCHK(hipMalloc(&c->cg_z, d * 4)); HIPCHK(hipMalloc(&c->cg_Ap, d * 4));
-  HIPCHK(hipMalloc((void**)&c->ticket, 256)); HIPCHK(hipMemset(c->ticket, 0, 256));
-  HIPCHK(hipMalloc(&c->cg_scal, 8 * sizeof(double)));
+  if (int rc = c->cg.alloc(d)) return rc;
+  c->tp.init(device, d, c->cg.ticket);
   std::vector<float> id(2 * n + 2 * m, 0.f);
   for (int i = 0; i < n; ++i) id[n + i] = 1.f;
   for (int i = 0; i < m; ++i) id[2 * n + m + i] = 1.f;
@@ -229,20 +176,22 @@ int mjx_create(mjx_ctx** out, int device, int n, int m, const int* hidden, int n
   HIPCHK(hipMemset(c->fz.spartials, 0, c->fz.spartials_bytes()));
   c->lw.init(n, m, c->hidden);
   c->lwmb.lw.init(n, m, c->hidden);
+  built.c = nullptr;
   *out = c;
   return MJX_OK;
 }
 
+// (a half-built context too: every owner releases what it has, null pointers included)
 void mjx_destroy(mjx_ctx* c) {
   if (!c) return;
   (void)hipSetDevice(c->device);
-  (void)mjx_comm_destroy(c);
+  c->tp.detach();
   c->lw.release();
   c->lwmb.release();
-  for (auto& e : c->prof_ev) hipEventDestroy(e);
+  c->prof.release();
   c->fz.release();
   hipFree(c->ident_tr);
-  hipFree(c->cg_x); hipFree(c->cg_r); hipFree(c->cg_p); hipFree(c->cg_z); hipFree(c->cg_Ap); hipFree(c->ticket); hipFree(c->cg_scal);
+  c->cg.release();
   delete c;
 }
 
@@ -302,10 +251,12 @@ int mjx_bind_rows(mjx_ctx* c, int64_t N_local, int64_t N_global, const float* ad
   return MJX_OK;
 }
 
+}  // extern "C"
+namespace {
 // keep_old_outputs: the one-call updates re-bind (stepped parameters, the SAME old parameters) between their K1 and their
 // evaluations -- the old policy's cached outputs stay usable; a caller's own binding may come with new contents under the same pointers
-static int bind_policy_impl(mjx_ctx* c, const float* theta_new, const float* theta_old, const float* tr_new,
-                            const float* tr_old, int old_is_new, bool keep_old_outputs) {
+int bind_policy_impl(mjx_ctx* c, const float* theta_new, const float* theta_old, const float* tr_new, const float* tr_old, int old_is_new,
+                     bool keep_old_outputs) {
   if (!c || !theta_new || !theta_old) return fail(MJX_ERR_ARG, "bad policy");
   if (c && !(keep_old_outputs && theta_old == c->theta_old && tr_old == c->tr_old && tr_new == c->tr_new)) c->lw_old_ok = false;
   if ((((uintptr_t)theta_new) | ((uintptr_t)theta_old)) & 15) return fail(MJX_ERR_ARG, "parameter vectors must be 16-byte aligned");
@@ -315,6 +266,9 @@ static int bind_policy_impl(mjx_ctx* c, const float* theta_new, const float* the
   c->fz.on_policy();
   return MJX_OK;
 }
+}  // namespace
+extern "C" {
+
 int mjx_bind_policy(mjx_ctx* c, const float* theta_new, const float* theta_old, const float* tr_new, const float* tr_old, int old_is_new) {
   return bind_policy_impl(c, theta_new, theta_old, tr_new, tr_old, old_is_new, false);
 }
@@ -1049,42 +1003,27 @@ int mjx_dyn_pred_error(const float* pred, int K, int64_t rows, int n, const floa
 int mjx_profile_enable(mjx_ctx* c, int on) {
   if (!c) return fail(MJX_ERR_ARG, "null context");
   HIPCHK(hipSetDevice(c->device));
-  if (on && c->prof_ev.empty()) {
-    c->prof_ev.resize(2 * 2048);
-    for (auto& e : c->prof_ev) HIPCHK(hipEventCreate(&e));
-  }
-  c->prof_on = on != 0;
-  c->prof_iter = on < 0;                       // on = -k: every k-th CG ITERATION (product, reduction / exchange, vector update) instead of the product alone
-  if (on) { c->prof_used = 0; c->prof_seen = 0; c->prof_stride = on < 0 ? -on : on; }
-  return MJX_OK;
+  return c->prof.enable(on);
 }
 
 int mjx_profile_read(mjx_ctx* c, double* out) {
   if (!c || !out) return fail(MJX_ERR_ARG, "bad arguments");
   HIPCHK(hipSetDevice(c->device));
-  double tot = 0.0;
-  for (size_t i = 0; i + 1 < c->prof_used; i += 2) {
-    HIPCHK(hipEventSynchronize(c->prof_ev[i + 1]));
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, c->prof_ev[i], c->prof_ev[i + 1]));
+  double tot = 0.0, ms = 0.0;
+  for (size_t i = 0; i < c->prof.used; ++i) {
+    if (int rc = c->prof.elapsed(i, &ms)) return rc;
     tot += ms;
   }
-  out[0] = tot; out[1] = (double)(c->prof_used / 2);
+  out[0] = tot; out[1] = (double)c->prof.used;
   return MJX_OK;
 }
 
 int mjx_profile_samples(mjx_ctx* c, double* ms_out_host, int cap, int* count_out) {
   if (!c || !count_out || (cap > 0 && !ms_out_host)) return fail(MJX_ERR_ARG, "bad arguments");
   HIPCHK(hipSetDevice(c->device));
-  int n = 0;
-  for (size_t i = 0; i + 1 < c->prof_used; i += 2, ++n) {
-    if (n >= cap) continue;
-    HIPCHK(hipEventSynchronize(c->prof_ev[i + 1]));
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, c->prof_ev[i], c->prof_ev[i + 1]));
-    ms_out_host[n] = (double)ms;
-  }
-  *count_out = n;
+  for (size_t i = 0; i < c->prof.used && (int64_t)i < cap; ++i)
+    if (int rc = c->prof.elapsed(i, ms_out_host + i)) return rc;
+  *count_out = (int)c->prof.used;
   return MJX_OK;
 }
 
@@ -1105,9 +1044,12 @@ int mjx_set_clock_buffer(mjx_ctx* c, int64_t* clk) {
   return MJX_OK;
 }
 
+}  // extern "C"
+namespace {
+// K1, the Fisher-vector product and K3 on the bound inputs, declared in update_host.h for the solve and the updates.
 // pp (peer exchange): the gradient's reduction kernel writes this rank's slot (grad_out IS that slot) into every peer's buffer,
 // K1's 4 sums travel with it at byte scal_off of the slot (scal_out: that place in the own slot), one arrival flag for both
-static int surr_vpg_impl(mjx_ctx* c, float* grad_out, double* scal_out, void* stream, const PeerPush* pp, int scal_off) {
+int surr_vpg_impl(mjx_ctx* c, float* grad_out, double* scal_out, void* stream, const PeerPush* pp, int scal_off) {
   if (int rc = check_bound(c, true)) return rc;
   if (!grad_out || !scal_out) return fail(MJX_ERR_ARG, "null output");
   hipStream_t st = (hipStream_t)stream;
@@ -1124,10 +1066,8 @@ static int surr_vpg_impl(mjx_ctx* c, float* grad_out, double* scal_out, void* st
   return MJX_OK;
 }
 
-int mjx_surr_vpg(mjx_ctx* c, float* grad_out, double* scal_out, void* stream) { return surr_vpg_impl(c, grad_out, scal_out, stream, nullptr, -1); }
-
 // pp: peer exchange folded into the reduction kernel (fused kernels with d % 4 == 0 only; `out` is then this rank's slot)
-static int fvp_impl(mjx_ctx* c, const float* v, float* out, void* stream, const PeerPush* pp) {
+int fvp_impl(mjx_ctx* c, const float* v, float* out, void* stream, const PeerPush* pp) {
   if (int rc = check_bound(c, false)) return rc;
   if (!v || !out) return fail(MJX_ERR_ARG, "null vector");
   if (c->fz.variant && (((uintptr_t)v) & 15)) return fail(MJX_ERR_ARG, "v must be 16-byte aligned (fused path)");   // (the layer-wise path takes any 4-byte aligned v)
@@ -1140,21 +1080,19 @@ static int fvp_impl(mjx_ctx* c, const float* v, float* out, void* stream, const 
     int rc = c->lw.hvp_general(c->obs, c->N_local, c->N_global, c->theta_new, c->theta_old, tr_new_or_ident(c), tr_old_or_ident(c), v, out, st);
     return rc ? fail(MJX_ERR_STATE, "general Hessian-vector product failed (%d)", rc) : MJX_OK;
   }
-  const bool prof = c->prof_on && !c->prof_iter && (c->prof_seen++ % (size_t)c->prof_stride == 0) && c->prof_used + 2 <= c->prof_ev.size();
-  if (prof) HIPCHK(hipEventRecord(c->prof_ev[c->prof_used], st));
+  int pair;
+  if (int rc = c->prof.begin(ProfPick::PRODUCT, false, st, &pair)) return rc;
   // (the bracket closes behind the product itself: the fused path's reduction of the partials stays outside it)
-  auto prof_end = [&]() -> int { if (prof) { HIPCHK(hipEventRecord(c->prof_ev[c->prof_used + 1], st)); c->prof_used += 2; } return MJX_OK; };
+  auto prof_end = [&]() -> int { return c->prof.end(pair, st); };
   if (c->fz.variant) return c->fz.fvp(bound_args(c, v), out, (float)((double)c->N_local / (double)c->N_global), pp, st, prof_end);
   const int rc = c->lw.fvp(c->obs, c->N_local, c->N_global, c->theta_new, tr_new_or_ident(c), v, out, st);
   if (int e = prof_end()) return e;
   return rc ? fail(MJX_ERR_STATE, "layer-wise fvp failed") : MJX_OK;
 }
 
-int mjx_fvp(mjx_ctx* c, const float* v, float* out, void* stream) { return fvp_impl(c, v, out, stream, nullptr); }
-
 // pp (peer exchange): the reduction of K3's sums writes them into slot `rank` of every buffer (scal_out IS the own slot) and raises
 // the flags; the caller launches the consumer (k_peer_sum<double>)
-static int eval_impl(mjx_ctx* c, double* scal_out, void* stream, const PeerPush* pp, bool old_ok = false) {
+int eval_impl(mjx_ctx* c, double* scal_out, void* stream, const PeerPush* pp, bool old_ok) {
   if (int rc = check_bound(c, true)) return rc;
   if (!scal_out) return fail(MJX_ERR_ARG, "null output");
   hipStream_t st = (hipStream_t)stream;
@@ -1165,238 +1103,37 @@ static int eval_impl(mjx_ctx* c, double* scal_out, void* stream, const PeerPush*
                     old_ok && c->lw_old_ok, c->old_is_new != 0)
              ? fail(MJX_ERR_STATE, "layer-wise eval failed") : MJX_OK;
 }
-
-int mjx_eval_surr_kl(mjx_ctx* c, double* scal_out, void* stream) { return eval_impl(c, scal_out, stream, nullptr); }
-
-// ---------------------------------------------------------------------------- peer exchange (HIP IPC + stream memory operations)
-namespace {
-bool has_ranks(const mjx_ctx* c) { return c->comm || c->reduce_cb || c->peer.on; }
-// slot `r` (the vector rank r contributed) of parity `par` in rank q's buffer; the arrival counter and the producers' ticket
-char* peer_slot(const mjx_ctx* c, int q, int par, int r) { return c->peer.map[q] + (size_t)(par * c->peer.world + r) * c->peer.slot_bytes; }
-// the flag block behind the slots of rank q's buffer: [0..15] one arrival flag per SOURCE rank (32-bit exchange numbers),
-// [32] timed-out waits of this rank's consumers (mjx_peer_status); a slot of zeros follows at +256
-unsigned* peer_flags(const mjx_ctx* c, int q) { return (unsigned*)(c->peer.map[q] + (size_t)2 * c->peer.world * c->peer.slot_bytes); }
-PeerPush peer_push(const mjx_ctx* c, int par, uint32_t seq) {
-  PeerPush pp{};
-  pp.world = c->peer.world; pp.rank = c->peer.rank; pp.seq = seq;
-  pp.ticket = c->ticket;
-  for (int q = 0; q < c->peer.world; ++q) {
-    pp.dst[q] = peer_slot(c, q, par, c->peer.rank);
-    // the flag rank q polls for this rank; loop-back rehearsal (every peer is the own buffer): the flag this rank polls for "peer" q
-    pp.flag[q] = c->peer.loopback ? peer_flags(c, c->peer.rank) + q : peer_flags(c, q) + c->peer.rank;
-    // fault injection (MJX_PEER_FAULT, tests/test_gpu_multirank.py): what a mis-mapped buffer or a lost flag store would look like
-    // to the known-answer sum the host runs before it trusts a transport (engine._transport_self_test)
-    if (q != c->peer.rank && c->peer.fault == 1) pp.dst[q] = peer_slot(c, q, par, (c->peer.rank + 1) % c->peer.world);
-    if (q != c->peer.rank && c->peer.fault == 2) pp.flag[q] = peer_flags(c, c->peer.rank) + 40;     // an unused word of the OWN flag block
-  }
-  return pp;
-}
-// (exchange numbers are 32 bits and compared as a signed difference: they may wrap)
-// the consumer's view of exchange `seq`: its local slots in rank order (the surplus entries: a slot of zeros behind the flag
-// block) and the flags the peers raise to `seq` once their vectors have landed
-PeerSlots peer_slots(const mjx_ctx* c, int par, uint32_t seq) {
-  PeerSlots ps{};
-  ps.world = c->peer.world; ps.rank = c->peer.rank; ps.seq = seq;
-  const char* zeros = (const char*)peer_flags(c, c->peer.rank) + 256;
-  for (int r = 0; r < 16; ++r) ps.slot[r] = r < c->peer.world ? peer_slot(c, c->peer.rank, par, r) : zeros;
-  ps.flags = peer_flags(c, c->peer.rank);
-  ps.timeouts = peer_flags(c, c->peer.rank) + 32;
-  ps.ticks = c->peer.timeout_ticks;
-  return ps;
-}
-// the next exchange: its number, this rank's slot in the own buffer, the producer's and the consumer's view of it
-struct PeerRound { uint32_t seq; char* own; PeerPush push; PeerSlots slots; };
-PeerRound next_round(mjx_ctx* c) {
-  const uint32_t seq = ++c->peer.seq;
-  const int par = (int)(seq & 1u);
-  return PeerRound{seq, peer_slot(c, c->peer.rank, par, c->peer.rank), peer_push(c, par, seq), peer_slots(c, par, seq)};
-}
-int peer_allreduce(mjx_ctx* c, void* buf, int64_t count, int dtype, hipStream_t st) {
-  const size_t bytes = (size_t)count * (dtype ? 8 : 4);
-  if (bytes > c->peer.slot_bytes) return fail(MJX_ERR_ARG, "peer all-reduce of %zu bytes exceeds the slot (%zu)", bytes, c->peer.slot_bytes);
-  const PeerRound r = next_round(c);
-  const unsigned grid = (unsigned)((count + 255) / 256);
-  if (dtype) hipLaunchKernelGGL(k_peer_push<double>, dim3(grid), dim3(256), 0, st, (const double*)buf, r.push, count);
-  else hipLaunchKernelGGL(k_peer_push<float>, dim3(grid), dim3(256), 0, st, (const float*)buf, r.push, count);
-  HIPCHK(hipGetLastError());
-  if (dtype) hipLaunchKernelGGL(k_peer_sum<double>, dim3(grid), dim3(256), 0, st, r.slots, (double*)buf, count);
-  else hipLaunchKernelGGL(k_peer_sum<float>, dim3(grid), dim3(256), 0, st, r.slots, (float*)buf, count);
-  HIPCHK(hipGetLastError());
-  return MJX_OK;
-}
-}  // namespace
-
-int mjx_cg_init(mjx_ctx* c, const float* b, void* stream) {
-  if (!c || !b) return fail(MJX_ERR_ARG, "bad arguments");
-  c->fz.on_solve();
-  hipLaunchKernelGGL(k_cg_init, dim3(1), dim3(1024), 0, (hipStream_t)stream, b, c->cg_x, c->cg_r, c->cg_p, c->cg_scal, (int)c->d);
-  HIPCHK(hipGetLastError());
-  return MJX_OK;
-}
-const float* mjx_cg_p(mjx_ctx* c) { return c ? c->cg_p : nullptr; }
-int mjx_cg_step(mjx_ctx* c, const float* Ap, float damping, double tol, void* stream) {
-  if (!c || !Ap) return fail(MJX_ERR_ARG, "bad arguments");
-  if (c->d <= 8 * 1024)
-    hipLaunchKernelGGL(k_cg_step_reg<8>, dim3(1), dim3(1024), 0, (hipStream_t)stream, Ap, damping, tol, c->cg_x, c->cg_r, c->cg_p,
-                       c->cg_scal, (int)c->d);
-  else {
-    static const bool multi = env_flag("MJX_CG_MULTI", true);
-    hipStream_t st = (hipStream_t)stream;
-    if (multi && c->d >= 4 * CGM_G) {                   // (the partials fit c->cg_z: d floats >= 2 x CGM_G doubles)
-      // large d: three launches of CGM_G workgroups (vecops.h); c->cg_z serves as their 2 x CGM_G fp64 partials
-      double* part = (double*)c->cg_z;
-      hipLaunchKernelGGL(k_cgm_pz, dim3(CGM_G), dim3(CGM_T), 0, st, Ap, (const float*)c->cg_p, damping, (const double*)c->cg_scal, part, (int)c->d);
-      hipLaunchKernelGGL(k_cgm_xr, dim3(CGM_G), dim3(CGM_T), 0, st, Ap, (const float*)c->cg_p, damping, c->cg_x, c->cg_r, c->cg_scal, part, (int)c->d);
-      hipLaunchKernelGGL(k_cgm_p, dim3(CGM_G), dim3(CGM_T), 0, st, (const float*)c->cg_r, c->cg_p, tol, c->cg_scal, (const double*)part, (int)c->d);
-    } else
-      hipLaunchKernelGGL(k_cg_step, dim3(1), dim3(1024), 0, st, Ap, damping, tol, c->cg_x, c->cg_r, c->cg_p,
-                         c->cg_z, c->cg_scal, (int)c->d);
-  }
-  HIPCHK(hipGetLastError());
-  return MJX_OK;
-}
-int mjx_cg_finish(mjx_ctx* c, const float* b, float* x_out, double* bdotx_out, void* stream) {
-  if (!c || !b) return fail(MJX_ERR_ARG, "bad arguments");
-  hipLaunchKernelGGL(k_cg_finish, dim3(1), dim3(1024), 0, (hipStream_t)stream, b, c->cg_x, x_out, bdotx_out, (int)c->d);
-  HIPCHK(hipGetLastError());
-  return MJX_OK;
-}
-
-}  // extern "C"  (internal helpers with C++ types follow)
-namespace {
-// d-float vectors the peer exchange folds into the loop's own kernels (k_reduce_partials4 / k_cg_step_reg<8, W>)
-bool peer_folded(const mjx_ctx* c) { return c->peer.on && c->fz.variant && (c->d & 3) == 0 && c->d <= 8 * 1024; }
-// where the 4 doubles that travel with a gradient sit in a slot (mjx_peer_export sizes the slots for it)
-int peer_scal_off(const mjx_ctx* c) { return (int)(((size_t)c->d * sizeof(float) + 15) & ~(size_t)15); }
-
-// The solve, with (r06) what precedes and follows it folded into its own launches when the shapes allow:
-//  * b_slots: the right-hand side arrives as one slot per rank (the gradient's peer exchange, with K1's 4 sums riding along):
-//    k_cg_init_w waits, sums, leaves the summed gradient in `b` and the sums in s4_out;
-//  * fin: after the LAST vector update the same kernel forms b.x, x_out and (mode 2 / 3) the stepped parameters -- k_cg_finish and
-//    k_apply_*_step are not launched (d <= 8192 and at least one iteration; otherwise they are, as before).
-int cg_solve_impl(mjx_ctx* c, float* b, int iters, float damping, double tol, float* x_out, double* bdotx_out, mjx_allreduce_fn allreduce,
-                  void* user, void* stream, const PeerSlots* b_slots, double* s4_out, CgFin fin) {
-  hipStream_t st = (hipStream_t)stream;
-  if (b_slots) {
-    c->fz.on_solve();
-    const int off = peer_scal_off(c);
-    with_world_width(c->peer.world, [&](auto w) {
-      hipLaunchKernelGGL((k_cg_init_w<decltype(w)::value>), dim3(1), dim3(1024), 0, st, *b_slots, off, b, s4_out, c->cg_x, c->cg_r, c->cg_p, c->cg_scal, (int)c->d);
-    });
-    HIPCHK(hipGetLastError());
-  } else if (int rc = mjx_cg_init(c, b, stream)) return rc;
-  const bool reg = c->d <= 8 * 1024;
-  bool fin_done = false;
-  fin.b = b; fin.x_out = x_out; fin.bdotx = bdotx_out; fin.oS = c->oS;
-  for (int i = 0; i < iters; ++i) {
-    const CgFin f = (reg && i == iters - 1) ? fin : CgFin{};
-    // (mjx_profile_enable(ctx, -k): every k-th iteration as a whole -- product, reduction / exchange, vector update -- between two events)
-    const bool piter = c->prof_on && c->prof_iter && i + 1 < iters && (c->prof_seen++ % (size_t)c->prof_stride == 0) && c->prof_used + 2 <= c->prof_ev.size();
-    if (piter) HIPCHK(hipEventRecord(c->prof_ev[c->prof_used], st));
-    struct IterEnd { mjx_ctx* c; hipStream_t st; bool on; ~IterEnd() { if (on) { (void)hipEventRecord(c->prof_ev[c->prof_used + 1], st); c->prof_used += 2; } } } iter_end{c, st, piter};
-    if (!allreduce && peer_folded(c) && c->old_is_new && c->N_local > 0) {
-      // peer exchange, folded into the loop's own kernels: the product's reduction kernel writes this rank's vector into slot `rank` of
-      // EVERY rank's buffer and raises its arrival flags, the vector-update kernel waits on the own flags and sums its local
-      // slots (rank order): per iteration FVP -> reduction -> step -- exactly the launches of the one-rank loop, no host round trip.
-      // (A rank on another route -- empty shard -- runs the same exchange through mjx_comm_allreduce.)
-      const PeerRound r = next_round(c);
-      if (int rc = fvp_impl(c, c->cg_p, (float*)r.own, stream, &r.push)) return rc;
-      with_world_width(c->peer.world, [&](auto w) {
-        hipLaunchKernelGGL((k_cg_step_reg<8, decltype(w)::value>), dim3(1), dim3(1024), 0, st, (const float*)nullptr, damping, tol,
-                           c->cg_x, c->cg_r, c->cg_p, c->cg_scal, (int)c->d, r.slots, f);
-      });
-      HIPCHK(hipGetLastError());
-      fin_done = f.mode != 0;
-      continue;
-    }
-    if (int rc = mjx_fvp(c, c->cg_p, c->cg_Ap, stream)) return rc;
-    if (allreduce) { if (int rc = allreduce(user, c->cg_Ap, c->d, stream)) return fail(rc, "allreduce callback failed (%d)", rc); }
-    else if (has_ranks(c)) { if (int rc = mjx_comm_allreduce(c, c->cg_Ap, c->d, 0, stream)) return rc; }
-    if (reg) {
-      hipLaunchKernelGGL(k_cg_step_reg<8>, dim3(1), dim3(1024), 0, st, (const float*)c->cg_Ap, damping, tol, c->cg_x, c->cg_r, c->cg_p,
-                         c->cg_scal, (int)c->d, PeerSlots{}, f);
-      HIPCHK(hipGetLastError());
-      fin_done = f.mode != 0;
-    } else if (int rc = mjx_cg_step(c, c->cg_Ap, damping, tol, stream)) return rc;
-  }
-  if (fin_done) return MJX_OK;
-  if (int rc = mjx_cg_finish(c, b, x_out, bdotx_out, stream)) return rc;
-  if (fin.mode == 2) return mjx_apply_npg_step(c, fin.theta, x_out, bdotx_out, fin.step_size, fin.min_log_std, fin.theta_out, fin.alpha_out, stream);
-  if (fin.mode == 3) return mjx_apply_step(c, fin.theta, x_out, fin.const_alpha, fin.min_log_std, fin.theta_out, stream);
-  return MJX_OK;
-}
-
-CgFin fin_step(const float* theta, float* theta_out, double* alpha_out, double step_size, double const_alpha, float min_log_std) {
-  CgFin f;
-  f.mode = std::isnan(const_alpha) ? 2 : 3;
-  f.theta = theta; f.theta_out = theta_out; f.alpha_out = alpha_out; f.step_size = step_size;
-  f.const_alpha = std::isnan(const_alpha) ? 0.f : (float)const_alpha; f.min_log_std = min_log_std;
-  return f;
-}
-CgFin fin_only() { CgFin f; f.mode = 1; return f; }
-
-// K1 and the rank sums of its outputs, up to the point where the solve starts.  -> *slots_out set when the gradient's sum is
-// left to the solve's first kernel (peer exchange, folded: ONE exchange carries the gradient and K1's sums -- every rank of the
-// job takes this route or none does: the condition depends on the architecture and the transport only)
-int vpg_and_rank_sums(mjx_ctx* c, float* grad_out, double* s4, bool need_s4_sum, void* stream, PeerSlots* slots_out, bool* folded) {
-  *folded = false;
-  hipStream_t st = (hipStream_t)stream;
-  if (peer_folded(c) && need_s4_sum) {
-    const PeerRound r = next_round(c);
-    const int off = peer_scal_off(c);
-    if (c->N_local > 0) {
-      if (int rc = surr_vpg_impl(c, (float*)r.own, (double*)(r.own + off), stream, &r.push, off)) return rc;
-    } else {                                     // a rank without samples: zeros, through the same exchange
-      HIPCHK(hipMemsetAsync(grad_out, 0, c->d * sizeof(float), st));
-      HIPCHK(hipMemsetAsync(s4, 0, 4 * sizeof(double), st));
-      hipLaunchKernelGGL(k_peer_push_vs, dim3((unsigned)((c->d + 255) / 256)), dim3(256), 0, st, (const float*)grad_out, (const double*)s4, r.push, (int)c->d, off);
-      HIPCHK(hipGetLastError());
-    }
-    *slots_out = r.slots;
-    *folded = true;
-    return MJX_OK;
-  }
-  if (int rc = mjx_surr_vpg(c, grad_out, s4, stream)) return rc;
-  if (c->comm && need_s4_sum) {
-    RcclApi& r = rccl();
-    (void)r.GroupStart();                       // one launch for the gradient and its scalars
-    int rc = mjx_comm_allreduce(c, grad_out, c->d, 0, stream);
-    if (!rc) rc = mjx_comm_allreduce(c, s4, 4, 1, stream);
-    const int ge = r.GroupEnd();
-    if (rc) return rc;
-    if (ge) return fail(1000 + ge, "ncclGroupEnd: %s", r.GetErrorString(ge));
-  } else if (has_ranks(c)) {
-    if (int rc = mjx_comm_allreduce(c, grad_out, c->d, 0, stream)) return rc;
-    if (need_s4_sum) if (int rc = mjx_comm_allreduce(c, s4, 4, 1, stream)) return rc;
-  }
-  return MJX_OK;
-}
-
-// K3 and the rank sum of its 4 doubles (peer exchange: the push rides on the reduction kernel)
-// (one-call updates only: their evaluations may use the old policy's outputs K1 left -- nothing outside the library ran in between)
-int eval_and_rank_sum(mjx_ctx* c, double* res4, void* stream) {
-  hipStream_t st = (hipStream_t)stream;
-  if (c->peer.on && c->fz.variant && c->N_local > 0) {
-    const PeerRound r = next_round(c);
-    if (int rc = eval_impl(c, (double*)r.own, stream, &r.push, true)) return rc;
-    hipLaunchKernelGGL(k_peer_sum<double>, dim3(1), dim3(256), 0, st, r.slots, res4, (int64_t)4);
-    HIPCHK(hipGetLastError());
-    return MJX_OK;
-  }
-  if (int rc = eval_impl(c, res4, stream, nullptr, true)) return rc;
-  if (has_ranks(c)) if (int rc = mjx_comm_allreduce(c, res4, 4, 1, stream)) return rc;
-  return MJX_OK;
-}
 }  // namespace
 extern "C" {
 
+int mjx_surr_vpg(mjx_ctx* c, float* grad_out, double* scal_out, void* stream) { return surr_vpg_impl(c, grad_out, scal_out, stream, nullptr, -1); }
+int mjx_fvp(mjx_ctx* c, const float* v, float* out, void* stream) { return fvp_impl(c, v, out, stream, nullptr); }
+int mjx_eval_surr_kl(mjx_ctx* c, double* scal_out, void* stream) { return eval_impl(c, scal_out, stream, nullptr, false); }
+
+// ---------------------------------------------------------------------------- the solve, call by call and whole (csrc/update_host.h: CgWS, cg_solve_impl)
+int mjx_cg_init(mjx_ctx* c, const float* b, void* stream) {
+  if (!c || !b) return fail(MJX_ERR_ARG, "bad arguments");
+  c->fz.on_solve();
+  return c->cg.init(b, (hipStream_t)stream);
+}
+const float* mjx_cg_p(mjx_ctx* c) { return c ? c->cg.p : nullptr; }
+int mjx_cg_step(mjx_ctx* c, const float* Ap, float damping, double tol, void* stream) {
+  if (!c || !Ap) return fail(MJX_ERR_ARG, "bad arguments");
+  return c->cg.step(Ap, nullptr, CgFin{}, damping, tol, (hipStream_t)stream);
+}
+int mjx_cg_finish(mjx_ctx* c, const float* b, float* x_out, double* bdotx_out, void* stream) {
+  if (!c || !b) return fail(MJX_ERR_ARG, "bad arguments");
+  return c->cg.finish(b, x_out, bdotx_out, (hipStream_t)stream);
+}
 int mjx_cg_solve(mjx_ctx* c, const float* b, int iters, float damping, double tol, float* x_out, double* bdotx_out,
                  mjx_allreduce_fn allreduce, void* user, void* stream) {
   if (!c || !b || iters < 0) return fail(MJX_ERR_ARG, "bad arguments");
-  return cg_solve_impl(c, const_cast<float*>(b), iters, damping, tol, x_out, bdotx_out, allreduce, user, stream, nullptr, nullptr, fin_only());
+  SolveReq q{const_cast<float*>(b), iters, damping, tol, x_out, bdotx_out, fin_only(), stream};
+  q.allreduce = allreduce; q.user = user;
+  return cg_solve_impl(c, q);
 }
 
-// ---------------------------------------------------------------------------- multi-rank (RCCL, bound at run time)
+// ---------------------------------------------------------------------------- multi-rank: RCCL (bound at run time), the hook, the peer exchange (csrc/update_host.h: Transport)
 int mjx_comm_unique_id(char* id_out) {
   if (!id_out) return fail(MJX_ERR_ARG, "null id buffer");
   RcclApi& r = rccl();
@@ -1406,153 +1143,57 @@ int mjx_comm_unique_id(char* id_out) {
   memcpy(id_out, id.internal, MJX_COMM_ID_BYTES);
   return MJX_OK;
 }
-
 int mjx_comm_init(mjx_ctx* c, int rank, int world, const char* id_host) {
   if (!c || !id_host || world < 1 || rank < 0 || rank >= world) return fail(MJX_ERR_ARG, "bad arguments");
-  if (c->comm) return fail(MJX_ERR_STATE, "a communicator is already attached");
-  RcclApi& r = rccl();
-  if (!r.load()) return fail(MJX_ERR_UNSUPPORTED, "%s", r.error.c_str());
-  HIPCHK(hipSetDevice(c->device));
-  RcclApi::UniqueId id;
-  memcpy(id.internal, id_host, MJX_COMM_ID_BYTES);
-  RcclApi::Comm comm = nullptr;
-  if (int rc = r.CommInitRank(&comm, world, id, rank)) return fail(1000 + rc, "ncclCommInitRank: %s", r.GetErrorString(rc));
-  c->comm = comm; c->comm_world = world; c->comm_rank = rank;
-  return MJX_OK;
+  return c->tp.attach_rccl(rank, world, id_host);
 }
-
 int mjx_comm_destroy(mjx_ctx* c) {
   if (!c) return fail(MJX_ERR_ARG, "null context");
-  if (c->peer.buf) {
-    (void)hipSetDevice(c->device);
-    (void)hipDeviceSynchronize();
-    for (int r = 0; r < c->peer.world; ++r)
-      if (r != c->peer.rank && c->peer.map[r] && c->peer.map[r] != c->peer.buf) (void)hipIpcCloseMemHandle(c->peer.map[r]);
-    (void)hipFree(c->peer.buf);
-    c->peer = mjx_ctx::Peer{};
-    c->comm_world = 0;
-  }
-  if (c->comm) {
-    (void)hipSetDevice(c->device);
-    (void)hipDeviceSynchronize();
-    (void)rccl().CommDestroy(c->comm);
-    c->comm = nullptr; c->comm_world = 0;
-  }
+  c->tp.detach();
   return MJX_OK;
 }
-
-int mjx_comm_world(const mjx_ctx* c) { return (c && (c->comm || c->reduce_cb || c->peer.on)) ? c->comm_world : 0; }
-
+int mjx_comm_world(const mjx_ctx* c) { return c ? c->tp.world() : 0; }
 int mjx_peer_export(mjx_ctx* c, int rank, int world, char* handle_out) {
-  if (!c || !handle_out || world < 2 || world > 16 || rank < 0 || rank >= world) return fail(MJX_ERR_ARG, "bad arguments (2 <= world <= 16)");
-  if (c->comm || c->reduce_cb || c->peer.buf) return fail(MJX_ERR_STATE, "a transport is already attached");
-  HIPCHK(hipSetDevice(c->device));
-  size_t slot = (((size_t)c->d * sizeof(float) + 15) & ~(size_t)15) + 4 * sizeof(double);   // a d-float vector + the 4 doubles that may travel with it (peer_scal_off)
-  if (slot < 64 * sizeof(double)) slot = 64 * sizeof(double);
-  slot = (slot + 255) & ~(size_t)255;
-  void* p = nullptr;
-  const size_t total = (size_t)(2 * world + 1) * slot + 256;      // [2 parities][world slots] | flag block (256 B) | one slot of zeros
-  HIPCHK(hipExtMallocWithFlags(&p, total, hipDeviceMallocUncached));
-  HIPCHK(hipMemset(p, 0, total));
-  HIPCHK(hipDeviceSynchronize());
-  hipIpcMemHandle_t h;
-  { hipError_t e = hipIpcGetMemHandle(&h, p); if (e != hipSuccess) { (void)hipFree(p); return fail((int)e, "hipIpcGetMemHandle: %s", hipGetErrorString(e)); } }
-  static_assert(sizeof(hipIpcMemHandle_t) == MJX_PEER_HANDLE_BYTES, "handle size");
-  memcpy(handle_out, &h, sizeof h);
-  c->peer.buf = (char*)p; c->peer.slot_bytes = slot; c->peer.rank = rank; c->peer.world = world; c->peer.seq = 0;
-  if (const char* f = getenv("MJX_PEER_FAULT")) {
-    const char* only = getenv("MJX_PEER_FAULT_RANK");               // (default: every rank misbehaves)
-    if (!only || atoi(only) == rank) c->peer.fault = !strcmp(f, "slot") ? 1 : !strcmp(f, "flag") ? 2 : 0;
-  }
-  if (const char* ms = getenv("MJX_PEER_TIMEOUT_MS")) {             // how long a consumer kernel waits for a peer's vector
-    const double v = atof(ms);
-    if (v > 0.0) c->peer.timeout_ticks = (unsigned long long)(v * 1e5);
-  }
-  return MJX_OK;
+  if (!c || !handle_out || world < 2 || world > PEER_MAX_WORLD || rank < 0 || rank >= world) return fail(MJX_ERR_ARG, "bad arguments (2 <= world <= 16)");
+  return c->tp.peer_export(rank, world, handle_out);
 }
-
 int mjx_peer_connect(mjx_ctx* c, const char* handles) {
   if (!c) return fail(MJX_ERR_ARG, "null context");
-  if (!c->peer.buf || c->peer.on) return fail(MJX_ERR_STATE, "call mjx_peer_export first (once)");
-  HIPCHK(hipSetDevice(c->device));
-  for (int r = 0; r < c->peer.world; ++r) {
-    if (r == c->peer.rank || !handles) { c->peer.map[r] = c->peer.buf; continue; }     // handles == NULL: loop-back rehearsal
-    hipIpcMemHandle_t h;
-    memcpy(&h, handles + (size_t)r * MJX_PEER_HANDLE_BYTES, sizeof h);
-    void* q = nullptr;
-    hipError_t e = hipIpcOpenMemHandle(&q, h, hipIpcMemLazyEnablePeerAccess);
-    if (e != hipSuccess) return fail((int)e, "hipIpcOpenMemHandle (rank %d): %s", r, hipGetErrorString(e));
-    c->peer.map[r] = (char*)q;
-  }
-  c->peer.on = true; c->peer.loopback = (handles == nullptr);
-  c->comm_world = c->peer.world; c->comm_rank = c->peer.rank;
-  return MJX_OK;
+  return c->tp.peer_connect(handles);
 }
-
 int mjx_peer_status(mjx_ctx* c, int* timeouts_out) {
   if (!c || !timeouts_out) return fail(MJX_ERR_ARG, "bad arguments");
-  *timeouts_out = 0;
-  if (!c->peer.on) return MJX_OK;
-  HIPCHK(hipSetDevice(c->device));
-  unsigned n = 0;
-  HIPCHK(hipMemcpy(&n, peer_flags(c, c->peer.rank) + 32, sizeof n, hipMemcpyDeviceToHost));   // (synchronises: read after the update's own read-back)
-  if (n) HIPCHK(hipMemset(peer_flags(c, c->peer.rank) + 32, 0, sizeof n));
-  *timeouts_out = (int)n;
-  return MJX_OK;
+  return c->tp.peer_status(timeouts_out);
 }
-
 int mjx_comm_set_callback(mjx_ctx* c, mjx_reduce_fn fn, void* user, int world) {
   if (!c || (fn && world < 1)) return fail(MJX_ERR_ARG, "bad arguments");
-  if (c->comm) return fail(MJX_ERR_STATE, "an RCCL communicator is attached");
-  c->reduce_cb = fn; c->reduce_user = user; c->comm_world = fn ? world : 0;
-  return MJX_OK;
+  return c->tp.attach_hook(fn, user, world);
 }
-
 int mjx_comm_allreduce(mjx_ctx* c, void* buf, int64_t count, int dtype, void* stream) {
   if (!c || !buf || count < 0 || (dtype != 0 && dtype != 1)) return fail(MJX_ERR_ARG, "bad arguments");
-  if (count == 0) return MJX_OK;
-  if (c->peer.on) return peer_allreduce(c, buf, count, dtype, (hipStream_t)stream);
-  if (!c->comm) {
-    if (!c->reduce_cb) return fail(MJX_ERR_STATE, "no communicator attached (mjx_comm_init)");
-    if (int rc = c->reduce_cb(c->reduce_user, buf, count, dtype, stream)) return fail(rc, "transport hook failed (%d)", rc);
-    return MJX_OK;
-  }
-  RcclApi& r = rccl();
-  if (int rc = r.AllReduce(buf, buf, (size_t)count, dtype ? RcclApi::kFloat64 : RcclApi::kFloat32, RcclApi::kSum, c->comm, stream))
-    return fail(1000 + rc, "ncclAllReduce: %s", r.GetErrorString(rc));
-  return MJX_OK;
+  return c->tp.allreduce(buf, count, dtype, stream);
 }
 
+// ---------------------------------------------------------------------------- the one-call updates (csrc/update_host.h)
 int mjx_npg_update(mjx_ctx* c, int iters, float damping, double tol, double step_size, double const_alpha, float min_log_std,
                    float* grad_out, float* x_out, float* theta_out, double* results, void* stream) {
-  if (int rc = check_bound(c, true)) return rc;
-  if (!grad_out || !x_out || !theta_out || !results || iters < 0) return fail(MJX_ERR_ARG, "bad arguments");
-  if (!c->old_is_new) return fail(MJX_ERR_STATE, "mjx_npg_update starts from theta_new == theta_old (mjx_bind_policy with old_is_new)");
-  if (theta_out == c->theta_old) return fail(MJX_ERR_ARG, "theta_out must not alias theta_old");
-  PeerSlots gs{};
-  bool folded = false;
-  if (int rc = vpg_and_rank_sums(c, grad_out, results + 4, true, stream, &gs, &folded)) return rc;
+  if (int rc = update_prologue(c, "mjx_npg_update", grad_out && x_out && theta_out && results && iters >= 0, true, theta_out)) return rc;
   const float* base = c->theta_old;               // == theta_new in value; theta_out may be the theta_new buffer itself
   // (theta_out == theta_new: the stepped parameters are written by the solve's LAST kernel, after every product has read theta)
-  if (int rc = cg_solve_impl(c, grad_out, iters, damping, tol, x_out, results + 8, nullptr, nullptr, stream, folded ? &gs : nullptr, results + 4,
-                             fin_step(base, theta_out, results + 9, step_size, const_alpha, min_log_std))) return rc;
+  if (int rc = vpg_then_solve(c, iters, damping, tol, grad_out, x_out, results,
+                              fin_step(base, theta_out, results + 9, step_size, const_alpha, min_log_std), stream)) return rc;
   if (int rc = bind_policy_impl(c, theta_out, c->theta_old, c->tr_new, c->tr_old, 0, true)) return rc;
   return eval_and_rank_sum(c, results, stream);
 }
 
 int mjx_trpo_update(mjx_ctx* c, int iters, float damping, double tol, double step_size, double kl_dist, int n_trials, int first,
                     float min_log_std, float* grad_out, float* x_out, float* theta_out, double* results, void* stream) {
-  if (int rc = check_bound(c, true)) return rc;
-  if (!grad_out || !x_out || !theta_out || !results || iters < 0 || n_trials < 1 || n_trials > 24) return fail(MJX_ERR_ARG, "bad arguments");
-  if (theta_out == c->theta_old) return fail(MJX_ERR_ARG, "theta_out must not alias theta_old");
+  if (int rc = update_prologue(c, "mjx_trpo_update", grad_out && x_out && theta_out && results && iters >= 0 && n_trials >= 1 && n_trials <= 24,
+                               false, theta_out)) return rc;
   hipStream_t st = (hipStream_t)stream;
   if (first) {
     if (!c->old_is_new) return fail(MJX_ERR_STATE, "mjx_trpo_update starts from theta_new == theta_old (mjx_bind_policy with old_is_new)");
-    PeerSlots gs{};
-    bool folded = false;
-    if (int rc = vpg_and_rank_sums(c, grad_out, results + 4, true, stream, &gs, &folded)) return rc;
-    if (int rc = cg_solve_impl(c, grad_out, iters, damping, tol, x_out, results + 8, nullptr, nullptr, stream, folded ? &gs : nullptr, results + 4,
-                               fin_only())) return rc;
+    if (int rc = vpg_then_solve(c, iters, damping, tol, grad_out, x_out, results, fin_only(), stream)) return rc;
   }
   for (int t = 0; t < n_trials; ++t) {
     hipLaunchKernelGGL(k_trpo_try, dim3((c->d + 255) / 256), dim3(256), 0, st, c->theta_old, x_out, results, step_size,
@@ -1566,27 +1207,25 @@ int mjx_trpo_update(mjx_ctx* c, int iters, float damping, double tol, double ste
   return MJX_OK;
 }
 
+// (its own sequence: the gradient is scaled between its rank sum and the solve, so that exchange is never folded into the solve)
 int mjx_dapg_update(mjx_ctx* c, int iters, float damping, double tol, double step_size, float min_log_std, int64_t rows_on,
                     int64_t N_on_global, const float* adv_on, float* grad_out, float* x_out, float* theta_out, double* results,
                     void* stream) {
-  if (int rc = check_bound(c, true)) return rc;
-  if (!grad_out || !x_out || !theta_out || !results || (!adv_on && rows_on > 0) || iters < 0) return fail(MJX_ERR_ARG, "bad arguments");   // (a rank without on-policy rows has no advantages)
-  if (!c->old_is_new) return fail(MJX_ERR_STATE, "mjx_dapg_update starts from theta_new == theta_old (mjx_bind_policy with old_is_new)");
-  if (theta_out == c->theta_old) return fail(MJX_ERR_ARG, "theta_out must not alias theta_old");
+  if (int rc = update_prologue(c, "mjx_dapg_update", grad_out && x_out && theta_out && results && (adv_on || rows_on <= 0) && iters >= 0,   // (a rank without on-policy rows has no advantages)
+                               true, theta_out)) return rc;
   if (rows_on < 0 || rows_on > c->N_local || N_on_global <= 0 || N_on_global > c->N_global) return fail(MJX_ERR_ARG, "bad on-policy row counts");
   hipStream_t st = (hipStream_t)stream;
-  const bool ranks = has_ranks(c);
   // the vanilla gradient over [on-policy ; demonstrations] (mean over N_all), then x N_all / N_on (dapg.py:97-98)
   const float coef = (float)((double)c->N_global / (double)N_on_global);
-  if (int rc = mjx_surr_vpg(c, grad_out, results + 4, stream)) return rc;
-  if (ranks) if (int rc = mjx_comm_allreduce(c, grad_out, c->d, 0, stream)) return rc;
+  if (int rc = surr_vpg_impl(c, grad_out, results + 4, stream, nullptr, -1)) return rc;
+  if (c->tp.attached()) if (int rc = c->tp.allreduce(grad_out, c->d, 0, stream)) return rc;
   hipLaunchKernelGGL(k_scale_f32, dim3((c->d + 255) / 256), dim3(256), 0, st, grad_out, coef, (int)c->d);
   HIPCHK(hipGetLastError());
   // Fisher metric, surrogate and KL: the on-policy prefix with its own advantages, means over the on-policy count (:92, :103)
   if (int rc = mjx_bind_rows(c, rows_on, N_on_global, adv_on)) return rc;
   if (int rc = eval_and_rank_sum(c, results + 4, stream)) return rc;                   // surr_before (theta_new == theta_old)
-  if (int rc = cg_solve_impl(c, grad_out, iters, damping, tol, x_out, results + 8, nullptr, nullptr, stream, nullptr, nullptr,
-                             fin_step(c->theta_old, theta_out, results + 9, step_size, std::nan(""), min_log_std))) return rc;
+  if (int rc = cg_solve_impl(c, SolveReq{grad_out, iters, damping, tol, x_out, results + 8,
+                                         fin_step(c->theta_old, theta_out, results + 9, step_size, std::nan(""), min_log_std), stream})) return rc;
   if (int rc = bind_policy_impl(c, theta_out, c->theta_old, c->tr_new, c->tr_old, 0, true)) return rc;
   return eval_and_rank_sum(c, results, stream);
 }

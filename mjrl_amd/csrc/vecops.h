@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "peer_layout.h"
+
 namespace mjx {
 
 // torch.optim.Adam's constants as torch hands them to its fp32 kernels, one definition for the policy fit on both of its routes
@@ -151,18 +153,8 @@ __global__ __launch_bounds__(256) void k_reduce_partials(const float* __restrict
   }
 }
 
-// Peer exchange (mjx_peer_*).  Every rank owns one uncached buffer [2 parities][world slots] + one arrival flag PER SOURCE RANK;
-// the peers' buffers are mapped through hipIpcOpenMemHandle.  An all-reduce = every rank WRITES its vector into slot `rank` of
-// every buffer (posted stores over xGMI), then stores the exchange number into ITS flag in every peer's buffer; the consumer
-// kernel waits (bounded) on the flags of its OWN buffer -- local memory, one polling thread per source rank -- and sums its local
-// slots in rank order: the same bits on every rank, no host in the loop.  A flag is written by exactly one rank over the same
-// path as that rank's data stores, after they were acknowledged: no ordering between DIFFERENT peers' traffic is relied upon
-// (an aggregate counter would need it for world > 2).
-struct PeerSlots {                     // consumer: the local slots of this exchange (entries >= world point at a slot of zeros)
-  const void* slot[16]; const unsigned* flags; unsigned* timeouts; unsigned long long ticks; unsigned seq; int world, rank;
-};
-// producer: slot `rank` in every buffer + the flag each peer polls for this rank; world == 0: off
-struct PeerPush { void* dst[16]; unsigned* flag[16]; unsigned* ticket; unsigned seq; int world, rank; };
+// Peer exchange (mjx_peer_*): the protocol, the buffer's layout and PeerSlots / PeerPush, the consumer's and the producer's view of
+// one exchange, are in peer_layout.h.
 
 // tail of a producer kernel (all threads call it): once the LAST workgroup's stores are visible system-wide, one thread
 // raises this rank's flag at every peer.  The ticket lives in ordinary device memory and is left at zero for the next kernel.
@@ -474,17 +466,7 @@ __device__ __forceinline__ float step_add(float theta, float alpha, float x) {
 // W > 0: the Fisher-vector product arrives as one slot per rank (peer exchange, W = slots read: world rounded up to a power
 // of two, the surplus entries point at zeros); the body waits for the arrivals and sums the slots in rank order.
 // Called by all 1024 threads of one workgroup.
-// what follows the LAST vector update of a solve, folded into its kernel (r06: k_cg_finish + k_apply_npg_step were two dependent
-// ~4.7 us launches of a 3.8 ms -- or, on an eighth of the batch, 0.8 ms -- update): mode 1: x_out = x, bdotx = b.x (k_cg_finish);
-// mode 2: ... and theta_out = theta + sqrt(|step_size / (b.x + 1e-20)|) x with the log_std clamp, the step length to alpha_out
-// (k_apply_npg_step); mode 3: the same with the caller's constant step length.  Same arithmetic, same order, same bits.
-struct CgFin {
-  int mode = 0;
-  const float* b = nullptr; float* x_out = nullptr; double* bdotx = nullptr;
-  const float* theta = nullptr; float* theta_out = nullptr; double* alpha_out = nullptr;
-  double step_size = 0.0; float const_alpha = 0.f, min_log_std = 0.f; int oS = 0;
-};
-
+// fin (CgFin, peer_layout.h): what follows the LAST vector update of a solve, folded into its kernel.
 template <int EPT, int W>
 __device__ __forceinline__ void cg_step_body(const float* Ap, float damping, double tol, float* x, float* r, float* p,
                                              double* scal, int d, const PeerSlots& ps, double* sh /* 17 doubles */, const CgFin& fin) {

@@ -437,6 +437,44 @@ def test_peer_exchange_in_loop_back_gives_the_single_rank_bits(world):
     assert np.array_equal(res[0][3], res[1][3]) and res[0][4:] == res[1][4:]
 
 
+@pytest.mark.parametrize("layerwise", [False, True])
+def test_profile_brackets_count_products_and_iterations(layerwise, monkeypatch):
+    """mjx_profile_enable(ctx, k) brackets every k-th Fisher-vector product, (ctx, -k) every k-th whole CG iteration except a
+    solve's last one (its kernel may carry the step); the count runs on across solves and any enable(+-k) starts it over.  Two
+    NPG updates of 10 iterations: ceil(20 / k) product brackets, ceil(18 / k) iteration brackets, from mjx_profile_read and
+    mjx_profile_samples alike, every bracket with a positive time (bench.py's roofline figures are read this way)."""
+    import ctypes
+    from mjrl_amd import _lib
+    from mjrl_amd.engine import UpdateEngine
+    c = NpgCase("npg_cfg2_small")
+    if layerwise:
+        monkeypatch.setenv("MJX_FORCE_LAYERWISE", "1")
+    tr = np.concatenate([np.zeros(c.n), np.ones(c.n), np.zeros(c.m), np.ones(c.m)]).astype(np.float32)
+    eng = UpdateEngine(c.n, c.m, c.hidden)
+    assert eng.backend.fused == (not layerwise)
+    lib, ctx = eng.backend.lib, eng.backend.ctx
+    eng.set_batch(c.obs, c.act, c.adv_w)
+    iters, solves = 10, 2
+    for sign, per_solve in ((1, iters), (-1, iters - 1)):
+        for k in (1, 7, 11):
+            _lib.check(lib.mjx_profile_enable(ctx, sign * k))
+            for _ in range(solves):
+                eng.set_policy(c.theta0, c.theta0, tr, tr)
+                eng.npg_update(iters, 1e-4, float(c.g["step"]), -3.0)
+            _lib.check(lib.mjx_profile_enable(ctx, 0))                    # off: what was recorded stays readable
+            want = -(-solves * per_solve // k)
+            out = (ctypes.c_double * 2)()
+            _lib.check(lib.mjx_profile_read(ctx, out))
+            ms = (ctypes.c_double * 64)()
+            cnt = ctypes.c_int(-1)
+            _lib.check(lib.mjx_profile_samples(ctx, ms, 64, ctypes.byref(cnt)))
+            print("profile brackets: layerwise %d enable(%d): read %d pairs, %.4f ms; samples %d" % (layerwise, sign * k, out[1], out[0], cnt.value))
+            assert int(out[1]) == want and cnt.value == want, (sign * k, out[1], cnt.value, want)
+            got = np.array(ms[:want])
+            assert np.all(got > 0.0) and abs(got.sum() - out[0]) <= 1e-6 * out[0], (sign * k, got, out[0])
+    eng.close()
+
+
 def test_upload_download_never_touch_pageable_memory_and_round_trip():
     """utils/ingest.upload / download: host <-> device through page-locked bounce buffers (pageable
     hipMemcpy of ~1 MB and more leaves userptr registrations behind that later stall the GPU queues), bit-exact for the

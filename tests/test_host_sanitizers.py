@@ -15,6 +15,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tests", "c", "host_san.cpp")
 SRC_LS = os.path.join(ROOT, "tests", "c", "launch_state_san.cpp")
 SRC_LP = os.path.join(ROOT, "tests", "c", "lw_plan.cpp")
+SRC_UH = os.path.join(ROOT, "tests", "c", "update_host.cpp")
 HIP_INC = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "include")
 SAN = [("asan_ubsan", ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer"]), ("tsan", ["-fsanitize=thread"])]
 
@@ -76,3 +77,21 @@ def test_lw_plan_under_sanitizers(tmp_path):
     assert b.returncode == 0, b.stderr[-3000:]
     r = subprocess.run([exe], capture_output=True, text=True, timeout=120, env=dict(os.environ, ASAN_OPTIONS="abort_on_error=0"))
     assert r.returncode == 0 and "lw_plan ok" in r.stdout and "Sanitizer" not in r.stderr, (r.stdout[-2000:], r.stderr[-4000:])
+
+
+def test_update_host_under_sanitizers(tmp_path):
+    """mjrl_amd/csrc/peer_layout.h and the plain-C++ top of mjrl_amd/csrc/update_host.h -- the peer buffer's layout and views, the
+    exchange counter, the CG and folding routes, the profiling brackets' pick -- are host C++ without a HIP call;
+    tests/c/update_host.cpp (their tables, tests/test_update_host_cpu.py) once more under -fsanitize=address,undefined: the views
+    are pointer arithmetic on every rank's base, the counter wraps on purpose."""
+    name, flags = SAN[0]
+    cxx = os.environ.get("CXX", "g++")
+    if shutil.which(cxx) is None:
+        pytest.skip("no C++ compiler")
+    exe = str(tmp_path / ("update_host_" + name))
+    b = subprocess.run([cxx, "-std=c++17", "-O1", "-g"] + flags + [SRC_UH, "-o", exe], capture_output=True, text=True, cwd=os.path.dirname(SRC_UH))
+    if b.returncode != 0 and "sanitize" in b.stderr and ("cannot find" in b.stderr or "unrecognized" in b.stderr):
+        pytest.skip("this toolchain has no %s runtime" % name)
+    assert b.returncode == 0, b.stderr[-3000:]
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120, env=dict(os.environ, ASAN_OPTIONS="abort_on_error=0"))
+    assert r.returncode == 0 and "update_host ok" in r.stdout and "Sanitizer" not in r.stderr, (r.stdout[-2000:], r.stderr[-4000:])
