@@ -54,7 +54,7 @@
 
 #include "dfe_tiles.h"
 #include "dynamics.h"
-#include "fused_policy.h"
+#include "mfma_prims.h"
 #include "launch_state.h"
 #include "vecops.h"
 

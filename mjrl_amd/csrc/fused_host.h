@@ -1,6 +1,8 @@
 // fused_host.h -- host side of the fused policy kernels (fused_policy.h): the table of their instances and FusedWS, the owner of the fused
-// path's buffers, caches and validity flags (the counterpart of LayerwiseWS, layerwise.h).  Included by mjx.hip after fail / HIPCHK / lds_limit.
+// path's buffers, caches and validity flags (the counterpart of LayerwiseWS, layerwise.h).  Included by mjx.hip after fail / HIPCHK / lds_limit
+// and after fused_policy.h (FusedWS::launch takes the address of k_fused); everything else it shares with the kernel is fused_layout.h.
 #pragma once
+#include "fused_layout.h"
 
 namespace mjx {
 
@@ -104,9 +106,9 @@ struct FusedWS {
     const FusedRoute r = fused_route(n, m, hidden);
     if (!layerwise_only) { variant = r.variant; npc = r.npc; }
     if (env_flag("MJX_NO_HCACHE", false)) use_hcache = 0;
-    with_fused_instance(variant, npc, [&](auto inst) {      // fused_policy.h HC_TILE
+    with_fused_instance(variant, npc, [&](auto inst) {
       using L = typename decltype(inst)::Layout;
-      hc_tile = (size_t)(L::MT1 + L::MT2) * 1024 + (size_t)(L(n).NP / 4) * 128;
+      hc_tile = (size_t)L::hc_tile(L(n).NP);
     });
     if (variant && r.raw_dr > 0 && env_flag("MJX_RAW_SLAB", true)) {
       HIPCHK(hipMalloc((void**)&raw_perm, (size_t)r.raw_dr * sizeof(int)));
@@ -198,8 +200,8 @@ struct FusedWS {
       const size_t tiles = (size_t)((a.N + 31) / 32);
       grow_or_drop(&hcache, &hcache_bytes, tiles * hc_tile * sizeof(float));
       if (hcache) { a.hcache = hcache; acts_ok = ximg_ok = true; hcache_obs = a.obs; hcache_rows = a.N; }
-      grow_or_drop(&ocache, &ocache_bytes, tiles * (fused_max_mp() + 1) * 32 * sizeof(float));     // [tile][MP + 1][32], any instance
-      grow_or_drop(&snap, &snap_bytes, (size_t)(d + 2 * (n + m)) * sizeof(float));
+      grow_or_drop(&ocache, &ocache_bytes, tiles * oc_tile(fused_max_mp()) * sizeof(float));     // any instance
+      grow_or_drop(&snap, &snap_bytes, (size_t)snap_len(d, n, m) * sizeof(float));
       ocache_ok = false;
       if (ocache && snap) { a.snap_out = snap; a.ocache = ocache; ocache_ok = true; ocache_rows = a.N; }
     }

@@ -19,48 +19,11 @@
 //   mjrl/algos/npg_cg.py:62-81           (MODE_FVP, Gauss-Newton form valid at new==old)
 //   mjrl/algos/batch_reinforce.py:40-52  (MODE_EVAL)
 #pragma once
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#include <type_traits>
-#include <vector>
+#include "bf16x3.h"
+#include "fused_layout.h"
+#include "mfma_prims.h"
 
 namespace mjx {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
-enum { MODE_VPG = 0, MODE_FVP = 1, MODE_EVAL = 2 };
-
-struct FusedArgs {
-  const float* obs;      // (N, n)
-  const float* act;      // (N, m)   VPG / EVAL
-  const float* adv;      // (N)      VPG / EVAL
-  int64_t N;             // local samples
-  float inv_N;           // 1 / N_global
-  const float* thetaA;   // new parameters (flat)
-  const float* thetaB;   // FVP: the vector v (flat);  VPG/EVAL: old parameters
-  const float* trA;      // packed transforms of the new net (never null)
-  const float* trB;      // packed transforms of the old net (never null)
-  int old_is_new;        // VPG: skip the old forward (LR == 1 exactly)
-  float* partials;       // [gridDim.x][d]   VPG / FVP
-  double* spartials;     // [gridDim.x][4]
-  float* dbg;            // optional dump of tile 0 (block 0, wave 0)
-  long long* clk;        // optional: workgroup 0 stamps {cycle, real time} at entry / exit
-  int reverse;           // cached FVP: walk the tiles from the far end (alternate launches: what the previous sweep touched
-                         // last is still in the memory-side cache when this one starts there)
-  float* hcache;         // forward-activation cache [tile][MT1+MT2][4][64 lanes][4]: written by MODE_VPG, read by cached FVP
-  float* ocache;         // old-policy outputs [tile][MP + 1][32]: mean per action + log-likelihood; written by MODE_VPG
-                         // (old == new), read by MODE_EVAL when thetaB / trB still equal `snap`
-  const float* snap;     // [d + 2n + 2m] parameters and transforms the ocache was computed with
-  int snap_trusted;      // MODE_EVAL: the caller vouches that thetaB / trB / trA still equal `snap` (the one-call updates: nothing
-                         // outside the library ran since K1) -- the bit-exact compare in the prologue is skipped (~4 us per launch)
-  float* snap_out;       // MODE_VPG: the kernel writes that snapshot (thetaB | trB) while it fills the ocache
-  int n, m;
-  int raw_dr;            // > 0: the gradient partial of a workgroup is written in ACCUMULATOR order (RawSlab<..>::DR floats per
-                         // workgroup, see RawSlab below); k_reduce_partials4 maps the columns to the flat order (perm)
-};
 
 #ifdef MJX_PHASE_CLOCK
 #define MJX_STAMP(k) do { __builtin_amdgcn_sched_barrier(0); if (A.dbg && blockIdx.x == 0 && wave == 0 && lane == 0 && tile == tstride) ((long long*)A.dbg)[k] = (long long)__builtin_readcyclecounter(); __builtin_amdgcn_sched_barrier(0); } while (0)
@@ -72,368 +35,6 @@ struct FusedArgs {
 #else
 #define MJX_GSTAMP(k) do {} while (0)
 #endif
-#define MJX_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_32x32x2f32((a), (b), (c), 0, 0, 0)
-// Accumulators that live across ALL tiles of a wave (the weight gradients of the cached Fisher-vector product) stay in the
-// accumulation registers: with -amdgpu-mfma-vgpr-form the builtins put every MFMA result in an architectural VGPR and hipcc then
-// shuttles the persistent ones to AGPRs and back around each use (120 v_accvgpr moves per tile, 6 cycles each: probe_fill.hip).
-// Written as inline assembly with an "a" constraint they are AGPR operands of the instruction itself.  The compiler does not see an
-// MFMA in them, so it inserts none of the wait states MFMA hazards need: (i) their results are only read after the tile loop;
-// (ii) `volatile` keeps them in program order, which walks the accumulators round-robin -- measured (r03): with the statements
-// free to move, hipcc grouped the 4x4x1 ones by accumulator, back to back with one s_nop, and the sums came out wrong (a
-// dependent 4x4x1 needs more wait states than that; the builtin form gets them from the hazard recogniser).  Used only where
-// >= 4 accumulators alternate (gW2, the 4x4x1 form of gW1) or the chain is made of 64-cycle 32x32x2 instructions.
-#define MJX_MFMA_ACC(acc, a, b) asm volatile("v_mfma_f32_32x32x2_f32 %0, %1, %2, %0" : "+a"(acc) : "v"(a), "v"(b))
-#define MJX_MFMA4_ACC(acc, a, b) asm volatile("v_mfma_f32_4x4x1_16b_f32 %0, %1, %2, %0" : "+a"(acc) : "v"(a), "v"(b))
-// The bf16 counterpart (R9 of the bf16x3 cached Fisher-vector product; a, b: four registers of 8 bf16 each).  Its operands are
-// pieces a vector-ALU instruction has just written, and a VGPR written by the VALU needs 2 wait states before an MFMA reads it as
-// SrcA / SrcB; the hazard recogniser pads nothing around inline assembly, so the two states open the statement itself (they
-// pass in the shadow of the MFMA in front: the matrix pipe is busy for 32 cycles per instruction).
-#define MJX_MFMA_BF16_ACC(acc, a, b) asm volatile("s_nop 1\n\tv_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+a"(acc) : "v"(a), "v"(b))
-// 4- and 8-byte LDS accesses of the cached Fisher-vector product.  (Measured, r03: making them volatile LDS-space accesses keeps
-// hipcc from pairing them into ds_read2 / ds_write2 -- whose 8-bit offset fields cost a vector add per pair to re-base the
-// address, 48 per tile -- and saves 2.5 % of the kernel's cycles, but the chip gives the same 2.5 % back in clock: no
-// change in time, and hipcc 7.2 crashes on the volatile form in one instance.  Plain accesses it is.)
-typedef __attribute__((address_space(3))) float lds_float;
-// LDS byte address of a shared-memory pointer as an opaque 32-bit value: the compiler must keep it in a register (it would
-// otherwise re-derive `base + constant` with a v_add_u32 next to every ds_write2 / ds_read2 whose 8-bit offsets do not reach --
-// ~25 single vector-ALU instructions inside the MFMA phases of a cached Fisher-vector-product tile, 12 cycles each there)
-__device__ __forceinline__ uint32_t lds_pin(const float* p) {
-  uint32_t a = (uint32_t)(uintptr_t)(const lds_float*)p;
-  asm volatile("" : "+v"(a));
-  return a;
-}
-#define LDS_AT(addr) ((lds_float*)(uintptr_t)(addr))
-#define LDS_ST(p, v) (*(p) = (v))
-#define LDS_LD(p) (*(p))
-#define LDS_LD2(p) (*(const f32x2*)(p))
-
-__device__ __forceinline__ void wave_sync() {
-  // LDS traffic between lanes of ONE wave: hardware executes a wave's DS ops in order,
-  // this only stops the compiler from moving them across the hand-off.
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// tanh(x) = 1 - 2 / (1 + exp2(2 log2(e) x)): branch-free, v_exp_f32 + v_rcp_f32 + one FMA; no |x|, no sign transfer, no
-// Newton step (exp2 -> inf gives rcp -> 0 -> +1, exp2 -> 0 gives -1; a Newton step would form inf * 0 there).  Max abs error
-// ~1.2e-7 (1 ulp of the reciprocal doubled + the exponential's ulp; ocml tanhf: 6e-8, branchy).  fp32 MFMAs do not hide
-// vector-ALU work (DESIGN "what an fp32 MFMA hides"), so every instruction here is paid in full: r02's form -- sign(x)(1 - t)/(1 + t),
-// t = exp2(-2 log2(e)|x|), Newton-refined -- cost 6 packed + 4 quarter-rate + 2 v_bfi per register pair, this one 3 + 4
-// (K1 0.379 -> 0.361 ms, K3 0.177 -> 0.155 ms; step direction vs the reference at 1M: 2.90e-6 -> 2.95e-6, bar 1e-5).
-__device__ __forceinline__ float fast_tanh(float x) {
-  const float d = 1.0f + __builtin_amdgcn_exp2f(x * 2.885390081777927f);
-  return fmaf(__builtin_amdgcn_rcpf(d), -2.0f, 1.0f);
-}
-
-// the same on a 16-register tile, two registers per packed instruction (scale, 1 + e, the final FMA; v_exp_f32 / v_rcp_f32
-// stay per register)
-__device__ __forceinline__ void fast_tanh16(f32x16& o, const f32x16& x) {
-#pragma unroll
-  for (int r = 0; r < 16; r += 2) {
-    const f32x2 s = f32x2{x[r], x[r + 1]} * (f32x2)(2.885390081777927f);
-    const f32x2 d = f32x2{__builtin_amdgcn_exp2f(s.x), __builtin_amdgcn_exp2f(s.y)} + (f32x2)(1.0f);
-    const f32x2 rr = {__builtin_amdgcn_rcpf(d.x), __builtin_amdgcn_rcpf(d.y)};
-    const f32x2 y = __builtin_elementwise_fma(rr, (f32x2)(-2.0f), (f32x2)(1.0f));
-    o[r] = y.x; o[r + 1] = y.y;
-  }
-}
-
-// a / b with v_rcp_f32 + one Newton step (<= 2 ulp; exact for b == 1): the per-sample divisions of the likelihood
-// head and of the input normalisation cost 4 VALU ops instead of the ~12 of the IEEE sequence
-__device__ __forceinline__ float fast_div(float a, float b) {
-  float r = __builtin_amdgcn_rcpf(b);
-  r = r * fmaf(-b, r, 2.0f);
-  return a * r;
-}
-
-// mask ? a : b on bit patterns (mask = all ones / all zeros per lane)
-__device__ __forceinline__ float half_select(uint32_t mask, float a, float b) {
-  return __uint_as_float((__float_as_uint(a) & mask) | (__float_as_uint(b) & ~mask));
-}
-
-// x[lane] + x[lane ^ 32] in every lane: v_permlane32_swap exchanges the upper half of one copy with the
-// lower half of the other (one VALU op, no LDS round trip like ds_bpermute)
-__device__ __forceinline__ float half_sum(float p) {
-  auto s = __builtin_amdgcn_permlane32_swap(__float_as_uint(p), __float_as_uint(p), false, false);
-  return __uint_as_float(s[0]) + __uint_as_float(s[1]);
-}
-
-// every lane: the sum over its 16-lane row, by DPP moves (vector-ALU latency; the same operand pairs, hence the same bits, as
-// `v += __shfl_xor(v, 1); ... 2; ... 4; ... 8` -- after each step all lanes of a group hold the group's sum -- without the four
-// ~100-cycle trips through the LDS pipe that ds_bpermute costs)
-__device__ __forceinline__ float row16_sum(float v) {
-  auto dpp = [](float x, auto ctrl) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), decltype(ctrl)::value, 0xF, 0xF, true));
-  };
-  v += dpp(v, std::integral_constant<int, 0xB1>{});       // quad_perm [1,0,3,2]
-  v += dpp(v, std::integral_constant<int, 0x4E>{});       // quad_perm [2,3,0,1]
-  v += dpp(v, std::integral_constant<int, 0x141>{});      // row_half_mirror
-  v += dpp(v, std::integral_constant<int, 0x140>{});      // row_mirror
-  return v;
-}
-
-// packed fp32 element-wise helpers on 16-register tiles (register pairs -> v_pk_fma_f32 / v_pk_mul_f32)
-__device__ __forceinline__ f32x16 pk_1mh2(const f32x16& h) {                      // 1 - h^2
-  f32x16 o;
-#pragma unroll
-  for (int r = 0; r < 16; r += 2) {
-    const f32x2 hh = {h[r], h[r + 1]};
-    const f32x2 ff = __builtin_elementwise_fma(-hh, hh, (f32x2)(1.0f));
-    o[r] = ff.x; o[r + 1] = ff.y;
-  }
-  return o;
-}
-__device__ __forceinline__ void pk_mul(f32x16& t, const f32x16& f) {              // t *= f
-#pragma unroll
-  for (int r = 0; r < 16; r += 2) {
-    f32x2 tt = {t[r], t[r + 1]};
-    tt *= f32x2{f[r], f[r + 1]};
-    t[r] = tt.x; t[r + 1] = tt.y;
-  }
-}
-__device__ __forceinline__ void pk_mul_1mh2(f32x16& t, const f32x16& h) {         // t *= 1 - h^2
-#pragma unroll
-  for (int r = 0; r < 16; r += 2) {
-    const f32x2 hh = {h[r], h[r + 1]};
-    f32x2 tt = {t[r], t[r + 1]};
-    tt *= __builtin_elementwise_fma(-hh, hh, (f32x2)(1.0f));
-    t[r] = tt.x; t[r + 1] = tt.y;
-  }
-}
-// The same two as ONE packed FMA per register pair with the negation in the instruction's modifiers: left to the compiler, -h
-// becomes a v_xor_b32 per register (32 extra vector-ALU instructions per cached Fisher-vector-product tile) or the pair is split
-// into scalar v_fma_f32 / v_mul_f32.  Inline asm is invisible to the compiler's hazard recogniser: NO wait states are inserted
-// between an MFMA and an asm instruction that reads its result -- use these only on registers whose producing MFMA retired long
-// ago (a whole MFMA phase in between), never directly behind the producer (the non-cached tile body does that: 2 % wrong and
-// nondeterministic when it was tried there).
-__device__ __forceinline__ f32x2 pk_1mh2_pair_far(f32x2 hh) {
-  f32x2 ff;
-  asm("v_pk_fma_f32 %0, %1, %1, 1.0 op_sel_hi:[1,1,0] neg_lo:[1,0,0] neg_hi:[1,0,0]" : "=v"(ff) : "v"(hh));
-  return ff;
-}
-__device__ __forceinline__ f32x16 pk_1mh2_far(const f32x16& h) {
-  f32x16 o;
-#pragma unroll
-  for (int r = 0; r < 16; r += 2) {
-    const f32x2 ff = pk_1mh2_pair_far(f32x2{h[r], h[r + 1]});
-    o[r] = ff.x; o[r + 1] = ff.y;
-  }
-  return o;
-}
-// a fresh MFMA result times 1 - h^2 of values that came from the vector ALU or from LDS: the factor as one packed FMA with
-// modifiers (asm: its operands are not MFMA results), the product as a builtin (the compiler sees the MFMA -> VALU hazard)
-__device__ __forceinline__ f32x2 mul_1mh2_pair(float a0, float a1, float h0, float h1) {
-  const f32x2 ff = pk_1mh2_pair_far(f32x2{h0, h1});
-  f32x2 tt = {a0, a1};
-  tt *= ff;
-  return tt;
-}
-__device__ __forceinline__ void pk_mul_1mh2_far(f32x16& t, const f32x16& h) {
-#pragma unroll
-  for (int r = 0; r < 16; r += 2) {
-    f32x2 tt = {t[r], t[r + 1]};
-    const f32x2 ff = pk_1mh2_pair_far(f32x2{h[r], h[r + 1]});
-    asm("v_pk_mul_f32 %0, %0, %1" : "+v"(tt) : "v"(ff));
-    t[r] = tt.x; t[r + 1] = tt.y;
-  }
-}
-
-// bf16x3 (the cached Fisher-vector product's 64x64 products on v_mfma_f32_32x32x16_bf16): x = hi + mid + lo EXACTLY, each piece a
-// bf16 -- hi = x with the low 16 bits cleared, r = x - hi (exact), mid = r truncated the same way, lo = r - mid (exact; at most 8
-// significant bits, so a bf16 as it stands).  The upper halves of x, r, lo ARE the three bf16 pieces: two values per register by
-// one v_perm_b32.  Only single-issue 4-cycle instructions (no packed fp32: beside MFMAs each costs +22-26 cycles).  Of the 9 piece
-// products the 6 with i + j <= 2 are formed (tools/probe_split_error.py: FVP / CG-10 at native-fp32 distance from fp64).
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-#define MJX_MFMA_BF16(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, (a)), __builtin_bit_cast(bf16x8, (b)), (c), 0, 0, 0)
-struct Pc3 { u32x4 p[3]; };                      // hi, mid, lo: 8 bf16 each (one operand of v_mfma_f32_32x32x16_bf16)
-// values 2 k, 2 k + 1 of an operand -> register k of its three pieces (11 vector-ALU instructions)
-__device__ __forceinline__ void split3_pair(Pc3& o, int k, float xa, float xb) {
-  const uint32_t ua = __float_as_uint(xa), ub = __float_as_uint(xb);
-  const float ra = xa - __uint_as_float(ua & 0xffff0000u), rb = xb - __uint_as_float(ub & 0xffff0000u);
-  const uint32_t va = __float_as_uint(ra), vb = __float_as_uint(rb);
-  const float la = ra - __uint_as_float(va & 0xffff0000u), lb = rb - __uint_as_float(vb & 0xffff0000u);
-  o.p[0][k] = __builtin_amdgcn_perm(ub, ua, 0x07060302u);
-  o.p[1][k] = __builtin_amdgcn_perm(vb, va, 0x07060302u);
-  o.p[2][k] = __builtin_amdgcn_perm(__float_as_uint(lb), __float_as_uint(la), 0x07060302u);
-}
-__device__ __forceinline__ Pc3 split3(const float (&x)[8]) {
-  Pc3 o;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) split3_pair(o, k, x[2 * k], x[2 * k + 1]);
-  return o;
-}
-// the pieces of registers 8 s .. 8 s + 7 of a 32x32 accumulator (K-step s of the next layer's operand)
-__device__ __forceinline__ Pc3 split3_of(const f32x16& v, int s) {
-  float x[8];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) x[i] = v[8 * s + i];
-  return split3(x);
-}
-// acc += a * b over the six piece products, the small ones first
-__device__ __forceinline__ f32x16 mfma_bf3(const Pc3& a, const Pc3& b, f32x16 c) {
-  c = MJX_MFMA_BF16(a.p[2], b.p[0], c);
-  c = MJX_MFMA_BF16(a.p[0], b.p[2], c);
-  c = MJX_MFMA_BF16(a.p[1], b.p[1], c);
-  c = MJX_MFMA_BF16(a.p[1], b.p[0], c);
-  c = MJX_MFMA_BF16(a.p[0], b.p[1], c);
-  c = MJX_MFMA_BF16(a.p[0], b.p[0], c);
-  return c;
-}
-// ... and one of the six at a time (p = 0 .. 5 in mfma_bf3's order), for schedules that place every MFMA by hand
-__device__ __forceinline__ f32x16 mfma_bf3_step(const Pc3& a, const Pc3& b, f32x16 c, int p) {
-  const int pa = p == 0 ? 2 : (p == 2 || p == 3) ? 1 : 0, pb = p == 1 ? 2 : (p == 2 || p == 4) ? 1 : 0;
-  return MJX_MFMA_BF16(a.p[pa], b.p[pb], c);
-}
-// split3() one instruction at a time: step idx = 0 .. 43 of the 44 that split eight values, the same operations on the same
-// values as split3_pair.  Two register pairs (four values) advance together, so that four consecutive steps never depend on
-// each other -- what one MFMA gap carries: 4 ands (hi masks), 4 subtractions (r), 2 perms (hi pieces), 4 ands, 4 subtractions
-// (lo), 2 + 2 perms (mid, lo pieces); then the other two pairs.  w holds the intermediate values between the steps.
-// The steps are plain arithmetic, which the compiler places wherever the data flow allows -- scheduling barriers alone left the
-// 44 steps of a group in lumps of 0 .. 10 per gap.  So every step is tied to its gap from both sides: its constant (the mask, the
-// perm selector) comes from the gap's opening statement (SplitGap::open: an empty volatile asm that passes the two constants on
-// in their scalar registers and, as a memory barrier, keeps the gap's LDS accesses behind it), and its result passes through an
-// empty volatile asm of its own before anything uses it.  No instruction comes of either: one wave per SIMD issues in order, and
-// even a scalar move per gap would take an issue slot of the 8 a 32-cycle MFMA gap has.
-// The 44 steps over the 12 gaps of a K-step group: 3 in each of the first four, 4 in the other eight.  (The first gaps of a
-// phase are where the register allocator parks one or two values in AGPRs in the instances with the most registers; with
-// three steps they stay within the five vector instructions a gap hides.)  Steps of one gap never depend on each other.
-__device__ __forceinline__ constexpr int split3_first(int gap) { return gap < 4 ? 3 * gap : 4 * gap - 4; }
-struct Split3Tmp { uint32_t h[8], m[8]; float r[8], l[8]; };
-struct SplitGap {
-  uint32_t mask = 0xffff0000u, sel = 0x07060302u;
-  __device__ __forceinline__ void open() { asm volatile("" : "+s"(mask), "+s"(sel) : : "memory"); }
-};
-// (an MFMA builtin is as free to move as the arithmetic: its result takes the same way)
-__device__ __forceinline__ void mfma_pin(f32x16& c) { asm volatile("" : "+v"(c)); }
-__device__ __forceinline__ uint32_t split3_pin(uint32_t v) { asm volatile("" : "+v"(v)); return v; }
-__device__ __forceinline__ float split3_pin(float v) { asm volatile("" : "+v"(v)); return v; }
-__device__ __forceinline__ void split3_step(Pc3& o, Split3Tmp& w, const float (&x)[8], int idx, const SplitGap& c) {
-  const int b = idx / 22, t = idx % 22;
-  if (t < 4) { const int i = 4 * b + t; w.h[i] = split3_pin(__float_as_uint(x[i]) & c.mask); }
-  else if (t < 8) { const int i = 4 * b + t - 4; w.r[i] = split3_pin(x[i] - __uint_as_float(w.h[i])); }
-  else if (t < 10) { const int k = 2 * b + t - 8; o.p[0][k] = split3_pin(__builtin_amdgcn_perm(__float_as_uint(x[2 * k + 1]), __float_as_uint(x[2 * k]), c.sel)); }
-  else if (t < 14) { const int i = 4 * b + t - 10; w.m[i] = split3_pin(__float_as_uint(w.r[i]) & c.mask); }
-  else if (t < 18) { const int i = 4 * b + t - 14; w.l[i] = split3_pin(w.r[i] - __uint_as_float(w.m[i])); }
-  else if (t < 20) { const int k = 2 * b + t - 18; o.p[1][k] = split3_pin(__builtin_amdgcn_perm(__float_as_uint(w.r[2 * k + 1]), __float_as_uint(w.r[2 * k]), c.sel)); }
-  else { const int k = 2 * b + t - 20; o.p[2][k] = split3_pin(__builtin_amdgcn_perm(__float_as_uint(w.l[2 * k + 1]), __float_as_uint(w.l[2 * k]), c.sel)); }
-}
-
-// compile-time loop: f(std::integral_constant<int, 0>{}), ..., f(std::integral_constant<int, N - 1>{})
-template <int N, int I = 0, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-  if constexpr (I < N) { f(std::integral_constant<int, I>{}); static_for<N, I + 1>(f); }
-}
-
-// unit index (within a 32-block) held by accumulator register r of lane-half hi
-__device__ __forceinline__ constexpr int unit_of(int r, int hi) { return (r & 3) + 8 * (r >> 2) + 4 * hi; }
-
-template <int H1, int H2, int NT1, int MP>
-struct FusedLayout {
-  static constexpr int MT1 = H1 / 32, MT2 = H2 / 32;
-  static constexpr int S2 = H1 + 4;             // row stride of W2 (ds_read_b128, S2/4 odd)
-  static constexpr int ST = 36;                 // row stride of [unit][sample] scratch
-  static constexpr int S3 = H2 + 4;             // row stride of W3 ([MP][S3])
-  static constexpr int HM = (H1 > H2 ? H1 : H2);
-  int NP;                                       // features + ones column, padded to 4
-  int S1;                                       // row stride of xs / W1a (ds_read_b64, == 2 mod 4)
-  int oW1, oW2, oW3, oB2, oB3, SLOT;            // weight slot (one per parameter set)
-  int oXS, oXT, oD3, oBA, oBB, WAVE;            // per-wave scratch
-  int oTR, oCST, oWAVES, TOTAL;
-  static constexpr int NCST = 13;               // osc, osh, sigma, log_std (new) ; the same for old ; Dk = 2/(2 sigma^2 + 1e-8) ; {c3, osc^2 Dk / N} pairs ; 1/sigma new, old
-                                                // (MODE_EVAL keeps mean_kl's per-action constants in the rows only the other modes read: 2, 8, 9, 10 --
-                                                //  the 16-action 64 x 64 instance with 17 observations sits exactly AT the 160 KB limit, no row to spare)
-  // eval_only: the layout of MODE_EVAL launches -- no backward pass, so a wave's scratch is just the raw image of its
-  // observation tile (3.2 KB instead of 25 KB at HalfCheetah shapes); the workgroup then needs ~64 KB and TWO of them
-  // share a CU, i.e. two waves per SIMD: one wave's tanh / likelihood VALU work runs under the other's MFMAs
-  // bf3: the cached Fisher-vector product on bf16x3 MFMAs (k_fused<..., BF3 = true>).  After its prologue it reads no fp32 W2 of
-  // either slot: the prologue overwrites each slot's W2 region with that matrix's bf16 pieces (F2_IMG floats: V2 in R2's operand
-  // order in slot B, W2^T in R8's in slot A), so the region is padded to hold them.  The raw observation image xs is never read
-  // by the cached schedule (x~ comes from the cache) and has no room in it.
-  static constexpr int F2_IMG = 3 * H1 * H2 / 2;
-  __host__ __device__ explicit FusedLayout(int n, bool eval_only = false, bool bf3 = false) {
-    NP = (n + 1 + 3) & ~3;
-    S1 = NP + 2;
-    oW1 = 0;
-    oW2 = oW1 + H1 * S1;
-    oW3 = oW2 + ((bf3 && H2 * S2 < F2_IMG) ? F2_IMG : H2 * S2);   // [MP][S3]
-    oB2 = oW3 + MP * S3;
-    oB3 = oB2 + H2;
-    SLOT = ((oB3 + MP + 3) / 4) * 4;
-    oXS = 0;                                    // raw image of the tile: 32*n floats (+ float4 slack)
-    oXT = bf3 ? 0 : ((oXS + 32 * n + 4 * 64 + 3) / 4) * 4; // [NP][ST]
-    oD3 = oXT + NP * ST;                        // [MP][ST]
-    oBA = oD3 + MP * ST;                        // [HM][ST]
-    oBB = oBA + HM * ST;                        // [HM][ST]
-    WAVE = eval_only ? ((oXT + 3) / 4) * 4 : ((oBB + HM * ST + 3) / 4) * 4;
-    oTR = 2 * SLOT;                             // in_shift / in_scale of A and B: 4 * NP
-    oCST = oTR + 4 * NP;                        // per-action constants [NCST][MP]
-    oWAVES = oCST + NCST * MP;
-    TOTAL = oWAVES + 4 * WAVE;
-  }
-  __host__ __device__ size_t bytes() const { return (size_t)TOTAL * 4; }
-  __host__ __device__ bool fits(int n) const { return n + 1 <= 32 * NT1; }
-};
-
-// offsets into the flat parameter vector
-struct FlatOff {
-  int W1, b1, W2, b2, W3, b3, S, d;
-  __host__ __device__ FlatOff(int n, int m, int h1, int h2) {
-    W1 = 0; b1 = W1 + h1 * n; W2 = b1 + h1; b2 = W2 + h2 * h1; W3 = b2 + h2; b3 = W3 + m * h2; S = b3 + m; d = S + m;
-  }
-};
-
-// The gradient partial of a workgroup in ACCUMULATOR order (r06).  The kernels keep the weight gradients in MFMA accumulator
-// layout; writing a workgroup's partial in the flat parameter order cost every launch ~8 400 cycles (4 us: per-element index
-// arithmetic with the runtime observation width, scattered LDS writes) -- 4 % of a 1M-sample product, 8 % of a 125 k-sample one
-// (one rank of eight).  Now every wave drops register r of accumulator X at slot [X][r][lane] of its LDS copy (one ds_write with
-// an immediate offset), the four copies are added as they lie, and the COLUMN -> flat index map (a table made once per context
-// on the host: perm[], -1 for the padding slots) is applied where each column's 256 partials have been summed
-// (k_reduce_partials4).  Same additions in the same order: the same bits as the flat-order epilogue (MJX_RAW_SLAB=0).
-template <int H1, int H2, int NT1, int MP, int NPC>
-struct RawSlab {
-  static constexpr int MT1 = H1 / 32, MT2 = H2 / 32, RA = MP / 2;
-  static constexpr int QPI3 = 16 / (MP / 4), UPI3 = 4 * QPI3, NT3 = H2 / UPI3;
-  static constexpr int NFQ = NPC ? NPC / 4 : 1;
-  static constexpr int oW2 = 0, nW2 = MT2 * MT1 * 16 * 64;                         // [mt][nt][r][lane]
-  static constexpr int oW1 = oW2 + nW2, nW1 = NPC ? MT1 * NFQ * 4 * 32 : MT1 * NT1 * 16 * 64;   // [mt][fq][r][lane < 32] | [mt][nt][r][lane]
-  static constexpr int oW3 = oW1 + nW1, nW3 = NT3 * 4 * 64;                        // [nt][r][lane]
-  static constexpr int oB2 = oW3 + nW3, nB2 = MT2 * 32;                            // [nt][j]
-  static constexpr int oB3 = oB2 + nB2;                                            // [r][hi]
-  static constexpr int oS = oB3 + 2 * RA;                                          // [r][hi]
-  static constexpr int DR = ((oS + 2 * RA) + 3) & ~3;
-  static int unit(int r, int hi) { return (r & 3) + 8 * (r >> 2) + 4 * hi; }
-  // perm[slot] = flat parameter index (mirrors the flat-order epilogue of k_fused) or -1; -> true when every flat index is hit exactly once
-  static bool fill_perm(int* perm, int n, int m) {
-    const FlatOff fo(n, m, H1, H2);
-    for (int i = 0; i < DR; ++i) perm[i] = -1;
-    auto w1 = [&](int u, int f) { return f < n ? fo.W1 + u * n + f : f == n ? fo.b1 + u : -1; };
-    for (int mt = 0; mt < MT2; ++mt) for (int nt = 0; nt < MT1; ++nt) for (int r = 0; r < 16; ++r) for (int l = 0; l < 64; ++l)
-      perm[oW2 + ((mt * MT1 + nt) * 16 + r) * 64 + l] = fo.W2 + (32 * mt + unit(r, l >> 5)) * H1 + 32 * nt + (l & 31);
-    if (NPC) {
-      for (int mt = 0; mt < MT1; ++mt) for (int fq = 0; fq < NFQ; ++fq) for (int r = 0; r < 4; ++r) for (int l = 0; l < 32; ++l)
-        perm[oW1 + ((mt * NFQ + fq) * 4 + r) * 32 + l] = w1(32 * mt + 4 * ((l >> 2) & 7) + r, 4 * fq + (l & 3));
-    } else {
-      for (int mt = 0; mt < MT1; ++mt) for (int nt = 0; nt < NT1; ++nt) for (int r = 0; r < 16; ++r) for (int l = 0; l < 64; ++l)
-        perm[oW1 + ((mt * NT1 + nt) * 16 + r) * 64 + l] = w1(32 * mt + unit(r, l >> 5), 32 * nt + (l & 31));
-    }
-    for (int nt = 0; nt < NT3; ++nt) for (int r = 0; r < 4; ++r) for (int l = 0; l < 64; ++l) {
-      const int blk = l >> 2, a = 4 * (blk / QPI3) + r, u = 4 * (blk % QPI3) + (l & 3) + UPI3 * nt;
-      perm[oW3 + (nt * 4 + r) * 64 + l] = a < m ? fo.W3 + a * H2 + u : -1;
-    }
-    for (int nt = 0; nt < MT2; ++nt) for (int jj = 0; jj < 32; ++jj) perm[oB2 + nt * 32 + jj] = fo.b2 + 32 * nt + jj;
-    for (int r = 0; r < RA; ++r) for (int hi = 0; hi < 2; ++hi) {
-      const int a = unit(r, hi);
-      perm[oB3 + 2 * r + hi] = a < m ? fo.b3 + a : -1;
-      perm[oS + 2 * r + hi] = a < m ? fo.S + a : -1;
-    }
-    std::vector<int> hits(fo.d, 0);
-    for (int i = 0; i < DR; ++i) if (perm[i] >= 0) { if (perm[i] >= fo.d) return false; ++hits[perm[i]]; }
-    for (int i = 0; i < fo.d; ++i) if (hits[i] != 1) return false;
-    return true;
-  }
-};
 
 template <int H1, int H2, int NT1, int MP, int MODE, bool DBG = false, int NPC = 0, bool CACHED = false, bool BF3 = false, bool BF3R9 = false>
 __global__ __launch_bounds__(256, (MODE == MODE_EVAL && !DBG && MP <= 8) ? 2 : 1) void k_fused(FusedArgs A) {
@@ -458,6 +59,7 @@ __global__ __launch_bounds__(256, (MODE == MODE_EVAL && !DBG && MP <= 8) ? 2 : 1
   // ... and R9 (gW2 += delta2^T h1) as well: BF3R9 (MJX_FVP_BF16X3_R9=0 keeps it on fp32 MFMAs)
   constexpr bool XR9 = XBF3 && BF3R9;
   static_assert(!BF3R9 || BF3, "bf16x3 R9: an option of the bf16x3 kernel");
+  static_assert(!CACHED || MODE == MODE_FVP, "CACHED: the Fisher-vector product on K1's activation cache only");
   const LT L(NPC ? NPC - 1 : n, EV2, XBF3);
   const int NP = NPC ? NPC : L.NP;                // compile-time when the variant is specialised for the obs dim
   const int S1 = NP + 2;
@@ -518,14 +120,14 @@ __global__ __launch_bounds__(256, (MODE == MODE_EVAL && !DBG && MP <= 8) ? 2 : 1
   int mism = 0, mismx = 0;
   if (MODE == MODE_EVAL && A.ocache && !A.snap_trusted) {
     for (int idx = tid; idx < fo.d; idx += 256) mism |= (A.thetaB[idx] != A.snap[idx]);
-    for (int idx = tid; idx < 2 * (n + m); idx += 256) mism |= (A.trB[idx] != A.snap[fo.d + idx]);
+    for (int idx = tid; idx < tr_len(n, m); idx += 256) mism |= (A.trB[idx] != A.snap[fo.d + idx]);
     // K1's normalised-observation image (in the forward-activation cache) may stand in for staging + normalising the raw
     // observations again -- if the NEW policy's input transform is still the one K1 normalised with (= the snapshot's: K1
     // fills the caches only when old == new)
     if (A.hcache) for (int idx = tid; idx < 2 * n; idx += 256) mismx |= (A.trA[idx] != A.snap[fo.d + idx]);
   }
   if (MODE == MODE_VPG && A.snap_out) {           // every block copies a slice: at most a few elements per thread
-    const int nsnap = fo.d + 2 * (n + m);
+    const int nsnap = snap_len(fo.d, n, m);
     for (int idx = blockIdx.x * 256 + tid; idx < nsnap; idx += gridDim.x * 256)
       A.snap_out[idx] = idx < fo.d ? A.thetaB[idx] : A.trB[idx - fo.d];
   }
@@ -570,8 +172,7 @@ __global__ __launch_bounds__(256, (MODE == MODE_EVAL && !DBG && MP <= 8) ? 2 : 1
 
   // ---------------- per-action constants (LDS, broadcast reads) ----------------
   float* cst = lds + L.oCST;
-  enum { C_OSC = 0, C_OSH = 1, C_SG = 2, C_LS = 3, C_OSCB = 4, C_OSHB = 5, C_SGB = 6, C_LSB = 7, C_DK = 8, C_ISG = 11, C_ISGB = 12,   // (9, 10: the FVP's {c3, scale} pairs)
-         C_RD = 8, C_SO2 = 9, C_SN2 = 10, C_KD = 2 };       // MODE_EVAL only: 1 / Dr, sigma_old^2, sigma_new^2, log_std_new - log_std_old (over C_DK, the FVP pairs, C_SG)
+  using CR = CstRows;                           // cst[CR::row * MP + a]
   if (tid < MP) {
     const int a = tid;
     const bool ok = a < m;
@@ -579,36 +180,36 @@ __global__ __launch_bounds__(256, (MODE == MODE_EVAL && !DBG && MP <= 8) ? 2 : 1
     const float lsb = (ok && MODE != MODE_FVP) ? csr[1] : lsa;
     const float sga = ok ? expf(lsa) : 1.0f;
     const float dk = 2.0f / (2.0f * sga * sga + 1e-8f);
-    cst[C_OSC * MP + a] = ok ? csr[2] : 0.f;
-    cst[C_OSH * MP + a] = ok ? csr[3] : 0.f;
-    cst[C_SG * MP + a] = sga;
-    cst[C_LS * MP + a] = lsa;
-    cst[C_OSCB * MP + a] = ok ? csr[4] : 0.f;
-    cst[C_OSHB * MP + a] = ok ? csr[5] : 0.f;
-    cst[C_SGB * MP + a] = ok ? expf(lsb) : 1.0f;
-    cst[C_LSB * MP + a] = lsb;
-    cst[C_DK * MP + a] = dk;
+    cst[CR::C_OSC * MP + a] = ok ? csr[2] : 0.f;
+    cst[CR::C_OSH * MP + a] = ok ? csr[3] : 0.f;
+    cst[CR::C_SG * MP + a] = sga;
+    cst[CR::C_LS * MP + a] = lsa;
+    cst[CR::C_OSCB * MP + a] = ok ? csr[4] : 0.f;
+    cst[CR::C_OSHB * MP + a] = ok ? csr[5] : 0.f;
+    cst[CR::C_SGB * MP + a] = ok ? expf(lsb) : 1.0f;
+    cst[CR::C_LSB * MP + a] = lsb;
+    cst[CR::C_DK * MP + a] = dk;
     // (0 for the padding actions a >= m: their z is then 0 whatever the action registers hold -- the likelihood head takes
     //  the loaded values as they are, no select per action and sample)
-    cst[C_ISG * MP + a] = ok ? 1.0f / sga : 0.f;
-    cst[C_ISGB * MP + a] = ok ? 1.0f / cst[C_SGB * MP + a] : 0.f;
+    cst[CR::C_ISG * MP + a] = ok ? 1.0f / sga : 0.f;
+    cst[CR::C_ISGB * MP + a] = ok ? 1.0f / cst[CR::C_SGB * MP + a] : 0.f;
     if (MODE == MODE_EVAL) {
       // mean_kl (gaussian_mlp.py:135-145): what does not depend on the sample is formed once -- 1 / Dr with fast_div's own
       // reciprocal + Newton step (the per-sample quotient keeps its bits), sigma^2 of both nets, the log_std difference.
       // (r06: the head recomputed them per action and sample, 8 quarter-rate reciprocals and ~40 instructions per tile and wave.)
-      const float sgb = cst[C_SGB * MP + a];
+      const float sgb = cst[CR::C_SGB * MP + a];
       const float Dr = 2.0f * sga * sga + 1e-8f;
       float r = __builtin_amdgcn_rcpf(Dr);
       r = r * fmaf(-Dr, r, 2.0f);
-      cst[C_RD * MP + a] = r;
-      cst[C_SO2 * MP + a] = sgb * sgb;
-      cst[C_SN2 * MP + a] = sga * sga;
-      cst[C_KD * MP + a] = lsa - lsb;
+      cst[CR::C_RD * MP + a] = r;
+      cst[CR::C_SO2 * MP + a] = sgb * sgb;
+      cst[CR::C_SN2 * MP + a] = sga * sga;
+      cst[CR::C_KD * MP + a] = lsa - lsb;
     }
     if (MODE == MODE_FVP) {                       // FVP epilogue: d3 = (md + c3) * osc^2 * Dk / N
       const float osc = ok ? csr[2] : 0.f;
-      cst[9 * MP + 2 * a] = ok ? csr[6] : 0.f;
-      cst[9 * MP + 2 * a + 1] = osc * (dk * (osc * A.inv_N));
+      cst[CR::C_FVP2 * MP + 2 * a] = ok ? csr[6] : 0.f;
+      cst[CR::C_FVP2 * MP + 2 * a + 1] = osc * (dk * (osc * A.inv_N));
     }
   }
   // (flag word in wave 0's staging area, zero since the fill above and rewritten by the first tile's staging;
@@ -669,14 +270,14 @@ __global__ __launch_bounds__(256, (MODE == MODE_EVAL && !DBG && MP <= 8) ? 2 : 1
   if (MODE == MODE_FVP) {
 #pragma unroll
     for (int a = 0; a < MP; ++a) {
-      kc3[a] = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(cst[9 * MP + 2 * a])));
-      kcs[a] = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(cst[9 * MP + 2 * a + 1])));
+      kc3[a] = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(cst[CR::C_FVP2 * MP + 2 * a])));
+      kcs[a] = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(cst[CR::C_FVP2 * MP + 2 * a + 1])));
     }
   }
   float kc3r[RA], kcsr[RA];                       // the same for the actions this lane half owns: a = unit_of(r, hi)
   if (MODE == MODE_FVP) {
 #pragma unroll
-    for (int r = 0; r < RA; ++r) { kc3r[r] = cst[9 * MP + 2 * unit_of(r, hi)]; kcsr[r] = cst[9 * MP + 2 * unit_of(r, hi) + 1]; }
+    for (int r = 0; r < RA; ++r) { kc3r[r] = cst[CR::C_FVP2 * MP + 2 * unit_of(r, hi)]; kcsr[r] = cst[CR::C_FVP2 * MP + 2 * unit_of(r, hi) + 1]; }
   }
   // One wave-uniform base (scalar registers, formed on the scalar unit) + the lane's 32-bit byte offset + an immediate: no
   // vector-ALU address arithmetic per access.  (readfirstlane of a uniform value is a scalar move; it keeps the compiler from
@@ -689,7 +290,7 @@ __global__ __launch_bounds__(256, (MODE == MODE_EVAL && !DBG && MP <= 8) ? 2 : 1
     const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)a), hi32 = __builtin_amdgcn_readfirstlane((uint32_t)(a >> 32));
     return (gcptr)(((uint64_t)hi32 << 32) | lo);
   };
-  constexpr int OC_TILE = (MP + 1) * 32;
+  constexpr int OC_TILE = oc_tile(MP);
   float ocn[MP + 1];                              // next tile's old-policy outputs (MODE_EVAL)
   auto load_oc = [&](int64_t t) {
     gcptr b = ubase(A.ocache + t * OC_TILE);
@@ -758,8 +359,8 @@ __global__ __launch_bounds__(256, (MODE == MODE_EVAL && !DBG && MP <= 8) ? 2 : 1
   // forward-activation cache (sample-lane accumulator layout, 16-byte granules: [tile][mt][q][lane][4])
   // followed by the normalised observations as the layer-1 B-operand image [q][lane][2] = x~[sample j][4q + 2hi + {0,1}]
   // (ones column and zero pad included), so the cached FVP neither stages nor normalises the tile again.
-  constexpr int HC_H = (MT1 + MT2) * 4 * 64 * 4;              // floats per tile: activations ...
-  const int HC_TILE = HC_H + (NP / 4) * 128;                  // ... + observation image
+  constexpr int HC_H = LT::HC_H;                              // floats per tile: activations ...
+  const int HC_TILE = LT::hc_tile(NP);                        // ... + observation image
   constexpr int NQC = NPC ? NPC / 4 : 1;
   // cached FVP: h1 / h2 / observation image of the tile being processed.  The next tile's copies are fetched into the
   // same registers as soon as the current ones are dead (behind the weight-gradient products), so nothing is copied.
@@ -870,7 +471,7 @@ __global__ __launch_bounds__(256, (MODE == MODE_EVAL && !DBG && MP <= 8) ? 2 : 1
   float sum_lsA = 0.f, sum_lsB = 0.f;             // sum of log_std over the actions (new, old): constants of the likelihood head
   if (MODE != MODE_FVP) {
 #pragma unroll
-    for (int a = 0; a < MP; ++a) { sum_lsA += cst[C_LS * MP + a]; sum_lsB += cst[C_LSB * MP + a]; }
+    for (int a = 0; a < MP; ++a) { sum_lsA += cst[CR::C_LS * MP + a]; sum_lsB += cst[CR::C_LSB * MP + a]; }
   }
   uint32_t aoff = (uint32_t)(j * m * 4);          // the lane's row in a tile of the action block
   asm volatile("" : "+v"(aoff));
@@ -1553,7 +1154,7 @@ __global__ __launch_bounds__(256, (MODE == MODE_EVAL && !DBG && MP <= 8) ? 2 : 1
         for (int q = 0; q < NQX; ++q) *(f32x2 __attribute__((address_space(1)))*)(xb + (uint32_t)(lane * 8) + q * 512) = xn[q];
       }
     }
-    if (!DIRX && !XCACHED && !XI) {
+    if (!DIRX && !XI) {
 #pragma unroll
       for (int c = 0; c < XL4; ++c) {
         const int e4 = c * 64 + lane;
@@ -1571,7 +1172,6 @@ __global__ __launch_bounds__(256, (MODE == MODE_EVAL && !DBG && MP <= 8) ? 2 : 1
     auto layers12 = [&](auto tan_tag, const float* slot, const float* tsh, const float* tsc, bool writeT,
                         f32x16 (&h1)[MT1], f32x16 (&h2)[MT2], f32x16 (&t1)[MT1], f32x16 (&t2)[MT2], const f32x2 (&xdir)[NQX]) {
       constexpr bool TAN = decltype(tan_tag)::value;
-      constexpr bool FWD = !(TAN && CACHED);          // cached FVP: h1 / h2 arrive from HBM, only the tangent products run
       f32x16 z1[MT1];
 #pragma unroll
       for (int mt = 0; mt < MT1; ++mt) { z1[mt] = (f32x16)(0.f); if (TAN) t1[mt] = (f32x16)(0.f); }
@@ -1586,12 +1186,9 @@ __global__ __launch_bounds__(256, (MODE == MODE_EVAL && !DBG && MP <= 8) ? 2 : 1
           const float v = (xs[j * n + f] - tsh[f]) * tsc[f];
           return (f == n) ? 1.0f : (valid ? v : 0.0f);
         };
-        const float* ximg = A.hcache + tile * HC_TILE + HC_H + lane * 2;
-        // group q's pair of features for this lane: computed, or (cached FVP) read back as K1 stored it
+        // group q's pair of features for this lane: computed, or (K3 on K1's image) read back as K1 stored it
         auto xpair = [&](int q) {
-          if constexpr (TAN && CACHED) {
-            if constexpr (NPC != 0) return xc[q]; else return *(const f32x2*)(ximg + q * 128);
-          } else if constexpr (XI) {
+          if constexpr (XI) {
             return xc[q];
           } else if constexpr (DIRX) {
             return xdir[q];
@@ -1604,7 +1201,7 @@ __global__ __launch_bounds__(256, (MODE == MODE_EVAL && !DBG && MP <= 8) ? 2 : 1
         float xb0 = xb.x, xb1 = xb.y;
 #pragma unroll
         for (int mt = 0; mt < MT1; ++mt) {
-          if (FWD) wc[mt] = *(const f32x2*)&slot[L.oW1 + (32 * mt + j) * S1 + f00];
+          wc[mt] = *(const f32x2*)&slot[L.oW1 + (32 * mt + j) * S1 + f00];
           if (TAN) vc[mt] = *(const f32x2*)&slotB[L.oW1 + (32 * mt + j) * S1 + f00];
         }
 #pragma unroll NPC ? NPC / 4 : 1
@@ -1617,24 +1214,24 @@ __global__ __launch_bounds__(256, (MODE == MODE_EVAL && !DBG && MP <= 8) ? 2 : 1
           if (!DIRX && MODE == MODE_VPG && writeT && A.hcache) *(f32x2*)(A.hcache + tile * HC_TILE + HC_H + (q * 64 + lane) * 2) = f32x2{xb0, xb1};
 #pragma unroll
           for (int mt = 0; mt < MT1; ++mt) {
-            if (FWD) wn[mt] = *(const f32x2*)&slot[L.oW1 + (32 * mt + j) * S1 + f1];
+            wn[mt] = *(const f32x2*)&slot[L.oW1 + (32 * mt + j) * S1 + f1];
             if (TAN) vn[mt] = *(const f32x2*)&slotB[L.oW1 + (32 * mt + j) * S1 + f1];
           }
           const float x0 = xb0, x1 = xb1;
           if (writeT) { xT[f0 * ST + j] = x0; xT[(f0 + 1) * ST + j] = x1; }
 #pragma unroll
           for (int mt = 0; mt < MT1; ++mt) {
-            if (FWD) z1[mt] = MJX_MFMA(wc[mt].x, x0, z1[mt]);
+            z1[mt] = MJX_MFMA(wc[mt].x, x0, z1[mt]);
             if (TAN) t1[mt] = MJX_MFMA(vc[mt].x, x0, t1[mt]);
           }
 #pragma unroll
           for (int mt = 0; mt < MT1; ++mt) {
-            if (FWD) z1[mt] = MJX_MFMA(wc[mt].y, x1, z1[mt]);
+            z1[mt] = MJX_MFMA(wc[mt].y, x1, z1[mt]);
             if (TAN) t1[mt] = MJX_MFMA(vc[mt].y, x1, t1[mt]);
           }
           xb0 = xn0; xb1 = xn1;
 #pragma unroll
-          for (int mt = 0; mt < MT1; ++mt) { if (FWD) wc[mt] = wn[mt]; if (TAN) vc[mt] = vn[mt]; }
+          for (int mt = 0; mt < MT1; ++mt) { wc[mt] = wn[mt]; if (TAN) vc[mt] = vn[mt]; }
         }
       }
       MJX_STAMP(2);
@@ -1647,7 +1244,7 @@ __global__ __launch_bounds__(256, (MODE == MODE_EVAL && !DBG && MP <= 8) ? 2 : 1
       if constexpr (BURST) { __builtin_amdgcn_sched_barrier(0); if (EV2) __builtin_amdgcn_s_setprio(3); }
 #pragma unroll
       for (int mt = 0; mt < MT1; ++mt) {
-        if (FWD) fast_tanh16(h1[mt], z1[mt]);
+        fast_tanh16(h1[mt], z1[mt]);
         if (TAN) pk_mul_1mh2(t1[mt], h1[mt]);
       }
       if constexpr (BURST) { if (EV2) __builtin_amdgcn_s_setprio(0); __builtin_amdgcn_sched_barrier(0); }
@@ -1669,10 +1266,8 @@ __global__ __launch_bounds__(256, (MODE == MODE_EVAL && !DBG && MP <= 8) ? 2 : 1
       for (int mt = 0; mt < MT2; ++mt)
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-          if (FWD) {
-            f32x4 b = *(const f32x4*)&slot[L.oB2 + 32 * mt + 8 * q + 4 * hi];
-            z2[mt][4 * q + 0] = b.x; z2[mt][4 * q + 1] = b.y; z2[mt][4 * q + 2] = b.z; z2[mt][4 * q + 3] = b.w;
-          }
+          f32x4 b = *(const f32x4*)&slot[L.oB2 + 32 * mt + 8 * q + 4 * hi];
+          z2[mt][4 * q + 0] = b.x; z2[mt][4 * q + 1] = b.y; z2[mt][4 * q + 2] = b.z; z2[mt][4 * q + 3] = b.w;
           if (TAN) {
             f32x4 c = *(const f32x4*)&slotB[L.oB2 + 32 * mt + 8 * q + 4 * hi];
             t2[mt][4 * q + 0] = c.x; t2[mt][4 * q + 1] = c.y; t2[mt][4 * q + 2] = c.z; t2[mt][4 * q + 3] = c.w;
@@ -1696,7 +1291,7 @@ __global__ __launch_bounds__(256, (MODE == MODE_EVAL && !DBG && MP <= 8) ? 2 : 1
           for (int t = 0; t < 4; ++t)
 #pragma unroll
             for (int mt = 0; mt < MT2; ++mt) {
-              if (FWD) z2[mt] = MJX_MFMA(wc[mt][t], h1[kb][4 * q + t], z2[mt]);
+              z2[mt] = MJX_MFMA(wc[mt][t], h1[kb][4 * q + t], z2[mt]);
               if (TAN) t2[mt] = MJX_MFMA(wc[mt][t], t1[kb][4 * q + t], t2[mt]);
             }
 #pragma unroll
@@ -1728,7 +1323,7 @@ __global__ __launch_bounds__(256, (MODE == MODE_EVAL && !DBG && MP <= 8) ? 2 : 1
 #pragma unroll
           for (int e = 0; e < R2; ++e) {
             const int idx = st * R2 + e, mt = idx >> 4, r = idx & 15;
-            if (FWD) h2[mt][r] = fast_tanh(z2[mt][r]);
+            h2[mt][r] = fast_tanh(z2[mt][r]);
             if constexpr (PINNED) LDS_AT(pinA[4 * mt + (r >> 2)])[(r & 3) * ST] = h2[mt][r];
             else bufA[(32 * mt + unit_of(r, hi)) * ST + j] = h2[mt][r];
           }
@@ -1832,9 +1427,7 @@ __global__ __launch_bounds__(256, (MODE == MODE_EVAL && !DBG && MP <= 8) ? 2 : 1
     };
 
     MJX_STAMP(1);
-    f32x16 h1l[MT1], h2l[MT2];
-    f32x16 (&h1)[MT1] = XCACHED ? hn1 : h1l;
-    f32x16 (&h2)[MT2] = XCACHED ? hn2 : h2l;
+    f32x16 h1[MT1], h2[MT2];
     f32x16 t1[MT1], t2[MT2];                        // tangent activations (FVP only)
     if (MODE == MODE_FVP) layers12(std::true_type{}, slotA, trs, trs + NP, true, h1, h2, t1, t2, xn);
     else layers12(std::false_type{}, slotA, trs, trs + NP, MODE != MODE_EVAL, h1, h2, t1, t2, xn);
@@ -1886,7 +1479,7 @@ __global__ __launch_bounds__(256, (MODE == MODE_EVAL && !DBG && MP <= 8) ? 2 : 1
       if (DBG) {
 #pragma unroll
         for (int a = 0; a < MP; ++a)
-          if (A.dbg && blockIdx.x == 0 && wave == 0 && tile == 0 && hi == 0) A.dbg[2048 * 4 + a * 32 + j] = cst[C_OSC * MP + a] * (md[a] + kc3[a]);
+          if (A.dbg && blockIdx.x == 0 && wave == 0 && tile == 0 && hi == 0) A.dbg[2048 * 4 + a * 32 + j] = cst[CR::C_OSC * MP + a] * (md[a] + kc3[a]);
       }
       // Each lane half needs the full sums of ITS actions only (a = unit_of(r, hi): group 2(r>>2) + hi, column r&3):
       // v_permlane32_swap of the two groups' partial sums hands the lower half both halves' values of group 2(r>>2)
@@ -1912,8 +1505,8 @@ __global__ __launch_bounds__(256, (MODE == MODE_EVAL && !DBG && MP <= 8) ? 2 : 1
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int gp = 0; gp < NGRP; ++gp) {
-          kb3[gp] = *(const f32x4*)&slotA[L.oB3 + 4 * gp]; kosc[gp] = *(const f32x4*)&cst[C_OSC * MP + 4 * gp];
-          kosh[gp] = *(const f32x4*)&cst[C_OSH * MP + 4 * gp]; kisg[gp] = *(const f32x4*)&cst[C_ISG * MP + 4 * gp];
+          kb3[gp] = *(const f32x4*)&slotA[L.oB3 + 4 * gp]; kosc[gp] = *(const f32x4*)&cst[CR::C_OSC * MP + 4 * gp];
+          kosh[gp] = *(const f32x4*)&cst[CR::C_OSH * MP + 4 * gp]; kisg[gp] = *(const f32x4*)&cst[CR::C_ISG * MP + 4 * gp];
         }
         __builtin_amdgcn_sched_barrier(0);
       }
@@ -1933,8 +1526,8 @@ __global__ __launch_bounds__(256, (MODE == MODE_EVAL && !DBG && MP <= 8) ? 2 : 1
           muv[a] = (oa[a] + kb3[a >> 2][a & 3]) * kosc[a >> 2][a & 3] + kosh[a >> 2][a & 3];
           z[a] = (av[a] - muv[a]) * kisg[a >> 2][a & 3];
         } else {
-          muv[a] = (oa[a] + slotA[L.oB3 + a]) * cst[C_OSC * MP + a] + cst[C_OSH * MP + a];
-          z[a] = (av[a] - muv[a]) * cst[C_ISG * MP + a];
+          muv[a] = (oa[a] + slotA[L.oB3 + a]) * cst[CR::C_OSC * MP + a] + cst[CR::C_OSH * MP + a];
+          z[a] = (av[a] - muv[a]) * cst[CR::C_ISG * MP + a];
         }
         llA = fmaf(-0.5f * z[a], z[a], llA);
       }
@@ -1972,8 +1565,8 @@ __global__ __launch_bounds__(256, (MODE == MODE_EVAL && !DBG && MP <= 8) ? 2 : 1
         llB = 0.f;
 #pragma unroll
         for (int a = 0; a < MP; ++a) {
-          muB[a] = (ob[a] + slotB[L.oB3 + a]) * cst[C_OSCB * MP + a] + cst[C_OSHB * MP + a];
-          float zb = (av[a] - muB[a]) * cst[C_ISGB * MP + a];
+          muB[a] = (ob[a] + slotB[L.oB3 + a]) * cst[CR::C_OSCB * MP + a] + cst[CR::C_OSHB * MP + a];
+          float zb = (av[a] - muB[a]) * cst[CR::C_ISGB * MP + a];
           llB = fmaf(-0.5f * zb, zb, llB);
         }
         llB = llB - sum_lsB - llc;
@@ -1988,8 +1581,8 @@ __global__ __launch_bounds__(256, (MODE == MODE_EVAL && !DBG && MP <= 8) ? 2 : 1
 #pragma unroll
         for (int a = 0; a < MP; ++a) {
           const float dm = muB[a] - muv[a];
-          const float Nr = (dm * dm + cst[C_SO2 * MP + a]) - cst[C_SN2 * MP + a];
-          kl += Nr * cst[C_RD * MP + a] + cst[C_KD * MP + a];
+          const float Nr = (dm * dm + cst[CR::C_SO2 * MP + a]) - cst[CR::C_SN2 * MP + a];
+          kl += Nr * cst[CR::C_RD * MP + a] + cst[CR::C_KD * MP + a];
         }
         if (valid && hi == 0) s_kl += (double)kl;
       } else {
@@ -1998,7 +1591,7 @@ __global__ __launch_bounds__(256, (MODE == MODE_EVAL && !DBG && MP <= 8) ? 2 : 1
 #pragma unroll
         for (int a = 0; a < MP; ++a) {
           if constexpr (HK) d3a[a] = kosc[a >> 2][a & 3] * ((w * z[a]) * kisg[a >> 2][a & 3]);
-          else d3a[a] = cst[C_OSC * MP + a] * ((w * z[a]) * cst[C_ISG * MP + a]);
+          else d3a[a] = cst[CR::C_OSC * MP + a] * ((w * z[a]) * cst[CR::C_ISG * MP + a]);
         }
 #pragma unroll
         for (int r = 0; r < RA; ++r) {
@@ -2064,7 +1657,9 @@ __global__ __launch_bounds__(256, (MODE == MODE_EVAL && !DBG && MP <= 8) ? 2 : 1
       for (int mt = 0; mt < MT2; ++mt)
 #pragma unroll
         for (int r = 0; r < 16; r += 2) { const f32x2 v = mul_1mh2_pair(dl2s[mt][r], dl2s[mt][r + 1], h2[mt][r], h2[mt][r + 1]); dl2s[mt][r] = v.x; dl2s[mt][r + 1] = v.y; }
-      // h1 / h2 are dead from here on: fetch the next tile's copies behind the weight-gradient products
+      // (never taken: CACHED products run the other schedule.  Kept, because without it the tile loop no longer names load_h and K1 / K3
+      //  allocate the registers of their fp64 sums in another order -- the one dead statement whose deletion changed compiled code,
+      //  and bench.py's step was 0.25 % slower with it gone: profiles/r22_fused_phases)
       if (MODE == MODE_FVP && CACHED && tile + tstride < ntiles) load_h(tile + tstride);
       wave_sync();
       MJX_STAMP(9);

@@ -23,7 +23,7 @@
 #include <utility>
 #include <vector>
 
-#include "fused_policy.h"
+#include "mfma_prims.h"
 #include "launch_state.h"
 #include "lw_head.h"
 #include "lw_launch.h"

@@ -8,7 +8,7 @@
 #include <type_traits>
 #include <utility>
 
-#include "fused_policy.h"
+#include "mfma_prims.h"
 #include "lw_plan.h"
 
 namespace mjx {

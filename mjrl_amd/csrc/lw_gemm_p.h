@@ -27,7 +27,7 @@
 
 #include <type_traits>
 
-#include "fused_policy.h"
+#include "mfma_prims.h"
 #include "lw_plan.h"       // GemmArgs, the EPI_* kinds, the GP_* tile geometry and gp_lds_bytes
 
 namespace mjx {

@@ -23,7 +23,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "fused_policy.h"
+#include "mfma_prims.h"
 
 #ifndef MJX_HEAD_EXP
 #define MJX_HEAD_EXP 0        // timing experiments (results WRONG): 1 = k_lw_head8 without phase 2, 2 = without phase 1's k-loop.

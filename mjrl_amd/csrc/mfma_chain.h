@@ -17,7 +17,7 @@
 #include <stdint.h>
 
 #include "dynamics.h"
-#include "fused_policy.h"
+#include "mfma_prims.h"
 
 namespace mjx {
 

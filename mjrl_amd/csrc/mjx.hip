@@ -168,7 +168,7 @@ int mjx_create(mjx_ctx** out, int device, int n, int m, const int* hidden, int n
   if (int rc = c->fz.init(n, m, d, c->oS, c->hidden, cu_count(), env_flag("MJX_FORCE_LAYERWISE", false))) return rc;
   if (int rc = c->cg.alloc(d)) return rc;
   c->tp.init(device, d, c->cg.ticket);
-  std::vector<float> id(2 * n + 2 * m, 0.f);
+  std::vector<float> id(tr_len(n, m), 0.f);
   for (int i = 0; i < n; ++i) id[n + i] = 1.f;
   for (int i = 0; i < m; ++i) id[2 * n + m + i] = 1.f;
   HIPCHK(hipMalloc(&c->ident_tr, id.size() * 4));

@@ -14,7 +14,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "fused_policy.h"
+#include "mfma_prims.h"
 #include "vecops.h"
 
 namespace mjx {

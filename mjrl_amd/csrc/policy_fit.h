@@ -21,7 +21,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "fused_policy.h"
+#include "mfma_prims.h"
 #include "vecops.h"
 
 namespace mjx {
@@ -105,7 +105,7 @@ template <int CTRL>
 __device__ __forceinline__ float dpp_move(float v) {
   return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
 }
-// (row16_sum -- the sum over the 16 lanes of a DPP row -- lives in fused_policy.h)
+// (row16_sum -- the sum over the 16 lanes of a DPP row -- lives in mfma_prims.h)
 
 #define MJX_MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
 

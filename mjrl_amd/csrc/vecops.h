@@ -24,7 +24,7 @@ constexpr float ADAM32_B1 = 0.9f, ADAM32_C1 = 1.0f - 0.9f, ADAM32_B2 = 0.999f, A
 struct AdamTorch { static constexpr float C1 = ADAM_C1, B2 = ADAM_B2, C2 = ADAM_C2; };
 struct AdamFp32Betas { static constexpr float C1 = ADAM32_C1, B2 = ADAM32_B2, C2 = ADAM32_C2; };
 
-typedef float f32x2 __attribute__((ext_vector_type(2)));      // (fused_policy.h's; the packed fp32 forms below)
+typedef float f32x2 __attribute__((ext_vector_type(2)));      // (mfma_prims.h's; the packed fp32 forms below)
 
 // torch.optim.Adam's update of one step (L2 weight decay folded into the gradient, bias-corrected) with the constant set K and
 // the two divides as v_rcp_f32 + one Newton step (<= 1 ulp from IEEE): ~18 vector-ALU instructions per weight, ~12 in the
@@ -235,7 +235,7 @@ __global__ __launch_bounds__(256) void k_reduce_partials4(const float* __restric
                                                            const float* v, int oS, float frac, PeerPush pp = PeerPush{},
                                                            ScalTail stl = ScalTail{nullptr, 0, nullptr, -1},
                                                            const int* __restrict__ perm = nullptr) {
-  // perm (r06): the partials' columns are in the fused kernels' accumulator order (fused_policy.h RawSlab); column c belongs to
+  // perm (r06): the partials' columns are in the fused kernels' accumulator order (fused_layout.h RawSlab); column c belongs to
   // flat index perm[c] (-1: a padding slot) -- `d` is then the slab width, and theta / v / out / the peers' slots are indexed flat
   typedef float f4 __attribute__((ext_vector_type(4)));
   __shared__ double sh[32][33];

@@ -68,7 +68,7 @@ def trunc16(x):
 
 
 def split_trunc(x):
-    """the kernel's exact split (fused_policy.h split3): hi = trunc(x), r = x - hi, mid = trunc(r), lo = r - mid; hi + mid + lo == x"""
+    """the kernel's exact split (bf16x3.h split3): hi = trunc(x), r = x - hi, mid = trunc(r), lo = r - mid; hi + mid + lo == x"""
     x = x.astype(np.float32)
     hi = trunc16(x)
     r = x - hi

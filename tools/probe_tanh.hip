@@ -1,5 +1,5 @@
 // probe_tanh.hip -- does a one-transcendental tanh beat the exp2 + rcp form the fused kernels use?
-//   A  fast_tanh of csrc/fused_policy.h: 1 - 2 / (1 + exp2(2 log2(e) x))          v_exp_f32 + v_rcp_f32 + 3 packed-able ops
+//   A  fast_tanh of csrc/mfma_prims.h: 1 - 2 / (1 + exp2(2 log2(e) x))          v_exp_f32 + v_rcp_f32 + 3 packed-able ops
 //   B  odd rational x P(x^2) / Q(x^2), degrees 13 / 6, clamped at |x| = 7.905         v_rcp_f32 + 2 clamps + 1 + 6 + 3 + 2 FMA / mul
 //      (the coefficients of the well-known single-precision rational fit; what fp32-level accuracy costs)
 //   C  the same rational at degrees 9 / 4 -- fewer FMAs, accuracy NOT at fp32 level: shown for the cycle count only
