@@ -553,6 +553,24 @@ int mjx_plan_route(const int* dyn_sizes, int dyn_n_sizes, int act_dim);
 int mjx_plan_rollout(const float* s0, int64_t s0_stride, int64_t N, int H, int K, const float* actions,
                      const int* dyn_sizes, int dyn_n_sizes, const float* dyn_params, const float* dyn_tr, int act,
                      int flags, float* obs_out, void* stream);
+/* Whether the wide MFMA plan rollout (csrc/plan_wide.h: activations as LDS tiles, weights streamed from global memory, one
+ * workgroup per tile of 32 trajectories of one member) serves a net dyn_sizes = [n + act_dim, h1, h2, n]: 1 = served: exactly
+ * two hidden layers, each width 1 .. 256, n <= 64, act_dim <= 64, n + act_dim <= 128 and the layout -- n + pad8(n + m) +
+ * pad32(h1) + pad32(h2) + pad32(n) rows of 36 floats (S, XD, H1, H2, Z3), then h1 + h2 + 5 n + 2 m floats of biases and
+ * transforms -- within 160 KiB (it always is: at most 114 432 bytes, at n = m = 64 and 256 x 256); 0 = not served; < 0 = bad
+ * sizes (as mjx_plan_route).  Arithmetic only: no device work and no runtime call.  The answer does not depend on
+ * mjx_plan_route's: the shapes the register-resident kernel takes are served as well. */
+int mjx_plan_rollout_wide_route(const int* dyn_sizes, int dyn_n_sizes, int act_dim);
+/* mjx_plan_rollout with the wide kernel in front of it: the same arguments in the same order, then route_out.  Where
+ * mjx_plan_rollout_wide_route serves the shape it runs k_plan_rollout_wide and reports route 2 in *route_out (a host int, may
+ * be NULL); otherwise, under MJX_PLAN_WIDE=0, under MJX_PLAN_MFMA=0 (both read per call) and after an LDS refusal it IS
+ * mjx_plan_rollout: same routing, same bits, *route_out 1 where mjx_plan_route serves and MJX_PLAN_MFMA is on, else 0.  N = 0 or
+ * H = 0 returns MJX_OK without a launch (and reports the route); bad arguments -- flag bits other than 1 | 2 | 4 among them --
+ * return MJX_ERR_ARG and touch nothing.  Route 2 uses no scratch, no atomics and no reductions across lanes: its bits are the
+ * same on every run. */
+int mjx_plan_rollout_wide(const float* s0, int64_t s0_stride, int64_t N, int H, int K, const float* actions,
+                          const int* dyn_sizes, int dyn_n_sizes, const float* dyn_params, const float* dyn_tr, int act,
+                          int flags, float* obs_out, int* route_out, void* stream);
 /* score_trajectory_ensemble (model_learning_mpc.py:85-99) and the softmax weighting (:70-74) in fp64 with fixed
  * summation orders.  obs: K x N x H x n fp32 (mjx_plan_rollout's output), rewards: K x N x H fp64, actions: N x H x m
  * fp64.  disagreement[i] = sum over (t, j) of the population standard deviation over the K members;

@@ -118,6 +118,9 @@ PROTOTYPES = {
     "mjx_plan_route": (c_int, [ctypes.POINTER(c_int), c_int, c_int]),
     "mjx_plan_rollout": (c_int, [c_void_p, c_int64, c_int64, c_int, c_int, c_void_p, ctypes.POINTER(c_int), c_int, c_void_p, c_void_p, c_int,
                                  c_int, c_void_p, c_void_p]),
+    "mjx_plan_rollout_wide_route": (c_int, [ctypes.POINTER(c_int), c_int, c_int]),
+    "mjx_plan_rollout_wide": (c_int, [c_void_p, c_int64, c_int64, c_int, c_int, c_void_p, ctypes.POINTER(c_int), c_int, c_void_p, c_void_p, c_int,
+                                      c_int, c_void_p, ctypes.POINTER(c_int), c_void_p]),
     "mjx_plan_score": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_int, c_double, c_double, c_double, c_int,
                                c_void_p, c_void_p, c_void_p, c_void_p]),
     "mjx_path_rewards_route": (c_int, [ctypes.POINTER(c_int), c_int, ctypes.POINTER(c_int), c_int]),

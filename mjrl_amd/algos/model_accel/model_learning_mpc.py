@@ -8,7 +8,13 @@ constructor arguments, attributes and ``get_action`` semantics, the warm-start s
    for bit and leaves the stream where they leave it;
 2. one upload of the fp64 actions, cast to fp32 on the device (the reference's ``.float()``);
 3. ``mjx_plan_rollout``: all K members in one launch (csrc/plan.h; the register-resident MFMA rollout where the net's shape
-   allows it -- ``mjx_plan_route`` -- and the generic persistent rollout otherwise);
+   allows it -- ``mjx_plan_route`` -- and the generic persistent rollout otherwise).  With ``wide=True`` members with two
+   hidden layers and a dynamics width above 128 (``nn_dynamics.wide_rows_shape``; 256 x 256 is the reference's own configs) go
+   to ``mjx_plan_rollout_wide`` instead: the same arguments, the wide MFMA rollout of csrc/plan_wide.h (route 2), and on
+   ``reward='learned'`` ``mjx_path_rewards_wide`` (csrc/rows_wide.h).  ``MJX_PLAN_WIDE=0`` / ``MJX_PATH_REWARDS_WIDE=0`` make
+   those calls the narrow entries, bit for bit.  ``wide`` is False by default: a planner built as before makes the calls and
+   reports the routes it did before (``route()`` is 0 on a 256-wide ensemble), although the wide route is the faster one
+   there (DESIGN.md section 7c);
 4. one read-back of the (K, N, H, n) observations and K calls of ``env.env.env.compute_path_rewards(paths)``, the reference's
    reward contract, which stays a host callback: it gets a dict of that member's fp32 observations and the fp64 actions;
 5. one upload of the (K, N, H) rewards, ``mjx_plan_score`` (disagreement, discounted returns, softmax weights and the weighted
@@ -33,11 +39,14 @@ environment is never asked for rewards, so it needs no ``compute_path_rewards``.
 the MEMBER index of row i, so the disagreement of trajectories 0 .. K-1 is what every member's rows get.  True (default)
 reproduces that; False uses the evidently intended per-trajectory index ``i % num_traj``.
 """
+import ctypes
+import os
+
 import numpy as np
 import torch
 
 from ..._lib import check, load, ptr
-from .nn_dynamics import _device, _ints, _stream, cached_members_pack, members_pack_key, path_rewards_call
+from .nn_dynamics import _device, _ints, _stream, cached_members_pack, members_pack_key, path_rewards_call, wide_rows_shape
 
 
 def perturbed_action_batch(num_traj, base_act, filter_coefs):
@@ -53,8 +62,15 @@ def perturbed_action_batch(num_traj, base_act, filter_coefs):
     return u
 
 
+def _switch_on(name):
+    """a route switch as the library reads it per call (on unless the variable starts with 0)"""
+    return os.environ.get(name, "1")[:1] != "0"
+
+
 class MPCPolicy(object):
     reward = 'env'              # (an instance pickled before the keyword existed plans as it did)
+    _routes = None
+    wide = False                # (an instance pickled before the keyword existed plans as it did)
 
     def __init__(self, env,
                  plan_horizon,
@@ -69,10 +85,12 @@ class MPCPolicy(object):
                  omega=5.0,
                  reference_indexing=True,
                  reward='env',
+                 wide=False,
                  **kwargs,
                  ):
-        """Arguments as in the reference (model_learning_mpc.py:6-40), plus reference_indexing and reward ('env': the
-        environment's compute_path_rewards on the host; 'learned': the members' reward nets on the device; module docstring)."""
+        """Arguments as in the reference (model_learning_mpc.py:6-40), plus reference_indexing, reward ('env': the
+        environment's compute_path_rewards on the host; 'learned': the members' reward nets on the device; module docstring) and
+        wide (True: ensembles wider than 128 plan on the wide MFMA entries; module docstring, step 3)."""
         self.env, self.seed = env, seed
         self.n, self.m = env.observation_dim, env.action_dim
         self.plan_horizon, self.num_traj = plan_horizon, plan_paths
@@ -95,13 +113,15 @@ class MPCPolicy(object):
         if reward == 'learned' and not all(getattr(mdl, "learn_reward", False) for mdl in self._members()):
             raise ValueError("reward='learned' needs every member to be a WorldModel(learn_reward=True)")
         self.reward = reward
+        self.wide = bool(wide)
         self._pack = None           # (key, device blocks) of the members' parameters and transforms
         self._last = None           # device blocks of the last call's scores (and, on learned rewards, the rewards)
+        self._routes = None         # the routes the last call's entries reported
 
     # ---- device state
     def __getstate__(self):
         d = dict(self.__dict__)
-        d["_pack"], d["_last"] = None, None
+        d["_pack"], d["_last"], d["_routes"] = None, None, None
         return d
 
     def _members(self):
@@ -123,9 +143,19 @@ class MPCPolicy(object):
         """drop the device copy of the members (after a write to ``p.data`` that went round this package's own functions)"""
         self._pack = None
 
+    def _wide(self):
+        """whether these members go to the ``_wide`` entries: asked for (``wide=True``) and ``nn_dynamics.wide_rows_shape`` (plain
+        Python, narrower than the kernels)"""
+        return self.wide and wide_rows_shape(tuple(self._members()[0].dynamics_net.layer_sizes))
+
     def route(self):
-        """1: the register-resident MFMA rollout serves these members, 0: the generic rollout (mjx_plan_route)"""
+        """2: the wide MFMA rollout serves these members (mjx_plan_rollout_wide_route, asked for the shapes :meth:`_wide` sends
+        there, with MJX_PLAN_WIDE and MJX_PLAN_MFMA as they stand now), 1: the register-resident MFMA rollout, 0: the generic
+        rollout (mjx_plan_route)"""
         sizes = tuple(self._members()[0].dynamics_net.layer_sizes)
+        if (self._wide() and _switch_on("MJX_PLAN_WIDE") and _switch_on("MJX_PLAN_MFMA")
+                and int(load().mjx_plan_rollout_wide_route(_ints(sizes), len(sizes), int(self.m))) == 1):
+            return 2
         return int(load().mjx_plan_route(_ints(sizes), len(sizes), int(self.m)))
 
     # ---- the planner
@@ -144,12 +174,19 @@ class MPCPolicy(object):
         s0_d = torch.from_numpy(np.ascontiguousarray(s0)).to(dev, torch.float32)
         assert s0.shape in ((n,), (N, n)), "obs is one state (n) or one per trajectory (N, n)"
         obs_d = torch.empty((K, N, H, n), dtype=torch.float32, device=dev)
-        check(lib.mjx_plan_rollout(ptr(s0_d), 0 if s0.ndim == 1 else n, N, H, K, ptr(a32), _ints(pk["sizes"]), len(pk["sizes"]),
-                                   ptr(pk["P"]), ptr(pk["tr"]), pk["act"], pk["flags"], ptr(obs_d), st))
+        roll_args = (ptr(s0_d), 0 if s0.ndim == 1 else n, N, H, K, ptr(a32), _ints(pk["sizes"]), len(pk["sizes"]),
+                     ptr(pk["P"]), ptr(pk["tr"]), pk["act"], pk["flags"], ptr(obs_d))
+        if self._wide():
+            route = ctypes.c_int(-1)
+            check(lib.mjx_plan_rollout_wide(*roll_args, ctypes.byref(route), st))
+            routes = dict(rollout=route.value, rewards=None)
+        else:
+            check(lib.mjx_plan_rollout(*roll_args, st))
+            routes = dict(rollout=None, rewards=None)        # (the narrow entry reports no route: route())
         if self.reward == 'learned':
             # r = RewardNet_k(s, a, DynamicsNet_k(s, a)) on the device, widened to fp64 for the scoring
             r_d = torch.empty((K, N, H), dtype=torch.float64, device=dev)
-            path_rewards_call(pk["rew"], obs_d, a32, True, N * H, K, None, r_d, dev)
+            routes["rewards"] = path_rewards_call(pk["rew"], obs_d, a32, True, N * H, K, None, r_d, dev, wide=self.wide)
         else:
             obs_h = obs_d.cpu().numpy()
             rewards = np.empty((K, N, H), np.float64)
@@ -165,6 +202,7 @@ class MPCPolicy(object):
                                  ptr(seq_d), st))
         act_sequence = seq_d.cpu().numpy().reshape(H, m)
         self._last = (R_d, S_d, r_d if self.reward == 'learned' else None)
+        self._routes = routes
         action = act_sequence[0].copy()
         if self.warmstart:
             self.act_sequence[:-1] = act_sequence[1:]
@@ -186,12 +224,23 @@ class MPCPolicy(object):
             return None
         return self._last[2].cpu().numpy()
 
+    def last_routes(self):
+        """dict(rollout=..., rewards=...) of the last get_action: the routes its entries reported (2 wide MFMA, 1 register-resident
+        MFMA, 0 generic; ``rewards`` None on reward='env', ``rollout`` None where the members went to ``mjx_plan_rollout``, which
+        reports none: :meth:`route`); None before the first call"""
+        return None if self._routes is None else dict(self._routes)
+
     def reward_route(self):
-        """1: the MFMA path-reward kernel serves these members, 0: the generic route (mjx_path_rewards_route); None on reward='env'"""
+        """2: the wide MFMA path-reward kernel serves these members (mjx_path_rewards_wide_route, asked for the shapes
+        ``nn_dynamics.wide_rows_shape`` sends there, with MJX_PATH_REWARDS_WIDE and MJX_PATH_REWARDS_MFMA as they stand now), 1: the
+        register-resident one, 0: the generic route (mjx_path_rewards_route); None on reward='env'"""
         if self.reward != 'learned':
             return None
         mdl = self._members()[0]
         ds, rs = tuple(mdl.dynamics_net.layer_sizes), tuple(mdl.reward_net.layer_sizes)
+        if (self.wide and wide_rows_shape(ds, rs) and _switch_on("MJX_PATH_REWARDS_WIDE") and _switch_on("MJX_PATH_REWARDS_MFMA")
+                and int(load().mjx_path_rewards_wide_route(_ints(ds), len(ds), _ints(rs), len(rs))) == 1):
+            return 2
         return int(load().mjx_path_rewards_route(_ints(ds), len(ds), _ints(rs), len(rs)))
 
     # ---- the reference's scoring functions, in NumPy, for callers that use them

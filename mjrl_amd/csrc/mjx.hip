@@ -30,6 +30,7 @@
 #include "mlp_fit.h"
 #include "path_reward.h"
 #include "plan.h"
+#include "plan_wide.h"
 #include "policy_rollout.h"
 #include "policy_rollout_wide.h"
 #include "rollout_batch.h"
@@ -495,23 +496,35 @@ int mjx_plan_route(const int* dyn_sizes, int dyn_n_sizes, int act_dim) {
   return plan_shape(net, act_dim, ps) ? 1 : 0;
 }
 
-int mjx_plan_rollout(const float* s0, int64_t s0_stride, int64_t N, int H, int K, const float* actions, const int* dyn_sizes,
-                     int dyn_n_sizes, const float* dyn_params, const float* dyn_tr, int act, int flags, float* obs_out, void* stream) {
+// mjx_plan_rollout (wide false) and mjx_plan_rollout_wide: route 2 where asked for, then 1, then 0
+static int plan_rollout(bool wide, const float* s0, int64_t s0_stride, int64_t N, int H, int K, const float* actions, const int* dyn_sizes,
+                        int dyn_n_sizes, const float* dyn_params, const float* dyn_tr, int act, int flags, float* obs_out, int* route_out,
+                        void* stream) {
   DynNet net;
   if (int rc = dyn_net(dyn_sizes, dyn_n_sizes, net)) return rc;
   const int n = net.dout(), m = net.din() - n;
   if (!s0 || !actions || !dyn_params || !dyn_tr || !obs_out || N < 0 || H < 0 || m <= 0 || (s0_stride != 0 && s0_stride != n) ||
-      !dyn_args_ok(net, K, act))
+      !dyn_args_ok(net, K, act) || (wide && (flags & ~(DYN_OUT_AFFINE | DYN_MASK | DYN_RESIDUAL))))
     return fail(MJX_ERR_ARG, "bad arguments");
-  if (N == 0 || H == 0) return MJX_OK;
+  // (the switches are read per call: A/B runs in one process; MJX_PLAN_MFMA=0 means no MFMA rollout at all)
+  ChainShape ps; size_t wide_bytes = 0;
+  const bool mfma = env_flag("MJX_PLAN_MFMA", true);
+  const bool served2 = wide && env_flag("MJX_PLAN_WIDE", true) && mfma && wide_plan_shape(net, wide_bytes);
+  const bool served1 = mfma && plan_shape(net, m, ps);
+  auto done = [&](int route) { if (route_out) *route_out = route; return MJX_OK; };
+  if (N == 0 || H == 0) return done(served2 ? 2 : served1 ? 1 : 0);
   MJX_DEVICE_ENTRY();
   hipStream_t st = (hipStream_t)stream;
-  ChainShape ps;
-  if (env_flag("MJX_PLAN_MFMA", true) && plan_shape(net, m, ps)) {      // (read per call: A/B runs in one process)
-    const PlanArgs a{s0, s0_stride, actions, dyn_params, dyn_tr, obs_out, N, net.P, H, n, m, net.sz[1], net.sz[2], act, flags};
-    bool launched;
-    if (int rc = launch_chained(plan_kernel(ps.HB, ps.NB), ps.bytes, dim3((unsigned)((N + 127) / 128), (unsigned)K), a, st, launched)) return rc;
-    if (launched) return MJX_OK;
+  const PlanArgs p{s0, s0_stride, actions, dyn_params, dyn_tr, obs_out, N, net.P, H, n, m, net.sz[1], net.sz[2], act, flags};
+  bool launched;
+  if (served2) {
+    if (int rc = launch_chained(k_plan_rollout_wide, wide_bytes, dim3((unsigned)((N + 31) / 32), (unsigned)K), p, st, launched, dim3(DFE_THREADS)))
+      return rc;
+    if (launched) return done(2);
+  }
+  if (served1) {
+    if (int rc = launch_chained(plan_kernel(ps.HB, ps.NB), ps.bytes, dim3((unsigned)((N + 127) / 128), (unsigned)K), p, st, launched)) return rc;
+    if (launched) return done(1);
   }
   // generic route: k_model_rollout with the actions given, as mjx_model_rollout launches it; its action copy and the tiled
   // start state go to scratch
@@ -521,7 +534,28 @@ int mjx_plan_rollout(const float* s0, int64_t s0_stride, int64_t N, int H, int K
   if (!s0_stride) s0 = tile_s0(s0, N, n, scr + act_floats, st);
   RolloutArgs a{};
   a.dyn = net;
-  return launch_model_rollout(a, s0, N, H, K, actions, dyn_params, dyn_tr, act, flags, obs_out, scr, st);
+  if (int rc = launch_model_rollout(a, s0, N, H, K, actions, dyn_params, dyn_tr, act, flags, obs_out, scr, st)) return rc;
+  return done(0);
+}
+
+int mjx_plan_rollout(const float* s0, int64_t s0_stride, int64_t N, int H, int K, const float* actions, const int* dyn_sizes,
+                     int dyn_n_sizes, const float* dyn_params, const float* dyn_tr, int act, int flags, float* obs_out, void* stream) {
+  return plan_rollout(false, s0, s0_stride, N, H, K, actions, dyn_sizes, dyn_n_sizes, dyn_params, dyn_tr, act, flags, obs_out, nullptr, stream);
+}
+
+// ---------------------------------------------------------------------------- the same for nets up to 256 wide (csrc/plan_wide.h)
+int mjx_plan_rollout_wide_route(const int* dyn_sizes, int dyn_n_sizes, int act_dim) {
+  DynNet net;
+  if (int rc = dyn_net(dyn_sizes, dyn_n_sizes, net)) return rc;
+  if (act_dim <= 0 || net.din() != net.dout() + act_dim) return fail(MJX_ERR_ARG, "dyn_sizes must be [n + m, h..., n] with m = act_dim > 0");
+  size_t bytes;
+  return wide_plan_shape(net, bytes) ? 1 : 0;
+}
+
+int mjx_plan_rollout_wide(const float* s0, int64_t s0_stride, int64_t N, int H, int K, const float* actions, const int* dyn_sizes,
+                          int dyn_n_sizes, const float* dyn_params, const float* dyn_tr, int act, int flags, float* obs_out, int* route_out,
+                          void* stream) {
+  return plan_rollout(true, s0, s0_stride, N, H, K, actions, dyn_sizes, dyn_n_sizes, dyn_params, dyn_tr, act, flags, obs_out, route_out, stream);
 }
 
 int mjx_plan_score(const float* obs, const double* rewards, const double* actions, int K, int64_t N, int H, int n, int m, double kappa,

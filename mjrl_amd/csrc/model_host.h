@@ -1,4 +1,4 @@
-// model_host.h -- host side of the learned-model kernels (dynamics.h, dyn_fit_ens.h, plan.h, path_reward.h, policy_rollout.h, policy_rollout_wide.h, rollout_batch.h, rows_wide.h): their shared
+// model_host.h -- host side of the learned-model kernels (dynamics.h, dyn_fit_ens.h, plan.h, path_reward.h, plan_wide.h, policy_rollout.h, policy_rollout_wide.h, rollout_batch.h, rows_wide.h): their shared
 // argument checks, their routes as plain arithmetic, and the launches more than one entry makes.  Included by mjx.hip after fail / HIPCHK /
 // lds_limit / capped_grid.
 #pragma once
@@ -41,7 +41,7 @@ inline const float* tile_s0(const float* s0, int64_t N, int n, float* dst, hipSt
 // ---- the three register-chained MFMA routes (k_plan_rollout, k_path_rewards, k_policy_rollout; csrc/mfma_chain.h).  What serves a
 // call: the instance's block counts (RB: the reward blocks, path rewards only) and the bytes of its LDS image.
 struct ChainShape { int HB = 0, NB = 0, RB = 0; size_t bytes = 0; };
-// One launch of such a kernel: 256 threads (k_policy_rollout_wide: DFE_THREADS), the image as its dynamic LDS.  -> MJX_OK with `launched` set, or the launch's error.
+// One launch of such a kernel: 256 threads (the wide kernels: DFE_THREADS), the image as its dynamic LDS.  -> MJX_OK with `launched` set, or the launch's error.
 // Not launched: the device refused the image and the caller takes its generic route.  A refusal that is not LDS_OVER came from the
 // runtime, whose error is cleared here so that the generic route's own check does not report it.
 template <class Args>
@@ -98,7 +98,7 @@ inline PolRollKernel pol_roll_kernel(int HB, int NB) {
                                           {k_policy_rollout<3, 1>, k_policy_rollout<3, 2>}, {k_policy_rollout<4, 1>, k_policy_rollout<4, 2>}};
   return tab[HB - 1][NB - 1];
 }
-// ---- the wide LDS-tile kernels (dfe_tiles.h: policy_rollout_wide.h, rows_wide.h).  A wide kernel takes the dynamics net and the
+// ---- the wide LDS-tile kernels (dfe_tiles.h: plan_wide.h, policy_rollout_wide.h, rows_wide.h).  A wide kernel takes the dynamics net and the
 // net beside it (a policy or a reward net; null: none): exactly two hidden layers each, every hidden width 1 .. 256, n <= 64,
 // m <= 64, n + m <= 128.  Plain arithmetic; each kernel adds the bytes of its own LDS layout.
 inline bool wide_nets_ok(const DynNet& dyn, const DynNet* other) {
@@ -121,6 +121,15 @@ inline bool wide_roll_shape(const DynNet& dyn, const DynNet& pol, size_t& bytes)
   if (!wide_nets_ok(dyn, &pol)) return false;
   const int n = dyn.dout(), m = dyn.din() - n;
   bytes = sizeof(float) * wide_roll_lds_floats(n, m, dyn.sz[1], dyn.sz[2], pol.sz[1], pol.sz[2]);
+  return bytes <= LDS_MAX;
+}
+// ---- wide plan rollout.  What k_plan_rollout_wide (plan_wide.h) serves: a dynamics net as wide_nets_ok takes it and its LDS layout
+// (the kernel has no static LDS) within LDS_MAX.  It does not ask what plan_shape answers: the shapes the chained kernel takes are
+// served as well.  MJX_PLAN_WIDE=0 or MJX_PLAN_MFMA=0 (read per call by mjx_plan_rollout_wide): mjx_plan_rollout's routes.
+inline bool wide_plan_shape(const DynNet& dyn, size_t& bytes) {
+  if (!wide_nets_ok(dyn, nullptr)) return false;
+  const int n = dyn.dout(), m = dyn.din() - n;
+  bytes = sizeof(float) * plan_wide_lds_floats(n, m, dyn.sz[1], dyn.sz[2]);
   return bytes <= LDS_MAX;
 }
 // the two nets of one call, parsed: sizes that fit each other ([n, p..., m] and [n + m, h..., n])
