@@ -18,7 +18,7 @@ from ..._lib import check, load, ptr
 from ...utils import ingest, process_samples
 from ..npg_cg import NPG
 from .nn_dynamics import (WorldModel, _device, _ints, _stream, cached_members_pack, ensemble_forward, ensemble_path_rewards,
-                          members_share_kind, path_rewards_call, rollout_disagreement_device)
+                          members_share_kind, path_rewards_call, predicted_route, rollout_disagreement_device)
 from .sampling import (_as_env, draw_rollout_noise, pack_rollouts_device, rollout_bounds, rollout_models, rollout_models_device,
                        wide_rollout_shape)
 
@@ -332,10 +332,8 @@ class ModelAccelNPG(NPG):
         net = self.learned_model[0].dynamics_net
         ds = tuple(net.layer_sizes)
         ps = (net.state_dim,) + tuple(self.policy.hidden_sizes) + (net.act_dim,)
-        lib = load()
-        if wide_rollout_shape(ps, ds) and int(lib.mjx_policy_rollout_wide_route(_ints(ps), len(ps), _ints(ds), len(ds))) == 1:
-            return 2
-        return int(lib.mjx_policy_rollout_route(_ints(ps), len(ps), _ints(ds), len(ds)))
+        return predicted_route(load(), wide_rollout_shape(ps, ds), (), "mjx_policy_rollout_wide_route", "mjx_policy_rollout_route",
+                               _ints(ps), len(ps), _ints(ds), len(ds))
 
     def last_scores(self):
         """(R, S) of the last refined call: the K N trajectory scores and their softmax weights (fp64, read back on demand)"""

@@ -40,13 +40,13 @@ the MEMBER index of row i, so the disagreement of trajectories 0 .. K-1 is what 
 reproduces that; False uses the evidently intended per-trajectory index ``i % num_traj``.
 """
 import ctypes
-import os
 
 import numpy as np
 import torch
 
 from ..._lib import check, load, ptr
-from .nn_dynamics import _device, _ints, _stream, cached_members_pack, members_pack_key, path_rewards_call, wide_rows_shape
+from .nn_dynamics import (_device, _ints, _stream, cached_members_pack, members_pack_key, path_rewards_call, predicted_route, wide_entry,
+                          wide_rows_shape)
 
 
 def perturbed_action_batch(num_traj, base_act, filter_coefs):
@@ -60,11 +60,6 @@ def perturbed_action_batch(num_traj, base_act, filter_coefs):
     for t in range(2, u.shape[1]):
         u[:, t] = b0 * u[:, t] + b1 * u[:, t - 1] + b2 * u[:, t - 2]
     return u
-
-
-def _switch_on(name):
-    """a route switch as the library reads it per call (on unless the variable starts with 0)"""
-    return os.environ.get(name, "1")[:1] != "0"
 
 
 class MPCPolicy(object):
@@ -153,10 +148,8 @@ class MPCPolicy(object):
         there, with MJX_PLAN_WIDE and MJX_PLAN_MFMA as they stand now), 1: the register-resident MFMA rollout, 0: the generic
         rollout (mjx_plan_route)"""
         sizes = tuple(self._members()[0].dynamics_net.layer_sizes)
-        if (self._wide() and _switch_on("MJX_PLAN_WIDE") and _switch_on("MJX_PLAN_MFMA")
-                and int(load().mjx_plan_rollout_wide_route(_ints(sizes), len(sizes), int(self.m))) == 1):
-            return 2
-        return int(load().mjx_plan_route(_ints(sizes), len(sizes), int(self.m)))
+        return predicted_route(load(), self._wide(), ("MJX_PLAN_WIDE", "MJX_PLAN_MFMA"), "mjx_plan_rollout_wide_route", "mjx_plan_route",
+                               _ints(sizes), len(sizes), int(self.m))
 
     # ---- the planner
     def get_action(self, obs):
@@ -176,13 +169,11 @@ class MPCPolicy(object):
         obs_d = torch.empty((K, N, H, n), dtype=torch.float32, device=dev)
         roll_args = (ptr(s0_d), 0 if s0.ndim == 1 else n, N, H, K, ptr(a32), _ints(pk["sizes"]), len(pk["sizes"]),
                      ptr(pk["P"]), ptr(pk["tr"]), pk["act"], pk["flags"], ptr(obs_d))
-        if self._wide():
-            route = ctypes.c_int(-1)
-            check(lib.mjx_plan_rollout_wide(*roll_args, ctypes.byref(route), st))
-            routes = dict(rollout=route.value, rewards=None)
-        else:
-            check(lib.mjx_plan_rollout(*roll_args, st))
-            routes = dict(rollout=None, rewards=None)        # (the narrow entry reports no route: route())
+        wide = self._wide()
+        route = ctypes.c_int(-1)
+        tail = (ctypes.byref(route), st) if wide else (st,)  # (the narrow entry takes no route pointer and reports none: route())
+        check(wide_entry(lib, "plan_rollout", wide)(*roll_args, *tail))
+        routes = dict(rollout=route.value if wide else None, rewards=None)
         if self.reward == 'learned':
             # r = RewardNet_k(s, a, DynamicsNet_k(s, a)) on the device, widened to fp64 for the scoring
             r_d = torch.empty((K, N, H), dtype=torch.float64, device=dev)
@@ -238,10 +229,8 @@ class MPCPolicy(object):
             return None
         mdl = self._members()[0]
         ds, rs = tuple(mdl.dynamics_net.layer_sizes), tuple(mdl.reward_net.layer_sizes)
-        if (self.wide and wide_rows_shape(ds, rs) and _switch_on("MJX_PATH_REWARDS_WIDE") and _switch_on("MJX_PATH_REWARDS_MFMA")
-                and int(load().mjx_path_rewards_wide_route(_ints(ds), len(ds), _ints(rs), len(rs))) == 1):
-            return 2
-        return int(load().mjx_path_rewards_route(_ints(ds), len(ds), _ints(rs), len(rs)))
+        return predicted_route(load(), self.wide and wide_rows_shape(ds, rs), ("MJX_PATH_REWARDS_WIDE", "MJX_PATH_REWARDS_MFMA"),
+                               "mjx_path_rewards_wide_route", "mjx_path_rewards_route", _ints(ds), len(ds), _ints(rs), len(rs))
 
     # ---- the reference's scoring functions, in NumPy, for callers that use them
     def score_trajectory_ensemble(self, paths, paths_list):

@@ -34,6 +34,7 @@ The module parameters stay ordinary torch tensors (CPU by default, as in the ref
 operations raise.
 """
 import ctypes
+import os
 
 import numpy as np
 import torch
@@ -637,13 +638,29 @@ def wide_rows_shape(dyn_sizes, rew_sizes=None):
     return all(len(sz) == 4 for sz in nets) and max(dyn_sizes[1:3]) > 128
 
 
+def wide_entry(lib, name, wide):
+    """``lib.mjx_<name>_wide`` where ``wide`` (the caller asked for it and its plain-Python shape predicate, :func:`wide_rows_shape`
+    or ``sampling.wide_rollout_shape``, says so), else ``lib.mjx_<name>``: the same arguments either way"""
+    return getattr(lib, "mjx_" + name + ("_wide" if wide else ""))
+
+
+def predicted_route(lib, wide, switches, wide_query, narrow_query, *query_args):
+    """the route an entry would report for these nets, before any call: 2 where ``wide`` (as :func:`wide_entry` takes it), every
+    switch named in ``switches`` is on as the library reads it per call (on unless the variable starts with 0) and
+    ``lib.<wide_query>`` answers 1; otherwise what ``lib.<narrow_query>`` answers (1: the register-resident MFMA kernel, 0: the
+    generic route)"""
+    if wide and all(os.environ.get(name, "1")[:1] != "0" for name in switches) and int(getattr(lib, wide_query)(*query_args)) == 1:
+        return 2
+    return int(getattr(lib, narrow_query)(*query_args))
+
+
 def path_rewards_call(pk, obs_d, act_d, shared, rows, K, r32, r64, dev, wide=False):
     """one ``mjx_path_rewards`` over packed members (:func:`pack_reward_members`) -> the route taken.  ``wide``: where
     :func:`wide_rows_shape` says so, ``mjx_path_rewards_wide`` with the same arguments (route 2 = the wide MFMA kernel)"""
     route = ctypes.c_int(-1)
     m = pk["dyn_sizes"][0] - pk["dyn_sizes"][-1]
     lib = load()
-    entry = lib.mjx_path_rewards_wide if wide and wide_rows_shape(pk["dyn_sizes"], pk["rew_sizes"]) else lib.mjx_path_rewards
+    entry = wide_entry(lib, "path_rewards", wide and wide_rows_shape(pk["dyn_sizes"], pk["rew_sizes"]))
     check(entry(ptr(obs_d), ptr(act_d), 0 if shared else rows * m, rows, K, _ints(pk["dyn_sizes"]), len(pk["dyn_sizes"]),
                 ptr(pk["dyn_P"]), ptr(pk["dyn_tr"]), pk["dyn_act"], pk["dyn_flags"], _ints(pk["rew_sizes"]),
                 len(pk["rew_sizes"]), ptr(pk["rew_P"]), ptr(pk["rew_tr"]), pk["rew_act"],
@@ -703,7 +720,7 @@ def rollout_disagreement_device(models, obs_d, act_d, packed=None, info=None, wi
     err = torch.empty((P, max(H - 1, 0)), dtype=torch.float32, device=dev)
     route = ctypes.c_int(-1)
     lib = load()
-    entry = lib.mjx_rollout_disagreement_wide if wide and wide_rows_shape(sizes) else lib.mjx_rollout_disagreement
+    entry = wide_entry(lib, "rollout_disagreement", wide and wide_rows_shape(sizes))
     check(entry(ptr(obs_d), ptr(act_d), P, H, len(models), _ints(sizes), len(sizes), ptr(pk["P"]), ptr(pk["tr"]),
                 pk["act"], pk["flags"], ptr(err), ctypes.byref(route), _stream(dev)))
     if info is not None:

@@ -15,7 +15,7 @@ import numpy as np
 import torch
 
 from ..._lib import check, load, ptr
-from .nn_dynamics import _device, _f32, _ints, _stream, pack_dynamics_members
+from .nn_dynamics import _device, _f32, _ints, _stream, pack_dynamics_members, wide_entry
 
 
 def _as_env(env, env_kwargs=None):
@@ -136,7 +136,7 @@ def rollout_models_device(models, policy, s0, horizon, noise=None, s_min=None, s
     act_out = torch.empty((K, N, H, m), dtype=torch.float32, device=dev)
     route = ctypes.c_int(-1)
     lib = load()
-    entry = lib.mjx_policy_rollout_wide if wide_rollout_shape(pol_sizes, sizes) else lib.mjx_policy_rollout
+    entry = wide_entry(lib, "policy_rollout", wide_rollout_shape(pol_sizes, sizes))
     check(entry(ptr(s0_d), n if s0_d.dim() == 2 else 0, N, H, K, _ints(pol_sizes), len(pol_sizes), ptr(pol_P),
                 ptr(pol_tr), ptr(nz), H * N * m if (nz is not None and nz.dim() == 4) else 0, _ints(sizes),
                 len(sizes), ptr(packed["P"]), ptr(packed["tr"]), packed["act"], packed["flags"], ptr(bnd[0]),

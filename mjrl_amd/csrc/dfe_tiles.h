@@ -2,7 +2,8 @@
 // (dyn_fit_ens.h k_dyn_fit_ens, policy_rollout_wide.h k_policy_rollout_wide, rows_wide.h k_rollout_disagree_wide and
 // k_path_rewards_wide): the workgroup's shape, the [unit][sample] tile conventions and the forward of one layer; for the three
 // forward-only kernels also their shape limits, the staging of a member's small vectors, the net as a workgroup reads it (WideNet),
-// its forward through two or three layers and the normaliser that fills an input tile.
+// its forward through two or three layers and the normaliser that fills an input tile; for the two rollout kernels (plan_wide.h,
+// policy_rollout_wide.h) the tile-row stride and the thread mapping.
 //
 // A tile is [unit][sample] fp32 with the sample dimension padded to the MFMA tile (32 or 64) and a row stride of that + 4; a
 // hidden layer's tile has its unit rows padded to 32.  Products run on v_mfma_f32_32x32x2_f32 in the chained, operand-swapped form
@@ -155,6 +156,23 @@ template <int NS>
 __device__ __forceinline__ void dfe_zero_rows(float* X, int r0, int r1, int tid) {
   constexpr int TILE = 32 * NS, ST = TILE + 4;
   for (int e = tid; e < (r1 - r0) * TILE; e += DFE_THREADS) X[(r0 + e / TILE) * ST + e % TILE] = 0.f;
+}
+
+// ---- the two rollout kernels (plan_wide.h k_plan_rollout_wide, policy_rollout_wide.h k_policy_rollout_wide): a workgroup is ONE
+// tile of 32 trajectories of one member through all H steps
+constexpr int WR_ST = 32 + 4;                               // floats a tile row
+constexpr int WR_UQ = DFE_THREADS / 32;                     // rows between a thread's elements
+constexpr int WR_NZ = WIDE_MAXM / WR_UQ;                    // action rows a thread owns (m <= 64): f = u0 + WR_UQ q
+// a thread's elements of a [rows][32] block: e = tid + DFE_THREADS q is row e / 32 = u0 + WR_UQ q, sample column c = tid % 32, which
+// is trajectory blockIdx.x * 32 + c of the call (valid: it exists; vrow: that row, or row 0 where it does not, for addresses)
+struct WideRollMap { int c, u0; bool valid; int64_t vrow; };
+__device__ __forceinline__ WideRollMap wr_map(int tid, int64_t N) {
+  WideRollMap t;
+  t.c = tid & 31; t.u0 = tid >> 5;
+  const int64_t row = (int64_t)blockIdx.x * 32 + t.c;
+  t.valid = row < N;
+  t.vrow = t.valid ? row : 0;
+  return t;
 }
 
 }  // namespace mjx

@@ -487,71 +487,14 @@ int mjx_model_rollout(const float* s0, int64_t N, int H, int K, const int* pol_s
   return launch_model_rollout(a, s0, N, H, K, actions, dyn_params, dyn_tr, act, flags, obs_out, act_out, (hipStream_t)stream);
 }
 
-// ---------------------------------------------------------------------------- MPC planning on learned models (csrc/plan.h)
-int mjx_plan_route(const int* dyn_sizes, int dyn_n_sizes, int act_dim) {
-  DynNet net;
-  if (int rc = dyn_net(dyn_sizes, dyn_n_sizes, net)) return rc;
-  if (act_dim <= 0 || net.din() != net.dout() + act_dim) return fail(MJX_ERR_ARG, "dyn_sizes must be [n + m, h..., n] with m = act_dim > 0");
-  ChainShape ps;
-  return plan_shape(net, act_dim, ps) ? 1 : 0;
-}
-
-// mjx_plan_rollout (wide false) and mjx_plan_rollout_wide: route 2 where asked for, then 1, then 0
-static int plan_rollout(bool wide, const float* s0, int64_t s0_stride, int64_t N, int H, int K, const float* actions, const int* dyn_sizes,
-                        int dyn_n_sizes, const float* dyn_params, const float* dyn_tr, int act, int flags, float* obs_out, int* route_out,
-                        void* stream) {
-  DynNet net;
-  if (int rc = dyn_net(dyn_sizes, dyn_n_sizes, net)) return rc;
-  const int n = net.dout(), m = net.din() - n;
-  if (!s0 || !actions || !dyn_params || !dyn_tr || !obs_out || N < 0 || H < 0 || m <= 0 || (s0_stride != 0 && s0_stride != n) ||
-      !dyn_args_ok(net, K, act) || (wide && (flags & ~(DYN_OUT_AFFINE | DYN_MASK | DYN_RESIDUAL))))
-    return fail(MJX_ERR_ARG, "bad arguments");
-  // (the switches are read per call: A/B runs in one process; MJX_PLAN_MFMA=0 means no MFMA rollout at all)
-  ChainShape ps; size_t wide_bytes = 0;
-  const bool mfma = env_flag("MJX_PLAN_MFMA", true);
-  const bool served2 = wide && env_flag("MJX_PLAN_WIDE", true) && mfma && wide_plan_shape(net, wide_bytes);
-  const bool served1 = mfma && plan_shape(net, m, ps);
-  auto done = [&](int route) { if (route_out) *route_out = route; return MJX_OK; };
-  if (N == 0 || H == 0) return done(served2 ? 2 : served1 ? 1 : 0);
-  MJX_DEVICE_ENTRY();
-  hipStream_t st = (hipStream_t)stream;
-  const PlanArgs p{s0, s0_stride, actions, dyn_params, dyn_tr, obs_out, N, net.P, H, n, m, net.sz[1], net.sz[2], act, flags};
-  bool launched;
-  if (served2) {
-    if (int rc = launch_chained(k_plan_rollout_wide, wide_bytes, dim3((unsigned)((N + 31) / 32), (unsigned)K), p, st, launched, dim3(DFE_THREADS)))
-      return rc;
-    if (launched) return done(2);
-  }
-  if (served1) {
-    if (int rc = launch_chained(plan_kernel(ps.HB, ps.NB), ps.bytes, dim3((unsigned)((N + 127) / 128), (unsigned)K), p, st, launched)) return rc;
-    if (launched) return done(1);
-  }
-  // generic route: k_model_rollout with the actions given, as mjx_model_rollout launches it; its action copy and the tiled
-  // start state go to scratch
-  float* scr = nullptr;
-  const size_t act_floats = (size_t)K * N * H * m, s0_floats = s0_stride ? 0 : (size_t)N * n;
-  if (int rc = dev_scratch(SITE_PLAN_ROLLOUT, stream, (act_floats + s0_floats) * sizeof(float), &scr)) return rc;
-  if (!s0_stride) s0 = tile_s0(s0, N, n, scr + act_floats, st);
-  RolloutArgs a{};
-  a.dyn = net;
-  if (int rc = launch_model_rollout(a, s0, N, H, K, actions, dyn_params, dyn_tr, act, flags, obs_out, scr, st)) return rc;
-  return done(0);
-}
-
+// ---------------------------------------------------------------------------- MPC planning on learned models (csrc/plan.h, csrc/plan_wide.h;
+// the entries with a wide route and their route queries: csrc/model_host.h)
+int mjx_plan_route(const int* dyn_sizes, int dyn_n_sizes, int act_dim) { return plan_route(false, dyn_sizes, dyn_n_sizes, act_dim); }
+int mjx_plan_rollout_wide_route(const int* dyn_sizes, int dyn_n_sizes, int act_dim) { return plan_route(true, dyn_sizes, dyn_n_sizes, act_dim); }
 int mjx_plan_rollout(const float* s0, int64_t s0_stride, int64_t N, int H, int K, const float* actions, const int* dyn_sizes,
                      int dyn_n_sizes, const float* dyn_params, const float* dyn_tr, int act, int flags, float* obs_out, void* stream) {
   return plan_rollout(false, s0, s0_stride, N, H, K, actions, dyn_sizes, dyn_n_sizes, dyn_params, dyn_tr, act, flags, obs_out, nullptr, stream);
 }
-
-// ---------------------------------------------------------------------------- the same for nets up to 256 wide (csrc/plan_wide.h)
-int mjx_plan_rollout_wide_route(const int* dyn_sizes, int dyn_n_sizes, int act_dim) {
-  DynNet net;
-  if (int rc = dyn_net(dyn_sizes, dyn_n_sizes, net)) return rc;
-  if (act_dim <= 0 || net.din() != net.dout() + act_dim) return fail(MJX_ERR_ARG, "dyn_sizes must be [n + m, h..., n] with m = act_dim > 0");
-  size_t bytes;
-  return wide_plan_shape(net, bytes) ? 1 : 0;
-}
-
 int mjx_plan_rollout_wide(const float* s0, int64_t s0_stride, int64_t N, int H, int K, const float* actions, const int* dyn_sizes,
                           int dyn_n_sizes, const float* dyn_params, const float* dyn_tr, int act, int flags, float* obs_out, int* route_out,
                           void* stream) {
@@ -583,66 +526,14 @@ int mjx_plan_score(const float* obs, const double* rewards, const double* action
   return MJX_OK;
 }
 
-// ---------------------------------------------------------------------------- learned path rewards (csrc/path_reward.h)
+// ---------------------------------------------------------------------------- learned path rewards (csrc/path_reward.h, csrc/rows_wide.h)
+int mjx_rows_wide_tile_rows(void) { return 32 * RW_NS; }
 int mjx_path_rewards_route(const int* dyn_sizes, int dyn_n_sizes, const int* rew_sizes, int rew_n_sizes) {
-  DynNet dyn, rew;
-  if (int rc = path_rew_nets(dyn_sizes, dyn_n_sizes, rew_sizes, rew_n_sizes, dyn, rew)) return rc;
-  ChainShape ps;
-  return path_rew_shape(dyn, rew, ps) ? 1 : 0;
+  return path_rewards_route(false, dyn_sizes, dyn_n_sizes, rew_sizes, rew_n_sizes);
 }
-
-// mjx_path_rewards (wide false) and mjx_path_rewards_wide: route 2 where asked for, then 1, then 0
-static int path_rewards(bool wide, const float* obs, const float* act, int64_t act_stride, int64_t rows, int K, const int* dyn_sizes,
-                        int dyn_n_sizes, const float* dyn_params, const float* dyn_tr, int dyn_act, int dyn_flags, const int* rew_sizes,
-                        int rew_n_sizes, const float* rew_params, const float* rew_tr, int rew_act, float* r32_out, double* r64_out,
-                        int* route_out, void* stream) {
-  DynNet dyn, rew;
-  if (int rc = path_rew_nets(dyn_sizes, dyn_n_sizes, rew_sizes, rew_n_sizes, dyn, rew)) return rc;
-  const int n = dyn.dout(), m = dyn.din() - n;
-  if (!path_rew_args_ok(dyn, rew, obs, act, act_stride, rows, K, dyn_params, dyn_tr, dyn_act, dyn_flags, rew_params, rew_tr, rew_act, r32_out, r64_out))
-    return fail(MJX_ERR_ARG, "bad arguments");
-  // (the switches are read per call: A/B runs in one process; MJX_PATH_REWARDS_MFMA=0 means no MFMA route at all)
-  ChainShape ps; size_t wide_bytes = 0;
-  const bool mfma = env_flag("MJX_PATH_REWARDS_MFMA", true);
-  const bool served2 = wide && env_flag("MJX_PATH_REWARDS_WIDE", true) && mfma && wide_rows_shape(dyn, &rew, wide_bytes);
-  const bool served1 = mfma && path_rew_shape(dyn, rew, ps);
-  auto done = [&](int route) { if (route_out) *route_out = route; return MJX_OK; };
-  if (rows == 0) return done(served2 ? 2 : served1 ? 1 : 0);
-  MJX_DEVICE_ENTRY();
-  hipStream_t st = (hipStream_t)stream;
-  const PathRewArgs a{obs, act, act_stride, dyn_params, dyn_tr, rew_params, rew_tr, r32_out, r64_out, rows, dyn.P, rew.P,
-                      n, m, dyn.sz[1], dyn.sz[2], dyn_act, dyn_flags, rew.sz[1], rew.sz[2], rew_act};
-  bool launched;
-  if (served2) {
-    if (int rc = launch_chained(k_path_rewards_wide<RW_NS>, wide_bytes, tile_grid(rows, 32 * RW_NS, K), a, st, launched, dim3(DFE_THREADS))) return rc;
-    if (launched) return done(2);
-  }
-  if (served1) {
-    // a wave owns tiles of 32 rows; one workgroup per CU holds the image, so the K members share the CUs and a wave walks the
-    // tiles beyond that (the staging prologue is paid once per workgroup)
-    if (int rc = launch_chained(path_rew_kernel(ps.HB, ps.NB), ps.bytes, tile_grid(rows, 128, K), a, st, launched)) return rc;
-    if (launched) return done(1);
-  }
-  // generic route: mjx_dyn_forward's kernel twice, over [s, a] and over [s, a, s'], both assembled in scratch
-  const int din = n + m, rin = din + n;
-  const int64_t kr = (int64_t)K * rows;
-  float* scr = nullptr;
-  if (int rc = dev_scratch(SITE_PATH_REWARDS, stream, (size_t)kr * (din + rin + n + 1) * sizeof(float), &scr)) return rc;
-  float* X1 = scr; float* X2 = X1 + kr * din; float* sp = X2 + kr * rin; float* r32 = r32_out ? r32_out : sp + kr * n;
-  const size_t b1 = sizeof(float) * 3 * DYN_FT * (size_t)dyn.maxw, b2 = sizeof(float) * 3 * DYN_FT * (size_t)rew.maxw;
-  if (int rc = lds_limit((const void*)k_dyn_forward, b1 > b2 ? b1 : b2)) return rc;
-  const dim3 grid((unsigned)((rows + DYN_FT - 1) / DYN_FT), (unsigned)K);
-  hipLaunchKernelGGL(k_pr_gather_sa, dim3(capped_grid(kr * din, 256, 4096)), dim3(256), 0, st, obs, act, act_stride, rows, K, n, m, X1, X2);
-  DynFwdArgs fa{dyn, X1, rows * din, rows, dyn_params, dyn_tr, dyn_act, dyn_flags, sp};
-  hipLaunchKernelGGL(k_dyn_forward, grid, dim3(256), b1, st, fa);
-  hipLaunchKernelGGL(k_pr_gather_sp, dim3(capped_grid(kr * n, 256, 4096)), dim3(256), 0, st, sp, kr, n, m, X2);
-  DynFwdArgs fr{rew, X2, rows * rin, rows, rew_params, rew_tr, rew_act, DYN_OUT_AFFINE, r32};
-  hipLaunchKernelGGL(k_dyn_forward, grid, dim3(256), b2, st, fr);
-  if (r64_out) hipLaunchKernelGGL(k_pr_widen, dim3(capped_grid(kr, 256, 4096)), dim3(256), 0, st, r32, kr, r64_out);
-  HIPCHK(hipGetLastError());
-  return done(0);
+int mjx_path_rewards_wide_route(const int* dyn_sizes, int dyn_n_sizes, const int* rew_sizes, int rew_n_sizes) {
+  return path_rewards_route(true, dyn_sizes, dyn_n_sizes, rew_sizes, rew_n_sizes);
 }
-
 int mjx_path_rewards(const float* obs, const float* act, int64_t act_stride, int64_t rows, int K, const int* dyn_sizes, int dyn_n_sizes,
                      const float* dyn_params, const float* dyn_tr, int dyn_act, int dyn_flags, const int* rew_sizes, int rew_n_sizes,
                      const float* rew_params, const float* rew_tr, int rew_act, float* r32_out, double* r64_out, int* route_out,
@@ -650,17 +541,6 @@ int mjx_path_rewards(const float* obs, const float* act, int64_t act_stride, int
   return path_rewards(false, obs, act, act_stride, rows, K, dyn_sizes, dyn_n_sizes, dyn_params, dyn_tr, dyn_act, dyn_flags, rew_sizes, rew_n_sizes,
                       rew_params, rew_tr, rew_act, r32_out, r64_out, route_out, stream);
 }
-
-// ---------------------------------------------------------------------------- the same for nets up to 256 wide (csrc/rows_wide.h)
-int mjx_rows_wide_tile_rows(void) { return 32 * RW_NS; }
-
-int mjx_path_rewards_wide_route(const int* dyn_sizes, int dyn_n_sizes, const int* rew_sizes, int rew_n_sizes) {
-  DynNet dyn, rew;
-  if (int rc = path_rew_nets(dyn_sizes, dyn_n_sizes, rew_sizes, rew_n_sizes, dyn, rew)) return rc;
-  size_t bytes;
-  return wide_rows_shape(dyn, &rew, bytes) ? 1 : 0;
-}
-
 int mjx_path_rewards_wide(const float* obs, const float* act, int64_t act_stride, int64_t rows, int K, const int* dyn_sizes, int dyn_n_sizes,
                           const float* dyn_params, const float* dyn_tr, int dyn_act, int dyn_flags, const int* rew_sizes, int rew_n_sizes,
                           const float* rew_params, const float* rew_tr, int rew_act, float* r32_out, double* r64_out, int* route_out,
@@ -669,66 +549,13 @@ int mjx_path_rewards_wide(const float* obs, const float* act, int64_t act_stride
                       rew_params, rew_tr, rew_act, r32_out, r64_out, route_out, stream);
 }
 
-// ---------------------------------------------------------------------------- policy rollout on learned models (csrc/policy_rollout.h)
+// ---------------------------------------------------------------------------- policy rollout on learned models (csrc/policy_rollout.h, csrc/policy_rollout_wide.h)
 int mjx_policy_rollout_route(const int* pol_sizes, int pol_n_sizes, const int* dyn_sizes, int dyn_n_sizes) {
-  DynNet pol, dyn;
-  if (int rc = pol_roll_nets(pol_sizes, pol_n_sizes, dyn_sizes, dyn_n_sizes, pol, dyn)) return rc;
-  ChainShape ps;
-  return pol_roll_shape(dyn, pol, ps) ? 1 : 0;
+  return policy_rollout_route(false, pol_sizes, pol_n_sizes, dyn_sizes, dyn_n_sizes);
 }
-
-// mjx_policy_rollout (wide false) and mjx_policy_rollout_wide: route 2 where asked for, then 1, then 0
-static int policy_rollout(bool wide, const float* s0, int64_t s0_stride, int64_t N, int H, int K, const int* pol_sizes, int pol_n_sizes,
-                          const float* pol_params, const float* pol_tr, const float* noise, int64_t noise_stride, const int* dyn_sizes,
-                          int dyn_n_sizes, const float* dyn_params, const float* dyn_tr, int act, int flags, const float* a_min,
-                          const float* a_max, const float* s_min, const float* s_max, float* obs_out, float* act_out, int* route_out,
-                          void* stream) {
-  RolloutArgs a{};
-  if (int rc = pol_roll_nets(pol_sizes, pol_n_sizes, dyn_sizes, dyn_n_sizes, a.pol, a.dyn)) return rc;
-  const int n = a.dyn.dout(), m = a.dyn.din() - n;
-  if (!pol_roll_args_ok(a.dyn, s0, s0_stride, N, H, K, pol_params, pol_tr, noise_stride, dyn_params, dyn_tr, act, flags, a_min, a_max, s_min,
-                        s_max, obs_out, act_out))
-    return fail(MJX_ERR_ARG, "bad arguments");
-  // (the switches are read per call: A/B runs in one process; MJX_POLICY_ROLLOUT_MFMA=0 means no MFMA rollout at all)
-  ChainShape ps; size_t wide_bytes = 0;
-  const bool mfma = env_flag("MJX_POLICY_ROLLOUT_MFMA", true);
-  const bool served2 = wide && env_flag("MJX_POLICY_ROLLOUT_WIDE", true) && mfma && wide_roll_shape(a.dyn, a.pol, wide_bytes);
-  const bool served1 = mfma && pol_roll_shape(a.dyn, a.pol, ps);
-  auto done = [&](int route) { if (route_out) *route_out = route; return MJX_OK; };
-  if (N == 0 || H == 0) return done(served2 ? 2 : served1 ? 1 : 0);
-  MJX_DEVICE_ENTRY();
-  hipStream_t st = (hipStream_t)stream;
-  const PolRollArgs p{s0, s0_stride, noise, noise_stride ? (int64_t)H : 0, pol_params, pol_tr, dyn_params, dyn_tr, a_min, a_max, s_min, s_max,
-                      obs_out, act_out, N, a.dyn.P, H, n, m, a.dyn.sz[1], a.dyn.sz[2], act, flags, a.pol.sz[1], a.pol.sz[2]};
-  bool launched;
-  if (served2) {
-    if (int rc = launch_chained(k_policy_rollout_wide, wide_bytes, dim3((unsigned)((N + 31) / 32), (unsigned)K), p, st, launched, dim3(DFE_THREADS)))
-      return rc;
-    if (launched) return done(2);
-  }
-  if (served1) {
-    if (int rc = launch_chained(pol_roll_kernel(ps.HB, ps.NB), ps.bytes, dim3((unsigned)((N + 127) / 128), (unsigned)K), p, st, launched)) return rc;
-    if (launched) return done(1);
-  }
-  // generic route: k_model_rollout as mjx_model_rollout launches it; the tiled start state and the K copies of a shared noise
-  // block go to the calling thread's scratch block of this site on (device, stream)
-  const size_t s0_floats = s0_stride ? 0 : (size_t)N * n, nz_floats = (noise && !noise_stride && K > 1) ? (size_t)K * H * N * m : 0;
-  if (s0_floats + nz_floats) {
-    float* scr = nullptr;
-    if (int rc = dev_scratch(SITE_POLICY_ROLLOUT, stream, (s0_floats + nz_floats) * sizeof(float), &scr)) return rc;
-    if (s0_floats) s0 = tile_s0(s0, N, n, scr, st);
-    if (nz_floats) {
-      hipLaunchKernelGGL(k_pol_expand_noise, dim3(capped_grid((int64_t)nz_floats, 256, 4096)), dim3(256), 0, st, noise, (int64_t)H * N * m, K,
-                         scr + s0_floats);
-      noise = scr + s0_floats;
-    }
-    HIPCHK(hipGetLastError());
-  }
-  a.pol_P = pol_params; a.pol_tr = pol_tr; a.noise = noise; a.a_lo = a_min; a.a_hi = a_max; a.s_lo = s_min; a.s_hi = s_max;
-  if (int rc = launch_model_rollout(a, s0, N, H, K, nullptr, dyn_params, dyn_tr, act, flags, obs_out, act_out, st)) return rc;
-  return done(0);
+int mjx_policy_rollout_wide_route(const int* pol_sizes, int pol_n_sizes, const int* dyn_sizes, int dyn_n_sizes) {
+  return policy_rollout_route(true, pol_sizes, pol_n_sizes, dyn_sizes, dyn_n_sizes);
 }
-
 int mjx_policy_rollout(const float* s0, int64_t s0_stride, int64_t N, int H, int K, const int* pol_sizes, int pol_n_sizes,
                        const float* pol_params, const float* pol_tr, const float* noise, int64_t noise_stride, const int* dyn_sizes,
                        int dyn_n_sizes, const float* dyn_params, const float* dyn_tr, int act, int flags, const float* a_min,
@@ -737,15 +564,6 @@ int mjx_policy_rollout(const float* s0, int64_t s0_stride, int64_t N, int H, int
   return policy_rollout(false, s0, s0_stride, N, H, K, pol_sizes, pol_n_sizes, pol_params, pol_tr, noise, noise_stride, dyn_sizes, dyn_n_sizes,
                         dyn_params, dyn_tr, act, flags, a_min, a_max, s_min, s_max, obs_out, act_out, route_out, stream);
 }
-
-// ---------------------------------------------------------------------------- the same for nets up to 256 wide (csrc/policy_rollout_wide.h)
-int mjx_policy_rollout_wide_route(const int* pol_sizes, int pol_n_sizes, const int* dyn_sizes, int dyn_n_sizes) {
-  DynNet pol, dyn;
-  if (int rc = pol_roll_nets(pol_sizes, pol_n_sizes, dyn_sizes, dyn_n_sizes, pol, dyn)) return rc;
-  size_t bytes;
-  return wide_roll_shape(dyn, pol, bytes) ? 1 : 0;
-}
-
 int mjx_policy_rollout_wide(const float* s0, int64_t s0_stride, int64_t N, int H, int K, const int* pol_sizes, int pol_n_sizes,
                             const float* pol_params, const float* pol_tr, const float* noise, int64_t noise_stride, const int* dyn_sizes,
                             int dyn_n_sizes, const float* dyn_params, const float* dyn_tr, int act, int flags, const float* a_min,
@@ -755,79 +573,14 @@ int mjx_policy_rollout_wide(const float* s0, int64_t s0_stride, int64_t N, int H
                         dyn_params, dyn_tr, act, flags, a_min, a_max, s_min, s_max, obs_out, act_out, route_out, stream);
 }
 
-// ---------------------------------------------------------------------------- device-resident model rollouts (csrc/rollout_batch.h)
-int mjx_rollout_disagreement_route(const int* dyn_sizes, int dyn_n_sizes) {
-  DynNet dyn;
-  if (int rc = roll_dis_net(dyn_sizes, dyn_n_sizes, dyn)) return rc;
-  ChainShape ps;
-  return plan_shape(dyn, dyn.din() - dyn.dout(), ps) ? 1 : 0;
-}
-
-// mjx_rollout_disagreement (wide false) and mjx_rollout_disagreement_wide: route 2 where asked for, then 1, then 0
-static int rollout_disagreement(bool wide, const float* obs, const float* act, int64_t P, int H, int K, const int* dyn_sizes, int dyn_n_sizes,
-                                const float* dyn_params, const float* dyn_tr, int dyn_act, int dyn_flags, float* err_out, int* route_out,
-                                void* stream) {
-  DynNet dyn;
-  if (int rc = roll_dis_net(dyn_sizes, dyn_n_sizes, dyn)) return rc;
-  const int n = dyn.dout(), m = dyn.din() - n;
-  if (!roll_dis_args_ok(dyn, obs, act, P, H, K, dyn_params, dyn_tr, dyn_act, dyn_flags, err_out)) return fail(MJX_ERR_ARG, "bad arguments");
-  // (the switches are read per call: A/B runs in one process; MJX_ROLLOUT_DISAGREE_MFMA=0 means no MFMA route at all)
-  ChainShape ps; size_t wide_bytes = 0;
-  const bool mfma = env_flag("MJX_ROLLOUT_DISAGREE_MFMA", true);
-  const bool served2 = wide && env_flag("MJX_ROLLOUT_DISAGREE_WIDE", true) && mfma && wide_rows_shape(dyn, nullptr, wide_bytes);
-  const bool served1 = mfma && plan_shape(dyn, m, ps);
-  auto done = [&](int route) { if (route_out) *route_out = route; return MJX_OK; };
-  if (P == 0 || H <= 1) return done(served2 ? 2 : served1 ? 1 : 0);
-  MJX_DEVICE_ENTRY();
-  hipStream_t st = (hipStream_t)stream;
-  const int64_t rows = P * H, R = P * (H - 1);
-  const int din = n + m;
-  // one block serves every route: member means (K x R) on routes 1 and 2, [s, a] rows and predictions (R x din, K x R x n) on route 0
-  float* scr = nullptr;
-  if (int rc = dev_scratch(SITE_ROLLOUT_DISAGREE, stream, (size_t)R * (din + (size_t)K * n) * sizeof(float), &scr)) return rc;
-  const RollDisArgs a{obs, act, dyn_params, dyn_tr, scr, rows, dyn.P, H, n, m, dyn.sz[1], dyn.sz[2], dyn_act, dyn_flags};
-  int route = 0;
-  bool launched;
-  if (served2) {
-    if (int rc = launch_chained(k_rollout_disagree_wide<RW_NS>, wide_bytes, tile_grid(rows, 32 * RW_NS, K), a, st, launched, dim3(DFE_THREADS))) return rc;
-    if (launched) route = 2;
-  }
-  if (!route && served1) {
-    // as mjx_path_rewards: a wave owns tiles of 32 rows, one workgroup per CU holds the image, the K members share the CUs
-    if (int rc = launch_chained(roll_dis_kernel(ps.HB, ps.NB), ps.bytes, tile_grid(rows, 128, K), a, st, launched)) return rc;
-    if (launched) route = 1;
-  }
-  if (route) {                                              // the members' means lie in scratch: their maximum, in member order
-    hipLaunchKernelGGL(k_rd_max, dim3(capped_grid(R, 256, 4096)), dim3(256), 0, st, scr, K, R, err_out);
-    HIPCHK(hipGetLastError());
-    return done(route);
-  }
-  // generic route: mjx_dyn_forward's kernel over the gathered [s, a] rows (shared by the members), then mjx_dyn_pred_error's arithmetic
-  float* X = scr; float* pred = X + R * din;
-  const size_t bytes = sizeof(float) * 3 * DYN_FT * (size_t)dyn.maxw;
-  if (int rc = lds_limit((const void*)k_dyn_forward, bytes)) return rc;
-  hipLaunchKernelGGL(k_rd_gather, dim3(capped_grid(R * din, 256, 4096)), dim3(256), 0, st, obs, act, R, H, n, m, X);
-  DynFwdArgs fa{dyn, X, 0, R, dyn_params, dyn_tr, dyn_act, dyn_flags, pred};
-  hipLaunchKernelGGL(k_dyn_forward, dim3((unsigned)((R + DYN_FT - 1) / DYN_FT), (unsigned)K), dim3(256), bytes, st, fa);
-  hipLaunchKernelGGL(k_rd_reduce, dim3(capped_grid(R, 256, 4096)), dim3(256), 0, st, pred, obs, K, R, H, n, err_out);
-  HIPCHK(hipGetLastError());
-  return done(0);
-}
-
+// ---------------------------------------------------------------------------- device-resident model rollouts (csrc/rollout_batch.h, csrc/rows_wide.h)
+int mjx_rollout_disagreement_route(const int* dyn_sizes, int dyn_n_sizes) { return rollout_disagreement_route(false, dyn_sizes, dyn_n_sizes); }
+int mjx_rollout_disagreement_wide_route(const int* dyn_sizes, int dyn_n_sizes) { return rollout_disagreement_route(true, dyn_sizes, dyn_n_sizes); }
 int mjx_rollout_disagreement(const float* obs, const float* act, int64_t P, int H, int K, const int* dyn_sizes, int dyn_n_sizes,
                              const float* dyn_params, const float* dyn_tr, int dyn_act, int dyn_flags, float* err_out, int* route_out,
                              void* stream) {
   return rollout_disagreement(false, obs, act, P, H, K, dyn_sizes, dyn_n_sizes, dyn_params, dyn_tr, dyn_act, dyn_flags, err_out, route_out, stream);
 }
-
-// the same for nets up to 256 wide (csrc/rows_wide.h)
-int mjx_rollout_disagreement_wide_route(const int* dyn_sizes, int dyn_n_sizes) {
-  DynNet dyn;
-  if (int rc = roll_dis_net(dyn_sizes, dyn_n_sizes, dyn)) return rc;
-  size_t bytes;
-  return wide_rows_shape(dyn, nullptr, bytes) ? 1 : 0;
-}
-
 int mjx_rollout_disagreement_wide(const float* obs, const float* act, int64_t P, int H, int K, const int* dyn_sizes, int dyn_n_sizes,
                                   const float* dyn_params, const float* dyn_tr, int dyn_act, int dyn_flags, float* err_out, int* route_out,
                                   void* stream) {

@@ -1,7 +1,30 @@
 // model_host.h -- host side of the learned-model kernels (dynamics.h, dyn_fit_ens.h, plan.h, path_reward.h, plan_wide.h, policy_rollout.h, policy_rollout_wide.h, rollout_batch.h, rows_wide.h): their shared
-// argument checks, their routes as plain arithmetic, and the launches more than one entry makes.  Included by mjx.hip after fail / HIPCHK /
-// lds_limit / capped_grid.
+// argument checks, their routes as plain arithmetic, the launches more than one entry makes, and the four entries that have a wide
+// route (plan rollout, path rewards, policy rollout, rollout disagreement) with their route queries: mjx.hip only forwards to them.
+// The rule that orders an entry's routes is plain C++ on top (tests/c/model_host.cpp checks it against a table without a GPU); the
+// rest needs the HIP compiler and is included by mjx.hip after fail / HIPCHK / lds_limit / dev_scratch / capped_grid / MJX_DEVICE_ENTRY.
 #pragma once
+namespace mjx {
+
+// ---- the route ladder.  Route 2 is the wide LDS-tile kernel, route 1 the register-chained instance, route 0 the entry's generic
+// tail.  From what was asked (the ..._wide entry), the entry's two switches and what the two shape functions answered: the MFMA
+// routes to try, in order (a route whose LDS image the device refuses falls through to the next, at last to route 0), and what a
+// call without rows reports, which is the first of them.
+struct ModelRoutes {
+  int n = 0, route[2] = {0, 0};
+  int empty() const { return n ? route[0] : 0; }
+};
+inline ModelRoutes model_routes(bool asked_wide, bool mfma_on, bool wide_on, bool wide_fits, bool chained_fits) {
+  ModelRoutes r;
+  if (asked_wide && wide_on && mfma_on && wide_fits) r.route[r.n++] = 2;
+  if (mfma_on && chained_fits) r.route[r.n++] = 1;
+  return r;
+}
+
+}  // namespace mjx
+
+#ifdef __HIPCC__
+
 namespace mjx {
 
 inline int dyn_net(const int* sizes, int n_sizes, DynNet& net) {
@@ -113,6 +136,25 @@ inline dim3 tile_grid(int64_t rows, int tile_rows, int K) {
   const int64_t tiles = (rows + tile_rows - 1) / tile_rows, cap = (cu_count() + K - 1) / K;
   return dim3((unsigned)(tiles < cap ? tiles : cap), (unsigned)K);
 }
+// The walk over an entry's MFMA routes: the wide kernel on tiles of wide_tile rows, then the instance `chained` names for ps on
+// tiles of 128.  per_cu: the kernels walk stored rows (tile_grid); else a workgroup per tile of trajectories.  -> MJX_OK with
+// `route` 2 or 1, whichever launched, or 0: none did and the caller takes its generic route; or a launch's error.
+template <class Args>
+inline int launch_routes(const ModelRoutes& r, void (*wide)(Args), size_t wide_bytes, int wide_tile, void (*(*chained)(int, int))(Args),
+                         const ChainShape& ps, int64_t rows, int K, bool per_cu, const Args& a, hipStream_t st, int& route) {
+  auto grid = [&](int tile) { return per_cu ? tile_grid(rows, tile, K) : dim3((unsigned)((rows + tile - 1) / tile), (unsigned)K); };
+  route = 0;
+  for (int i = 0; i < r.n; ++i) {
+    bool launched;
+    if (int rc = r.route[i] == 2 ? launch_chained(wide, wide_bytes, grid(wide_tile), a, st, launched, dim3(DFE_THREADS))
+                                 : launch_chained(chained(ps.HB, ps.NB), ps.bytes, grid(128), a, st, launched))
+      return rc;
+    if (launched) { route = r.route[i]; break; }
+  }
+  return MJX_OK;
+}
+// an entry's last statement: the route that served the call, where the caller asked for it
+inline int route_done(int* route_out, int route) { if (route_out) *route_out = route; return MJX_OK; }
 // ---- wide policy rollout.  What k_policy_rollout_wide (policy_rollout_wide.h) serves: nets as wide_nets_ok takes them and its LDS
 // layout (the kernel has no static LDS) within LDS_MAX.  It does not ask what pol_roll_shape answers: the shapes the chained
 // kernel takes are served as well.  MJX_POLICY_ROLLOUT_WIDE=0 or MJX_POLICY_ROLLOUT_MFMA=0 (read per call by
@@ -253,4 +295,193 @@ inline bool reward_fit_serves(const DynNet& net, int batch) {
   for (int l = 1; l <= 2; ++l) if (net.sz[l] < 1 || net.sz[l] > DFE_MAXH) return false;
   return net.din() <= DFE_MAXIN && net.dout() <= DFE_MAXOUT;
 }
+
+// ---------------------------------------------------------------------------- the four entries with a wide route, and their route queries
+// Each: parse the nets, check the arguments, model_routes from the entry's two switches (read per call: A/B runs in one process;
+// ..._MFMA=0 means no MFMA route at all) and its two shape functions, the answer of a call without rows before any device work,
+// launch_routes, then the entry's own generic tail.  `wide`: the ..._wide entry (the query: of the wide route).
+
+// ---- MPC planning on learned models (plan.h, plan_wide.h)
+inline int plan_route(bool wide, const int* dyn_sizes, int dyn_n_sizes, int act_dim) {
+  DynNet net;
+  if (int rc = dyn_net(dyn_sizes, dyn_n_sizes, net)) return rc;
+  if (act_dim <= 0 || net.din() != net.dout() + act_dim) return fail(MJX_ERR_ARG, "dyn_sizes must be [n + m, h..., n] with m = act_dim > 0");
+  ChainShape ps; size_t bytes;
+  return (wide ? wide_plan_shape(net, bytes) : plan_shape(net, act_dim, ps)) ? 1 : 0;
+}
+// (mjx_plan_rollout takes any flags, as it always has; mjx_plan_rollout_wide refuses unknown bits)
+inline int plan_rollout(bool wide, const float* s0, int64_t s0_stride, int64_t N, int H, int K, const float* actions, const int* dyn_sizes,
+                        int dyn_n_sizes, const float* dyn_params, const float* dyn_tr, int act, int flags, float* obs_out, int* route_out,
+                        void* stream) {
+  DynNet net;
+  if (int rc = dyn_net(dyn_sizes, dyn_n_sizes, net)) return rc;
+  const int n = net.dout(), m = net.din() - n;
+  if (!s0 || !actions || !dyn_params || !dyn_tr || !obs_out || N < 0 || H < 0 || m <= 0 || (s0_stride != 0 && s0_stride != n) ||
+      !dyn_args_ok(net, K, act) || (wide && (flags & ~(DYN_OUT_AFFINE | DYN_MASK | DYN_RESIDUAL))))
+    return fail(MJX_ERR_ARG, "bad arguments");
+  ChainShape ps; size_t wide_bytes = 0;
+  const ModelRoutes r = model_routes(wide, env_flag("MJX_PLAN_MFMA", true), env_flag("MJX_PLAN_WIDE", true), wide_plan_shape(net, wide_bytes),
+                                     plan_shape(net, m, ps));
+  if (N == 0 || H == 0) return route_done(route_out, r.empty());
+  MJX_DEVICE_ENTRY();
+  hipStream_t st = (hipStream_t)stream;
+  const PlanArgs p{s0, s0_stride, actions, dyn_params, dyn_tr, obs_out, N, net.P, H, n, m, net.sz[1], net.sz[2], act, flags};
+  int route;
+  if (int rc = launch_routes(r, k_plan_rollout_wide, wide_bytes, 32, plan_kernel, ps, N, K, false, p, st, route)) return rc;
+  if (route) return route_done(route_out, route);
+  // generic route: k_model_rollout with the actions given, as mjx_model_rollout launches it; its action copy and the tiled
+  // start state go to scratch
+  float* scr = nullptr;
+  const size_t act_floats = (size_t)K * N * H * m, s0_floats = s0_stride ? 0 : (size_t)N * n;
+  if (int rc = dev_scratch(SITE_PLAN_ROLLOUT, stream, (act_floats + s0_floats) * sizeof(float), &scr)) return rc;
+  if (!s0_stride) s0 = tile_s0(s0, N, n, scr + act_floats, st);
+  RolloutArgs a{};
+  a.dyn = net;
+  if (int rc = launch_model_rollout(a, s0, N, H, K, actions, dyn_params, dyn_tr, act, flags, obs_out, scr, st)) return rc;
+  return route_done(route_out, 0);
+}
+
+// ---- learned path rewards (path_reward.h, rows_wide.h)
+inline int path_rewards_route(bool wide, const int* dyn_sizes, int dyn_n_sizes, const int* rew_sizes, int rew_n_sizes) {
+  DynNet dyn, rew;
+  if (int rc = path_rew_nets(dyn_sizes, dyn_n_sizes, rew_sizes, rew_n_sizes, dyn, rew)) return rc;
+  ChainShape ps; size_t bytes;
+  return (wide ? wide_rows_shape(dyn, &rew, bytes) : path_rew_shape(dyn, rew, ps)) ? 1 : 0;
+}
+inline int path_rewards(bool wide, const float* obs, const float* act, int64_t act_stride, int64_t rows, int K, const int* dyn_sizes,
+                        int dyn_n_sizes, const float* dyn_params, const float* dyn_tr, int dyn_act, int dyn_flags, const int* rew_sizes,
+                        int rew_n_sizes, const float* rew_params, const float* rew_tr, int rew_act, float* r32_out, double* r64_out,
+                        int* route_out, void* stream) {
+  DynNet dyn, rew;
+  if (int rc = path_rew_nets(dyn_sizes, dyn_n_sizes, rew_sizes, rew_n_sizes, dyn, rew)) return rc;
+  const int n = dyn.dout(), m = dyn.din() - n;
+  if (!path_rew_args_ok(dyn, rew, obs, act, act_stride, rows, K, dyn_params, dyn_tr, dyn_act, dyn_flags, rew_params, rew_tr, rew_act, r32_out, r64_out))
+    return fail(MJX_ERR_ARG, "bad arguments");
+  ChainShape ps; size_t wide_bytes = 0;
+  const ModelRoutes r = model_routes(wide, env_flag("MJX_PATH_REWARDS_MFMA", true), env_flag("MJX_PATH_REWARDS_WIDE", true),
+                                     wide_rows_shape(dyn, &rew, wide_bytes), path_rew_shape(dyn, rew, ps));
+  if (rows == 0) return route_done(route_out, r.empty());
+  MJX_DEVICE_ENTRY();
+  hipStream_t st = (hipStream_t)stream;
+  const PathRewArgs a{obs, act, act_stride, dyn_params, dyn_tr, rew_params, rew_tr, r32_out, r64_out, rows, dyn.P, rew.P,
+                      n, m, dyn.sz[1], dyn.sz[2], dyn_act, dyn_flags, rew.sz[1], rew.sz[2], rew_act};
+  // (route 1: a wave owns tiles of 32 rows; one workgroup per CU holds the image, so the K members share the CUs and a wave walks
+  //  the tiles beyond that -- the staging prologue is paid once per workgroup)
+  int route;
+  if (int rc = launch_routes(r, k_path_rewards_wide<RW_NS>, wide_bytes, 32 * RW_NS, path_rew_kernel, ps, rows, K, true, a, st, route)) return rc;
+  if (route) return route_done(route_out, route);
+  // generic route: mjx_dyn_forward's kernel twice, over [s, a] and over [s, a, s'], both assembled in scratch
+  const int din = n + m, rin = din + n;
+  const int64_t kr = (int64_t)K * rows;
+  float* scr = nullptr;
+  if (int rc = dev_scratch(SITE_PATH_REWARDS, stream, (size_t)kr * (din + rin + n + 1) * sizeof(float), &scr)) return rc;
+  float* X1 = scr; float* X2 = X1 + kr * din; float* sp = X2 + kr * rin; float* r32 = r32_out ? r32_out : sp + kr * n;
+  const size_t b1 = sizeof(float) * 3 * DYN_FT * (size_t)dyn.maxw, b2 = sizeof(float) * 3 * DYN_FT * (size_t)rew.maxw;
+  if (int rc = lds_limit((const void*)k_dyn_forward, b1 > b2 ? b1 : b2)) return rc;
+  const dim3 grid((unsigned)((rows + DYN_FT - 1) / DYN_FT), (unsigned)K);
+  hipLaunchKernelGGL(k_pr_gather_sa, dim3(capped_grid(kr * din, 256, 4096)), dim3(256), 0, st, obs, act, act_stride, rows, K, n, m, X1, X2);
+  DynFwdArgs fa{dyn, X1, rows * din, rows, dyn_params, dyn_tr, dyn_act, dyn_flags, sp};
+  hipLaunchKernelGGL(k_dyn_forward, grid, dim3(256), b1, st, fa);
+  hipLaunchKernelGGL(k_pr_gather_sp, dim3(capped_grid(kr * n, 256, 4096)), dim3(256), 0, st, sp, kr, n, m, X2);
+  DynFwdArgs fr{rew, X2, rows * rin, rows, rew_params, rew_tr, rew_act, DYN_OUT_AFFINE, r32};
+  hipLaunchKernelGGL(k_dyn_forward, grid, dim3(256), b2, st, fr);
+  if (r64_out) hipLaunchKernelGGL(k_pr_widen, dim3(capped_grid(kr, 256, 4096)), dim3(256), 0, st, r32, kr, r64_out);
+  HIPCHK(hipGetLastError());
+  return route_done(route_out, 0);
+}
+
+// ---- policy rollout on learned models (policy_rollout.h, policy_rollout_wide.h)
+inline int policy_rollout_route(bool wide, const int* pol_sizes, int pol_n_sizes, const int* dyn_sizes, int dyn_n_sizes) {
+  DynNet pol, dyn;
+  if (int rc = pol_roll_nets(pol_sizes, pol_n_sizes, dyn_sizes, dyn_n_sizes, pol, dyn)) return rc;
+  ChainShape ps; size_t bytes;
+  return (wide ? wide_roll_shape(dyn, pol, bytes) : pol_roll_shape(dyn, pol, ps)) ? 1 : 0;
+}
+inline int policy_rollout(bool wide, const float* s0, int64_t s0_stride, int64_t N, int H, int K, const int* pol_sizes, int pol_n_sizes,
+                          const float* pol_params, const float* pol_tr, const float* noise, int64_t noise_stride, const int* dyn_sizes,
+                          int dyn_n_sizes, const float* dyn_params, const float* dyn_tr, int act, int flags, const float* a_min,
+                          const float* a_max, const float* s_min, const float* s_max, float* obs_out, float* act_out, int* route_out,
+                          void* stream) {
+  RolloutArgs a{};
+  if (int rc = pol_roll_nets(pol_sizes, pol_n_sizes, dyn_sizes, dyn_n_sizes, a.pol, a.dyn)) return rc;
+  const int n = a.dyn.dout(), m = a.dyn.din() - n;
+  if (!pol_roll_args_ok(a.dyn, s0, s0_stride, N, H, K, pol_params, pol_tr, noise_stride, dyn_params, dyn_tr, act, flags, a_min, a_max, s_min,
+                        s_max, obs_out, act_out))
+    return fail(MJX_ERR_ARG, "bad arguments");
+  ChainShape ps; size_t wide_bytes = 0;
+  const ModelRoutes r = model_routes(wide, env_flag("MJX_POLICY_ROLLOUT_MFMA", true), env_flag("MJX_POLICY_ROLLOUT_WIDE", true),
+                                     wide_roll_shape(a.dyn, a.pol, wide_bytes), pol_roll_shape(a.dyn, a.pol, ps));
+  if (N == 0 || H == 0) return route_done(route_out, r.empty());
+  MJX_DEVICE_ENTRY();
+  hipStream_t st = (hipStream_t)stream;
+  const PolRollArgs p{s0, s0_stride, noise, noise_stride ? (int64_t)H : 0, pol_params, pol_tr, dyn_params, dyn_tr, a_min, a_max, s_min, s_max,
+                      obs_out, act_out, N, a.dyn.P, H, n, m, a.dyn.sz[1], a.dyn.sz[2], act, flags, a.pol.sz[1], a.pol.sz[2]};
+  int route;
+  if (int rc = launch_routes(r, k_policy_rollout_wide, wide_bytes, 32, pol_roll_kernel, ps, N, K, false, p, st, route)) return rc;
+  if (route) return route_done(route_out, route);
+  // generic route: k_model_rollout as mjx_model_rollout launches it; the tiled start state and the K copies of a shared noise
+  // block go to the calling thread's scratch block of this site on (device, stream)
+  const size_t s0_floats = s0_stride ? 0 : (size_t)N * n, nz_floats = (noise && !noise_stride && K > 1) ? (size_t)K * H * N * m : 0;
+  if (s0_floats + nz_floats) {
+    float* scr = nullptr;
+    if (int rc = dev_scratch(SITE_POLICY_ROLLOUT, stream, (s0_floats + nz_floats) * sizeof(float), &scr)) return rc;
+    if (s0_floats) s0 = tile_s0(s0, N, n, scr, st);
+    if (nz_floats) {
+      hipLaunchKernelGGL(k_pol_expand_noise, dim3(capped_grid((int64_t)nz_floats, 256, 4096)), dim3(256), 0, st, noise, (int64_t)H * N * m, K,
+                         scr + s0_floats);
+      noise = scr + s0_floats;
+    }
+    HIPCHK(hipGetLastError());
+  }
+  a.pol_P = pol_params; a.pol_tr = pol_tr; a.noise = noise; a.a_lo = a_min; a.a_hi = a_max; a.s_lo = s_min; a.s_hi = s_max;
+  if (int rc = launch_model_rollout(a, s0, N, H, K, nullptr, dyn_params, dyn_tr, act, flags, obs_out, act_out, st)) return rc;
+  return route_done(route_out, 0);
+}
+
+// ---- disagreement of stored rollouts (rollout_batch.h, rows_wide.h)
+inline int rollout_disagreement_route(bool wide, const int* dyn_sizes, int dyn_n_sizes) {
+  DynNet dyn;
+  if (int rc = roll_dis_net(dyn_sizes, dyn_n_sizes, dyn)) return rc;
+  ChainShape ps; size_t bytes;
+  return (wide ? wide_rows_shape(dyn, nullptr, bytes) : plan_shape(dyn, dyn.din() - dyn.dout(), ps)) ? 1 : 0;
+}
+inline int rollout_disagreement(bool wide, const float* obs, const float* act, int64_t P, int H, int K, const int* dyn_sizes, int dyn_n_sizes,
+                                const float* dyn_params, const float* dyn_tr, int dyn_act, int dyn_flags, float* err_out, int* route_out,
+                                void* stream) {
+  DynNet dyn;
+  if (int rc = roll_dis_net(dyn_sizes, dyn_n_sizes, dyn)) return rc;
+  const int n = dyn.dout(), m = dyn.din() - n;
+  if (!roll_dis_args_ok(dyn, obs, act, P, H, K, dyn_params, dyn_tr, dyn_act, dyn_flags, err_out)) return fail(MJX_ERR_ARG, "bad arguments");
+  ChainShape ps; size_t wide_bytes = 0;
+  const ModelRoutes r = model_routes(wide, env_flag("MJX_ROLLOUT_DISAGREE_MFMA", true), env_flag("MJX_ROLLOUT_DISAGREE_WIDE", true),
+                                     wide_rows_shape(dyn, nullptr, wide_bytes), plan_shape(dyn, m, ps));
+  if (P == 0 || H <= 1) return route_done(route_out, r.empty());
+  MJX_DEVICE_ENTRY();
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t rows = P * H, R = P * (H - 1);
+  const int din = n + m;
+  // one block serves every route: member means (K x R) on routes 1 and 2, [s, a] rows and predictions (R x din, K x R x n) on route 0
+  float* scr = nullptr;
+  if (int rc = dev_scratch(SITE_ROLLOUT_DISAGREE, stream, (size_t)R * (din + (size_t)K * n) * sizeof(float), &scr)) return rc;
+  const RollDisArgs a{obs, act, dyn_params, dyn_tr, scr, rows, dyn.P, H, n, m, dyn.sz[1], dyn.sz[2], dyn_act, dyn_flags};
+  int route;
+  if (int rc = launch_routes(r, k_rollout_disagree_wide<RW_NS>, wide_bytes, 32 * RW_NS, roll_dis_kernel, ps, rows, K, true, a, st, route)) return rc;
+  if (route) {                                              // the members' means lie in scratch: their maximum, in member order
+    hipLaunchKernelGGL(k_rd_max, dim3(capped_grid(R, 256, 4096)), dim3(256), 0, st, scr, K, R, err_out);
+    HIPCHK(hipGetLastError());
+    return route_done(route_out, route);
+  }
+  // generic route: mjx_dyn_forward's kernel over the gathered [s, a] rows (shared by the members), then mjx_dyn_pred_error's arithmetic
+  float* X = scr; float* pred = X + R * din;
+  const size_t bytes = sizeof(float) * 3 * DYN_FT * (size_t)dyn.maxw;
+  if (int rc = lds_limit((const void*)k_dyn_forward, bytes)) return rc;
+  hipLaunchKernelGGL(k_rd_gather, dim3(capped_grid(R * din, 256, 4096)), dim3(256), 0, st, obs, act, R, H, n, m, X);
+  DynFwdArgs fa{dyn, X, 0, R, dyn_params, dyn_tr, dyn_act, dyn_flags, pred};
+  hipLaunchKernelGGL(k_dyn_forward, dim3((unsigned)((R + DYN_FT - 1) / DYN_FT), (unsigned)K), dim3(256), bytes, st, fa);
+  hipLaunchKernelGGL(k_rd_reduce, dim3(capped_grid(R, 256, 4096)), dim3(256), 0, st, pred, obs, K, R, H, n, err_out);
+  HIPCHK(hipGetLastError());
+  return route_done(route_out, 0);
+}
 }  // namespace mjx
+
+#endif  // __HIPCC__

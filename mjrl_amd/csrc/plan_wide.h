@@ -2,42 +2,22 @@
 // K members, from s0, storing obs (K, N, H, n)) for the nets its register chain does not hold: dynamics nets up to 256 x 256 (the
 // shape of both configs the reference ships), any hidden width 1 .. 256, n <= 64, m <= 64, n + m <= 128 (wide_nets_ok).
 //
-// The scheme is k_policy_rollout_wide's (policy_rollout_wide.h) without the policy half: activations as [unit][sample] LDS tiles,
-// weights streamed row-major from the member's block in global memory, products on v_mfma_f32_32x32x2_f32 through
-// dfe_forward3<1> (dfe_tiles.h), a wave per output tile of 32 units.  Grid (ceil(N / 32), K), DFE_THREADS threads: a workgroup is
-// ONE tile of 32 trajectories of one member through all H steps.  The planner's call (K 4, N 250) is 32 workgroups on 256 CUs and a
-// step is a dependent chain, so the 32-row tile is the latency choice.
+// The scheme, the tile conventions, the thread mapping (dfe_tiles.h wr_map), the padding rules and what is out of scope are
+// k_policy_rollout_wide's (policy_rollout_wide.h), and a step has its order and expressions.  What is different here:
 //
-// Where things live (ST = 32 + 4 floats a row):
-//   S    n rows            the raw state of the tile, kept between steps
-//   XD   pad8(n + m) rows  the normalised dynamics input [s, a]; its padding rows are zeroed once (nothing else writes them)
-//   H1   pad32(h1) rows | H2  pad32(h2) rows | Z3  pad32(n) rows: the hidden and output tiles
-//   C    h1 + h2 + n + 2 (n + m) + 2 n floats: the member's b1, b2, b3 and transforms, staged once by dfe_stage_net
-// Z3 keeps rows of its own (it could take H1's, as rows_wide.h's regions do): the largest served shape (64, 64, 256 x 256) is
-// (768 x 36 + 960) x 4 B = 114 432 B without that, under the 160 KiB a workgroup may have, and a grid of a few dozen workgroups
-// leaves nothing to gain from a smaller footprint.  plan_wide_lds_floats is the only place that sums the layout; the kernel has
-// no static LDS.
+// No policy half.  The layout is S | XD | H1 | H2 | Z3 and the member's staged vectors; Z3 keeps rows of its own (it could take
+// H1's, as rows_wide.h's regions do): the largest served shape (64, 64, 256 x 256) is (768 x 36 + 960) x 4 B = 114 432 B without
+// that, and a grid of a few dozen workgroups (the planner's call, K 4, N 250, is 32 on 256 CUs) leaves nothing to gain from a
+// smaller footprint.  plan_wide_lds_floats is the only place that sums the layout; the kernel has no static LDS.  There is no
+// clamp (trajectory_rollout has none), and the forward after the last stored state is not run.
 //
-// A step, with a workgroup barrier between the phases, in k_model_rollout's order and with its expressions (dynamics.h):
-//   store s; the state rows of XD = (s - in_shift) / (in_scale + 1e-8) | request the actions of step t + 1 | H1 | H2 | Z3 |
-//   flags (1 affine, 2 mask, 4 residual) -> S, the residual reading S before it is overwritten; the action rows of XD for
-//   step t + 1 = (a - in_shift) / (in_scale + 1e-8)
-// The last phase and the next step's first one give an element of S to the same thread, so no barrier stands between them.  There
-// is no clamp (trajectory_rollout has none), and the forward after the last stored state is not run.
-//
-// The actions.  Thread (u0, c) owns the action rows f = u0 + 16 q of sample column c.  It requests those of step t + 1 from global
-// memory into registers BEFORE the forward of step t and writes them into XD AFTER that forward, so the load is in flight under
-// the three layers.  Only layer 1 reads XD, and dfe_forward2's barrier after layer 1 stands between every wave's last read of XD
-// and this write; the barrier that ends the next step's first phase stands between the write and layer 1's next read.  (The
-// policy kernel writes its action rows before the forward because its actions come out of the policy of the same step; here
-// they are known a step ahead, which is the one deviation from its order.)
-//
-// Padded unit rows of every tile are exact zeros (dfe_forward writes zeros there whatever act(b) would be); padded sample columns
-// (row >= N) start from a zero state with zero actions, are computed and never stored.  A sample column reaches only its own
-// output column, so a NaN trajectory stays alone.  No atomics and no reductions across lanes: the bits are the same every run.
-//
-// Out of scope: more or fewer than two hidden layers, several workgroups per tile, bf16x3 products, a 64-row tile (768 rows x 68
-// floats is over 160 KiB at the largest served shape).
+// The actions are known a step ahead.  Thread (u0, c) owns the action rows f = u0 + 16 q of sample column c.  It requests those of
+// step t + 1 from global memory into registers BEFORE the forward of step t and writes them into XD AFTER that forward, so the
+// load is in flight under the three layers.  Only layer 1 reads XD, and dfe_forward2's barrier after layer 1 stands between every
+// wave's last read of XD and this write; the barrier that ends the next step's first phase stands between the write and layer
+// 1's next read.  (The policy kernel writes its action rows before the forward: its actions come out of the policy of the same
+// step.)  A step is then: store s and the state rows of XD | request the actions of step t + 1 | H1 | H2 | Z3 | flags -> S; the
+// action rows of XD for step t + 1.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -47,10 +27,9 @@
 
 namespace mjx {
 
-constexpr int PLW_ST = 32 + 4;                              // floats a tile row
 // the layout: S | XD | H1 | H2 | Z3 rows, then the staged vectors (b1, b2, b3, transforms)
 __host__ __device__ constexpr size_t plan_wide_lds_floats(int n, int m, int h1, int h2) {
-  return (size_t)(n + pad8(n + m) + dfe_pad32(h1) + dfe_pad32(h2) + dfe_pad32(n)) * PLW_ST + (h1 + h2 + n + 2 * (n + m) + 2 * n);
+  return (size_t)(n + pad8(n + m) + dfe_pad32(h1) + dfe_pad32(h2) + dfe_pad32(n)) * WR_ST + (h1 + h2 + n + 2 * (n + m) + 2 * n);
 }
 // (the count itself, pinned: the largest served shape, the reference's config, a ragged shape, the smallest shape)
 static_assert(plan_wide_lds_floats(64, 64, 256, 256) == 36 * 768 + 960, "plan_wide_lds_floats");
@@ -62,7 +41,7 @@ static_assert(plan_wide_lds_floats(1, 1, 1, 1) == 36 * (1 + 8 + 32 + 32 + 32) + 
 // PlanArgs as mjx_plan_rollout fills them (plan.h)
 __global__ __launch_bounds__(DFE_THREADS) void k_plan_rollout_wide(PlanArgs a) {
   extern __shared__ __attribute__((aligned(16))) float plw[];
-  constexpr int ST = PLW_ST;
+  constexpr int ST = WR_ST, UQ = WR_UQ, NZ = WR_NZ;
   const int tid = threadIdx.x, w = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, j = lane & 31, hi = lane >> 5;
   const int n = a.n, m = a.m, din = n + m, h1 = a.h1, h2 = a.h2;
   const int K0 = pad8(din);
@@ -73,15 +52,12 @@ __global__ __launch_bounds__(DFE_THREADS) void k_plan_rollout_wide(PlanArgs a) {
   float* cst = Z3 + dfe_pad32(n) * ST;
   const WideNet dyn = dfe_stage_net(cst, a.P + k * a.Pstride, a.tr + (int64_t)k * (2 * din + 2 * n), din, h1, h2, n, a.act, 0, tid);
   const float* dtr = dyn.tr;
-  // a thread's elements of a [rows][32] block: e = tid + DFE_THREADS q is row e / 32, sample column tid % 32
-  const int c = tid & 31, u0 = tid >> 5;
-  constexpr int UQ = DFE_THREADS / 32;                      // rows between a thread's elements
-  const int64_t row = (int64_t)blockIdx.x * 32 + c;
-  const bool valid = row < a.N;
-  const int64_t vrow = valid ? row : 0;
+  const WideRollMap tm = wr_map(tid, a.N);
+  const int c = tm.c, u0 = tm.u0;
+  const bool valid = tm.valid;
+  const int64_t vrow = tm.vrow;
   float* __restrict__ orow = a.obs + ((int64_t)k * a.N + vrow) * a.H * (int64_t)n;
   const float* __restrict__ arow = a.actions + vrow * a.H * (int64_t)m;
-  constexpr int NZ = WIDE_MAXM / UQ;                         // action rows a thread owns (m <= 64)
   float an[NZ];
 #pragma unroll
   for (int q = 0; q < NZ; ++q) { const int f = u0 + UQ * q; an[q] = (valid && f < m) ? arow[f] : 0.f; }

@@ -43,7 +43,6 @@
 
 namespace mjx {
 
-constexpr int PRW_ST = 32 + 4;                              // floats a tile row
 // rows of the region the policy and the dynamics forward take in turn
 __host__ __device__ constexpr int prw_shared_rows(int n, int m, int h1, int h2, int p1, int p2) {
   return dfe_pad32(h1) + dfe_pad32(h2) + dfe_pad32(n) > pad8(n) + dfe_pad32(p1) + dfe_pad32(p2) + dfe_pad32(m)
@@ -55,13 +54,13 @@ __host__ __device__ constexpr int prw_const_floats(int n, int m, int h1, int h2,
   return p1 + p2 + 2 * m + (2 * n + 2 * m) + h1 + h2 + n + (2 * (n + m) + 2 * n);
 }
 __host__ __device__ constexpr size_t wide_roll_lds_floats(int n, int m, int h1, int h2, int p1, int p2) {
-  return (size_t)(n + pad8(n + m) + prw_shared_rows(n, m, h1, h2, p1, p2)) * PRW_ST + prw_const_floats(n, m, h1, h2, p1, p2);
+  return (size_t)(n + pad8(n + m) + prw_shared_rows(n, m, h1, h2, p1, p2)) * WR_ST + prw_const_floats(n, m, h1, h2, p1, p2);
 }
 
 // PolRollArgs as mjx_policy_rollout fills them (policy_rollout.h)
 __global__ __launch_bounds__(DFE_THREADS) void k_policy_rollout_wide(PolRollArgs a) {
   extern __shared__ __attribute__((aligned(16))) float prw[];
-  constexpr int ST = PRW_ST;
+  constexpr int ST = WR_ST, UQ = WR_UQ, NZ = WR_NZ;
   const int tid = threadIdx.x, w = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, j = lane & 31, hi = lane >> 5;
   const int n = a.n, m = a.m, din = n + m, h1 = a.h1, h2 = a.h2, p1 = a.p1, p2 = a.p2;
   const int n8 = pad8(n), K0 = pad8(din);
@@ -75,18 +74,15 @@ __global__ __launch_bounds__(DFE_THREADS) void k_policy_rollout_wide(PolRollArgs
   const WideNet pol = dfe_stage_net(cst, a.pP, a.ptr, n, p1, p2, m, DYN_ACT_TANH, m, tid);
   const WideNet dyn = dfe_stage_net(cst, a.P + k * a.Pstride, a.tr + (int64_t)k * (2 * din + 2 * n), din, h1, h2, n, a.act, 0, tid);
   const float* ptr = pol.tr; const float* sig = pol.tail; const float* dtr = dyn.tr;
-  // a thread's elements of a [rows][32] block: e = tid + DFE_THREADS q is row e / 32, sample column tid % 32
-  const int c = tid & 31, u0 = tid >> 5;
-  constexpr int UQ = DFE_THREADS / 32;                      // rows between a thread's elements
-  const int64_t row = (int64_t)blockIdx.x * 32 + c;
-  const bool valid = row < a.N;
-  const int64_t vrow = valid ? row : 0;
+  const WideRollMap tm = wr_map(tid, a.N);
+  const int c = tm.c, u0 = tm.u0;
+  const bool valid = tm.valid;
+  const int64_t vrow = tm.vrow;
   float* __restrict__ orow = a.obs + ((int64_t)k * a.N + vrow) * a.H * (int64_t)n;
   float* __restrict__ arow = a.act_out + ((int64_t)k * a.N + vrow) * a.H * (int64_t)m;
   const bool noisy = a.noise != nullptr;
   const float* __restrict__ zrow = noisy ? a.noise + ((int64_t)k * a.noise_k * a.N + vrow) * m : nullptr;
   const int64_t zstep = a.N * (int64_t)m;
-  constexpr int NZ = WIDE_MAXM / UQ;                         // actions a thread forms (m <= 64)
   float nz[NZ];
 #pragma unroll
   for (int q = 0; q < NZ; ++q) { const int f = u0 + UQ * q; nz[q] = (noisy && valid && f < m) ? zrow[f] : 0.f; }

@@ -159,7 +159,7 @@ def kref(name):
     return float(np.load(FIXTURE)["kref_" + name])
 
 
-# ---- the host's launch arithmetic (mjx_path_rewards in mjx.hip, path_rew_shape in model_host.h)
+# ---- the host's launch arithmetic (path_rewards and path_rew_shape in model_host.h)
 def instance(name):
     c = CASES[name]
     HB = max(c["dh"]) // 32

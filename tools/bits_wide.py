@@ -1,9 +1,10 @@
-"""Every output array of the three _wide entries over the cases of tests/_rows_wide_cases.py and tests/_rollout_wide_cases.py, for
-comparing two builds bit by bit (a refactor's evidence; needs the GPU):
+"""Every output array of the four _wide entries over the cases of tests/_rows_wide_cases.py, tests/_rollout_wide_cases.py and
+tests/_plan_wide_cases.py, for comparing two builds bit by bit (a refactor's evidence; needs the GPU):
     MJX_LIB=<libmjx.so> python tools/bits_wide.py dump out.npz      one fresh process per library
     python tools/bits_wide.py compare a.npz b.npz [out.json]         array_equal on the raw bytes of every array
 Each case runs through its wide entry on every route: the default, MJX_..._WIDE=0 and MJX_..._MFMA=0.  Rewards: both action modes
-the case has, r32 and r64; the rollout: the case's noise and the other layout (shared by the members / per member) too."""
+the case has, r32 and r64; the policy rollout: the case's noise and the other layout (shared by the members / per member) too; the
+plan rollout: every start-state mode the case has."""
 import ctypes
 import json
 import os
@@ -21,6 +22,7 @@ def dump(path):
     import torch
     from mjrl_amd import _lib
     from mjrl_amd._lib import ptr
+    import _plan_wide_cases as Q
     import _rollout_wide_cases as R
     import _rows_wide_cases as W
     from tests._worker_dev import ints, nan_block, switch, up
@@ -82,6 +84,19 @@ def dump(path):
                 key = "rollout/%s/noise_%s/%s" % (name, nzname, tag)
                 take(key + "/obs", ob, K * N * H * n, route)
                 take(key + "/act", ab, K * N * H * m, route)
+    for name in Q.ORDER:
+        mem, data = Q.cached_case(name)
+        c, ds = Q.CASES[name], mem["sizes"]
+        K, N, H, n = c["K"], c["rows"], c["H"], c["n"]
+        d = [up(np.stack(mem[k])) for k in ("thetas", "trs")]
+        for mode, (s0, actions) in sorted(data.items()):
+            s0_d, act_d = up(s0), up(actions)
+            for tag, wide, mfma in ROUTES:
+                ob, route = nan_block(K * N * H * n), ctypes.c_int(-9)
+                with switch("MJX_PLAN_WIDE", wide), switch("MJX_PLAN_MFMA", mfma):
+                    _lib.check(lib.mjx_plan_rollout_wide(ptr(s0_d), n if s0.ndim == 2 else 0, N, H, K, ptr(act_d), ints(ds), len(ds), ptr(d[0]),
+                                                         ptr(d[1]), mem["act"], mem["flags"], ptr(ob), ctypes.byref(route), None))
+                take("plan/%s/s0_%s/%s/obs" % (name, mode, tag), ob, K * N * H * n, route)
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
     np.savez(path, **out)
     print("dumped", len(out) // 2, "arrays from", _lib.LIB_PATH)
