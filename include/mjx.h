@@ -402,15 +402,19 @@ int mjx_mlp_predict(const float* feat, int64_t N, int d_in, const int* hidden, i
  * drawn by the caller to keep NumPy's RNG stream); params / m / v are updated in place, step0 = number
  * of Adam steps already taken; epoch_loss_out[e] = sum of minibatch losses of epoch e (device).
  * The reference's shape (two hidden layers of 128, batch 64) runs as ONE persistent launch: one workgroup up to 55 inputs,
- * ceil(d_in / 48) workgroups with a grid barrier per half-step beyond (up to 768 inputs; csrc/mlp_fit.h).  A wait of ~2 s for
+ * ceil(d_in / 48) workgroups with a grid barrier per half-step beyond (up to 768 inputs; csrc/mlp_fit.h).  The same hidden
+ * sizes at batch 128, 192 .. 512 and up to 55 inputs run as ONE persistent launch of batch / 64 workgroups: each takes 64 rows of
+ * every minibatch, one gradient exchange and one grid barrier per step, the Adam update replicated (csrc/mlp_fit_team.h;
+ * MJX_FIT_TEAM=0: per-step launches).  A wait of ~2 s for
  * another workgroup poisons epoch_loss_out with NaN instead of hanging.  The launch uses per-host-thread scratch (moment pairs,
  * the uncached exchange block): fits issued by one host thread must be stream-ordered with respect to each other. */
 int mjx_mlp_fit_adam(const float* feat, const float* y, int64_t N, int d_in, const int* hidden, int n_hidden,
                      float* params, float* m, float* v, int64_t step0, const int32_t* perm, int epochs, int batch,
                      float lr, float wd, double* epoch_loss_out, void* stream);
 /* What would serve such a fit, from the same table and the same switches (MJX_MLP_FIT_LAUNCHES, MJX_FIT_WIDE, MJX_FIT_REGMOM,
- * MJX_FIT_ONEPASS, read per call): out6 = {kind (0 per-step launches, 1 one workgroup in two halves, 2 one workgroup in one pass,
- * 3 several workgroups), NF1, REGMOM, workgroups, bytes of dynamic LDS, scratch site}.  Arithmetic only: no device work and no
+ * MJX_FIT_ONEPASS, MJX_FIT_TEAM, read per call): out6 = {kind (0 per-step launches, 1 one workgroup in two halves, 2 one workgroup
+ * in one pass, 3 several workgroups by feature slices, 4 a team of batch / 64 workgroups), NF1, REGMOM, workgroups, bytes of dynamic
+ * LDS, scratch site}.  Arithmetic only: no device work and no
  * runtime call (tests/test_aux_routes_cpu.py). */
 int mjx_mlp_fit_route(int d_in, const int* hidden, int n_hidden, int batch, int64_t N, int epochs, int32_t* out6);
 

@@ -259,8 +259,14 @@ class MLPBaseline:
         same permutations (the LAST rank's draw from NumPy's global stream -- it sampled the batch's last episodes, so under the
         samplers' per-episode seeding its stream stands where a single process's would; every rank draws, so the streams advance
         alike).  The
-        trainer is one workgroup whatever the batch size: running it redundantly costs no wall time over running it once and
-        broadcasting, and the ranks' baselines stay bit-identical -- equal to a one-rank fit on the rank-ordered paths."""
+        trainer is one launch of a few workgroups whatever the number of rows: running it redundantly costs no wall time over
+        running it once and broadcasting, and the ranks' baselines stay bit-identical -- equal to a one-rank fit on the
+        rank-ordered paths.
+
+        batch_size 64 runs on the one-workgroup trainers (csrc/mlp_fit.h); batch_size 128, 192 .. 512 -- the model-based driver's
+        256 -- on the team trainer (csrc/mlp_fit_team.h): batch_size / 64 workgroups share every step, still one launch per fit.
+        Nothing here depends on the batch size: the permutations are drawn per epoch over all rows, and every rank launches
+        the same team.  Other batch sizes, and MJX_FIT_TEAM=0, run per-step launches."""
         self._settle()
         if paths:
             blk = DeviceBlock(paths, self.inp)

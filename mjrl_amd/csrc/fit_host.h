@@ -45,17 +45,26 @@ inline GramRoute gram_route(int F, int n, int64_t N, bool no_mfma) {
 // least one step and one epoch; every other shape, and every shape no trainer takes, runs the launch route.  HALVES: one workgroup, a step as
 // two 32-sample halves, while the layout of d_in inputs fits LDS; ONEPASS: one workgroup, one pass over the 64 rows, up to 23 inputs,
 // register-resident moments (REGMOM) only; WIDE: feature slices of MLPFIT_FS on up to MLPFIT_GMAX workgroups of the two-halves trainer.
-enum { MLPFIT_LAUNCHES, MLPFIT_HALVES, MLPFIT_ONEPASS, MLPFIT_WIDE };
+// TEAM (mlp_fit_team.h): the same shape at minibatches of 128, 192 .. 512 rows, batch / 64 workgroups a step, while the two-halves layout
+// of d_in inputs fits LDS, register-resident moments only.
+enum { MLPFIT_LAUNCHES, MLPFIT_HALVES, MLPFIT_ONEPASS, MLPFIT_WIDE, MLPFIT_TEAM };
 constexpr int MLPFIT_FS = 48, MLPFIT_GMAX = 16;
-// the four switches, read per call: launch route for all / for the wide shapes, moments through L2 (so no one-pass trainer), two halves for all
-struct MlpFitSwitches { bool launches, wide, regmom, onepass; };
+// the five switches, read per call: launch route for all / for the wide shapes, moments through L2 (so no one-pass and no team trainer), two
+// halves for all, launch route for the larger minibatches
+struct MlpFitSwitches { bool launches, wide, regmom, onepass, team; };
 inline MlpFitSwitches mlp_fit_switches() {
-  return {env_flag("MJX_MLP_FIT_LAUNCHES", false), env_flag("MJX_FIT_WIDE", true), env_flag("MJX_FIT_REGMOM", true), env_flag("MJX_FIT_ONEPASS", true)};
+  return {env_flag("MJX_MLP_FIT_LAUNCHES", false), env_flag("MJX_FIT_WIDE", true), env_flag("MJX_FIT_REGMOM", true), env_flag("MJX_FIT_ONEPASS", true),
+          env_flag("MJX_FIT_TEAM", true)};
 }
 struct MlpFitRoute { int kind = MLPFIT_LAUNCHES, nf1 = 0, regmom = 0, G = 0; size_t bytes = 0; int site = SITE_MLP_FIT_LAUNCHES; };
 inline MlpFitRoute mlp_fit_route(int d_in, const int* hidden, int n_hidden, int batch, int64_t N, int epochs, const MlpFitSwitches& sw) {
-  if (sw.launches || n_hidden != 2 || hidden[0] != 128 || hidden[1] != 128 || batch != 64 || N / batch - 1 <= 0 || epochs <= 0) return {};
+  if (sw.launches || n_hidden != 2 || hidden[0] != 128 || hidden[1] != 128 || N / batch - 1 <= 0 || epochs <= 0) return {};
   const int nf1 = d_in <= 31 ? 1 : 2, G = (d_in + MLPFIT_FS - 1) / MLPFIT_FS;
+  if (batch != 64) {
+    if (batch % 64 || batch < 128 || batch > 64 * MLPFIT_TEAM_GMAX || d_in > 63 || !sw.regmom || !sw.team) return {};
+    const size_t bytes = MlpFitLayout<128>(d_in, nf1 == 2).bytes();
+    return bytes <= LDS_MAX ? MlpFitRoute{MLPFIT_TEAM, nf1, 1, batch / 64, bytes, SITE_MLP_FIT_TEAM} : MlpFitRoute{};
+  }
   const size_t halves = MlpFitLayout<128>(d_in, nf1 == 2).bytes(), onepass = MlpFit1pLayout<128>(d_in).bytes();
   if (d_in <= 63 && halves <= LDS_MAX) {
     if (d_in <= 23 && sw.regmom && sw.onepass && onepass <= LDS_MAX) return {MLPFIT_ONEPASS, nf1, 1, 1, onepass, SITE_MLP_FIT};
@@ -64,12 +73,14 @@ inline MlpFitRoute mlp_fit_route(int d_in, const int* hidden, int n_hidden, int 
   if (sw.wide && d_in > 48 && G <= MLPFIT_GMAX) return {MLPFIT_WIDE, 2, sw.regmom, G, MlpFitLayout<128>(MLPFIT_FS, true).bytes(), SITE_MLP_FIT_WIDE};
   return {};
 }
-// the one table of the seven trainer instances, in the order they have in the code object: [REGMOM][NF1 - 1], the one-pass trainer, [REGMOM]
+// the one table of the nine trainer instances, in the order they have in the code object: [REGMOM][NF1 - 1], the one-pass trainer, [REGMOM],
+// the team trainer's [NF1 - 1]
 typedef void (*MlpFitKernel)(MlpFitArgs);
 inline MlpFitKernel mlp_fit_kernel(const MlpFitRoute& r) {
   static const MlpFitKernel halves[2][2] = {{k_mlp_fit<128, 1, false>, k_mlp_fit<128, 2, false>}, {k_mlp_fit<128, 1, true>, k_mlp_fit<128, 2, true>}};
   static const MlpFitKernel onepass = k_mlp_fit1p<128>, wide[2] = {k_mlp_fit<128, 2, false, true>, k_mlp_fit<128, 2, true, true>};
-  return r.kind == MLPFIT_ONEPASS ? onepass : r.kind == MLPFIT_WIDE ? wide[r.regmom] : halves[r.regmom][r.nf1 - 1];
+  static const MlpFitKernel team[2] = {k_mlp_fit_team<1>, k_mlp_fit_team<2>};
+  return r.kind == MLPFIT_ONEPASS ? onepass : r.kind == MLPFIT_WIDE ? wide[r.regmom] : r.kind == MLPFIT_TEAM ? team[r.nf1 - 1] : halves[r.regmom][r.nf1 - 1];
 }
 
 // ---- policy minibatch fit (policy_fit.h): two layers of H = 64 or 32, minibatches of 8 .. 64 rows in fours, every step in ONE launch; H = 0: none

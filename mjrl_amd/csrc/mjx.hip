@@ -28,6 +28,7 @@
 #include "launch_state.h"
 #include "layerwise.h"
 #include "mlp_fit.h"
+#include "mlp_fit_team.h"
 #include "path_reward.h"
 #include "plan.h"
 #include "plan_wide.h"
@@ -65,7 +66,7 @@ int lds_limit(const void* kern, size_t bytes) {
   if (e) return fail(e, "dynamic LDS limit of %zu bytes: %s", bytes, hipGetErrorString((hipError_t)e));
   return MJX_OK;
 }
-enum ScratchSite { SITE_GRAM, SITE_MLP_PREDICT, SITE_MLP_FIT, SITE_MLP_FIT_WIDE, SITE_MLP_FIT_LAUNCHES, SITE_DYN_FIT, SITE_SUM_STATS, SITE_PLAN_ROLLOUT, SITE_PLAN_SCORE, SITE_DYN_FIT_ENS, SITE_PATH_REWARDS, SITE_POLICY_ROLLOUT, SITE_ROLLOUT_DISAGREE };
+enum ScratchSite { SITE_GRAM, SITE_MLP_PREDICT, SITE_MLP_FIT, SITE_MLP_FIT_WIDE, SITE_MLP_FIT_LAUNCHES, SITE_DYN_FIT, SITE_SUM_STATS, SITE_PLAN_ROLLOUT, SITE_PLAN_SCORE, SITE_DYN_FIT_ENS, SITE_PATH_REWARDS, SITE_POLICY_ROLLOUT, SITE_ROLLOUT_DISAGREE, SITE_MLP_FIT_TEAM };
 template <class T>
 int dev_scratch(ScratchSite site, void* stream, size_t bytes, T** out) {
   HIPCHK(mjx::scratch(site, (hipStream_t)stream, bytes, (void**)out));
@@ -383,7 +384,7 @@ int mjx_mlp_fit_adam(const float* feat, const float* y, int64_t N, int d_in, con
   MlpRegressor net; net.init(d_in, hidden, n_hidden);
   const MlpFitRoute r = mlp_fit_route(d_in, hidden, n_hidden, batch, N, epochs, mlp_fit_switches());
   if (r.kind != MLPFIT_LAUNCHES) {
-    const bool wide = r.kind == MLPFIT_WIDE;
+    const bool wide = r.kind == MLPFIT_WIDE, team = r.kind == MLPFIT_TEAM;
     float* mvws = nullptr;
     if (int rc = dev_scratch((ScratchSite)r.site, stream, (size_t)r.G * net.P * 2 * sizeof(float), &mvws)) return rc;
     MlpFitArgs a{feat, y, perm, N, d_in, epochs, N / batch - 1, params, m, v, mvws, step0, lr, wd, epoch_loss_out};
@@ -398,12 +399,21 @@ int mjx_mlp_fit_adam(const float* feat, const float* y, int64_t N, int d_in, con
       a.xch = (float*)xch; a.bar = (unsigned*)(xch + xbytes); a.G = r.G; a.FS = MLPFIT_FS;
       { const char* f = getenv("MJX_FIT_FAULT"); a.fault = (f && !strcmp(f, "straggler")) ? 1 : 0; }      // (tests/test_gpu_lifecycle.py)
     }
+    if (team) {
+      // the team trainer's exchange block (every workgroup's partial gradients, two parities) and its arrival counter: uncached
+      // like the wide trainer's, a block of its own per thread and device, never freed
+      static thread_local PerDevice<char*> team_xch_of;
+      char*& xch = team_xch_of.here();
+      if (!xch) HIPCHK(hipExtMallocWithFlags((void**)&xch, MLPFIT_TEAM_XBYTES + 256, hipDeviceMallocUncached));
+      HIPCHK(hipMemsetAsync(xch + MLPFIT_TEAM_XBYTES, 0, 256, st));           // the counter and the give-up word behind it
+      a.xch = (float*)xch; a.bar = (unsigned*)(xch + MLPFIT_TEAM_XBYTES); a.G = r.G; a.batch = batch;
+    }
     const MlpFitKernel k = mlp_fit_kernel(r);
     if (int rc = lds_limit((const void*)k, r.bytes)) return rc;
     hipLaunchKernelGGL(k, dim3(r.G), dim3(256), r.bytes, st, a);
     // a barrier wait that timed out (a workgroup without a CU) is recorded in a word of its own; this turns it into NaN epoch
     // losses AFTER every workgroup has left -- the last writer of epoch_loss no longer decides
-    if (wide) hipLaunchKernelGGL(k_mlp_fit_verdict, dim3(1), dim3(64), 0, st, (const unsigned*)a.bar + 1, epoch_loss_out, epochs);
+    if (wide || team) hipLaunchKernelGGL(k_mlp_fit_verdict, dim3(1), dim3(64), 0, st, (const unsigned*)a.bar + 1, epoch_loss_out, epochs);
     HIPCHK(hipGetLastError());
     return MJX_OK;
   }

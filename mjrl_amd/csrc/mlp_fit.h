@@ -74,7 +74,7 @@ struct MlpFitArgs {
   const int32_t* perm;     // epochs * N row indices
   int64_t N;
   int d_in, epochs;
-  int64_t steps;           // minibatch steps per epoch = N / 64 - 1
+  int64_t steps;           // minibatch steps per epoch = N / batch - 1
   float* params;           // flat [W1 (H x d_in), b1, W2 (H x H), b2, W3 (H), b3], updated in place
   float* m;                // Adam first moment  (same layout)
   float* v;                // Adam second moment
@@ -87,6 +87,8 @@ struct MlpFitArgs {
   unsigned* bar = nullptr; // UNCACHED arrival counter (zero at launch); bar[1]: "a workgroup gave up on a barrier" (k_mlp_fit_verdict)
   int G = 1, FS = 0;       // workgroups; features per workgroup (the last one takes what is left + the bias column)
   int fault = 0;           // tests (MJX_FIT_FAULT=straggler): workgroup 0 starts 2.6 s late -- the others give up on the first barrier
+  // ---- the team trainer (mlp_fit_team.h: k_mlp_fit_team, G = batch / 64 workgroups share a step; xch, bar and G as above)
+  int batch = 64;          // rows of a minibatch
 };
 
 // ---------------------------------------------------------------------------------------------------------------------------
