@@ -1,5 +1,7 @@
-// fit_host.h -- host side of the baseline and minibatch trainers (baseline.h, mlp_fit.h, policy_fit.h): the feature-table cache and the
-// routes of the ridge Gram, the MLP-baseline fit and the policy minibatch fit as plain arithmetic.  Included by mjx.hip after model_host.h.
+// fit_host.h -- host side of the baseline and minibatch trainers (baseline.h, mlp_fit.h, mlp_fit_team.h, dynamics.h, dyn_fit_ens.h, policy_fit.h):
+// the feature-table cache, the routes of the ridge Gram, the MLP-baseline predict and fit and the policy minibatch fit as plain arithmetic, and
+// what acts on a route -- the bodies of the predict and fit entries; mjx.hip checks arguments and forwards.  Included by mjx.hip after model_host.h
+// (DynNet's helpers) and before update_host.h: the policy fit takes the pieces of mjx_ctx it uses as parameters.
 #pragma once
 namespace mjx {
 
@@ -41,6 +43,41 @@ inline GramRoute gram_route(int F, int n, int64_t N, bool no_mfma) {
   return {GRAM_FMA, ranges(4096, (2048 + npairs - 1) / npairs), nbt, npairs, GT, ((size_t)GKS * n + 2 * (size_t)GKS * (GT + 1)) * sizeof(double)};
 }
 
+// ---- MLP-baseline predict (baseline.h): the reference's default value network (128 x 128 ReLU) in one launch of k_mlp_predict128
+// (MJX_MLP_PREDICT_FUSED=0, read per call: A/B); every other shape layer by layer, in chunks of 2^17 rows
+inline bool mlp_predict_route(int d_in, const int* hidden, int n_hidden, const float* params) {
+  return env_flag("MJX_MLP_PREDICT_FUSED", true) && n_hidden == 2 && hidden[0] == 128 && hidden[1] == 128 && d_in <= 64 &&
+         (((uintptr_t)params) & 15) == 0 && mlp_predict_lds_bytes(d_in) <= LDS_MAX;
+}
+inline int mlp_predict(const float* feat, int64_t N, int d_in, const int* hidden, int n_hidden, const float* params, float* out, void* stream) {
+  if (mlp_predict_route(d_in, hidden, n_hidden, params)) {
+    const size_t bytes = mlp_predict_lds_bytes(d_in);
+    if (int rc = lds_limit((const void*)k_mlp_predict128, bytes)) return rc;
+    const int ncu = cu_count();
+    const int64_t ntiles = (N + 31) / 32;
+    const int64_t want = (ntiles + 7) / 8;
+    MlpPredictArgs pa{feat, params, out, N, d_in};
+    hipLaunchKernelGGL(k_mlp_predict128, dim3((unsigned)(want < ncu ? want : ncu)), dim3(512), bytes, (hipStream_t)stream, pa);
+    HIPCHK(hipGetLastError());
+    return MJX_OK;
+  }
+  MlpRegressor net; net.init(d_in, hidden, n_hidden);
+  const int64_t CH = 1 << 17;
+  size_t per_row = 0; for (int i = 0; i < n_hidden; ++i) per_row += hidden[i];
+  // (the activation scratch is per stream: MLPBaseline.fit_async runs its before / after forwards on a side stream while the
+  //  caller's stream may be predicting with another baseline -- one shared block would be written by both at once)
+  float* sc = nullptr;
+  if (int rc = dev_scratch(SITE_MLP_PREDICT, stream, (size_t)CH * (per_row ? per_row : 1) * sizeof(float), &sc)) return rc;
+  std::vector<float*> acts(n_hidden);
+  { float* q = sc; for (int i = 0; i < n_hidden; ++i) { acts[i] = q; q += (size_t)CH * hidden[i]; } }
+  for (int64_t r0 = 0; r0 < N; r0 += CH) {
+    int64_t rows = (N - r0 < CH) ? N - r0 : CH;
+    net.forward(params, feat + r0 * d_in, rows, acts, out + r0, (hipStream_t)stream);
+  }
+  HIPCHK(lw_status());
+  return MJX_OK;
+}
+
 // ---- MLP-baseline fit (mlp_fit.h): persistent trainers for the reference's default baseline shape, 128 x 128 at minibatches of 64 with at
 // least one step and one epoch; every other shape, and every shape no trainer takes, runs the launch route.  HALVES: one workgroup, a step as
 // two 32-sample halves, while the layout of d_in inputs fits LDS; ONEPASS: one workgroup, one pass over the 64 rows, up to 23 inputs,
@@ -49,6 +86,9 @@ inline GramRoute gram_route(int F, int n, int64_t N, bool no_mfma) {
 // of d_in inputs fits LDS, register-resident moments only.
 enum { MLPFIT_LAUNCHES, MLPFIT_HALVES, MLPFIT_ONEPASS, MLPFIT_WIDE, MLPFIT_TEAM };
 constexpr int MLPFIT_FS = 48, MLPFIT_GMAX = 16;
+// the wide trainer's exchange block [2 parities][G][128 units][32 samples]; the larger of it and the team trainer's (mlp_fit_team.h)
+constexpr size_t MLPFIT_WIDE_XBYTES = (size_t)2 * MLPFIT_GMAX * 128 * 32 * sizeof(float);
+constexpr size_t MLPFIT_XBYTES = MLPFIT_WIDE_XBYTES > MLPFIT_TEAM_XBYTES ? MLPFIT_WIDE_XBYTES : MLPFIT_TEAM_XBYTES;
 // the five switches, read per call: launch route for all / for the wide shapes, moments through L2 (so no one-pass and no team trainer), two
 // halves for all, launch route for the larger minibatches
 struct MlpFitSwitches { bool launches, wide, regmom, onepass, team; };
@@ -82,6 +122,99 @@ inline MlpFitKernel mlp_fit_kernel(const MlpFitRoute& r) {
   static const MlpFitKernel team[2] = {k_mlp_fit_team<1>, k_mlp_fit_team<2>};
   return r.kind == MLPFIT_ONEPASS ? onepass : r.kind == MLPFIT_WIDE ? wide[r.regmom] : r.kind == MLPFIT_TEAM ? team[r.nf1 - 1] : halves[r.regmom][r.nf1 - 1];
 }
+// The exchange block of the WIDE and the TEAM trainer and, behind it, the arrival counter and the give-up word: UNCACHED device memory (stores
+// are acknowledged by memory, loads bypass the per-XCD L2s -- the workgroups of one grid sit on different XCDs), allocated once per thread and
+// device, never freed.  The 256 counter bytes are cleared on `st`; the block needs no clearing.  One block serves both trainers: the fits a
+// thread puts on one stream follow each other (two streams of ONE thread would share it, as they shared each trainer's block: MLPBaseline
+// never does that -- one side stream per device).
+struct FitExchange { float* xch = nullptr; unsigned* bar = nullptr; };
+inline int fit_exchange(hipStream_t st, FitExchange& x) {
+  static thread_local PerDevice<char*> block_of;
+  char*& block = block_of.here();
+  if (!block) HIPCHK(hipExtMallocWithFlags((void**)&block, MLPFIT_XBYTES + 256, hipDeviceMallocUncached));
+  HIPCHK(hipMemsetAsync(block + MLPFIT_XBYTES, 0, 256, st));
+  x.xch = (float*)block; x.bar = (unsigned*)(block + MLPFIT_XBYTES);
+  return MJX_OK;
+}
+// kinds 1 .. 4: every step of every epoch in ONE launch of the route's trainer; `a` as mlp_fit filled it
+inline int mlp_fit_persistent(const MlpFitRoute& r, MlpFitArgs a, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  a.G = r.G;
+  if (r.G > 1) {                                                // WIDE and TEAM
+    FitExchange x;
+    if (int rc = fit_exchange(st, x)) return rc;
+    a.xch = x.xch; a.bar = x.bar;
+  }
+  if (r.kind == MLPFIT_WIDE) {
+    a.FS = MLPFIT_FS;
+    const char* f = getenv("MJX_FIT_FAULT"); a.fault = (f && !strcmp(f, "straggler")) ? 1 : 0;      // (tests/test_gpu_lifecycle.py)
+  }
+  const MlpFitKernel k = mlp_fit_kernel(r);
+  if (int rc = lds_limit((const void*)k, r.bytes)) return rc;
+  hipLaunchKernelGGL(k, dim3(r.G), dim3(256), r.bytes, st, a);
+  // a barrier wait that timed out (a workgroup without a CU) is recorded in a word of its own; this turns it into NaN epoch
+  // losses AFTER every workgroup has left -- the last writer of epoch_loss no longer decides
+  if (r.G > 1) hipLaunchKernelGGL(k_mlp_fit_verdict, dim3(1), dim3(64), 0, st, (const unsigned*)a.bar + 1, a.epoch_loss, a.epochs);
+  HIPCHK(hipGetLastError());
+  return MJX_OK;
+}
+// kind 0: ~14 launches per step (gather, forward, MSE head, per layer weight gradient / bias gradient / delta, Adam)
+inline int mlp_fit_launches(MlpRegressor& net, const MlpFitArgs& a, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  const int L = net.nL(), nh = L - 1, bs = a.batch, d_in = a.d_in;
+  size_t hsum = 0; for (int i = 0; i < nh; ++i) hsum += net.sizes[i + 1];
+  // scratch: Xb, yb, yhat, d_out, acts (bs x h_l), deltas (bs x h_l), grads (P)
+  size_t fl = (size_t)bs * d_in + 3 * (size_t)bs + 2 * (size_t)bs * hsum + (size_t)net.P;
+  float* q = nullptr;
+  if (int rc = dev_scratch(SITE_MLP_FIT_LAUNCHES, stream, fl * sizeof(float), &q)) return rc;
+  float* Xb = q; q += (size_t)bs * d_in;
+  float* yb = q; q += bs;
+  float* yhat = q; q += bs;
+  float* dout = q; q += bs;
+  std::vector<float*> acts(nh), dl(nh);
+  for (int i = 0; i < nh; ++i) { acts[i] = q; q += (size_t)bs * net.sizes[i + 1]; }
+  for (int i = 0; i < nh; ++i) { dl[i] = q; q += (size_t)bs * net.sizes[i + 1]; }
+  float* grads = q;
+  int64_t t = a.step0;
+  // the fp32-beta set (vecops.h: ADAM32_*), in 1 - beta and in the corrections too: the arithmetic of the persistent trainers
+  // (mlp_fit.h), self-consistent -- the steps stay within 1e-6 lr of torch's, v itself is 1.3e-5 low (tests/test_gpu_fit_matrix.py)
+  for (int ep = 0; ep < a.epochs; ++ep) {
+    for (int64_t mb = 0; mb < a.steps; ++mb) {
+      hipLaunchKernelGGL(k_gather_rows, dim3((bs * d_in + 255) / 256), dim3(256), 0, st, a.feat, a.y, a.perm + (int64_t)ep * a.N + mb * bs, bs, d_in, Xb, yb);
+      net.forward(a.params, Xb, bs, acts, yhat, st);
+      hipLaunchKernelGGL(k_mse_grad, dim3(1), dim3(256), 0, st, yhat, yb, bs, dout, a.epoch_loss + ep);
+      const float* delta = dout;
+      for (int l = L - 1; l >= 0; --l) {
+        const int ho = net.sizes[l + 1], hi_ = net.sizes[l];
+        const float* in = (l == 0) ? Xb : acts[l - 1];
+        lw_launch_gemm(gemm_wgrad(bs, ho, hi_, delta, in, hi_, grads + net.oW[l]), 1, st);
+        hipLaunchKernelGGL(k_colsum, dim3((ho + 63) / 64, 1), dim3(256), 0, st, delta, (int64_t)bs, ho, (int64_t)ho, grads + net.ob[l]);
+        if (l > 0) {
+          lw_launch_gemm(gemm_delta(bs, ho, hi_, delta, a.params + net.oW[l], false, dl[l - 1], acts[l - 1], EPI_BACK_RELU), 1, st);
+          delta = dl[l - 1];
+        }
+      }
+      const AdamBias bc = adam_bias(ADAM32_B1, ADAM32_B2, ++t);
+      hipLaunchKernelGGL(k_adam, dim3((unsigned)((net.P + 255) / 256)), dim3(256), 0, st, a.params, grads, a.m, a.v, net.P, a.lr, a.wd, ADAM32_C1, ADAM32_B2, ADAM32_C2, ADAM_EPS, bc.bc1, bc.bc2s);
+    }
+  }
+  HIPCHK(lw_status());
+  return MJX_OK;
+}
+// mjx_mlp_fit_adam behind its argument check: the epoch losses cleared, the arguments every route takes, the route
+inline int mlp_fit(const float* feat, const float* y, int64_t N, int d_in, const int* hidden, int n_hidden, float* params, float* m, float* v,
+                   int64_t step0, const int32_t* perm, int epochs, int batch, float lr, float wd, double* epoch_loss_out, void* stream) {
+  HIPCHK(hipMemsetAsync(epoch_loss_out, 0, sizeof(double) * (epochs > 0 ? epochs : 1), (hipStream_t)stream));
+  MlpRegressor net; net.init(d_in, hidden, n_hidden);
+  const MlpFitRoute r = mlp_fit_route(d_in, hidden, n_hidden, batch, N, epochs, mlp_fit_switches());
+  MlpFitArgs a{};
+  a.feat = feat; a.y = y; a.perm = perm; a.N = N; a.d_in = d_in; a.epochs = epochs;
+  a.steps = N / batch - 1;                            // optimize_model.py:24
+  a.params = params; a.m = m; a.v = v; a.step0 = step0; a.lr = lr; a.wd = wd; a.epoch_loss = epoch_loss_out; a.batch = batch;
+  if (r.kind == MLPFIT_LAUNCHES) return mlp_fit_launches(net, a, stream);
+  if (int rc = dev_scratch((ScratchSite)r.site, stream, (size_t)r.G * net.P * 2 * sizeof(float), &a.mv)) return rc;
+  return mlp_fit_persistent(r, a, stream);
+}
 
 // ---- policy minibatch fit (policy_fit.h): two layers of H = 64 or 32, minibatches of 8 .. 64 rows in fours, every step in ONE launch; H = 0: none
 // serves (MJX_NO_POLICY_FIT=1, read per call: no_fit).  PPO with an old network of its own keeps a third parameter image in LDS.
@@ -93,6 +226,153 @@ inline PolicyFitRoute policy_fit_route(int n, int m, const std::vector<int>& hid
   const int H = hidden[0]; const bool old_net = loss == 2 && !old_tracks_new;
   const size_t bytes = 4 * (H == 64 ? PolicyFitLayout<64>(n, m).lds_floats(B, old_net) : PolicyFitLayout<32>(n, m).lds_floats(B, old_net));
   return bytes <= LDS_MAX ? PolicyFitRoute{H, bytes} : PolicyFitRoute{};
+}
+// mjx_policy_minibatch_adam behind its argument check, on the context's device: (n, m, hidden, ident_tr, oS, d) are the context's shape,
+// its identity transform (for a null tr / tr_old), the offset of log_std and the parameter count; `w` is its launch route's workspace
+inline int policy_fit(int n, int m, const std::vector<int>& hidden, const float* ident_tr, int oS, int64_t d, MinibatchWS& w, int loss,
+                      const float* obs, const float* act, const float* adv, const int32_t* idx, int64_t steps, int B, float* theta,
+                      const float* tr, const float* theta_old, const float* tr_old, int old_tracks_new, float* adam_m, float* adam_v,
+                      int64_t step0, float lr, float clip, double* loss_trace, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  const float* trn = tr ? tr : ident_tr;
+  const float* tro = tr_old ? tr_old : ident_tr;
+  const PolicyFitRoute r = policy_fit_route(n, m, hidden, B, loss, old_tracks_new, env_flag("MJX_NO_POLICY_FIT", false));   // (read per call)
+  if (r.H) {
+    PolicyFitArgs a{obs, act, adv, idx, steps, B, n, m, theta, theta_old, trn, tro, loss, old_tracks_new, adam_m, adam_v,
+                    step0, lr, clip, loss_trace, (int)(r.bytes / 4)};
+    void (*k)(PolicyFitArgs) = (r.H == 64) ? k_policy_fit<64> : k_policy_fit<32>;
+    if (int rc = lds_limit((const void*)k, r.bytes)) return rc;
+    hipLaunchKernelGGL(k, dim3(1), dim3(PFIT_THREADS), r.bytes, st, a);
+    HIPCHK(hipGetLastError());
+    return MJX_OK;
+  }
+  if (int rc = w.reserve(B)) return fail(rc, "minibatch workspace allocation failed");
+  const int64_t cnt = (loss == 0) ? (int64_t)oS : d;             // MSE: log_std has no gradient -> untouched (like torch's grad None)
+  const unsigned ggrid = capped_grid(B * (n > m ? n : m), 256, 1024);
+  for (int64_t s = 0; s < steps; ++s) {
+    const bool old_fwd = (loss == 2) && !old_tracks_new;
+    if (int rc = w.grad_step(loss, obs, act, adv, idx + s * B, B, theta, trn, theta_old, tro, old_fwd, clip,
+                             loss_trace ? loss_trace + s : (double*)nullptr, ggrid, st))
+      return fail(MJX_ERR_STATE, "minibatch backward failed (%d)", rc);
+    const AdamBias bc = adam_bias(ADAM_B1D, ADAM_B2D, step0 + s + 1);      // torch's constants, as k_policy_fit takes them (vecops.h)
+    hipLaunchKernelGGL(k_adam, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, theta, w.grad.p, adam_m, adam_v, cnt, lr, 0.f,
+                       ADAM_C1, ADAM_B2, ADAM_C2, ADAM_EPS, bc.bc1, bc.bc2s);
+  }
+  HIPCHK(lw_status());
+  return MJX_OK;
+}
+
+// ---- dynamics fit of one member (dynamics.h) behind mjx_dyn_fit_adam's argument check, steps > 0: prep, then k_dyn_fit, the persistent
+// trainer, where dyn_fit_shape / dyn_fit_persistent (model_host.h) allow, else launches per step
+inline int dyn_fit_impl(const DynNet& net, const float* x, const float* y, int64_t N, const float* in_tr, const float* out_tr, int target_mode,
+                        int act, float* params, float* m, float* v, int64_t step0, const int32_t* idx, int64_t steps, int batch, float lr,
+                        float wd, float* loss_out, void* stream) {
+  const int din = net.din(), dout = net.dout();
+  MJX_DEVICE_ENTRY();
+  hipStream_t st = (hipStream_t)stream;
+  // scratch: normalised inputs + targets (prep), then the launch route's minibatch activations and deltas
+  int wmax = 0; size_t hsum = 0;
+  for (int l = 1; l <= net.nl; ++l) { wmax = net.sz[l] > wmax ? net.sz[l] : wmax; hsum += net.sz[l]; }
+  const size_t prep = (size_t)N * (din + dout), mb = (size_t)batch * (din + dout + hsum + 2 * (size_t)wmax);
+  float* xn = nullptr;
+  if (int rc = dev_scratch(SITE_DYN_FIT, stream, (prep + mb) * sizeof(float), &xn)) return rc;
+  float* tg = xn + (size_t)N * din;
+  launch_dyn_prep(x, y, N, din, dout, in_tr, out_tr, target_mode, xn, tg, st);
+  const float* oaff = target_mode == DYN_TGT_AFFINE ? out_tr : nullptr;
+  const size_t fbytes = dyn_fit_lds_bytes(net, batch);
+  if (dyn_fit_shape(net, batch, env_flag("MJX_DYN_FIT_LAUNCHES", false)) && dyn_fit_persistent(fbytes, static_lds((const void*)k_dyn_fit))) {
+    if (int rc = lds_limit((const void*)k_dyn_fit, fbytes)) return rc;
+    DynFitArgs a{net, xn, tg, idx, steps, batch, params, m, v, step0, lr, wd, act, oaff, loss_out};
+    hipLaunchKernelGGL(k_dyn_fit, dim3(1), dim3(1024), fbytes, st, a);
+    HIPCHK(hipGetLastError());
+    return MJX_OK;
+  }
+  float* q = tg + (size_t)N * dout;
+  std::vector<float*> A(net.nl + 1);
+  for (int l = 0; l <= net.nl; ++l) { A[l] = q; q += (size_t)batch * net.sz[l]; }
+  float* T = q; q += (size_t)batch * dout;
+  float* D[2] = {q, q + (size_t)batch * wmax};
+  auto blocks = [](int64_t e) { return dim3(capped_grid(e, 256, 2048)); };
+  for (int64_t s = 0; s < steps; ++s) {
+    hipLaunchKernelGGL(k_dl_gather, blocks((int64_t)batch * (din + dout)), dim3(256), 0, st, xn, tg, idx + s * batch, batch, din, dout, A[0], T);
+    for (int l = 0; l < net.nl; ++l)
+      hipLaunchKernelGGL(k_dl_fwd, blocks((int64_t)batch * net.sz[l + 1]), dim3(256), 0, st, A[l], batch, net.sz[l], params + net.oW[l],
+                         params + net.ob[l], net.sz[l + 1], A[l + 1], l + 1 < net.nl ? act : -1);
+    hipLaunchKernelGGL(k_dl_loss, dim3(1), dim3(1024), 0, st, A[net.nl], T, batch, dout, oaff, D[0], loss_out + s);
+    int cur = 0;
+    for (int l = net.nl - 1; l >= 0; --l) {
+      const int di = net.sz[l], dj = net.sz[l + 1];
+      if (l > 0)
+        hipLaunchKernelGGL(k_dl_bwd, blocks((int64_t)batch * di), dim3(256), 0, st, D[cur], batch, di, params + net.oW[l], dj, A[l], act, D[cur ^ 1]);
+      hipLaunchKernelGGL(k_dl_adam, blocks((int64_t)di * dj + dj), dim3(256), 0, st, D[cur], A[l], batch, di, dj, params, m, v, net.oW[l],
+                         step0 + s + 1, lr, wd);
+      cur ^= 1;
+    }
+  }
+  HIPCHK(hipGetLastError());
+  return MJX_OK;
+}
+
+// ---- the fit of a whole ensemble (dyn_fit_ens.h).  Route 1 of both ensemble entries: per-member prep into scratch, then one
+// k_dyn_fit_ens<RAG> launch per DFE_CHUNK members
+template <bool RAG>
+inline int dfe_run(const float* x, int64_t x_stride, const float* y, int64_t y_stride, int64_t N, int K, const DynNet& net, const float* in_tr,
+                   const float* out_tr, int target_mode, int act, float* params, float* m, float* v, const int64_t* step0,
+                   const int32_t* idx, int64_t steps, int batch, float lr, float wd, float* loss_out, void* stream) {
+  const int din = net.din(), dout = net.dout();
+  MJX_DEVICE_ENTRY();
+  hipStream_t st = (hipStream_t)stream;
+  const DfeLayout L(net, batch);
+  // scratch, per member: normalised inputs and targets (every member has its own transforms), and the X tile where LDS has no room
+  const size_t xt = L.x_in_lds ? 0 : L.xtile;
+  float* scr = nullptr;
+  if (int rc = dev_scratch(SITE_DYN_FIT_ENS, stream, ((size_t)K * (size_t)N * (din + dout) + 4 + (size_t)K * xt) * sizeof(float), &scr)) return rc;
+  float* xn = scr; float* tg = xn + (size_t)K * N * din;
+  float* xscr = xt ? scr + (((size_t)K * N * (din + dout) + 3) & ~(size_t)3) : nullptr;
+  for (int k = 0; k < K; ++k)
+    launch_dyn_prep(x + k * x_stride, y + k * y_stride, N, din, dout, in_tr + (int64_t)k * 2 * din, out_tr + (int64_t)k * 2 * dout, target_mode,
+                    xn + (size_t)k * N * din, tg + (size_t)k * N * dout, st);
+  if (int rc = lds_limit((const void*)k_dyn_fit_ens<RAG>, L.lds_bytes())) return rc;
+  DynFitEnsArgs a{};
+  a.din = din; a.h1 = net.sz[1]; a.h2 = net.sz[2]; a.dout = dout; a.B = batch; a.act = act;
+  a.P = net.P; a.N = N; a.steps = steps; a.xn = xn; a.tg = tg; a.idx = idx; a.W = params; a.m = m; a.v = v; a.loss = loss_out; a.xscr = xscr;
+  a.lr = lr; a.wd = wd; a.otr = RAG ? out_tr : nullptr;
+  for (int k0 = 0; k0 < K; k0 += DFE_CHUNK) {               // one launch for K <= DFE_CHUNK members
+    const int kn = K - k0 < DFE_CHUNK ? K - k0 : DFE_CHUNK;
+    a.k0 = k0;
+    for (int q = 0; q < kn; ++q) a.step0[q] = step0[k0 + q];
+    hipLaunchKernelGGL(k_dyn_fit_ens<RAG>, dim3((unsigned)kn), dim3(DFE_THREADS), L.lds_bytes(), st, a);
+  }
+  HIPCHK(hipGetLastError());
+  return MJX_OK;
+}
+
+// the body of both ensemble entries, after the sizes are parsed: the argument check, the route (the entry's switch, read per call -- the
+// tests and tools/bench_dyn_fit.py compare the two routes in one process -- and what its shape predicate answered) written to route_out,
+// then route 0, member by member on the routes of dyn_fit_impl (the check above covers every member's), or route 1, dfe_run<RAG>
+template <bool RAG>
+inline int dfe_entry(const float* x, int64_t x_stride, const float* y, int64_t y_stride, int64_t N, int K, const DynNet& net, const float* in_tr,
+                     const float* out_tr, int target_mode, int act, float* params, float* m, float* v, const int64_t* step0, const int32_t* idx,
+                     int64_t steps, int batch, float lr, float wd, float* loss_out, const char* switch_name, bool shape_served, int* route_out,
+                     void* stream) {
+  const int din = net.din(), dout = net.dout();
+  if (!x || !y || !in_tr || !out_tr || !params || !m || !v || !step0 || (steps > 0 && (!idx || !loss_out)) || N <= 0 ||
+      x_stride < 0 || y_stride < 0 || batch <= 0 || batch > N || steps < 0 || !dyn_args_ok(net, K, act, target_mode))
+    return fail(MJX_ERR_ARG, "bad arguments");
+  for (int k = 0; k < K; ++k) if (step0[k] < 0) return fail(MJX_ERR_ARG, "bad arguments");
+  const int route = env_flag(switch_name, true) && shape_served ? 1 : 0;
+  if (route_out) *route_out = route;
+  if (steps == 0) return MJX_OK;
+  if (route == 0) {
+    for (int k = 0; k < K; ++k)
+      if (int rc = dyn_fit_impl(net, x + k * x_stride, y + k * y_stride, N, in_tr + (int64_t)k * 2 * din, out_tr + (int64_t)k * 2 * dout, target_mode,
+                                act, params + k * net.P, m + k * net.P, v + k * net.P, step0[k], idx + (int64_t)k * steps * batch, steps, batch,
+                                lr, wd, loss_out + (int64_t)k * steps, stream))
+        return rc;
+    return MJX_OK;
+  }
+  return dfe_run<RAG>(x, x_stride, y, y_stride, N, K, net, in_tr, out_tr, target_mode, act, params, m, v, step0, idx, steps, batch, lr, wd,
+                      loss_out, stream);
 }
 
 }  // namespace mjx

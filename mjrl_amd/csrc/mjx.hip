@@ -334,36 +334,7 @@ int mjx_bl_predict(int kind, const double* obs, const int32_t* tpos, int64_t N, 
 int mjx_mlp_predict(const float* feat, int64_t N, int d_in, const int* hidden, int n_hidden, const float* params, float* out, void* stream) {
   if (!feat || !params || !out || N < 0 || d_in <= 0 || n_hidden < 0 || (n_hidden && !hidden)) return fail(MJX_ERR_ARG, "bad arguments");
   if (N == 0) return MJX_OK;
-  {
-    // the reference's default value network (128 x 128 ReLU) in one launch: csrc/baseline.h k_mlp_predict128 (MJX_MLP_PREDICT_FUSED=0: A/B)
-    const size_t bytes = mlp_predict_lds_bytes(d_in);
-    if (env_flag("MJX_MLP_PREDICT_FUSED", true) && n_hidden == 2 && hidden[0] == 128 && hidden[1] == 128 && d_in <= 64 &&
-        (((uintptr_t)params) & 15) == 0 && bytes <= LDS_MAX) {
-      if (int rc = lds_limit((const void*)k_mlp_predict128, bytes)) return rc;
-      const int ncu = cu_count();
-      const int64_t ntiles = (N + 31) / 32;
-      const int64_t want = (ntiles + 7) / 8;
-      MlpPredictArgs pa{feat, params, out, N, d_in};
-      hipLaunchKernelGGL(k_mlp_predict128, dim3((unsigned)(want < ncu ? want : ncu)), dim3(512), bytes, (hipStream_t)stream, pa);
-      HIPCHK(hipGetLastError());
-      return MJX_OK;
-    }
-  }
-  MlpRegressor net; net.init(d_in, hidden, n_hidden);
-  const int64_t CH = 1 << 17;
-  size_t per_row = 0; for (int i = 0; i < n_hidden; ++i) per_row += hidden[i];
-  // (the activation scratch is per stream: MLPBaseline.fit_async runs its before / after forwards on a side stream while the
-  //  caller's stream may be predicting with another baseline -- one shared block would be written by both at once)
-  float* sc = nullptr;
-  if (int rc = dev_scratch(SITE_MLP_PREDICT, stream, (size_t)CH * (per_row ? per_row : 1) * sizeof(float), &sc)) return rc;
-  std::vector<float*> acts(n_hidden);
-  { float* q = sc; for (int i = 0; i < n_hidden; ++i) { acts[i] = q; q += (size_t)CH * hidden[i]; } }
-  for (int64_t r0 = 0; r0 < N; r0 += CH) {
-    int64_t rows = (N - r0 < CH) ? N - r0 : CH;
-    net.forward(params, feat + r0 * d_in, rows, acts, out + r0, (hipStream_t)stream);
-  }
-  HIPCHK(lw_status());
-  return MJX_OK;
+  return mlp_predict(feat, N, d_in, hidden, n_hidden, params, out, stream);
 }
 
 int mjx_mlp_fit_route(int d_in, const int* hidden, int n_hidden, int batch, int64_t N, int epochs, int32_t* out6) {
@@ -379,84 +350,7 @@ int mjx_mlp_fit_adam(const float* feat, const float* y, int64_t N, int d_in, con
                      double* epoch_loss_out, void* stream) {
   if (!feat || !y || !params || !m || !v || !perm || !epoch_loss_out || N <= 0 || batch <= 0 || epochs < 0 || n_hidden < 0)
     return fail(MJX_ERR_ARG, "bad arguments");
-  hipStream_t st = (hipStream_t)stream;
-  HIPCHK(hipMemsetAsync(epoch_loss_out, 0, sizeof(double) * (epochs > 0 ? epochs : 1), st));
-  MlpRegressor net; net.init(d_in, hidden, n_hidden);
-  const MlpFitRoute r = mlp_fit_route(d_in, hidden, n_hidden, batch, N, epochs, mlp_fit_switches());
-  if (r.kind != MLPFIT_LAUNCHES) {
-    const bool wide = r.kind == MLPFIT_WIDE, team = r.kind == MLPFIT_TEAM;
-    float* mvws = nullptr;
-    if (int rc = dev_scratch((ScratchSite)r.site, stream, (size_t)r.G * net.P * 2 * sizeof(float), &mvws)) return rc;
-    MlpFitArgs a{feat, y, perm, N, d_in, epochs, N / batch - 1, params, m, v, mvws, step0, lr, wd, epoch_loss_out};
-    if (wide) {
-      // the exchange block and the arrival counter: UNCACHED device memory (stores are acknowledged by memory, loads bypass the
-      // per-XCD L2s -- the workgroups of one grid sit on different XCDs), allocated once per thread and device
-      static thread_local PerDevice<char*> xch_of;
-      char*& xch = xch_of.here();
-      const size_t xbytes = (size_t)2 * MLPFIT_GMAX * 128 * 32 * sizeof(float);
-      if (!xch) HIPCHK(hipExtMallocWithFlags((void**)&xch, xbytes + 256, hipDeviceMallocUncached));
-      HIPCHK(hipMemsetAsync(xch + xbytes, 0, 256, st));                       // the counter (the exchange block needs no clearing)
-      a.xch = (float*)xch; a.bar = (unsigned*)(xch + xbytes); a.G = r.G; a.FS = MLPFIT_FS;
-      { const char* f = getenv("MJX_FIT_FAULT"); a.fault = (f && !strcmp(f, "straggler")) ? 1 : 0; }      // (tests/test_gpu_lifecycle.py)
-    }
-    if (team) {
-      // the team trainer's exchange block (every workgroup's partial gradients, two parities) and its arrival counter: uncached
-      // like the wide trainer's, a block of its own per thread and device, never freed
-      static thread_local PerDevice<char*> team_xch_of;
-      char*& xch = team_xch_of.here();
-      if (!xch) HIPCHK(hipExtMallocWithFlags((void**)&xch, MLPFIT_TEAM_XBYTES + 256, hipDeviceMallocUncached));
-      HIPCHK(hipMemsetAsync(xch + MLPFIT_TEAM_XBYTES, 0, 256, st));           // the counter and the give-up word behind it
-      a.xch = (float*)xch; a.bar = (unsigned*)(xch + MLPFIT_TEAM_XBYTES); a.G = r.G; a.batch = batch;
-    }
-    const MlpFitKernel k = mlp_fit_kernel(r);
-    if (int rc = lds_limit((const void*)k, r.bytes)) return rc;
-    hipLaunchKernelGGL(k, dim3(r.G), dim3(256), r.bytes, st, a);
-    // a barrier wait that timed out (a workgroup without a CU) is recorded in a word of its own; this turns it into NaN epoch
-    // losses AFTER every workgroup has left -- the last writer of epoch_loss no longer decides
-    if (wide || team) hipLaunchKernelGGL(k_mlp_fit_verdict, dim3(1), dim3(64), 0, st, (const unsigned*)a.bar + 1, epoch_loss_out, epochs);
-    HIPCHK(hipGetLastError());
-    return MJX_OK;
-  }
-  const int L = net.nL(), bs = batch;
-  size_t hsum = 0; for (int i = 0; i < n_hidden; ++i) hsum += hidden[i];
-  // scratch: Xb, yb, yhat, d_out, acts (bs x h_l), deltas (bs x h_l), grads (P)
-  size_t fl = (size_t)bs * d_in + 3 * (size_t)bs + 2 * (size_t)bs * hsum + (size_t)net.P;
-  float* q = nullptr;
-  if (int rc = dev_scratch(SITE_MLP_FIT_LAUNCHES, stream, fl * sizeof(float), &q)) return rc;
-  float* Xb = q; q += (size_t)bs * d_in;
-  float* yb = q; q += bs;
-  float* yhat = q; q += bs;
-  float* dout = q; q += bs;
-  std::vector<float*> acts(n_hidden), dl(n_hidden);
-  for (int i = 0; i < n_hidden; ++i) { acts[i] = q; q += (size_t)bs * hidden[i]; }
-  for (int i = 0; i < n_hidden; ++i) { dl[i] = q; q += (size_t)bs * hidden[i]; }
-  float* grads = q;
-  const int64_t steps = N / bs - 1;                 // optimize_model.py:24
-  int64_t t = step0;
-  // the fp32-beta set (vecops.h: ADAM32_*), in 1 - beta and in the corrections too: the arithmetic of the persistent trainers
-  // (mlp_fit.h), self-consistent -- the steps stay within 1e-6 lr of torch's, v itself is 1.3e-5 low (tests/test_gpu_fit_matrix.py)
-  for (int ep = 0; ep < epochs; ++ep) {
-    for (int64_t mb = 0; mb < steps; ++mb) {
-      hipLaunchKernelGGL(k_gather_rows, dim3((bs * d_in + 255) / 256), dim3(256), 0, st, feat, y, perm + (int64_t)ep * N + mb * bs, bs, d_in, Xb, yb);
-      net.forward(params, Xb, bs, acts, yhat, st);
-      hipLaunchKernelGGL(k_mse_grad, dim3(1), dim3(256), 0, st, yhat, yb, bs, dout, epoch_loss_out + ep);
-      const float* delta = dout;
-      for (int l = L - 1; l >= 0; --l) {
-        const int ho = net.sizes[l + 1], hi_ = net.sizes[l];
-        const float* in = (l == 0) ? Xb : acts[l - 1];
-        lw_launch_gemm(gemm_wgrad(bs, ho, hi_, delta, in, hi_, grads + net.oW[l]), 1, st);
-        hipLaunchKernelGGL(k_colsum, dim3((ho + 63) / 64, 1), dim3(256), 0, st, delta, (int64_t)bs, ho, (int64_t)ho, grads + net.ob[l]);
-        if (l > 0) {
-          lw_launch_gemm(gemm_delta(bs, ho, hi_, delta, params + net.oW[l], false, dl[l - 1], acts[l - 1], EPI_BACK_RELU), 1, st);
-          delta = dl[l - 1];
-        }
-      }
-      const AdamBias bc = adam_bias(ADAM32_B1, ADAM32_B2, ++t);
-      hipLaunchKernelGGL(k_adam, dim3((unsigned)((net.P + 255) / 256)), dim3(256), 0, st, params, grads, m, v, net.P, lr, wd, ADAM32_C1, ADAM32_B2, ADAM32_C2, ADAM_EPS, bc.bc1, bc.bc2s);
-    }
-  }
-  HIPCHK(lw_status());
-  return MJX_OK;
+  return mlp_fit(feat, y, N, d_in, hidden, n_hidden, params, m, v, step0, perm, epochs, batch, lr, wd, epoch_loss_out, stream);
 }
 
 // ---------------------------------------------------------------------------- model-based NPG (csrc/dynamics.h; host side: csrc/model_host.h)
@@ -629,120 +523,14 @@ int mjx_dyn_fit_adam(const float* x, const float* y, int64_t N, const int* sizes
                      int batch, float lr, float wd, float* loss_out, void* stream) {
   DynNet net;
   if (int rc = dyn_net(sizes, n_sizes, net)) return rc;
-  const int din = net.din(), dout = net.dout();
   if (!x || !y || !in_tr || !out_tr || !params || !m || !v || (steps > 0 && (!idx || !loss_out)) || N <= 0 || batch <= 0 || batch > N ||
       steps < 0 || step0 < 0 || !dyn_args_ok(net, 1, act, target_mode))
     return fail(MJX_ERR_ARG, "bad arguments");
   if (steps == 0) return MJX_OK;
-  MJX_DEVICE_ENTRY();
-  hipStream_t st = (hipStream_t)stream;
-  // scratch: normalised inputs + targets (prep), then the launch route's minibatch activations and deltas
-  int wmax = 0; size_t hsum = 0;
-  for (int l = 1; l <= net.nl; ++l) { wmax = net.sz[l] > wmax ? net.sz[l] : wmax; hsum += net.sz[l]; }
-  const size_t prep = (size_t)N * (din + dout), mb = (size_t)batch * (din + dout + hsum + 2 * (size_t)wmax);
-  float* xn = nullptr;
-  if (int rc = dev_scratch(SITE_DYN_FIT, stream, (prep + mb) * sizeof(float), &xn)) return rc;
-  float* tg = xn + (size_t)N * din;
-  launch_dyn_prep(x, y, N, din, dout, in_tr, out_tr, target_mode, xn, tg, st);
-  const float* oaff = target_mode == DYN_TGT_AFFINE ? out_tr : nullptr;
-  const size_t fbytes = dyn_fit_lds_bytes(net, batch);
-  if (dyn_fit_shape(net, batch, env_flag("MJX_DYN_FIT_LAUNCHES", false)) && dyn_fit_persistent(fbytes, static_lds((const void*)k_dyn_fit))) {
-    if (int rc = lds_limit((const void*)k_dyn_fit, fbytes)) return rc;
-    DynFitArgs a{net, xn, tg, idx, steps, batch, params, m, v, step0, lr, wd, act, oaff, loss_out};
-    hipLaunchKernelGGL(k_dyn_fit, dim3(1), dim3(1024), fbytes, st, a);
-    HIPCHK(hipGetLastError());
-    return MJX_OK;
-  }
-  float* q = tg + (size_t)N * dout;
-  std::vector<float*> A(net.nl + 1);
-  for (int l = 0; l <= net.nl; ++l) { A[l] = q; q += (size_t)batch * net.sz[l]; }
-  float* T = q; q += (size_t)batch * dout;
-  float* D[2] = {q, q + (size_t)batch * wmax};
-  auto blocks = [](int64_t e) { return dim3(capped_grid(e, 256, 2048)); };
-  for (int64_t s = 0; s < steps; ++s) {
-    hipLaunchKernelGGL(k_dl_gather, blocks((int64_t)batch * (din + dout)), dim3(256), 0, st, xn, tg, idx + s * batch, batch, din, dout, A[0], T);
-    for (int l = 0; l < net.nl; ++l)
-      hipLaunchKernelGGL(k_dl_fwd, blocks((int64_t)batch * net.sz[l + 1]), dim3(256), 0, st, A[l], batch, net.sz[l], params + net.oW[l],
-                         params + net.ob[l], net.sz[l + 1], A[l + 1], l + 1 < net.nl ? act : -1);
-    hipLaunchKernelGGL(k_dl_loss, dim3(1), dim3(1024), 0, st, A[net.nl], T, batch, dout, oaff, D[0], loss_out + s);
-    int cur = 0;
-    for (int l = net.nl - 1; l >= 0; --l) {
-      const int di = net.sz[l], dj = net.sz[l + 1];
-      if (l > 0)
-        hipLaunchKernelGGL(k_dl_bwd, blocks((int64_t)batch * di), dim3(256), 0, st, D[cur], batch, di, params + net.oW[l], dj, A[l], act, D[cur ^ 1]);
-      hipLaunchKernelGGL(k_dl_adam, blocks((int64_t)di * dj + dj), dim3(256), 0, st, D[cur], A[l], batch, di, dj, params, m, v, net.oW[l],
-                         step0 + s + 1, lr, wd);
-      cur ^= 1;
-    }
-  }
-  HIPCHK(hipGetLastError());
-  return MJX_OK;
+  return dyn_fit_impl(net, x, y, N, in_tr, out_tr, target_mode, act, params, m, v, step0, idx, steps, batch, lr, wd, loss_out, stream);
 }
 
-// route 1 of both ensemble entries: per-member prep into scratch, then one k_dyn_fit_ens<RAG> launch per DFE_CHUNK members
-extern "C++" {
-template <bool RAG>
-static int dfe_run(const float* x, int64_t x_stride, const float* y, int64_t y_stride, int64_t N, int K, const DynNet& net, const float* in_tr,
-                   const float* out_tr, int target_mode, int act, float* params, float* m, float* v, const int64_t* step0,
-                   const int32_t* idx, int64_t steps, int batch, float lr, float wd, float* loss_out, void* stream) {
-  const int din = net.din(), dout = net.dout();
-  MJX_DEVICE_ENTRY();
-  hipStream_t st = (hipStream_t)stream;
-  const DfeLayout L(net, batch);
-  // scratch, per member: normalised inputs and targets (every member has its own transforms), and the X tile where LDS has no room
-  const size_t xt = L.x_in_lds ? 0 : L.xtile;
-  float* scr = nullptr;
-  if (int rc = dev_scratch(SITE_DYN_FIT_ENS, stream, ((size_t)K * (size_t)N * (din + dout) + 4 + (size_t)K * xt) * sizeof(float), &scr)) return rc;
-  float* xn = scr; float* tg = xn + (size_t)K * N * din;
-  float* xscr = xt ? scr + (((size_t)K * N * (din + dout) + 3) & ~(size_t)3) : nullptr;
-  for (int k = 0; k < K; ++k)
-    launch_dyn_prep(x + k * x_stride, y + k * y_stride, N, din, dout, in_tr + (int64_t)k * 2 * din, out_tr + (int64_t)k * 2 * dout, target_mode,
-                    xn + (size_t)k * N * din, tg + (size_t)k * N * dout, st);
-  if (int rc = lds_limit((const void*)k_dyn_fit_ens<RAG>, L.lds_bytes())) return rc;
-  DynFitEnsArgs a{};
-  a.din = din; a.h1 = net.sz[1]; a.h2 = net.sz[2]; a.dout = dout; a.B = batch; a.act = act;
-  a.P = net.P; a.N = N; a.steps = steps; a.xn = xn; a.tg = tg; a.idx = idx; a.W = params; a.m = m; a.v = v; a.loss = loss_out; a.xscr = xscr;
-  a.lr = lr; a.wd = wd; a.otr = RAG ? out_tr : nullptr;
-  for (int k0 = 0; k0 < K; k0 += DFE_CHUNK) {               // one launch for K <= DFE_CHUNK members
-    const int kn = K - k0 < DFE_CHUNK ? K - k0 : DFE_CHUNK;
-    a.k0 = k0;
-    for (int q = 0; q < kn; ++q) a.step0[q] = step0[k0 + q];
-    hipLaunchKernelGGL(k_dyn_fit_ens<RAG>, dim3((unsigned)kn), dim3(DFE_THREADS), L.lds_bytes(), st, a);
-  }
-  HIPCHK(hipGetLastError());
-  return MJX_OK;
-}
-
-// the body of both ensemble entries, after the sizes are parsed: the argument check, the route (the entry's switch, read per call -- the
-// tests and tools/bench_dyn_fit.py compare the two routes in one process -- and what its shape predicate answered) written to route_out,
-// then route 0, member by member on the routes of mjx_dyn_fit_adam, or route 1, dfe_run<RAG>
-template <bool RAG>
-static int dfe_entry(const float* x, int64_t x_stride, const float* y, int64_t y_stride, int64_t N, int K, const int* sizes, int n_sizes,
-                     const DynNet& net, const float* in_tr, const float* out_tr, int target_mode, int act, float* params, float* m, float* v,
-                     const int64_t* step0, const int32_t* idx, int64_t steps, int batch, float lr, float wd, float* loss_out,
-                     const char* switch_name, bool shape_served, int* route_out, void* stream) {
-  const int din = net.din(), dout = net.dout();
-  if (!x || !y || !in_tr || !out_tr || !params || !m || !v || !step0 || (steps > 0 && (!idx || !loss_out)) || N <= 0 ||
-      x_stride < 0 || y_stride < 0 || batch <= 0 || batch > N || steps < 0 || !dyn_args_ok(net, K, act, target_mode))
-    return fail(MJX_ERR_ARG, "bad arguments");
-  for (int k = 0; k < K; ++k) if (step0[k] < 0) return fail(MJX_ERR_ARG, "bad arguments");
-  const int route = env_flag(switch_name, true) && shape_served ? 1 : 0;
-  if (route_out) *route_out = route;
-  if (steps == 0) return MJX_OK;
-  if (route == 0) {
-    for (int k = 0; k < K; ++k)
-      if (int rc = mjx_dyn_fit_adam(x + k * x_stride, y + k * y_stride, N, sizes, n_sizes, in_tr + (int64_t)k * 2 * din, out_tr + (int64_t)k * 2 * dout,
-                                    target_mode, act, params + k * net.P, m + k * net.P, v + k * net.P, step0[k],
-                                    idx + (int64_t)k * steps * batch, steps, batch, lr, wd, loss_out + (int64_t)k * steps, stream))
-        return rc;
-    return MJX_OK;
-  }
-  return dfe_run<RAG>(x, x_stride, y, y_stride, N, K, net, in_tr, out_tr, target_mode, act, params, m, v, step0, idx, steps, batch, lr, wd,
-                      loss_out, stream);
-}
-}  // extern "C++"
-
-// ---- the whole ensemble's fit (csrc/dyn_fit_ens.h)
+// ---- the whole ensemble's fit (csrc/dyn_fit_ens.h; host side: csrc/fit_host.h dfe_entry, as mjx_dyn_fit_adam's is dyn_fit_impl)
 int mjx_dyn_fit_route(const int* sizes, int n_sizes, int batch, int target_mode) {
   DynNet net;
   if (int rc = dyn_net(sizes, n_sizes, net)) return rc;
@@ -756,7 +544,7 @@ int mjx_dyn_fit_ensemble(const float* x, int64_t x_stride, const float* y, int64
                          int* route_out, void* stream) {
   DynNet net;
   if (int rc = dyn_net(sizes, n_sizes, net)) return rc;
-  return dfe_entry<false>(x, x_stride, y, y_stride, N, K, sizes, n_sizes, net, in_tr, out_tr, target_mode, act, params, m, v, step0, idx, steps,
+  return dfe_entry<false>(x, x_stride, y, y_stride, N, K, net, in_tr, out_tr, target_mode, act, params, m, v, step0, idx, steps,
                           batch, lr, wd, loss_out, "MJX_DYN_FIT_ENS", dfe_serves(net, batch, target_mode), route_out, stream);
 }
 
@@ -783,7 +571,7 @@ int mjx_reward_fit_ensemble(const float* x, int64_t x_stride, const float* y, in
                             int* route_out, void* stream) {
   DynNet net;
   if (int rc = dyn_net(sizes, n_sizes, net)) return rc;
-  return dfe_entry<true>(x, x_stride, y, y_stride, N, K, sizes, n_sizes, net, in_tr, out_tr, DYN_TGT_AFFINE, act, params, m, v, step0, idx, steps,
+  return dfe_entry<true>(x, x_stride, y, y_stride, N, K, net, in_tr, out_tr, DYN_TGT_AFFINE, act, params, m, v, step0, idx, steps,
                          batch, lr, wd, loss_out, "MJX_REWARD_FIT_ENS", reward_fit_serves(net, batch), route_out, stream);
 }
 
@@ -1119,36 +907,9 @@ int mjx_policy_minibatch_adam(mjx_ctx* c, int loss, const float* obs, const floa
   if (steps == 0) return MJX_OK;
   if (!obs || !act || !idx || !theta || !adam_m || !adam_v) return fail(MJX_ERR_ARG, "null buffer");
   if (loss == 2 && (!adv || !theta_old)) return fail(MJX_ERR_ARG, "PPO needs advantages and the old parameters");
-  hipStream_t st = (hipStream_t)stream;
   HIPCHK(hipSetDevice(c->device));
-  const float* trn0 = tr ? tr : c->ident_tr;
-  const float* tro0 = tr_old ? tr_old : c->ident_tr;
-  const PolicyFitRoute r = policy_fit_route(c->n, c->m, c->hidden, B, loss, old_tracks_new, env_flag("MJX_NO_POLICY_FIT", false));   // (read per call)
-  if (r.H) {
-    PolicyFitArgs a{obs, act, adv, idx, steps, B, c->n, c->m, theta, theta_old, trn0, tro0, loss, old_tracks_new, adam_m, adam_v,
-                    step0, lr, clip, loss_trace, (int)(r.bytes / 4)};
-    void (*k)(PolicyFitArgs) = (r.H == 64) ? k_policy_fit<64> : k_policy_fit<32>;
-    if (int rc = lds_limit((const void*)k, r.bytes)) return rc;
-    hipLaunchKernelGGL(k, dim3(1), dim3(PFIT_THREADS), r.bytes, st, a);
-    HIPCHK(hipGetLastError());
-    return MJX_OK;
-  }
-  MinibatchWS& w = c->lwmb;
-  if (int rc = w.reserve(B)) return fail(rc, "minibatch workspace allocation failed");
-  const float *trn = trn0, *tro = tro0;
-  const int64_t cnt = (loss == 0) ? (int64_t)c->oS : c->d;       // MSE: log_std has no gradient -> untouched (like torch's grad None)
-  const unsigned ggrid = capped_grid(B * (c->n > c->m ? c->n : c->m), 256, 1024);
-  for (int64_t s = 0; s < steps; ++s) {
-    const bool old_fwd = (loss == 2) && !old_tracks_new;
-    if (int rc = w.grad_step(loss, obs, act, adv, idx + s * B, B, theta, trn, theta_old, tro, old_fwd, clip,
-                             loss_trace ? loss_trace + s : (double*)nullptr, ggrid, st))
-      return fail(MJX_ERR_STATE, "minibatch backward failed (%d)", rc);
-    const AdamBias bc = adam_bias(ADAM_B1D, ADAM_B2D, step0 + s + 1);      // torch's constants, as k_policy_fit takes them (vecops.h)
-    hipLaunchKernelGGL(k_adam, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, theta, w.grad.p, adam_m, adam_v, cnt, lr, 0.f,
-                       ADAM_C1, ADAM_B2, ADAM_C2, ADAM_EPS, bc.bc1, bc.bc2s);
-  }
-  HIPCHK(lw_status());
-  return MJX_OK;
+  return policy_fit(c->n, c->m, c->hidden, c->ident_tr, c->oS, c->d, c->lwmb, loss, obs, act, adv, idx, steps, B, theta, tr, theta_old, tr_old,
+                    old_tracks_new, adam_m, adam_v, step0, lr, clip, loss_trace, stream);
 }
 
 }  // extern "C"

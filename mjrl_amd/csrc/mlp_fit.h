@@ -255,6 +255,27 @@ __global__ void k_mlp_fit_verdict(const unsigned* __restrict__ gave_up, double* 
   for (int e = threadIdx.x; e < (epochs > 0 ? epochs : 1); e += blockDim.x) epoch_loss[e] = (double)__builtin_nanf("");
 }
 
+// The grid barrier of the several-workgroup trainers (k_mlp_fit<.., MULTI>, k_mlp_fit_team), called by thread 0 between two
+// __syncthreads(): one arrival on the uncached counter, then the wait (s_sleep) for all G arrivals of barrier number `phase`.  A
+// wait of ~2 s gives up, once -- this workgroup's later barriers fall through -- and poisons the losses through a word of its own
+// next to the counter (uncached, OR-ed: no other writer can undo it).  The epoch losses alone are not a safe place: workgroup 0 --
+// if IT was the straggler -- passes every abandoned barrier at once later and overwrites the NaNs with finite sums of stale
+// partials.  k_mlp_fit_verdict, launched behind the trainer, turns the word into NaN losses once every workgroup
+// has left.  -> timed_out.  (By value and returned: by reference, two k_mlp_fit<.., MULTI> instances scheduled one move elsewhere.)
+__device__ __forceinline__ bool mlp_fit_grid_barrier(unsigned* bar, int G, unsigned phase, bool timed_out) {
+  __hip_atomic_fetch_add(bar, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  const unsigned want = (unsigned)G * (phase + 1u);
+  const unsigned long long t0 = wall_clock64();                       // 100 MHz
+  while ((int)(__hip_atomic_load(bar, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - want) < 0) {
+    __builtin_amdgcn_s_sleep(1);
+    if (timed_out || wall_clock64() - t0 > 200000000ull) {
+      if (!timed_out) __hip_atomic_fetch_or(bar + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      timed_out = true; break;
+    }
+  }
+  return timed_out;
+}
+
 template <int H, int NF1 = 1, bool REGMOM = false, bool MULTI = false>
 __global__ __launch_bounds__(256, 1) void k_mlp_fit(MlpFitArgs A) {
   static_assert(H == 128, "wave w owns unit tile w: 4 waves x 32 units");
@@ -431,22 +452,7 @@ __global__ __launch_bounds__(256, 1) void k_mlp_fit(MlpFitArgs A) {
           for (int q = 0; q < 4; ++q) xo[q * 64] = f32x4{z1[4 * q], z1[4 * q + 1], z1[4 * q + 2], z1[4 * q + 3]};
           asm volatile("s_waitcnt vmcnt(0)" ::: "memory");            // uncached stores: acknowledged by memory, nothing holds them back
           __syncthreads();
-          if (tid == 0) {
-            __hip_atomic_fetch_add(A.bar, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const unsigned want = (unsigned)A.G * (phase + 1u);
-            const unsigned long long t0 = wall_clock64();             // 100 MHz
-            while ((int)(__hip_atomic_load(A.bar, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - want) < 0) {
-              __builtin_amdgcn_s_sleep(1);
-              if (timed_out || wall_clock64() - t0 > 200000000ull) {                                  // ~2 s: give up (once), poison the losses
-                // ... through a word of its own next to the counter (uncached, OR-ed: no other writer can undo it).  The epoch
-                // losses alone are not a safe place: workgroup 0 -- if IT was the straggler -- passes every abandoned barrier at
-                // once later and overwrites the NaNs with finite sums of stale partials.  k_mlp_fit_verdict, launched
-                // behind this kernel, turns the word into NaN losses once every workgroup has left.
-                if (!timed_out) __hip_atomic_fetch_or(A.bar + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                timed_out = true; break;
-              }
-            }
-          }
+          if (tid == 0) timed_out = mlp_fit_grid_barrier(A.bar, A.G, phase, timed_out);
           __syncthreads();
           const f32x4* xi = (const f32x4*)(A.xch + (size_t)(phase & 1u) * (size_t)A.G * slot) + (size_t)(w * 4) * 64 + lane;
           asm volatile("" : "+v"(xi) :: "memory");                    // (a fresh look at memory every phase: nothing cached in registers)

@@ -364,18 +364,7 @@ __global__ __launch_bounds__(256, 1) __attribute__((target("no-packed-fp32-ops")
       }
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                // uncached stores: acknowledged by memory, nothing holds them back
       __syncthreads();
-      if (tid == 0) {
-        __hip_atomic_fetch_add(A.bar, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const unsigned want = (unsigned)G * (phase + 1u);
-        const unsigned long long t0 = wall_clock64();                 // 100 MHz
-        while ((int)(__hip_atomic_load(A.bar, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - want) < 0) {
-          __builtin_amdgcn_s_sleep(1);
-          if (timed_out || wall_clock64() - t0 > 200000000ull) {      // ~2 s: give up (once) and say so in the word behind the counter
-            if (!timed_out) __hip_atomic_fetch_or(A.bar + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            timed_out = true; break;
-          }
-        }
-      }
+      if (tid == 0) timed_out = mlp_fit_grid_barrier(A.bar, G, phase, timed_out);
       __syncthreads();
       // ---- every workgroup: the sum of all G slots from zero, in workgroup order (its own slot through memory as well: its
       // registers are dead after the publish, the sum needs no second copy) -- the same bits on every workgroup

@@ -16,7 +16,7 @@ def kernels(co):
         m = re.match(r"^[0-9a-f]+ <(.+)>:$", line)
         if m:
             name = m.group(1); body[name] = []
-        elif name and line.strip():
+        elif name and line.strip() and line.strip() != "...":       # ("...": objdump's mark for the zero padding behind the last kernel of the section)
             # "  addr:  insn  // comment" -> insn; branch targets keep their label (<name+0x...> offsets are relative to the function)
             body[name].append(re.sub(r"\s*//.*$", "", re.sub(r"^\s*[0-9a-f]+:\s*", "", line)).strip())
     res = {}
