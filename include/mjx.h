@@ -515,6 +515,23 @@ int mjx_dyn_fit_ensemble(const float* x, int64_t x_stride, const float* y, int64
                          const int* sizes, int n_sizes, const float* in_tr, const float* out_tr, int target_mode, int act,
                          float* params, float* m, float* v, const int64_t* step0, const int32_t* idx, int64_t steps,
                          int batch, float lr, float wd, float* loss_out, int* route_out, void* stream);
+/* The team mjx_dyn_fit_ensemble_team gives each of K members of `sizes` at minibatch `batch`: G = 4 (both hidden widths
+ * multiples of 128) or 2 (both multiples of 64) workgroups that split the hidden units of both layers
+ * (csrc/dyn_fit_ens_team.h), for a shape mjx_dyn_fit_route answers 1 for whose team layout (full H1, own H2 slice, Z3 and the
+ * gathered inputs in LDS) fits 160 KiB and whose team fits the device at a workgroup per CU; 0 = not served: the entry is
+ * mjx_dyn_fit_ensemble; < 0 = bad sizes, batch, K or target mode.  Arithmetic only, except for the cached CU count of the
+ * current device. */
+int mjx_dyn_fit_team_route(const int* sizes, int n_sizes, int batch, int target_mode, int K);
+/* mjx_dyn_fit_ensemble, its arguments exactly, with a team of workgroups per member: *route_out = 2 where the team kernel
+ * ran (at most floor(CUs / G) members per launch).  A shape mjx_dyn_fit_team_route answers 0 for, MJX_DYN_FIT_TEAM=0 or
+ * MJX_DYN_FIT_ENS=0 (read per call): the call IS mjx_dyn_fit_ensemble -- its routing, its bits, its *route_out.  A team
+ * whose workgroups were not all running (a barrier wait of ~2 s) stops writing parameters and moments and the member's
+ * losses come back NaN.  Bad arguments return MJX_ERR_ARG and touch nothing; steps == 0 returns MJX_OK without a launch.
+ * Uses per-host-thread scratch and a per-host-thread uncached exchange block that is never freed. */
+int mjx_dyn_fit_ensemble_team(const float* x, int64_t x_stride, const float* y, int64_t y_stride, int64_t N, int K,
+                              const int* sizes, int n_sizes, const float* in_tr, const float* out_tr, int target_mode, int act,
+                              float* params, float* m, float* v, const int64_t* step0, const int32_t* idx, int64_t steps,
+                              int batch, float lr, float wd, float* loss_out, int* route_out, void* stream);
 /* Which route mjx_reward_fit_ensemble takes for nets of `sizes` at minibatch `batch`: 1 = the ensemble kernel's instance for
  * ragged widths and the affine head (csrc/dyn_fit_ens.h): exactly two hidden layers, each width 1 .. 256, batch <= 64,
  * d_in <= 128, d_out <= 64; 0 = member by member on the routes of mjx_dyn_fit_adam; < 0 = bad sizes or batch <= 0.

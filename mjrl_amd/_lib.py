@@ -109,6 +109,11 @@ PROTOTYPES = {
     "mjx_dyn_fit_ensemble": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int, ctypes.POINTER(c_int), c_int, c_void_p, c_void_p,
                                      c_int, c_int, c_void_p, c_void_p, c_void_p, ctypes.POINTER(c_int64), c_void_p, c_int64, c_int, c_float,
                                      c_float, c_void_p, ctypes.POINTER(c_int), c_void_p]),
+    "mjx_dyn_fit_team_route": (c_int, [ctypes.POINTER(c_int), c_int, c_int, c_int, c_int]),
+    # (mjx_dyn_fit_ensemble's argument list; route 2 = a team of workgroups per member, MJX_DYN_FIT_TEAM=0: mjx_dyn_fit_ensemble itself)
+    "mjx_dyn_fit_ensemble_team": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int, ctypes.POINTER(c_int), c_int, c_void_p, c_void_p,
+                                          c_int, c_int, c_void_p, c_void_p, c_void_p, ctypes.POINTER(c_int64), c_void_p, c_int64, c_int, c_float,
+                                          c_float, c_void_p, ctypes.POINTER(c_int), c_void_p]),
     "mjx_reward_fit_route": (c_int, [ctypes.POINTER(c_int), c_int, c_int]),
     "mjx_dyn_fit_ens_layout": (c_int, [ctypes.POINTER(c_int), c_int, c_int, ctypes.POINTER(c_int64)]),
     "mjx_reward_fit_ensemble": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int, ctypes.POINTER(c_int), c_int, c_void_p, c_void_p,

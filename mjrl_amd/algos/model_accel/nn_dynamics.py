@@ -362,7 +362,7 @@ def _write_back(nets, opts, P, m, v, steps, losses, num_steps, ran):
 
 def _fit_members(nets, opts, make_x, Y, target_mode, batch_size, epochs, max_steps, entry, draws=None):
     """THE fit body: K nets (one shape, activation and optimiser setting) on N rows through ``entry`` -- ``mjx_dyn_fit_adam`` (K = 1),
-    ``mjx_dyn_fit_ensemble`` or ``mjx_reward_fit_ensemble``.  The index draws (``draws``, or member by member from NumPy's global
+    ``mjx_dyn_fit_ensemble``, ``mjx_dyn_fit_ensemble_team`` or ``mjx_reward_fit_ensemble``.  The index draws (``draws``, or member by member from NumPy's global
     stream here), then ``make_x(dev)`` -> (X on the device, its member stride), then the members' parameters, transforms and
     optimiser state stacked, the call, the write-back.  -> K epoch-loss lists."""
     dev = _device()
@@ -421,14 +421,27 @@ def _same_fit(models):
     return True
 
 
-def fit_ensemble(models, s, a, sp, fit_mb_size, fit_epochs, max_steps=1e4, set_transformations=True, _draws=None):
+def team_fit_shape(sizes):
+    """whether :func:`fit_ensemble` hands nets of these layer sizes to ``mjx_dyn_fit_ensemble_team`` (a team of workgroups per
+    member, csrc/dyn_fit_ens_team.h) when its caller asks for it: two hidden layers, both widths 128 or 256 -- the teams of four
+    of ``mjx_dyn_fit_team_route``.  Plain Python, no library call; narrower on purpose than what the entry serves: a team of two
+    (widths that are multiples of 64 only) measured slower than the one-workgroup kernel at 64 x 64 ("Team ensemble
+    fit") and is not measured at 192, so those shapes keep their call.  Whatever else keeps the team kernel from serving a call
+    (the minibatch, the input and output widths, ``MJX_DYN_FIT_TEAM=0``) the entry settles itself, by being
+    ``mjx_dyn_fit_ensemble``."""
+    return len(sizes) == 4 and all(h in (128, 256) for h in sizes[1:3])
+
+
+def fit_ensemble(models, s, a, sp, fit_mb_size, fit_epochs, max_steps=1e4, set_transformations=True, _draws=None, team=False):
     """``[mdl.fit_dynamics(s, a, sp, fit_mb_size, fit_epochs, max_steps, set_transformations) for mdl in models]`` (the
     driver's loop, run_model_accel_npg.py:168-177) with every member's Adam chain in ONE launch (``mjx_dyn_fit_ensemble``:
     a workgroup per member; shapes it does not serve run member by member inside the same call).  Per member the same
     transform expressions, the same draws from NumPy's global stream in the same order, the same optimiser state carried
     and advanced, the parameters written back and ``_generation`` bumped.  -> a list of K epoch-loss lists.  Members that
     differ in layer sizes, activation, ``residual`` or optimiser settings run the plain loop.  (_draws: the index draws made
-    ahead by :func:`fit_world_models`.)"""
+    ahead by :func:`fit_world_models`.)  ``team``: where :func:`team_fit_shape` says so, ``mjx_dyn_fit_ensemble_team`` with the
+    same arguments -- several workgroups share each member's step; other bits than the one-workgroup kernel's, the same
+    arithmetic against fp64."""
     models = list(models)
     if not models:
         return []
@@ -446,7 +459,8 @@ def fit_ensemble(models, s, a, sp, fit_mb_size, fit_epochs, max_steps=1e4, set_t
         for mdl, net in zip(models, nets):       # on each member's device, as fit_dynamics forms them
             net.set_transformations(*_dynamics_transforms(net.residual, s.to(mdl.device), a.to(mdl.device), sp.to(mdl.device)))
     return _fit_members(nets, opts, lambda dev: (_f32(torch.cat([s, a], -1), dev), 0), sp, TGT_RESIDUAL if nets[0].residual else TGT_PLAIN,
-                        fit_mb_size, fit_epochs, max_steps, "mjx_dyn_fit_ensemble", _draws)
+                        fit_mb_size, fit_epochs, max_steps,
+                        "mjx_dyn_fit_ensemble" + ("_team" if team and team_fit_shape(list(nets[0].layer_sizes)) else ""), _draws)
 
 
 def _same_reward_fit(models):
@@ -518,17 +532,19 @@ def world_model_fit_indices(K, num_samples, batch_size, epochs, max_steps=1e10, 
     return tuple((np.stack([d[0] for d in draws]), draws[0][1], draws[0][2]) for draws in (dyn, rew))
 
 
-def fit_world_models(models, s, a, sp, r, fit_mb_size, fit_epochs, max_steps=1e4, set_transformations=True):
+def fit_world_models(models, s, a, sp, r, fit_mb_size, fit_epochs, max_steps=1e4, set_transformations=True, team=False):
     """the driver's fit loop (run_model_accel_npg.py:170-178, without the logging) --
     ``for mdl in models: mdl.fit_dynamics(s, a, sp, ...); mdl.fit_reward(s, a, r, ...)`` -- as two launches: all index draws
     first, in the driver's order (:func:`world_model_fit_indices`), then the dynamics ensemble fit, then the reward ensemble fit
     (it reads the fitted dynamics; stream order gives it that).  -> (K dynamics epoch-loss lists, K reward epoch-loss lists or
-    None).  With no learned rewards it is :func:`fit_ensemble`; members that cannot share a call run the driver's loop."""
+    None).  With no learned rewards it is :func:`fit_ensemble`; members that cannot share a call run the driver's loop.
+    ``team``: passed to :func:`fit_ensemble` (the dynamics fit alone has a team kernel)."""
     models = list(models)
     if not models:
         return [], []
     if not any(mdl.learn_reward for mdl in models):
-        return fit_ensemble(models, s, a, sp, fit_mb_size, fit_epochs, max_steps=max_steps, set_transformations=set_transformations), None
+        return fit_ensemble(models, s, a, sp, fit_mb_size, fit_epochs, max_steps=max_steps, set_transformations=set_transformations,
+                            team=team), None
     if not (_same_fit(models) and _same_reward_fit(models)):
         dl, rl = [], []
         for mdl in models:
@@ -538,7 +554,7 @@ def fit_world_models(models, s, a, sp, r, fit_mb_size, fit_epochs, max_steps=1e4
         return dl, rl
     dyn_draws, rew_draws = world_model_fit_indices(len(models), int(sp.shape[0]), fit_mb_size, fit_epochs, max_steps, True)
     dl = fit_ensemble(models, s, a, sp, fit_mb_size, fit_epochs, max_steps=max_steps, set_transformations=set_transformations,
-                      _draws=dyn_draws)
+                      _draws=dyn_draws, team=team)
     rl = fit_reward_ensemble(models, s, a, r, fit_mb_size, fit_epochs, max_steps=max_steps, set_transformations=set_transformations,
                              _draws=rew_draws)
     return dl, rl

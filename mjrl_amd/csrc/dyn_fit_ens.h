@@ -46,8 +46,8 @@
 // Every delta is formed before the layer it reads is updated.  A weight-gradient tile (32 x 32, 16 accumulator registers) goes
 // straight from the MFMA chain into the Adam update of the 16 weights the lane holds: gradients never touch memory.
 //
-// Out of scope: teams of several workgroups per member, bf16x3 products and more than two hidden layers: mjx_dyn_fit_route /
-// mjx_reward_fit_route send them to mjx_dyn_fit_adam member by member.
+// Out of scope: bf16x3 products and more than two hidden layers: mjx_dyn_fit_route / mjx_reward_fit_route send them to
+// mjx_dyn_fit_adam member by member.  (Teams of several workgroups per member: dyn_fit_ens_team.h.)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -1,4 +1,4 @@
-// fit_host.h -- host side of the baseline and minibatch trainers (baseline.h, mlp_fit.h, mlp_fit_team.h, dynamics.h, dyn_fit_ens.h, policy_fit.h):
+// fit_host.h -- host side of the baseline and minibatch trainers (baseline.h, mlp_fit.h, mlp_fit_team.h, dynamics.h, dyn_fit_ens.h, dyn_fit_ens_team.h, policy_fit.h):
 // the feature-table cache, the routes of the ridge Gram, the MLP-baseline predict and fit and the policy minibatch fit as plain arithmetic, and
 // what acts on a route -- the bodies of the predict and fit entries; mjx.hip checks arguments and forwards.  Included by mjx.hip after model_host.h
 // (DynNet's helpers) and before update_host.h: the policy fit takes the pieces of mjx_ctx it uses as parameters.
@@ -347,6 +347,74 @@ inline int dfe_run(const float* x, int64_t x_stride, const float* y, int64_t y_s
   return MJX_OK;
 }
 
+// ---- ... with a team of G workgroups per member (dyn_fit_ens_team.h).  Route 2 of mjx_dyn_fit_ensemble_team.
+// Its exchange block and, behind it, the members' [arrival counter, give-up word] pairs: uncached device memory as fit_exchange's, per thread
+// and device.  The fits a thread puts on one stream follow each other, so one block serves them all; a call that needs more than the block
+// holds gets a new one of at least twice the size and the old one STAYS (uncached memory a kernel has read is never freed): all blocks of a
+// thread and device together stay under twice the largest call's need.
+inline int fit_exchange_sized(size_t xbytes, size_t bar_bytes, FitExchange& x) {
+  struct Block { char* p = nullptr; size_t xcap = 0, bcap = 0; };
+  static thread_local PerDevice<Block> block_of;
+  Block& b = block_of.here();
+  if (!b.p || b.xcap < xbytes || b.bcap < bar_bytes) {
+    auto grown = [](size_t need, size_t cap) { need = (need + 255) & ~(size_t)255; return need <= cap ? cap : need > 2 * cap ? need : 2 * cap; };
+    const size_t xcap = grown(xbytes, b.xcap), bcap = grown(bar_bytes, b.bcap);
+    char* p = nullptr;
+    HIPCHK(hipExtMallocWithFlags((void**)&p, xcap + bcap, hipDeviceMallocUncached));
+    b.p = p; b.xcap = xcap; b.bcap = bcap;
+  }
+  x.xch = (float*)b.p; x.bar = (unsigned*)(b.p + b.xcap);
+  return MJX_OK;
+}
+// dfe_run's per-member prep, then per launch at most floor(CUs / G) teams (and at most DFE_CHUNK: their step counts travel as kernel arguments),
+// each workgroup with LDS that leaves no room for a second one on its CU -- every team of a launch is co-resident on an idle device; the
+// give-up path covers a busy one -- and behind the launches the verdict.  The caller has asked dfe_team_serves.
+inline int dfe_team_run(const float* x, int64_t x_stride, const float* y, int64_t y_stride, int64_t N, int K, const DynNet& net, const float* in_tr,
+                        const float* out_tr, int target_mode, int act, float* params, float* m, float* v, const int64_t* step0,
+                        const int32_t* idx, int64_t steps, int batch, float lr, float wd, float* loss_out, void* stream) {
+  const int din = net.din(), dout = net.dout();
+  MJX_DEVICE_ENTRY();
+  hipStream_t st = (hipStream_t)stream;
+  const DfeTeamLayout L(net, batch);
+  const int cap = cu_count() / L.G, chunk = cap < DFE_CHUNK ? cap : DFE_CHUNK;
+  if (chunk < 1) return fail(MJX_ERR_UNSUPPORTED, "a team of %d workgroups needs %d CUs", L.G, L.G);
+  float* scr = nullptr;
+  if (int rc = dev_scratch(SITE_DYN_FIT_ENS, stream, (size_t)K * (size_t)N * (din + dout) * sizeof(float), &scr)) return rc;
+  float* xn = scr; float* tg = xn + (size_t)K * N * din;
+  for (int k = 0; k < K; ++k)
+    launch_dyn_prep(x + k * x_stride, y + k * y_stride, N, din, dout, in_tr + (int64_t)k * 2 * din, out_tr + (int64_t)k * 2 * dout, target_mode,
+                    xn + (size_t)k * N * din, tg + (size_t)k * N * dout, st);
+  FitExchange ex;
+  if (int rc = fit_exchange_sized((size_t)(K < chunk ? K : chunk) * L.slot_floats() * sizeof(float), (size_t)K * 2 * sizeof(unsigned), ex)) return rc;
+  hipLaunchKernelGGL(k_dfe_team_clear, dim3(capped_grid(2 * (int64_t)K, 256, 64)), dim3(256), 0, st, ex.bar, 2 * (int64_t)K);
+  if (int rc = lds_limit((const void*)k_dyn_fit_ens_team, L.lds_bytes())) return rc;
+  DynFitTeamArgs t{};
+  DynFitEnsArgs& a = t.e;
+  a.din = din; a.h1 = net.sz[1]; a.h2 = net.sz[2]; a.dout = dout; a.B = batch; a.act = act;
+  a.P = net.P; a.N = N; a.steps = steps; a.xn = xn; a.tg = tg; a.idx = idx; a.W = params; a.m = m; a.v = v; a.loss = loss_out;
+  a.lr = lr; a.wd = wd;
+  t.G = L.G; t.xch = ex.xch; t.bar = ex.bar; t.xslot = (int64_t)L.slot_floats();
+  for (int k0 = 0; k0 < K; k0 += chunk) {
+    const int kn = K - k0 < chunk ? K - k0 : chunk;
+    a.k0 = k0;
+    for (int q = 0; q < kn; ++q) a.step0[q] = step0[k0 + q];
+    hipLaunchKernelGGL(k_dyn_fit_ens_team, dim3((unsigned)(kn * L.G)), dim3(DFE_THREADS), L.lds_bytes(), st, t);
+  }
+  hipLaunchKernelGGL(k_dfe_team_verdict, dim3((unsigned)K), dim3(64), 0, st, (const unsigned*)ex.bar, loss_out, steps);
+  HIPCHK(hipGetLastError());
+  return MJX_OK;
+}
+
+// what both ensemble entries and the team entry ask of their arguments, after the sizes are parsed
+inline bool dfe_args_ok(const float* x, int64_t x_stride, const float* y, int64_t y_stride, int64_t N, int K, const DynNet& net, const float* in_tr,
+                        const float* out_tr, int target_mode, int act, const float* params, const float* m, const float* v, const int64_t* step0,
+                        const int32_t* idx, int64_t steps, int batch, const float* loss_out) {
+  if (!x || !y || !in_tr || !out_tr || !params || !m || !v || !step0 || (steps > 0 && (!idx || !loss_out)) || N <= 0 ||
+      x_stride < 0 || y_stride < 0 || batch <= 0 || batch > N || steps < 0 || !dyn_args_ok(net, K, act, target_mode))
+    return false;
+  for (int k = 0; k < K; ++k) if (step0[k] < 0) return false;
+  return true;
+}
 // the body of both ensemble entries, after the sizes are parsed: the argument check, the route (the entry's switch, read per call -- the
 // tests and tools/bench_dyn_fit.py compare the two routes in one process -- and what its shape predicate answered) written to route_out,
 // then route 0, member by member on the routes of dyn_fit_impl (the check above covers every member's), or route 1, dfe_run<RAG>
@@ -356,10 +424,8 @@ inline int dfe_entry(const float* x, int64_t x_stride, const float* y, int64_t y
                      int64_t steps, int batch, float lr, float wd, float* loss_out, const char* switch_name, bool shape_served, int* route_out,
                      void* stream) {
   const int din = net.din(), dout = net.dout();
-  if (!x || !y || !in_tr || !out_tr || !params || !m || !v || !step0 || (steps > 0 && (!idx || !loss_out)) || N <= 0 ||
-      x_stride < 0 || y_stride < 0 || batch <= 0 || batch > N || steps < 0 || !dyn_args_ok(net, K, act, target_mode))
+  if (!dfe_args_ok(x, x_stride, y, y_stride, N, K, net, in_tr, out_tr, target_mode, act, params, m, v, step0, idx, steps, batch, loss_out))
     return fail(MJX_ERR_ARG, "bad arguments");
-  for (int k = 0; k < K; ++k) if (step0[k] < 0) return fail(MJX_ERR_ARG, "bad arguments");
   const int route = env_flag(switch_name, true) && shape_served ? 1 : 0;
   if (route_out) *route_out = route;
   if (steps == 0) return MJX_OK;

@@ -22,6 +22,7 @@
 #include "baseline.h"
 #include "dynamics.h"
 #include "dyn_fit_ens.h"
+#include "dyn_fit_ens_team.h"
 #include "fused_policy.h"
 #include "policy_fit.h"
 #include "rccl_dyn.h"
@@ -546,6 +547,33 @@ int mjx_dyn_fit_ensemble(const float* x, int64_t x_stride, const float* y, int64
   if (int rc = dyn_net(sizes, n_sizes, net)) return rc;
   return dfe_entry<false>(x, x_stride, y, y_stride, N, K, net, in_tr, out_tr, target_mode, act, params, m, v, step0, idx, steps,
                           batch, lr, wd, loss_out, "MJX_DYN_FIT_ENS", dfe_serves(net, batch, target_mode), route_out, stream);
+}
+
+// ---- ... with a team of workgroups per member (csrc/dyn_fit_ens_team.h; host side: csrc/fit_host.h dfe_team_run)
+int mjx_dyn_fit_team_route(const int* sizes, int n_sizes, int batch, int target_mode, int K) {
+  DynNet net;
+  if (int rc = dyn_net(sizes, n_sizes, net)) return rc;
+  if (batch <= 0 || K <= 0 || target_mode < DYN_TGT_AFFINE || target_mode > DYN_TGT_RESIDUAL) return fail(MJX_ERR_ARG, "bad batch, member count or target mode");
+  return dfe_team_serves(net, batch, target_mode, cu_count());
+}
+
+int mjx_dyn_fit_ensemble_team(const float* x, int64_t x_stride, const float* y, int64_t y_stride, int64_t N, int K, const int* sizes, int n_sizes,
+                              const float* in_tr, const float* out_tr, int target_mode, int act, float* params, float* m, float* v,
+                              const int64_t* step0, const int32_t* idx, int64_t steps, int batch, float lr, float wd, float* loss_out,
+                              int* route_out, void* stream) {
+  DynNet net;
+  if (int rc = dyn_net(sizes, n_sizes, net)) return rc;
+  // (both switches read per call; a shape or a switch that leaves no team: the call IS mjx_dyn_fit_ensemble)
+  const int G = env_flag("MJX_DYN_FIT_TEAM", true) && env_flag("MJX_DYN_FIT_ENS", true) ? dfe_team_serves(net, batch, target_mode, cu_count()) : 0;
+  if (!G)
+    return mjx_dyn_fit_ensemble(x, x_stride, y, y_stride, N, K, sizes, n_sizes, in_tr, out_tr, target_mode, act, params, m, v, step0, idx, steps,
+                                batch, lr, wd, loss_out, route_out, stream);
+  if (!dfe_args_ok(x, x_stride, y, y_stride, N, K, net, in_tr, out_tr, target_mode, act, params, m, v, step0, idx, steps, batch, loss_out))
+    return fail(MJX_ERR_ARG, "bad arguments");
+  if (route_out) *route_out = 2;
+  if (steps == 0) return MJX_OK;
+  return dfe_team_run(x, x_stride, y, y_stride, N, K, net, in_tr, out_tr, target_mode, act, params, m, v, step0, idx, steps, batch, lr, wd,
+                      loss_out, stream);
 }
 
 // ---- the reward nets of the whole ensemble (target mode 0: the loss runs through the output affine on raw r)

@@ -1,4 +1,4 @@
-// model_host.h -- host side of the learned-model kernels (dynamics.h, dyn_fit_ens.h, plan.h, path_reward.h, plan_wide.h, policy_rollout.h, policy_rollout_wide.h, rollout_batch.h, rows_wide.h): their shared
+// model_host.h -- host side of the learned-model kernels (dynamics.h, dyn_fit_ens.h, dyn_fit_ens_team.h, plan.h, path_reward.h, plan_wide.h, policy_rollout.h, policy_rollout_wide.h, rollout_batch.h, rows_wide.h): their shared
 // argument checks, their routes as plain arithmetic, the launches more than one entry makes, and the four entries that have a wide
 // route (plan rollout, path rewards, policy rollout, rollout disagreement) with their route queries: mjx.hip only forwards to them.
 // The rule that orders an entry's routes is plain C++ on top (tests/c/model_host.cpp checks it against a table without a GPU); the
@@ -287,6 +287,14 @@ inline bool dfe_serves(const DynNet& net, int batch, int target_mode) {
   if (target_mode != DYN_TGT_PLAIN && target_mode != DYN_TGT_RESIDUAL) return false;
   for (int l = 1; l <= 2; ++l) if (net.sz[l] % 32 || net.sz[l] < 32 || net.sz[l] > DFE_MAXH) return false;
   return net.din() <= DFE_MAXIN && net.dout() <= DFE_MAXOUT;
+}
+// The team k_dyn_fit_ens_team (dyn_fit_ens_team.h) fits a member of such a shape with, on a device of `cus` CUs: what dfe_serves takes,
+// narrowed to both hidden widths multiples of 128 (G = 4) or of 64 (G = 2), the team's LDS layout -- X always in LDS -- within LDS_MAX, and
+// one team co-resident at a workgroup per CU.  -> G, or 0: not served (MJX_DYN_FIT_TEAM=0, read per call: none).  Plain arithmetic.
+inline int dfe_team_serves(const DynNet& net, int batch, int target_mode, int cus) {
+  if (!dfe_serves(net, batch, target_mode)) return 0;
+  const DfeTeamLayout L(net, batch);
+  return L.fits() && L.G <= cus ? L.G : 0;
 }
 // The shapes k_dyn_fit_ens<true> serves for mjx_reward_fit_ensemble (target mode 0; MJX_REWARD_FIT_ENS=0, read per call: none): any two
 // hidden widths the padded tiles hold.  Plain arithmetic.
