@@ -47,7 +47,9 @@
 // straight from the MFMA chain into the Adam update of the 16 weights the lane holds: gradients never touch memory.
 //
 // Out of scope: bf16x3 products and more than two hidden layers: mjx_dyn_fit_route / mjx_reward_fit_route send them to
-// mjx_dyn_fit_adam member by member.  (Teams of several workgroups per member: dyn_fit_ens_team.h.)
+// mjx_dyn_fit_adam member by member.  Teams of several workgroups per member: dyn_fit_ens_team.h, whose kernel calls this
+// header's dfe_dims, dfe_delta, dfe_delta_store, dfe_grad_adam and dfe_bias_corr on a slice of the units -- hence their leading
+// dimension, row stride and flag parameters, which k_dyn_fit_ens passes as the layer's own width, the tile's stride and `true`.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -65,13 +67,20 @@ constexpr int DFE_MAXH = 256, DFE_MAXIN = 128, DFE_MAXOUT = 64, DFE_MAXB = 64;
 constexpr int DFE_CHUNK = 64;                                // members per launch (their step counts travel as kernel arguments)
 constexpr size_t DFE_STATIC_LDS = 8 * sizeof(double) + 64 * sizeof(int);
 
-struct DfeLayout {
-  int Bp, ST, K0, ZR;
+// The tile dimensions of a minibatch of B rows on a net of din inputs and dout outputs, for the host's layouts and for both
+// kernels: sample columns Bp in NS tiles of 32, tile row stride ST, the rows of X (K0) and of Z3 (ZR)
+struct DfeDims { int Bp, NS, ST, K0, ZR; };
+__host__ __device__ __forceinline__ DfeDims dfe_dims(int B, int din, int dout) {
+  DfeDims d;
+  d.Bp = B > 32 ? 64 : 32; d.NS = d.Bp >> 5; d.ST = d.Bp + 4;
+  d.K0 = (din + 7) & ~7; d.ZR = (dout + 31) & ~31;
+  return d;
+}
+
+struct DfeLayout : DfeDims {
   size_t tiles, xtile;                                      // floats of H1 + H2 + Z3; of X
   bool x_in_lds;
-  __host__ DfeLayout(const DynNet& net, int batch) {
-    Bp = batch > 32 ? 64 : 32; ST = Bp + 4;
-    K0 = (net.din() + 7) & ~7; ZR = (net.dout() + 31) & ~31;
+  __host__ DfeLayout(const DynNet& net, int batch) : DfeDims(dfe_dims(batch, net.din(), net.dout())) {
     tiles = (size_t)(dfe_pad32(net.sz[1]) + dfe_pad32(net.sz[2]) + ZR) * ST; xtile = (size_t)K0 * ST;
     x_in_lds = (tiles + xtile) * sizeof(float) + DFE_STATIC_LDS <= LDS_MAX;
   }
@@ -106,11 +115,12 @@ __device__ __forceinline__ void dfe_adam(float* p, float* m, float* v, int64_t i
 
 // dreg[q] = (sum_{jj < dj} W[jj][u] D[jj][s]) * act'(H[u][s]) for the wave's tiles q = 0, 1 of the MT x NS tiles of H
 // (MT = di / 32; RAG: ceil(di / 32), where the columns u >= di of W read as zeros and the unit rows u >= di of the last tile
-// come out as exact zeros whatever act'(0) is: tanh' (0) = 1 would pass a stray product on).  D: the [dj rounded up to
-// 8][sample] delta tile, zeros beyond dj.
+// come out as exact zeros whatever act'(0) is: tanh' (0) = 1 would pass a stray product on).  W: dj rows of ldw floats, unit u
+// at column u (the whole layer: ldw = di; a team's slice of units: the columns that start at W).  D: the [dj rounded up to
+// 8][sample] delta tile, zeros beyond dj.  dact false: the bare sum, H unread (a team's partial delta, summed before act').
 template <bool RAG>
-__device__ __forceinline__ void dfe_delta(const float* __restrict__ W, int dj, int di, const float* D, const float* H, int ST, int NS,
-                                          int act, int w, int j, int hi, f32x16 (&dreg)[2]) {
+__device__ __forceinline__ void dfe_delta(const float* __restrict__ W, int ldw, int dj, int di, const float* D, const float* H, int ST, int NS,
+                                          int act, bool dact, int w, int j, int hi, f32x16 (&dreg)[2]) {
   dfe_fresh(w, j, hi);
   const int MT = RAG ? (di + 31) >> 5 : di >> 5, Kp = (dj + 7) & ~7;
 #pragma unroll
@@ -125,7 +135,7 @@ __device__ __forceinline__ void dfe_delta(const float* __restrict__ W, int dj, i
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
           const bool ok = kk + q < dj && cok;
-          const float x = wc[(int64_t)(ok ? kk + q : 0) * di];
+          const float x = wc[(int64_t)(ok ? kk + q : 0) * ldw];
           av[q] = ok ? x : 0.f;
           bv[q] = D[(kk + q) * ST + 32 * nt + j];
         }
@@ -141,7 +151,7 @@ __device__ __forceinline__ void dfe_delta(const float* __restrict__ W, int dj, i
       }
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        acc[r] *= dyn_dact(H[(32 * mt + unit_of(r, hi)) * ST + 32 * nt + j], act);
+        if (dact) acc[r] *= dyn_dact(H[(32 * mt + unit_of(r, hi)) * ST + 32 * nt + j], act);
         if (RAG && 32 * mt + unit_of(r, hi) >= di) acc[r] = 0.f;
       }
       dreg[q2] = acc;
@@ -149,8 +159,10 @@ __device__ __forceinline__ void dfe_delta(const float* __restrict__ W, int dj, i
   }
 }
 
+// the registers dfe_delta left -> out[unit][sample], rows of ldo floats: over the LDS tile dfe_delta read (ldo = ST), or into a
+// team-mate's [di][Bp] block of the exchange (ldo = Bp)
 template <bool RAG>
-__device__ __forceinline__ void dfe_delta_store(const f32x16 (&dreg)[2], int di, float* H, int ST, int NS, int w, int j, int hi) {
+__device__ __forceinline__ void dfe_delta_store(const f32x16 (&dreg)[2], int di, float* out, int ldo, int NS, int w, int j, int hi) {
   const int MT = RAG ? (di + 31) >> 5 : di >> 5;
 #pragma unroll
   for (int q2 = 0; q2 < 2; ++q2) {
@@ -158,18 +170,19 @@ __device__ __forceinline__ void dfe_delta_store(const f32x16 (&dreg)[2], int di,
     if (t < MT * NS) {
       const int mt = t % MT, nt = t / MT;
 #pragma unroll
-      for (int r = 0; r < 16; ++r) H[(32 * mt + unit_of(r, hi)) * ST + 32 * nt + j] = dreg[q2][r];
+      for (int r = 0; r < 16; ++r) out[(32 * mt + unit_of(r, hi)) * ldo + 32 * nt + j] = dreg[q2][r];
     }
   }
 }
 
 // g[jj][i] = sum_s D[jj][s] In[i][s] tile by tile (32 x 32, a wave per tile), each tile straight into the Adam update of the
-// weights W[jj][i] (jj < dj, i < di) its lanes hold; then the bias: g[jj] = sum_s D[jj][s], a thread per unit.  D: [dj rounded
-// up to 32][sample]; in4(i, s) reads In[i][s .. s + 3] (zeros for a row the tile does not have).
+// weights W[jj][i] (jj < dj, i < di) its lanes hold: at offset oW of the member's block, rows ldw floats apart (the whole layer:
+// ldw = di; di columns of a wider layer: they start at oW); then, where `bias`, the bias at ob: g[jj] = sum_s D[jj][s], a thread
+// per unit.  D: [dj rounded up to 32][sample]; in4(i, s) reads In[i][s .. s + 3] (zeros for a row the tile does not have).
 template <class LdIn4>
-__device__ __forceinline__ void dfe_grad_adam(const float* D, int dj, int di, LdIn4 in4, int Bp, int ST, float* __restrict__ P,
-                                              float* __restrict__ Pm, float* __restrict__ Pv, int64_t oW, int64_t ob, float lr_bc1,
-                                              float inv_bc2s, float wd, int tid, int w, int j, int hi) {
+__device__ __forceinline__ void dfe_grad_adam(const float* D, int dj, int di, int ldw, LdIn4 in4, int Bp, int ST, float* __restrict__ P,
+                                              float* __restrict__ Pm, float* __restrict__ Pv, int64_t oW, int64_t ob, bool bias,
+                                              float lr_bc1, float inv_bc2s, float wd, int tid, int w, int j, int hi) {
   dfe_fresh(w, j, hi);
   asm volatile("" : "+v"(tid));
   const int RT = (dj + 31) >> 5, CT = (di + 31) >> 5;
@@ -188,34 +201,44 @@ __device__ __forceinline__ void dfe_grad_adam(const float* D, int dj, int di, Ld
     // are requested before the first update.  Offsets are 32-bit from the member's (uniform) base, so a row costs one register
     // for the three blocks; a lane outside the matrix reads the layer's first entry and stores nothing.
     const int col = 32 * nt + j;
-    const unsigned e0 = (unsigned)oW + (unsigned)((32 * mt + 4 * hi) * di + col);
+    const unsigned e0 = (unsigned)oW + (unsigned)((32 * mt + 4 * hi) * ldw + col);
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
       float pw[8], pm[8], pv[8];
 #pragma unroll
       for (int r = 8 * h; r < 8 * h + 8; ++r) {
         const bool ok = 32 * mt + unit_of(r, hi) < dj && col < di;
-        const unsigned e = ok ? e0 + (unsigned)(unit_of(r, 0) * di) : (unsigned)oW;
+        const unsigned e = ok ? e0 + (unsigned)(unit_of(r, 0) * ldw) : (unsigned)oW;
         pw[r & 7] = P[e]; pm[r & 7] = Pm[e]; pv[r & 7] = Pv[e];
       }
 #pragma unroll
       for (int r = 8 * h; r < 8 * h + 8; ++r) {
         const bool ok = 32 * mt + unit_of(r, hi) < dj && col < di;
-        const unsigned e = e0 + (unsigned)(unit_of(r, 0) * di);
+        const unsigned e = e0 + (unsigned)(unit_of(r, 0) * ldw);
         dfe_adam_math(pw[r & 7], pm[r & 7], pv[r & 7], acc[r], lr_bc1, inv_bc2s, wd);
         if (ok) { P[e] = pw[r & 7]; Pm[e] = pm[r & 7]; Pv[e] = pv[r & 7]; }
       }
     }
   }
-  for (int u = tid; u < dj; u += DFE_THREADS) {
-    float g = 0.f;
-    for (int s = 0; s < Bp; ++s) g += D[u * ST + s];
-    dfe_adam(P, Pm, Pv, ob + u, g, lr_bc1, inv_bc2s, wd);
-  }
+  if (bias)
+    for (int u = tid; u < dj; u += DFE_THREADS) {
+      float g = 0.f;
+      for (int s = 0; s < Bp; ++s) g += D[u * ST + s];
+      dfe_adam(P, Pm, Pv, ob + u, g, lr_bc1, inv_bc2s, wd);
+    }
+}
+
+// Adam's bias corrections after t steps, as dfe_adam_math takes them
+__device__ __forceinline__ void dfe_bias_corr(int64_t t, float lr, float& lr_bc1, float& inv_bc2s) {
+  float bc2s;
+  dyn_bias_corr(t, lr, lr_bc1, bc2s);
+  inv_bc2s = 1.0f / bc2s;
 }
 
 // RAG = false: the instance of the dynamics ensembles (hidden widths multiples of 32, targets formed by k_dyn_prep, plain MSE).
 // RAG = true: any hidden width 1 .. 256 (tiles padded to 32 unit rows) and the affine head of target mode 0 (RewardNet).
+// (The gather, the head and the member's pointers stand here and, on the LDS tile and the summed partials, in k_dyn_fit_ens_team:
+// written as shared functions they changed this kernel's instructions.)
 template <bool RAG>
 __global__ __launch_bounds__(DFE_THREADS) void k_dyn_fit_ens(DynFitEnsArgs a) {
   extern __shared__ __attribute__((aligned(16))) float els[];
@@ -224,8 +247,8 @@ __global__ __launch_bounds__(DFE_THREADS) void k_dyn_fit_ens(DynFitEnsArgs a) {
   const int tid = threadIdx.x, w = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, j = lane & 31, hi = lane >> 5;
   const int k = a.k0 + (int)blockIdx.x;
   const int din = a.din, h1 = a.h1, h2 = a.h2, dout = a.dout, B = a.B, act = a.act;
-  const int Bp = B > 32 ? 64 : 32, NS = Bp >> 5, ST = Bp + 4;
-  const int K0 = (din + 7) & ~7, ZR = (dout + 31) & ~31;
+  const DfeDims T = dfe_dims(B, din, dout);
+  const int Bp = T.Bp, NS = T.NS, ST = T.ST, K0 = T.K0, ZR = T.ZR;
   const int h1p = RAG ? dfe_pad32(h1) : h1, h2p = RAG ? dfe_pad32(h2) : h2;
   float* H1 = els; float* H2 = H1 + h1p * ST; float* Z3 = H2 + h2p * ST; float* XL = Z3 + ZR * ST;
   const bool xg = a.xscr != nullptr;
@@ -286,30 +309,30 @@ __global__ __launch_bounds__(DFE_THREADS) void k_dyn_fit_ens(DynFitEnsArgs a) {
       for (int q = 0; q < DFE_WAVES; ++q) tot += red[q];
       loss[s] = (float)(tot / (double)(B * dout));
     }
-    float lr_bc1, bc2s;
-    dyn_bias_corr(step0 + s + 1, a.lr, lr_bc1, bc2s);
-    const float inv_bc2s = 1.0f / bc2s;
+    float lr_bc1, inv_bc2s;
+    dfe_bias_corr(step0 + s + 1, a.lr, lr_bc1, inv_bc2s);
     // ---- layer 3: delta2 with W3 as it is, then W3's own update
     f32x16 dreg[2];
-    dfe_delta<RAG>(P + oW3, dout, h2, Z3, H2, ST, NS, act, w, j, hi, dreg);
+    dfe_delta<RAG>(P + oW3, h2, dout, h2, Z3, H2, ST, NS, act, true, w, j, hi, dreg);
     __syncthreads();
-    dfe_grad_adam(Z3, dout, h2, [&](int r, int c) { return *(const f32x4*)&H2[r * ST + c]; }, Bp, ST, P, Pm, Pv, oW3, ob3, lr_bc1,
+    dfe_grad_adam(Z3, dout, h2, h2, [&](int r, int c) { return *(const f32x4*)&H2[r * ST + c]; }, Bp, ST, P, Pm, Pv, oW3, ob3, true, lr_bc1,
                   inv_bc2s, a.wd, tid, w, j, hi);
     __syncthreads();
     dfe_delta_store<RAG>(dreg, h2, H2, ST, NS, w, j, hi);
     __syncthreads();
     // ---- layer 2
-    dfe_delta<RAG>(P + oW2, h2, h1, H2, H1, ST, NS, act, w, j, hi, dreg);
+    dfe_delta<RAG>(P + oW2, h1, h2, h1, H2, H1, ST, NS, act, true, w, j, hi, dreg);
     __syncthreads();
-    dfe_grad_adam(H2, h2, h1, [&](int r, int c) { return *(const f32x4*)&H1[r * ST + c]; }, Bp, ST, P, Pm, Pv, oW2, ob2, lr_bc1,
+    dfe_grad_adam(H2, h2, h1, h1, [&](int r, int c) { return *(const f32x4*)&H1[r * ST + c]; }, Bp, ST, P, Pm, Pv, oW2, ob2, true, lr_bc1,
                   inv_bc2s, a.wd, tid, w, j, hi);
     __syncthreads();
     dfe_delta_store<RAG>(dreg, h1, H1, ST, NS, w, j, hi);
     __syncthreads();
     // ---- layer 1
-    dfe_grad_adam(H1, h1, din, ldx4, Bp, ST, P, Pm, Pv, oW1, ob1, lr_bc1, inv_bc2s, a.wd, tid, w, j, hi);
+    dfe_grad_adam(H1, h1, din, din, ldx4, Bp, ST, P, Pm, Pv, oW1, ob1, true, lr_bc1, inv_bc2s, a.wd, tid, w, j, hi);
     __syncthreads();
   }
 }
 
 }  // namespace mjx
+

@@ -313,36 +313,55 @@ inline int dyn_fit_impl(const DynNet& net, const float* x, const float* y, int64
   return MJX_OK;
 }
 
-// ---- the fit of a whole ensemble (dyn_fit_ens.h).  Route 1 of both ensemble entries: per-member prep into scratch, then one
-// k_dyn_fit_ens<RAG> launch per DFE_CHUNK members
-template <bool RAG>
-inline int dfe_run(const float* x, int64_t x_stride, const float* y, int64_t y_stride, int64_t N, int K, const DynNet& net, const float* in_tr,
-                   const float* out_tr, int target_mode, int act, float* params, float* m, float* v, const int64_t* step0,
-                   const int32_t* idx, int64_t steps, int batch, float lr, float wd, float* loss_out, void* stream) {
-  const int din = net.din(), dout = net.dout();
-  MJX_DEVICE_ENTRY();
-  hipStream_t st = (hipStream_t)stream;
-  const DfeLayout L(net, batch);
-  // scratch, per member: normalised inputs and targets (every member has its own transforms), and the X tile where LDS has no room
-  const size_t xt = L.x_in_lds ? 0 : L.xtile;
+// ---- the fit of a whole ensemble (dyn_fit_ens.h, dyn_fit_ens_team.h).  What mjx_dyn_fit_ensemble, mjx_dyn_fit_ensemble_team and
+// mjx_reward_fit_ensemble receive, after dyn_net has parsed the sizes: each entry fills one record, and everything below takes it
+struct DfeCall {
+  const float* x; int64_t x_stride; const float* y; int64_t y_stride; int64_t N; int K;
+  DynNet net;
+  const float* in_tr; const float* out_tr; int target_mode, act;
+  float* params; float* m; float* v; const int64_t* step0;
+  const int32_t* idx; int64_t steps; int batch; float lr, wd;
+  float* loss_out; void* stream;
+};
+// what routes 1 and 2 share ahead of their launches: the scratch -- per member the normalised inputs and targets (every member has its own
+// transforms) and, behind them, `xtiles` floats for the X tiles where the caller's LDS has no room --, the per-member prep, the kernel's arguments
+inline int dfe_prepare(const DfeCall& c, size_t xtiles, DynFitEnsArgs& a) {
+  const int din = c.net.din(), dout = c.net.dout();
+  const size_t rows = (size_t)c.K * (size_t)c.N * (din + dout);
   float* scr = nullptr;
-  if (int rc = dev_scratch(SITE_DYN_FIT_ENS, stream, ((size_t)K * (size_t)N * (din + dout) + 4 + (size_t)K * xt) * sizeof(float), &scr)) return rc;
-  float* xn = scr; float* tg = xn + (size_t)K * N * din;
-  float* xscr = xt ? scr + (((size_t)K * N * (din + dout) + 3) & ~(size_t)3) : nullptr;
-  for (int k = 0; k < K; ++k)
-    launch_dyn_prep(x + k * x_stride, y + k * y_stride, N, din, dout, in_tr + (int64_t)k * 2 * din, out_tr + (int64_t)k * 2 * dout, target_mode,
-                    xn + (size_t)k * N * din, tg + (size_t)k * N * dout, st);
-  if (int rc = lds_limit((const void*)k_dyn_fit_ens<RAG>, L.lds_bytes())) return rc;
-  DynFitEnsArgs a{};
-  a.din = din; a.h1 = net.sz[1]; a.h2 = net.sz[2]; a.dout = dout; a.B = batch; a.act = act;
-  a.P = net.P; a.N = N; a.steps = steps; a.xn = xn; a.tg = tg; a.idx = idx; a.W = params; a.m = m; a.v = v; a.loss = loss_out; a.xscr = xscr;
-  a.lr = lr; a.wd = wd; a.otr = RAG ? out_tr : nullptr;
-  for (int k0 = 0; k0 < K; k0 += DFE_CHUNK) {               // one launch for K <= DFE_CHUNK members
-    const int kn = K - k0 < DFE_CHUNK ? K - k0 : DFE_CHUNK;
+  if (int rc = dev_scratch(SITE_DYN_FIT_ENS, c.stream, (rows + (xtiles ? 4 + xtiles : 0)) * sizeof(float), &scr)) return rc;
+  float* xn = scr; float* tg = xn + (size_t)c.K * c.N * din;
+  for (int k = 0; k < c.K; ++k)
+    launch_dyn_prep(c.x + k * c.x_stride, c.y + k * c.y_stride, c.N, din, dout, c.in_tr + (int64_t)k * 2 * din, c.out_tr + (int64_t)k * 2 * dout,
+                    c.target_mode, xn + (size_t)k * c.N * din, tg + (size_t)k * c.N * dout, (hipStream_t)c.stream);
+  a = DynFitEnsArgs{};
+  a.din = din; a.h1 = c.net.sz[1]; a.h2 = c.net.sz[2]; a.dout = dout; a.B = c.batch; a.act = c.act;
+  a.P = c.net.P; a.N = c.N; a.steps = c.steps; a.xn = xn; a.tg = tg; a.idx = c.idx; a.W = c.params; a.m = c.m; a.v = c.v; a.loss = c.loss_out;
+  a.xscr = xtiles ? scr + ((rows + 3) & ~(size_t)3) : nullptr;
+  a.lr = c.lr; a.wd = c.wd;
+  return MJX_OK;
+}
+// the launches of a trainer over the members, `chunk` at a time (at most DFE_CHUNK: their step counts travel as kernel arguments), `wgs`
+// workgroups a member; `a` is the DynFitEnsArgs inside `args`
+template <class Args>
+inline void dfe_launch_chunks(void (*kern)(Args), Args& args, DynFitEnsArgs& a, const DfeCall& c, int chunk, int wgs, size_t lds) {
+  for (int k0 = 0; k0 < c.K; k0 += chunk) {
+    const int kn = c.K - k0 < chunk ? c.K - k0 : chunk;
     a.k0 = k0;
-    for (int q = 0; q < kn; ++q) a.step0[q] = step0[k0 + q];
-    hipLaunchKernelGGL(k_dyn_fit_ens<RAG>, dim3((unsigned)kn), dim3(DFE_THREADS), L.lds_bytes(), st, a);
+    for (int q = 0; q < kn; ++q) a.step0[q] = c.step0[k0 + q];
+    hipLaunchKernelGGL(kern, dim3((unsigned)(kn * wgs)), dim3(DFE_THREADS), lds, (hipStream_t)c.stream, args);
   }
+}
+// Route 1 of both ensemble entries: one k_dyn_fit_ens<RAG> launch per DFE_CHUNK members (one launch for K <= DFE_CHUNK)
+template <bool RAG>
+inline int dfe_run(const DfeCall& c) {
+  MJX_DEVICE_ENTRY();
+  const DfeLayout L(c.net, c.batch);
+  DynFitEnsArgs a;
+  if (int rc = dfe_prepare(c, L.x_in_lds ? 0 : (size_t)c.K * L.xtile, a)) return rc;
+  if (int rc = lds_limit((const void*)k_dyn_fit_ens<RAG>, L.lds_bytes())) return rc;
+  a.otr = RAG ? c.out_tr : nullptr;
+  dfe_launch_chunks(k_dyn_fit_ens<RAG>, a, a, c, DFE_CHUNK, 1, L.lds_bytes());
   HIPCHK(hipGetLastError());
   return MJX_OK;
 }
@@ -366,79 +385,55 @@ inline int fit_exchange_sized(size_t xbytes, size_t bar_bytes, FitExchange& x) {
   x.xch = (float*)b.p; x.bar = (unsigned*)(b.p + b.xcap);
   return MJX_OK;
 }
-// dfe_run's per-member prep, then per launch at most floor(CUs / G) teams (and at most DFE_CHUNK: their step counts travel as kernel arguments),
-// each workgroup with LDS that leaves no room for a second one on its CU -- every team of a launch is co-resident on an idle device; the
-// give-up path covers a busy one -- and behind the launches the verdict.  The caller has asked dfe_team_serves.
-inline int dfe_team_run(const float* x, int64_t x_stride, const float* y, int64_t y_stride, int64_t N, int K, const DynNet& net, const float* in_tr,
-                        const float* out_tr, int target_mode, int act, float* params, float* m, float* v, const int64_t* step0,
-                        const int32_t* idx, int64_t steps, int batch, float lr, float wd, float* loss_out, void* stream) {
-  const int din = net.din(), dout = net.dout();
+// dfe_run's prep, then per launch at most floor(CUs / G) teams, each workgroup with LDS that leaves no room for a second one on its CU --
+// every team of a launch is co-resident on an idle device; the give-up path covers a busy one -- and behind the launches the verdict.  The
+// caller has asked dfe_team_serves.
+inline int dfe_team_run(const DfeCall& c) {
   MJX_DEVICE_ENTRY();
-  hipStream_t st = (hipStream_t)stream;
-  const DfeTeamLayout L(net, batch);
+  hipStream_t st = (hipStream_t)c.stream;
+  const DfeTeamLayout L(c.net, c.batch);
   const int cap = cu_count() / L.G, chunk = cap < DFE_CHUNK ? cap : DFE_CHUNK;
   if (chunk < 1) return fail(MJX_ERR_UNSUPPORTED, "a team of %d workgroups needs %d CUs", L.G, L.G);
-  float* scr = nullptr;
-  if (int rc = dev_scratch(SITE_DYN_FIT_ENS, stream, (size_t)K * (size_t)N * (din + dout) * sizeof(float), &scr)) return rc;
-  float* xn = scr; float* tg = xn + (size_t)K * N * din;
-  for (int k = 0; k < K; ++k)
-    launch_dyn_prep(x + k * x_stride, y + k * y_stride, N, din, dout, in_tr + (int64_t)k * 2 * din, out_tr + (int64_t)k * 2 * dout, target_mode,
-                    xn + (size_t)k * N * din, tg + (size_t)k * N * dout, st);
-  FitExchange ex;
-  if (int rc = fit_exchange_sized((size_t)(K < chunk ? K : chunk) * L.slot_floats() * sizeof(float), (size_t)K * 2 * sizeof(unsigned), ex)) return rc;
-  hipLaunchKernelGGL(k_dfe_team_clear, dim3(capped_grid(2 * (int64_t)K, 256, 64)), dim3(256), 0, st, ex.bar, 2 * (int64_t)K);
-  if (int rc = lds_limit((const void*)k_dyn_fit_ens_team, L.lds_bytes())) return rc;
   DynFitTeamArgs t{};
-  DynFitEnsArgs& a = t.e;
-  a.din = din; a.h1 = net.sz[1]; a.h2 = net.sz[2]; a.dout = dout; a.B = batch; a.act = act;
-  a.P = net.P; a.N = N; a.steps = steps; a.xn = xn; a.tg = tg; a.idx = idx; a.W = params; a.m = m; a.v = v; a.loss = loss_out;
-  a.lr = lr; a.wd = wd;
-  t.G = L.G; t.xch = ex.xch; t.bar = ex.bar; t.xslot = (int64_t)L.slot_floats();
-  for (int k0 = 0; k0 < K; k0 += chunk) {
-    const int kn = K - k0 < chunk ? K - k0 : chunk;
-    a.k0 = k0;
-    for (int q = 0; q < kn; ++q) a.step0[q] = step0[k0 + q];
-    hipLaunchKernelGGL(k_dyn_fit_ens_team, dim3((unsigned)(kn * L.G)), dim3(DFE_THREADS), L.lds_bytes(), st, t);
-  }
-  hipLaunchKernelGGL(k_dfe_team_verdict, dim3((unsigned)K), dim3(64), 0, st, (const unsigned*)ex.bar, loss_out, steps);
+  if (int rc = dfe_prepare(c, 0, t.e)) return rc;
+  FitExchange ex;
+  if (int rc = fit_exchange_sized((size_t)(c.K < chunk ? c.K : chunk) * L.slot * sizeof(float), (size_t)c.K * 2 * sizeof(unsigned), ex)) return rc;
+  hipLaunchKernelGGL(k_dfe_team_clear, dim3(capped_grid(2 * (int64_t)c.K, 256, 64)), dim3(256), 0, st, ex.bar, 2 * (int64_t)c.K);
+  if (int rc = lds_limit((const void*)k_dyn_fit_ens_team, L.lds_bytes())) return rc;
+  t.G = L.G; t.xch = ex.xch; t.bar = ex.bar; t.xslot = (int64_t)L.slot;
+  dfe_launch_chunks(k_dyn_fit_ens_team, t, t.e, c, chunk, L.G, L.lds_bytes());
+  hipLaunchKernelGGL(k_dfe_team_verdict, dim3((unsigned)c.K), dim3(64), 0, st, (const unsigned*)ex.bar, c.loss_out, c.steps);
   HIPCHK(hipGetLastError());
   return MJX_OK;
 }
 
 // what both ensemble entries and the team entry ask of their arguments, after the sizes are parsed
-inline bool dfe_args_ok(const float* x, int64_t x_stride, const float* y, int64_t y_stride, int64_t N, int K, const DynNet& net, const float* in_tr,
-                        const float* out_tr, int target_mode, int act, const float* params, const float* m, const float* v, const int64_t* step0,
-                        const int32_t* idx, int64_t steps, int batch, const float* loss_out) {
-  if (!x || !y || !in_tr || !out_tr || !params || !m || !v || !step0 || (steps > 0 && (!idx || !loss_out)) || N <= 0 ||
-      x_stride < 0 || y_stride < 0 || batch <= 0 || batch > N || steps < 0 || !dyn_args_ok(net, K, act, target_mode))
+inline bool dfe_args_ok(const DfeCall& c) {
+  if (!c.x || !c.y || !c.in_tr || !c.out_tr || !c.params || !c.m || !c.v || !c.step0 || (c.steps > 0 && (!c.idx || !c.loss_out)) || c.N <= 0 ||
+      c.x_stride < 0 || c.y_stride < 0 || c.batch <= 0 || c.batch > c.N || c.steps < 0 || !dyn_args_ok(c.net, c.K, c.act, c.target_mode))
     return false;
-  for (int k = 0; k < K; ++k) if (step0[k] < 0) return false;
+  for (int k = 0; k < c.K; ++k) if (c.step0[k] < 0) return false;
   return true;
 }
 // the body of both ensemble entries, after the sizes are parsed: the argument check, the route (the entry's switch, read per call -- the
 // tests and tools/bench_dyn_fit.py compare the two routes in one process -- and what its shape predicate answered) written to route_out,
 // then route 0, member by member on the routes of dyn_fit_impl (the check above covers every member's), or route 1, dfe_run<RAG>
 template <bool RAG>
-inline int dfe_entry(const float* x, int64_t x_stride, const float* y, int64_t y_stride, int64_t N, int K, const DynNet& net, const float* in_tr,
-                     const float* out_tr, int target_mode, int act, float* params, float* m, float* v, const int64_t* step0, const int32_t* idx,
-                     int64_t steps, int batch, float lr, float wd, float* loss_out, const char* switch_name, bool shape_served, int* route_out,
-                     void* stream) {
-  const int din = net.din(), dout = net.dout();
-  if (!dfe_args_ok(x, x_stride, y, y_stride, N, K, net, in_tr, out_tr, target_mode, act, params, m, v, step0, idx, steps, batch, loss_out))
-    return fail(MJX_ERR_ARG, "bad arguments");
+inline int dfe_entry(const DfeCall& c, const char* switch_name, bool shape_served, int* route_out) {
+  const int din = c.net.din(), dout = c.net.dout();
+  if (!dfe_args_ok(c)) return fail(MJX_ERR_ARG, "bad arguments");
   const int route = env_flag(switch_name, true) && shape_served ? 1 : 0;
   if (route_out) *route_out = route;
-  if (steps == 0) return MJX_OK;
+  if (c.steps == 0) return MJX_OK;
   if (route == 0) {
-    for (int k = 0; k < K; ++k)
-      if (int rc = dyn_fit_impl(net, x + k * x_stride, y + k * y_stride, N, in_tr + (int64_t)k * 2 * din, out_tr + (int64_t)k * 2 * dout, target_mode,
-                                act, params + k * net.P, m + k * net.P, v + k * net.P, step0[k], idx + (int64_t)k * steps * batch, steps, batch,
-                                lr, wd, loss_out + (int64_t)k * steps, stream))
+    for (int k = 0; k < c.K; ++k)
+      if (int rc = dyn_fit_impl(c.net, c.x + k * c.x_stride, c.y + k * c.y_stride, c.N, c.in_tr + (int64_t)k * 2 * din, c.out_tr + (int64_t)k * 2 * dout,
+                                c.target_mode, c.act, c.params + k * c.net.P, c.m + k * c.net.P, c.v + k * c.net.P, c.step0[k],
+                                c.idx + (int64_t)k * c.steps * c.batch, c.steps, c.batch, c.lr, c.wd, c.loss_out + (int64_t)k * c.steps, c.stream))
         return rc;
     return MJX_OK;
   }
-  return dfe_run<RAG>(x, x_stride, y, y_stride, N, K, net, in_tr, out_tr, target_mode, act, params, m, v, step0, idx, steps, batch, lr, wd,
-                      loss_out, stream);
+  return dfe_run<RAG>(c);
 }
 
 }  // namespace mjx

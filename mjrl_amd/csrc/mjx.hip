@@ -543,10 +543,12 @@ int mjx_dyn_fit_ensemble(const float* x, int64_t x_stride, const float* y, int64
                          const float* in_tr, const float* out_tr, int target_mode, int act, float* params, float* m, float* v,
                          const int64_t* step0, const int32_t* idx, int64_t steps, int batch, float lr, float wd, float* loss_out,
                          int* route_out, void* stream) {
-  DynNet net;
-  if (int rc = dyn_net(sizes, n_sizes, net)) return rc;
-  return dfe_entry<false>(x, x_stride, y, y_stride, N, K, net, in_tr, out_tr, target_mode, act, params, m, v, step0, idx, steps,
-                          batch, lr, wd, loss_out, "MJX_DYN_FIT_ENS", dfe_serves(net, batch, target_mode), route_out, stream);
+  DfeCall c{};
+  if (int rc = dyn_net(sizes, n_sizes, c.net)) return rc;
+  c.x = x; c.x_stride = x_stride; c.y = y; c.y_stride = y_stride; c.N = N; c.K = K; c.in_tr = in_tr; c.out_tr = out_tr;
+  c.target_mode = target_mode; c.act = act; c.params = params; c.m = m; c.v = v; c.step0 = step0; c.idx = idx; c.steps = steps;
+  c.batch = batch; c.lr = lr; c.wd = wd; c.loss_out = loss_out; c.stream = stream;
+  return dfe_entry<false>(c, "MJX_DYN_FIT_ENS", dfe_serves(c.net, batch, target_mode), route_out);
 }
 
 // ---- ... with a team of workgroups per member (csrc/dyn_fit_ens_team.h; host side: csrc/fit_host.h dfe_team_run)
@@ -561,19 +563,18 @@ int mjx_dyn_fit_ensemble_team(const float* x, int64_t x_stride, const float* y, 
                               const float* in_tr, const float* out_tr, int target_mode, int act, float* params, float* m, float* v,
                               const int64_t* step0, const int32_t* idx, int64_t steps, int batch, float lr, float wd, float* loss_out,
                               int* route_out, void* stream) {
-  DynNet net;
-  if (int rc = dyn_net(sizes, n_sizes, net)) return rc;
+  DfeCall c{};
+  if (int rc = dyn_net(sizes, n_sizes, c.net)) return rc;
+  c.x = x; c.x_stride = x_stride; c.y = y; c.y_stride = y_stride; c.N = N; c.K = K; c.in_tr = in_tr; c.out_tr = out_tr;
+  c.target_mode = target_mode; c.act = act; c.params = params; c.m = m; c.v = v; c.step0 = step0; c.idx = idx; c.steps = steps;
+  c.batch = batch; c.lr = lr; c.wd = wd; c.loss_out = loss_out; c.stream = stream;
   // (both switches read per call; a shape or a switch that leaves no team: the call IS mjx_dyn_fit_ensemble)
-  const int G = env_flag("MJX_DYN_FIT_TEAM", true) && env_flag("MJX_DYN_FIT_ENS", true) ? dfe_team_serves(net, batch, target_mode, cu_count()) : 0;
-  if (!G)
-    return mjx_dyn_fit_ensemble(x, x_stride, y, y_stride, N, K, sizes, n_sizes, in_tr, out_tr, target_mode, act, params, m, v, step0, idx, steps,
-                                batch, lr, wd, loss_out, route_out, stream);
-  if (!dfe_args_ok(x, x_stride, y, y_stride, N, K, net, in_tr, out_tr, target_mode, act, params, m, v, step0, idx, steps, batch, loss_out))
-    return fail(MJX_ERR_ARG, "bad arguments");
+  const int G = env_flag("MJX_DYN_FIT_TEAM", true) && env_flag("MJX_DYN_FIT_ENS", true) ? dfe_team_serves(c.net, batch, target_mode, cu_count()) : 0;
+  if (!G) return dfe_entry<false>(c, "MJX_DYN_FIT_ENS", dfe_serves(c.net, batch, target_mode), route_out);
+  if (!dfe_args_ok(c)) return fail(MJX_ERR_ARG, "bad arguments");
   if (route_out) *route_out = 2;
   if (steps == 0) return MJX_OK;
-  return dfe_team_run(x, x_stride, y, y_stride, N, K, net, in_tr, out_tr, target_mode, act, params, m, v, step0, idx, steps, batch, lr, wd,
-                      loss_out, stream);
+  return dfe_team_run(c);
 }
 
 // ---- the reward nets of the whole ensemble (target mode 0: the loss runs through the output affine on raw r)
@@ -597,10 +598,12 @@ int mjx_reward_fit_ensemble(const float* x, int64_t x_stride, const float* y, in
                             int n_sizes, const float* in_tr, const float* out_tr, int act, float* params, float* m, float* v,
                             const int64_t* step0, const int32_t* idx, int64_t steps, int batch, float lr, float wd, float* loss_out,
                             int* route_out, void* stream) {
-  DynNet net;
-  if (int rc = dyn_net(sizes, n_sizes, net)) return rc;
-  return dfe_entry<true>(x, x_stride, y, y_stride, N, K, net, in_tr, out_tr, DYN_TGT_AFFINE, act, params, m, v, step0, idx, steps,
-                         batch, lr, wd, loss_out, "MJX_REWARD_FIT_ENS", reward_fit_serves(net, batch), route_out, stream);
+  DfeCall c{};
+  if (int rc = dyn_net(sizes, n_sizes, c.net)) return rc;
+  c.x = x; c.x_stride = x_stride; c.y = y; c.y_stride = y_stride; c.N = N; c.K = K; c.in_tr = in_tr; c.out_tr = out_tr;
+  c.target_mode = DYN_TGT_AFFINE; c.act = act; c.params = params; c.m = m; c.v = v; c.step0 = step0; c.idx = idx; c.steps = steps;
+  c.batch = batch; c.lr = lr; c.wd = wd; c.loss_out = loss_out; c.stream = stream;
+  return dfe_entry<true>(c, "MJX_REWARD_FIT_ENS", reward_fit_serves(c.net, batch), route_out);
 }
 
 int mjx_dyn_pred_error(const float* pred, int K, int64_t rows, int n, const float* s_next, const int64_t* seg_off, int nseg, double lim,

@@ -39,6 +39,15 @@ for env in ("0", "1"):
     clock("dyn_fit_ensemble_route" + env, lambda: check(lib.mjx_dyn_fit_ensemble(ptr(xs), N * 7, ptr(ys), N * 5, N, K, W.ints(sizes), 4, ptr(ti), ptr(to), 1, 1, ptr(P), ptr(m), ptr(v), s0,
                                                                                  ptr(idx), steps, B, 1e-4, 0.0, ptr(loss), ctypes.byref(route), st)))
 del os.environ["MJX_DYN_FIT_ENS"]
+clock("dyn_fit_ensemble_team_route2", lambda: check(lib.mjx_dyn_fit_ensemble_team(ptr(xs), N * 7, ptr(ys), N * 5, N, K, W.ints(sizes), 4, ptr(ti), ptr(to), 1, 1, ptr(P), ptr(m), ptr(v), s0,
+                                                                                  ptr(idx), steps, B, 1e-4, 0.0, ptr(loss), ctypes.byref(route), st)))
+assert route.value == 2, route.value
+rsizes = [7, 100, 100, 1]
+rP = up(rand_theta(rng, rsizes, K=K)); rm, rv = torch.zeros_like(rP), torch.zeros_like(rP)
+rtrs = np.stack([rand_tr(rng, 7, 1) for _ in range(K)]); rti, rto, rys = up(rtrs[:, :14]), up(rtrs[:, 14:]), up(rng.randn(K, N, 1))
+clock("reward_fit_ensemble_route1", lambda: check(lib.mjx_reward_fit_ensemble(ptr(xs), N * 7, ptr(rys), N, N, K, W.ints(rsizes), 4, ptr(rti), ptr(rto), 1, ptr(rP), ptr(rm), ptr(rv), s0,
+                                                                              ptr(idx), steps, B, 1e-4, 0.0, ptr(loss), ctypes.byref(route), st)))
+assert route.value == 1, route.value
 n, ep = 1000000, 2
 out = np.empty(n * ep, np.int32); rs = np.random.RandomState(0).get_state(); ts = []
 for r in range(14):

@@ -93,6 +93,24 @@ for which, sw, fn, szs, t0, tr_, y_, extra in (("ens", "MJX_DYN_FIT_ENS", lib.mj
         assert route.value == int(env), (which, env, route.value)
         save("%s_route%s" % (which, env), P, m, v, loss)
 
+# ---- the team ensemble fit (route 2), the smallest shape of each team size: G = 2 with one 32-unit tile a slice and padded d_in / d_out;
+# G = 4 with Bp 64 and 31 padded sample columns
+for name, tsizes, tB, G, mode, act in (("team_g2", [13, 64, 64, 11], 16, 2, 1, 1), ("team_g4", [13, 128, 128, 11], 33, 4, 2, 0)):
+    tK, tsteps, tN = 2, 5, 200
+    rng = np.random.RandomState(11 + G)
+    P = up(rand_theta(rng, tsizes, K=tK)); m, v = torch.zeros_like(P), torch.zeros_like(P)
+    ttr = np.stack([rand_tr(rng, 13, 11) for _ in range(tK)])
+    tx, ty = up(rng.randn(tK, tN, 13)), up(rng.randn(tK, tN, 11))
+    tidx = up(rng.randint(0, tN, size=(tK, tsteps * tB)), np.int32)
+    loss = torch.full((tK, tsteps), float("nan"), device=dev)
+    s0 = (ctypes.c_int64 * tK)(0, 3)
+    route = ctypes.c_int(-9)
+    assert lib.mjx_dyn_fit_team_route(W.ints(tsizes), 4, tB, mode, tK) == G, name
+    check(lib.mjx_dyn_fit_ensemble_team(ptr(tx), tN * 13, ptr(ty), tN * 11, tN, tK, W.ints(tsizes), 4, ptr(up(ttr[:, :26])), ptr(up(ttr[:, 26:])), mode, act,
+                                        ptr(P), ptr(m), ptr(v), s0, ptr(tidx), tsteps, tB, 1e-3, 1e-4, ptr(loss), ctypes.byref(route), W.stream()))
+    assert route.value == 2, (name, route.value)
+    save(name, P, m, v, loss)
+
 # ---- policy minibatch fit: H 64, H 32, the launch route; MSE, and PPO with an old net of its own
 for name, n, mm, hid, env in (("pol_h64", 11, 3, (64, 64), {}), ("pol_h32", 11, 3, (32, 32), {}), ("pol_launches", 11, 3, (64, 64), {"MJX_NO_POLICY_FIT": "1"})):
     Bp, st = 16, 3
