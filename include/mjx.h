@@ -326,6 +326,19 @@ int mjx_policy_minibatch_adam(mjx_ctx* ctx, int loss, const float* obs, const fl
  * (csrc/policy_fit.h), or {0, 0} = per-step launches (MJX_NO_POLICY_FIT=1, read per call, forces them).  Arithmetic only: no
  * device work and no runtime call. */
 int mjx_policy_fit_route(int n, int m, const int* hidden, int n_hidden, int B, int loss, int old_tracks_new, int32_t* out2);
+/* mjx_policy_minibatch_adam on a ladder of routes, for the policies its one-launch trainer does not take (more than 16 actions, or
+ * more observations than hidden units: the hand-manipulation shapes).  Same arguments and the same argument check; route_out
+ * (optional) receives the route that ran:  1 = k_policy_fit where mjx_policy_fit_route serves the shape;  2 = k_policy_fit_wide
+ * (csrc/policy_fit_wide.h: two equal hidden widths of 32 or 64, n <= 64, m <= 32, B in fours from 8 to 64, while its layout fits LDS);
+ * 0 = per-step launches.  A route whose LDS request the device refuses falls through to the next.  MJX_POLICY_FIT_WIDE=0 removes
+ * route 2, MJX_NO_POLICY_FIT=1 routes 1 and 2 (both read per call). */
+int mjx_policy_minibatch_adam_wide(mjx_ctx* ctx, int loss, const float* obs, const float* act, const float* adv, const int32_t* idx,
+                                   int64_t steps, int B, float* theta, const float* tr, const float* theta_old, const float* tr_old,
+                                   int old_tracks_new, float* adam_m, float* adam_v, int64_t step0, float lr, float clip,
+                                   double* loss_trace, void* stream, int* route_out);
+/* The ladder as arithmetic, under the same switches: out3 = {route, H, bytes of dynamic LDS}, {0, 0, 0} for the per-step launches.
+ * No device work and no runtime call. */
+int mjx_policy_fit_wide_route(int n, int m, const int* hidden, int n_hidden, int B, int loss, int old_tracks_new, int32_t* out3);
 
 /* Host-side gather for rollout ingestion: copies blocks [first, first + count) of a list of
  * per-trajectory arrays -- src[i] is rows(i) x row_bytes, C-contiguous -- to their place in one staging block,

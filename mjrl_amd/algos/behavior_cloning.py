@@ -10,9 +10,9 @@ import time as timer
 
 import numpy as np
 
-from .._lib import check, ptr
+from .._lib import ptr
 from ..engine import UpdateEngine
-from ..utils.ingest import minibatch_indices, upload
+from ..utils.ingest import fit_call, minibatch_indices, upload
 from ..utils.logger import DataLog
 
 LOSS_IDS = {"MSE": 0, "MLE": 1}
@@ -20,7 +20,7 @@ LOSS_IDS = {"MSE": 0, "MLE": 1}
 
 class BC:
     def __init__(self, expert_paths, policy, epochs=5, batch_size=64, lr=1e-3, optimizer=None, loss_type='MSE',
-                 save_logs=True, set_transforms=False, **kwargs):
+                 save_logs=True, set_transforms=False, wide_fit=False, **kwargs):
         if loss_type not in LOSS_IDS:
             raise ValueError("Please use valid loss type ('MSE' or 'MLE')")
         self.policy = policy
@@ -43,6 +43,10 @@ class BC:
             in_shift, in_scale, out_shift, out_scale = self.compute_transformations()
             self.set_transformations(in_shift, in_scale, out_shift, out_scale)
             self.set_variance_with_data(out_scale)
+        # wide_fit: the fit's one call goes to mjx_policy_minibatch_adam_wide (the route ladder with k_policy_fit_wide for policies of up
+        # to 64 observations and 32 actions); last_fit_route: the route that served the last fit (None: the default entry)
+        self.wide_fit = wide_fit
+        self.last_fit_route = None
         self._adam = None           # (m, v) device tensors + steps taken: the torch.optim.Adam state of the reference
 
     def _adopt_optimizer(self, opt):
@@ -145,9 +149,9 @@ class BC:
             if self._adam is None:
                 self._adam = [torch.zeros_like(theta), torch.zeros_like(theta), 0]
             didx = upload(eng.backend, idx)
-            check(eng.lib.mjx_policy_minibatch_adam(eng.ctx, LOSS_IDS[self.loss_type], ptr(obs), ptr(act), None, ptr(didx), steps,
-                                                    self.mb_size, ptr(theta), ptr(tr), None, None, 0, ptr(self._adam[0]),
-                                                    ptr(self._adam[1]), self._adam[2], self.lr, 0.0, None, eng.stream()))
+            args = (eng.ctx, LOSS_IDS[self.loss_type], ptr(obs), ptr(act), None, ptr(didx), steps, self.mb_size, ptr(theta), ptr(tr), None,
+                    None, 0, ptr(self._adam[0]), ptr(self._adam[1]), self._adam[2], self.lr, 0.0, None, eng.stream())
+            self.last_fit_route = fit_call(eng.lib, self.wide_fit, args)
             self._adam[2] += steps
             p.set_param_values(eng.to_host(theta), set_new=True, set_old=True)
             self._optimizer_state_out(torch)

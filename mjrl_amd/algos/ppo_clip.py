@@ -16,16 +16,18 @@ import time as timer
 
 import numpy as np
 
-from .._lib import check, ptr
-from ..utils.ingest import minibatch_indices, upload
+from .._lib import ptr
+from ..utils.ingest import fit_call, minibatch_indices, upload
 from ..utils.logger import DataLog
 from .batch_reinforce import BatchREINFORCE
 
 
 class PPO(BatchREINFORCE):
     def __init__(self, env, policy, baseline, clip_coef=0.2, epochs=10, mb_size=64, learn_rate=3e-4, seed=123,
-                 save_logs=False, reference_aliasing=True, **kwargs):
+                 save_logs=False, reference_aliasing=True, wide_fit=False, **kwargs):
         self.reference_aliasing = reference_aliasing
+        self.wide_fit = wide_fit            # the epochs go to mjx_policy_minibatch_adam_wide (see BC)
+        self.last_fit_route = None
         self.env = env
         self.policy = policy
         self.baseline = baseline
@@ -81,10 +83,10 @@ class PPO(BatchREINFORCE):
             # reference_aliasing: reproduce what the reference computes once its new / old network tensors share memory
             # (policies/gaussian_mlp.py set_param_values); False = the old policy stays fixed during the epochs
             track = int(bool(self.reference_aliasing and getattr(self.policy, "reference_new_old_alias", False)))
-            check(eng.lib.mjx_policy_minibatch_adam(eng.ctx, 2, ptr(obs_b), ptr(act_b), ptr(adv_b), ptr(didx), steps,
-                                                    self.mb_size, ptr(eng.theta_new), ptr(eng.tr_new), ptr(eng.theta_old),
-                                                    ptr(eng.tr_old), track, ptr(self._adam[0]), ptr(self._adam[1]), self._adam[2],
-                                                    self.learn_rate, self.clip_coef, None, eng.stream()))
+            args = (eng.ctx, 2, ptr(obs_b), ptr(act_b), ptr(adv_b), ptr(didx), steps, self.mb_size, ptr(eng.theta_new), ptr(eng.tr_new),
+                    ptr(eng.theta_old), ptr(eng.tr_old), track, ptr(self._adam[0]), ptr(self._adam[1]), self._adam[2], self.learn_rate,
+                    self.clip_coef, None, eng.stream())
+            self.last_fit_route = fit_call(eng.lib, self.wide_fit, args)
             self._adam[2] += steps
             eng.old_is_new = False
             eng._bind_policy()

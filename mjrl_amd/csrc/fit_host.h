@@ -1,4 +1,4 @@
-// fit_host.h -- host side of the baseline and minibatch trainers (baseline.h, mlp_fit.h, mlp_fit_team.h, dynamics.h, dyn_fit_ens.h, dyn_fit_ens_team.h, policy_fit.h):
+// fit_host.h -- host side of the baseline and minibatch trainers (baseline.h, mlp_fit.h, mlp_fit_team.h, dynamics.h, dyn_fit_ens.h, dyn_fit_ens_team.h, policy_fit.h, policy_fit_wide.h):
 // the feature-table cache, the routes of the ridge Gram, the MLP-baseline predict and fit and the policy minibatch fit as plain arithmetic, and
 // what acts on a route -- the bodies of the predict and fit entries; mjx.hip checks arguments and forwards.  Included by mjx.hip after model_host.h
 // (DynNet's helpers) and before update_host.h: the policy fit takes the pieces of mjx_ctx it uses as parameters.
@@ -227,6 +227,27 @@ inline PolicyFitRoute policy_fit_route(int n, int m, const std::vector<int>& hid
   const size_t bytes = 4 * (H == 64 ? PolicyFitLayout<64>(n, m).lds_floats(B, old_net) : PolicyFitLayout<32>(n, m).lds_floats(B, old_net));
   return bytes <= LDS_MAX ? PolicyFitRoute{H, bytes} : PolicyFitRoute{};
 }
+// the per-step route of both policy entries: gather, forward, loss head, backward and k_adam as launches of their own (`w`: the context's
+// workspace; trn / tro: the transforms, never null)
+inline int policy_fit_launches(int n, int m, int oS, int64_t d, MinibatchWS& w, int loss, const float* obs, const float* act, const float* adv,
+                               const int32_t* idx, int64_t steps, int B, float* theta, const float* trn, const float* theta_old, const float* tro,
+                               int old_tracks_new, float* adam_m, float* adam_v, int64_t step0, float lr, float clip, double* loss_trace,
+                               hipStream_t st) {
+  if (int rc = w.reserve(B)) return fail(rc, "minibatch workspace allocation failed");
+  const int64_t cnt = (loss == 0) ? (int64_t)oS : d;             // MSE: log_std has no gradient -> untouched (like torch's grad None)
+  const unsigned ggrid = capped_grid(B * (n > m ? n : m), 256, 1024);
+  for (int64_t s = 0; s < steps; ++s) {
+    const bool old_fwd = (loss == 2) && !old_tracks_new;
+    if (int rc = w.grad_step(loss, obs, act, adv, idx + s * B, B, theta, trn, theta_old, tro, old_fwd, clip,
+                             loss_trace ? loss_trace + s : (double*)nullptr, ggrid, st))
+      return fail(MJX_ERR_STATE, "minibatch backward failed (%d)", rc);
+    const AdamBias bc = adam_bias(ADAM_B1D, ADAM_B2D, step0 + s + 1);      // torch's constants, as k_policy_fit takes them (vecops.h)
+    hipLaunchKernelGGL(k_adam, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, theta, w.grad.p, adam_m, adam_v, cnt, lr, 0.f,
+                       ADAM_C1, ADAM_B2, ADAM_C2, ADAM_EPS, bc.bc1, bc.bc2s);
+  }
+  HIPCHK(lw_status());
+  return MJX_OK;
+}
 // mjx_policy_minibatch_adam behind its argument check, on the context's device: (n, m, hidden, ident_tr, oS, d) are the context's shape,
 // its identity transform (for a null tr / tr_old), the offset of log_std and the parameter count; `w` is its launch route's workspace
 inline int policy_fit(int n, int m, const std::vector<int>& hidden, const float* ident_tr, int oS, int64_t d, MinibatchWS& w, int loss,
@@ -246,20 +267,53 @@ inline int policy_fit(int n, int m, const std::vector<int>& hidden, const float*
     HIPCHK(hipGetLastError());
     return MJX_OK;
   }
-  if (int rc = w.reserve(B)) return fail(rc, "minibatch workspace allocation failed");
-  const int64_t cnt = (loss == 0) ? (int64_t)oS : d;             // MSE: log_std has no gradient -> untouched (like torch's grad None)
-  const unsigned ggrid = capped_grid(B * (n > m ? n : m), 256, 1024);
-  for (int64_t s = 0; s < steps; ++s) {
-    const bool old_fwd = (loss == 2) && !old_tracks_new;
-    if (int rc = w.grad_step(loss, obs, act, adv, idx + s * B, B, theta, trn, theta_old, tro, old_fwd, clip,
-                             loss_trace ? loss_trace + s : (double*)nullptr, ggrid, st))
-      return fail(MJX_ERR_STATE, "minibatch backward failed (%d)", rc);
-    const AdamBias bc = adam_bias(ADAM_B1D, ADAM_B2D, step0 + s + 1);      // torch's constants, as k_policy_fit takes them (vecops.h)
-    hipLaunchKernelGGL(k_adam, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, theta, w.grad.p, adam_m, adam_v, cnt, lr, 0.f,
-                       ADAM_C1, ADAM_B2, ADAM_C2, ADAM_EPS, bc.bc1, bc.bc2s);
+  return policy_fit_launches(n, m, oS, d, w, loss, obs, act, adv, idx, steps, B, theta, trn, theta_old, tro, old_tracks_new, adam_m, adam_v, step0, lr,
+                             clip, loss_trace, st);
+}
+
+// ---- ... for the manipulation-sized policies (policy_fit_wide.h): H = 64 or 32 twice, up to 64 observations and 32 actions, the same
+// minibatches; plain arithmetic over the kernel's own layout, H = 0: it does not serve (`off`: MJX_POLICY_FIT_WIDE=0 or MJX_NO_POLICY_FIT=1)
+inline PolicyFitRoute policy_fit_wide_route(int n, int m, const std::vector<int>& hidden, int B, int loss, int old_tracks_new, bool off) {
+  if (off || hidden.size() != 2 || hidden[0] != hidden[1] || (hidden[0] != 64 && hidden[0] != 32) || B % 4 || B < 8 || B > 64 || n < 1 ||
+      n > 64 || m < 1 || m > 32)
+    return {};
+  const int H = hidden[0]; const bool old_net = loss == 2 && !old_tracks_new;
+  const size_t bytes = 4 * (H == 64 ? PolicyFitWideLayout<64>(n, m).lds_floats(B, old_net) : PolicyFitWideLayout<32>(n, m).lds_floats(B, old_net));
+  return bytes <= LDS_MAX ? PolicyFitRoute{H, bytes} : PolicyFitRoute{};
+}
+// The ladder of mjx_policy_minibatch_adam_wide as arithmetic: 1 = k_policy_fit where policy_fit_route serves (the measured kernel for its
+// shapes), 2 = k_policy_fit_wide, 0 = per-step launches; `r`: H and bytes of route 1 or 2.  Both switches are read per call.
+inline int policy_fit_ladder(int n, int m, const std::vector<int>& hidden, int B, int loss, int old_tracks_new, int from, PolicyFitRoute& r) {
+  const bool no_fit = env_flag("MJX_NO_POLICY_FIT", false), wide_off = !env_flag("MJX_POLICY_FIT_WIDE", true);
+  if (from <= 1 && (r = policy_fit_route(n, m, hidden, B, loss, old_tracks_new, no_fit)).H) return 1;
+  if (from <= 2 && (r = policy_fit_wide_route(n, m, hidden, B, loss, old_tracks_new, no_fit || wide_off)).H) return 2;
+  r = PolicyFitRoute{};
+  return 0;
+}
+// mjx_policy_minibatch_adam_wide behind its argument check (parameters as policy_fit's): the ladder, where a route whose LDS request the
+// device refuses falls through to the next (launch_chained, model_host.h); the route that ran goes to route_out
+inline int policy_fit_wide(int n, int m, const std::vector<int>& hidden, const float* ident_tr, int oS, int64_t d, MinibatchWS& w, int loss,
+                           const float* obs, const float* act, const float* adv, const int32_t* idx, int64_t steps, int B, float* theta,
+                           const float* tr, const float* theta_old, const float* tr_old, int old_tracks_new, float* adam_m, float* adam_v,
+                           int64_t step0, float lr, float clip, double* loss_trace, void* stream, int* route_out) {
+  hipStream_t st = (hipStream_t)stream;
+  const float* trn = tr ? tr : ident_tr;
+  const float* tro = tr_old ? tr_old : ident_tr;
+  PolicyFitRoute r;
+  for (int from = 1; from <= 2; ++from) {
+    const int route = policy_fit_ladder(n, m, hidden, B, loss, old_tracks_new, from, r);
+    if (route == 0) break;
+    const PolicyFitArgs a{obs, act, adv, idx, steps, B, n, m, theta, theta_old, trn, tro, loss, old_tracks_new, adam_m, adam_v,
+                          step0, lr, clip, loss_trace, (int)(r.bytes / 4)};
+    void (*k)(PolicyFitArgs) = route == 1 ? (r.H == 64 ? k_policy_fit<64> : k_policy_fit<32>) : (r.H == 64 ? k_policy_fit_wide<64> : k_policy_fit_wide<32>);
+    bool launched = false;
+    if (int rc = launch_chained(k, r.bytes, dim3(1), a, st, launched, dim3(PFIT_THREADS))) return rc;
+    if (launched) { if (route_out) *route_out = route; return MJX_OK; }
+    from = route;                                                // (refused: the next rung)
   }
-  HIPCHK(lw_status());
-  return MJX_OK;
+  if (route_out) *route_out = 0;
+  return policy_fit_launches(n, m, oS, d, w, loss, obs, act, adv, idx, steps, B, theta, trn, theta_old, tro, old_tracks_new, adam_m, adam_v, step0, lr,
+                             clip, loss_trace, st);
 }
 
 // ---- dynamics fit of one member (dynamics.h) behind mjx_dyn_fit_adam's argument check, steps > 0: prep, then k_dyn_fit, the persistent

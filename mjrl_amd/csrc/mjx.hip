@@ -25,6 +25,7 @@
 #include "dyn_fit_ens_team.h"
 #include "fused_policy.h"
 #include "policy_fit.h"
+#include "policy_fit_wide.h"
 #include "rccl_dyn.h"
 #include "launch_state.h"
 #include "layerwise.h"
@@ -941,6 +942,29 @@ int mjx_policy_minibatch_adam(mjx_ctx* c, int loss, const float* obs, const floa
   HIPCHK(hipSetDevice(c->device));
   return policy_fit(c->n, c->m, c->hidden, c->ident_tr, c->oS, c->d, c->lwmb, loss, obs, act, adv, idx, steps, B, theta, tr, theta_old, tr_old,
                     old_tracks_new, adam_m, adam_v, step0, lr, clip, loss_trace, stream);
+}
+
+// the same call on the ladder k_policy_fit -> k_policy_fit_wide -> per-step launches (fit_host.h: policy_fit_wide)
+int mjx_policy_minibatch_adam_wide(mjx_ctx* c, int loss, const float* obs, const float* act, const float* adv, const int32_t* idx,
+                                   int64_t steps, int B, float* theta, const float* tr, const float* theta_old, const float* tr_old,
+                                   int old_tracks_new, float* adam_m, float* adam_v, int64_t step0, float lr, float clip,
+                                   double* loss_trace, void* stream, int* route_out) {
+  if (!c || loss < 0 || loss > 2 || steps < 0 || B <= 0 || step0 < 0) return fail(MJX_ERR_ARG, "bad arguments");
+  if (steps == 0) return MJX_OK;
+  if (!obs || !act || !idx || !theta || !adam_m || !adam_v) return fail(MJX_ERR_ARG, "null buffer");
+  if (loss == 2 && (!adv || !theta_old)) return fail(MJX_ERR_ARG, "PPO needs advantages and the old parameters");
+  HIPCHK(hipSetDevice(c->device));
+  return policy_fit_wide(c->n, c->m, c->hidden, c->ident_tr, c->oS, c->d, c->lwmb, loss, obs, act, adv, idx, steps, B, theta, tr, theta_old, tr_old,
+                         old_tracks_new, adam_m, adam_v, step0, lr, clip, loss_trace, stream, route_out);
+}
+
+int mjx_policy_fit_wide_route(int n, int m, const int* hidden, int n_hidden, int B, int loss, int old_tracks_new, int32_t* out3) {
+  if (!out3 || n <= 0 || m <= 0 || n_hidden < 0 || (n_hidden && !hidden) || B <= 0 || loss < 0 || loss > 2) return fail(MJX_ERR_ARG, "bad arguments");
+  for (int i = 0; i < n_hidden; ++i) if (hidden[i] <= 0) return fail(MJX_ERR_ARG, "bad hidden size");
+  PolicyFitRoute r;
+  out3[0] = policy_fit_ladder(n, m, std::vector<int>(hidden, hidden + n_hidden), B, loss, old_tracks_new, 1, r);
+  out3[1] = r.H; out3[2] = (int32_t)r.bytes;
+  return MJX_OK;
 }
 
 }  // extern "C"

@@ -81,6 +81,18 @@ def minibatch_indices(lib, num_samples, steps, mb_size):
     return out
 
 
+def fit_call(lib, wide, args):
+    """the one library call of BC.fit / PPO's epochs: mjx_policy_minibatch_adam(*args), or with `wide` its route ladder
+    mjx_policy_minibatch_adam_wide -> the route that served the fit (None for the default entry, which reports none)"""
+    if not wide:
+        check(lib.mjx_policy_minibatch_adam(*args))
+        return None
+    import ctypes
+    route = ctypes.c_int(-1)
+    check(lib.mjx_policy_minibatch_adam_wide(*args, ctypes.byref(route)))
+    return int(route.value)
+
+
 def collect_arrays(paths, key):
     """addresses and first dimensions of paths[.][key] -> (ptrs: (n,) uint64 ndarray, lens: (n,) int64 ndarray, width, itemsize), or
     None when the arrays are not uniform C-contiguous float32 / float64 blocks (the caller converts / copies them itself).  The
