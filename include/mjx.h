@@ -235,6 +235,26 @@ int mjx_peer_status(mjx_ctx* ctx, int* timeouts_out);
 int mjx_npg_update(mjx_ctx* ctx, int iters, float damping, double tol, double step_size, double const_alpha,
                    float min_log_std, float* grad_out, float* x_out, float* theta_out, double* results, void* stream);
 
+/* ---- the Gram route for LinearPolicy (no hidden layer; csrc/linear_policy.h) ----------------------------------
+ * With z = [x~ ; 1] the Hessian of mean_kl at theta_new == theta_old is a closed form in G = (1/N) sum z z^T, block diagonal per
+ * action: the update needs ONE pass over the batch (G, the gradient, the surrogate sums), a solve that never touches the batch,
+ * and one closing pass (surrogate / KL at the step) -- and one rank sum before the solve instead of one per CG iteration.
+ * What would serve a shape (arithmetic only): out4 = {route, NP, bytes of LDS of the two passes, rows per fp32 chain at the most};
+ * route 1 = the Gram route (n_hidden == 0, n <= 63, m <= 32; NP = n + 1 padded to 32 or 64), route 0 = everything else, all four
+ * outputs 0.  MJX_LINEAR_GRAM=0 (read per call) gives route 0.  MJX_ERR_ARG: null pointers, sizes <= 0. */
+int mjx_linear_route(int n, int m, const int* hidden, int n_hidden, int32_t* out4);
+/* Pass 1 alone on the bound batch and policy (needs old_is_new and a route-1 shape): block_out (device, NP NP + m NP + m + 4
+ * doubles) = [G (NP x NP) | g_[W|b] (m x NP: row j = d/dW_j, d/db_j, zeros) | g_log_std (m) | sum LR*adv, rows, 0, 0], local
+ * sums NOT divided by N.  fp32 sums run over at most 1024 rows; beyond that fp64 in a fixed order: two calls give the same bits. */
+int mjx_linear_moments(mjx_ctx* ctx, double* block_out, void* stream);
+/* mjx_npg_update on the Gram route: the same arguments, results, requirements and state on return; the CG runs in fp64 on the
+ * closed form.  *route_out (may be NULL) = 1.  With a transport attached: one rank sum of the moment block and one of K3's 4
+ * doubles.  Both policies are taken through tr_new (old_is_new: tr_old holds the same values).  Where the shape, the switch or
+ * the transport (a peer exchange whose slots cannot hold the block) leaves no Gram route the call IS mjx_npg_update, *route_out = 0. */
+int mjx_npg_update_linear(mjx_ctx* ctx, int iters, float damping, double tol, double step_size, double const_alpha,
+                          float min_log_std, float* grad_out, float* x_out, float* theta_out, double* results, void* stream,
+                          int32_t* route_out);
+
 /* The TRPO update with its backtracking line search on the device (mjrl/algos/trpo.py:100-126): K1, CG and
  * alpha = sqrt(|step_size / (grad.x + 1e-20)|) (step_size = 2 kl_dist, :103-104) as in mjx_npg_update when `first`, then
  * n_trials (1..24) line-search trials enqueued back to back: theta_out = theta_old + alpha x, K3 (rank sums as above), accept

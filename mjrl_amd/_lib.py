@@ -54,6 +54,11 @@ PROTOTYPES = {
     "mjx_peer_status": (c_int, [c_void_p, ctypes.POINTER(c_int)]),
     "mjx_npg_update": (c_int, [c_void_p, c_int, c_float, c_double, c_double, c_double, c_float, c_void_p, c_void_p, c_void_p, c_void_p,
                                c_void_p]),
+    # (LinearPolicy: route 1 = the Gram route of csrc/linear_policy.h, MJX_LINEAR_GRAM=0: mjx_npg_update itself)
+    "mjx_linear_route": (c_int, [c_int, c_int, ctypes.POINTER(c_int), c_int, ctypes.POINTER(ctypes.c_int32)]),
+    "mjx_linear_moments": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "mjx_npg_update_linear": (c_int, [c_void_p, c_int, c_float, c_double, c_double, c_double, c_float, c_void_p, c_void_p, c_void_p, c_void_p,
+                                      c_void_p, ctypes.POINTER(ctypes.c_int32)]),
     "mjx_trpo_update": (c_int, [c_void_p, c_int, c_float, c_double, c_double, c_double, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p,
                                 c_void_p, c_void_p]),
     "mjx_dapg_update": (c_int, [c_void_p, c_int, c_float, c_double, c_double, c_float, c_int64, c_int64, c_void_p, c_void_p, c_void_p,

@@ -23,7 +23,9 @@ class NPG(BatchREINFORCE):
     def __init__(self, env, policy, baseline, normalized_step_size=0.01, const_learn_rate=None,
                  FIM_invert_args={'iters': 10, 'damping': 1e-4}, hvp_sample_frac=1.0, seed=123, save_logs=False,
                  kl_dist=None, input_normalization=None, **kwargs):
-        """Arguments as in the reference (npg_cg.py:24-60)."""
+        """Arguments as in the reference (npg_cg.py:24-60), the signature too.  gram=True (through **kwargs, default False): a
+        LinearPolicy's one-call update goes to mjx_npg_update_linear (one pass for the second moments, the CG on the closed-form Fisher matrix; csrc/linear_policy.h);
+        last_update["route"] names what ran."""
         self.env = env
         self.policy = policy
         self.baseline = baseline
@@ -36,6 +38,7 @@ class NPG(BatchREINFORCE):
         self.running_score = None
         if save_logs:
             self.logger = DataLog()
+        self.gram = bool(kwargs.get('gram', False))
         self.input_normalization = input_normalization
         if self.input_normalization is not None and not (0 < self.input_normalization <= 1):
             self.input_normalization = None
@@ -132,19 +135,22 @@ class NPG(BatchREINFORCE):
         const_alpha = self.alpha is not None
         subsampled = self.hvp_subsample is not None and self.hvp_subsample < 0.99
         iters, damping = self.FIM_invert_args['iters'], self.FIM_invert_args['damping']
+        route = None
         if not subsampled and eng.old_is_new:
+            gram = dict(gram=True) if getattr(self, 'gram', False) else {}      # (the default call stays as it was)
             # The whole update in ONE call into libmjx (mjx_npg_update): K1, CG, step length formed on the device from g.x,
             # step, K3 -- rank sums included -- and one read-back.  (t_gLL / t_FIM cannot be told apart any more: the
             # gradient time is logged as 0, the solve time is the whole call.)
             t0 = timer.time()
             eng.npg_update(iters, damping, self.n_step_size, self.policy.min_log_std,
-                           const_alpha=self.alpha if const_alpha else None, enqueue_only=True)      # npg_cg.py:108-141
+                           const_alpha=self.alpha if const_alpha else None, enqueue_only=True, **gram)      # npg_cg.py:108-141
             # host work the update does not depend on runs under its device time: per-path return statistics, rollout log entries
             if stats_later is not None:
                 base_stats, stats_later = stats_later(), None
             if self.save_logs:
                 self.log_rollout_statistics(paths)
             surr_after, kl_dist = eng.npg_update_result()
+            route = getattr(eng, "last_route", None)
             t_gLL, t_FIM = 0.0, timer.time() - t0
         else:
             if stats_later is not None:
@@ -176,5 +182,5 @@ class NPG(BatchREINFORCE):
         if self.save_logs:
             self._log_update(paths, alpha, n_step_size, t_gLL, t_FIM, kl_dist, surr_before, surr_after)
         self.last_update = dict(alpha=float(alpha), kl_dist=kl_dist, surr_before=surr_before, surr_after=surr_after,
-                                gdotx=gdotx)
+                                gdotx=gdotx, route=route)
         return base_stats

@@ -29,6 +29,7 @@
 #include "rccl_dyn.h"
 #include "launch_state.h"
 #include "layerwise.h"
+#include "linear_policy.h"
 #include "mlp_fit.h"
 #include "mlp_fit_team.h"
 #include "path_reward.h"
@@ -68,7 +69,7 @@ int lds_limit(const void* kern, size_t bytes) {
   if (e) return fail(e, "dynamic LDS limit of %zu bytes: %s", bytes, hipGetErrorString((hipError_t)e));
   return MJX_OK;
 }
-enum ScratchSite { SITE_GRAM, SITE_MLP_PREDICT, SITE_MLP_FIT, SITE_MLP_FIT_WIDE, SITE_MLP_FIT_LAUNCHES, SITE_DYN_FIT, SITE_SUM_STATS, SITE_PLAN_ROLLOUT, SITE_PLAN_SCORE, SITE_DYN_FIT_ENS, SITE_PATH_REWARDS, SITE_POLICY_ROLLOUT, SITE_ROLLOUT_DISAGREE, SITE_MLP_FIT_TEAM };
+enum ScratchSite { SITE_GRAM, SITE_MLP_PREDICT, SITE_MLP_FIT, SITE_MLP_FIT_WIDE, SITE_MLP_FIT_LAUNCHES, SITE_DYN_FIT, SITE_SUM_STATS, SITE_PLAN_ROLLOUT, SITE_PLAN_SCORE, SITE_DYN_FIT_ENS, SITE_PATH_REWARDS, SITE_POLICY_ROLLOUT, SITE_ROLLOUT_DISAGREE, SITE_MLP_FIT_TEAM, SITE_LINEAR_GRAM };
 template <class T>
 int dev_scratch(ScratchSite site, void* stream, size_t bytes, T** out) {
   HIPCHK(mjx::scratch(site, (hipStream_t)stream, bytes, (void**)out));
@@ -801,6 +802,37 @@ int mjx_npg_update(mjx_ctx* c, int iters, float damping, double tol, double step
                               fin_step(base, theta_out, results + 9, step_size, const_alpha, min_log_std), stream)) return rc;
   if (int rc = bind_policy_impl(c, theta_out, c->theta_old, c->tr_new, c->tr_old, 0, true)) return rc;
   return eval_and_rank_sum(c, results, stream);
+}
+
+// ---- the Gram route of LinearPolicy (csrc/linear_policy.h; host side: csrc/update_host.h npg_update_gram)
+int mjx_linear_route(int n, int m, const int* hidden, int n_hidden, int32_t* out4) {
+  if (!out4 || n <= 0 || m <= 0 || n_hidden < 0 || (n_hidden > 0 && !hidden)) return fail(MJX_ERR_ARG, "bad arguments");
+  for (int i = 0; i < n_hidden; ++i) if (hidden[i] <= 0) return fail(MJX_ERR_ARG, "bad hidden size");
+  const LinRoute r = linear_route(n, m, n_hidden, env_flag("MJX_LINEAR_GRAM", true));
+  out4[0] = r.route; out4[1] = r.NP; out4[2] = (int32_t)r.lds; out4[3] = r.chain_rows;
+  return MJX_OK;
+}
+
+int mjx_linear_moments(mjx_ctx* c, double* block_out, void* stream) {
+  if (int rc = check_bound(c, true)) return rc;
+  if (!block_out) return fail(MJX_ERR_ARG, "null output");
+  if (!c->old_is_new) return fail(MJX_ERR_STATE, "mjx_linear_moments needs theta_new == theta_old (mjx_bind_policy with old_is_new)");
+  if (!linear_route(c->n, c->m, (int)c->hidden.size(), true).route) return fail(MJX_ERR_UNSUPPORTED, "not a shape of the Gram route (no hidden layer, n <= 63, m <= 32)");
+  HIPCHK(hipSetDevice(c->device));
+  LinPlan p;
+  if (int rc = lin_plan(c, stream, &p)) return rc;
+  return lin_moments(c, p, block_out, stream);
+}
+
+int mjx_npg_update_linear(mjx_ctx* c, int iters, float damping, double tol, double step_size, double const_alpha, float min_log_std,
+                          float* grad_out, float* x_out, float* theta_out, double* results, void* stream, int32_t* route_out) {
+  if (!c || !lin_serves(c)) {                       // (the switch, the shape or the transport leaves no Gram route: the call IS mjx_npg_update)
+    if (route_out) *route_out = 0;
+    return mjx_npg_update(c, iters, damping, tol, step_size, const_alpha, min_log_std, grad_out, x_out, theta_out, results, stream);
+  }
+  if (int rc = update_prologue(c, "mjx_npg_update_linear", grad_out && x_out && theta_out && results && iters >= 0, true, theta_out)) return rc;
+  if (route_out) *route_out = 1;
+  return npg_update_gram(c, iters, damping, tol, step_size, const_alpha, min_log_std, grad_out, x_out, theta_out, results, stream);
 }
 
 int mjx_trpo_update(mjx_ctx* c, int iters, float damping, double tol, double step_size, double kl_dist, int n_trials, int first,

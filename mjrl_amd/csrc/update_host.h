@@ -497,6 +497,100 @@ int vpg_then_solve(mjx_ctx* c, int iters, float damping, double tol, float* grad
   return cg_solve_impl(c, q);
 }
 
+// ---------------------------------------------------------------------------- the Gram route of LinearPolicy (linear_policy.h)
+// How the bound rows split into chains, and where the passes keep their partials: one scratch block per (thread, device, stream)
+// [moment block | per-chain doubles | per-chain slabs].  Every wave of the grid gets one chain; about 8 waves per CU before the
+// chains grow to their 32 tiles.  The split depends on the row count and the device alone.
+struct LinPlan {
+  LinLayout L; int chain_tiles; int64_t chains, count;
+  double *block, *ds; float* slab;
+};
+int lin_plan(mjx_ctx* c, void* stream, LinPlan* out) {
+  LinPlan p{LinLayout(c->n), 1, 0, 0, nullptr, nullptr, nullptr};
+  const int64_t tiles = (c->N_local + 31) / 32, target = 8 * (int64_t)cu_count();
+  const int64_t ct = (tiles + target - 1) / target;
+  p.chain_tiles = (int)(ct < 1 ? 1 : ct > LIN_CHAIN_TILES ? LIN_CHAIN_TILES : ct);
+  p.chains = (tiles + p.chain_tiles - 1) / p.chain_tiles;
+  p.count = p.L.block_count(c->m);
+  const size_t nd = (size_t)p.count + (size_t)p.chains * LIN_DS;
+  char* base = nullptr;
+  if (int rc = dev_scratch(SITE_LINEAR_GRAM, stream, nd * sizeof(double) + (size_t)p.chains * p.L.slab_floats() * sizeof(float), &base)) return rc;
+  p.block = (double*)base; p.ds = p.block + p.count; p.slab = (float*)(p.ds + (size_t)p.chains * LIN_DS);
+  *out = p;
+  return MJX_OK;
+}
+LinArgs lin_args(const mjx_ctx* c, const LinPlan& p) {
+  return LinArgs{c->obs, c->act, c->adv, c->N_local, c->n, c->m, c->theta_new, c->theta_old, c->tr_new ? c->tr_new : c->ident_tr,
+                 p.chain_tiles, p.chains, p.slab, p.ds};
+}
+unsigned lin_grid(const LinPlan& p) { return (unsigned)((p.chains + LIN_WAVES - 1) / LIN_WAVES); }
+
+// pass 1 on the bound batch and policy: the moment block (not divided by N) to block_out; a rank without rows writes zeros
+int lin_moments(mjx_ctx* c, const LinPlan& p, double* block_out, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  if (c->N_local == 0) {
+    hipLaunchKernelGGL(k_lin_zero, dim3((unsigned)((p.count + 255) / 256)), dim3(256), 0, st, block_out, p.count);
+    HIPCHK(hipGetLastError());
+    return MJX_OK;
+  }
+  const LinArgs a = lin_args(c, p);
+  if (p.L.NB == 1) hipLaunchKernelGGL(k_lin_moments<1>, dim3(lin_grid(p)), dim3(64 * LIN_WAVES), p.L.bytes(), st, a);
+  else hipLaunchKernelGGL(k_lin_moments<2>, dim3(lin_grid(p)), dim3(64 * LIN_WAVES), p.L.bytes(), st, a);
+  HIPCHK(hipGetLastError());
+  hipLaunchKernelGGL(k_lin_reduce, dim3((unsigned)((p.count + 15) / 16)), dim3(256), 0, st, (const float*)p.slab, (const double*)p.ds, p.chains,
+                     c->n, c->m, block_out);
+  HIPCHK(hipGetLastError());
+  return MJX_OK;
+}
+
+// the closing pass at (theta_new, theta_old) as bound: sum LR adv, sum KL, 0, 0 to res4
+int lin_eval(mjx_ctx* c, const LinPlan& p, double* res4, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  if (c->N_local == 0) {
+    hipLaunchKernelGGL(k_lin_zero, dim3(1), dim3(256), 0, st, res4, (int64_t)4);
+    HIPCHK(hipGetLastError());
+    return MJX_OK;
+  }
+  const LinArgs a = lin_args(c, p);
+  if (p.L.NB == 1) hipLaunchKernelGGL(k_lin_eval<1>, dim3(lin_grid(p)), dim3(64 * LIN_WAVES), p.L.bytes(), st, a);
+  else hipLaunchKernelGGL(k_lin_eval<2>, dim3(lin_grid(p)), dim3(64 * LIN_WAVES), p.L.bytes(), st, a);
+  HIPCHK(hipGetLastError());
+  hipLaunchKernelGGL(k_lin_eval_reduce, dim3(1), dim3(256), 0, st, (const double*)p.ds, p.chains, c->theta_new + c->oS, c->theta_old + c->oS, c->m,
+                     (double)c->N_local, res4);
+  HIPCHK(hipGetLastError());
+  return MJX_OK;
+}
+
+// Does the Gram route serve this context now?  The shape and the switch (MJX_LINEAR_GRAM, read per call), and a transport that
+// can carry the moment block: the peer exchange's slots hold d floats + 4 doubles, which the block outgrows.
+bool lin_serves(const mjx_ctx* c) {
+  if (!linear_route(c->n, c->m, (int)c->hidden.size(), env_flag("MJX_LINEAR_GRAM", true)).route) return false;
+  return c->tp.kind() != TP_PEER || (size_t)LinLayout(c->n).block_count(c->m) * sizeof(double) <= c->tp.layout().slot_bytes();
+}
+
+// The whole update on the Gram route: pass 1, ONE rank sum of the moment block, the solve, the closing pass and the rank sum of
+// its 4 doubles.  The context is left as mjx_npg_update leaves it.
+int npg_update_gram(mjx_ctx* c, int iters, float damping, double tol, double step_size, double const_alpha, float min_log_std,
+                    float* grad_out, float* x_out, float* theta_out, double* results, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  HIPCHK(hipSetDevice(c->device));
+  LinPlan p;
+  if (int rc = lin_plan(c, stream, &p)) return rc;
+  if (int rc = lin_moments(c, p, p.block, stream)) return rc;
+  if (c->tp.attached()) if (int rc = c->tp.allreduce(p.block, p.count, 1, stream)) return rc;
+  const LinSolveArgs s{p.block, c->n, c->m, iters, 1.0 / (double)c->N_global, (double)damping, tol, step_size, const_alpha, min_log_std,
+                       c->theta_old, c->tr_new ? c->tr_new : c->ident_tr, grad_out, x_out, theta_out, results};
+  const size_t bytes = p.L.solve_bytes(c->m);
+  if (int rc = lds_limit((const void*)k_lin_solve, bytes)) return rc;
+  hipLaunchKernelGGL(k_lin_solve, dim3(1), dim3(LIN_SOLVE_NT), bytes, st, s);
+  HIPCHK(hipGetLastError());
+  if (int rc = bind_policy_impl(c, theta_out, c->theta_old, c->tr_new, c->tr_old, 0, true)) return rc;
+  c->lw_old_ok = false;                          // (no layer-wise K1 ran: its output block does not hold the old policy's means)
+  if (int rc = lin_eval(c, p, results, stream)) return rc;
+  if (c->tp.attached()) if (int rc = c->tp.allreduce(results, 4, 1, stream)) return rc;
+  return MJX_OK;
+}
+
 }  // namespace
 
 #endif  // __HIPCC__

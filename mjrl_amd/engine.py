@@ -196,6 +196,14 @@ class HipBackend:
         check(self.lib.mjx_npg_update(self.ctx, int(iters), float(damping), float(tol), float(step_size), float("nan") if const_alpha is None else float(const_alpha),
                                       float(min_log_std), ptr(grad_out), ptr(x_out), ptr(theta_out), ptr(results), self.stream()))
 
+    def npg_update_linear(self, iters, damping, tol, step_size, const_alpha, min_log_std, grad_out, x_out, theta_out, results):
+        """mjx_npg_update_linear -> the route that ran (1: the Gram route of csrc/linear_policy.h, 0: mjx_npg_update itself)"""
+        route = ctypes.c_int32(-1)
+        check(self.lib.mjx_npg_update_linear(self.ctx, int(iters), float(damping), float(tol), float(step_size),
+                                             float("nan") if const_alpha is None else float(const_alpha), float(min_log_std), ptr(grad_out),
+                                             ptr(x_out), ptr(theta_out), ptr(results), self.stream(), ctypes.byref(route)))
+        return int(route.value)
+
     def trpo_update(self, iters, damping, tol, step_size, kl_dist, n_trials, first, min_log_std, grad_out, x_out, theta_out, results):
         check(self.lib.mjx_trpo_update(self.ctx, int(iters), float(damping), float(tol), float(step_size), float(kl_dist), int(n_trials),
                                        1 if first else 0, float(min_log_std), ptr(grad_out), ptr(x_out), ptr(theta_out), ptr(results),
@@ -552,7 +560,7 @@ class UpdateEngine:
         self.old_is_new = False
         self._bind_policy()
 
-    def npg_update(self, iters, damping, step_size, min_log_std, const_alpha=None, tol=1e-10, enqueue_only=False):
+    def npg_update(self, iters, damping, step_size, min_log_std, const_alpha=None, tol=1e-10, enqueue_only=False, gram=False):
         """The whole NPG update (npg_cg.py:108-142: K1, CG, step length, step, K3) enqueued by ONE call into libmjx
         (mjx_npg_update), rank sums included -> (surr_after, kl); deferred() has surr_before / g.x / alpha.
         Needs theta_new == theta_old at entry; the torch.distributed fallback path (no RCCL inside libmjx) issues the same
@@ -560,9 +568,15 @@ class UpdateEngine:
         does not depend on it (path statistics, log entries) under the 3.8 ms of device time and then asks npg_update_result()."""
         assert self.old_is_new, "npg_update starts from theta_new == theta_old"
         d = _dist()
+        self.last_route = None                      # what mjx_npg_update_linear ran; None: the entry was not used
         if (d is None or self._native_comm()) and hasattr(self.backend, "npg_update"):
             self._host_results = None
-            self.backend.npg_update(iters, damping, tol, step_size, const_alpha, min_log_std, self.grad, self.x, self.theta_new, self.results)
+            args = (iters, damping, tol, step_size, const_alpha, min_log_std, self.grad, self.x, self.theta_new, self.results)
+            if gram and not self.hidden and hasattr(self.backend, "npg_update_linear"):
+                # LinearPolicy, opt-in: one pass for the second moments, the CG on the closed-form Fisher matrix, one closing pass
+                self.last_route = self.backend.npg_update_linear(*args)
+            else:
+                self.backend.npg_update(*args)
             self.old_is_new = False
             self._npg_pending = True
             return None if enqueue_only else self.npg_update_result()

@@ -1,0 +1,105 @@
+#!/usr/bin/env python
+"""One NPG update of a LinearPolicy: route 1 of mjx_npg_update_linear (the Gram route, csrc/linear_policy.h: one pass for the second
+moments, the CG on the closed form, one closing pass) against route 0 (mjx_npg_update on the layer-wise path), one HIP-event pair
+around each update, MJX_LINEAR_GRAM alternating 1, 0 in one process, at
+    (6, 2) x 10 000 rows (configs[0])    (17, 6) x 1M rows    (63, 17) x 1M rows
+The child process runs under a time limit.  Prints one JSON line: per shape the microseconds of every update after the warm-up,
+their median and spread (max - min) per route, a second route-0 series (route 0 against itself: what two series of the same code
+differ by) and `wins` (route 1 beats route 0 by more than the largest spread).
+    python tools/bench_linear_gram.py [--passes 9] [--out FILE]"""
+import ctypes
+import json
+import os
+import subprocess
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+SHAPES = [(6, 2, 10000), (17, 6, 1000000), (63, 17, 1000000)]      # (n, m, rows)
+WARMUP = 3
+
+
+def arg(name, dflt):
+    return type(dflt)(sys.argv[sys.argv.index(name) + 1]) if name in sys.argv else dflt
+
+
+def child(passes):
+    import numpy as np
+    import torch
+    from mjrl_amd._lib import check, load, ptr
+    dev = torch.device("cuda", 0)
+    lib = load()
+    out = {}
+    for n, m, N in SHAPES:
+        rng = np.random.RandomState(3)
+        d = m * n + 2 * m
+        th = torch.as_tensor(np.concatenate([0.3 * rng.randn(m * n) / np.sqrt(n), 0.1 * rng.randn(m), np.full(m, -0.5)]).astype(np.float32)).to(dev)
+        obs = torch.randn(N, n, device=dev) * (1 + 2 * torch.rand(n, device=dev)) + torch.randn(n, device=dev)
+        act, adv = 0.7 * torch.randn(N, m, device=dev), torch.randn(N, device=dev)
+        tho = th.clone()
+        g, x, new = (torch.zeros(d, device=dev) for _ in range(3))
+        res = torch.zeros(16, dtype=torch.float64, device=dev)
+        ctx = ctypes.c_void_p()
+        check(lib.mjx_create(ctypes.byref(ctx), 0, n, m, (ctypes.c_int * 1)(), 0))
+        check(lib.mjx_bind_batch(ctx, ptr(obs), ptr(act), ptr(adv), N, N))
+        st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+        def update(switch):
+            os.environ["MJX_LINEAR_GRAM"] = switch
+            check(lib.mjx_bind_policy(ctx, ptr(th), ptr(tho), None, None, 1))
+            route = ctypes.c_int32(-1)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            e0.record()
+            check(lib.mjx_npg_update_linear(ctx, 10, 1e-4, 1e-10, 0.05, float("nan"), -3.0, ptr(g), ptr(x), ptr(new), ptr(res), st, ctypes.byref(route)))
+            e1.record()
+            e1.synchronize()
+            assert route.value == int(switch), route.value
+            return round(e0.elapsed_time(e1) * 1e3, 1), new.clone()
+
+        for _ in range(WARMUP):
+            a, b = update("1")[1], update("0")[1]
+        agree = float(((a - th) - (b - th)).norm() / (b - th).norm())
+        # recorded, not bounded: ten iterations on a handful of parameters run past convergence, where route 0's fp32 residuals
+        # are rounding noise that 1 / damping amplifies (tests/test_gpu_linear_gram.py prints both routes' distance to fp64)
+        assert agree == agree, agree
+        series = {"gram_us": [], "layerwise_us": [], "layerwise_again_us": []}
+        for _ in range(passes):
+            series["gram_us"].append(update("1")[0])
+            series["layerwise_us"].append(update("0")[0])
+            series["layerwise_again_us"].append(update("0")[0])
+        series["step_agreement"] = agree
+        out["n%d_m%d_N%d" % (n, m, N)] = series
+        torch.cuda.synchronize()
+        lib.mjx_destroy(ctx)
+    print("CHILD " + json.dumps(out), flush=True)
+
+
+def main():
+    passes = arg("--passes", 9)
+    out = {"passes": passes, "warmup": WARMUP}
+    p = subprocess.run(["timeout", "-k", "10", "240", sys.executable, os.path.abspath(__file__), "--child", "--passes", str(passes)],
+                       capture_output=True, text=True, cwd=ROOT)
+    line = [l for l in p.stdout.splitlines() if l.startswith("CHILD ")]
+    if p.returncode != 0 or not line:
+        out["failed"], out["log"] = p.returncode, (p.stdout + p.stderr)[-1500:]
+    else:
+        for name, b in json.loads(line[-1][6:]).items():
+            for key in ("gram_us", "layerwise_us", "layerwise_again_us"):
+                ts = sorted(b[key])
+                b[key + "_median"], b[key + "_spread"] = ts[len(ts) // 2], round(ts[-1] - ts[0], 1)
+            spread = max(b[k + "_spread"] for k in ("gram_us", "layerwise_us", "layerwise_again_us"))
+            b["wins"] = bool(b["layerwise_us_median"] - b["gram_us_median"] > max(spread, abs(b["layerwise_us_median"] - b["layerwise_again_us_median"])))
+            out[name] = b
+    print(json.dumps(out))
+    if "--out" in sys.argv:
+        json.dump(out, open(arg("--out", ""), "w"), indent=1)
+    sys.exit(1 if "failed" in out else 0)
+
+
+if __name__ == "__main__":
+    if "--child" in sys.argv:
+        child(arg("--passes", 9))
+    else:
+        main()
