@@ -281,6 +281,35 @@ int mjx_dapg_update(mjx_ctx* ctx, int iters, float damping, double tol, double s
                     int64_t N_on_global, const float* adv_on, float* grad_out, float* x_out, float* theta_out, double* results,
                     void* stream);
 
+/* ---- TRPO and DAPG on the Gram route for LinearPolicy (csrc/linear_policy.h) ------------------------------------
+ * The whole TRPO update in ONE call: pass 1 and the rank sum of the moment block as in mjx_npg_update_linear, then the solve
+ * kernel runs the CG and the reference's backtracking line search (up to max_trials = 100 trials, trpo.py:107-126) on the
+ * closed form of the mean KL, KL_t = sum_j [(out_scale_j^2 Delta_j^T G Delta_j + u_old,j - u_new,j) / (2 u_new,j + 1e-8) + ls_new,j
+ * - ls_old,j] with Delta = [W_t - W_old | b_t - b_old] taken from the fp32 parameters of the trial, never touching the batch; one
+ * closing pass at the final theta_out.  Needs old_is_new.  results (device, 64 doubles) as for mjx_trpo_update: [0] / [1] sum
+ * LR*adv / sum KL of the closing pass (what an agent logs), [9] step length of the last trial, [10] accepted, [11] trials
+ * performed, [12] the next step length, [17 + 2k] the closed-form KL of trial k x N_global at ring position k % 24 (the last 24
+ * trials), [16 + 2k] NaN: no trial's surrogate is evaluated.  The closed form decides; where it and the batch KL of [1] fall on
+ * different sides of kl_dist by rounding, the closed form stands.  After max_trials rejections theta_out holds the zero step.
+ * On return the context is bound as after an accepted mjx_trpo_update (NEW = theta_out).  *route_out (may be NULL) = 1; where
+ * the shape, MJX_LINEAR_GRAM=0 or the transport leaves no Gram route NOTHING is enqueued, *route_out = 0, and the caller runs
+ * mjx_trpo_update. */
+int mjx_trpo_update_linear(mjx_ctx* ctx, int iters, float damping, double tol, double step_size, double kl_dist, int max_trials,
+                           float min_log_std, float* grad_out, float* x_out, float* theta_out, double* results, void* stream,
+                           int32_t* route_out);
+/* Pass 1 alone as mjx_dapg_update_linear runs it (needs old_is_new and a route-1 shape): the bound rows as two segments, the
+ * on-policy prefix [0, rows_on) and the rows behind it.  block_out as for mjx_linear_moments, with G summed over the prefix only
+ * (the bits mjx_linear_moments gives on a batch bound to the prefix alone), the gradient and d log_std sums over all rows with
+ * the bound advantages, and [sum adv_on (device, rows_on floats), rows_on, 0, 0] behind them. */
+int mjx_linear_moments_segments(mjx_ctx* ctx, int64_t rows_on, const float* adv_on, double* block_out, void* stream);
+/* mjx_dapg_update on the Gram route: the same arguments, results and state on return.  Pass 1 runs as two row segments -- the
+ * on-policy prefix (G, gradient, sum adv_on) and the demonstrations (gradient only) --, the gradient is sum / N_all x (N_all /
+ * N_on) in fp64 (mjx_dapg_update: one fp32 product per element), G / N_on_global.  One rank sum of the moment block and one of
+ * the closing pass's 4 doubles.  *route_out (may be NULL) = 1; with no Gram route the call IS mjx_dapg_update, *route_out = 0. */
+int mjx_dapg_update_linear(mjx_ctx* ctx, int iters, float damping, double tol, double step_size, float min_log_std, int64_t rows_on,
+                           int64_t N_on_global, const float* adv_on, float* grad_out, float* x_out, float* theta_out, double* results,
+                           void* stream, int32_t* route_out);
+
 /* theta_out = theta + alpha * x, then log_std = max(log_std, min_log_std)
  * (npg_cg.py:137-139 + gaussian_mlp.py:73-75). */
 int mjx_apply_step(mjx_ctx* ctx, const float* theta, const float* x, float alpha,

@@ -63,6 +63,12 @@ PROTOTYPES = {
                                 c_void_p, c_void_p]),
     "mjx_dapg_update": (c_int, [c_void_p, c_int, c_float, c_double, c_double, c_float, c_int64, c_int64, c_void_p, c_void_p, c_void_p,
                                 c_void_p, c_void_p, c_void_p]),
+    # (TRPO / DAPG on the Gram route; route 0: the TRPO entry enqueues nothing, the DAPG entry is mjx_dapg_update)
+    "mjx_trpo_update_linear": (c_int, [c_void_p, c_int, c_float, c_double, c_double, c_double, c_int, c_float, c_void_p, c_void_p, c_void_p,
+                                       c_void_p, c_void_p, ctypes.POINTER(ctypes.c_int32)]),
+    "mjx_linear_moments_segments": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    "mjx_dapg_update_linear": (c_int, [c_void_p, c_int, c_float, c_double, c_double, c_float, c_int64, c_int64, c_void_p, c_void_p, c_void_p,
+                                       c_void_p, c_void_p, c_void_p, ctypes.POINTER(ctypes.c_int32)]),
     "mjx_apply_step": (c_int, [c_void_p, c_void_p, c_void_p, c_float, c_float, c_void_p, c_void_p]),
     "mjx_apply_npg_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_float, c_void_p, c_void_p, c_void_p]),
     "mjx_time_index": (c_int, [c_void_p, c_int64, c_void_p, c_void_p]),

@@ -18,7 +18,9 @@ class DAPG(NPG):
     def __init__(self, env, policy, baseline, demo_paths=None, normalized_step_size=0.01,
                  FIM_invert_args={'iters': 10, 'damping': 1e-4}, hvp_sample_frac=1.0, seed=123, save_logs=False,
                  kl_dist=None, lam_0=1.0, lam_1=0.95, **kwargs):
-        """Arguments as in the reference (dapg.py:26-52)."""
+        """Arguments as in the reference (dapg.py:26-52).  gram=True (through **kwargs, default False): a LinearPolicy's one-call
+        update goes to mjx_dapg_update_linear (csrc/linear_policy.h); last_update["route"] names what ran."""
+        self.gram = bool(kwargs.get('gram', False))
         self.env = env
         self.policy = policy
         self.baseline = baseline
@@ -71,8 +73,9 @@ class DAPG(NPG):
             # the whole update in ONE call into libmjx (mjx_dapg_update): K1 over all rows, gradient x N_all / N_on, the
             # on-policy prefix bound with its own advantages, K3, CG, step length, step, K3 -- one read-back
             t0 = timer.time()
+            gram = dict(gram=True) if getattr(self, 'gram', False) else {}      # (the default call stays as it was)
             res = eng.dapg_update(self.FIM_invert_args['iters'], self.FIM_invert_args['damping'], 2.0 * self.kl_dist,
-                                  self.policy.min_log_std, N, advantages, N_on_global=N_on_global)
+                                  self.policy.min_log_std, N, advantages, N_on_global=N_on_global, **gram)
             if res is not None:
                 surr_after, kl_dist = res
                 late = eng.deferred()
@@ -81,7 +84,7 @@ class DAPG(NPG):
                 if self.save_logs:
                     self._log_update(paths, alpha, 2.0 * self.kl_dist, 0.0, timer.time() - t0, kl_dist, surr_before, surr_after)
                 self.last_update = dict(alpha=float(alpha), kl_dist=kl_dist, surr_before=surr_before, surr_after=surr_after,
-                                        gdotx=gdotx)
+                                        gdotx=gdotx, route=getattr(eng, "last_route", None))
                 return base_stats
 
         t0 = timer.time()
@@ -105,5 +108,5 @@ class DAPG(NPG):
         if self.save_logs:
             self._log_update(paths, alpha, n_step_size, t_gLL, t_FIM, kl_dist, surr_before, surr_after)
         self.last_update = dict(alpha=float(alpha), kl_dist=kl_dist, surr_before=surr_before, surr_after=surr_after,
-                                gdotx=gdotx)
+                                gdotx=gdotx, route=None)
         return base_stats

@@ -15,7 +15,10 @@ from .npg_cg import NPG
 class TRPO(NPG):
     def __init__(self, env, policy, baseline, kl_dist=0.01, FIM_invert_args={'iters': 10, 'damping': 1e-4},
                  hvp_sample_frac=1.0, seed=123, save_logs=False, normalized_step_size=0.01, **kwargs):
-        """Arguments as in the reference (trpo.py:25-54)."""
+        """Arguments as in the reference (trpo.py:25-54).  gram=True (through **kwargs, default False): a LinearPolicy's one-call
+        update goes to mjx_trpo_update_linear (the line search decided on the closed-form KL; csrc/linear_policy.h);
+        last_update["route"] names what ran."""
+        self.gram = bool(kwargs.get('gram', False))
         self.env = env
         self.policy = policy
         self.baseline = baseline
@@ -44,18 +47,22 @@ class TRPO(NPG):
             # (torch.distributed fallback: the loop below.)
             t0 = timer.time()
             iters, damping = self.FIM_invert_args['iters'], self.FIM_invert_args['damping']
-            res = eng.trpo_update(iters, damping, 2.0 * self.kl_dist, self.kl_dist, self.policy.min_log_std)
+            gram = dict(gram=True) if getattr(self, 'gram', False) else {}      # (the default call stays as it was)
+            res = eng.trpo_update(iters, damping, 2.0 * self.kl_dist, self.kl_dist, self.policy.min_log_std, **gram)
             if res is not None:
                 late = eng.deferred()
                 surr_before, gdotx = late["surr_before"], late["gdotx"]
                 for (sa, klk) in (res["history"][:-1] if res["accepted"] else res["history"]):
-                    print("Step size too high. Backtracking. | kl = %f | surr diff = %f" % (klk, sa - surr_before))
+                    if sa != sa:                               # (the Gram route evaluates no rejected trial's surrogate)
+                        print("Step size too high. Backtracking. | kl = %f" % klk)
+                    else:
+                        print("Step size too high. Backtracking. | kl = %f | surr diff = %f" % (klk, sa - surr_before))
                 alpha, trials, surr_after, kl_dist = res["alpha"], res["trials"], res["surr_after"], res["kl"]
                 self.policy.set_param_values(eng.to_host(eng.theta_new), set_new=True, set_old=True)
                 if self.save_logs:
                     self._log_update(paths, alpha, 2.0 * self.kl_dist, 0.0, timer.time() - t0, kl_dist, surr_before, surr_after)
                 self.last_update = dict(alpha=float(alpha), kl_dist=kl_dist, surr_before=surr_before, surr_after=surr_after,
-                                        gdotx=gdotx, trials=trials)
+                                        gdotx=gdotx, trials=trials, route=getattr(eng, "last_route", None))
                 return base_stats
 
         t0 = timer.time()
@@ -88,5 +95,5 @@ class TRPO(NPG):
         if self.save_logs:
             self._log_update(paths, alpha, n_step_size, t_gLL, t_FIM, kl_dist, surr_before, surr_after)
         self.last_update = dict(alpha=float(alpha), kl_dist=kl_dist, surr_before=surr_before, surr_after=surr_after,
-                                gdotx=gdotx, trials=trials)
+                                gdotx=gdotx, trials=trials, route=None)
         return base_stats

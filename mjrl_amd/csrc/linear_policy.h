@@ -1,4 +1,4 @@
-// linear_policy.h -- the Gram route of the NPG update for LinearPolicy (no hidden layer; n <= 63 observations, m <= 32 actions).
+// linear_policy.h -- the Gram route of the NPG / TRPO / DAPG updates for LinearPolicy (no hidden layer; n <= 63 observations, m <= 32 actions).
 //
 // With z_i = [x~_i ; 1] (the normalised observation and a ones column) the Hessian of mean_kl at theta_new == theta_old depends on
 // the batch only through G = (1/N) sum_i z_i z_i^T: (F v)_[W|b] = diag(c) P G with c_j = 2 / (2 u_j + 1e-8) out_scale_j^2 and
@@ -31,6 +31,21 @@
 // The closing pass forwards [W_new | b_new] and the DIFFERENCE image [W_new - W_old | b_new - b_old] on the same Z tile: mu_old -
 // mu_new comes out of its own MFMA chain instead of the difference of two means (the KL is its square).  Both policies are taken
 // through tr_new: the route starts from old_is_new, where the two transforms hold the same values.
+//
+// TRPO and DAPG run on the same route (update_host.h trpo_update_gram / dapg_update_gram).
+//   DAPG  the gradient runs over [on-policy ; demonstration] rows, the metric over the on-policy prefix (dapg.py:97-103): pass 1
+//         is launched as two row SEGMENTS into one slab / ds array, on-policy chains first.  k_lin_moments<NB, true> takes rows
+//         [0, rows_on); k_lin_moments<NB, false> -- the same tile loop without the Gram steps, only the gradient blocks of its
+//         slab written -- takes the rows behind them on offset pointers with its own row count, so its tiles start at row rows_on
+//         whatever that is modulo 32 and its last tile is zero-filled behind the segment's end.  Each segment's chain split is the
+//         rule above applied to its own row count: no chain straddles the boundary.  k_lin_reduce sums the G elements over the
+//         on-policy chains only (the order above over those chains), everything else over all chains.  The surrogate slot holds
+//         sum adv_on (LinArgs::adv_sum: the whitened on-policy advantages, not the first rows_on bound ones), the rows slot N_on.
+//         The solve divides G by N_on and forms the gradient as sum / N_all x (N_all / N_on) in fp64; mjx_dapg_update applies
+//         that factor as one fp32 product per element -- 6e-8 relative, inside TOL_VPG / TOL_STEP.
+//   TRPO  the mean KL of a trial step is a closed form in G, so k_lin_solve<LIN_SOLVE_TRPO> decides all of the reference's 100
+//         backtracking trials in LDS behind the CG (the comment there); k_lin_eval runs once, at the final theta_out.  Its batch
+//         KL is what is logged; where it and the closed form disagree about kl_dist by rounding, the closed form stands.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -82,6 +97,7 @@ struct LinArgs {
   int64_t chains;
   float* slab;                               // pass 1: chains x slab_floats
   double* ds;                                // pass 1: chains x LIN_DS; closing pass: chains x 4
+  const float* adv_sum = nullptr;            // pass 1, optional: the vector whose sum goes to the surrogate-sum slot (null: adv)
 };
 
 __device__ __forceinline__ float lin_sum32(float v) {        // every lane: the sum over its 32-lane half
@@ -162,7 +178,9 @@ __device__ __forceinline__ void lin_write_tile(float* Z, const LinLayout L, cons
 }
 
 // ---------------------------------------------------------------------------- pass 1
-template <int NB>
+// GRAM = false (a row segment that feeds the gradient only -- DAPG's demonstrations): the same tile loop without the G00 / G01 /
+// G11 steps; only the gradient blocks of the slab are written, and the chain's surrogate-sum and row-count slots hold 0.
+template <int NB, bool GRAM = true>
 __global__ __launch_bounds__(64 * LIN_WAVES) void k_lin_moments(const LinArgs a) {
   extern __shared__ float lin_lds[];
   constexpr int LE = 16 * NB;                         // 32 n / 64 loads per lane: n <= 31 -> 16, n <= 63 -> 32
@@ -182,11 +200,13 @@ __global__ __launch_bounds__(64 * LIN_WAVES) void k_lin_moments(const LinArgs a)
   const int64_t tile1 = tile0 + a.chain_tiles < tiles ? tile0 + a.chain_tiles : tiles;
 
   f32x16 G00 = (f32x16)(0.f), G01 = (f32x16)(0.f), G11 = (f32x16)(0.f), gA0 = (f32x16)(0.f), gA1 = (f32x16)(0.f);
-  double gls = 0.0, sadv = 0.0;
+  double gls = 0.0, sadv = 0.0, sadv2 = 0.0;
   LinTile<LE> t;
   lin_load_tile(t, a, tile0 * 32, lane);
   for (int64_t tile = tile0; tile < tile1; ++tile) {
     const int64_t row0 = tile * 32;
+    // (adv_sum: row `lane` of the tile, one coalesced load, added behind the MFMAs below)
+    const float w2 = (GRAM && a.adv_sum && lane < 32 && row0 + lane < a.N) ? a.adv_sum[row0 + lane] : 0.f;
     lin_write_tile(Z, L, vec, t, a, row0, lane, row_l, f_l, q64, r64);
     wave_sync();
     // forward
@@ -222,36 +242,49 @@ __global__ __launch_bounds__(64 * LIN_WAVES) void k_lin_moments(const LinArgs a)
       for (int r = 0; r < 4; ++r) {
         const float* zc = &Z[(8 * q + 4 * hi + r) * L.S + j];
         const float z0 = zc[0];
-        G00 = MJX_MFMA(z0, z0, G00);
+        if (GRAM) G00 = MJX_MFMA(z0, z0, G00);
         gA0 = MJX_MFMA(z0, D[4 * q + r], gA0);
         if (NB == 2) {
           const float z1 = zc[32];
-          G01 = MJX_MFMA(z0, z1, G01);
-          G11 = MJX_MFMA(z1, z1, G11);
+          if (GRAM) { G01 = MJX_MFMA(z0, z1, G01); G11 = MJX_MFMA(z1, z1, G11); }
           gA1 = MJX_MFMA(z1, D[4 * q + r], gA1);
         }
       }
     }
+    sadv2 += (double)w2;
     wave_sync();
   }
   // the chain's register images
   float* sl = a.slab + chain * L.slab_floats() + lane;
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
-    sl[(0 * 16 + r) * 64] = G00[r];
+    if (GRAM) sl[(0 * 16 + r) * 64] = G00[r];
     if (NB == 1) sl[(1 * 16 + r) * 64] = gA0[r];
-    else { sl[(1 * 16 + r) * 64] = G01[r]; sl[(2 * 16 + r) * 64] = G11[r]; sl[(3 * 16 + r) * 64] = gA0[r]; sl[(4 * 16 + r) * 64] = gA1[r]; }
+    else {
+      if (GRAM) { sl[(1 * 16 + r) * 64] = G01[r]; sl[(2 * 16 + r) * 64] = G11[r]; }
+      sl[(3 * 16 + r) * 64] = gA0[r]; sl[(4 * 16 + r) * 64] = gA1[r];
+    }
   }
   double* ds = a.ds + chain * LIN_DS;
   ds[lane] = gls;
-  if (j == 0) ds[64 + hi] = sadv;
+  if (!GRAM) {
+    if (lane < 4) ds[64 + lane] = 0.0;
+    return;
+  }
+  if (a.adv_sum) {                                   // (uniform: every lane of the wave takes the same side)
+    const double s2 = wave_sum(sadv2);
+    if (lane < 2) ds[64 + lane] = lane == 0 ? s2 : 0.0;
+  } else if (j == 0) {
+    ds[64 + hi] = sadv;
+  }
   if (lane == 0) { const int64_t r1 = tile1 * 32 < a.N ? tile1 * 32 : a.N; ds[66] = (double)(r1 - tile0 * 32); ds[67] = 0.0; }
 }
 
 // block[e] = the fp64 sum over the chains of what the slabs hold for element e: 16 elements x 16 chain groups per workgroup, a
-// group adds its chains in chain order, then the groups are added in order
-__global__ __launch_bounds__(256) void k_lin_reduce(const float* __restrict__ slab, const double* __restrict__ ds, int64_t chains, int n, int m,
-                                                    double* __restrict__ block) {
+// group adds its chains in chain order, then the groups are added in order.  The G elements are summed over the first chains_g
+// chains only (a segmented pass: the chains of the GRAM = true segment come first; otherwise chains_g == chains).
+__global__ __launch_bounds__(256) void k_lin_reduce(const float* __restrict__ slab, const double* __restrict__ ds, int64_t chains, int64_t chains_g,
+                                                    int n, int m, double* __restrict__ block) {
   __shared__ double sh[16][17];
   const LinLayout L(n);
   const int el = threadIdx.x & 15, grp = threadIdx.x >> 4;
@@ -271,7 +304,8 @@ __global__ __launch_bounds__(256) void k_lin_reduce(const float* __restrict__ sl
     }
     const int off = (blk * 16 + (i & 3) + 4 * (i >> 3)) * 64 + 32 * ((i >> 2) & 1) + jj;      // register, lane half, column
     const size_t SL = (size_t)L.slab_floats();
-    for (int64_t c = grp; c < chains; c += 16) acc += (double)slab[c * SL + off];
+    const int64_t cn = e < nG ? chains_g : chains;
+    for (int64_t c = grp; c < cn; c += 16) acc += (double)slab[c * SL + off];
   } else if (e < cnt) {
     const int k = (int)(e - nA);
     for (int64_t c = grp; c < chains; c += 16) {
@@ -299,6 +333,22 @@ __global__ void k_lin_zero(double* p, int64_t count) {
 // One workgroup: cg_solve.py:3-22 in fp64 with A p = [diag(c) P G | s .* p_log_std] + damping p (G and g divided by N here),
 // then g.x, the step length and the stepped parameters as k_apply_npg_step / k_apply_step form them.  Vectors are kept in the
 // padded layout [m x NP | m]; a padded column meets zero rows of G and a zero gradient and stays exactly 0.
+//
+// MODE LIN_SOLVE_DAPG: the gradient is the block's sum / N_all x (N_all / N_on) in fp64 (dapg.py:97-98; mjx_dapg_update forms the
+// quotient in fp64 too but applies it as one fp32 product per element: a relative 6e-8 apart, inside TOL_VPG = 3e-6), G / N_on.
+//
+// MODE LIN_SOLVE_TRPO: TRPO's backtracking line search (trpo.py:107-126) behind the CG, without the batch.  mu_old - mu_new =
+// out_scale .* (Delta z) with Delta = [W_new - W_old | b_new - b_old], so the mean KL of a trial is
+//   KL_t = sum_j [(out_scale_j^2 Delta_j^T G Delta_j + u_old,j - u_new,j) / (2 u_new,j + 1e-8) + ls_new,j - ls_old,j],  u = exp(ls)^2
+// (gaussian_mlp.py:135-145).  Trial t: every thread forms its padded elements of theta_t = step_add(theta, (float)alpha_t,
+// (float)x) with the clamp -- the fp32 values the epilogue would store -- and leaves Delta (fp64, exact) in the CG's r; after a
+// barrier element (j, k) forms (Delta_j G)_k Delta_jk / (2 u_new,j + 1e-8) out_scale_j^2 like the CG's P G product, a log_std
+// element its three terms, and one block_sum gives KL_t to every thread.  KL_t < kl_dist accepts; else alpha <- 0.9 alpha (fp64,
+// cast per trial: what k_trpo_try / k_trpo_check carry).  After max_trials rejections the step is zero.  results[9..12] and the
+// ring are mjx_trpo_update's ([17 + 2 (k % 24)] = KL_t x N_global: a sum, like a K3 pass leaves there); the surrogate slots
+// [16 + 2 (k % 24)] hold NaN (no trial's surrogate is evaluated).  The closing pass at the final theta_out gives the batch KL
+// that is logged; where it and KL_t disagree about kl_dist by rounding, the closed form has decided.
+enum { LIN_SOLVE_NPG = 0, LIN_SOLVE_TRPO = 1, LIN_SOLVE_DAPG = 2 };
 struct LinSolveArgs {
   const double* block;
   int n, m, iters;
@@ -307,8 +357,12 @@ struct LinSolveArgs {
   const float *theta, *tr;
   float *grad_out, *x_out, *theta_out;
   double* results;
+  double g_scale = 0.0;                                      // DAPG: 1 / N_all x (N_all / N_on), what the gradient sums are multiplied by
+  double kl_dist = 0.0, N_global = 0.0;                      // TRPO
+  int max_trials = 0;
 };
 
+template <int MODE>
 __global__ __launch_bounds__(LIN_SOLVE_NT) void k_lin_solve(const LinSolveArgs a) {
   extern __shared__ double lin_sol[];
   const LinLayout L(a.n);
@@ -317,7 +371,7 @@ __global__ __launch_bounds__(LIN_SOLVE_NT) void k_lin_solve(const LinSolveArgs a
   double* cv = z + E; double* sv = cv + 32; double* sh = sv + 32;
   for (int i = tid; i < NP * NP; i += LIN_SOLVE_NT) G[i] = a.block[i] * a.inv_N;
   for (int e = tid; e < E; e += LIN_SOLVE_NT) {
-    const double g = a.block[NP * NP + e] * a.inv_N;
+    const double g = a.block[NP * NP + e] * (MODE == LIN_SOLVE_DAPG ? a.g_scale : a.inv_N);
     gv[e] = g; x[e] = 0.0; r[e] = g; p[e] = g;
   }
   if (tid < m) {
@@ -356,9 +410,57 @@ __global__ __launch_bounds__(LIN_SOLVE_NT) void k_lin_solve(const LinSolveArgs a
   const double gx = dot(gv, x);
   const bool npg = a.const_alpha != a.const_alpha;
   const double a64 = npg ? sqrt(fabs(a.step_size / (gx + 1e-20))) : a.const_alpha;
-  const float alpha = (float)a64;
+  float alpha = (float)a64;
   if (tid == 0) { a.results[8] = gx; if (npg) a.results[9] = a64; }
   if (tid < 4) a.results[4 + tid] = a.block[L.block_count(m) - 4 + tid];
+  if (MODE == LIN_SOLVE_TRPO) {
+    // r: Delta (log_std elements: the new log_std itself); cv: out_scale^2; sv: 1 / (2 u_new + 1e-8) of the trial
+    double* dl = r;
+    __syncthreads();
+    if (tid < m) { const double osc = (double)a.tr[2 * n + m + tid]; cv[tid] = osc * osc; }
+    double at = a64, tried = a64;
+    int trials = 0;
+    bool accepted = false;
+    while (trials < a.max_trials && !accepted) {
+      const float af = (float)at;
+      for (int e = tid; e < E; e += LIN_SOLVE_NT) {
+        if (e < MN) {
+          const int act = e / NP, k = e - act * NP;
+          double d = 0.0;
+          if (k <= n) {
+            const float th = a.theta[k < n ? act * n + k : oB + act];
+            d = (double)step_add(th, af, (float)x[e]) - (double)th;
+          }
+          dl[e] = d;
+        } else {
+          const double ln = (double)fmaxf(step_add(a.theta[oS + e - MN], af, (float)x[e]), a.min_log_std), sg = exp(ln);
+          dl[e] = ln;
+          sv[e - MN] = 1.0 / (2.0 * sg * sg + 1e-8);
+        }
+      }
+      __syncthreads();
+      double s = 0.0;
+      for (int e = tid; e < E; e += LIN_SOLVE_NT) {
+        if (e < MN) {
+          const int act = e / NP, k = e - act * NP;
+          double q = 0.0;
+          for (int kk = 0; kk < NP; ++kk) q += dl[act * NP + kk] * G[kk * NP + k];
+          s += cv[act] * sv[act] * (q * dl[e]);
+        } else {
+          const double lo = (double)a.theta[oS + e - MN], so = exp(lo), sn = exp(dl[e]);
+          s += (so * so - sn * sn) * sv[e - MN] + dl[e] - lo;
+        }
+      }
+      const double kl = block_sum(s, sh);               // (every thread holds the same sum; its barriers also free dl / sv for the next trial)
+      if (tid == 0) { a.results[16 + 2 * (trials % 24)] = nan(""); a.results[17 + 2 * (trials % 24)] = kl * a.N_global; }
+      ++trials;
+      tried = at;
+      if (kl < a.kl_dist) accepted = true;
+      else at = 0.9 * at;
+    }
+    alpha = accepted ? (float)tried : 0.f;
+    if (tid == 0) { a.results[9] = tried; a.results[10] = accepted ? 1.0 : 0.0; a.results[11] = (double)trials; a.results[12] = at; }
+  }
   for (int e = tid; e < E; e += LIN_SOLVE_NT) {
     int i;
     if (e < MN) {

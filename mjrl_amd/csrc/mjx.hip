@@ -879,6 +879,41 @@ int mjx_dapg_update(mjx_ctx* c, int iters, float damping, double tol, double ste
   return eval_and_rank_sum(c, results, stream);
 }
 
+// ---- TRPO and DAPG on the Gram route of LinearPolicy (host side: csrc/update_host.h trpo_update_gram / dapg_update_gram)
+int mjx_trpo_update_linear(mjx_ctx* c, int iters, float damping, double tol, double step_size, double kl_dist, int max_trials, float min_log_std,
+                           float* grad_out, float* x_out, float* theta_out, double* results, void* stream, int32_t* route_out) {
+  if (int rc = update_prologue(c, "mjx_trpo_update_linear", grad_out && x_out && theta_out && results && iters >= 0 && max_trials >= 1, true, theta_out)) return rc;
+  const bool gram = lin_serves(c);                  // (no Gram route: nothing is enqueued, the caller runs mjx_trpo_update)
+  if (route_out) *route_out = gram ? 1 : 0;
+  if (!gram) return MJX_OK;
+  return trpo_update_gram(c, iters, damping, tol, step_size, kl_dist, max_trials, min_log_std, grad_out, x_out, theta_out, results, stream);
+}
+
+int mjx_linear_moments_segments(mjx_ctx* c, int64_t rows_on, const float* adv_on, double* block_out, void* stream) {
+  if (int rc = check_bound(c, true)) return rc;
+  if (!block_out || rows_on < 0 || rows_on > c->N_local || (!adv_on && rows_on > 0)) return fail(MJX_ERR_ARG, "bad arguments");
+  if (!c->old_is_new) return fail(MJX_ERR_STATE, "mjx_linear_moments_segments needs theta_new == theta_old (mjx_bind_policy with old_is_new)");
+  if (!linear_route(c->n, c->m, (int)c->hidden.size(), true).route) return fail(MJX_ERR_UNSUPPORTED, "not a shape of the Gram route (no hidden layer, n <= 63, m <= 32)");
+  HIPCHK(hipSetDevice(c->device));
+  LinPlan p; LinSplit t;
+  if (int rc = lin_plan_rows(c, rows_on, c->N_local - rows_on, stream, &p, &t)) return rc;
+  return lin_moments_segments(c, p, t, rows_on, adv_on, block_out, stream);
+}
+
+int mjx_dapg_update_linear(mjx_ctx* c, int iters, float damping, double tol, double step_size, float min_log_std, int64_t rows_on,
+                           int64_t N_on_global, const float* adv_on, float* grad_out, float* x_out, float* theta_out, double* results,
+                           void* stream, int32_t* route_out) {
+  if (!c || !lin_serves(c)) {                       // (the call IS mjx_dapg_update)
+    if (route_out) *route_out = 0;
+    return mjx_dapg_update(c, iters, damping, tol, step_size, min_log_std, rows_on, N_on_global, adv_on, grad_out, x_out, theta_out, results, stream);
+  }
+  if (int rc = update_prologue(c, "mjx_dapg_update_linear", grad_out && x_out && theta_out && results && (adv_on || rows_on <= 0) && iters >= 0,
+                               true, theta_out)) return rc;
+  if (rows_on < 0 || rows_on > c->N_local || N_on_global <= 0 || N_on_global > c->N_global) return fail(MJX_ERR_ARG, "bad on-policy row counts");
+  if (route_out) *route_out = 1;
+  return dapg_update_gram(c, iters, damping, tol, step_size, min_log_std, rows_on, N_on_global, adv_on, grad_out, x_out, theta_out, results, stream);
+}
+
 int mjx_apply_step(mjx_ctx* c, const float* theta, const float* x, float alpha, float min_log_std, float* theta_out, void* stream) {
   if (!c || !theta || !x || !theta_out) return fail(MJX_ERR_ARG, "bad arguments");
   hipLaunchKernelGGL(k_apply_step, dim3((c->d + 255) / 256), dim3(256), 0, (hipStream_t)stream, theta, x, alpha, min_log_std,

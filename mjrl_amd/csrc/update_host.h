@@ -505,20 +505,30 @@ struct LinPlan {
   LinLayout L; int chain_tiles; int64_t chains, count;
   double *block, *ds; float* slab;
 };
-int lin_plan(mjx_ctx* c, void* stream, LinPlan* out) {
-  LinPlan p{LinLayout(c->n), 1, 0, 0, nullptr, nullptr, nullptr};
-  const int64_t tiles = (c->N_local + 31) / 32, target = 8 * (int64_t)cu_count();
+// a row segment's chain split: a function of its row count and the device alone
+struct LinSplit { int chain_tiles; int64_t chains; };
+LinSplit lin_split(int64_t rows) {
+  const int64_t tiles = (rows + 31) / 32, target = 8 * (int64_t)cu_count();
   const int64_t ct = (tiles + target - 1) / target;
-  p.chain_tiles = (int)(ct < 1 ? 1 : ct > LIN_CHAIN_TILES ? LIN_CHAIN_TILES : ct);
-  p.chains = (tiles + p.chain_tiles - 1) / p.chain_tiles;
+  const int chain_tiles = (int)(ct < 1 ? 1 : ct > LIN_CHAIN_TILES ? LIN_CHAIN_TILES : ct);
+  return LinSplit{chain_tiles, (tiles + chain_tiles - 1) / chain_tiles};
+}
+// the plan of the first `rows` bound rows; *tail (may be NULL): the split of the `rows_tail` rows behind them, whose chains'
+// slabs and doubles follow the plan's own in the same scratch block
+int lin_plan_rows(mjx_ctx* c, int64_t rows, int64_t rows_tail, void* stream, LinPlan* out, LinSplit* tail) {
+  LinPlan p{LinLayout(c->n), 1, 0, 0, nullptr, nullptr, nullptr};
+  const LinSplit s = lin_split(rows), t = lin_split(rows_tail);
+  p.chain_tiles = s.chain_tiles; p.chains = s.chains;
   p.count = p.L.block_count(c->m);
-  const size_t nd = (size_t)p.count + (size_t)p.chains * LIN_DS;
+  const size_t all = (size_t)(s.chains + t.chains), nd = (size_t)p.count + all * LIN_DS;
   char* base = nullptr;
-  if (int rc = dev_scratch(SITE_LINEAR_GRAM, stream, nd * sizeof(double) + (size_t)p.chains * p.L.slab_floats() * sizeof(float), &base)) return rc;
-  p.block = (double*)base; p.ds = p.block + p.count; p.slab = (float*)(p.ds + (size_t)p.chains * LIN_DS);
+  if (int rc = dev_scratch(SITE_LINEAR_GRAM, stream, nd * sizeof(double) + all * p.L.slab_floats() * sizeof(float), &base)) return rc;
+  p.block = (double*)base; p.ds = p.block + p.count; p.slab = (float*)(p.ds + all * LIN_DS);
   *out = p;
+  if (tail) *tail = t;
   return MJX_OK;
 }
+int lin_plan(mjx_ctx* c, void* stream, LinPlan* out) { return lin_plan_rows(c, c->N_local, 0, stream, out, nullptr); }
 LinArgs lin_args(const mjx_ctx* c, const LinPlan& p) {
   return LinArgs{c->obs, c->act, c->adv, c->N_local, c->n, c->m, c->theta_new, c->theta_old, c->tr_new ? c->tr_new : c->ident_tr,
                  p.chain_tiles, p.chains, p.slab, p.ds};
@@ -538,7 +548,7 @@ int lin_moments(mjx_ctx* c, const LinPlan& p, double* block_out, void* stream) {
   else hipLaunchKernelGGL(k_lin_moments<2>, dim3(lin_grid(p)), dim3(64 * LIN_WAVES), p.L.bytes(), st, a);
   HIPCHK(hipGetLastError());
   hipLaunchKernelGGL(k_lin_reduce, dim3((unsigned)((p.count + 15) / 16)), dim3(256), 0, st, (const float*)p.slab, (const double*)p.ds, p.chains,
-                     c->n, c->m, block_out);
+                     p.chains, c->n, c->m, block_out);
   HIPCHK(hipGetLastError());
   return MJX_OK;
 }
@@ -568,11 +578,25 @@ bool lin_serves(const mjx_ctx* c) {
   return c->tp.kind() != TP_PEER || (size_t)LinLayout(c->n).block_count(c->m) * sizeof(double) <= c->tp.layout().slot_bytes();
 }
 
+// What every update of the route ends with: the solve on the (rank-summed) moment block, theta_out bound as the NEW parameters,
+// the closing pass on the rows bound now and the rank sum of its 4 doubles.
+template <int MODE>
+int lin_solve_and_close(mjx_ctx* c, const LinPlan& p, const LinSolveArgs& s, void* stream) {
+  const size_t bytes = p.L.solve_bytes(c->m);
+  if (int rc = lds_limit((const void*)k_lin_solve<MODE>, bytes)) return rc;
+  hipLaunchKernelGGL(k_lin_solve<MODE>, dim3(1), dim3(LIN_SOLVE_NT), bytes, (hipStream_t)stream, s);
+  HIPCHK(hipGetLastError());
+  if (int rc = bind_policy_impl(c, s.theta_out, c->theta_old, c->tr_new, c->tr_old, 0, true)) return rc;
+  c->lw_old_ok = false;                          // (no layer-wise K1 ran: its output block does not hold the old policy's means)
+  if (int rc = lin_eval(c, p, s.results, stream)) return rc;
+  if (c->tp.attached()) if (int rc = c->tp.allreduce(s.results, 4, 1, stream)) return rc;
+  return MJX_OK;
+}
+
 // The whole update on the Gram route: pass 1, ONE rank sum of the moment block, the solve, the closing pass and the rank sum of
 // its 4 doubles.  The context is left as mjx_npg_update leaves it.
 int npg_update_gram(mjx_ctx* c, int iters, float damping, double tol, double step_size, double const_alpha, float min_log_std,
                     float* grad_out, float* x_out, float* theta_out, double* results, void* stream) {
-  hipStream_t st = (hipStream_t)stream;
   HIPCHK(hipSetDevice(c->device));
   LinPlan p;
   if (int rc = lin_plan(c, stream, &p)) return rc;
@@ -580,15 +604,70 @@ int npg_update_gram(mjx_ctx* c, int iters, float damping, double tol, double ste
   if (c->tp.attached()) if (int rc = c->tp.allreduce(p.block, p.count, 1, stream)) return rc;
   const LinSolveArgs s{p.block, c->n, c->m, iters, 1.0 / (double)c->N_global, (double)damping, tol, step_size, const_alpha, min_log_std,
                        c->theta_old, c->tr_new ? c->tr_new : c->ident_tr, grad_out, x_out, theta_out, results};
-  const size_t bytes = p.L.solve_bytes(c->m);
-  if (int rc = lds_limit((const void*)k_lin_solve, bytes)) return rc;
-  hipLaunchKernelGGL(k_lin_solve, dim3(1), dim3(LIN_SOLVE_NT), bytes, st, s);
+  return lin_solve_and_close<LIN_SOLVE_NPG>(c, p, s, stream);
+}
+
+// TRPO on the route: the same two passes; the solve kernel decides the whole line search on the closed-form KL (linear_policy.h).
+// The context is left as an accepted mjx_trpo_update leaves it (after max_trials rejections: theta_out == theta_old in value).
+int trpo_update_gram(mjx_ctx* c, int iters, float damping, double tol, double step_size, double kl_dist, int max_trials, float min_log_std,
+                     float* grad_out, float* x_out, float* theta_out, double* results, void* stream) {
+  HIPCHK(hipSetDevice(c->device));
+  LinPlan p;
+  if (int rc = lin_plan(c, stream, &p)) return rc;
+  if (int rc = lin_moments(c, p, p.block, stream)) return rc;
+  if (c->tp.attached()) if (int rc = c->tp.allreduce(p.block, p.count, 1, stream)) return rc;
+  LinSolveArgs s{p.block, c->n, c->m, iters, 1.0 / (double)c->N_global, (double)damping, tol, step_size, std::nan(""), min_log_std,
+                 c->theta_old, c->tr_new ? c->tr_new : c->ident_tr, grad_out, x_out, theta_out, results};
+  s.kl_dist = kl_dist; s.N_global = (double)c->N_global; s.max_trials = max_trials;
+  return lin_solve_and_close<LIN_SOLVE_TRPO>(c, p, s, stream);
+}
+
+// Pass 1 as two row segments into one slab / ds array (DAPG): the on-policy prefix [0, rows_on) of the bound rows with the Gram
+// steps and sum adv_on in its surrogate slot, the demonstrations [rows_on, N) on offset pointers without them; each segment's
+// chains follow lin_split of its own row count, so no chain straddles the boundary and G has the bits mjx_linear_moments gives
+// on the prefix alone.  p / t: lin_plan_rows(rows_on, N - rows_on).  The moment block (local sums) to block_out.
+int lin_moments_segments(mjx_ctx* c, const LinPlan& p, const LinSplit& t, int64_t rows_on, const float* adv_on, double* block_out, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t rows_demo = c->N_local - rows_on;
+  const float* tr = c->tr_new ? c->tr_new : c->ident_tr;
+  const size_t SL = (size_t)p.L.slab_floats();
+  if (rows_on > 0) {
+    const LinArgs a{c->obs, c->act, c->adv, rows_on, c->n, c->m, c->theta_new, c->theta_old, tr, p.chain_tiles, p.chains, p.slab, p.ds, adv_on};
+    if (p.L.NB == 1) hipLaunchKernelGGL((k_lin_moments<1, true>), dim3(lin_grid(p)), dim3(64 * LIN_WAVES), p.L.bytes(), st, a);
+    else hipLaunchKernelGGL((k_lin_moments<2, true>), dim3(lin_grid(p)), dim3(64 * LIN_WAVES), p.L.bytes(), st, a);
+    HIPCHK(hipGetLastError());
+  }
+  if (rows_demo > 0) {
+    const LinArgs a{c->obs + rows_on * c->n, c->act + rows_on * c->m, c->adv + rows_on, rows_demo, c->n, c->m, c->theta_new, c->theta_old, tr,
+                    t.chain_tiles, t.chains, p.slab + (size_t)p.chains * SL, p.ds + (size_t)p.chains * LIN_DS};
+    const unsigned grid = (unsigned)((t.chains + LIN_WAVES - 1) / LIN_WAVES);
+    if (p.L.NB == 1) hipLaunchKernelGGL((k_lin_moments<1, false>), dim3(grid), dim3(64 * LIN_WAVES), p.L.bytes(), st, a);
+    else hipLaunchKernelGGL((k_lin_moments<2, false>), dim3(grid), dim3(64 * LIN_WAVES), p.L.bytes(), st, a);
+    HIPCHK(hipGetLastError());
+  }
+  // (a rank without rows: no chains, every sum of the reduction is empty -- zeros)
+  hipLaunchKernelGGL(k_lin_reduce, dim3((unsigned)((p.count + 15) / 16)), dim3(256), 0, st, (const float*)p.slab, (const double*)p.ds,
+                     p.chains + t.chains, p.chains, c->n, c->m, block_out);
   HIPCHK(hipGetLastError());
-  if (int rc = bind_policy_impl(c, theta_out, c->theta_old, c->tr_new, c->tr_old, 0, true)) return rc;
-  c->lw_old_ok = false;                          // (no layer-wise K1 ran: its output block does not hold the old policy's means)
-  if (int rc = lin_eval(c, p, results, stream)) return rc;
-  if (c->tp.attached()) if (int rc = c->tp.allreduce(results, 4, 1, stream)) return rc;
   return MJX_OK;
+}
+
+// DAPG on the route: the segmented pass 1, ONE rank sum of the moment block, the solve (gradient x N_all / N_on, G / N_on), the
+// on-policy prefix bound, the closing pass and its rank sum.  The context is left as mjx_dapg_update leaves it.
+int dapg_update_gram(mjx_ctx* c, int iters, float damping, double tol, double step_size, float min_log_std, int64_t rows_on,
+                     int64_t N_on_global, const float* adv_on, float* grad_out, float* x_out, float* theta_out, double* results, void* stream) {
+  HIPCHK(hipSetDevice(c->device));
+  const int64_t N_all_global = c->N_global;
+  LinPlan p; LinSplit t;
+  if (int rc = lin_plan_rows(c, rows_on, c->N_local - rows_on, stream, &p, &t)) return rc;
+  if (int rc = lin_moments_segments(c, p, t, rows_on, adv_on, p.block, stream)) return rc;
+  if (c->tp.attached()) if (int rc = c->tp.allreduce(p.block, p.count, 1, stream)) return rc;
+  LinSolveArgs s{p.block, c->n, c->m, iters, 1.0 / (double)N_on_global, (double)damping, tol, step_size, std::nan(""), min_log_std,
+                 c->theta_old, c->tr_new ? c->tr_new : c->ident_tr, grad_out, x_out, theta_out, results};
+  s.g_scale = 1.0 / (double)N_all_global * ((double)N_all_global / (double)N_on_global);
+  // Fisher metric, surrogate and KL: the on-policy prefix with its own advantages (dapg.py:92, :103)
+  if (int rc = mjx_bind_rows(c, rows_on, N_on_global, adv_on)) return rc;
+  return lin_solve_and_close<LIN_SOLVE_DAPG>(c, p, s, stream);
 }
 
 }  // namespace

@@ -209,6 +209,22 @@ class HipBackend:
                                        1 if first else 0, float(min_log_std), ptr(grad_out), ptr(x_out), ptr(theta_out), ptr(results),
                                        self.stream()))
 
+    def trpo_update_linear(self, iters, damping, tol, step_size, kl_dist, max_trials, min_log_std, grad_out, x_out, theta_out, results):
+        """mjx_trpo_update_linear -> the route that ran (1: the whole update is enqueued, line search included; 0: nothing is)"""
+        route = ctypes.c_int32(-1)
+        check(self.lib.mjx_trpo_update_linear(self.ctx, int(iters), float(damping), float(tol), float(step_size), float(kl_dist), int(max_trials),
+                                              float(min_log_std), ptr(grad_out), ptr(x_out), ptr(theta_out), ptr(results), self.stream(),
+                                              ctypes.byref(route)))
+        return int(route.value)
+
+    def dapg_update_linear(self, iters, damping, tol, step_size, min_log_std, rows_on, N_on_global, adv_on, grad_out, x_out, theta_out, results):
+        """mjx_dapg_update_linear -> the route that ran (1: the Gram route, 0: mjx_dapg_update itself)"""
+        route = ctypes.c_int32(-1)
+        check(self.lib.mjx_dapg_update_linear(self.ctx, int(iters), float(damping), float(tol), float(step_size), float(min_log_std),
+                                              int(rows_on), int(N_on_global), ptr(adv_on), ptr(grad_out), ptr(x_out), ptr(theta_out),
+                                              ptr(results), self.stream(), ctypes.byref(route)))
+        return int(route.value)
+
     def dapg_update(self, iters, damping, tol, step_size, min_log_std, rows_on, N_on_global, adv_on, grad_out, x_out, theta_out, results):
         check(self.lib.mjx_dapg_update(self.ctx, int(iters), float(damping), float(tol), float(step_size), float(min_log_std),
                                        int(rows_on), int(N_on_global), ptr(adv_on), ptr(grad_out), ptr(x_out), ptr(theta_out),
@@ -599,21 +615,26 @@ class UpdateEngine:
         s = self._host_results = self._checked(self.results.cpu().numpy())
         return float(s[0] / self.N_global), float(s[1] / self.N_global)
 
-    def dapg_update(self, iters, damping, step_size, min_log_std, rows_on, adv_on, N_on_global=None, tol=1e-10):
+    def dapg_update(self, iters, damping, step_size, min_log_std, rows_on, adv_on, N_on_global=None, tol=1e-10, gram=False):
         """The whole DAPG update (dapg.py:92-121) through ONE call into libmjx (mjx_dapg_update), rank sums included: K1
         over the bound [on-policy ; demonstrations] block, gradient x N_all / N_on, the on-policy prefix bound with its
         whitened advantages `adv_on`, K3 (surr_before), CG, step length from step_size = 2 kl_dist, step, K3 ->
         (surr_after, kl); deferred() has surr_before / g.x / alpha.  None when the one-call path is not available
-        (torch.distributed fallback): the caller issues the sequence itself."""
+        (torch.distributed fallback): the caller issues the sequence itself.  gram (LinearPolicy, opt-in): mjx_dapg_update_linear,
+        last_route names what ran."""
         assert self.old_is_new, "dapg_update starts from theta_new == theta_old"
         d = _dist()
+        self.last_route = None
         if not ((d is None or self._native_comm()) and hasattr(self.backend, "dapg_update")):
             return None
         adv_dev = self.to_device_f32(adv_on)
         N_on_global = self.global_count(rows_on) if N_on_global is None else int(N_on_global)
         self._host_results = None
-        self.backend.dapg_update(iters, damping, tol, step_size, min_log_std, rows_on, N_on_global, adv_dev, self.grad, self.x,
-                                 self.theta_new, self.results)
+        args = (iters, damping, tol, step_size, min_log_std, rows_on, N_on_global, adv_dev, self.grad, self.x, self.theta_new, self.results)
+        if gram and not self.hidden and hasattr(self.backend, "dapg_update_linear"):
+            self.last_route = self.backend.dapg_update_linear(*args)
+        else:
+            self.backend.dapg_update(*args)
         self.adv = adv_dev
         self.N_global, self.N_bound = N_on_global, int(rows_on)
         self._prefix = (int(rows_on), N_on_global, adv_dev)
@@ -621,18 +642,35 @@ class UpdateEngine:
         s = self._host_results = self._checked(self.results.cpu().numpy())
         return float(s[0] / self.N_global), float(s[1] / self.N_global)
 
-    def trpo_update(self, iters, damping, step_size, kl_dist, min_log_std, tol=1e-10, batch=3, max_trials=100):
+    def trpo_update(self, iters, damping, step_size, kl_dist, min_log_std, tol=1e-10, batch=3, max_trials=100, gram=False):
         """The whole TRPO update (trpo.py:100-126: K1, CG, step length, backtracking line search on the KL) through libmjx's
         mjx_trpo_update: the line-search trials are enqueued `batch` at a time with the accept / shrink decision taken on the
         device, one read-back per batch (the call-by-call form reads back after every trial) -> dict(alpha, trials, accepted,
         surr_after, kl, history=[(surr, kl) per trial]); deferred() has surr_before / g.x.  The search runs to the reference's
         100 trials on the device (batches of 3, 6, 12, 24, 24, ... trials per read-back); when none is accepted the zero step
         is applied and evaluated like the reference does (accepted = False, alpha = 0).  None when the one-call path is not
-        available (torch.distributed fallback): the caller runs the loop itself."""
+        available (torch.distributed fallback): the caller runs the loop itself.  gram (LinearPolicy, opt-in): the whole update,
+        all trials included, is ONE call and one read-back (mjx_trpo_update_linear: the trials are decided on the closed-form KL,
+        so the history's surrogates are NaN except the accepted trial's); last_route names what ran."""
         assert self.old_is_new, "trpo_update starts from theta_new == theta_old"
         d = _dist()
+        self.last_route = None
         if not ((d is None or self._native_comm()) and hasattr(self.backend, "trpo_update")):
             return None
+        if gram and not self.hidden and hasattr(self.backend, "trpo_update_linear"):
+            self._host_results = None
+            self.last_route = self.backend.trpo_update_linear(iters, damping, tol, step_size, kl_dist, max_trials, min_log_std, self.grad, self.x,
+                                                              self.theta_new, self.results)
+            if self.last_route == 1:
+                self.old_is_new = False
+                s = self._host_results = self._checked(self.results.cpu().numpy())
+                trials, accepted = int(s[11]), s[10] != 0.0
+                hist = [(float("nan"), float(s[17 + 2 * (k % 24)] / self.N_global)) for k in range(max(0, trials - 24), trials)]
+                surr_after, kl = float(s[0] / self.N_global), float(s[1] / self.N_global)
+                if accepted:
+                    hist[-1] = (surr_after, hist[-1][1])
+                return dict(alpha=float(s[9]) if accepted else 0.0, trials=trials, accepted=bool(accepted), surr_after=surr_after, kl=kl,
+                            history=hist)
         first, hist, done = True, [], 0
         while True:
             self._host_results = None

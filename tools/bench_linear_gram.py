@@ -6,7 +6,10 @@ around each update, MJX_LINEAR_GRAM alternating 1, 0 in one process, at
 The child process runs under a time limit.  Prints one JSON line: per shape the microseconds of every update after the warm-up,
 their median and spread (max - min) per route, a second route-0 series (route 0 against itself: what two series of the same code
 differ by) and `wins` (route 1 beats route 0 by more than the largest spread).
-    python tools/bench_linear_gram.py [--passes 9] [--out FILE]"""
+--mode trpo: one TRPO update (kl_dist 0.025) -- route 1 is ONE mjx_trpo_update_linear call (the line search inside the solve), route 0
+what a caller runs when that entry reports route 0: mjx_trpo_update with its first batch of 3 trials.  --mode dapg: one DAPG update
+with 5 000 demonstration rows behind the on-policy rows, mjx_dapg_update_linear on either side of the switch.
+    python tools/bench_linear_gram.py [--mode npg|trpo|dapg] [--passes 9] [--out FILE]"""
 import ctypes
 import json
 import os
@@ -18,13 +21,14 @@ sys.path.insert(0, ROOT)
 
 SHAPES = [(6, 2, 10000), (17, 6, 1000000), (63, 17, 1000000)]      # (n, m, rows)
 WARMUP = 3
+DEMO_ROWS, KL_DIST = 5000, 0.025
 
 
 def arg(name, dflt):
     return type(dflt)(sys.argv[sys.argv.index(name) + 1]) if name in sys.argv else dflt
 
 
-def child(passes):
+def child(passes, mode):
     import numpy as np
     import torch
     from mjrl_amd._lib import check, load, ptr
@@ -35,24 +39,36 @@ def child(passes):
         rng = np.random.RandomState(3)
         d = m * n + 2 * m
         th = torch.as_tensor(np.concatenate([0.3 * rng.randn(m * n) / np.sqrt(n), 0.1 * rng.randn(m), np.full(m, -0.5)]).astype(np.float32)).to(dev)
-        obs = torch.randn(N, n, device=dev) * (1 + 2 * torch.rand(n, device=dev)) + torch.randn(n, device=dev)
-        act, adv = 0.7 * torch.randn(N, m, device=dev), torch.randn(N, device=dev)
+        rows = N + (DEMO_ROWS if mode == "dapg" else 0)
+        obs = torch.randn(rows, n, device=dev) * (1 + 2 * torch.rand(n, device=dev)) + torch.randn(n, device=dev)
+        act, adv = 0.7 * torch.randn(rows, m, device=dev), torch.randn(rows, device=dev)
+        if mode == "dapg":                             # dapg.py:62-70: 1e-2 [adv / std ; lam_0 lam_1^iter], the whitened advantages apart
+            adv_on = adv[:N].clone()
+            adv = 1e-2 * torch.cat([adv_on / (adv_on.std() + 1e-8), torch.ones(DEMO_ROWS, device=dev)])
         tho = th.clone()
         g, x, new = (torch.zeros(d, device=dev) for _ in range(3))
-        res = torch.zeros(16, dtype=torch.float64, device=dev)
+        res = torch.zeros(64, dtype=torch.float64, device=dev)
         ctx = ctypes.c_void_p()
         check(lib.mjx_create(ctypes.byref(ctx), 0, n, m, (ctypes.c_int * 1)(), 0))
-        check(lib.mjx_bind_batch(ctx, ptr(obs), ptr(act), ptr(adv), N, N))
         st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+        out4 = (ptr(g), ptr(x), ptr(new), ptr(res), st)
 
         def update(switch):
             os.environ["MJX_LINEAR_GRAM"] = switch
+            check(lib.mjx_bind_batch(ctx, ptr(obs), ptr(act), ptr(adv), rows, rows))       # (DAPG leaves the on-policy prefix bound)
             check(lib.mjx_bind_policy(ctx, ptr(th), ptr(tho), None, None, 1))
             route = ctypes.c_int32(-1)
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             torch.cuda.synchronize()
             e0.record()
-            check(lib.mjx_npg_update_linear(ctx, 10, 1e-4, 1e-10, 0.05, float("nan"), -3.0, ptr(g), ptr(x), ptr(new), ptr(res), st, ctypes.byref(route)))
+            if mode == "trpo":
+                check(lib.mjx_trpo_update_linear(ctx, 10, 1e-4, 1e-10, 2 * KL_DIST, KL_DIST, 100, -3.0, *out4, ctypes.byref(route)))
+                if route.value == 0:
+                    check(lib.mjx_trpo_update(ctx, 10, 1e-4, 1e-10, 2 * KL_DIST, KL_DIST, 3, 1, -3.0, *out4))
+            elif mode == "dapg":
+                check(lib.mjx_dapg_update_linear(ctx, 10, 1e-4, 1e-10, 2 * KL_DIST, -3.0, N, N, ptr(adv_on), *out4, ctypes.byref(route)))
+            else:
+                check(lib.mjx_npg_update_linear(ctx, 10, 1e-4, 1e-10, 0.05, float("nan"), -3.0, *out4, ctypes.byref(route)))
             e1.record()
             e1.synchronize()
             assert route.value == int(switch), route.value
@@ -77,9 +93,9 @@ def child(passes):
 
 
 def main():
-    passes = arg("--passes", 9)
-    out = {"passes": passes, "warmup": WARMUP}
-    p = subprocess.run(["timeout", "-k", "10", "240", sys.executable, os.path.abspath(__file__), "--child", "--passes", str(passes)],
+    passes, mode = arg("--passes", 9), arg("--mode", "npg")
+    out = {"passes": passes, "warmup": WARMUP, "mode": mode}
+    p = subprocess.run(["timeout", "-k", "10", "240", sys.executable, os.path.abspath(__file__), "--child", "--passes", str(passes), "--mode", mode],
                        capture_output=True, text=True, cwd=ROOT)
     line = [l for l in p.stdout.splitlines() if l.startswith("CHILD ")]
     if p.returncode != 0 or not line:
@@ -100,6 +116,6 @@ def main():
 
 if __name__ == "__main__":
     if "--child" in sys.argv:
-        child(arg("--passes", 9))
+        child(arg("--passes", 9), arg("--mode", "npg"))
     else:
         main()
