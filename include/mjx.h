@@ -310,6 +310,25 @@ int mjx_dapg_update_linear(mjx_ctx* ctx, int iters, float damping, double tol, d
                            int64_t N_on_global, const float* adv_on, float* grad_out, float* x_out, float* theta_out, double* results,
                            void* stream, int32_t* route_out);
 
+/* ---- the wide Gram route for LinearPolicy, 64 <= n <= 127 (csrc/linear_policy_wide.h) ---------------------------
+ * The same update at three or four feature blocks: in pass 1 a workgroup of four waves shares the distinct Gram blocks over
+ * rounds of 128 rows, the solve keeps G in the fp64 moment block in device memory.  Opt-in through entries of its own:
+ * mjx_linear_route and the entries above keep their answers for every shape.
+ * out4 as for mjx_linear_route (the LDS bytes on route 2: pass 1's, which stages one [W | b] image); route 2 = the wide route (n_hidden == 0, 64 <= n <= 127, m <= 32; NP = 96 for n <= 95, else 128);
+ * every other shape, and MJX_LINEAR_GRAM_WIDE=0 (read per call), gives what mjx_linear_route gives; MJX_LINEAR_GRAM=0 route 0. */
+int mjx_linear_route_wide(int n, int m, const int* hidden, int n_hidden, int32_t* out4);
+/* Pass 1 alone (needs old_is_new and a route-2 shape): block_out in mjx_linear_moments' layout with the wide NP, same summation rules. */
+int mjx_linear_moments_wide(mjx_ctx* ctx, double* block_out, void* stream);
+/* mjx_npg_update_linear / mjx_trpo_update_linear with the wide route in front: the same arguments, results and state on return,
+ * *route_out (may be NULL) = 2.  Where the wide route does not serve the context (shape, a switch, the transport) the call IS
+ * the entry above, *route_out = 1 or 0 (TRPO, route 0: nothing is enqueued). */
+int mjx_npg_update_linear_wide(mjx_ctx* ctx, int iters, float damping, double tol, double step_size, double const_alpha,
+                               float min_log_std, float* grad_out, float* x_out, float* theta_out, double* results, void* stream,
+                               int32_t* route_out);
+int mjx_trpo_update_linear_wide(mjx_ctx* ctx, int iters, float damping, double tol, double step_size, double kl_dist, int max_trials,
+                                float min_log_std, float* grad_out, float* x_out, float* theta_out, double* results, void* stream,
+                                int32_t* route_out);
+
 /* theta_out = theta + alpha * x, then log_std = max(log_std, min_log_std)
  * (npg_cg.py:137-139 + gaussian_mlp.py:73-75). */
 int mjx_apply_step(mjx_ctx* ctx, const float* theta, const float* x, float alpha,

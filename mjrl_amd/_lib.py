@@ -69,6 +69,13 @@ PROTOTYPES = {
     "mjx_linear_moments_segments": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
     "mjx_dapg_update_linear": (c_int, [c_void_p, c_int, c_float, c_double, c_double, c_float, c_int64, c_int64, c_void_p, c_void_p, c_void_p,
                                        c_void_p, c_void_p, c_void_p, ctypes.POINTER(ctypes.c_int32)]),
+    # (the wide Gram route, 64 <= n <= 127: route 2 of csrc/linear_policy_wide.h, else the entries above)
+    "mjx_linear_route_wide": (c_int, [c_int, c_int, ctypes.POINTER(c_int), c_int, ctypes.POINTER(ctypes.c_int32)]),
+    "mjx_linear_moments_wide": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "mjx_npg_update_linear_wide": (c_int, [c_void_p, c_int, c_float, c_double, c_double, c_double, c_float, c_void_p, c_void_p, c_void_p,
+                                           c_void_p, c_void_p, ctypes.POINTER(ctypes.c_int32)]),
+    "mjx_trpo_update_linear_wide": (c_int, [c_void_p, c_int, c_float, c_double, c_double, c_double, c_int, c_float, c_void_p, c_void_p,
+                                            c_void_p, c_void_p, c_void_p, ctypes.POINTER(ctypes.c_int32)]),
     "mjx_apply_step": (c_int, [c_void_p, c_void_p, c_void_p, c_float, c_float, c_void_p, c_void_p]),
     "mjx_apply_npg_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_float, c_void_p, c_void_p, c_void_p]),
     "mjx_time_index": (c_int, [c_void_p, c_int64, c_void_p, c_void_p]),

@@ -11,7 +11,7 @@ import time as timer
 import numpy as np
 
 from ..utils.logger import DataLog
-from .npg_cg import NPG
+from .npg_cg import NPG, _gram_choice
 
 
 class DAPG(NPG):
@@ -19,7 +19,10 @@ class DAPG(NPG):
                  FIM_invert_args={'iters': 10, 'damping': 1e-4}, hvp_sample_frac=1.0, seed=123, save_logs=False,
                  kl_dist=None, lam_0=1.0, lam_1=0.95, **kwargs):
         """Arguments as in the reference (dapg.py:26-52).  gram=True (through **kwargs, default False): a LinearPolicy's one-call
-        update goes to mjx_dapg_update_linear (csrc/linear_policy.h); last_update["route"] names what ran."""
+        update goes to mjx_dapg_update_linear (csrc/linear_policy.h); last_update["route"] names what ran.  The wide route
+        (gram='wide', csrc/linear_policy_wide.h) serves NPG and TRPO only: ValueError."""
+        if _gram_choice(kwargs.get('gram', False)) == 'wide':
+            raise ValueError("DAPG has no wide Gram route: gram='wide' serves NPG and TRPO")
         self.gram = bool(kwargs.get('gram', False))
         self.env = env
         self.policy = policy

@@ -19,13 +19,19 @@ from ..utils.logger import DataLog
 from .batch_reinforce import BatchREINFORCE
 
 
+def _gram_choice(gram):
+    """the gram keyword of NPG / TRPO / DAPG: 'wide', or its truth value"""
+    return 'wide' if isinstance(gram, str) and gram == 'wide' else bool(gram)
+
+
 class NPG(BatchREINFORCE):
     def __init__(self, env, policy, baseline, normalized_step_size=0.01, const_learn_rate=None,
                  FIM_invert_args={'iters': 10, 'damping': 1e-4}, hvp_sample_frac=1.0, seed=123, save_logs=False,
                  kl_dist=None, input_normalization=None, **kwargs):
         """Arguments as in the reference (npg_cg.py:24-60), the signature too.  gram=True (through **kwargs, default False): a
         LinearPolicy's one-call update goes to mjx_npg_update_linear (one pass for the second moments, the CG on the closed-form Fisher matrix; csrc/linear_policy.h);
-        last_update["route"] names what ran."""
+        last_update["route"] names what ran.  gram='wide': mjx_npg_update_linear_wide, which puts the wide route for 64 to 127
+        observations (route 2, csrc/linear_policy_wide.h) in front of that."""
         self.env = env
         self.policy = policy
         self.baseline = baseline
@@ -38,7 +44,7 @@ class NPG(BatchREINFORCE):
         self.running_score = None
         if save_logs:
             self.logger = DataLog()
-        self.gram = bool(kwargs.get('gram', False))
+        self.gram = _gram_choice(kwargs.get('gram', False))
         self.input_normalization = input_normalization
         if self.input_normalization is not None and not (0 < self.input_normalization <= 1):
             self.input_normalization = None
@@ -137,7 +143,7 @@ class NPG(BatchREINFORCE):
         iters, damping = self.FIM_invert_args['iters'], self.FIM_invert_args['damping']
         route = None
         if not subsampled and eng.old_is_new:
-            gram = dict(gram=True) if getattr(self, 'gram', False) else {}      # (the default call stays as it was)
+            gram = dict(gram=self.gram) if getattr(self, 'gram', False) else {}      # (the default call stays as it was)
             # The whole update in ONE call into libmjx (mjx_npg_update): K1, CG, step length formed on the device from g.x,
             # step, K3 -- rank sums included -- and one read-back.  (t_gLL / t_FIM cannot be told apart any more: the
             # gradient time is logged as 0, the solve time is the whole call.)

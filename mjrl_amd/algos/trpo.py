@@ -9,7 +9,7 @@ import time as timer
 import numpy as np
 
 from ..utils.logger import DataLog
-from .npg_cg import NPG
+from .npg_cg import NPG, _gram_choice
 
 
 class TRPO(NPG):
@@ -17,8 +17,9 @@ class TRPO(NPG):
                  hvp_sample_frac=1.0, seed=123, save_logs=False, normalized_step_size=0.01, **kwargs):
         """Arguments as in the reference (trpo.py:25-54).  gram=True (through **kwargs, default False): a LinearPolicy's one-call
         update goes to mjx_trpo_update_linear (the line search decided on the closed-form KL; csrc/linear_policy.h);
-        last_update["route"] names what ran."""
-        self.gram = bool(kwargs.get('gram', False))
+        last_update["route"] names what ran.  gram='wide': mjx_trpo_update_linear_wide (route 2 for 64 to 127 observations,
+        csrc/linear_policy_wide.h)."""
+        self.gram = _gram_choice(kwargs.get('gram', False))
         self.env = env
         self.policy = policy
         self.baseline = baseline
@@ -47,7 +48,7 @@ class TRPO(NPG):
             # (torch.distributed fallback: the loop below.)
             t0 = timer.time()
             iters, damping = self.FIM_invert_args['iters'], self.FIM_invert_args['damping']
-            gram = dict(gram=True) if getattr(self, 'gram', False) else {}      # (the default call stays as it was)
+            gram = dict(gram=self.gram) if getattr(self, 'gram', False) else {}      # (the default call stays as it was)
             res = eng.trpo_update(iters, damping, 2.0 * self.kl_dist, self.kl_dist, self.policy.min_log_std, **gram)
             if res is not None:
                 late = eng.deferred()

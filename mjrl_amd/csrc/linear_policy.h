@@ -67,6 +67,8 @@ constexpr int LIN_SOLVE_NT = 1024;
 struct LinLayout {
   int NP, S, NB;
   __host__ __device__ constexpr explicit LinLayout(int n = 1) : NP(n + 1 <= 32 ? 32 : 64), S(NP + 4), NB(NP / 32) {}
+  // the wide route (linear_policy_wide.h, 64 <= n <= 127): three or four feature blocks, everything below by the same arithmetic
+  static __host__ __device__ constexpr LinLayout wide(int n) { LinLayout L; L.NP = n + 1 <= 96 ? 96 : 128; L.S = L.NP + 4; L.NB = L.NP / 32; return L; }
   __host__ __device__ constexpr int img() const { return 32 * S; }
   __host__ __device__ constexpr int off_vec() const { return 2 * img(); }
   __host__ __device__ constexpr int off_z() const { return off_vec() + 2 * NP + 5 * 32; }
@@ -106,11 +108,12 @@ __device__ __forceinline__ float lin_sum32(float v) {        // every lane: the 
   return __uint_as_float(s[0]) + __uint_as_float(s[1]);
 }
 
-// all 256 threads, before the barrier: the images and the per-column / per-action vectors
-template <bool EVAL>
+// all 256 threads, before the barrier: the images and the per-column / per-action vectors (IM: images in front of the vectors;
+// the wide route's pass 1 keeps one)
+template <bool EVAL, int IM = 2>
 __device__ __forceinline__ void lin_stage_policy(float* lds, const LinLayout L, const LinArgs& a, int tid) {
   const int lane = tid & 63, n = a.n, m = a.m, oB = m * n, oS = oB + m;
-  float* w0 = lds; float* w1 = lds + L.img(); float* vec = lds + L.off_vec();
+  float* w0 = lds; float* w1 = lds + L.img(); float* vec = lds + IM * L.img();
   for (int u = tid >> 6; u < 32; u += LIN_WAVES)
     for (int c = lane; c < L.S; c += 64) {
       const int i = c < n ? u * n + c : oB + u;
@@ -480,11 +483,12 @@ __global__ __launch_bounds__(LIN_SOLVE_NT) void k_lin_solve(const LinSolveArgs a
 }
 
 // ---------------------------------------------------------------------------- the closing pass
-template <int NB>
+// (Tile, WIDE: the wide route, linear_policy_wide.h, runs this kernel at NB = 3 / 4 on LinLayout::wide with its row-wise
+// LinTileW, whose lin_load_tile / lin_write_tile overloads are found at instantiation)
+template <int NB, class Tile = LinTile<16 * NB>, bool WIDE = false>
 __global__ __launch_bounds__(64 * LIN_WAVES) void k_lin_eval(const LinArgs a) {
   extern __shared__ float lin_lds[];
-  constexpr int LE = 16 * NB;
-  const LinLayout L(a.n);
+  const LinLayout L = WIDE ? LinLayout::wide(a.n) : LinLayout(a.n);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, j = lane & 31, hi = lane >> 5;
   lin_stage_policy<true>(lin_lds, L, a, tid);
   float* Z = lin_lds + L.off_z() + wave * L.img();
@@ -504,7 +508,7 @@ __global__ __launch_bounds__(64 * LIN_WAVES) void k_lin_eval(const LinArgs a) {
   const int64_t tile1 = tile0 + a.chain_tiles < tiles ? tile0 + a.chain_tiles : tiles;
 
   double ssurr = 0.0, skl = 0.0;
-  LinTile<LE> t;
+  Tile t;
   lin_load_tile(t, a, tile0 * 32, lane);
   for (int64_t tile = tile0; tile < tile1; ++tile) {
     const int64_t row0 = tile * 32;

@@ -30,6 +30,7 @@
 #include "launch_state.h"
 #include "layerwise.h"
 #include "linear_policy.h"
+#include "linear_policy_wide.h"
 #include "mlp_fit.h"
 #include "mlp_fit_team.h"
 #include "path_reward.h"
@@ -912,6 +913,46 @@ int mjx_dapg_update_linear(mjx_ctx* c, int iters, float damping, double tol, dou
   if (rows_on < 0 || rows_on > c->N_local || N_on_global <= 0 || N_on_global > c->N_global) return fail(MJX_ERR_ARG, "bad on-policy row counts");
   if (route_out) *route_out = 1;
   return dapg_update_gram(c, iters, damping, tol, step_size, min_log_std, rows_on, N_on_global, adv_on, grad_out, x_out, theta_out, results, stream);
+}
+
+// ---- the wide Gram route, 64 <= n <= 127 (csrc/linear_policy_wide.h; host side: csrc/update_host.h update_gram_wide)
+int mjx_linear_route_wide(int n, int m, const int* hidden, int n_hidden, int32_t* out4) {
+  if (!out4 || n <= 0 || m <= 0 || n_hidden < 0 || (n_hidden > 0 && !hidden)) return fail(MJX_ERR_ARG, "bad arguments");
+  for (int i = 0; i < n_hidden; ++i) if (hidden[i] <= 0) return fail(MJX_ERR_ARG, "bad hidden size");
+  const LinRoute r = linear_route_wide(n, m, n_hidden, env_flag("MJX_LINEAR_GRAM", true), env_flag("MJX_LINEAR_GRAM_WIDE", true));
+  out4[0] = r.route; out4[1] = r.NP; out4[2] = (int32_t)r.lds; out4[3] = r.chain_rows;
+  return MJX_OK;
+}
+
+int mjx_linear_moments_wide(mjx_ctx* c, double* block_out, void* stream) {
+  if (int rc = check_bound(c, true)) return rc;
+  if (!block_out) return fail(MJX_ERR_ARG, "null output");
+  if (!c->old_is_new) return fail(MJX_ERR_STATE, "mjx_linear_moments_wide needs theta_new == theta_old (mjx_bind_policy with old_is_new)");
+  if (linear_route_wide(c->n, c->m, (int)c->hidden.size(), true, true).route != 2)
+    return fail(MJX_ERR_UNSUPPORTED, "not a shape of the wide Gram route (no hidden layer, 64 <= n <= 127, m <= 32)");
+  HIPCHK(hipSetDevice(c->device));
+  LinWidePlan w;
+  if (int rc = lin_plan_wide(c, stream, &w)) return rc;
+  return lin_moments_wide(c, w, block_out, stream);
+}
+
+int mjx_npg_update_linear_wide(mjx_ctx* c, int iters, float damping, double tol, double step_size, double const_alpha, float min_log_std,
+                               float* grad_out, float* x_out, float* theta_out, double* results, void* stream, int32_t* route_out) {
+  if (!c || !lin_serves_wide(c))                    // (the call IS mjx_npg_update_linear)
+    return mjx_npg_update_linear(c, iters, damping, tol, step_size, const_alpha, min_log_std, grad_out, x_out, theta_out, results, stream, route_out);
+  if (int rc = update_prologue(c, "mjx_npg_update_linear_wide", grad_out && x_out && theta_out && results && iters >= 0, true, theta_out)) return rc;
+  if (route_out) *route_out = 2;
+  return update_gram_wide(c, iters, damping, tol, step_size, const_alpha, std::nan(""), 0, min_log_std, grad_out, x_out, theta_out, results, stream);
+}
+
+int mjx_trpo_update_linear_wide(mjx_ctx* c, int iters, float damping, double tol, double step_size, double kl_dist, int max_trials,
+                                float min_log_std, float* grad_out, float* x_out, float* theta_out, double* results, void* stream,
+                                int32_t* route_out) {
+  if (!c || !lin_serves_wide(c) || kl_dist != kl_dist)       // (the call IS mjx_trpo_update_linear)
+    return mjx_trpo_update_linear(c, iters, damping, tol, step_size, kl_dist, max_trials, min_log_std, grad_out, x_out, theta_out, results, stream, route_out);
+  if (int rc = update_prologue(c, "mjx_trpo_update_linear_wide", grad_out && x_out && theta_out && results && iters >= 0 && max_trials >= 1, true, theta_out)) return rc;
+  if (route_out) *route_out = 2;
+  return update_gram_wide(c, iters, damping, tol, step_size, std::nan(""), kl_dist, max_trials, min_log_std, grad_out, x_out, theta_out, results, stream);
 }
 
 int mjx_apply_step(mjx_ctx* c, const float* theta, const float* x, float alpha, float min_log_std, float* theta_out, void* stream) {

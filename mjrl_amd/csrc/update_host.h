@@ -670,6 +670,99 @@ int dapg_update_gram(mjx_ctx* c, int iters, float damping, double tol, double st
   return lin_solve_and_close<LIN_SOLVE_DAPG>(c, p, s, stream);
 }
 
+// ---------------------------------------------------------------------------- the wide Gram route (linear_policy_wide.h, 64 <= n <= 127)
+// p: the plan of the closing pass (a chain per wave, lin_split) on LinLayout::wide; pass 1 has its own split into workgroup
+// chains of chain_rounds rounds of 128 rows: a workgroup per CU before the chains grow to their 8 rounds.  One scratch block:
+// [moment block | closing pass's doubles | pass 1's LIN_DS records, 4 per chain | slabs].
+struct LinWidePlan { LinPlan p; int chain_rounds; int64_t wchains; double* ds_m; };
+int lin_plan_wide(mjx_ctx* c, void* stream, LinWidePlan* out) {
+  LinWidePlan w{LinPlan{LinLayout::wide(c->n), 1, 0, 0, nullptr, nullptr, nullptr}, 1, 0, nullptr};
+  const LinSplit s = lin_split(c->N_local);
+  w.p.chain_tiles = s.chain_tiles; w.p.chains = s.chains;
+  w.p.count = w.p.L.block_count(c->m);
+  const int64_t rounds = (c->N_local + 127) / 128, cr = (rounds + cu_count() - 1) / cu_count();
+  w.chain_rounds = (int)(cr < 1 ? 1 : cr > LINW_CHAIN_ROUNDS ? LINW_CHAIN_ROUNDS : cr);
+  w.wchains = (rounds + w.chain_rounds - 1) / w.chain_rounds;
+  const size_t nd = (size_t)w.p.count + (size_t)s.chains * 4 + (size_t)w.wchains * LIN_WAVES * LIN_DS;
+  char* base = nullptr;
+  if (int rc = dev_scratch(SITE_LINEAR_GRAM, stream, nd * sizeof(double) + (size_t)w.wchains * linw_slab_floats(w.p.L.NB) * sizeof(float), &base)) return rc;
+  w.p.block = (double*)base; w.p.ds = w.p.block + w.p.count; w.ds_m = w.p.ds + (size_t)s.chains * 4;
+  w.p.slab = (float*)(w.ds_m + (size_t)w.wchains * LIN_WAVES * LIN_DS);
+  *out = w;
+  return MJX_OK;
+}
+
+template <class K3, class K4>
+int lin_launch_wide(K3 k3, K4 k4, const LinLayout L, size_t lds, unsigned grid, const LinArgs& a, hipStream_t st) {
+  if (int rc = lds_limit(L.NB == 3 ? (const void*)k3 : (const void*)k4, lds)) return rc;
+  if (L.NB == 3) hipLaunchKernelGGL(k3, dim3(grid), dim3(64 * LIN_WAVES), lds, st, a);
+  else hipLaunchKernelGGL(k4, dim3(grid), dim3(64 * LIN_WAVES), lds, st, a);
+  HIPCHK(hipGetLastError());
+  return MJX_OK;
+}
+
+// pass 1 of the wide route: the moment block (not divided by N) to block_out; a rank without rows writes zeros
+int lin_moments_wide(mjx_ctx* c, const LinWidePlan& w, double* block_out, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  const LinPlan& p = w.p;
+  if (c->N_local == 0) {
+    hipLaunchKernelGGL(k_lin_zero, dim3((unsigned)((p.count + 255) / 256)), dim3(256), 0, st, block_out, p.count);
+    HIPCHK(hipGetLastError());
+    return MJX_OK;
+  }
+  LinArgs a = lin_args(c, p);
+  a.chain_tiles = w.chain_rounds; a.chains = w.wchains; a.ds = w.ds_m;
+  if (int rc = lin_launch_wide(k_lin_moments_wide<3>, k_lin_moments_wide<4>, p.L, linw_moments_bytes(p.L), (unsigned)w.wchains, a, st)) return rc;
+  hipLaunchKernelGGL(k_lin_reduce_wide, dim3((unsigned)((p.count + 15) / 16)), dim3(256), 0, st, (const float*)p.slab, (const double*)w.ds_m,
+                     w.wchains, c->n, c->m, block_out);
+  HIPCHK(hipGetLastError());
+  return MJX_OK;
+}
+
+// lin_serves for the wide route: its shape and both switches (read per call), and a transport that can carry its moment block
+bool lin_serves_wide(const mjx_ctx* c) {
+  if (linear_route_wide(c->n, c->m, (int)c->hidden.size(), env_flag("MJX_LINEAR_GRAM", true), env_flag("MJX_LINEAR_GRAM_WIDE", true)).route != 2) return false;
+  return c->tp.kind() != TP_PEER || (size_t)LinLayout::wide(c->n).block_count(c->m) * sizeof(double) <= c->tp.layout().slot_bytes();
+}
+
+// lin_solve_and_close on the wide kernels
+template <int MODE>
+int lin_solve_and_close_wide(mjx_ctx* c, const LinPlan& p, const LinSolveArgs& s, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  const size_t bytes = linw_solve_bytes(p.L, c->m);
+  if (int rc = lds_limit((const void*)k_lin_solve_wide<MODE>, bytes)) return rc;
+  hipLaunchKernelGGL(k_lin_solve_wide<MODE>, dim3(1), dim3(LIN_SOLVE_NT), bytes, st, s);
+  HIPCHK(hipGetLastError());
+  if (int rc = bind_policy_impl(c, s.theta_out, c->theta_old, c->tr_new, c->tr_old, 0, true)) return rc;
+  c->lw_old_ok = false;
+  if (c->N_local == 0) {
+    hipLaunchKernelGGL(k_lin_zero, dim3(1), dim3(256), 0, st, s.results, (int64_t)4);
+    HIPCHK(hipGetLastError());
+  } else {
+    if (int rc = lin_launch_wide(k_lin_eval<3, LinTileW, true>, k_lin_eval<4, LinTileW, true>, p.L, p.L.bytes(), lin_grid(p), lin_args(c, p), st)) return rc;
+    hipLaunchKernelGGL(k_lin_eval_reduce, dim3(1), dim3(256), 0, st, (const double*)p.ds, p.chains, c->theta_new + c->oS, c->theta_old + c->oS, c->m,
+                       (double)c->N_local, s.results);
+    HIPCHK(hipGetLastError());
+  }
+  if (c->tp.attached()) if (int rc = c->tp.allreduce(s.results, 4, 1, stream)) return rc;
+  return MJX_OK;
+}
+
+// NPG (kl_dist NaN) or TRPO on the wide route: npg_update_gram / trpo_update_gram with the wide kernels
+int update_gram_wide(mjx_ctx* c, int iters, float damping, double tol, double step_size, double const_alpha, double kl_dist, int max_trials,
+                     float min_log_std, float* grad_out, float* x_out, float* theta_out, double* results, void* stream) {
+  HIPCHK(hipSetDevice(c->device));
+  LinWidePlan w;
+  if (int rc = lin_plan_wide(c, stream, &w)) return rc;
+  if (int rc = lin_moments_wide(c, w, w.p.block, stream)) return rc;
+  if (c->tp.attached()) if (int rc = c->tp.allreduce(w.p.block, w.p.count, 1, stream)) return rc;
+  LinSolveArgs s{w.p.block, c->n, c->m, iters, 1.0 / (double)c->N_global, (double)damping, tol, step_size, const_alpha, min_log_std,
+                 c->theta_old, c->tr_new ? c->tr_new : c->ident_tr, grad_out, x_out, theta_out, results};
+  if (kl_dist != kl_dist) return lin_solve_and_close_wide<LIN_SOLVE_NPG>(c, w.p, s, stream);
+  s.kl_dist = kl_dist; s.N_global = (double)c->N_global; s.max_trials = max_trials;
+  return lin_solve_and_close_wide<LIN_SOLVE_TRPO>(c, w.p, s, stream);
+}
+
 }  // namespace
 
 #endif  // __HIPCC__

@@ -217,6 +217,22 @@ class HipBackend:
                                               ctypes.byref(route)))
         return int(route.value)
 
+    def npg_update_linear_wide(self, iters, damping, tol, step_size, const_alpha, min_log_std, grad_out, x_out, theta_out, results):
+        """mjx_npg_update_linear_wide -> the route that ran (2: the wide Gram route of csrc/linear_policy_wide.h, else as above)"""
+        route = ctypes.c_int32(-1)
+        check(self.lib.mjx_npg_update_linear_wide(self.ctx, int(iters), float(damping), float(tol), float(step_size),
+                                                  float("nan") if const_alpha is None else float(const_alpha), float(min_log_std),
+                                                  ptr(grad_out), ptr(x_out), ptr(theta_out), ptr(results), self.stream(), ctypes.byref(route)))
+        return int(route.value)
+
+    def trpo_update_linear_wide(self, iters, damping, tol, step_size, kl_dist, max_trials, min_log_std, grad_out, x_out, theta_out, results):
+        """mjx_trpo_update_linear_wide -> the route that ran (2 or 1: the whole update is enqueued; 0: nothing is)"""
+        route = ctypes.c_int32(-1)
+        check(self.lib.mjx_trpo_update_linear_wide(self.ctx, int(iters), float(damping), float(tol), float(step_size), float(kl_dist),
+                                                   int(max_trials), float(min_log_std), ptr(grad_out), ptr(x_out), ptr(theta_out), ptr(results),
+                                                   self.stream(), ctypes.byref(route)))
+        return int(route.value)
+
     def dapg_update_linear(self, iters, damping, tol, step_size, min_log_std, rows_on, N_on_global, adv_on, grad_out, x_out, theta_out, results):
         """mjx_dapg_update_linear -> the route that ran (1: the Gram route, 0: mjx_dapg_update itself)"""
         route = ctypes.c_int32(-1)
@@ -590,7 +606,9 @@ class UpdateEngine:
             args = (iters, damping, tol, step_size, const_alpha, min_log_std, self.grad, self.x, self.theta_new, self.results)
             if gram and not self.hidden and hasattr(self.backend, "npg_update_linear"):
                 # LinearPolicy, opt-in: one pass for the second moments, the CG on the closed-form Fisher matrix, one closing pass
-                self.last_route = self.backend.npg_update_linear(*args)
+                # (gram == 'wide': the wide route for 64 to 127 observations in front of it, route 2)
+                wide = isinstance(gram, str) and gram == 'wide' and hasattr(self.backend, "npg_update_linear_wide")
+                self.last_route = (self.backend.npg_update_linear_wide if wide else self.backend.npg_update_linear)(*args)
             else:
                 self.backend.npg_update(*args)
             self.old_is_new = False
@@ -659,9 +677,10 @@ class UpdateEngine:
             return None
         if gram and not self.hidden and hasattr(self.backend, "trpo_update_linear"):
             self._host_results = None
-            self.last_route = self.backend.trpo_update_linear(iters, damping, tol, step_size, kl_dist, max_trials, min_log_std, self.grad, self.x,
-                                                              self.theta_new, self.results)
-            if self.last_route == 1:
+            wide = isinstance(gram, str) and gram == 'wide' and hasattr(self.backend, "trpo_update_linear_wide")
+            entry = self.backend.trpo_update_linear_wide if wide else self.backend.trpo_update_linear
+            self.last_route = entry(iters, damping, tol, step_size, kl_dist, max_trials, min_log_std, self.grad, self.x, self.theta_new, self.results)
+            if self.last_route in (1, 2):
                 self.old_is_new = False
                 s = self._host_results = self._checked(self.results.cpu().numpy())
                 trials, accepted = int(s[11]), s[10] != 0.0

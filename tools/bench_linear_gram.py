@@ -9,7 +9,10 @@ differ by) and `wins` (route 1 beats route 0 by more than the largest spread).
 --mode trpo: one TRPO update (kl_dist 0.025) -- route 1 is ONE mjx_trpo_update_linear call (the line search inside the solve), route 0
 what a caller runs when that entry reports route 0: mjx_trpo_update with its first batch of 3 trials.  --mode dapg: one DAPG update
 with 5 000 demonstration rows behind the on-policy rows, mjx_dapg_update_linear on either side of the switch.
-    python tools/bench_linear_gram.py [--mode npg|trpo|dapg] [--passes 9] [--out FILE]"""
+--wide (npg, trpo): the wide route for 64 to 127 observations (route 2 of mjx_npg_update_linear_wide / mjx_trpo_update_linear_wide,
+csrc/linear_policy_wide.h) against route 0, MJX_LINEAR_GRAM_WIDE alternating 1, 0, at
+    (111, 8) x 10 000 rows    (111, 8) x 1M rows    (127, 32) x 1M rows
+    python tools/bench_linear_gram.py [--mode npg|trpo|dapg] [--wide] [--passes 9] [--out FILE]"""
 import ctypes
 import json
 import os
@@ -20,6 +23,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 SHAPES = [(6, 2, 10000), (17, 6, 1000000), (63, 17, 1000000)]      # (n, m, rows)
+WIDE_SHAPES = [(111, 8, 10000), (111, 8, 1000000), (127, 32, 1000000)]
 WARMUP = 3
 DEMO_ROWS, KL_DIST = 5000, 0.025
 
@@ -28,14 +32,17 @@ def arg(name, dflt):
     return type(dflt)(sys.argv[sys.argv.index(name) + 1]) if name in sys.argv else dflt
 
 
-def child(passes, mode):
+def child(passes, mode, wide):
     import numpy as np
     import torch
     from mjrl_amd._lib import check, load, ptr
     dev = torch.device("cuda", 0)
     lib = load()
     out = {}
-    for n, m, N in SHAPES:
+    env, on = ("MJX_LINEAR_GRAM_WIDE", 2) if wide else ("MJX_LINEAR_GRAM", 1)
+    npg_entry = lib.mjx_npg_update_linear_wide if wide else lib.mjx_npg_update_linear
+    trpo_entry = lib.mjx_trpo_update_linear_wide if wide else lib.mjx_trpo_update_linear
+    for n, m, N in (WIDE_SHAPES if wide else SHAPES):
         rng = np.random.RandomState(3)
         d = m * n + 2 * m
         th = torch.as_tensor(np.concatenate([0.3 * rng.randn(m * n) / np.sqrt(n), 0.1 * rng.randn(m), np.full(m, -0.5)]).astype(np.float32)).to(dev)
@@ -54,7 +61,7 @@ def child(passes, mode):
         out4 = (ptr(g), ptr(x), ptr(new), ptr(res), st)
 
         def update(switch):
-            os.environ["MJX_LINEAR_GRAM"] = switch
+            os.environ[env] = switch
             check(lib.mjx_bind_batch(ctx, ptr(obs), ptr(act), ptr(adv), rows, rows))       # (DAPG leaves the on-policy prefix bound)
             check(lib.mjx_bind_policy(ctx, ptr(th), ptr(tho), None, None, 1))
             route = ctypes.c_int32(-1)
@@ -62,16 +69,16 @@ def child(passes, mode):
             torch.cuda.synchronize()
             e0.record()
             if mode == "trpo":
-                check(lib.mjx_trpo_update_linear(ctx, 10, 1e-4, 1e-10, 2 * KL_DIST, KL_DIST, 100, -3.0, *out4, ctypes.byref(route)))
+                check(trpo_entry(ctx, 10, 1e-4, 1e-10, 2 * KL_DIST, KL_DIST, 100, -3.0, *out4, ctypes.byref(route)))
                 if route.value == 0:
                     check(lib.mjx_trpo_update(ctx, 10, 1e-4, 1e-10, 2 * KL_DIST, KL_DIST, 3, 1, -3.0, *out4))
             elif mode == "dapg":
                 check(lib.mjx_dapg_update_linear(ctx, 10, 1e-4, 1e-10, 2 * KL_DIST, -3.0, N, N, ptr(adv_on), *out4, ctypes.byref(route)))
             else:
-                check(lib.mjx_npg_update_linear(ctx, 10, 1e-4, 1e-10, 0.05, float("nan"), -3.0, *out4, ctypes.byref(route)))
+                check(npg_entry(ctx, 10, 1e-4, 1e-10, 0.05, float("nan"), -3.0, *out4, ctypes.byref(route)))
             e1.record()
             e1.synchronize()
-            assert route.value == int(switch), route.value
+            assert route.value == on * int(switch), route.value
             return round(e0.elapsed_time(e1) * 1e3, 1), new.clone()
 
         for _ in range(WARMUP):
@@ -93,9 +100,10 @@ def child(passes, mode):
 
 
 def main():
-    passes, mode = arg("--passes", 9), arg("--mode", "npg")
-    out = {"passes": passes, "warmup": WARMUP, "mode": mode}
-    p = subprocess.run(["timeout", "-k", "10", "240", sys.executable, os.path.abspath(__file__), "--child", "--passes", str(passes), "--mode", mode],
+    passes, mode, wide = arg("--passes", 9), arg("--mode", "npg"), "--wide" in sys.argv
+    assert not (wide and mode == "dapg"), "the wide route serves NPG and TRPO"
+    out = {"passes": passes, "warmup": WARMUP, "mode": mode, "wide": wide}
+    p = subprocess.run(["timeout", "-k", "10", "240", sys.executable, os.path.abspath(__file__), "--child", "--passes", str(passes), "--mode", mode] + (["--wide"] if wide else []),
                        capture_output=True, text=True, cwd=ROOT)
     line = [l for l in p.stdout.splitlines() if l.startswith("CHILD ")]
     if p.returncode != 0 or not line:
@@ -116,6 +124,6 @@ def main():
 
 if __name__ == "__main__":
     if "--child" in sys.argv:
-        child(arg("--passes", 9), arg("--mode", "npg"))
+        child(arg("--passes", 9), arg("--mode", "npg"), "--wide" in sys.argv)
     else:
         main()
